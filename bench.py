@@ -20,13 +20,17 @@ N > 1: one process per GPU, weights broadcast from rank 0 over RCCL once (time r
 each rank serves its own requests with no data-path collective -> "scaling": "weak".  Timing: barrier +
 synchronize on both sides, MAX over ranks; value = N * K * num_samples / t.
 
-Extra objects on the JSON line: `roofline` (dominant kernel of the UNet forward, algorithmic flops / HIP-event time
+A plain run sets up, warms up, times the K steps and prints the line; `roofline`, `cpu_baseline` and `parity` are null there.
+`--full` adds them after the timed steps (the `--no-*` options below drop single ones again):
+`roofline` (dominant kernel of the UNet forward, algorithmic flops / HIP-event time
 vs the 2.5 PFLOP/s dense fp16 MFMA peak), `cpu_baseline` (the whole `__call__` of BASELINE.json configs[0] on the fp32 CPU
 oracle, the Euler loop interrupted after 2 of 20 steps and only the loop extrapolated; rank 0 at N=1 only) and `parity`
 (`path: "__call__"`: the SAME call - prompt, negative prompt, noise, weights, interrupt point - through `pipe(...)` on the
 GPU: relative L2 of the latents, and the uint8 image bytes compared.  The bench FAILS when the latents differ by more than
 6e-3 (bounded 2-step sample; measured 1.7e-3) / 1.2e-2 (`--cpu-full`, all 20 steps: fp16 storage vs fp32 compounds through
 CFG 7.5; measured 2.1e-3) or the image by more than 8e-3 (measured 1.9e-3); until round 5 these gates were 3e-2 / 6e-2 / 5e-2).
+
+`--dump-outputs DIR` writes what the last timed step returned (rank 0) as float32 / float64 `.npy` files, see dump_outputs().
 """
 from __future__ import annotations
 
@@ -37,6 +41,7 @@ import os
 import sys
 import time
 
+T_START = time.perf_counter()
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
@@ -49,6 +54,10 @@ HBM_PEAK_GBS = 8000.0
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def log_phase(what):
+    log(f"bench.py: {what} at {time.perf_counter() - T_START:.1f} s")
 
 
 def build_pipeline(device, num_gpus, rank, seed=0, with_vae=True, agent=None, keep_oracle=False):
@@ -276,6 +285,37 @@ def vae_precision_note(pipe, ns, size, call_s, world):
                                      "value_lower_bound_if_fp32_decode": round(world * ns / (call_s + extra_s), 4)}}
 
 
+DUMP_WHOLE_BYTES = 48 << 20     # outputs up to this size (as float32) are written whole, and no dump is larger
+DUMP_SAMPLE = 1 << 22           # else: this many elements drawn with numpy's default_rng(0), + the first panel + per-panel means
+
+
+def dump_outputs(images, out_type, ddir):
+    """`--dump-outputs DIR`: what the last timed step handed its caller, for an output-by-output comparison of two builds.
+    pil: the uint8 RGB images as one (n, H, W, 3) array; pt: the (n, 3, H, W) [0,1] images; latent: the (n, 4, h, w) latents.
+    Written as float32 `<name>.npy` when it fits DUMP_WHOLE_BYTES; otherwise `<name>_sample.npy` (DUMP_SAMPLE elements of the
+    flattened array at indices drawn by numpy.random.default_rng(0), so they depend only on the output's size),
+    `<name>_first.npy` (panel 0 whole, when it fits the rest of DUMP_WHOLE_BYTES: up to 1024^2 at the default --size) and
+    `<name>_mean.npy` (float64 mean of every panel)."""
+    import numpy as np
+    if out_type == "pil":
+        name, arr = "images", np.stack([np.asarray(im) for im in images])
+    else:
+        name, arr = ("latents" if out_type == "latent" else "images"), images.float().cpu().numpy()
+    os.makedirs(ddir, exist_ok=True)
+    files = {}
+    if arr.size * 4 <= DUMP_WHOLE_BYTES:
+        files[name] = arr.astype(np.float32)
+    else:
+        idx = np.random.default_rng(0).integers(0, arr.size, DUMP_SAMPLE)
+        files[name + "_sample"] = arr.reshape(-1)[idx].astype(np.float32)
+        if (arr[0].size + DUMP_SAMPLE) * 4 + arr.shape[0] * 8 <= DUMP_WHOLE_BYTES:
+            files[name + "_first"] = arr[0].astype(np.float32)
+        files[name + "_mean"] = arr.reshape(arr.shape[0], -1).mean(axis=1, dtype=np.float64)
+    for k, v in files.items():
+        np.save(os.path.join(ddir, k + ".npy"), v)
+    log("bench.py: outputs written to", ddir, {k: list(v.shape) for k, v in files.items()})
+
+
 def profile_forward_ops(pipe, reps=3):
     """HIP-event time of every op of the UNet forward plan, on the stream the kernels are launched on; grouped by
     the gfx950 kernel they dispatch to.  Returns (per-kernel table, forward_ms)."""
@@ -362,8 +402,14 @@ def main():
                          "batch: 32 makes every projection of the level-2 transformers a whole number of 256-tile rounds "
                          "(round 3: 1.34 panels/s vs 1.29 at 16, profiles/r03_bench_ns32_*.json); DS_BENCH_NUM_SAMPLES overrides")
     ap.add_argument("--size", type=int, default=1024)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure `roofline` (per-kernel HIP-event times of the UNet forward), "
+                         "`cpu_baseline` and `parity` (BASELINE configs[0] on the fp32 CPU oracle and through pipe(...)); "
+                         "a plain run leaves them null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) to DIR/*.npy, float32 / float64 (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline / parity")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: no roofline")
     ap.add_argument("--no-vae", action="store_true", help="stop at the latents (the first timed region of round 1)")
     ap.add_argument("--output", choices=("pil", "pt"), default="pil",
                     help="pil: PIL images on the host like the reference's __call__ (default, the metric's region); "
@@ -371,11 +417,12 @@ def main():
     ap.add_argument("--refs", type=int, default=2, choices=(0, 1, 2, 3, 4),
                     help="character references in the request (BASELINE config 2: 1, config 5: 4)")
     ap.add_argument("--no-dialog", action="store_true", help="no dialog boxes (BASELINE config 2)")
-    ap.add_argument("--no-parity", action="store_true", help="skip the GPU-vs-oracle parity run on BASELINE configs[0]")
+    ap.add_argument("--no-parity", action="store_true",
+                    help="with --full: skip the GPU-vs-oracle parity run on BASELINE configs[0]")
     ap.add_argument("--cpu-full", action="store_true",
-                    help="cpu_baseline runs ALL 20 Euler steps of BASELINE configs[0] plus the fp32 VAE decode on the host "
-                         "cores (~6 min on the GPU box) instead of the bounded 2-step sample, and `parity` compares the "
-                         "20-step latents and the decoded image (SURVEY 8d: the whole call, not an extrapolation)")
+                    help="implies --full: cpu_baseline runs ALL 20 Euler steps of BASELINE configs[0] plus the fp32 VAE "
+                         "decode on the host cores (~6 min on the GPU box) instead of the bounded 2-step sample, and `parity` "
+                         "compares the 20-step latents and the decoded image (SURVEY 8d: the whole call, not an extrapolation)")
     ap.add_argument("--mllm", action="store_true",
                     help="BASELINE config 3: run the MLLM pre-pass (LLaMA-2-13B dims, 66 new tokens) inside the timed "
                          "region and feed its ip_image_embeds to the sampler (scripts/demo/gradio.py:85-129); "
@@ -385,6 +432,9 @@ def main():
                     help="control flow only (launcher, process group, barriers, max-over-ranks timing, the JSON line): the "
                          "step is a 10 ms sleep, no kernels, runs without a GPU - tests/test_distributed_gloo.py uses it")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    args.full = args.full or args.cpu_full
 
     # `python bench.py --gpus N` without a torchrun environment: start the N ranks ourselves (the plain form
     # used to die on the WORLD_SIZE assert).  Under torchrun (RANK / WORLD_SIZE exported) this is skipped.
@@ -404,12 +454,15 @@ def main():
         _build.build(verbose=False)
     if world > 1:
         dist.barrier()
+    log_phase("library ready")
 
+    do_roofline = args.full and not args.no_roofline
+    do_cpu_baseline = args.full and not args.no_cpu_baseline and rank == 0 and world == 1
     agent = mllm_in = None
     if args.mllm:
         agent, mllm_in = build_mllm_agent(device, seed=7 if rank == 0 else 70 + rank)
-    pipe, setup = build_pipeline(device, world, rank, with_vae=not args.no_vae, agent=agent,
-                                 keep_oracle=(rank == 0 and world == 1 and not args.no_cpu_baseline))
+    pipe, setup = build_pipeline(device, world, rank, with_vae=not args.no_vae, agent=agent, keep_oracle=do_cpu_baseline)
+    log_phase("weights ready")
     ns = args.num_samples
     out_type = "latent" if args.no_vae else args.output
     req = synthetic_request(device, args.size, seed=1234 + rank, output_type=out_type, refs=args.refs)
@@ -426,11 +479,15 @@ def main():
         out = pipe(num_samples=ns, **r)
         return out.images
 
-    for _ in range(args.warmup):
+    for i in range(args.warmup):
         one_step()
+        if i == 0:
+            torch.cuda.synchronize()
+            log_phase("first warmup step done")
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
+    log_phase("timed steps start")
     t0 = time.perf_counter()
     for _ in range(args.steps):
         lat = one_step()
@@ -453,10 +510,13 @@ def main():
             assert lat.shape == (ns, 3, args.size, args.size) and float(lat.min()) >= 0.0 and float(lat.max()) <= 1.0
     panels = world * args.steps * ns
     value = panels / dt
+    log_phase("timed steps done")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(lat, out_type, args.dump_outputs)
 
     roofline = None
     extra = {}
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and do_roofline:
         table, fwd_ms = profile_forward_ops(pipe)
         # gemm_pp_kernel has five instantiations since round 4 (template argument FUSE: 0 plain, 1 / 9 / 4 fused-LayerNorm
         # consumers with the plain / GEGLU / operand-swapped epilogue, 2 producer): the same main loop, separate symbols in a
@@ -504,7 +564,7 @@ def main():
         log(json.dumps(extra, indent=1))
 
     cpu_baseline = parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if do_cpu_baseline:
         cpu_baseline, parity = cpu_call_and_gpu_parity(pipe, req, cpu_full=args.cpu_full,
                                                          parity=not (args.no_parity or args.no_vae))
         if parity is not None:

@@ -321,6 +321,30 @@ def test_bench_mllm_request_path_contract():
     assert max(cfg.hidden_size, 2048) <= 8192
 
 
+def test_bench_dump_outputs_are_float_npy_within_64mb_and_fixed(tmp_path):
+    """`bench.py --dump-outputs DIR`: the last timed step's outputs as float32 / float64 .npy files, 64 MB at most; a small
+    output is written whole, a large one as a sample whose indices depend only on its size (two builds compare element for
+    element), its first panel and the mean of every panel."""
+    import numpy as np
+    from PIL import Image
+    import bench
+    rng = np.random.RandomState(0)
+    u8 = rng.randint(0, 256, (5, 1024, 1024, 3), dtype=np.uint8)
+    for out, kind, d in (([Image.fromarray(a) for a in u8], "pil", "pil"), (torch.from_numpy(u8[:2]).float() / 255, "pt", "pt"),
+                         (torch.randn(2, 4, 128, 128).half(), "latent", "lat"), (torch.rand(2, 3, 2048, 2048), "pt", "pt2048")):
+        bench.dump_outputs(out, kind, str(tmp_path / d))
+        files = {f: np.load(tmp_path / d / f) for f in os.listdir(tmp_path / d)}
+        assert all(f.endswith(".npy") and a.dtype in (np.float32, np.float64) for f, a in files.items())
+        assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert sorted(os.listdir(tmp_path / "pil")) == ["images_first.npy", "images_mean.npy", "images_sample.npy"]
+    idx = np.random.default_rng(0).integers(0, u8.size, bench.DUMP_SAMPLE)
+    assert np.array_equal(np.load(tmp_path / "pil" / "images_sample.npy"), u8.reshape(-1)[idx])
+    assert np.array_equal(np.load(tmp_path / "pil" / "images_first.npy"), u8[0])
+    assert np.allclose(np.load(tmp_path / "pil" / "images_mean.npy"), u8.reshape(5, -1).mean(1))
+    assert os.listdir(tmp_path / "pt") == ["images.npy"] and os.listdir(tmp_path / "lat") == ["latents.npy"]
+    assert sorted(os.listdir(tmp_path / "pt2048")) == ["images_mean.npy", "images_sample.npy"]     # a 2048^2 panel is 48 MB
+
+
 def test_one_block_per_cu_tile_rules_are_pure_host_logic(hip_lib):
     """Round 6: the planner's host queries for the tile shapes built for the reference's own call shape (one request, batch 1;
     reference scripts/demo/gradio_wo_mllm.py:45-62) answer without a GPU, are thread-local A/B switches, and pick exactly the

@@ -8,6 +8,10 @@ import torch
 import torch.multiprocessing as mp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# The ranks of these tests run on the host.  Where a GPU is visible, init_from_env() selects device LOCAL_RANK, which a
+# 1-GPU box does not have for ranks 1..7: its test hook DS_FORCE_DEVICE puts every rank on device 0 instead (no effect
+# without a GPU), and DS_DIST_BACKEND keeps bench.py's ranks on gloo, whose collectives need no device per rank.
+HOST_RANK_ENV = {"DS_FORCE_DEVICE": "0"}
 
 
 def _free_port():
@@ -21,7 +25,7 @@ def _free_port():
 def _worker(rank, world, port, q):
     sys.path.insert(0, ROOT)
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
-                      MASTER_PORT=str(port))
+                      MASTER_PORT=str(port), **HOST_RANK_ENV)
     import torch.distributed as dist
     from diffsensei_amd.distributed import PanelRequest, broadcast_tensors, init_from_env, run_sharded
     r, w, _ = init_from_env("gloo")
@@ -83,7 +87,7 @@ def test_shard_requests_balanced_and_deterministic():
 def _worker_batched(rank, world, port, q):
     sys.path.insert(0, ROOT)
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
-                      MASTER_PORT=str(port))
+                      MASTER_PORT=str(port), **HOST_RANK_ENV)
     import torch.distributed as dist
     from diffsensei_amd.distributed import PanelRequest, init_from_env, run_sharded_batched
     init_from_env("gloo")
@@ -130,7 +134,7 @@ def _mllm_worker(rank, world, port, q):
     N > 1 start-up broadcast must cover: rank 1 starts from different seeds and must end bit-identical to rank 0."""
     sys.path.insert(0, ROOT)
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
-                      MASTER_PORT=str(port))
+                      MASTER_PORT=str(port), **HOST_RANK_ENV)
     import torch.distributed as dist
     from diffsensei_amd.distributed import broadcast_tensors, init_from_env
     from diffsensei_amd.mllm import LlamaConfig, LlamaDecodeEngine, llama_param_shapes
@@ -173,7 +177,7 @@ def _pipeline_bcast_worker(rank, world, port, q):
     then perturbed on one rank makes `verify_replicas` raise on EVERY rank."""
     sys.path.insert(0, ROOT)
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
-                      MASTER_PORT=str(port))
+                      MASTER_PORT=str(port), **HOST_RANK_ENV)
     import torch.distributed as dist
     from diffsensei_amd.distributed import broadcast_pipeline, init_from_env, tensors_checksum, verify_replicas
     init_from_env("gloo")
@@ -319,7 +323,7 @@ def _loose_worker(rank, world, port, q):
     intact on rank 1 (RCCL / NCCL raise "Tensors must be contiguous" for the first one if it is sent as it is)."""
     sys.path.insert(0, ROOT)
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
-                      MASTER_PORT=str(port))
+                      MASTER_PORT=str(port), **HOST_RANK_ENV)
     import torch.distributed as dist
     from diffsensei_amd.distributed import broadcast_tensors, init_from_env
     init_from_env("gloo")
@@ -395,6 +399,7 @@ def _run_bench(args, env_extra=None, drop=("RANK", "WORLD_SIZE", "LOCAL_RANK", "
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in drop}
+    env.update(HOST_RANK_ENV, DS_DIST_BACKEND="gloo")
     env.update(env_extra or {})
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), *args], env=env, capture_output=True, text=True,
                        timeout=300)
@@ -426,7 +431,7 @@ def test_bench_under_torchrun_env_mismatch_is_an_error_not_a_hang():
 def _worker_c3_world8(rank, world, port, q):
     sys.path.insert(0, ROOT)
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
-                      MASTER_PORT=str(port))
+                      MASTER_PORT=str(port), **HOST_RANK_ENV)
     import torch.distributed as dist
     from diffsensei_amd.distributed import PanelRequest, init_from_env, run_sharded_batched
     init_from_env("gloo")

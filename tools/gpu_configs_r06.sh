@@ -7,7 +7,7 @@ out=gpurun_out; mkdir -p "$out"; export TMPDIR=/tmp
 python -c "import __graft_entry__ as g; g.build()" > "$out/r06_configs_build.log" 2>&1
 run() { # name, args...
   n=$1; shift
-  timeout 900 python bench.py "$@" --no-cpu-baseline --no-parity > "$out/r06_bench_$n.json" 2> "$out/r06_bench_$n.err"
+  timeout 900 python bench.py "$@" --full --no-cpu-baseline --no-parity > "$out/r06_bench_$n.json" 2> "$out/r06_bench_$n.err"
   echo "$n rc=$? $(python - "$out/r06_bench_$n.json" <<'PY'
 import json, sys
 try:

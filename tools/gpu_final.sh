@@ -1,5 +1,5 @@
 #!/usr/bin/env bash
-# End-of-round evidence run: build, GPU test suite, smoke, default bench (incl. cpu_baseline + roofline), and the
+# End-of-round evidence run: build, GPU test suite, smoke, bench --full (cpu_baseline + roofline + parity), and the
 # rocprofv3 kernel-trace summary of the same workload (graph replay off so every launch is traced).
 set -u
 out=gpurun_out
@@ -10,7 +10,7 @@ timeout 1400 python -m pytest tests -m gpu -x -q -p no:cacheprovider > "$out/fin
 echo "pytest rc=$? $(tail -1 $out/final_pytest_gpu.log)" | tee -a "$out/final_run.log"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" >> "$out/final_run.log" 2>&1
 echo "smoke rc=$?" | tee -a "$out/final_run.log"
-timeout 1500 python bench.py > "$out/final_bench_default.json" 2> "$out/final_bench_default.err"
+timeout 1500 python bench.py --full > "$out/final_bench_default.json" 2> "$out/final_bench_default.err"
 echo "bench default rc=$?" | tee -a "$out/final_run.log"
 tail -1 "$out/final_bench_default.json" | cut -c1-400
 cd /tmp
