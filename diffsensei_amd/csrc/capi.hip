@@ -196,7 +196,7 @@ int ds_gemm_f16_batched(const void* x, int64_t ldx, int64_t sx, const void* w, i
 static int conv3x3_impl(const void* x, const void* w, const void* bias, const void* rowbias, int64_t rowbias_ld,
                         const void* residual, void* y, int B, int H_, int W_, int Cin, int Cout, int stride,
                         int upsample, hipStream_t stream, int dtype = DS_DTYPE_F16, int out_h = 0, int out_w = 0,
-                        float* gn_partial = nullptr, int* gn_chunks_out = nullptr) {
+                        float* gn_partial = nullptr, int* gn_chunks_out = nullptr, int gn_chunks_planned = 0) {
     DS_REQUIRE(stride == 1 || stride == 2, "conv3x3: stride must be 1 or 2");
     DS_REQUIRE(!(upsample && stride != 1), "conv3x3: upsample with stride 2 is not a thing");
     DS_REQUIRE((out_h == 0 && out_w == 0) || (upsample && out_h > 0 && out_w > 0),
@@ -216,6 +216,7 @@ static int conv3x3_impl(const void* x, const void* w, const void* bias, const vo
     p.rows_per_group = p.Hout * p.Wout;
     p.dtype = dtype;
     p.gn_partial = gn_partial;
+    p.gn_chunks = gn_chunks_planned;   // checked against the kernel the launch picks (conv_halo.hip)
     if (gn_chunks_out) {   // host query only (ds_conv3x3_gn_chunks): no launch
         *gn_chunks_out = ds_gemm_conv_gn_chunks(p);
         return 0;
@@ -526,7 +527,7 @@ static int run_op(const ds_op& o, hipStream_t st) {
                                          o.f[0], st);
         case DS_OP_CONV3X3:
             return conv3x3_impl(p[0], p[1], p[3], p[4], i[7], p[5], p[2], i[0], i[1], i[2], i[3], i[4], i[5], i[6], st,
-                                DS_DTYPE_F16, i[8], i[9], reinterpret_cast<float*>(p[6]));
+                                DS_DTYPE_F16, i[8], i[9], reinterpret_cast<float*>(p[6]), nullptr, i[10]);
         case DS_OP_GROUPNORM: {
             GroupNormParams g;
             g.x1 = H(p[0]); g.x2 = H(p[1]); g.y = HM(p[2]); g.gamma = H(p[3]); g.beta = H(p[4]);

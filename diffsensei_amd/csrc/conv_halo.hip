@@ -817,18 +817,59 @@ int ds_conv_halo_gn_chunks(const GemmParams& p) {
     return n <= 128 ? (int)n : 0;
 }
 
+// Which of the three halo-patch kernels ds_launch_conv_halo runs on this problem - the one selection both the launch and
+// ds_conv_halo_kernel_name (the plan's kernel inventory, ds_op_describe) go through, CU-count query included.
+enum HaloKernel { HALO_8X16, HALO_16X16, HALO_DEEP };
+
+static int halo_cus() {
+    static int cus = 0;
+    if (!cus) {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+            return 256;   // no device (plans built on a host without a GPU): the MI355X's count, not cached
+        cus = n;
+    }
+    return cus;
+}
+
+static HaloKernel halo_pick(const GemmParams& p) {
+    if (halo_big(p)) return HALO_16X16;
+    // Grids of at most one 8 x 16 block per CU (UNet batch 2 at the 1280-channel level: 160 blocks): the ring-buffered variant -
+    // nothing else on the CU hides the single-buffer kernel's DMA round trip per k-tile.  f16 only (the bf16 VAE decoder never
+    // has such a grid).  Same bits out.
+    const int batch = p.M / (p.Hout * p.Wout);
+    const long blocks8 = (long)batch * ((p.Hout + PH - 1) / PH) * ((p.Wout + PW - 1) / PW) * ((p.N + BN - 1) / BN);
+    if (p.dtype == DS_DTYPE_F16 && (g_halo_variant == 3 || (g_halo_variant == 0 && blocks8 <= g_deep_max_blocks_per_cu * (long)halo_cus())))
+        return HALO_DEEP;
+    return HALO_8X16;
+}
+
+const char* ds_conv_halo_kernel_name(const GemmParams& p) {
+    switch (halo_pick(p)) {
+        case HALO_16X16: return "conv_halo256_kernel";
+        case HALO_DEEP: return "conv_halo_deep_kernel";
+        default: return "conv_halo_kernel";
+    }
+}
+
 int ds_launch_conv_halo(const GemmParams& p0, hipStream_t stream) {
     GemmParams p = p0;
     DS_REQUIRE(ds_conv_halo_applicable(p), "conv_halo: shape not supported");
     const int batch = p.M / (p.Hout * p.Wout);
     p.tiles_n = (p.N + BN - 1) / BN;
     const int ty8 = (p.Hout + PH - 1) / PH, ty16 = (p.Hout + PH2 - 1) / PH2, txs = (p.Wout + PW - 1) / PW;
-    const bool big = halo_big(p);
+    const HaloKernel kern = halo_pick(p);
     if (p.gn_partial) {
+        const int planned = p.gn_chunks;
         p.gn_chunks = ds_conv_halo_gn_chunks(p);
         DS_REQUIRE(p.gn_chunks > 0, "conv_halo: GroupNorm statistics requested for a problem with more than 128 pixel tiles per image");
+        // the GroupNorm behind this convolution adds up the chunk count of plan time (DsOp GROUPNORM i[6]); the kernel picked now
+        // must write exactly that many per image (a conv_halo_variant set on the launching thread since can change the pixel tiles).
+        // 0 = the caller states no count (CONV3X3 ops built before i[10] existed): it asked ds_conv3x3_gn_chunks itself
+        DS_REQUIRE(planned == 0 || planned == p.gn_chunks,"conv_halo: GroupNorm statistics planned as %d chunks per image, the launch would write %d",
+                   planned, p.gn_chunks);
     }
-    if (big) {
+    if (kern == HALO_16X16) {
         p.tiles_m = batch * ty16 * txs;
         const size_t lds2 = PBYTES2 + 2 * BN * 128;  // 76 KiB; the 256 x 272 B epilogue tile (68 KiB) + 4 KiB of GroupNorm partials fit inside
         static unsigned long long attr_devs = 0;
@@ -845,18 +886,7 @@ int ds_launch_conv_halo(const GemmParams& p0, hipStream_t stream) {
         return 0;
     }
     p.tiles_m = batch * ty8 * txs;
-    // Grids of at most one 8 x 16 block per CU (UNet batch 2 at the 1280-channel level: 160 blocks): the ring-buffered variant -
-    // nothing else on the CU hides the single-buffer kernel's DMA round trip per k-tile.  f16 only (the bf16 VAE decoder never
-    // has such a grid).  Same bits out.
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        DS_HIP(hipGetDevice(&dev));
-        DS_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        if (cus <= 0) cus = 256;
-    }
-    const long blocks8 = (long)p.tiles_m * p.tiles_n;
-    if (p.dtype == DS_DTYPE_F16 && (g_halo_variant == 3 || (g_halo_variant == 0 && blocks8 <= g_deep_max_blocks_per_cu * (long)cus))) {
+    if (kern == HALO_DEEP) {
         static unsigned long long attr_devs_deep = 0;
         if (ds_first_on_device(attr_devs_deep))
             DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_halo_deep_kernel<half_t>),

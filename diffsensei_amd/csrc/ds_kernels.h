@@ -46,7 +46,8 @@ struct GemmParams {
     // (image, pixel tile, output channel), the (sum, sum of squares) of the f16 values they store - the partial-sum layout of
     // gn_stats_kernel, [B][gn_chunks][Cout] float2 - so the GroupNorm that follows skips its statistics pass (one read of x less)
     float* gn_partial = nullptr;
-    int gn_chunks = 0;                 // pixel tiles per image of the kernel variant the dispatch picks (ds_conv_halo_gn_chunks)
+    int gn_chunks = 0;                 // chunks per image the plan expects (DsOp CONV3X3 i[10] = ds_conv3x3_gn_chunks at plan time); the
+                                       //   launch requires it to equal ds_conv_halo_gn_chunks of the kernel it picks (0: not stated)
     int dtype = DS_DTYPE_F16;  // element type of A / W / C / bias / residual (the pointers are 2-byte opaque): bf16 = VAE path
     int debug = 0;  // ablation only (ds_set_option "gemm_debug"): 1 skip MFMA, 2 skip tile loads — results are garbage
 };
@@ -57,6 +58,7 @@ bool ds_gemm_pp_applicable(const GemmParams& p);  // gemm_pp.hip: 256 x 256 ping
 int ds_launch_gemm_pp(const GemmParams& p, int batch, hipStream_t stream);
 bool ds_conv_halo_applicable(const GemmParams& p);  // conv_halo.hip: halo-patch 3x3 convolution takes this shape
 int ds_launch_conv_halo(const GemmParams& p, hipStream_t stream);
+const char* ds_conv_halo_kernel_name(const GemmParams& p);  // conv_halo_kernel | conv_halo256_kernel | conv_halo_deep_kernel: what ds_launch_conv_halo runs
 int ds_conv_halo_gn_chunks(const GemmParams& p);  // pixel tiles per image of the variant ds_launch_conv_halo would run; 0: no statistics (too many tiles / not applicable)
 void ds_conv_halo_set_variant(int v);  // 0 auto, 1 8x16-pixel blocks, 2 16x16-pixel blocks, 3 ring-buffered 8x16 blocks, 4 auto without the ring-buffered kernel
 void ds_conv_halo_set_deep_blocks(int v);  // the ring-buffered 8x16 kernel takes grids of <= v blocks per CU (default 1)

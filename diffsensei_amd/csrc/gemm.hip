@@ -907,7 +907,7 @@ const char* ds_gemm_kernel_name(const GemmParams& p, int batch) {
     const bool conv = p.conv != 0;
     switch (c.kind) {
         case K_PP: return "gemm_pp_kernel<0,0>";
-        case K_HALO: return "conv_halo_kernel";
+        case K_HALO: return ds_conv_halo_kernel_name(p);
         case K_RING: return c.bm == 4 ? "gemm_glds_kernel<64,false,4>" : "gemm_glds_kernel<64,false,3>";
         case K_T160: return ds_gemm_t160_rows(p.M, p.N, p.K, batch) == 128 ? "gemm_t160_kernel<128 rows>" : "gemm_t160_kernel";
         case K_G320: return "gemm_g320_kernel<plain>";
@@ -992,6 +992,14 @@ int ds_launch_gemm(const GemmParams& p_in, int batch, hipStream_t stream) {
             DS_REQUIRE(ds_gemm_pp_applicable(p), "gemm bf16: needs M, N %% 16 == 0 and K %% 128 == 0 (M=%d N=%d K=%d)", p.M, p.N, p.K);
             c.kind = K_PP;
         }
+    }
+    if (p.stats_out) {
+        // The statistics format is the planner's request: 160 (three entries per 160-column tile) only because ds_gemm_t160_fits said
+        // yes at plan time.  Any other kernel writes one entry per 64 columns - N / 64 of the 3 N / 160 its consumers add - so a
+        // launch that lands elsewhere (an A/B knob set on the launching thread since) is refused instead of leaving wrong statistics.
+        DS_REQUIRE(p.stats_strip == 160 ? c.kind == K_T160 : (p.stats_strip == 0 || p.stats_strip == 64),
+                   "gemm: LayerNorm statistics format stats_strip = %d is not what the dispatched kernel emits (M=%d N=%d K=%d)",
+                   p.stats_strip, p.M, p.N, p.K);
     }
     switch (c.kind) {
         case K_PP: return ds_launch_gemm_pp(p, batch, stream);

@@ -466,7 +466,10 @@ class UNetEngine:
         """gn_stats: the convolution's epilogue also writes the GroupNorm partial sums of its output into the workspace
         (csrc/conv_halo.hip; the caller has asked `ds_conv3x3_gn_chunks` first and passes the count to the GroupNorm op)."""
         w = self.pk.w
-        ops.append(make_op("CONV3X3", i=(self.B, H, W, Cin, Cout, stride, upsample, self.pk.temb_total, out_hw[0], out_hw[1]),
+        # i[10]: the chunk count the GroupNorm op is told; the launch checks it against the kernel it picks
+        nch = int(_lib.load().ds_conv3x3_gn_chunks(self.B, H, W, Cin, Cout)) if gn_stats else 0
+        assert not gn_stats or (nch > 0 and stride == 1 and not upsample)
+        ops.append(make_op("CONV3X3", i=(self.B, H, W, Cin, Cout, stride, upsample, self.pk.temb_total, out_hw[0], out_hw[1], nch),
                            p=(x, w[wname + ".weight"], y, w[wname + ".bias"], rowbias, residual, self.gn_ws if gn_stats else None)))
 
     def _gemm(self, ops, x, wt, y, M, N, K, bias=None, residual=None, geglu=False, x2=None, K1=0, ln_stats=None, ln_c=None,

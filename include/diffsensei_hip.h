@@ -371,9 +371,14 @@ enum ds_opcode {
     DS_OP_GEMM = 1,          /* p: x, x2, w, y, bias, rowbias, residual, ln_stats, ln_c, stats_out (fused LayerNorm, see ds_gemm_ln_f16; i[8] = operand-swapped form, l[10] = ln_bstride; i[9] = ln_stats holds PARTIAL sums, f[0] = eps, l[11] = ln_rows: ds_gemm_ln_partial_f16 / ds_gemm_ln_swapped_partial_f16)   l: ldx ldx2 ldw ldy ldr sx sx2 sw sy sr
                                 i: M N K K1 epilogue (0 none, 1 GEGLU in 128-row groups, 2 GELU, 3 QuickGELU, 4 GEGLU in 320-row groups: ds_gemm_g320_fits)
                                 batch rowbias_ld rows_per_group; i[10] = strips a consumer of partial sums adds per
-                                row (0 = K / 64), i[11] = statistics format a producer emits (0 = one entry per 64 columns; 160: ds_gemm_t160_fits) */
+                                row (0 = K / 64), i[11] = statistics format a producer emits (0 = one entry per 64 columns; 160: ds_gemm_t160_fits;
+                                the launch fails if the kernel it picks does not emit that format, e.g. 160 off gemm_t160_kernel) */
     DS_OP_CONV3X3 = 2,       /* p: x, w, y, bias, rowbias, residual, gn_partial (optional: GroupNorm workspace, see ds_conv3x3_gn_chunks)
-                                i: B H W Cin Cout stride upsample rowbias_ld Hout Wout (upsample only; 0 0 = 2H x 2W) */
+                                i: B H W Cin Cout stride upsample rowbias_ld Hout Wout (upsample only; 0 0 = 2H x 2W);
+                                i[10] = GroupNorm partial-sum chunks per image the plan expects (with p[6]: ds_conv3x3_gn_chunks at plan
+                                time, the GROUPNORM op's i[6]); the launch fails unless the kernel it picks writes exactly that many.
+                                0 = no count stated: the launch writes what its kernel writes (the caller asked ds_conv3x3_gn_chunks
+                                on the launching thread); a launch plan always states it */
     DS_OP_GROUPNORM = 3,     /* p: x1, x2, y, gamma, beta, ws             i: B HW C1 C2 groups silu pre_chunks (0, or the number of
                                 partial-sum chunks per image the producing convolution left in ws)   f: eps */
     DS_OP_LAYERNORM = 4,     /* p: x, y, gamma, beta                      i: rows C                   f: eps */

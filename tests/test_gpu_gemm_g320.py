@@ -174,3 +174,65 @@ def test_g320_plain_form_for_the_one_block_per_cu_qk_projection(hip_lib):
         assert torch.equal(ops.gemm(x, w, b), got) and torch.equal(ops.gemm_ln_partial(x, gw, b2, c2, part), got_ln)
     finally:
         lib.ds_set_option(b"gemm_g320", 0)
+
+
+# Every (kernel, M, N, K) the launch plans send to gemm_g320_kernel - SDXL at 1024 x 1024, UNet batch 2, 4, 8, 64, and 2048 x 2048
+# at batch 2 (tests/test_gpu_unet_plans.py::test_plans_send_the_one_block_per_cu_kernels_only_tested_shapes holds the plans to
+# this list) - with the form the plan uses it in: "ln" (consumer of the 64-column LayerNorm partials: q|k, attn2.to_q), "bias"
+# (resnet conv_shortcut), "geglu-ln" (the 320-packed GEGLU consumer: test_g320_consumes_a_fused_layernorm_like_the_128_wide_kernels).
+# (13100, 1280, 640) is no plan's shape: a ragged M inside the rule's range (52 row tiles, the last one 44 rows).
+PLAN_SHAPES = [
+    ("gemm_g320_kernel", 2048, 10240, 1280, "geglu-ln"),            # batch 2, 1280-channel level
+    ("gemm_g320_kernel<plain>", 16384, 1280, 640, "ln"),            # batch 4, q|k of the 640-channel level
+    ("gemm_g320_kernel<plain>", 8192, 2560, 1280, "ln"),            # batch 8 (and 2048 x 2048 batch 2), q|k of the 1280-channel level
+    ("gemm_g320_kernel<plain>", 32768, 640, 320, "bias"),           # batch 8, 640-channel level
+    ("gemm_g320_kernel<plain>", 32768, 640, 640, "ln"),
+    ("gemm_g320_kernel<plain>", 13100, 1280, 640, "bias"),
+]
+
+
+@pytest.mark.parametrize("name,M,N,K,form", [s for s in PLAN_SHAPES if s[4] != "geglu-ln"])
+def test_g320_plain_at_the_shapes_the_plans_send_it(hip_lib, name, M, N, K, form):
+    """Automatic dispatch picks the plain gemm_g320_kernel at (M, N, K) in the plan's form; vs an fp64 reference of the same f16
+    inputs (<= 2e-3 of max|ref|, 3e-3 behind the fused LayerNorm) and bit for bit vs the kernel the rule replaces (gemm_g320 = 1)."""
+    from diffsensei_amd import _lib
+    from diffsensei_amd.engine import make_op, pack_ln_fused
+    lib = _lib.load()
+    g = torch.Generator().manual_seed(M + 5 * N + 11 * K)
+    x, w, b = _r((M, K), g).to(DEV), _r((N, K), g, 1 / math.sqrt(K)).to(DEV), _r((N,), g, 0.3).to(DEV)
+    ln_part = ln_c = None
+    if form == "ln":
+        gamma, beta = (1 + 0.2 * torch.randn(K, generator=g)).half().to(DEV), _r((K,), g, 0.2).to(DEV)
+        wt, ln_c, bias = pack_ln_fused(w, b, gamma, beta)
+        xs = x.double().view(M, K // 64, 64)
+        ln_part = torch.stack([xs.sum(-1).t(), (xs * xs).sum(-1).t()], dim=-1).float().contiguous()
+        want = F.layer_norm(x.double(), (K,), gamma.double(), beta.double(), 1e-5) @ w.double().t() + b.double()
+        tol = 3e-3
+    else:
+        wt, bias, tol = w, b, 2e-3
+        want = x.double() @ w.double().t() + b.double()
+
+    def run():
+        y = torch.empty((M, N), dtype=torch.float16, device=DEV)
+        op = make_op("GEMM", i=(M, N, K, K, 0, 1, 0, 1, 0, int(ln_part is not None), 0, 0), f=(1e-5,), l=(K, 0, K, N, N),
+                     p=(x, None, wt, y, bias, None, None, ln_part, ln_c, None))
+        nm = C.create_string_buffer(128)
+        fl, by = C.c_double(), C.c_double()
+        assert lib.ds_op_describe(C.byref(op), nm, 128, C.byref(fl), C.byref(by)) == 0
+        rc = lib.ds_op_run(C.byref(op), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        assert rc == 0, lib.ds_last_error().decode()
+        torch.cuda.synchronize()
+        return y, nm.value.decode()
+
+    y, nm = run()
+    assert nm == name, nm
+    e = _relmax(y, want)
+    print(f"{name} M={M} N={N} K={K} {form}: max err / max|ref| {e:.2e}")
+    assert e <= tol, e
+    assert lib.ds_set_option(b"gemm_g320", 1) == 0
+    try:
+        old, nm_old = run()
+    finally:
+        lib.ds_set_option(b"gemm_g320", 0)
+    assert not nm_old.startswith("gemm_g320"), nm_old
+    assert torch.equal(y, old), f"{name} and {nm_old} differ"

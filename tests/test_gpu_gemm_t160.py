@@ -223,3 +223,80 @@ def test_t160_tall_tiles_rule_and_fused_layernorm_chain(hip_lib):
     assert _relmax(outs[3][2], ref) <= 3e-3
     # automatic dispatch at the q|k shape of a batch-1 request
     assert _gemm_op(lib, outs[3][0], gw, bias=b2, ln_partial=outs[3][1], ln_c=c2, ln_nstrips=24)[2] == "gemm_t160_kernel<128 rows>"
+
+
+# Every (kernel, M, N, K) the launch plans send to gemm_t160_kernel - SDXL at 1024 x 1024, UNet batch 2, 4, 8, 64, and 2048 x 2048
+# at batch 2 (tests/test_gpu_unet_plans.py::test_plans_send_the_one_block_per_cu_kernels_only_tested_shapes holds the plans to
+# this list) - with the form the plan uses it in: "bias" (resnet conv_shortcut), "stats" (LayerNorm-statistics producer in the
+# 160-column format: proj_in without, the out-projections / FF down-projection with a residual), "ln" (consumer of those partials).
+PLAN_SHAPES = [
+    ("gemm_t160_kernel", 2048, 1280, 640, "bias"),                  # batch 2, 1280-channel level
+    ("gemm_t160_kernel", 2048, 1280, 1280, "stats"),
+    ("gemm_t160_kernel", 2048, 1280, 1280, "ln"),
+    ("gemm_t160_kernel", 2048, 1280, 5120, "stats"),
+    ("gemm_t160_kernel<128 rows>", 2048, 2560, 1280, "ln"),         # batch 2, q|k of the 1280-channel level
+    ("gemm_t160_kernel<128 rows>", 8192, 640, 320, "bias"),         # batch 2, 640-channel level
+    ("gemm_t160_kernel<128 rows>", 8192, 640, 640, "stats"),
+    ("gemm_t160_kernel<128 rows>", 8192, 640, 640, "ln"),
+    ("gemm_t160_kernel<128 rows>", 8192, 640, 2560, "stats"),
+    ("gemm_t160_kernel<128 rows>", 4096, 1280, 640, "bias"),        # batch 4, 1280-channel level
+    ("gemm_t160_kernel<128 rows>", 4096, 1280, 1280, "stats"),
+    ("gemm_t160_kernel<128 rows>", 4096, 1280, 1280, "ln"),
+    ("gemm_t160_kernel<128 rows>", 4096, 1280, 5120, "stats"),
+]
+
+
+def _partials160(y):
+    """[3 N / 160, M, 2] fp64 (sum, sum of squares) of y's columns 0..63 | 64..127 | 128..159 of every 160-column tile."""
+    M, N = y.shape
+    t = y.double().view(M, N // 160, 160)
+    ent = [t[..., :64], t[..., 64:128], t[..., 128:]]
+    s = torch.stack([e.sum(-1) for e in ent], 2).reshape(M, -1)
+    q = torch.stack([(e * e).sum(-1) for e in ent], 2).reshape(M, -1)
+    return torch.stack([s.t(), q.t()], -1)
+
+
+@pytest.mark.parametrize("name,M,N,K,form", PLAN_SHAPES)
+def test_t160_at_the_shapes_the_plans_send_it(hip_lib, name, M, N, K, form):
+    """Automatic dispatch picks `name` at (M, N, K) in the plan's form; vs an fp64 reference of the same f16 inputs (<= 2e-3 of
+    max|ref|, 3e-3 behind the fused LayerNorm); producer partials vs fp64 row sums of the stored output; and bit for bit the
+    output of the kernel the rule replaces there (gemm_t160 = 1)."""
+    from diffsensei_amd import _lib
+    from diffsensei_amd.engine import pack_ln_fused
+    lib = _lib.load()
+    g = torch.Generator().manual_seed(M + 3 * N + 7 * K)
+    x, w, b = _r((M, K), g).to(DEV), _r((N, K), g, 1 / math.sqrt(K)).to(DEV), _r((N,), g, 0.3).to(DEV)
+    r = (_r((M, N), g) * 2 + 0.5).half().to(DEV)
+    ref = x.double() @ w.double().t() + b.double()
+    runs = []   # (description, kwargs of _gemm_op, reference, tolerance)
+    if form == "bias":
+        runs.append(("bias", dict(bias=b), ref, 2e-3))
+    elif form == "stats":
+        runs.append(("producer", dict(bias=b, stats_strip=160), ref, 2e-3))
+        runs.append(("producer + residual", dict(bias=b, residual=r, stats_strip=160), ref.half().double() + r.double(), 2e-3))
+    else:
+        gamma, beta = (1 + 0.2 * torch.randn(K, generator=g)).half().to(DEV), _r((K,), g, 0.2).to(DEV)
+        gw, c2, b2 = pack_ln_fused(w, b, gamma, beta)
+        part = _partials160(x).float().contiguous()
+        ln = F.layer_norm(x.double(), (K,), gamma.double(), beta.double(), 1e-5)
+        runs.append(("LayerNorm consumer", dict(w=gw, bias=b2, ln_partial=part, ln_c=c2, ln_nstrips=3 * (K // 160)),
+                     ln @ w.double().t() + b.double(), 3e-3))
+    for what, kw, want, tol in runs:
+        wt = kw.pop("w", w)
+        y, part, nm = _gemm_op(lib, x, wt, **kw)
+        assert nm == name, (what, nm)
+        e = _relmax(y, want)
+        print(f"{name} M={M} N={N} K={K} {what}: max err / max|ref| {e:.2e}")
+        assert e <= tol, (what, e)
+        if part is not None:
+            want_p = _partials160(y)
+            assert part.shape == want_p.shape
+            assert torch.allclose(part.double(), want_p, rtol=1e-5, atol=1e-3), f"{what}: statistics differ from fp64 row sums"
+        kw.pop("stats_strip", None)   # the replaced kernel does not emit the 160-column format: compare the stored output
+        assert lib.ds_set_option(b"gemm_t160", 1) == 0
+        try:
+            old, _, nm_old = _gemm_op(lib, x, wt, **kw)
+        finally:
+            lib.ds_set_option(b"gemm_t160", 0)
+        assert not nm_old.startswith("gemm_t160"), nm_old
+        assert torch.equal(y, old), f"{what}: {name} and {nm_old} differ"

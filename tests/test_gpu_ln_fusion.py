@@ -146,7 +146,9 @@ def test_fused_chain_producer_finalize_consumer_and_refusals(hip_lib):
         ops.gemm_ln(dv(a), gw, None, c2, st)
 
 
-@pytest.mark.parametrize("Z,N,C", [(3, 512, 256), (3, 512, 640), (2, 1024, 384), (5, 256, 1280)])
+# (2, 4096, 1280): the 1280-channel V^T projection of 2048 x 2048 at UNet batch 2, one of the two GEMM shapes of that plan that the
+# 1024 x 1024 batch-8 plan does not have (tests/test_gpu_unet_plans.py::test_2048_batch2_plan_is_the_1024_batch8_plan_but_for_the_vt_projections)
+@pytest.mark.parametrize("Z,N,C", [(3, 512, 256), (3, 512, 640), (2, 1024, 384), (5, 256, 1280), (2, 4096, 1280)])
 def test_consumer_swapped_vs_layernorm_linear(hip_lib, Z, N, C):
     """norm1 -> attn1.to_v, produced transposed per image: out[z] = Wv LN(x[z])^T (operand-swapped form: the statistics run
     along the output columns, c and b' along its rows, batch items folded into the persistent tile walk).  C = 640 / 384: the
@@ -262,7 +264,8 @@ def test_wide_consumer_geglu_and_chain(hip_lib):
 
 
 
-@pytest.mark.parametrize("Z,N,C", [(2, 1024, 1280), (3, 296, 640), (2, 4096, 640), (1, 72, 128)])
+# (2, 16384, 640): the 640-channel V^T projection of 2048 x 2048 at UNet batch 2 (see test_consumer_swapped_vs_layernorm_linear)
+@pytest.mark.parametrize("Z,N,C", [(2, 1024, 1280), (3, 296, 640), (2, 4096, 640), (1, 72, 128), (2, 16384, 640)])
 def test_wide_consumer_swapped_vs_layernorm_linear(hip_lib, Z, N, C):
     """norm1 -> attn1.to_v on the 128-wide kernels (small batches; any token count, e.g. 296):
     every block finalises the statistics of its 128 output columns from the producer's partial sums.  vs fp32, and vs the

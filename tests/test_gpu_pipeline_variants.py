@@ -275,6 +275,8 @@ def test_forward_flop_inventory_matches_survey(hip_lib):
     # 128 x 160 tiles of gemm_t160_kernel, the other N = 1280 projections on its 64 x 160 tiles: the UNet-vs-oracle gates of
     # tests/test_gpu_unet.py at this shape therefore cover them
     assert names["gemm_g320_kernel"] == 60 and names["gemm_t160_kernel<128 rows>"] >= 60 and names["gemm_t160_kernel"] >= 240, names
+    # the 1280-channel level's 3x3 convolutions (160 blocks of 8 x 16 pixels: at most one per CU) run the ring-buffered halo kernel
+    assert names["conv_halo_deep_kernel"] == 14 and names["conv_halo_kernel"] == 22 and names["conv_halo256_kernel"] == 0, names
     # 963 launches with every LayerNorm a launch of its own; at this batch all 210 are folded into the GEMMs around them (the
     # 128-wide kernels' fused epilogues) at the price of 10 finalize launches (the GEGLU projections of the 64 x 64-token level are
     # gemm_pp_kernel consumers): 763, + CFG/scheduler step + counter advance = 765 launches per denoise step
