@@ -9,7 +9,8 @@ classes without the built library raises (no CPU / PyTorch fallback exists).
 from .unet_config import UNetMangaConfig, sdxl_config, tiny_config  # noqa: F401
 
 __all__ = ["UNetMangaConfig", "sdxl_config", "tiny_config", "UNetMangaModel", "DiffSenseiPipeline", "Resampler",
-           "AttnProcessor2_0", "MaskedIPAttnProcessor2_0", "EulerDiscreteScheduler", "DDIMScheduler"]
+           "AttnProcessor2_0", "MaskedIPAttnProcessor2_0", "EulerDiscreteScheduler", "DDIMScheduler",
+           "DPMSolverMultistepScheduler"]
 
 
 def __getattr__(name):
@@ -26,7 +27,7 @@ def __getattr__(name):
     if name in ("AttnProcessor2_0", "MaskedIPAttnProcessor2_0"):
         from . import attention_processor
         return getattr(attention_processor, name)
-    if name in ("EulerDiscreteScheduler", "DDIMScheduler"):
+    if name in ("EulerDiscreteScheduler", "DDIMScheduler", "DPMSolverMultistepScheduler"):
         from . import schedulers
         return getattr(schedulers, name)
     raise AttributeError(name)

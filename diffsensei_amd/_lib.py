@@ -76,6 +76,7 @@ SIGNATURES = {
     "ds_timestep_embed_f16": (i32, [vp, vp, vp, i32, i32, i32, f32, vp]),
     "ds_add_time_ids_f16": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp]),
     "ds_cfg_sampler_step_f16": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "ds_cfg_dpm_step_f16": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "ds_prepare_model_input_f16": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
     "ds_nhwc_to_nchw_f16": (i32, [vp, vp, i32, i32, i32, vp]),
     "ds_nchw_to_nhwc_f16": (i32, [vp, vp, i32, i32, i32, vp]),

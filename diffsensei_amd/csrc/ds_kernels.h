@@ -180,8 +180,10 @@ struct SamplerStepParams {
     half_t* latents = nullptr;      // NCHW [ns,4,H,W], updated in place (fp16 between steps, like the reference)
     half_t* model_in = nullptr;     // NHWC [2*ns, HW, 4]: next step's scaled input (both CFG halves)
     const float* coef = nullptr;    // per-step scalar table (see elementwise.hip)
+    half_t* prev_x0 = nullptr;      // kind 2: NCHW [ns,4,H,W] x0 of the previous step (read, then overwritten)
+    const float* solver = nullptr;  // kind 2: per-step solver rows [n_steps,8] (include/diffsensei_hip.h)
     int ns = 0, HW = 0, C = 4;
-    int kind = 0;                   // 0 Euler, 1 DDIM
+    int kind = 0;                   // 0 Euler, 1 DDIM, 2 DPM-Solver++ (multistep, order 1|2 per row)
     int do_cfg = 1;
 };
 int ds_launch_sampler_step(const SamplerStepParams& p, const int* ctr, hipStream_t stream);

@@ -222,12 +222,17 @@ __global__ void add_time_ids_kernel(const half_t* text_embeds, const half_t* tim
 // ---------------------------------------------------------------- CFG + scheduler step + next model input
 // One thread per (sample, pixel): 4 latent channels.  All arithmetic mirrors the reference's rounding points:
 // CFG in fp16 (noise_pred tensors are fp16), Euler update in fp32, latents stored fp16 between steps.
+// DPM-Solver++ (kind 2) rounds where diffusers' DPMSolverMultistepScheduler [3P] does with fp16 tensors and 0-dim fp32
+// scalars: x0 in fp16 (convert_model_output sees the fp16 sample), every scalar*fp16-tensor product in fp16, the
+// update itself in fp32 on the upcast sample (fp32 intermediates under the library's fast-math flags, like the
+// Euler / DDIM branches).  Its x0 is kept in `prev_x0` for the next row's second-order term.
 __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p, const int* ctr) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     const long total = (long)p.ns * p.HW;
     if (i >= total) return;
     const int n = (int)(i / p.HW), pix = (int)(i - (long)n * p.HW);
     const float* cf = coef_row(p.coef, ctr);
+    const float* sv = p.kind == 2 ? coef_row(p.solver, ctr) : nullptr;
     const h4 eu = *reinterpret_cast<const h4*>(p.eps + ((long)n * p.HW + pix) * 4);
     h4 e = eu;
     if (p.do_cfg) {
@@ -251,9 +256,18 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p, 
             const float pred_x0 = x - s * ef;
             const float deriv = (x - pred_x0) / s;
             xn = x + deriv * (sn - s);
-        } else {            // DDIM eta=0: k0 = sqrt(a_t), k1 = sqrt(1-a_t), k2 = sqrt(a_prev), k3 = sqrt(1-a_prev)
+        } else if (p.kind == 1) {  // DDIM eta=0: k0 = sqrt(a_t), k1 = sqrt(1-a_t), k2 = sqrt(a_prev), k3 = sqrt(1-a_prev)
             const float pred_x0 = (x - cf[3] * ef) / cf[2];
             xn = cf[4] * pred_x0 + cf[5] * ef;
+        } else {                   // DPM-Solver++: sv = {order, sigma_s, alpha_s, a, b, 1/r0, c, -}
+            half_t* pp = p.prev_x0 + ((long)n * 4 + c) * p.HW + pix;
+            const half_t x0 = (half_t)((float)(half_t)(x - (float)(half_t)(sv[1] * ef)) / sv[2]);
+            xn = sv[3] * x - (float)(half_t)(sv[4] * (float)x0);
+            if (sv[0] == 2.0f) {   // a branch, not a zero weight: prev_x0 is garbage before a call's first step
+                const half_t d1 = (half_t)((float)(half_t)((float)x0 - (float)*pp) * sv[5]);
+                xn = xn - (float)(half_t)(sv[6] * (float)d1);
+            }
+            *pp = x0;
         }
         const half_t xh = (half_t)xn;
         *lp = xh;
@@ -431,6 +445,8 @@ int ds_launch_add_time_ids(const half_t* text_embeds, const half_t* time_ids, ha
 int ds_launch_sampler_step(const SamplerStepParams& p, const int* ctr, hipStream_t stream) {
     DS_REQUIRE(p.C == 4, "sampler_step: latent channels must be 4");
     DS_REQUIRE(p.ns > 0 && p.HW > 0 && p.coef, "sampler_step: bad arguments");
+    DS_REQUIRE(p.kind >= 0 && p.kind <= 2, "sampler_step: kind must be 0 (Euler), 1 (DDIM) or 2 (DPM-Solver++)");
+    DS_REQUIRE(p.kind != 2 || (p.prev_x0 && p.solver), "sampler_step: kind 2 needs prev_x0 and the solver rows");
     const long total = (long)p.ns * p.HW;
     hipLaunchKernelGGL(sampler_step_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p, ctr);
     DS_LAUNCH_CHECK();

@@ -742,20 +742,36 @@ class UNetEngine:
         self.latents = self._alloc((ns, self.cfg.in_channels, self.H, self.W), torch.float16)
         self.prep_plan = Plan([make_op("PREP_INPUT", i=(ns, HW, int(do_cfg)),
                                        p=(self.latents, self.x_in, self.table, self.ctr))], self.keep)
+        dpm = ()
+        if kind == 2:  # DPM-Solver++: the previous step's x0 + the per-step solver rows (allocated once per shape)
+            if getattr(self, "prev_x0", None) is None or self.prev_x0.shape != self.latents.shape:
+                self.prev_x0 = self._alloc(tuple(self.latents.shape), torch.float16)
+            if getattr(self, "solver", None) is None:
+                self.solver = self._alloc((self.table.shape[0], 8), torch.float32)
+                self.solver.zero_()
+            dpm = (self.prev_x0, self.solver)
         step_ops = list(self.forward_ops) + [
             make_op("SAMPLER_STEP", i=(ns, HW, kind, int(do_cfg)),
-                    p=(self.eps, self.latents, self.x_in, self.table, self.ctr)),
+                    p=(self.eps, self.latents, self.x_in, self.table, self.ctr) + dpm),
             make_op("ADVANCE", p=(self.ctr,)),
         ]
         self.step_plan = Plan(step_ops, self.keep)
         self._sampler_key = key
 
-    def load_schedule(self, table_rows: Tensor):
-        """table_rows: fp32 [n_steps, 8] (see include/diffsensei_hip.h); resets the device step counter."""
+    def load_schedule(self, table_rows: Tensor, solver_rows: Optional[Tensor] = None):
+        """table_rows: fp32 [n_steps, 8]; solver_rows: fp32 [n_steps, 8], the DPM-Solver++ rows (kind 2 only)
+        (see include/diffsensei_hip.h); resets the device step counter."""
         n = table_rows.shape[0]
         if n > self.table.shape[0]:
             raise ValueError("too many steps for the scalar table")
+        kind = getattr(self, "_sampler_key", (None, None))[1]
+        if (solver_rows is not None) != (kind == 2):
+            raise ValueError(f"solver rows are given exactly for a DPM-Solver++ sampler (built kind: {kind})")
         self.table[:n].copy_(table_rows.to(self.dev, torch.float32))
+        if solver_rows is not None:
+            if tuple(solver_rows.shape) != (n, 8):
+                raise ValueError(f"solver rows {tuple(solver_rows.shape)} do not match the {n} table rows")
+            self.solver[:n].copy_(solver_rows.to(self.dev, torch.float32))
         self.ctr.zero_()
 
     # -- host-side setters (tiny H2D copies; never inside a captured graph)

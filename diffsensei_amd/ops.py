@@ -367,6 +367,20 @@ def cfg_sampler_step(eps: Tensor, latents: Tensor, model_in: Tensor, table: Tens
                                               int(do_cfg), _stream()), "ds_cfg_sampler_step_f16")
 
 
+def cfg_dpm_step(eps: Tensor, latents: Tensor, model_in: Tensor, table: Tensor, solver: Tensor, prev_x0: Tensor,
+                 do_cfg: bool = True, ctr: Optional[Tensor] = None) -> None:
+    """DPM-Solver++ step: eps [2ns,HW,4] NHWC; latents, prev_x0: [ns,4,H,W] NCHW (both in place); model_in: [2ns,HW,4];
+    solver: fp32 rows [n,8] (include/diffsensei_hip.h)."""
+    _chk(eps, latents, model_in, prev_x0)
+    _chk(table, solver, dtype=torch.float32)
+    if prev_x0.shape != latents.shape:
+        raise ValueError(f"prev_x0 {tuple(prev_x0.shape)} must have the latents' shape {tuple(latents.shape)}")
+    ns = latents.shape[0]
+    HW = latents.shape[2] * latents.shape[3]
+    check(_lib.load().ds_cfg_dpm_step_f16(_p(eps), _p(latents), _p(model_in), _p(table), _p(solver), _p(prev_x0),
+                                          _p(ctr), ns, HW, int(do_cfg), _stream()), "ds_cfg_dpm_step_f16")
+
+
 def prepare_model_input(latents: Tensor, model_in: Tensor, table: Tensor, do_cfg: bool = True,
                         ctr: Optional[Tensor] = None) -> None:
     _chk(latents, model_in)

@@ -410,7 +410,9 @@ class DiffSenseiPipeline:
         eng = self.unet.engine(B, H, W, aspect_ratio)
         eng.build_sampler(num_samples, self.scheduler.kind, do_cfg)
         eng.set_request(enc, add_text_embeds, add_time_ids, bbox, dialog_pixel_boxes(dialog, H, W), float(ip_scale))
-        eng.load_schedule(torch.from_numpy(self.scheduler.coef_table(float(guidance_scale))))
+        solver = self.scheduler.solver_table()             # DPM-Solver++ rows; None for Euler / DDIM
+        eng.load_schedule(torch.from_numpy(self.scheduler.coef_table(float(guidance_scale))),
+                          None if solver is None else torch.from_numpy(solver))
         eng.latents.copy_(lat)
         if self._stream is None:
             self._stream = torch.cuda.Stream(device=device)

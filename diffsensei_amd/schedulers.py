@@ -4,11 +4,15 @@
 
 Host side = the schedule tables only (a few hundred scalars computed once per `set_timesteps`, in numpy exactly
 where diffusers uses numpy).  All per-element arithmetic (CFG combine, the update, the next step's input scaling)
-runs in ONE HIP kernel (`ds_cfg_sampler_step_f16`) reading a per-step scalar table the engine indexes with a
-device-side step counter — the reference issues 5+ elementwise launches per step here.
+runs in ONE HIP kernel (`ds_cfg_sampler_step_f16`, `ds_cfg_dpm_step_f16`) reading a per-step scalar table the engine
+indexes with a device-side step counter — the reference issues 5+ elementwise launches per step here.
+
+Every class has diffusers' `.config` and `from_config(config, **overrides)`, so the usual scheduler swap
+`pipe.scheduler = DPMSolverMultistepScheduler.from_config(pipe.scheduler.config, use_karras_sigmas=True)` works.
 """
 from __future__ import annotations
 
+import math
 from typing import Optional
 
 import numpy as np
@@ -16,7 +20,31 @@ import torch
 
 from . import ops
 
-KIND_EULER, KIND_DDIM = 0, 1
+KIND_EULER, KIND_DDIM, KIND_DPM = 0, 1, 2
+
+
+class _Config(dict):
+    """diffusers' FrozenDict stand-in: item and attribute access."""
+
+    def __getattr__(self, key):
+        try:
+            return self[key]
+        except KeyError:
+            raise AttributeError(key) from None
+
+
+class _ConfigMixin:
+    @classmethod
+    def _config_keys(cls):
+        raise NotImplementedError
+
+    @classmethod
+    def from_config(cls, config=None, **overrides):
+        """diffusers `SchedulerMixin.from_config`: keys the class does not take are ignored (another class's config)."""
+        merged = dict(config or {})
+        merged.update(overrides)
+        keys = cls._config_keys()
+        return cls(**{k: v for k, v in merged.items() if k in keys})
 
 
 def _alphas_cumprod(T: int, beta_start: float, beta_end: float) -> torch.Tensor:
@@ -24,9 +52,10 @@ def _alphas_cumprod(T: int, beta_start: float, beta_end: float) -> torch.Tensor:
     return torch.cumprod(1.0 - betas, dim=0)
 
 
-class _SchedulerBase:
+class _SchedulerBase(_ConfigMixin):
     kind = -1
     order = 1
+    _CONFIG_FIXED = ()  # the `_FIXED` keys that are constructor arguments of the diffusers class (kept in `.config`)
     _FIXED = {"trained_betas": (None,), "rescale_betas_zero_snr": (False,), "use_karras_sigmas": (False,),
               "use_exponential_sigmas": (False,), "use_beta_sigmas": (False,), "interpolation_type": ("linear",),
               "final_sigmas_type": ("zero",), "timestep_type": ("discrete",), "sigma_min": (None,), "sigma_max": (None,),
@@ -43,6 +72,10 @@ class _SchedulerBase:
             if key in unused and unused[key] not in ok:
                 raise NotImplementedError(f"scheduler config {key}={unused[key]!r}: the MI355X sampler kernel implements "
                                           f"{key} in {ok} only")
+        self.config = _Config(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                              beta_schedule=beta_schedule, steps_offset=steps_offset, timestep_spacing=timestep_spacing,
+                              prediction_type=prediction_type,
+                              **{k: unused.get(k, self._FIXED[k][0]) for k in self._CONFIG_FIXED})
         self.T = num_train_timesteps
         self.steps_offset = steps_offset
         self.alphas_cumprod = _alphas_cumprod(num_train_timesteps, beta_start, beta_end)
@@ -51,9 +84,18 @@ class _SchedulerBase:
         self._step_index = 0
         self._dev_table = None
 
+    @classmethod
+    def _config_keys(cls):
+        return ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "steps_offset", "timestep_spacing",
+                "prediction_type") + cls._CONFIG_FIXED
+
     # -- table for the engine: rows [n_steps, 8] = {t, c_in_div, k0..k3, c_in_div_next, guidance}
     def coef_table(self, guidance_scale: float) -> np.ndarray:
         raise NotImplementedError
+
+    # -- second per-step table (DPM-Solver++ only; see include/diffsensei_hip.h)
+    def solver_table(self) -> Optional[np.ndarray]:
+        return None
 
     def _table_on(self, device, guidance: float) -> torch.Tensor:
         return torch.from_numpy(self.coef_table(guidance)).to(device)
@@ -92,6 +134,9 @@ class _SchedulerBase:
 class EulerDiscreteScheduler(_SchedulerBase):
     """diffusers EulerDiscreteScheduler [3P] (deterministic: s_churn = 0, final sigma 0, linear interpolation)."""
     kind = KIND_EULER
+    _CONFIG_FIXED = ("trained_betas", "use_karras_sigmas", "use_exponential_sigmas", "use_beta_sigmas",
+                     "interpolation_type", "sigma_min", "sigma_max", "timestep_type", "rescale_betas_zero_snr",
+                     "final_sigmas_type")
 
     def set_timesteps(self, num_inference_steps: int, device=None):
         n = num_inference_steps
@@ -124,6 +169,7 @@ class EulerDiscreteScheduler(_SchedulerBase):
 class DDIMScheduler(_SchedulerBase):
     """diffusers DDIMScheduler [3P], eta = 0, clip_sample False, set_alpha_to_one False."""
     kind = KIND_DDIM
+    _CONFIG_FIXED = ("trained_betas", "clip_sample", "set_alpha_to_one", "thresholding", "rescale_betas_zero_snr")
     init_noise_sigma = 1.0
 
     def set_timesteps(self, num_inference_steps: int, device=None):
@@ -145,3 +191,183 @@ class DDIMScheduler(_SchedulerBase):
             a_p = ac[prev] if prev >= 0 else ac[0]
             tab[i] = [float(t), 1.0, a_t ** 0.5, (1 - a_t) ** 0.5, a_p ** 0.5, (1 - a_p) ** 0.5, 1.0, guidance_scale]
         return tab
+
+
+class DPMSolverMultistepScheduler(_ConfigMixin):
+    """diffusers DPMSolverMultistepScheduler [3P]: DPM-Solver++ (algorithm_type "dpmsolver++"), multistep, solver_order
+    1 or 2, solver_type "midpoint" or "heun", epsilon prediction, deterministic.
+
+    Per step the engine reads the shared table row {t, 1, 0, 0, 0, 0, 1, guidance} (init_noise_sigma = 1 and
+    scale_model_input is the identity) plus one solver row {order, sigma_s, alpha_s, a, b, 1/r0, c, 0}
+    (include/diffsensei_hip.h).  Which rows run first order (diffusers' `lower_order_nums` / `lower_order_final` rules)
+    is decided here, per row, so a captured step graph needs no host logic.  Scalars are 0-dim fp32 torch values
+    computed in diffusers' order; the last row of a zero final sigma gives a = 0, b = -1 (lambda_t = +inf, no NaN)."""
+    kind = KIND_DPM
+    order = 1
+    init_noise_sigma = 1.0
+    # diffusers' constructor defaults for this class (linear betas: NOT the SDXL schedule, so a bare config is refused)
+    _DEFAULTS = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
+                     trained_betas=None, solver_order=2, prediction_type="epsilon", thresholding=False,
+                     dynamic_thresholding_ratio=0.995, sample_max_value=1.0, algorithm_type="dpmsolver++",
+                     solver_type="midpoint", lower_order_final=True, euler_at_final=False, use_karras_sigmas=False,
+                     use_exponential_sigmas=False, use_beta_sigmas=False, use_lu_lambdas=False, use_flow_sigmas=False,
+                     flow_shift=1.0, final_sigmas_type="zero", lambda_min_clipped=-float("inf"), variance_type=None,
+                     timestep_spacing="linspace", steps_offset=0, rescale_betas_zero_snr=False)
+    # keys whose other values change the schedule or the update rule: only what the device kernel implements is accepted
+    _SUPPORTED = {"beta_schedule": ("scaled_linear",), "trained_betas": (None,), "solver_order": (1, 2),
+                  "prediction_type": ("epsilon",), "thresholding": (False,), "algorithm_type": ("dpmsolver++",),
+                  "solver_type": ("midpoint", "heun"), "use_exponential_sigmas": (False,), "use_beta_sigmas": (False,),
+                  "use_lu_lambdas": (False,), "use_flow_sigmas": (False,), "final_sigmas_type": ("zero", "sigma_min"),
+                  "variance_type": (None,), "timestep_spacing": ("leading", "linspace", "trailing"),
+                  "rescale_betas_zero_snr": (False,)}
+
+    def __init__(self, **kwargs):
+        cfg = _Config(self._DEFAULTS)
+        cfg.update({k: v for k, v in kwargs.items() if k in self._DEFAULTS})   # other keys: not this class's (ignored)
+        for key, ok in self._SUPPORTED.items():
+            if isinstance(cfg[key], (list, tuple)) or cfg[key] not in ok:
+                raise NotImplementedError(f"scheduler config {key}={cfg[key]!r}: the MI355X DPM-Solver++ kernel "
+                                          f"implements {key} in {ok} only")
+        lmc = float(cfg["lambda_min_clipped"])
+        if not (math.isinf(lmc) and lmc < 0):
+            raise NotImplementedError(f"scheduler config lambda_min_clipped={lmc!r}: only -inf (no clipping)")
+        self.config = cfg
+        self.T = int(cfg["num_train_timesteps"])
+        self.alphas_cumprod = _alphas_cumprod(self.T, cfg["beta_start"], cfg["beta_end"])
+        self.timesteps = None
+        self.sigmas = None
+        self.num_inference_steps = None
+        self.lower_order_nums = 0
+        self._step_index = None
+        self._prev_x0 = None
+
+    @classmethod
+    def _config_keys(cls):
+        return tuple(cls._DEFAULTS)
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        """diffusers `set_timesteps` (lambda_min_clipped = -inf, so the last usable timestep is num_train_timesteps)."""
+        cfg, n, T = self.config, int(num_inference_steps), self.T
+        if cfg.timestep_spacing == "linspace":
+            ts = np.linspace(0, T - 1, n + 1).round()[::-1][:-1].copy().astype(np.int64)
+        elif cfg.timestep_spacing == "leading":
+            step_ratio = T // (n + 1)
+            ts = (np.arange(0, n + 1) * step_ratio).round()[::-1][:-1].copy().astype(np.int64)
+            ts += cfg.steps_offset
+        else:  # trailing
+            ts = np.arange(T, 0, -T / n).round().copy().astype(np.int64)
+            ts -= 1
+        ac = self.alphas_cumprod
+        sigmas = np.array(((1 - ac) / ac) ** 0.5)
+        log_sigmas = np.log(sigmas)
+        if cfg.use_karras_sigmas:
+            sigmas = np.flip(sigmas).copy()
+            rho, s_min, s_max = 7.0, sigmas[-1].item(), sigmas[0].item()
+            ramp = np.linspace(0, 1, n)
+            sigmas = (s_max ** (1 / rho) + ramp * (s_min ** (1 / rho) - s_max ** (1 / rho))) ** rho
+            ts = _sigma_to_t(sigmas, log_sigmas).round()
+        else:
+            sigmas = np.interp(ts, np.arange(0, len(sigmas)), sigmas)
+        last = float(((1 - ac[0]) / ac[0]) ** 0.5) if cfg.final_sigmas_type == "sigma_min" else 0.0
+        self.sigmas = torch.from_numpy(np.concatenate([sigmas, [last]]).astype(np.float32))
+        self.timesteps_np = np.asarray(ts).astype(np.int64)
+        self.timesteps = torch.from_numpy(self.timesteps_np.copy())
+        if device is not None:
+            self.timesteps = self.timesteps.to(device)
+        self.num_inference_steps = len(self.timesteps_np)
+        self.lower_order_nums = 0
+        self._step_index = None
+
+    # -- which rows run first order (diffusers `step`: lower_order_nums < 1, lower_order_final)
+    def _order(self, i: int, lower_order_nums: int) -> int:
+        cfg, n = self.config, self.num_inference_steps
+        final = i == n - 1 and (cfg.euler_at_final or (cfg.lower_order_final and n < 15)
+                                or cfg.final_sigmas_type == "zero")
+        return 1 if (cfg.solver_order == 1 or lower_order_nums < 1 or final) else 2
+
+    def step_orders(self) -> np.ndarray:
+        """Order of every row when the whole schedule runs from step 0 (what the device table encodes)."""
+        return np.array([self._order(i, min(i, self.config.solver_order)) for i in range(self.num_inference_steps)])
+
+    def _solver_row(self, i: int, order: int) -> np.ndarray:
+        def alpha_sigma(sig):
+            alpha = 1 / ((sig ** 2 + 1) ** 0.5)
+            return alpha, sig * alpha
+
+        s = self.sigmas
+        alpha_t, sigma_t = alpha_sigma(s[i + 1])
+        alpha_s0, sigma_s0 = alpha_sigma(s[i])
+        lambda_t = torch.log(alpha_t) - torch.log(sigma_t)
+        lambda_s0 = torch.log(alpha_s0) - torch.log(sigma_s0)
+        h = lambda_t - lambda_s0
+        b = alpha_t * (torch.exp(-h) - 1.0)
+        row = [float(order), sigma_s0, alpha_s0, sigma_t / sigma_s0, b, 0.0, 0.0, 0.0]
+        if order == 2:
+            alpha_s1, sigma_s1 = alpha_sigma(s[i - 1])
+            lambda_s1 = torch.log(alpha_s1) - torch.log(sigma_s1)
+            r0 = (lambda_s0 - lambda_s1) / h
+            row[5] = 1.0 / r0
+            # the kernel subtracts c*D1: midpoint's "- 0.5*b*D1", heun's "+ alpha_t*((e^-h - 1)/h + 1)*D1"
+            row[6] = 0.5 * b if self.config.solver_type == "midpoint" else -(alpha_t * ((torch.exp(-h) - 1.0) / h + 1.0))
+        return np.array([float(v) for v in row], dtype=np.float32)
+
+    def solver_table(self) -> np.ndarray:
+        """fp32 [n_steps, 8] solver rows {order, sigma_s, alpha_s, a, b, 1/r0, c, 0} (include/diffsensei_hip.h)."""
+        if self.num_inference_steps is None:
+            raise RuntimeError("call set_timesteps first")
+        orders = self.step_orders()
+        return np.stack([self._solver_row(i, int(o)) for i, o in enumerate(orders)])
+
+    def coef_table(self, guidance_scale: float) -> np.ndarray:
+        n = self.num_inference_steps
+        tab = np.zeros((n, 8), dtype=np.float32)
+        tab[:, 0] = self.timesteps_np
+        tab[:, 1] = 1.0
+        tab[:, 6] = 1.0
+        tab[:, 7] = guidance_scale
+        return tab
+
+    # -- stand-alone protocol (one kernel launch per step; the pipeline's fused loop does not go through these)
+    def scale_model_input(self, sample: torch.Tensor, timestep=None) -> torch.Tensor:
+        return sample
+
+    def _index_for_timestep(self, timestep) -> int:
+        """diffusers `index_for_timestep`: the second match when a timestep repeats, the last row when none matches."""
+        idx = np.nonzero(self.timesteps_np == int(round(float(timestep))))[0]
+        if len(idx) == 0:
+            return self.num_inference_steps - 1
+        return int(idx[1] if len(idx) > 1 else idx[0])
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, return_dict: bool = True, **kw):
+        """model_output: the (already CFG-combined) noise prediction, NCHW like `sample`; keeps the previous x0 on the
+        device between calls.  Computes in fp16 like the pipeline's fused loop."""
+        if self.num_inference_steps is None:
+            raise RuntimeError("call set_timesteps first")
+        if self._step_index is None:
+            self._step_index = self._index_for_timestep(timestep)
+        i = self._step_index
+        order = self._order(i, self.lower_order_nums)
+        dev = sample.device
+        solver = torch.from_numpy(self._solver_row(i, order)[None]).to(dev)
+        table = torch.tensor([[0, 1, 0, 0, 0, 0, 1, 1]], dtype=torch.float32, device=dev)
+        ns, c, h, w = sample.shape
+        eps = ops.nchw_to_nhwc(model_output.to(torch.float16).reshape(ns, c, h * w).contiguous())
+        lat = sample.to(torch.float16).contiguous().clone()
+        if self._prev_x0 is None or self._prev_x0.shape != lat.shape or self._prev_x0.device != lat.device:
+            self._prev_x0 = torch.empty_like(lat)
+        scratch = torch.empty((ns, h * w, c), dtype=torch.float16, device=dev)
+        ops.cfg_dpm_step(eps, lat, scratch, table, solver, self._prev_x0, do_cfg=False)
+        self.lower_order_nums = min(self.lower_order_nums + 1, self.config.solver_order)
+        self._step_index = i + 1
+        return (lat,) if not return_dict else {"prev_sample": lat}
+
+
+def _sigma_to_t(sigmas: np.ndarray, log_sigmas: np.ndarray) -> np.ndarray:
+    """diffusers `_sigma_to_t` [3P]: piecewise-linear interpolation of log-sigma back to (fractional) timesteps."""
+    log_sigma = np.log(np.maximum(sigmas, 1e-10))
+    dists = log_sigma - log_sigmas[:, np.newaxis]
+    low_idx = np.cumsum((dists >= 0), axis=0).argmax(axis=0).clip(max=log_sigmas.shape[0] - 2)
+    high_idx = low_idx + 1
+    low, high = log_sigmas[low_idx], log_sigmas[high_idx]
+    w = np.clip((low - log_sigma) / (low - high), 0, 1)
+    return (1 - w) * low_idx + w * high_idx

@@ -290,6 +290,18 @@ int ds_add_time_ids_f16(const void* text_embeds, const void* time_ids, void* out
  * latents: NCHW [ns,4,HW] updated in place; model_in: NHWC [2ns,HW,4].  kind: 0 Euler, 1 DDIM. */
 int ds_cfg_sampler_step_f16(const void* eps, void* latents, void* model_in, const float* table,
                             const int32_t* step_ctr, int ns, int HW, int kind, int do_cfg, void* stream);
+/* DPM-Solver++ (diffusers DPMSolverMultistepScheduler, algorithm_type "dpmsolver++", epsilon prediction, order 1|2):
+ * CFG + the multistep update + the next model input (= the new latents) in one launch, on the same layouts as above.
+ * The per-step table carries {t, 1, 0, 0, 0, 0, 1, guidance}; `solver` (device, fp32, 8 floats per row, the same
+ * step_ctr) carries the update:
+ *   {order, sigma_s, alpha_s, a, b, 1/r0, c, 0}   with alpha = 1/sqrt(1+sigma_ve^2), sigma = sigma_ve*alpha,
+ *   lambda = log(alpha) - log(sigma), h = lambda_t - lambda_s, r0 = (lambda_s - lambda_s1) / h,
+ *   a = sigma_t/sigma_s, b = alpha_t*(exp(-h)-1), c = 0.5*b (midpoint) or -alpha_t*((exp(-h)-1)/h+1) (heun)
+ *   x0 = fp16(fp16(x - fp16(sigma_s*eps)) / alpha_s);  x' = fp16(a*x - fp16(b*x0) [- fp16(c*D1)]) with
+ *   D1 = fp16(fp16(x0 - prev_x0) * (1/r0)), the bracket only on rows with order 2.
+ * prev_x0: NCHW [ns,4,HW] fp16, read by order-2 rows and overwritten with x0 on every row (never read on order 1). */
+int ds_cfg_dpm_step_f16(const void* eps, void* latents, void* model_in, const float* table, const float* solver,
+                        void* prev_x0, const int32_t* step_ctr, int ns, int HW, int do_cfg, void* stream);
 int ds_prepare_model_input_f16(const void* latents, void* model_in, const float* table, const int32_t* step_ctr,
                                int ns, int HW, int do_cfg, void* stream);
 int ds_nhwc_to_nchw_f16(const void* x, void* y, int B, int HW, int C, void* stream);
@@ -390,7 +402,8 @@ enum ds_opcode {
     DS_OP_SKINNY = 9,        /* p: x, w, bias, addend, y                  i: M N K silu_in silu_out */
     DS_OP_TIMESTEP_EMBED = 10, /* p: table, ctr, out                      i: B dim flip               f: freq_shift */
     DS_OP_ADD_TIME_IDS = 11, /* p: text_embeds, time_ids, out             i: B pooled n_ids dim flip  f: freq_shift */
-    DS_OP_SAMPLER_STEP = 12, /* p: eps, latents, model_in, table, ctr     i: ns HW kind do_cfg */
+    DS_OP_SAMPLER_STEP = 12, /* p: eps, latents, model_in, table, ctr, prev_x0, solver (the last two: kind 2 only)
+                                i: ns HW kind (0 Euler, 1 DDIM, 2 DPM-Solver++) do_cfg */
     DS_OP_PREP_INPUT = 13,   /* p: latents, model_in, table, ctr          i: ns HW do_cfg */
     DS_OP_ADVANCE = 14,      /* p: ctr */
     DS_OP_NHWC2NCHW = 15,    /* p: x, y                                   i: B HW C */
