@@ -10,7 +10,7 @@ from .unet_config import UNetMangaConfig, sdxl_config, tiny_config  # noqa: F401
 
 __all__ = ["UNetMangaConfig", "sdxl_config", "tiny_config", "UNetMangaModel", "DiffSenseiPipeline", "Resampler",
            "AttnProcessor2_0", "MaskedIPAttnProcessor2_0", "EulerDiscreteScheduler", "DDIMScheduler",
-           "DPMSolverMultistepScheduler"]
+           "DPMSolverMultistepScheduler", "EulerAncestralDiscreteScheduler"]
 
 
 def __getattr__(name):
@@ -27,7 +27,8 @@ def __getattr__(name):
     if name in ("AttnProcessor2_0", "MaskedIPAttnProcessor2_0"):
         from . import attention_processor
         return getattr(attention_processor, name)
-    if name in ("EulerDiscreteScheduler", "DDIMScheduler", "DPMSolverMultistepScheduler"):
+    if name in ("EulerDiscreteScheduler", "DDIMScheduler", "DPMSolverMultistepScheduler",
+                "EulerAncestralDiscreteScheduler"):
         from . import schedulers
         return getattr(schedulers, name)
     raise AttributeError(name)

@@ -77,6 +77,9 @@ SIGNATURES = {
     "ds_add_time_ids_f16": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp]),
     "ds_cfg_sampler_step_f16": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "ds_cfg_dpm_step_f16": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "ds_cfg_sampler_step_noise_f16": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "ds_philox_u32": (i32, [vp, i32, i32, vp, i32, i32, vp]),
+    "ds_philox_normal_f32": (i32, [vp, i32, i32, vp, i32, i32, vp]),
     "ds_prepare_model_input_f16": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
     "ds_nhwc_to_nchw_f16": (i32, [vp, vp, i32, i32, i32, vp]),
     "ds_nchw_to_nhwc_f16": (i32, [vp, vp, i32, i32, i32, vp]),

@@ -25,7 +25,7 @@ void ds_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* ds_last_error(void) { return g_err; }
-int ds_version(void) { return 101; }
+int ds_version(void) { return 102; }
 
 int ds_device_info(int* cu_count, int* lds_bytes, char* arch_name, int arch_name_len) {
     int dev = 0;
@@ -491,6 +491,24 @@ int ds_cfg_dpm_step_f16(const void* eps, void* latents, void* model_in, const fl
     return ds_launch_sampler_step(p, step_ctr, S(stream));
 }
 
+int ds_cfg_sampler_step_noise_f16(const void* eps, void* latents, void* model_in, const float* table,
+                                  const int64_t* seeds, const int32_t* step_ctr, int ns, int HW, int kind, int do_cfg,
+                                  void* stream) {
+    SamplerStepParams p;
+    p.eps = H(eps); p.latents = HM(latents); p.model_in = HM(model_in); p.coef = table;
+    p.seeds = reinterpret_cast<const long long*>(seeds);
+    p.ns = ns; p.HW = HW; p.kind = kind; p.do_cfg = do_cfg;
+    return ds_launch_sampler_step(p, step_ctr, S(stream));
+}
+
+int ds_philox_u32(const int64_t* seeds, int step, int stream_id, uint32_t* out, int ns, int HW, void* stream) {
+    return ds_launch_philox_u32(reinterpret_cast<const long long*>(seeds), step, stream_id, out, ns, HW, S(stream));
+}
+
+int ds_philox_normal_f32(const int64_t* seeds, int step, int stream_id, float* out, int ns, int HW, void* stream) {
+    return ds_launch_philox_normal(reinterpret_cast<const long long*>(seeds), step, stream_id, out, ns, HW, S(stream));
+}
+
 int ds_prepare_model_input_f16(const void* latents, void* model_in, const float* table, const int32_t* step_ctr,
                                int ns, int HW, int do_cfg, void* stream) {
     return ds_launch_prepare_model_input(H(latents), HM(model_in), table, step_ctr, ns, HW, 4, do_cfg, S(stream));
@@ -581,6 +599,7 @@ static int run_op(const ds_op& o, hipStream_t st) {
             SamplerStepParams s;
             s.eps = H(p[0]); s.latents = HM(p[1]); s.model_in = HM(p[2]); s.coef = reinterpret_cast<const float*>(p[3]);
             s.prev_x0 = HM(p[5]); s.solver = reinterpret_cast<const float*>(p[6]);
+            s.seeds = reinterpret_cast<const long long*>(p[7]);
             s.ns = i[0]; s.HW = i[1]; s.kind = i[2]; s.do_cfg = i[3];
             return ds_launch_sampler_step(s, reinterpret_cast<const int*>(p[4]), st);
         }

@@ -182,11 +182,17 @@ struct SamplerStepParams {
     const float* coef = nullptr;    // per-step scalar table (see elementwise.hip)
     half_t* prev_x0 = nullptr;      // kind 2: NCHW [ns,4,H,W] x0 of the previous step (read, then overwritten)
     const float* solver = nullptr;  // kind 2: per-step solver rows [n_steps,8] (include/diffsensei_hip.h)
+    const long long* seeds = nullptr;  // kind 3: int64 [ns], one Philox key per panel (noise = f(seed, pixel, *ctr))
     int ns = 0, HW = 0, C = 4;
-    int kind = 0;                   // 0 Euler, 1 DDIM, 2 DPM-Solver++ (multistep, order 1|2 per row)
+    int kind = 0;                   // 0 Euler, 1 DDIM, 2 DPM-Solver++ (multistep, order 1|2 per row), 3 Euler Ancestral
     int do_cfg = 1;
 };
 int ds_launch_sampler_step(const SamplerStepParams& p, const int* ctr, hipStream_t stream);
+// Philox4x32-10 keyed per panel, counter (pixel, 0, step, stream_id): raw words [ns,HW,4] / Box-Muller normals [ns,4,HW]
+int ds_launch_philox_u32(const long long* seeds, int step, int stream_id, unsigned* out, int ns, int HW,
+                         hipStream_t stream);
+int ds_launch_philox_normal(const long long* seeds, int step, int stream_id, float* out, int ns, int HW,
+                            hipStream_t stream);
 int ds_launch_prepare_model_input(const half_t* latents, half_t* model_in, const float* table, const int* ctr, int ns,
                                   int HW, int C, int do_cfg, hipStream_t stream);
 int ds_launch_advance_counter(int* ctr, hipStream_t stream);

@@ -219,6 +219,70 @@ __global__ void add_time_ids_kernel(const half_t* text_embeds, const half_t* tim
     }
 }
 
+// ---------------------------------------------------------------- device noise: Philox4x32-10 + Box-Muller
+// Counter-based generator of Salmon et al. (Random123), so a captured step graph draws fresh noise on every replay with
+// no host work between replays.  Key = the panel's 64-bit seed, counter = (pixel in the panel, 0, step, stream): what a
+// panel sees depends on its own seed and the step only, never on its row in the batch.  One call = the four latent
+// channels of one pixel, i.e. the sampler kernel's own work split (include/diffsensei_hip.h, "device noise").
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
+                                              unsigned k1, unsigned out[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+__device__ __forceinline__ void panel_philox(long long seed, int pix, int step, int stream_id, unsigned out[4]) {
+    const unsigned long long s = (unsigned long long)seed;
+    philox4x32_10((unsigned)pix, 0u, (unsigned)step, (unsigned)stream_id, (unsigned)s, (unsigned)(s >> 32), out);
+}
+
+// u = x * 2^-32 + 2^-33 in (0, 1] (the product is exact, so an fma contraction rounds the same); v_sin_f32 / v_cos_f32
+// take revolutions, which is what u1 is.
+__device__ __forceinline__ void box_muller(unsigned a, unsigned b, float& z0, float& z1) {
+    const float u0 = (float)a * 0x1p-32f + 0x1p-33f;
+    const float u1 = (float)b * 0x1p-32f + 0x1p-33f;
+    const float r = sqrtf(-2.0f * __logf(u0));
+    z0 = r * __builtin_amdgcn_cosf(u1);
+    z1 = r * __builtin_amdgcn_sinf(u1);
+}
+
+__device__ __forceinline__ void panel_normals(long long seed, int pix, int step, int stream_id, float z[4]) {
+    unsigned x[4];
+    panel_philox(seed, pix, step, stream_id, x);
+    box_muller(x[0], x[1], z[0], z[1]);
+    box_muller(x[2], x[3], z[2], z[3]);
+}
+
+__global__ __launch_bounds__(256) void philox_u32_kernel(const long long* __restrict__ seeds, int step, int stream_id,
+                                                         unsigned* __restrict__ out, int ns, int HW) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)ns * HW) return;
+    const int n = (int)(i / HW), pix = (int)(i - (long)n * HW);
+    unsigned x[4];
+    panel_philox(seeds[n], pix, step, stream_id, x);
+    *reinterpret_cast<uint4*>(out + i * 4) = make_uint4(x[0], x[1], x[2], x[3]);
+}
+
+__global__ __launch_bounds__(256) void philox_normal_kernel(const long long* __restrict__ seeds, int step, int stream_id,
+                                                            float* __restrict__ out, int ns, int HW) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)ns * HW) return;
+    const int n = (int)(i / HW), pix = (int)(i - (long)n * HW);
+    float z[4];
+    panel_normals(seeds[n], pix, step, stream_id, z);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) out[((long)n * 4 + c) * HW + pix] = z[c];
+}
+
 // ---------------------------------------------------------------- CFG + scheduler step + next model input
 // One thread per (sample, pixel): 4 latent channels.  All arithmetic mirrors the reference's rounding points:
 // CFG in fp16 (noise_pred tensors are fp16), Euler update in fp32, latents stored fp16 between steps.
@@ -226,6 +290,9 @@ __global__ void add_time_ids_kernel(const half_t* text_embeds, const half_t* tim
 // scalars: x0 in fp16 (convert_model_output sees the fp16 sample), every scalar*fp16-tensor product in fp16, the
 // update itself in fp32 on the upcast sample (fp32 intermediates under the library's fast-math flags, like the
 // Euler / DDIM branches).  Its x0 is kept in `prev_x0` for the next row's second-order term.
+// Euler Ancestral (kind 3) is diffusers' EulerAncestralDiscreteScheduler [3P]: the Euler update towards sigma_down in
+// fp32, then sigma_up * noise with the noise drawn in the model output's dtype (fp16) and the product an fp16 tensor.
+// The noise is this thread's own Philox draw for (seed[n], pixel, *ctr): nothing is read for it but the seed.
 __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p, const int* ctr) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     const long total = (long)p.ns * p.HW;
@@ -244,6 +311,8 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p, 
             e[c] = (half_t)((float)eu[c] + (float)gd);
         }
     }
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if (p.kind == 3) panel_normals(p.seeds[n], pix, ctr ? *ctr : 0, 0, z);   // stream 0 = sampler-step noise
     h4 xin;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -259,6 +328,12 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p, 
         } else if (p.kind == 1) {  // DDIM eta=0: k0 = sqrt(a_t), k1 = sqrt(1-a_t), k2 = sqrt(a_prev), k3 = sqrt(1-a_prev)
             const float pred_x0 = (x - cf[3] * ef) / cf[2];
             xn = cf[4] * pred_x0 + cf[5] * ef;
+        } else if (p.kind == 3) {  // Euler Ancestral: k0 = sigma, k1 = sigma_down, k2 = sigma_up (both 0 on the last row)
+            const float s = cf[2];
+            const float pred_x0 = x - s * ef;
+            const float deriv = (x - pred_x0) / s;
+            xn = x + deriv * (cf[3] - s);
+            xn = xn + (float)(half_t)(cf[4] * (float)(half_t)z[c]);
         } else {                   // DPM-Solver++: sv = {order, sigma_s, alpha_s, a, b, 1/r0, c, -}
             half_t* pp = p.prev_x0 + ((long)n * 4 + c) * p.HW + pix;
             const half_t x0 = (half_t)((float)(half_t)(x - (float)(half_t)(sv[1] * ef)) / sv[2]);
@@ -445,10 +520,32 @@ int ds_launch_add_time_ids(const half_t* text_embeds, const half_t* time_ids, ha
 int ds_launch_sampler_step(const SamplerStepParams& p, const int* ctr, hipStream_t stream) {
     DS_REQUIRE(p.C == 4, "sampler_step: latent channels must be 4");
     DS_REQUIRE(p.ns > 0 && p.HW > 0 && p.coef, "sampler_step: bad arguments");
-    DS_REQUIRE(p.kind >= 0 && p.kind <= 2, "sampler_step: kind must be 0 (Euler), 1 (DDIM) or 2 (DPM-Solver++)");
+    DS_REQUIRE(p.kind >= 0 && p.kind <= 3,
+               "sampler_step: kind must be 0 (Euler), 1 (DDIM), 2 (DPM-Solver++) or 3 (Euler Ancestral)");
     DS_REQUIRE(p.kind != 2 || (p.prev_x0 && p.solver), "sampler_step: kind 2 needs prev_x0 and the solver rows");
+    DS_REQUIRE(p.kind != 3 || p.seeds, "sampler_step: kind 3 needs the per-panel seeds");
     const long total = (long)p.ns * p.HW;
     hipLaunchKernelGGL(sampler_step_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p, ctr);
+    DS_LAUNCH_CHECK();
+    return 0;
+}
+
+int ds_launch_philox_u32(const long long* seeds, int step, int stream_id, unsigned* out, int ns, int HW,
+                         hipStream_t stream) {
+    DS_REQUIRE(seeds && out && ns > 0 && HW > 0 && step >= 0 && stream_id >= 0, "philox_u32: bad arguments");
+    const long total = (long)ns * HW;
+    hipLaunchKernelGGL(philox_u32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, seeds, step,
+                       stream_id, out, ns, HW);
+    DS_LAUNCH_CHECK();
+    return 0;
+}
+
+int ds_launch_philox_normal(const long long* seeds, int step, int stream_id, float* out, int ns, int HW,
+                            hipStream_t stream) {
+    DS_REQUIRE(seeds && out && ns > 0 && HW > 0 && step >= 0 && stream_id >= 0, "philox_normal: bad arguments");
+    const long total = (long)ns * HW;
+    hipLaunchKernelGGL(philox_normal_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, seeds, step,
+                       stream_id, out, ns, HW);
     DS_LAUNCH_CHECK();
     return 0;
 }

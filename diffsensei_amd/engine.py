@@ -750,6 +750,11 @@ class UNetEngine:
                 self.solver = self._alloc((self.table.shape[0], 8), torch.float32)
                 self.solver.zero_()
             dpm = (self.prev_x0, self.solver)
+        if kind == 3:  # Euler Ancestral: one Philox seed per panel, in the op's next free pointer slot (p[7])
+            if getattr(self, "noise_seeds", None) is None or self.noise_seeds.shape[0] != ns:
+                self.noise_seeds = self._alloc((ns,), torch.int64)
+                self.noise_seeds.zero_()
+            dpm = (None, None, self.noise_seeds)
         step_ops = list(self.forward_ops) + [
             make_op("SAMPLER_STEP", i=(ns, HW, kind, int(do_cfg)),
                     p=(self.eps, self.latents, self.x_in, self.table, self.ctr) + dpm),
@@ -758,15 +763,24 @@ class UNetEngine:
         self.step_plan = Plan(step_ops, self.keep)
         self._sampler_key = key
 
-    def load_schedule(self, table_rows: Tensor, solver_rows: Optional[Tensor] = None):
-        """table_rows: fp32 [n_steps, 8]; solver_rows: fp32 [n_steps, 8], the DPM-Solver++ rows (kind 2 only)
-        (see include/diffsensei_hip.h); resets the device step counter."""
+    def load_schedule(self, table_rows: Tensor, solver_rows: Optional[Tensor] = None, noise_seeds=None):
+        """table_rows: fp32 [n_steps, 8]; solver_rows: fp32 [n_steps, 8], the DPM-Solver++ rows (kind 2 only);
+        noise_seeds: one non-negative int64 per panel, the Euler Ancestral Philox keys (kind 3 only)
+        (see include/diffsensei_hip.h); resets the device step counter.  The seed buffer is static: a captured step
+        graph replays with the new seeds and, through the device step counter, new noise every step."""
         n = table_rows.shape[0]
         if n > self.table.shape[0]:
             raise ValueError("too many steps for the scalar table")
         kind = getattr(self, "_sampler_key", (None, None))[1]
         if (solver_rows is not None) != (kind == 2):
             raise ValueError(f"solver rows are given exactly for a DPM-Solver++ sampler (built kind: {kind})")
+        if (noise_seeds is not None) != (kind == 3):
+            raise ValueError(f"noise seeds are given exactly for an Euler Ancestral sampler (built kind: {kind})")
+        if noise_seeds is not None:
+            seeds = torch.as_tensor(noise_seeds, dtype=torch.int64).reshape(-1)
+            if seeds.shape != self.noise_seeds.shape:
+                raise ValueError(f"{seeds.shape[0]} noise seeds for {self.noise_seeds.shape[0]} panels")
+            self.noise_seeds.copy_(seeds.to(self.dev))
         self.table[:n].copy_(table_rows.to(self.dev, torch.float32))
         if solver_rows is not None:
             if tuple(solver_rows.shape) != (n, 8):

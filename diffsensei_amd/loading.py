@@ -70,10 +70,12 @@ class _Loaded:
 
 
 def load_scheduler(folder: str):
-    from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler
+    from .schedulers import (DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,
+                             EulerDiscreteScheduler)
     cfg = read_json(os.path.join(folder, "scheduler_config.json"))
     classes = {"EulerDiscreteScheduler": EulerDiscreteScheduler, "DDIMScheduler": DDIMScheduler,
-               "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler}
+               "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler,
+               "EulerAncestralDiscreteScheduler": EulerAncestralDiscreteScheduler}
     name = cfg.get("_class_name", "EulerDiscreteScheduler")
     if name not in classes:
         raise NotImplementedError(f"scheduler {name}: the MI355X sampler kernel implements {sorted(classes)}")

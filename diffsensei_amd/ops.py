@@ -381,6 +381,45 @@ def cfg_dpm_step(eps: Tensor, latents: Tensor, model_in: Tensor, table: Tensor, 
                                           _p(ctr), ns, HW, int(do_cfg), _stream()), "ds_cfg_dpm_step_f16")
 
 
+def _chk_seeds(seeds: Optional[Tensor], ns: int) -> None:
+    _chk(seeds, dtype=torch.int64)
+    if seeds is not None and tuple(seeds.shape) != (ns,):
+        raise ValueError(f"seeds {tuple(seeds.shape)}: one int64 per panel, ({ns},), is needed")
+
+
+def cfg_sampler_step_noise(eps: Tensor, latents: Tensor, model_in: Tensor, table: Tensor, seeds: Optional[Tensor],
+                           kind: int, do_cfg: bool = True, ctr: Optional[Tensor] = None) -> None:
+    """`cfg_sampler_step` with the per-panel Philox seeds (int64 [ns]) that kind 3, Euler Ancestral, draws its noise
+    from: the noise of panel n at this launch is a function of (seeds[n], pixel, *ctr) only."""
+    _chk(eps, latents, model_in)
+    _chk(table, dtype=torch.float32)
+    ns = latents.shape[0]
+    HW = latents.shape[2] * latents.shape[3]
+    _chk_seeds(seeds, ns)
+    check(_lib.load().ds_cfg_sampler_step_noise_f16(_p(eps), _p(latents), _p(model_in), _p(table), _p(seeds), _p(ctr),
+                                                    ns, HW, kind, int(do_cfg), _stream()),
+          "ds_cfg_sampler_step_noise_f16")
+
+
+def philox_u32(seeds: Tensor, step: int, HW: int, stream_id: int = 0) -> Tensor:
+    """Raw Philox4x32-10 words, int32 [ns,HW,4] holding the uint32 bit patterns (include/diffsensei_hip.h)."""
+    ns = seeds.shape[0]
+    _chk_seeds(seeds, ns)
+    out = torch.empty((ns, HW, 4), dtype=torch.int32, device=seeds.device)
+    check(_lib.load().ds_philox_u32(_p(seeds), int(step), int(stream_id), _p(out), ns, HW, _stream()), "ds_philox_u32")
+    return out
+
+
+def philox_normal(seeds: Tensor, step: int, HW: int, stream_id: int = 0) -> Tensor:
+    """The sampler's noise on its own: fp32 [ns,4,HW] standard normals for (seeds[n], pixel, step, stream_id)."""
+    ns = seeds.shape[0]
+    _chk_seeds(seeds, ns)
+    out = torch.empty((ns, 4, HW), dtype=torch.float32, device=seeds.device)
+    check(_lib.load().ds_philox_normal_f32(_p(seeds), int(step), int(stream_id), _p(out), ns, HW, _stream()),
+          "ds_philox_normal_f32")
+    return out
+
+
 def prepare_model_input(latents: Tensor, model_in: Tensor, table: Tensor, do_cfg: bool = True,
                         ctr: Optional[Tensor] = None) -> None:
     _chk(latents, model_in)

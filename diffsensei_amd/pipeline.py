@@ -24,6 +24,7 @@ from typing import Any, List, Optional, Sequence, Tuple, Union
 import torch
 
 from .encoders import ClipTextEngine, ClipVisionEngine, ViTMAEEngine
+from .schedulers import draw_noise_seeds
 from .unet import UNetMangaModel, dialog_pixel_boxes
 from .vae import VaeDecoderEngine
 
@@ -312,13 +313,18 @@ class DiffSenseiPipeline:
                  latents: Optional[Tensor] = None, prompt_embeds: Optional[Tensor] = None,
                  negative_prompt_embeds: Optional[Tensor] = None, pooled_prompt_embeds: Optional[Tensor] = None,
                  negative_pooled_prompt_embeds: Optional[Tensor] = None, output_type: str = "pil",
-                 callback_on_step_end=None, callback_on_step_end_tensor_inputs: Sequence[str] = ("latents",)):
+                 callback_on_step_end=None, callback_on_step_end_tensor_inputs: Sequence[str] = ("latents",),
+                 noise_seeds: Optional[Sequence[int]] = None):
         """`callback_on_step_end(pipe, step_index, timestep, {"latents": device tensor}) -> dict | None` is diffusers'
         SDXL-pipeline hook [3P]; together with `pipe._interrupt = True` it is the reference's early exit: the loop
         `continue`s over the remaining steps (reference :314-315) and the call still decodes and post-processes.  Latents
         may be edited in place or returned (`{"latents": new}`), as in diffusers; `latents` is the only tensor the launch
         plan can hand out per step, so other `callback_on_step_end_tensor_inputs` are refused like diffusers refuses unknown
-        names."""
+        names.
+
+        `noise_seeds` (stochastic samplers only, i.e. `EulerAncestralDiscreteScheduler`): `num_samples` non-negative
+        int64 seeds, one per panel, that the step kernel draws its noise from; by default they are drawn from `generator`
+        after the initial latents (`schedulers.draw_noise_seeds`).  The seeds used are in `last_run_info["noise_seeds"]`."""
         bad = [k for k in callback_on_step_end_tensor_inputs if k != "latents"]
         if bad:
             raise ValueError(f"`callback_on_step_end_tensor_inputs` has to be in ['latents'], but found {bad}")
@@ -327,7 +333,7 @@ class DiffSenseiPipeline:
                                   negative_prompt_2, num_samples, generator, original_size, crops_coords_top_left,
                                   target_size, ip_images, ip_image_embeds, ip_bbox, ip_scale, dialog_bbox, latents,
                                   prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds,
-                                  negative_pooled_prompt_embeds)
+                                  negative_pooled_prompt_embeds, noise_seeds)
         out_latents = self._denoise([cond], num_inference_steps, guidance_scale, ip_scale, callback_on_step_end)
         return StableDiffusionXLPipelineOutput(images=self._postprocess(out_latents, output_type))
 
@@ -335,7 +341,7 @@ class DiffSenseiPipeline:
     def _conditioning(self, prompt, prompt_2, height, width, num_inference_steps, guidance_scale, negative_prompt,
                       negative_prompt_2, num_samples, generator, original_size, crops_coords_top_left, target_size,
                       ip_images, ip_image_embeds, ip_bbox, ip_scale, dialog_bbox, latents, prompt_embeds,
-                      negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds):
+                      negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, noise_seeds=None):
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         original_size = original_size or (height, width)
@@ -367,12 +373,21 @@ class DiffSenseiPipeline:
         self.scheduler.set_timesteps(num_inference_steps, device=device)
         lat = self.prepare_latents(num_samples, self.unet.config.in_channels, height, width, torch.float16, device,
                                    generator, latents)
+        # a stochastic sampler's per-panel Philox seeds, drawn AFTER the initial latents: a deterministic scheduler
+        # consumes the generator exactly as before, and a given generator starts Euler Ancestral from Euler's latents
+        seeds = None
+        if getattr(self.scheduler, "stochastic", False):
+            seeds = [int(v) for v in noise_seeds] if noise_seeds is not None else draw_noise_seeds(num_samples, generator)
+            if len(seeds) != num_samples or any(v < 0 or v >= 2 ** 63 for v in seeds):
+                raise ValueError(f"`noise_seeds`: {num_samples} integers in [0, 2**63) are needed, got {seeds}")
+        elif noise_seeds is not None:
+            raise ValueError(f"`noise_seeds` given, but {type(self.scheduler).__name__} draws no noise")
         neg_img, img, neg_bbox, bbox = self.prepare_ip_image_embeds(ip_images, ip_image_embeds, list(ip_bbox), num_samples)
         add_time_ids = torch.tensor([list(original_size) + list(crops_coords_top_left) + list(target_size)],
                                     dtype=torch.float16, device=device).repeat(num_samples, 1)
         neg_dialog, dialog = self.prepare_dialog_bbox(list(dialog_bbox), num_samples)
         to = lambda t: t.to(device)
-        return {"n": num_samples, "lat": lat, "time_ids": add_time_ids,
+        return {"n": num_samples, "lat": lat, "time_ids": add_time_ids, "noise_seeds": seeds,
                 "pos": (to(prompt_embeds), to(pooled_prompt_embeds), to(img), to(bbox), to(dialog)),
                 "neg": (to(negative_prompt_embeds), to(negative_pooled_prompt_embeds), to(neg_img), to(neg_bbox),
                         to(neg_dialog))}
@@ -411,8 +426,10 @@ class DiffSenseiPipeline:
         eng.build_sampler(num_samples, self.scheduler.kind, do_cfg)
         eng.set_request(enc, add_text_embeds, add_time_ids, bbox, dialog_pixel_boxes(dialog, H, W), float(ip_scale))
         solver = self.scheduler.solver_table()             # DPM-Solver++ rows; None for Euler / DDIM
+        # the panels' own seeds, in batch order: a panel's noise does not depend on the requests batched beside it
+        seeds = [v for c in conds for v in c["noise_seeds"]] if getattr(self.scheduler, "stochastic", False) else None
         eng.load_schedule(torch.from_numpy(self.scheduler.coef_table(float(guidance_scale))),
-                          None if solver is None else torch.from_numpy(solver))
+                          None if solver is None else torch.from_numpy(solver), seeds)
         eng.latents.copy_(lat)
         if self._stream is None:
             self._stream = torch.cuda.Stream(device=device)
@@ -451,7 +468,8 @@ class DiffSenseiPipeline:
                 if callback_on_step_end is not None:              # launched, not synchronised: the hook sees device tensors
                     hook(i)
         torch.cuda.current_stream(device).wait_stream(st)
-        self.last_run_info = {"graph": graph, "ops_per_step": eng.step_plan.n, "batch": B, "latent_hw": (H, W)}
+        self.last_run_info = {"graph": graph, "ops_per_step": eng.step_plan.n, "batch": B, "latent_hw": (H, W),
+                              "noise_seeds": seeds}
         return eng.latents.clone()
 
     # ---- reference :339-367: VAE decode + image_processor.postprocess
@@ -542,12 +560,12 @@ class DiffSenseiPipeline:
         names = ("prompt", "prompt_2", "height", "width", "num_inference_steps", "guidance_scale", "negative_prompt",
                  "negative_prompt_2", "num_samples", "generator", "original_size", "crops_coords_top_left", "target_size",
                  "ip_images", "ip_image_embeds", "ip_bbox", "ip_scale", "dialog_bbox", "latents", "prompt_embeds",
-                 "negative_prompt_embeds", "pooled_prompt_embeds", "negative_pooled_prompt_embeds")
+                 "negative_prompt_embeds", "pooled_prompt_embeds", "negative_pooled_prompt_embeds", "noise_seeds")
         defaults = dict(prompt_2=None, height=None, width=None, num_inference_steps=40, guidance_scale=5.0,
                         negative_prompt=None, negative_prompt_2=None, num_samples=1, generator=None, original_size=None,
                         crops_coords_top_left=(0, 0), target_size=None, ip_images=[], ip_image_embeds=None, ip_bbox=[],
                         ip_scale=1.0, dialog_bbox=[], latents=None, prompt_embeds=None, negative_prompt_embeds=None,
-                        pooled_prompt_embeds=None, negative_pooled_prompt_embeds=None)
+                        pooled_prompt_embeds=None, negative_pooled_prompt_embeds=None, noise_seeds=None)
         conds = []
         for r in requests:
             unknown = set(r) - set(names)

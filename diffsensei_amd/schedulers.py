@@ -9,6 +9,9 @@ indexes with a device-side step counter — the reference issues 5+ elementwise 
 
 Every class has diffusers' `.config` and `from_config(config, **overrides)`, so the usual scheduler swap
 `pipe.scheduler = DPMSolverMultistepScheduler.from_config(pipe.scheduler.config, use_karras_sigmas=True)` works.
+
+`EulerAncestralDiscreteScheduler` is the one stochastic sampler: its per-step noise is drawn inside the step kernel
+(`ds_cfg_sampler_step_noise_f16`) from one int64 seed per panel, `draw_noise_seeds`.
 """
 from __future__ import annotations
 
@@ -20,7 +23,7 @@ import torch
 
 from . import ops
 
-KIND_EULER, KIND_DDIM, KIND_DPM = 0, 1, 2
+KIND_EULER, KIND_DDIM, KIND_DPM, KIND_EULER_ANCESTRAL = 0, 1, 2, 3
 
 
 class _Config(dict):
@@ -360,6 +363,164 @@ class DPMSolverMultistepScheduler(_ConfigMixin):
         self.lower_order_nums = min(self.lower_order_nums + 1, self.config.solver_order)
         self._step_index = i + 1
         return (lat,) if not return_dict else {"prev_sample": lat}
+
+
+def draw_noise_seeds(num_samples: int, generator=None) -> list:
+    """One non-negative int64 Philox seed per panel for a stochastic sampler: `torch.randint(0, 2**63 - 1, (n,),
+    generator=generator)` on the generator's device for one generator, one draw from each of a list of generators (a
+    panel's seed then depends on its own generator only), the global torch generator when `generator` is None."""
+    hi = 2 ** 63 - 1
+    if isinstance(generator, (list, tuple)):
+        if len(generator) != num_samples:
+            raise ValueError(f"{len(generator)} generators for {num_samples} samples")
+        return [int(torch.randint(0, hi, (1,), generator=g, device=g.device).item()) for g in generator]
+    if generator is None:
+        return [int(v) for v in torch.randint(0, hi, (num_samples,)).tolist()]
+    return [int(v) for v in torch.randint(0, hi, (num_samples,), generator=generator, device=generator.device).tolist()]
+
+
+class EulerAncestralDiscreteScheduler(_ConfigMixin):
+    """diffusers EulerAncestralDiscreteScheduler [3P] ("Euler a"), epsilon prediction: an Euler step from sigma_from down
+    to sigma_down, then fresh noise of std sigma_up, with sigma_up^2 + sigma_down^2 = sigma_to^2.
+
+    Per step the engine reads the table row {t, c_in_div, sigma, sigma_down, sigma_up, 0, c_in_div_next, guidance}; the
+    noise is drawn inside the step kernel from a Philox counter keyed by one int64 seed per panel and indexed by the
+    device step counter (include/diffsensei_hip.h, "device noise"), so a captured step graph needs no host work between
+    replays and a panel's noise does not depend on the batch it runs in.  Scalars are 0-dim fp32 torch values computed
+    in diffusers' order; the last row (sigma_to = 0) has sigma_up = sigma_down = 0."""
+    kind = KIND_EULER_ANCESTRAL
+    order = 1
+    stochastic = True   # the pipeline draws `noise_seeds` for such a scheduler (after the initial latents)
+    # diffusers' constructor defaults for this class (linear betas: NOT the SDXL schedule, so a bare config is refused)
+    _DEFAULTS = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
+                     trained_betas=None, prediction_type="epsilon", timestep_spacing="linspace", steps_offset=0,
+                     rescale_betas_zero_snr=False)
+    # keys whose other values change the schedule or the update rule: only what the device kernel implements is accepted
+    _SUPPORTED = {"beta_schedule": ("scaled_linear",), "trained_betas": (None,), "prediction_type": ("epsilon",),
+                  "timestep_spacing": ("leading", "linspace", "trailing"), "rescale_betas_zero_snr": (False,)}
+
+    def __init__(self, **kwargs):
+        cfg = _Config(self._DEFAULTS)
+        cfg.update({k: v for k, v in kwargs.items() if k in self._DEFAULTS})   # other keys: not this class's (ignored)
+        for key, ok in self._SUPPORTED.items():
+            if isinstance(cfg[key], (list, tuple)) or cfg[key] not in ok:
+                raise NotImplementedError(f"scheduler config {key}={cfg[key]!r}: the MI355X Euler Ancestral kernel "
+                                          f"implements {key} in {ok} only")
+        self.config = cfg
+        self.T = int(cfg["num_train_timesteps"])
+        self.alphas_cumprod = _alphas_cumprod(self.T, cfg["beta_start"], cfg["beta_end"])
+        ac = self.alphas_cumprod.numpy()
+        self.sigmas = torch.from_numpy(np.concatenate([np.array(((1 - ac) / ac) ** 0.5)[::-1], [0.0]]).astype(np.float32))
+        self.timesteps = None
+        self.num_inference_steps = None
+        self._step_index = 0
+        self._seeds = None
+        self._dev = None
+
+    @classmethod
+    def _config_keys(cls):
+        return tuple(cls._DEFAULTS)
+
+    @property
+    def init_noise_sigma(self) -> float:
+        smax = self.sigmas.max()
+        if self.config.timestep_spacing in ("linspace", "trailing"):
+            return float(smax)
+        return float((smax ** 2 + 1) ** 0.5)
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        cfg, n, T = self.config, int(num_inference_steps), self.T
+        if cfg.timestep_spacing == "linspace":
+            ts = np.linspace(0, T - 1, n, dtype=np.float32)[::-1].copy()
+        elif cfg.timestep_spacing == "leading":
+            step_ratio = T // n
+            ts = (np.arange(0, n) * step_ratio).round()[::-1].copy().astype(np.float32)
+            ts += cfg.steps_offset
+        else:  # trailing
+            step_ratio = T / n
+            ts = (np.arange(T, 0, -step_ratio)).round().copy().astype(np.float32)
+            ts -= 1
+        ac = self.alphas_cumprod.numpy()
+        sig = np.array(((1 - ac) / ac) ** 0.5)
+        sig = np.interp(ts, np.arange(0, len(sig)), sig)
+        self.sigmas = torch.from_numpy(np.concatenate([sig, [0.0]]).astype(np.float32))
+        self.timesteps_np = ts
+        self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
+        self.num_inference_steps = n
+        self._step_index = 0
+        self._seeds = None      # the stand-alone `step` draws new seeds for a new run
+        self._dev = None
+
+    def sigma_up_down(self, i: int):
+        """(sigma_up, sigma_down) of row i, 0-dim fp32 tensors in diffusers' order of operations."""
+        sigma_from, sigma_to = self.sigmas[i], self.sigmas[i + 1]
+        sigma_up = (sigma_to ** 2 * (sigma_from ** 2 - sigma_to ** 2) / sigma_from ** 2) ** 0.5
+        sigma_down = (sigma_to ** 2 - sigma_up ** 2) ** 0.5
+        return sigma_up, sigma_down
+
+    def coef_table(self, guidance_scale: float) -> np.ndarray:
+        if self.num_inference_steps is None:
+            raise RuntimeError("call set_timesteps first")
+        n = self.num_inference_steps
+        tab = np.zeros((n, 8), dtype=np.float32)
+        s = self.sigmas.numpy()
+        div = ((s ** 2 + 1) ** 0.5).astype(np.float32)   # fp32 like the 0-dim sigma tensor arithmetic in diffusers
+        tab[:, 0] = self.timesteps_np
+        tab[:, 1] = div[:n]
+        tab[:, 2] = s[:n]
+        for i in range(n):
+            up, down = self.sigma_up_down(i)
+            tab[i, 3], tab[i, 4] = float(down), float(up)
+        tab[:, 6] = div[1:n + 1]
+        tab[:, 7] = guidance_scale
+        return tab
+
+    def solver_table(self) -> Optional[np.ndarray]:
+        return None
+
+    # -- stand-alone protocol (one kernel launch each; the pipeline's fused loop does not go through these)
+    def _index_of(self, t) -> int:
+        idx = np.nonzero(np.isclose(np.asarray(self.timesteps_np, dtype=np.float64), float(t)))[0]
+        return int(idx[0]) if len(idx) else self._step_index
+
+    def scale_model_input(self, sample: torch.Tensor, timestep) -> torch.Tensor:
+        i = self._index_of(timestep)
+        div = float(self.coef_table(1.0)[i, 1])
+        ns, c, h, w = sample.shape
+        table = torch.tensor([[0, div, 0, 0, 0, 0, 1, 1]], dtype=torch.float32, device=sample.device)
+        tmp = torch.empty((ns, h * w, c), dtype=torch.float16, device=sample.device)
+        ops.prepare_model_input(sample.contiguous(), tmp, table, do_cfg=False)
+        return ops.nhwc_to_nchw(tmp).reshape(ns, c, h, w)
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, generator=None,
+             return_dict: bool = True, **kw):
+        """model_output: the (already CFG-combined) noise prediction, NCHW like `sample`.  The per-panel seeds are drawn
+        once per run (`draw_noise_seeds(batch, generator)` at the first step after `set_timesteps`, kept in
+        `noise_seeds`); the noise of step i is the device's Philox draw for (seed, pixel, i)."""
+        if self.num_inference_steps is None:
+            raise RuntimeError("call set_timesteps first")
+        i = self._index_of(timestep)
+        ns, c, h, w = sample.shape
+        dev = sample.device
+        if self._seeds is None or len(self._seeds) != ns:
+            self._seeds = draw_noise_seeds(ns, generator)
+            self._dev = None
+        if self._dev is None or self._dev[0].device != dev:
+            self._dev = (torch.from_numpy(self.coef_table(1.0)).to(dev),
+                         torch.tensor(self._seeds, dtype=torch.int64, device=dev))
+        table, seeds = self._dev
+        ctr = torch.tensor([i], dtype=torch.int32, device=dev)
+        eps = ops.nchw_to_nhwc(model_output.to(torch.float16).reshape(ns, c, h * w).contiguous())
+        lat = sample.to(torch.float16).contiguous().clone()
+        scratch = torch.empty((ns, h * w, c), dtype=torch.float16, device=dev)
+        ops.cfg_sampler_step_noise(eps, lat, scratch, table, seeds, self.kind, do_cfg=False, ctr=ctr)
+        self._step_index = i + 1
+        return (lat,) if not return_dict else {"prev_sample": lat}
+
+    @property
+    def noise_seeds(self):
+        """The seeds of the current stand-alone run (None before its first `step`)."""
+        return None if self._seeds is None else list(self._seeds)
 
 
 def _sigma_to_t(sigmas: np.ndarray, log_sigmas: np.ndarray) -> np.ndarray:

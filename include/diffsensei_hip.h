@@ -287,7 +287,8 @@ int ds_add_time_ids_f16(const void* text_embeds, const void* time_ids, void* out
                         int dim, int flip_sin_to_cos, float freq_shift, void* stream);
 /* classifier-free guidance + scheduler.step + next scale_model_input in one launch
  * (reference src/pipelines/pipeline_diffsensei.py:315-317, :333-337).  eps: NHWC [2ns,HW,4] (uncond first);
- * latents: NCHW [ns,4,HW] updated in place; model_in: NHWC [2ns,HW,4].  kind: 0 Euler, 1 DDIM. */
+ * latents: NCHW [ns,4,HW] updated in place; model_in: NHWC [2ns,HW,4].  kind: 0 Euler, 1 DDIM (2 and 3 need more
+ * arguments: ds_cfg_dpm_step_f16, ds_cfg_sampler_step_noise_f16). */
 int ds_cfg_sampler_step_f16(const void* eps, void* latents, void* model_in, const float* table,
                             const int32_t* step_ctr, int ns, int HW, int kind, int do_cfg, void* stream);
 /* DPM-Solver++ (diffusers DPMSolverMultistepScheduler, algorithm_type "dpmsolver++", epsilon prediction, order 1|2):
@@ -302,6 +303,27 @@ int ds_cfg_sampler_step_f16(const void* eps, void* latents, void* model_in, cons
  * prev_x0: NCHW [ns,4,HW] fp16, read by order-2 rows and overwritten with x0 on every row (never read on order 1). */
 int ds_cfg_dpm_step_f16(const void* eps, void* latents, void* model_in, const float* table, const float* solver,
                         void* prev_x0, const int32_t* step_ctr, int ns, int HW, int do_cfg, void* stream);
+/* Device noise: Philox4x32-10 (Salmon et al., Random123; multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants
+ * 0x9E3779B9 / 0xBB67AE85) + Box-Muller, keyed per panel so that what a panel sees depends on its own seed and the step
+ * only - not on its row in the batch, the rows beside it or the rank it runs on:
+ *   key     = (seed & 0xffffffff, seed >> 32)            seeds: device int64 [ns], one per panel
+ *   counter = (pixel, 0, step, stream_id)                pixel = 0 .. HW-1 inside the panel
+ *   x0..x3  = the four latent channels of that pixel;  u_k = x_k * 2^-32 + 2^-33 in fp32 (never 0)
+ *   channels 0,1 = sqrt(-2 ln u0) * {cos, sin}(2 pi u1);  channels 2,3 the same from (u2, u3)
+ * stream_id 0 = sampler-step noise; 1.. are reserved (initial latents, other samplers) and unused so far.
+ * ds_philox_u32: the raw words, uint32 [ns,HW,4].  ds_philox_normal_f32: the normals, fp32 NCHW [ns,4,HW]. */
+int ds_philox_u32(const int64_t* seeds, int step, int stream_id, uint32_t* out, int ns, int HW, void* stream);
+int ds_philox_normal_f32(const int64_t* seeds, int step, int stream_id, float* out, int ns, int HW, void* stream);
+/* ds_cfg_sampler_step_f16 with a noise source: kind 0 / 1 as above (seeds unused, may be NULL) and
+ * kind 3 = Euler Ancestral (diffusers EulerAncestralDiscreteScheduler, epsilon prediction), table row
+ *   {t, c_in_div, sigma, sigma_down, sigma_up, 0, c_in_div_next, guidance}
+ *   x' = fp16( x + ((x - (x - sigma*eps)) / sigma) * (sigma_down - sigma) + fp16(sigma_up * fp16(z)) ),  x upcast to fp32,
+ *   z = the normals above for (seeds[n], pixel, step = *step_ctr (0 when NULL), stream_id 0).
+ * The last row has sigma_down = sigma_up = 0: no noise.  kind 3 needs `seeds`; ds_cfg_sampler_step_f16 has none to give
+ * and refuses it. */
+int ds_cfg_sampler_step_noise_f16(const void* eps, void* latents, void* model_in, const float* table,
+                                  const int64_t* seeds, const int32_t* step_ctr, int ns, int HW, int kind, int do_cfg,
+                                  void* stream);
 int ds_prepare_model_input_f16(const void* latents, void* model_in, const float* table, const int32_t* step_ctr,
                                int ns, int HW, int do_cfg, void* stream);
 int ds_nhwc_to_nchw_f16(const void* x, void* y, int B, int HW, int C, void* stream);
@@ -402,8 +424,9 @@ enum ds_opcode {
     DS_OP_SKINNY = 9,        /* p: x, w, bias, addend, y                  i: M N K silu_in silu_out */
     DS_OP_TIMESTEP_EMBED = 10, /* p: table, ctr, out                      i: B dim flip               f: freq_shift */
     DS_OP_ADD_TIME_IDS = 11, /* p: text_embeds, time_ids, out             i: B pooled n_ids dim flip  f: freq_shift */
-    DS_OP_SAMPLER_STEP = 12, /* p: eps, latents, model_in, table, ctr, prev_x0, solver (the last two: kind 2 only)
-                                i: ns HW kind (0 Euler, 1 DDIM, 2 DPM-Solver++) do_cfg */
+    DS_OP_SAMPLER_STEP = 12, /* p: eps, latents, model_in, table, ctr, prev_x0, solver (these two: kind 2 only),
+                                   seeds (kind 3 only)
+                                i: ns HW kind (0 Euler, 1 DDIM, 2 DPM-Solver++, 3 Euler Ancestral) do_cfg */
     DS_OP_PREP_INPUT = 13,   /* p: latents, model_in, table, ctr          i: ns HW do_cfg */
     DS_OP_ADVANCE = 14,      /* p: ctr */
     DS_OP_NHWC2NCHW = 15,    /* p: x, y                                   i: B HW C */
