@@ -25,7 +25,7 @@ void ds_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* ds_last_error(void) { return g_err; }
-int ds_version(void) { return 102; }
+int ds_version(void) { return 103; }
 
 int ds_device_info(int* cu_count, int* lds_bytes, char* arch_name, int arch_name_len) {
     int dev = 0;
@@ -199,13 +199,17 @@ static int conv3x3_impl(const void* x, const void* w, const void* bias, const vo
                         float* gn_partial = nullptr, int* gn_chunks_out = nullptr, int gn_chunks_planned = 0) {
     DS_REQUIRE(stride == 1 || stride == 2, "conv3x3: stride must be 1 or 2");
     DS_REQUIRE(!(upsample && stride != 1), "conv3x3: upsample with stride 2 is not a thing");
+    // upsample == 2: exact x2, `w` holds the four folded 2 x 2 phase weights [4][Cout][4 Cin] (ds_fold_upsample2x_f16)
+    const bool fold = upsample == 2;
+    DS_REQUIRE(!fold || (dtype == DS_DTYPE_F16 && (out_h == 0 || out_h == 2 * H_) && (out_w == 0 || out_w == 2 * W_)),
+               "conv3x3: folded upsample weights serve the exact x2 f16 case only");
     DS_REQUIRE((out_h == 0 && out_w == 0) || (upsample && out_h > 0 && out_w > 0),
                "conv3x3: an explicit output size needs the upsample flag");
     GemmParams p;
     p.conv = 1;
-    p.A = H(x); p.W = H(w); p.ldw = 9L * Cin; p.bias = H(bias); p.rowbias = H(rowbias); p.rowbias_ld = (int)rowbias_ld;
+    p.A = H(x); p.W = H(w); p.ldw = (fold ? 4L : 9L) * Cin; p.bias = H(bias); p.rowbias = H(rowbias); p.rowbias_ld = (int)rowbias_ld;
     p.residual = H(residual); p.ldr = Cout; p.C = HM(y); p.ldc = Cout;
-    p.Hin = H_; p.Win = W_; p.Cin = Cin; p.cstride = stride; p.upsample = upsample;
+    p.Hin = H_; p.Win = W_; p.Cin = Cin; p.cstride = stride; p.upsample = upsample != 0; p.up_fold = fold;
     p.Hout = upsample ? (out_h ? out_h : 2 * H_) : (stride == 2 ? (H_ + 1) / 2 : H_);
     p.Wout = upsample ? (out_w ? out_w : 2 * W_) : (stride == 2 ? (W_ + 1) / 2 : W_);
     if (upsample) {  // ATen: scale = float(input_size) / output_size
@@ -234,7 +238,16 @@ int ds_conv3x3_gn_chunks(int B, int H_, int W_, int Cin, int Cout) {
 int ds_conv3x3_f16(const void* x, const void* w, const void* bias, const void* rowbias, int64_t rowbias_ld,
                    const void* residual, void* y, int B, int H_, int W_, int Cin, int Cout, int stride, int upsample,
                    void* stream) {
-    return conv3x3_impl(x, w, bias, rowbias, rowbias_ld, residual, y, B, H_, W_, Cin, Cout, stride, upsample, S(stream));
+    return conv3x3_impl(x, w, bias, rowbias, rowbias_ld, residual, y, B, H_, W_, Cin, Cout, stride, upsample != 0, S(stream));
+}
+
+int ds_conv3x3_up2fold_f16(const void* x, const void* wfold, const void* bias, const void* rowbias, int64_t rowbias_ld,
+                           const void* residual, void* y, int B, int H_, int W_, int Cin, int Cout, void* stream) {
+    return conv3x3_impl(x, wfold, bias, rowbias, rowbias_ld, residual, y, B, H_, W_, Cin, Cout, 1, 2, S(stream));
+}
+
+int ds_fold_upsample2x_f16(const void* w, void* wfold, int Cout, int Cin, void* stream) {
+    return ds_launch_fold_upsample2x(H(w), HM(wfold), Cout, Cin, S(stream));
 }
 
 int ds_conv3x3_resize_f16(const void* x, const void* w, const void* bias, const void* rowbias, int64_t rowbias_ld,
@@ -247,7 +260,7 @@ int ds_conv3x3_resize_f16(const void* x, const void* w, const void* bias, const 
 // ---- bf16 entry points: the VAE decoder (fp16 overflows there; the reference runs it in fp32) ----------------------
 int ds_conv3x3_bf16(const void* x, const void* w, const void* bias, const void* residual, void* y, int B, int H_,
                     int W_, int Cin, int Cout, int upsample, void* stream) {
-    return conv3x3_impl(x, w, bias, nullptr, 0, residual, y, B, H_, W_, Cin, Cout, 1, upsample, S(stream), DS_DTYPE_BF16);
+    return conv3x3_impl(x, w, bias, nullptr, 0, residual, y, B, H_, W_, Cin, Cout, 1, upsample != 0, S(stream), DS_DTYPE_BF16);
 }
 
 int ds_gemm_bf16(const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias, const void* residual,
@@ -667,8 +680,10 @@ int ds_op_describe(const ds_op* op, char* name, int name_len, double* flops, dou
             const int Wo = i[6] ? (i[9] ? i[9] : 2 * i[2]) : (i[5] == 2 ? (i[2] + 1) / 2 : i[2]);
             g.M = i[0] * Ho * Wo; g.N = i[4]; g.K = 9 * i[3];
             g.conv = 1;
-            g.Hin = i[1]; g.Win = i[2]; g.Cin = i[3]; g.Hout = Ho; g.Wout = Wo; g.cstride = i[5]; g.upsample = i[6];
+            g.Hin = i[1]; g.Win = i[2]; g.Cin = i[3]; g.Hout = Ho; g.Wout = Wo; g.cstride = i[5]; g.upsample = i[6] != 0;
+            g.up_fold = i[6] == 2;
             nm = ds_gemm_kernel_name(g, 1);
+            // i[6] == 2 (folded x2 upsample, 4 taps executed): still the ALGORITHMIC work of the nearest x2 + 3 x 3 it replaces
             fl = 2.0 * g.M * (double)g.N * g.K;
             by = 2.0 * ((double)i[0] * i[1] * i[2] * i[3] + (double)g.N * g.K + (double)g.M * g.N);
             break;

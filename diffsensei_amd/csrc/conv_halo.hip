@@ -21,7 +21,8 @@
 // shift changes qx per lane, so the reader rebuilds it per tap: base = q*128 + ((lhi ^ ((qx0+kx)>>1)&7) << 4), k-step kk
 // at base ^ (kk << 5).
 // Halo pixels outside the image come from a zero page.  With upsample the patch is gathered from input pixel
-// nearest_src(uy), nearest_src(ux) (= uy>>1, ux>>1 for the plain x2 case): the upsampled tensor never exists.
+// nearest_src(uy), nearest_src(ux) (= uy>>1, ux>>1 for the plain x2 case): the upsampled tensor never exists.  An exact x2
+// upsampler whose weights were folded (GemmParams::up_fold) skips the gather and 5 of the 9 taps: "Phase mode" below.
 //
 // K order: channel slices outer, taps inner (k = tap*Cin + ci in the weight rows) - the sum is the same set of
 // products as the tap-major kernel's, in a different order, so results agree to fp32-accumulation rounding.
@@ -88,9 +89,10 @@ __device__ __forceinline__ void gn_emit(const GemmParams& p, float (&gs)[8], flo
 }
 
 // Epilogue of the two 8 x 16-pixel kernels (conv_halo_kernel, conv_halo_deep_kernel): the caller has passed its last barrier.
-template <typename T>
+template <typename T, bool FOLD = false>
 __device__ __forceinline__ void conv_halo_epilogue8(const GemmParams& p, f32x16 (&acc)[2][2], char* smem, int tid, int wm, int wn,
-                                                    int l31, int lhi, int b, int oy0, int ox0, int n0, int tile_in_image) {
+                                                    int l31, int lhi, int b, int oy0, int ox0, int n0, int tile_in_image, int phase = 0) {
+    const int TH = FOLD ? p.Hin : p.Hout, TW = FOLD ? p.Win : p.Wout;   // extent of the tile grid (phase mode: input resolution)
     typedef typename Elt<T>::v8 V8;
     typedef typename Elt<T>::v4 V4;
     // ---- epilogue: bias (+ per-image bias), round to f16, park the 128 x 128 tile in LDS, then whole 16-byte pieces
@@ -153,9 +155,12 @@ __device__ __forceinline__ void conv_halo_epilogue8(const GemmParams& p, f32x16 
         for (int u = 0; u < 4; ++u) {
             const int id = tid + 256 * (j0 + u);
             const int row = id >> 4, c = id & 15;
-            const int oy = oy0 + (row >> 4), ox = ox0 + (row & 15);
-            ok[u] = (n0 + c * 8 < p.N) & (oy < p.Hout) & (ox < p.Wout);
-            mrow[u] = ((long)b * p.Hout + min(oy, p.Hout - 1)) * p.Wout + min(ox, p.Wout - 1);
+            const int ty_ = oy0 + (row >> 4), tx_ = ox0 + (row & 15);
+            ok[u] = (n0 + c * 8 < p.N) & (ty_ < TH) & (tx_ < TW);
+            // phase mode: tile pixel (Y, X) of phase (py, px) is output pixel (2Y + py, 2X + px)
+            const int oy = FOLD ? 2 * min(ty_, TH - 1) + (phase >> 1) : min(ty_, TH - 1);
+            const int ox = FOLD ? 2 * min(tx_, TW - 1) + (phase & 1) : min(tx_, TW - 1);
+            mrow[u] = ((long)b * p.Hout + oy) * p.Wout + ox;
             ncol[u] = min(n0 + c * 8, p.N - 8);
             if (Rp) rv[u] = *reinterpret_cast<const V8*>(Rp + mrow[u] * p.ldr + ncol[u]);
         }
@@ -180,8 +185,32 @@ __device__ __forceinline__ void conv_halo_epilogue8(const GemmParams& p, f32x16 
     if (p.gn_partial) gn_emit(p, gs, gq, smem + 128 * CS_STRIDE, tid, b, tile_in_image, n0);
 }
 
-template <typename T>  // half_t (UNet) or bf16_t (VAE decoder)
+// ---------------------------------------------------------------------------------------------------------------
+// Phase mode (TPS = 4, GemmParams::up_fold): nearest x2 + 3 x 3 as four 2 x 2 convolutions of the INPUT-resolution image.
+// In the upsampled image every 2 x 2 block is one input pixel, so of the three rows a tap window covers two are the same
+// input row: for output pixel (2Y + py, 2X + px), py = 0 reads input rows Y - 1 | Y with taps ky = {0} | {1, 2}, py = 1 reads
+// rows Y | Y + 1 with taps {0, 1} | {2}; columns alike.  The taps that meet the same input pixel are added up once per
+// weight load (fold_upsample2x_kernel below): W = [phase py*2+px][Cout][(a*2+b) Cin + ci], and a block owns a tile of
+// input-resolution positions of ONE phase (the phase is the low two bits of its pixel-tile index).  It stages the plain
+// halo patch of the input (origin (Y0 - 1, X0 - 1); the zero padding of the upsampled image is exactly the zero padding of
+// the input), runs slices x 4 k-tiles with tap (a, b) at patch shift (py + a) * HWD + (px + b) - one of the nine shifts of
+// the 3 x 3 form, so the column swizzle stays conflict-free - and stores tile pixel (Y, X) to output pixel (2Y + py, 2X + px).
+// 4/9 of the MFMAs; not bit-identical to the 3 x 3 form (the folded weights are rounded to f16 once more).
+// ---------------------------------------------------------------------------------------------------------------
+template <int TPS>
+__device__ __forceinline__ void halo_tap(int tap, int phase, int& ky, int& kx) {   // patch-row / -column shift of k-tile `tap`
+    if constexpr (TPS == 4) {
+        ky = (phase >> 1) + (tap >> 1);
+        kx = (phase & 1) + (tap & 1);
+    } else {
+        ky = tap / 3;
+        kx = tap - 3 * ky;
+    }
+}
+
+template <typename T, int TPS = 9>  // half_t (UNet) or bf16_t (VAE decoder); TPS: k-tiles (taps) per channel slice, 4 = phase mode
 __global__ __launch_bounds__(256, 3) void conv_halo_kernel(const GemmParams p) {
+    constexpr bool FOLD = TPS == 4;
     typedef typename Elt<T>::v8 V8;
     typedef typename Elt<T>::v4 V4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -197,7 +226,10 @@ __global__ __launch_bounds__(256, 3) void conv_halo_kernel(const GemmParams p) {
     const int tile = xcd_remap(blockIdx.x, gridDim.x);
     int tm, tn;
     tile_coords(tile, p.tiles_m, p.tiles_n, tm, tn);
-    const int tiles_x = (p.Wout + PW - 1) / PW, tiles_y = (p.Hout + PH - 1) / PH;  // ragged edges: masked stores
+    const int phase = FOLD ? (tm & 3) : 0;
+    if (FOLD) tm >>= 2;
+    const int TH = FOLD ? p.Hin : p.Hout, TW = FOLD ? p.Win : p.Wout;
+    const int tiles_x = (TW + PW - 1) / PW, tiles_y = (TH + PH - 1) / PH;  // ragged edges: masked stores
     const int tx = tm % tiles_x, ty = (tm / tiles_x) % tiles_y, b = tm / (tiles_x * tiles_y);
     const int oy0 = ty * PH, ox0 = tx * PW, n0 = tn * BN;
 
@@ -208,8 +240,8 @@ __global__ __launch_bounds__(256, 3) void conv_halo_kernel(const GemmParams p) {
         const int q = (wave * 6 + j) * 8 + lrow;
         const int qy = q / HWD, qx = q - qy * HWD;
         const int uy = oy0 - 1 + qy, ux = ox0 - 1 + qx;  // output-resolution pixel
-        const bool ok = (q < HROWS) & (uy >= 0) & (uy < p.Hout) & (ux >= 0) & (ux < p.Wout);
-        const int iy = p.upsample ? nearest_src(uy, p.up_sy, p.Hin) : uy, ix = p.upsample ? nearest_src(ux, p.up_sx, p.Win) : ux;
+        const bool ok = (q < HROWS) & (uy >= 0) & (uy < TH) & (ux >= 0) & (ux < TW);
+        const int iy = !FOLD && p.upsample ? nearest_src(uy, p.up_sy, p.Hin) : uy, ix = !FOLD && p.upsample ? nearest_src(ux, p.up_sx, p.Win) : ux;
         const int chunk = slot ^ (((rowswz ? q : qx) >> 1) & 7);  // swizzle by patch COLUMN (see the header)
         poff[j] = ok ? ((b * p.Hin + iy) * p.Win + ix) * p.Cin + chunk * 8 : -1;
     }
@@ -219,7 +251,7 @@ __global__ __launch_bounds__(256, 3) void conv_halo_kernel(const GemmParams p) {
         const int row = (wave * 4 + j) * 8 + lrow;
         const int chunk = slot ^ ((row >> 1) & 7);
         const int n = min(n0 + row, p.N - 1);
-        woff[j] = n * (int)p.ldw + chunk * 8;
+        woff[j] = (FOLD ? phase * p.N + n : n) * (int)p.ldw + chunk * 8;   // phase mode: weight slab `phase` of [4][N][4 Cin]
     }
     auto issue_patch = [&](int ci0) {
         char* d = sP + wave * 6 * 1024;
@@ -254,11 +286,12 @@ __global__ __launch_bounds__(256, 3) void conv_halo_kernel(const GemmParams p) {
     issue_w(0);
     for (int s = 0; s < slices; ++s) {
 #pragma unroll 1
-        for (int tap = 0; tap < 9; ++tap) {
+        for (int tap = 0; tap < TPS; ++tap) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
-            const int ky = tap / 3, kx = tap - 3 * ky;
+            int ky, kx;
+            halo_tap<TPS>(tap, phase, ky, kx);
             const int shift = ky * HWD + kx;
             V8 af[4][2], bf[4][2];
 #pragma unroll
@@ -276,11 +309,11 @@ __global__ __launch_bounds__(256, 3) void conv_halo_kernel(const GemmParams p) {
                     bf[kk][ni] = *reinterpret_cast<const V8*>(sW + r * 128 + swz(r, kk * 2 + lhi));
                 }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            const bool last = (s + 1 == slices) & (tap == 8);
-            if (!last) {  // the W buffer (and after tap 8 the patch) is drained once everyone holds its fragments
+            const bool last = (s + 1 == slices) & (tap == TPS - 1);
+            if (!last) {  // the W buffer (and after the last tap the patch) is drained once everyone holds its fragments
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
-                if (tap == 8) {
+                if (tap == TPS - 1) {
                     issue_patch((s + 1) * 64);
                     issue_w((s + 1) * 64);
                 } else {
@@ -298,7 +331,7 @@ __global__ __launch_bounds__(256, 3) void conv_halo_kernel(const GemmParams p) {
     }
     __syncthreads();
 
-    conv_halo_epilogue8<T>(p, acc, smem, tid, wm, wn, l31, lhi, b, oy0, ox0, n0, ty * tiles_x + tx);
+    conv_halo_epilogue8<T, FOLD>(p, acc, smem, tid, wm, wn, l31, lhi, b, oy0, ox0, n0, ty * tiles_x + tx, phase);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -350,8 +383,10 @@ __device__ __forceinline__ void deep_wait_vm() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-template <typename T>
+template <typename T, int TPS = 9>
 __global__ __launch_bounds__(256, 1) void conv_halo_deep_kernel(const GemmParams p) {
+    constexpr bool FOLD = TPS == 4;
+    static_assert(TPS >= DEEP_NW, "the next slice's patch must be older than the W tile its first k-tile waits for");
     typedef typename Elt<T>::v8 V8;
     typedef typename Elt<T>::v4 V4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -364,7 +399,10 @@ __global__ __launch_bounds__(256, 1) void conv_halo_deep_kernel(const GemmParams
     const int tile = xcd_remap(blockIdx.x, gridDim.x);
     int tm, tn;
     tile_coords(tile, p.tiles_m, p.tiles_n, tm, tn);
-    const int tiles_x = (p.Wout + PW - 1) / PW, tiles_y = (p.Hout + PH - 1) / PH;
+    const int phase = FOLD ? (tm & 3) : 0;
+    if (FOLD) tm >>= 2;
+    const int TH = FOLD ? p.Hin : p.Hout, TW = FOLD ? p.Win : p.Wout;
+    const int tiles_x = (TW + PW - 1) / PW, tiles_y = (TH + PH - 1) / PH;
     const int tx = tm % tiles_x, ty = (tm / tiles_x) % tiles_y, b = tm / (tiles_x * tiles_y);
     const int oy0 = ty * PH, ox0 = tx * PW, n0 = tn * BN;
 
@@ -374,8 +412,8 @@ __global__ __launch_bounds__(256, 1) void conv_halo_deep_kernel(const GemmParams
         const int q = (wave * 6 + j) * 8 + lrow;
         const int qy = q / HWD, qx = q - qy * HWD;
         const int uy = oy0 - 1 + qy, ux = ox0 - 1 + qx;
-        const bool ok = (q < HROWS) & (uy >= 0) & (uy < p.Hout) & (ux >= 0) & (ux < p.Wout);
-        const int iy = p.upsample ? nearest_src(uy, p.up_sy, p.Hin) : uy, ix = p.upsample ? nearest_src(ux, p.up_sx, p.Win) : ux;
+        const bool ok = (q < HROWS) & (uy >= 0) & (uy < TH) & (ux >= 0) & (ux < TW);
+        const int iy = !FOLD && p.upsample ? nearest_src(uy, p.up_sy, p.Hin) : uy, ix = !FOLD && p.upsample ? nearest_src(ux, p.up_sx, p.Win) : ux;
         const int chunk = slot ^ ((qx >> 1) & 7);  // swizzle by patch COLUMN (see the file header)
         poff[j] = ok ? ((b * p.Hin + iy) * p.Win + ix) * p.Cin + chunk * 8 : -1;
     }
@@ -385,7 +423,7 @@ __global__ __launch_bounds__(256, 1) void conv_halo_deep_kernel(const GemmParams
         const int row = (wave * 4 + j) * 8 + lrow;
         const int chunk = slot ^ ((row >> 1) & 7);
         const int n = min(n0 + row, p.N - 1);
-        woff[j] = n * (int)p.ldw + chunk * 8;
+        woff[j] = (FOLD ? phase * p.N + n : n) * (int)p.ldw + chunk * 8;   // phase mode: weight slab `phase` of [4][N][4 Cin]
     }
     const unsigned lds0 = (unsigned)(size_t)(lds_void*)smem;
     auto issue_patch = [&](int ci0, int pbuf) {
@@ -415,13 +453,14 @@ __global__ __launch_bounds__(256, 1) void conv_halo_deep_kernel(const GemmParams
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
     const int slices = p.Cin / 64;
-    const int nkt = slices * 9;
+    const int nkt = slices * TPS;
     auto w_k0 = [&](int kt) {   // k-tile kt = (slice, tap): column offset of its W tile (k = tap * Cin + ci)
-        const int sl = kt / 9, tp = kt - sl * 9;
+        const int sl = kt / TPS, tp = kt - sl * TPS;
         return tp * p.Cin + sl * 64;
     };
     auto set_abase = [&](int (&ab)[2], int tp) {
-        const int ky = tp / 3, kx = tp - 3 * ky;
+        int ky, kx;
+        halo_tap<TPS>(tp, phase, ky, kx);
         const int shift = ky * HWD + kx;
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi) {
@@ -467,7 +506,7 @@ __global__ __launch_bounds__(256, 1) void conv_halo_deep_kernel(const GemmParams
     // W k-tile that is NW ahead of the previous slice's last k-tile)
     issue_patch(0, 0);
 #pragma unroll
-    for (int j = 0; j < DEEP_NW; ++j) issue_w(w_k0(j), j);          // nkt >= 9 > NW
+    for (int j = 0; j < DEEP_NW; ++j) issue_w(w_k0(j), j);          // nkt >= TPS >= NW
     if (slices > 1) issue_patch(64, 1);
     wait_newer(DEEP_NW - 1, slices > 1);
     __builtin_amdgcn_s_barrier();
@@ -495,7 +534,7 @@ __global__ __launch_bounds__(256, 1) void conv_halo_deep_kernel(const GemmParams
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
                 if (kt + DEEP_NW < nkt) issue_w(w_k0(kt + DEEP_NW), wb);   // the buffer this k-tile has just left
-                const int ntap = tap == 8 ? 0 : tap + 1, ns = tap == 8 ? s + 1 : s;
+                const int ntap = tap == TPS - 1 ? 0 : tap + 1, ns = tap == TPS - 1 ? s + 1 : s;
                 // entering slice ns: its successor's patch goes out now, behind W(first k-tile of ns + 2) - the prologue's order -,
                 // into the buffer the slice just finished has left
                 if (ntap == 0 && ns + 1 < slices) issue_patch((ns + 1) * 64, (ns + 1) & 1);
@@ -513,7 +552,7 @@ __global__ __launch_bounds__(256, 1) void conv_halo_deep_kernel(const GemmParams
         }
     }
     __syncthreads();
-    conv_halo_epilogue8<T>(p, acc, smem, tid, wm, wn, l31, lhi, b, oy0, ox0, n0, ty * tiles_x + tx);
+    conv_halo_epilogue8<T, FOLD>(p, acc, smem, tid, wm, wn, l31, lhi, b, oy0, ox0, n0, ty * tiles_x + tx, phase);
 }
 
 constexpr int PH2 = 16;
@@ -529,8 +568,9 @@ struct IC2 {
     static constexpr int value = V;
 };
 
-template <typename T>
+template <typename T, int TPS = 9>
 __global__ __launch_bounds__(256, 2) void conv_halo256_kernel(const GemmParams p) {
+    constexpr bool FOLD = TPS == 4;
     typedef typename Elt<T>::v8 V8;
     typedef typename Elt<T>::v4 V4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -546,7 +586,10 @@ __global__ __launch_bounds__(256, 2) void conv_halo256_kernel(const GemmParams p
     const int tile = xcd_remap(blockIdx.x, gridDim.x);
     int tm, tn;
     tile_coords(tile, p.tiles_m, p.tiles_n, tm, tn);
-    const int tiles_x = (p.Wout + PW - 1) / PW, tiles_y = (p.Hout + PH2 - 1) / PH2;
+    const int phase = FOLD ? (tm & 3) : 0;
+    if (FOLD) tm >>= 2;
+    const int TH = FOLD ? p.Hin : p.Hout, TW = FOLD ? p.Win : p.Wout;
+    const int tiles_x = (TW + PW - 1) / PW, tiles_y = (TH + PH2 - 1) / PH2;
     const int tx = tm % tiles_x, ty = (tm / tiles_x) % tiles_y, b = tm / (tiles_x * tiles_y);
     const int oy0 = ty * PH2, ox0 = tx * PW, n0 = tn * BN;
 
@@ -556,8 +599,8 @@ __global__ __launch_bounds__(256, 2) void conv_halo256_kernel(const GemmParams p
         const int q = (wave * PPW2 + j) * 8 + lrow;
         const int qy = q / HWD, qx = q - qy * HWD;
         const int uy = oy0 - 1 + qy, ux = ox0 - 1 + qx;
-        const bool ok = (q < HROWS2) & (uy >= 0) & (uy < p.Hout) & (ux >= 0) & (ux < p.Wout);
-        const int iy = p.upsample ? nearest_src(uy, p.up_sy, p.Hin) : uy, ix = p.upsample ? nearest_src(ux, p.up_sx, p.Win) : ux;
+        const bool ok = (q < HROWS2) & (uy >= 0) & (uy < TH) & (ux >= 0) & (ux < TW);
+        const int iy = !FOLD && p.upsample ? nearest_src(uy, p.up_sy, p.Hin) : uy, ix = !FOLD && p.upsample ? nearest_src(ux, p.up_sx, p.Win) : ux;
         const int chunk = slot ^ (((rowswz ? q : qx) >> 1) & 7);  // swizzle by patch COLUMN (see the header)
         poff[j] = ok ? ((b * p.Hin + iy) * p.Win + ix) * p.Cin + chunk * 8 : -1;
     }
@@ -567,7 +610,7 @@ __global__ __launch_bounds__(256, 2) void conv_halo256_kernel(const GemmParams p
         const int row = (wave * 4 + j) * 8 + lrow;
         const int chunk = slot ^ ((row >> 1) & 7);
         const int n = min(n0 + row, p.N - 1);
-        woff[j] = n * (int)p.ldw + chunk * 8;
+        woff[j] = (FOLD ? phase * p.N + n : n) * (int)p.ldw + chunk * 8;   // phase mode: weight slab `phase` of [4][N][4 Cin]
     }
     // LDS-DMA from inline asm (`lds_dma16_v`, ds_common.h): behind the builtin the compiler turns every LDS wait of the kernel
     // into lgkmcnt(0), and the fragment read-ahead of the k-loop below would wait for the reads it has just issued
@@ -614,9 +657,10 @@ __global__ __launch_bounds__(256, 2) void conv_halo256_kernel(const GemmParams p
         // and, because the staging went through __builtin_amdgcn_global_load_lds, every wait an lgkmcnt(0): a fragment round
         // trip exposed per four MFMAs.)
         const int slices = p.Cin / 64;
-        const int nkt = slices * 9;
+        const int nkt = slices * TPS;
         auto set_abase = [&](int (&ab)[MI], int tp) {
-            const int ky = tp / 3, kx = tp - 3 * ky;
+            int ky, kx;
+            halo_tap<TPS>(tp, phase, ky, kx);
             const int shift = ky * HWD + kx;
     #pragma unroll
             for (int mi = 0; mi < MI; ++mi) {
@@ -662,8 +706,8 @@ __global__ __launch_bounds__(256, 2) void conv_halo256_kernel(const GemmParams p
                 if (kk < 3) {
                     load(af[(kk + 1) & 1], bf[(kk + 1) & 1], abase, cW, kk + 1);
                 } else {
-                    const int ntap = tap == 8 ? 0 : tap + 1, ns = tap == 8 ? s + 1 : s;
-                    const int ntap2 = ntap == 8 ? 0 : ntap + 1, ns2 = ntap == 8 ? ns + 1 : ns;
+                    const int ntap = tap == TPS - 1 ? 0 : tap + 1, ns = tap == TPS - 1 ? s + 1 : s;
+                    const int ntap2 = ntap == TPS - 1 ? 0 : ntap + 1, ns2 = ntap == TPS - 1 ? ns + 1 : ns;
                     // every fragment read of this k-tile has returned (the last ones were requested a k-step ago)
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                     if (ntap == 0) {
@@ -756,9 +800,12 @@ __global__ __launch_bounds__(256, 2) void conv_halo256_kernel(const GemmParams p
         for (int u = 0; u < 4; ++u) {
             const int id = tid + 256 * (j0 + u);
             const int row = id >> 4, c = id & 15;
-            const int oy = oy0 + (row >> 4), ox = ox0 + (row & 15);
-            ok[u] = (n0 + c * 8 < p.N) & (oy < p.Hout) & (ox < p.Wout);
-            mrow[u] = ((long)b * p.Hout + min(oy, p.Hout - 1)) * p.Wout + min(ox, p.Wout - 1);
+            const int ty_ = oy0 + (row >> 4), tx_ = ox0 + (row & 15);
+            ok[u] = (n0 + c * 8 < p.N) & (ty_ < TH) & (tx_ < TW);
+            // phase mode: tile pixel (Y, X) of phase (py, px) is output pixel (2Y + py, 2X + px)
+            const int oy = FOLD ? 2 * min(ty_, TH - 1) + (phase >> 1) : min(ty_, TH - 1);
+            const int ox = FOLD ? 2 * min(tx_, TW - 1) + (phase & 1) : min(tx_, TW - 1);
+            mrow[u] = ((long)b * p.Hout + oy) * p.Wout + ox;
             ncol[u] = min(n0 + c * 8, p.N - 8);
             if (Rp) rv[u] = *reinterpret_cast<const V8*>(Rp + mrow[u] * p.ldr + ncol[u]);
         }
@@ -783,10 +830,41 @@ __global__ __launch_bounds__(256, 2) void conv_halo256_kernel(const GemmParams p
     if (p.gn_partial) gn_emit(p, gs, gq, smem + 256 * CS_STRIDE, tid, b, ty * tiles_x + tx, n0);
 }
 
+// Weights of the phase mode: packed 3 x 3 weight [Cout][(ky*3+kx) Cin + ci] -> [phase py*2+px][Cout][(a*2+b) Cin + ci], each entry the
+// sum of the 1, 2 or 4 taps that read the same input pixel (rows: py = 0 -> {0} | {1, 2}, py = 1 -> {0, 1} | {2}; columns alike),
+// added in fp32 in (ky, kx) order and rounded to f16 once.  One thread per output element; made once per weight load.
+__global__ __launch_bounds__(256) void fold_upsample2x_kernel(const half_t* __restrict__ w, half_t* __restrict__ out, int Cout, int Cin) {
+    const long per_phase = (long)Cout * 4 * Cin;
+    const long id = (long)blockIdx.x * 256 + threadIdx.x;
+    if (id >= 4 * per_phase) return;
+    const int phase = (int)(id / per_phase);
+    const long r = id - phase * per_phase;
+    const int n = (int)(r / (4 * Cin)), k = (int)(r - (long)n * 4 * Cin);
+    const int t = k / Cin, ci = k - t * Cin;
+    const int py = phase >> 1, px = phase & 1, a = t >> 1, b = t & 1;
+    // taps of row group a under phase py: py = 0: a = 0 -> {0}, a = 1 -> {1, 2};  py = 1: a = 0 -> {0, 1}, a = 1 -> {2}
+    const int ky0 = a == 0 ? 0 : (py == 0 ? 1 : 2), ky1 = a == 0 ? (py == 0 ? 0 : 1) : 2;
+    const int kx0 = b == 0 ? 0 : (px == 0 ? 1 : 2), kx1 = b == 0 ? (px == 0 ? 0 : 1) : 2;
+    const half_t* wr = w + (long)n * 9 * Cin + ci;
+    float acc = 0.f;
+    for (int ky = ky0; ky <= ky1; ++ky)
+        for (int kx = kx0; kx <= kx1; ++kx) acc += (float)wr[(ky * 3 + kx) * Cin];
+    out[id] = (half_t)acc;
+}
+
 static thread_local int g_deep_max_blocks_per_cu = 1;   // ring-buffered 8 x 16 kernel for grids of <= this many blocks per CU (A/B: "conv_deep_blocks")
 static thread_local int g_halo_variant = 0;  // 0 auto, 1 force the 8 x 16 kernel, 2 force the 16 x 16 kernel (where its shape rule holds), 3 force the ring-buffered 8 x 16 kernel, 4 never use it
 
 }  // namespace
+
+int ds_launch_fold_upsample2x(const half_t* w, half_t* out, int Cout, int Cin, hipStream_t stream) {
+    DS_REQUIRE(w && out && Cout > 0 && Cin > 0, "fold_upsample2x: empty weight");
+    const long total = 16L * Cout * Cin;
+    DS_REQUIRE(total < (1L << 31), "fold_upsample2x: Cout * Cin too large");
+    hipLaunchKernelGGL(fold_upsample2x_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, w, out, Cout, Cin);
+    DS_LAUNCH_CHECK();
+    return 0;
+}
 
 void ds_conv_halo_set_variant(int v) { g_halo_variant = v; }
 void ds_conv_halo_set_deep_blocks(int v) { g_deep_max_blocks_per_cu = v; }
@@ -800,20 +878,25 @@ bool ds_conv_halo_applicable(const GemmParams& p) {
     return batch * p.Hin * p.Win * p.Cin < (1L << 31);
 }
 
+// Pixel tiles of `ph` rows per image.  Phase mode: the tiles cover the INPUT resolution, once per phase.
+static long halo_tiles(const GemmParams& p, int ph) {
+    const int h = p.up_fold ? p.Hin : p.Hout, w = p.up_fold ? p.Win : p.Wout;
+    return (long)((h + ph - 1) / ph) * ((w + PW - 1) / PW) * (p.up_fold ? 4 : 1);
+}
+
 // 16 x 16 patches once they still fill the chip twice over (two blocks per CU): large batches / resolutions
 static bool halo_big(const GemmParams& p) {
     const int batch = p.M / (p.Hout * p.Wout);
-    const int ty16 = (p.Hout + PH2 - 1) / PH2, txs = (p.Wout + PW - 1) / PW;
-    const long tiles256 = (long)batch * ty16 * txs * ((p.N + BN - 1) / BN);
+    const long tiles256 = (long)batch * halo_tiles(p, PH2) * ((p.N + BN - 1) / BN);
     return g_halo_variant == 2 || ((g_halo_variant == 0 || g_halo_variant == 4) && tiles256 >= 1024);
 }
 
 // Pixel tiles per image of the variant ds_launch_conv_halo runs on this problem = partial-sum chunks the GroupNorm behind it
 // has to add up; 0 when the statistics cannot come from the convolution (the GroupNorm workspace holds 128 chunks per image).
 int ds_conv_halo_gn_chunks(const GemmParams& p) {
-    if (!ds_conv_halo_applicable(p) || p.dtype != DS_DTYPE_F16) return 0;
+    if (!ds_conv_halo_applicable(p) || p.dtype != DS_DTYPE_F16 || p.up_fold) return 0;   // (phase mode: a tile is not a patch of the output)
     const int ph = halo_big(p) ? PH2 : PH;
-    const long n = (long)((p.Hout + ph - 1) / ph) * ((p.Wout + PW - 1) / PW);
+    const long n = halo_tiles(p, ph);
     return n <= 128 ? (int)n : 0;
 }
 
@@ -838,7 +921,7 @@ static HaloKernel halo_pick(const GemmParams& p) {
     // nothing else on the CU hides the single-buffer kernel's DMA round trip per k-tile.  f16 only (the bf16 VAE decoder never
     // has such a grid).  Same bits out.
     const int batch = p.M / (p.Hout * p.Wout);
-    const long blocks8 = (long)batch * ((p.Hout + PH - 1) / PH) * ((p.Wout + PW - 1) / PW) * ((p.N + BN - 1) / BN);
+    const long blocks8 = (long)batch * halo_tiles(p, PH) * ((p.N + BN - 1) / BN);
     if (p.dtype == DS_DTYPE_F16 && (g_halo_variant == 3 || (g_halo_variant == 0 && blocks8 <= g_deep_max_blocks_per_cu * (long)halo_cus())))
         return HALO_DEEP;
     return HALO_8X16;
@@ -857,8 +940,13 @@ int ds_launch_conv_halo(const GemmParams& p0, hipStream_t stream) {
     DS_REQUIRE(ds_conv_halo_applicable(p), "conv_halo: shape not supported");
     const int batch = p.M / (p.Hout * p.Wout);
     p.tiles_n = (p.N + BN - 1) / BN;
-    const int ty8 = (p.Hout + PH - 1) / PH, ty16 = (p.Hout + PH2 - 1) / PH2, txs = (p.Wout + PW - 1) / PW;
     const HaloKernel kern = halo_pick(p);
+    if (p.up_fold) {
+        DS_REQUIRE(p.upsample && p.Hout == 2 * p.Hin && p.Wout == 2 * p.Win, "conv_halo: the phase mode is the exact x2 upsample (%d x %d -> %d x %d)",
+                   p.Hin, p.Win, p.Hout, p.Wout);
+        DS_REQUIRE(p.dtype == DS_DTYPE_F16 && !p.gn_partial && p.ldw == 4L * p.Cin,
+                   "conv_halo: the phase mode takes f16 folded weights [4][Cout][4 Cin] and emits no GroupNorm statistics");
+    }
     if (p.gn_partial) {
         const int planned = p.gn_chunks;
         p.gn_chunks = ds_conv_halo_gn_chunks(p);
@@ -870,7 +958,7 @@ int ds_launch_conv_halo(const GemmParams& p0, hipStream_t stream) {
                    planned, p.gn_chunks);
     }
     if (kern == HALO_16X16) {
-        p.tiles_m = batch * ty16 * txs;
+        p.tiles_m = batch * (int)halo_tiles(p, PH2);
         const size_t lds2 = PBYTES2 + 2 * BN * 128;  // 76 KiB; the 256 x 272 B epilogue tile (68 KiB) + 4 KiB of GroupNorm partials fit inside
         static unsigned long long attr_devs = 0;
         if (ds_first_on_device(attr_devs)) {
@@ -878,26 +966,34 @@ int ds_launch_conv_halo(const GemmParams& p0, hipStream_t stream) {
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
             DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_halo256_kernel<bf16_t>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+            DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_halo256_kernel<half_t, 4>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
         }
         dim3 grid2(p.tiles_m * p.tiles_n);
-        if (p.dtype == DS_DTYPE_BF16) hipLaunchKernelGGL(conv_halo256_kernel<bf16_t>, grid2, dim3(256), lds2, stream, p);
+        if (p.up_fold) hipLaunchKernelGGL((conv_halo256_kernel<half_t, 4>), grid2, dim3(256), lds2, stream, p);
+        else if (p.dtype == DS_DTYPE_BF16) hipLaunchKernelGGL(conv_halo256_kernel<bf16_t>, grid2, dim3(256), lds2, stream, p);
         else hipLaunchKernelGGL(conv_halo256_kernel<half_t>, grid2, dim3(256), lds2, stream, p);
         DS_LAUNCH_CHECK();
         return 0;
     }
-    p.tiles_m = batch * ty8 * txs;
+    p.tiles_m = batch * (int)halo_tiles(p, PH);
     if (kern == HALO_DEEP) {
         static unsigned long long attr_devs_deep = 0;
-        if (ds_first_on_device(attr_devs_deep))
+        if (ds_first_on_device(attr_devs_deep)) {
             DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_halo_deep_kernel<half_t>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEEP_LDS));
-        hipLaunchKernelGGL(conv_halo_deep_kernel<half_t>, dim3(p.tiles_m * p.tiles_n), dim3(256), (size_t)DEEP_LDS, stream, p);
+            DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_halo_deep_kernel<half_t, 4>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEEP_LDS));
+        }
+        if (p.up_fold) hipLaunchKernelGGL((conv_halo_deep_kernel<half_t, 4>), dim3(p.tiles_m * p.tiles_n), dim3(256), (size_t)DEEP_LDS, stream, p);
+        else hipLaunchKernelGGL(conv_halo_deep_kernel<half_t>, dim3(p.tiles_m * p.tiles_n), dim3(256), (size_t)DEEP_LDS, stream, p);
         DS_LAUNCH_CHECK();
         return 0;
     }
     const size_t lds = PROWS * 128 + BN * 128;  // 40 KiB; the 128 x 272 B epilogue tile (34 KiB) + 4 KiB of GroupNorm partials fit inside
     dim3 grid(p.tiles_m * p.tiles_n);
-    if (p.dtype == DS_DTYPE_BF16) hipLaunchKernelGGL(conv_halo_kernel<bf16_t>, grid, dim3(256), lds, stream, p);
+    if (p.up_fold) hipLaunchKernelGGL((conv_halo_kernel<half_t, 4>), grid, dim3(256), lds, stream, p);
+    else if (p.dtype == DS_DTYPE_BF16) hipLaunchKernelGGL(conv_halo_kernel<bf16_t>, grid, dim3(256), lds, stream, p);
     else hipLaunchKernelGGL(conv_halo_kernel<half_t>, grid, dim3(256), lds, stream, p);
     DS_LAUNCH_CHECK();
     return 0;

@@ -21,6 +21,8 @@ struct GemmParams {
     int conv = 0;
     int Hin = 0, Win = 0, Cin = 0, Hout = 0, Wout = 0, cstride = 1, upsample = 0;
     float up_sy = 0.5f, up_sx = 0.5f;  // upsample: nearest-resize scales float(Hin)/Hout, float(Win)/Wout (ATen's definition)
+    int up_fold = 0;  // upsample, exactly 2Hin x 2Win, halo-patch kernels only: W holds the four 2 x 2 phase weights [4][N][4 Cin]
+                      //   (ldw = 4 Cin, ds_launch_fold_upsample2x) instead of [N][9 Cin]; K stays 9 Cin, the work of the op it replaces
     int tiles_m = 0, tiles_n = 0;
     int nbatch = 1;  // gemm_pp_kernel only: batch items folded into the persistent tile walk (id -> item, tile); others use grid.z
     // ---- LayerNorm fused across a producer / consumer pair of gemm_pp_kernel launches (gemm_pp.hip header, "LayerNorm"):
@@ -60,6 +62,7 @@ bool ds_conv_halo_applicable(const GemmParams& p);  // conv_halo.hip: halo-patch
 int ds_launch_conv_halo(const GemmParams& p, hipStream_t stream);
 const char* ds_conv_halo_kernel_name(const GemmParams& p);  // conv_halo_kernel | conv_halo256_kernel | conv_halo_deep_kernel: what ds_launch_conv_halo runs
 int ds_conv_halo_gn_chunks(const GemmParams& p);  // pixel tiles per image of the variant ds_launch_conv_halo would run; 0: no statistics (too many tiles / not applicable)
+int ds_launch_fold_upsample2x(const half_t* w, half_t* out, int Cout, int Cin, hipStream_t stream);  // [Cout][9 Cin] -> [4][Cout][4 Cin]
 void ds_conv_halo_set_variant(int v);  // 0 auto, 1 8x16-pixel blocks, 2 16x16-pixel blocks, 3 ring-buffered 8x16 blocks, 4 auto without the ring-buffered kernel
 void ds_conv_halo_set_deep_blocks(int v);  // the ring-buffered 8x16 kernel takes grids of <= v blocks per CU (default 1)
 const char* ds_gemm_kernel_name(const GemmParams& p, int batch);  // the instantiation ds_launch_gemm dispatches to

@@ -903,8 +903,9 @@ const char* ds_gemm_kernel_name(const GemmParams& p, int batch) {
     // the fused-LayerNorm instantiations of gemm_pp_kernel are kernels of their own in a rocprofv3 trace (template argument FUSE)
     if (p.ln_stats && !p.ln_partial) return p.ln_swapped ? "gemm_pp_kernel<0,4>" : p.epi == EPI_GEGLU ? "gemm_pp_kernel<0,9>" : "gemm_pp_kernel<0,1>";
     if (p.stats_out && ds_gemm_ln_kind(p.M, p.N, p.K, batch, p.epi) == 1) return "gemm_pp_kernel<0,2>";
-    const Choice c = choose(p, batch);
+    Choice c = choose(p, batch);
     const bool conv = p.conv != 0;
+    if (conv && p.up_fold) c.kind = K_HALO;   // folded phase weights: the halo-patch kernels are the only readers of that layout
     switch (c.kind) {
         case K_PP: return "gemm_pp_kernel<0,0>";
         case K_HALO: return ds_conv_halo_kernel_name(p);
@@ -950,6 +951,10 @@ int ds_launch_gemm(const GemmParams& p_in, int batch, hipStream_t stream) {
         return ds_launch_gemm_g320(p, stream);
     }
     Choice c = choose(p, batch);
+    if (conv && p.up_fold) {   // folded phase weights [4][N][4 Cin]: only the halo-patch kernels read that layout, whatever A/B knob is set
+        DS_REQUIRE(ds_conv_halo_applicable(p), "conv3x3: the folded x2 upsample needs the halo-patch kernels (stride 1, Cin %% 64 == 0)");
+        c.kind = K_HALO;
+    }
     DS_REQUIRE(!p.gn_partial || (conv && c.kind == K_HALO && p.dtype == DS_DTYPE_F16),
                "conv3x3: GroupNorm statistics come out of the halo-patch kernels only (ask ds_conv3x3_gn_chunks first)");
     if (p.ln_stats || p.ln_c || p.stats_out) {

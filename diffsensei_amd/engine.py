@@ -74,6 +74,38 @@ def pack_ln_fused(w: Tensor, bias: Optional[Tensor], gamma: Tensor, beta: Tensor
     return gw.contiguous(), torch.stack([hi, lo], dim=1).contiguous(), bp.to(torch.float16).contiguous()
 
 
+# Upsample2D at exactly x2: the taps of the 3x3 kernel that meet the same input pixel, per output phase (py or px) and 2x2 tap
+# (a or b) - csrc/conv_halo.hip, "Phase mode"
+UPSAMPLE_FOLD_GROUPS = (((0,), (1, 2)), ((0, 1), (2,)))
+
+
+def fold_upsample2x_reference(w: Tensor, out_dtype=torch.float16) -> Tensor:
+    """Torch model of `ds_fold_upsample2x_f16`: packed 3x3 weight [Cout, 9*Cin] (k = (ky*3+kx)*Cin + ci) -> the four 2x2 phase
+    weights [4, Cout, 4*Cin] (phase py*2+px, k = (a*2+b)*Cin + ci) of nearest x2 + conv3x3, each the fp32 sum - in (ky, kx)
+    order - of the taps that read the same input pixel, rounded once to `out_dtype` (float32: the exact algebra)."""
+    Cout = w.shape[0]
+    w9 = w.reshape(Cout, 3, 3, -1).float()
+    Cin = w9.shape[3]
+    out = torch.empty(4, Cout, 2, 2, Cin, dtype=torch.float32, device=w.device)
+    for py in range(2):
+        for px in range(2):
+            for a in range(2):
+                for b in range(2):
+                    acc = torch.zeros(Cout, Cin, dtype=torch.float32, device=w.device)
+                    for ky in UPSAMPLE_FOLD_GROUPS[py][a]:
+                        for kx in UPSAMPLE_FOLD_GROUPS[px][b]:
+                            acc = acc + w9[:, ky, kx]
+                    out[py * 2 + px, :, a, b] = acc
+    return out.reshape(4, Cout, 4 * Cin).to(out_dtype).contiguous()
+
+
+def upsample_fold_enabled() -> bool:
+    """DIFFSENSEI_UPSAMPLE_FOLD=0 keeps the nine-tap gather form of every Upsample2D convolution (A/B runs): by default an
+    exact x2 upsampler runs as four 2x2 phase convolutions on folded weights (4/9 of the MFMAs)."""
+    import os
+    return os.environ.get("DIFFSENSEI_UPSAMPLE_FOLD", "1") != "0"
+
+
 def gn_fusion_enabled() -> bool:
     """DIFFSENSEI_GN_FUSION=0 keeps the three-launch GroupNorm behind conv1 of every resnet (A/B runs): by default conv1's
     epilogue emits the partial sums norm2 needs (csrc/conv_halo.hip) and the GroupNorm reads its input once."""
@@ -246,6 +278,20 @@ class PackedUNet:
             if ln:
                 self.w[f"{t}.ff.net.0.proj.c_ln.g320"] = pack_geglu320(unpack_geglu(self.w[f"{t}.ff.net.0.proj.c_ln"]))
         return self.w[key], self.w[f"{t}.ff.net.0.proj.bias{sfx}.g320"], (self.w[f"{t}.ff.net.0.proj.c_ln.g320"] if ln else None)
+
+    def upsample_fold(self, name: str) -> Tensor:
+        """The four 2x2 phase weights [4, Cout, 4*Cin] of upsampler `name` (csrc/conv_halo.hip, "Phase mode") - made on first use
+        by the native fold kernel from the packed 3x3 weight, which stays for output sizes that are not exactly x2 (+16/9 of
+        the weight).  Host-only plans (CPU tensors, nothing is launched) take the torch model of the same sum."""
+        key = name + ".weight.up2fold"
+        if key not in self.w:
+            w3 = self.w[name + ".weight"]
+            if w3.is_cuda:
+                from . import ops
+                self.w[key] = ops.fold_upsample2x(w3)
+            else:
+                self.w[key] = fold_upsample2x_reference(w3)
+        return self.w[key]
 
     def nbytes(self) -> int:
         return sum(t.numel() * t.element_size() for t in self.w.values())
@@ -469,8 +515,13 @@ class UNetEngine:
         # i[10]: the chunk count the GroupNorm op is told; the launch checks it against the kernel it picks
         nch = int(_lib.load().ds_conv3x3_gn_chunks(self.B, H, W, Cin, Cout)) if gn_stats else 0
         assert not gn_stats or (nch > 0 and stride == 1 and not upsample)
+        wt = w[wname + ".weight"]
+        # an exact x2 upsampler runs as four 2x2 phase convolutions on folded weights (i[6] = 2); any other output size keeps the
+        # gather form on the 3x3 weight (i[6] = 1).  Decided by the sizes alone, never by the batch.
+        if upsample and tuple(out_hw) == (2 * H, 2 * W) and Cin % 64 == 0 and upsample_fold_enabled():
+            upsample, wt = 2, self.pk.upsample_fold(wname)
         ops.append(make_op("CONV3X3", i=(self.B, H, W, Cin, Cout, stride, upsample, self.pk.temb_total, out_hw[0], out_hw[1], nch),
-                           p=(x, w[wname + ".weight"], y, w[wname + ".bias"], rowbias, residual, self.gn_ws if gn_stats else None)))
+                           p=(x, wt, y, w[wname + ".bias"], rowbias, residual, self.gn_ws if gn_stats else None)))
 
     def _gemm(self, ops, x, wt, y, M, N, K, bias=None, residual=None, geglu=False, x2=None, K1=0, ln_stats=None, ln_c=None,
               stats_out=None, ln_partial=False, ln_nstrips=0, stats_strip=0):

@@ -204,6 +204,30 @@ def conv3x3(x: Tensor, w: Tensor, bias: Optional[Tensor], stride: int = 1, upsam
     return y
 
 
+def fold_upsample2x(w: Tensor) -> Tensor:
+    """w: [Cout,3,3,Cin] (= packed [Cout, 9*Cin]) -> [4, Cout, 4*Cin]: the four 2x2 phase weights of nearest x2 + conv3x3
+    (ds_fold_upsample2x_f16; torch model: `engine.fold_upsample2x_reference`)."""
+    _chk(w)
+    Cout, Cin = w.shape[0], w.numel() // (9 * w.shape[0])
+    out = torch.empty((4, Cout, 4 * Cin), dtype=torch.float16, device=w.device)
+    check(_lib.load().ds_fold_upsample2x_f16(_p(w), _p(out), Cout, Cin, _stream()), "ds_fold_upsample2x_f16")
+    return out
+
+
+def conv3x3_up2fold(x: Tensor, wfold: Tensor, bias: Optional[Tensor], rowbias: Optional[Tensor] = None,
+                    residual: Optional[Tensor] = None) -> Tensor:
+    """x: [B,H,W,Cin] NHWC, wfold: [4,Cout,4*Cin] from `fold_upsample2x` -> [B,2H,2W,Cout]: Upsample2D (nearest x2 + conv3x3)
+    as four 2x2 phase convolutions of x."""
+    _chk(x, wfold, bias, rowbias, residual)
+    B, H, W, Cin = x.shape
+    Cout = wfold.shape[1]
+    assert wfold.shape == (4, Cout, 4 * Cin), (tuple(wfold.shape), Cin)
+    y = torch.empty((B, 2 * H, 2 * W, Cout), dtype=torch.float16, device=x.device)
+    check(_lib.load().ds_conv3x3_up2fold_f16(_p(x), _p(wfold), _p(bias), _p(rowbias), 0 if rowbias is None else rowbias.shape[1],
+                                             _p(residual), _p(y), B, H, W, Cin, Cout, _stream()), "ds_conv3x3_up2fold_f16")
+    return y
+
+
 def groupnorm(x: Tensor, gamma: Tensor, beta: Tensor, groups: int, eps: float, silu: bool,
               x2: Optional[Tensor] = None) -> Tensor:
     """x: [B,HW,C1] (+ x2 [B,HW,C2] concatenated on channels) -> [B,HW,C1+C2]."""

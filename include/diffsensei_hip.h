@@ -211,6 +211,16 @@ int ds_conv3x3_f16(const void* x, const void* w, const void* bias, const void* r
 int ds_conv3x3_resize_f16(const void* x, const void* w, const void* bias, const void* rowbias, int64_t rowbias_ld,
                           const void* residual, void* y, int B, int H, int W, int Cin, int Cout, int Hout, int Wout,
                           void* stream);
+/* Upsample2D at exactly x2 without the arithmetic the nearest resize makes redundant: every 2x2 block of the upsampled
+ * image is one input pixel, so output pixel (2Y+py, 2X+px) is a 2x2 convolution of the INPUT with sums of the 3x3 taps
+ * (rows: py = 0 -> {0} | {1,2}, py = 1 -> {0,1} | {2}; columns alike) - 4 taps per pixel instead of 9.
+ * ds_fold_upsample2x_f16: packed w [Cout, 9*Cin] (k = (ky*3+kx)*Cin + ci) -> wfold [4][Cout, 4*Cin] (phase py*2+px,
+ * k = (a*2+b)*Cin + ci), summed in fp32 in (ky, kx) order and rounded to f16 once; done once per weight load.
+ * ds_conv3x3_up2fold_f16: y[B,2H,2W,Cout] from x[B,H,W,Cin] and wfold; same epilogue as ds_conv3x3_f16.  Cin % 64 == 0.
+ * Agrees with ds_conv3x3_f16(upsample = 1) to the extra f16 rounding of the folded weights, not bit for bit. */
+int ds_fold_upsample2x_f16(const void* w, void* wfold, int Cout, int Cin, void* stream);
+int ds_conv3x3_up2fold_f16(const void* x, const void* wfold, const void* bias, const void* rowbias, int64_t rowbias_ld,
+                           const void* residual, void* y, int B, int H, int W, int Cin, int Cout, void* stream);
 
 /* GroupNorm (+SiLU) over NHWC; x2 (may be NULL) supplies channels C1..C1+C2 (skip concat).  ws: device scratch
  * of ds_groupnorm_workspace_bytes(B, C1+C2) bytes. */
@@ -409,6 +419,7 @@ enum ds_opcode {
                                 the launch fails if the kernel it picks does not emit that format, e.g. 160 off gemm_t160_kernel) */
     DS_OP_CONV3X3 = 2,       /* p: x, w, y, bias, rowbias, residual, gn_partial (optional: GroupNorm workspace, see ds_conv3x3_gn_chunks)
                                 i: B H W Cin Cout stride upsample rowbias_ld Hout Wout (upsample only; 0 0 = 2H x 2W);
+                                   upsample == 2: exact x2 with the folded weights of ds_fold_upsample2x_f16 in p[1];
                                 i[10] = GroupNorm partial-sum chunks per image the plan expects (with p[6]: ds_conv3x3_gn_chunks at plan
                                 time, the GROUPNORM op's i[6]); the launch fails unless the kernel it picks writes exactly that many.
                                 0 = no count stated: the launch writes what its kernel writes (the caller asked ds_conv3x3_gn_chunks

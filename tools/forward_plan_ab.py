@@ -3,7 +3,8 @@
 variable of the plan builder (UPPERCASE: DIFFSENSEI_GN_FUSION) or a library option that the planner's host queries read
 (lowercase: gemm_t160) - same process, same weights, plans rebuilt per mode, rounds interleaved: per-kernel HIP-event table of
 both plans, the difference of the outputs, launches per forward.
-    python tools/forward_plan_ab.py 2 gemm_t160=1,0            python tools/forward_plan_ab.py 64 DIFFSENSEI_GN_FUSION=0,1 [latent]"""
+    python tools/forward_plan_ab.py 2 gemm_t160=1,0            python tools/forward_plan_ab.py 64 DIFFSENSEI_GN_FUSION=0,1 [latent]
+The same value twice (DIFFSENSEI_UPSAMPLE_FOLD=0,0) is an A/A run: the spread of its four rounds is the noise yardstick."""
 import ctypes as C
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -84,7 +85,7 @@ for rnd in range(2):
         tabs.setdefault(mode, []).append(table(eng))
 rel = ((outs[MODES[1]] - outs[MODES[0]]).norm() / outs[MODES[0]].norm()).item()
 print(f"UNet batch {B}, {LAT * 8} x {LAT * 8}: {KEY}={MODES[1]} vs {MODES[0]} output rel-L2 {rel:.3e}, bit-equal {bool(torch.equal(outs[MODES[0]], outs[MODES[1]]))}")
-for mode in MODES:
+for mode in dict.fromkeys(MODES):     # (an A/A run names one mode twice: its rounds are one list)
     best = min(tabs[mode], key=lambda t: t[1])
     print(f"{KEY}={mode}: forward {best[1]:.2f} ms (rounds: {[round(t[1], 2) for t in tabs[mode]]}), {best[2]} launches")
     shapes = best[0].pop("__shapes__")

@@ -8,6 +8,10 @@
     python tools/one_op.py t160 [reps]       gemm_t160_kernel: M=2048, N=1280, K=1280 + bias + residual
     python tools/one_op.py t160tall [reps]   gemm_t160_kernel<4,4> (128 x 160 tiles): M=2048, N=2560, K=1280 + bias (q|k of a batch-1 request)
     python tools/one_op.py g320 [reps]       gemm_g320_kernel: M=2048, N=10240 packed, K=1280 + bias, GEGLU (a batch-1 request's FF projection)
+    python tools/one_op.py up1280 [reps]     conv_halo256_kernel, nine-tap gather: the benchmark's level-2 upsampler, B=64, 32x32 -> 64x64, 1280 -> 1280
+    python tools/one_op.py up1280_fold       ... the same launch as four 2x2 phase convolutions on folded weights (ds_conv3x3_up2fold_f16)
+    python tools/one_op.py up640 | up640_fold   the level-1 upsampler, B=64, 64x64 -> 128x128, 640 -> 640
+  (the printed TF/s of every up* mode counts the ALGORITHMIC work, 2 M N 9 Cin; DS_ONE_OP_B overrides the batch of the up* modes)
 """
 import os
 import sys
@@ -27,6 +31,16 @@ if what in ("conv", "conv_b2"):
     x, w, b = R(B, H, H, C), R(C, 3, 3, C) * ((9 * C) ** -0.5) * 2, R(C)
     fn = lambda: ops.conv3x3(x, w, b)
     flop = 2.0 * B * H * H * C * C * 9
+elif what.startswith("up"):
+    C, H = (1280, 32) if "1280" in what else (640, 64)
+    B = int(os.environ.get("DS_ONE_OP_B", "64"))
+    x, w, b = R(B, H, H, C), R(C, 3, 3, C) * ((9 * C) ** -0.5) * 2, R(C)
+    if what.endswith("_fold"):
+        wf = ops.fold_upsample2x(w)
+        fn = lambda: ops.conv3x3_up2fold(x, wf, b)
+    else:
+        fn = lambda: ops.conv3x3(x, w, b, upsample=True)
+    flop = 2.0 * B * 4 * H * H * C * C * 9
 elif what == "t160":
     M, N, K = 2048, 1280, 1280
     x, w, b, r = R(M, K), R(N, K) * (K ** -0.5), R(N), R(M, N)
