@@ -21,6 +21,7 @@ import torch
 from . import _lib
 from ._lib import OP, DsOp, check
 from .attention_processor import mask_grid_size
+from .schedulers import KIND_DPM, KIND_EULER_ANCESTRAL
 from .unet_config import AttnSpec, ResnetSpec, UNetMangaConfig, build_topology
 
 Tensor = torch.Tensor
@@ -401,6 +402,12 @@ class UNetEngine:
         self.table.zero_()
         self.ctr = E(1, dtype=torch.int32)
         self.ctr.zero_()
+        # ---- sampler (`build_sampler`): the built (ns, kind, do_cfg) and the buffers only some kinds have
+        self._sampler_key = None
+        self.sampler_kind = None
+        self.prev_x0 = None                                     # DPM-Solver++: the previous step's x0
+        self.solver = None                                      # DPM-Solver++: the per-step solver rows
+        self.noise_seeds = None                                 # Euler Ancestral: one Philox seed per panel
         # ---- request-level derived tensors
         self.enc_txt = E(B, LP, xdim)
         self.enc_ip = E(B, LP, xdim)
@@ -787,32 +794,32 @@ class UNetEngine:
         if self.B != (2 * ns if do_cfg else ns):
             raise ValueError(f"engine batch {self.B} does not match num_samples {ns} (cfg={do_cfg})")
         key = (ns, kind, do_cfg)
-        if getattr(self, "_sampler_key", None) == key:
+        if self._sampler_key == key:
             return
         HW = self.H * self.W
         self.latents = self._alloc((ns, self.cfg.in_channels, self.H, self.W), torch.float16)
         self.prep_plan = Plan([make_op("PREP_INPUT", i=(ns, HW, int(do_cfg)),
                                        p=(self.latents, self.x_in, self.table, self.ctr))], self.keep)
-        dpm = ()
-        if kind == 2:  # DPM-Solver++: the previous step's x0 + the per-step solver rows (allocated once per shape)
-            if getattr(self, "prev_x0", None) is None or self.prev_x0.shape != self.latents.shape:
+        # the buffers of this kind, allocated once per shape and kept when another kind is built in between
+        if kind == KIND_DPM:
+            if self.prev_x0 is None or self.prev_x0.shape != self.latents.shape:
                 self.prev_x0 = self._alloc(tuple(self.latents.shape), torch.float16)
-            if getattr(self, "solver", None) is None:
+            if self.solver is None:
                 self.solver = self._alloc((self.table.shape[0], 8), torch.float32)
                 self.solver.zero_()
-            dpm = (self.prev_x0, self.solver)
-        if kind == 3:  # Euler Ancestral: one Philox seed per panel, in the op's next free pointer slot (p[7])
-            if getattr(self, "noise_seeds", None) is None or self.noise_seeds.shape[0] != ns:
+        if kind == KIND_EULER_ANCESTRAL:
+            if self.noise_seeds is None or self.noise_seeds.shape[0] != ns:
                 self.noise_seeds = self._alloc((ns,), torch.int64)
                 self.noise_seeds.zero_()
-            dpm = (None, None, self.noise_seeds)
+        prev_x0, solver = (self.prev_x0, self.solver) if kind == KIND_DPM else (None, None)
+        noise_seeds = self.noise_seeds if kind == KIND_EULER_ANCESTRAL else None
         step_ops = list(self.forward_ops) + [
             make_op("SAMPLER_STEP", i=(ns, HW, kind, int(do_cfg)),
-                    p=(self.eps, self.latents, self.x_in, self.table, self.ctr) + dpm),
+                    p=(self.eps, self.latents, self.x_in, self.table, self.ctr, prev_x0, solver, noise_seeds)),
             make_op("ADVANCE", p=(self.ctr,)),
         ]
         self.step_plan = Plan(step_ops, self.keep)
-        self._sampler_key = key
+        self._sampler_key, self.sampler_kind = key, kind
 
     def load_schedule(self, table_rows: Tensor, solver_rows: Optional[Tensor] = None, noise_seeds=None):
         """table_rows: fp32 [n_steps, 8]; solver_rows: fp32 [n_steps, 8], the DPM-Solver++ rows (kind 2 only);
@@ -822,10 +829,10 @@ class UNetEngine:
         n = table_rows.shape[0]
         if n > self.table.shape[0]:
             raise ValueError("too many steps for the scalar table")
-        kind = getattr(self, "_sampler_key", (None, None))[1]
-        if (solver_rows is not None) != (kind == 2):
+        kind = self.sampler_kind
+        if (solver_rows is not None) != (kind == KIND_DPM):
             raise ValueError(f"solver rows are given exactly for a DPM-Solver++ sampler (built kind: {kind})")
-        if (noise_seeds is not None) != (kind == 3):
+        if (noise_seeds is not None) != (kind == KIND_EULER_ANCESTRAL):
             raise ValueError(f"noise seeds are given exactly for an Euler Ancestral sampler (built kind: {kind})")
         if noise_seeds is not None:
             seeds = torch.as_tensor(noise_seeds, dtype=torch.int64).reshape(-1)

@@ -8,7 +8,8 @@ The reference inherits it from diffusers' `DiffusionPipeline`; diffusers is not 
 directory layout [3P] is read directly:
 
     model_index.json                      component table {name: [library, class]} + pipeline flags
-    scheduler/scheduler_config.json       `_class_name` EulerDiscreteScheduler | DDIMScheduler + its constructor arguments
+    scheduler/scheduler_config.json       `_class_name` EulerDiscreteScheduler | DDIMScheduler | DPMSolverMultistepScheduler
+                                          | EulerAncestralDiscreteScheduler + its constructor arguments
     vae/config.json + weights             AutoencoderKL (only the decoder + post_quant_conv are used on this path)
     text_encoder/, text_encoder_2/        transformers CLIPTextModel / CLIPTextModelWithProjection (config.json + weights)
     tokenizer/, tokenizer_2/              transformers CLIPTokenizer files (loaded with transformers, host only)
@@ -70,12 +71,8 @@ class _Loaded:
 
 
 def load_scheduler(folder: str):
-    from .schedulers import (DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,
-                             EulerDiscreteScheduler)
+    from .schedulers import SCHEDULERS as classes
     cfg = read_json(os.path.join(folder, "scheduler_config.json"))
-    classes = {"EulerDiscreteScheduler": EulerDiscreteScheduler, "DDIMScheduler": DDIMScheduler,
-               "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler,
-               "EulerAncestralDiscreteScheduler": EulerAncestralDiscreteScheduler}
     name = cfg.get("_class_name", "EulerDiscreteScheduler")
     if name not in classes:
         raise NotImplementedError(f"scheduler {name}: the MI355X sampler kernel implements {sorted(classes)}")

@@ -380,13 +380,28 @@ def add_time_ids(text_embeds: Tensor, time_ids: Tensor, dim: int, flip: bool = T
     return out
 
 
+def _chk_seeds(seeds: Optional[Tensor], ns: int) -> None:
+    _chk(seeds, dtype=torch.int64)
+    if seeds is not None and tuple(seeds.shape) != (ns,):
+        raise ValueError(f"seeds {tuple(seeds.shape)}: one int64 per panel, ({ns},), is needed")
+
+
+def _sampler_step_dims(eps: Tensor, latents: Tensor, model_in: Tensor, table: Tensor, solver: Optional[Tensor] = None,
+                       prev_x0: Optional[Tensor] = None, seeds: Optional[Tensor] = None) -> Tuple[int, int]:
+    """The checks the three entry points of `sampler_step_kernel` share; returns (ns, HW)."""
+    _chk(eps, latents, model_in, prev_x0)
+    _chk(table, solver, dtype=torch.float32)
+    if prev_x0 is not None and prev_x0.shape != latents.shape:
+        raise ValueError(f"prev_x0 {tuple(prev_x0.shape)} must have the latents' shape {tuple(latents.shape)}")
+    ns = latents.shape[0]
+    _chk_seeds(seeds, ns)
+    return ns, latents.shape[2] * latents.shape[3]
+
+
 def cfg_sampler_step(eps: Tensor, latents: Tensor, model_in: Tensor, table: Tensor, kind: int, do_cfg: bool = True,
                      ctr: Optional[Tensor] = None) -> None:
     """eps: [2ns,HW,4] NHWC; latents: [ns,4,H,W] NCHW (in place); model_in: [2ns,HW,4]."""
-    _chk(eps, latents, model_in)
-    _chk(table, dtype=torch.float32)
-    ns = latents.shape[0]
-    HW = latents.shape[2] * latents.shape[3]
+    ns, HW = _sampler_step_dims(eps, latents, model_in, table)
     check(_lib.load().ds_cfg_sampler_step_f16(_p(eps), _p(latents), _p(model_in), _p(table), _p(ctr), ns, HW, kind,
                                               int(do_cfg), _stream()), "ds_cfg_sampler_step_f16")
 
@@ -395,31 +410,16 @@ def cfg_dpm_step(eps: Tensor, latents: Tensor, model_in: Tensor, table: Tensor, 
                  do_cfg: bool = True, ctr: Optional[Tensor] = None) -> None:
     """DPM-Solver++ step: eps [2ns,HW,4] NHWC; latents, prev_x0: [ns,4,H,W] NCHW (both in place); model_in: [2ns,HW,4];
     solver: fp32 rows [n,8] (include/diffsensei_hip.h)."""
-    _chk(eps, latents, model_in, prev_x0)
-    _chk(table, solver, dtype=torch.float32)
-    if prev_x0.shape != latents.shape:
-        raise ValueError(f"prev_x0 {tuple(prev_x0.shape)} must have the latents' shape {tuple(latents.shape)}")
-    ns = latents.shape[0]
-    HW = latents.shape[2] * latents.shape[3]
+    ns, HW = _sampler_step_dims(eps, latents, model_in, table, solver=solver, prev_x0=prev_x0)
     check(_lib.load().ds_cfg_dpm_step_f16(_p(eps), _p(latents), _p(model_in), _p(table), _p(solver), _p(prev_x0),
                                           _p(ctr), ns, HW, int(do_cfg), _stream()), "ds_cfg_dpm_step_f16")
-
-
-def _chk_seeds(seeds: Optional[Tensor], ns: int) -> None:
-    _chk(seeds, dtype=torch.int64)
-    if seeds is not None and tuple(seeds.shape) != (ns,):
-        raise ValueError(f"seeds {tuple(seeds.shape)}: one int64 per panel, ({ns},), is needed")
 
 
 def cfg_sampler_step_noise(eps: Tensor, latents: Tensor, model_in: Tensor, table: Tensor, seeds: Optional[Tensor],
                            kind: int, do_cfg: bool = True, ctr: Optional[Tensor] = None) -> None:
     """`cfg_sampler_step` with the per-panel Philox seeds (int64 [ns]) that kind 3, Euler Ancestral, draws its noise
     from: the noise of panel n at this launch is a function of (seeds[n], pixel, *ctr) only."""
-    _chk(eps, latents, model_in)
-    _chk(table, dtype=torch.float32)
-    ns = latents.shape[0]
-    HW = latents.shape[2] * latents.shape[3]
-    _chk_seeds(seeds, ns)
+    ns, HW = _sampler_step_dims(eps, latents, model_in, table, seeds=seeds)
     check(_lib.load().ds_cfg_sampler_step_noise_f16(_p(eps), _p(latents), _p(model_in), _p(table), _p(seeds), _p(ctr),
                                                     ns, HW, kind, int(do_cfg), _stream()),
           "ds_cfg_sampler_step_noise_f16")

@@ -376,7 +376,7 @@ class DiffSenseiPipeline:
         # a stochastic sampler's per-panel Philox seeds, drawn AFTER the initial latents: a deterministic scheduler
         # consumes the generator exactly as before, and a given generator starts Euler Ancestral from Euler's latents
         seeds = None
-        if getattr(self.scheduler, "stochastic", False):
+        if self.scheduler.stochastic:
             seeds = [int(v) for v in noise_seeds] if noise_seeds is not None else draw_noise_seeds(num_samples, generator)
             if len(seeds) != num_samples or any(v < 0 or v >= 2 ** 63 for v in seeds):
                 raise ValueError(f"`noise_seeds`: {num_samples} integers in [0, 2**63) are needed, got {seeds}")
@@ -427,7 +427,7 @@ class DiffSenseiPipeline:
         eng.set_request(enc, add_text_embeds, add_time_ids, bbox, dialog_pixel_boxes(dialog, H, W), float(ip_scale))
         solver = self.scheduler.solver_table()             # DPM-Solver++ rows; None for Euler / DDIM
         # the panels' own seeds, in batch order: a panel's noise does not depend on the requests batched beside it
-        seeds = [v for c in conds for v in c["noise_seeds"]] if getattr(self.scheduler, "stochastic", False) else None
+        seeds = [v for c in conds for v in c["noise_seeds"]] if self.scheduler.stochastic else None
         eng.load_schedule(torch.from_numpy(self.scheduler.coef_table(float(guidance_scale))),
                           None if solver is None else torch.from_numpy(solver), seeds)
         eng.latents.copy_(lat)

@@ -4,14 +4,18 @@
 
 Host side = the schedule tables only (a few hundred scalars computed once per `set_timesteps`, in numpy exactly
 where diffusers uses numpy).  All per-element arithmetic (CFG combine, the update, the next step's input scaling)
-runs in ONE HIP kernel (`ds_cfg_sampler_step_f16`, `ds_cfg_dpm_step_f16`) reading a per-step scalar table the engine
-indexes with a device-side step counter — the reference issues 5+ elementwise launches per step here.
+runs in ONE HIP kernel (`sampler_step_kernel`, switched by `kind`) reading a per-step scalar table the engine indexes
+with a device-side step counter — the reference issues 5+ elementwise launches per step here.
 
-Every class has diffusers' `.config` and `from_config(config, **overrides)`, so the usual scheduler swap
-`pipe.scheduler = DPMSolverMultistepScheduler.from_config(pipe.scheduler.config, use_karras_sigmas=True)` works.
+`_Scheduler` is the whole host protocol: config handling (`.config`, `from_config(config, **overrides)`, so the usual
+swap `pipe.scheduler = DPMSolverMultistepScheduler.from_config(pipe.scheduler.config, use_karras_sigmas=True)` works),
+the training sigmas and their interpolation, the timestep -> row lookup and the stand-alone `scale_model_input` /
+`step`.  A sampler is a subclass with its `kind`, its config keys as class data, `set_timesteps` and `coef_table`
+(DPM-Solver++ adds `solver_table`); tests/golden/scheduler_tables.npz pins every table and every refusal
+(tools/dump_scheduler_tables.py).
 
 `EulerAncestralDiscreteScheduler` is the one stochastic sampler: its per-step noise is drawn inside the step kernel
-(`ds_cfg_sampler_step_noise_f16`) from one int64 seed per panel, `draw_noise_seeds`.
+from one int64 seed per panel, `draw_noise_seeds`.
 """
 from __future__ import annotations
 
@@ -36,82 +40,104 @@ class _Config(dict):
             raise AttributeError(key) from None
 
 
-class _ConfigMixin:
-    @classmethod
-    def _config_keys(cls):
-        raise NotImplementedError
+def _timestep_grid(spacing: str, T: int, n: int, steps_offset: int) -> np.ndarray:
+    """diffusers' n-point fp32 grid of EulerDiscrete / EulerAncestral / DDIM [3P] (DDIM casts it to int64)."""
+    if spacing == "linspace":
+        return np.linspace(0, T - 1, n, dtype=np.float32)[::-1].copy()
+    if spacing == "leading":
+        return (np.arange(0, n) * (T // n)).round()[::-1].copy().astype(np.float32) + steps_offset
+    return np.arange(T, 0, -T / n).round().copy().astype(np.float32) - 1   # trailing
+
+
+class _Scheduler:
+    kind = -1
+    order = 1
+    stochastic = False   # True: the pipeline draws one Philox seed per panel (`draw_noise_seeds`) for `load_schedule`
+    # scheduler_config.json handling, as class data.  `_DEFAULTS`: the constructor arguments of the diffusers class [3P]
+    # that are kept in `.config`, with their defaults; every other key is another class's and is ignored.  `_SUPPORTED`:
+    # the keys that CHANGE the schedule or the update rule, with the values the device kernel implements - anything else
+    # would sample on a different schedule than the reference's scheduler without a word, so it is refused.  A
+    # `_SUPPORTED` key outside `_DEFAULTS` is refused by the constructor and dropped by `from_config`.
+    _DEFAULTS: dict = {}
+    _SUPPORTED: dict = {}
+
+    def __init__(self, **kwargs):
+        cfg = _Config(self._DEFAULTS)
+        cfg.update({k: v for k, v in kwargs.items() if k in cfg})
+        for key, ok in self._SUPPORTED.items():
+            value = cfg[key] if key in cfg else kwargs.get(key, ok[0])
+            if isinstance(value, (list, tuple)) or value not in ok:
+                raise NotImplementedError(f"scheduler config {key}={value!r}: the MI355X sampler kernel implements "
+                                          f"{type(self).__name__} with {key} in {ok} only")
+        self.config = cfg
+        self.T = int(cfg.num_train_timesteps)
+        self.steps_offset = cfg.steps_offset
+        betas = torch.linspace(cfg.beta_start ** 0.5, cfg.beta_end ** 0.5, self.T, dtype=torch.float32) ** 2  # scaled_linear
+        self.alphas_cumprod = torch.cumprod(1.0 - betas, dim=0)
+        self.timesteps = None
+        self.num_inference_steps = None
+        self._step_index = 0
 
     @classmethod
     def from_config(cls, config=None, **overrides):
         """diffusers `SchedulerMixin.from_config`: keys the class does not take are ignored (another class's config)."""
         merged = dict(config or {})
         merged.update(overrides)
-        keys = cls._config_keys()
-        return cls(**{k: v for k, v in merged.items() if k in keys})
+        return cls(**{k: v for k, v in merged.items() if k in cls._DEFAULTS})
 
+    # -- pieces of `set_timesteps`
+    def _train_sigmas(self) -> np.ndarray:
+        ac = self.alphas_cumprod.numpy()
+        return ((1 - ac) / ac) ** 0.5
 
-def _alphas_cumprod(T: int, beta_start: float, beta_end: float) -> torch.Tensor:
-    betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, T, dtype=torch.float32) ** 2  # scaled_linear
-    return torch.cumprod(1.0 - betas, dim=0)
+    def _interp_sigmas(self, ts: np.ndarray) -> np.ndarray:
+        sig = self._train_sigmas()
+        return np.interp(ts, np.arange(0, len(sig)), sig)
 
-
-class _SchedulerBase(_ConfigMixin):
-    kind = -1
-    order = 1
-    _CONFIG_FIXED = ()  # the `_FIXED` keys that are constructor arguments of the diffusers class (kept in `.config`)
-    _FIXED = {"trained_betas": (None,), "rescale_betas_zero_snr": (False,), "use_karras_sigmas": (False,),
-              "use_exponential_sigmas": (False,), "use_beta_sigmas": (False,), "interpolation_type": ("linear",),
-              "final_sigmas_type": ("zero",), "timestep_type": ("discrete",), "sigma_min": (None,), "sigma_max": (None,),
-              "clip_sample": (False,), "set_alpha_to_one": (False,), "thresholding": (False,)}
-
-    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
-                 steps_offset=1, timestep_spacing="leading", prediction_type="epsilon", **unused):
-        if beta_schedule != "scaled_linear" or timestep_spacing != "leading" or prediction_type != "epsilon":
-            raise NotImplementedError("only the SDXL scheduler configuration (scaled_linear / leading / epsilon)")
-        # scheduler_config.json keys of diffusers' Euler / DDIM classes [3P] that CHANGE the sigma schedule or the update
-        # rule: only the value the device kernel implements is accepted - anything else would sample on a different
-        # schedule than the reference's scheduler without a word.  Keys that do not touch the arithmetic are ignored.
-        for key, ok in self._FIXED.items():
-            if key in unused and unused[key] not in ok:
-                raise NotImplementedError(f"scheduler config {key}={unused[key]!r}: the MI355X sampler kernel implements "
-                                          f"{key} in {ok} only")
-        self.config = _Config(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
-                              beta_schedule=beta_schedule, steps_offset=steps_offset, timestep_spacing=timestep_spacing,
-                              prediction_type=prediction_type,
-                              **{k: unused.get(k, self._FIXED[k][0]) for k in self._CONFIG_FIXED})
-        self.T = num_train_timesteps
-        self.steps_offset = steps_offset
-        self.alphas_cumprod = _alphas_cumprod(num_train_timesteps, beta_start, beta_end)
-        self.timesteps = None
-        self.num_inference_steps = None
+    def _set_grid(self, ts: np.ndarray, device):
+        self.timesteps_np = ts
+        self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
+        self.num_inference_steps = len(ts)
         self._step_index = 0
-        self._dev_table = None
-
-    @classmethod
-    def _config_keys(cls):
-        return ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "steps_offset", "timestep_spacing",
-                "prediction_type") + cls._CONFIG_FIXED
 
     # -- table for the engine: rows [n_steps, 8] = {t, c_in_div, k0..k3, c_in_div_next, guidance}
     def coef_table(self, guidance_scale: float) -> np.ndarray:
         raise NotImplementedError
 
+    def _coef_frame(self, guidance_scale: float, sigmas: Optional[np.ndarray] = None) -> np.ndarray:
+        """The table with k1..k3 left 0.  `sigmas` (fp32, n + 1): k0 = sigma and the model input is x / sqrt(sigma^2 + 1)
+        (fp32 like the 0-dim sigma tensor arithmetic in diffusers); without them the model input is x."""
+        if self.num_inference_steps is None:
+            raise RuntimeError("call set_timesteps first")
+        n = self.num_inference_steps
+        tab = np.zeros((n, 8), dtype=np.float32)
+        div = np.ones(n + 1, dtype=np.float32) if sigmas is None else ((sigmas ** 2 + 1) ** 0.5).astype(np.float32)
+        tab[:, 0] = self.timesteps_np
+        tab[:, 1] = div[:n]
+        if sigmas is not None:
+            tab[:, 2] = sigmas[:n]
+        tab[:, 6] = div[1:n + 1]
+        tab[:, 7] = guidance_scale
+        return tab
+
     # -- second per-step table (DPM-Solver++ only; see include/diffsensei_hip.h)
     def solver_table(self) -> Optional[np.ndarray]:
         return None
 
-    def _table_on(self, device, guidance: float) -> torch.Tensor:
-        return torch.from_numpy(self.coef_table(guidance)).to(device)
-
-    def _index_of(self, t) -> int:
-        tv = float(t)
-        idx = np.nonzero(np.isclose(np.asarray(self.timesteps_np, dtype=np.float64), tv))[0]
-        return int(idx[0]) if len(idx) else self._step_index
-
     # -- stand-alone protocol (one kernel launch each; the pipeline's fused loop does not go through these)
+    def _index_of(self, timestep, default: int) -> int:
+        """diffusers `index_for_timestep`: the row of `timestep` - the second one when a timestep repeats (a Karras grid
+        rounded to integers can) - or `default` when there is none."""
+        idx = np.nonzero(np.isclose(np.asarray(self.timesteps_np, dtype=np.float64), float(timestep)))[0]
+        if len(idx) == 0:
+            return default
+        return int(idx[1] if len(idx) > 1 else idx[0])
+
+    def _step_row(self, timestep) -> int:
+        return self._index_of(timestep, self._step_index)
+
     def scale_model_input(self, sample: torch.Tensor, timestep) -> torch.Tensor:
-        i = self._index_of(timestep)
-        div = float(self.coef_table(1.0)[i, 1])
+        div = float(self.coef_table(1.0)[self._step_row(timestep), 1])
         if div == 1.0:
             return sample
         ns, c, h, w = sample.shape
@@ -120,69 +146,81 @@ class _SchedulerBase(_ConfigMixin):
         ops.prepare_model_input(sample.contiguous(), tmp, table, do_cfg=False)
         return ops.nhwc_to_nchw(tmp).reshape(ns, c, h, w)
 
-    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, return_dict: bool = True, **kw):
-        """model_output: the (already CFG-combined) noise prediction, NCHW like `sample`."""
-        i = self._index_of(timestep)
-        row = self.coef_table(1.0)[i:i + 1].copy()
-        table = torch.from_numpy(row).to(sample.device)
+    def _step_extras(self, i: int, lat: torch.Tensor, generator) -> dict:
+        """What row i of this sampler reads besides the table: `solver` + `prev_x0` (DPM-Solver++) or `seeds`
+        (Euler Ancestral), on `lat`'s device.  Both tables are indexed with the step counter, here i."""
+        return {}
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, *, generator=None,
+             return_dict: bool = True, **kw):
+        """model_output: the (already CFG-combined) noise prediction, NCHW like `sample`.  Computes in fp16 like the
+        pipeline's fused loop.  `generator`: where a stochastic sampler draws its per-panel seeds from."""
+        if self.num_inference_steps is None:
+            raise RuntimeError("call set_timesteps first")
+        i = self._step_row(timestep)
         ns, c, h, w = sample.shape
+        dev = sample.device
         eps = ops.nchw_to_nhwc(model_output.to(torch.float16).reshape(ns, c, h * w).contiguous())
         lat = sample.to(torch.float16).contiguous().clone()
-        scratch = torch.empty((ns, h * w, c), dtype=torch.float16, device=sample.device)
-        ops.cfg_sampler_step(eps, lat, scratch, table, self.kind, do_cfg=False)
+        scratch = torch.empty((ns, h * w, c), dtype=torch.float16, device=dev)
+        table = torch.from_numpy(self.coef_table(1.0)).to(dev)
+        ctr = torch.tensor([i], dtype=torch.int32, device=dev)
+        _launch_step(eps, lat, scratch, table, self.kind, ctr, **self._step_extras(i, lat, generator))
         self._step_index = i + 1
         return (lat,) if not return_dict else {"prev_sample": lat}
 
 
-class EulerDiscreteScheduler(_SchedulerBase):
+def _launch_step(eps, lat, scratch, table, kind, ctr, solver=None, prev_x0=None, seeds=None):
+    """One `sampler_step_kernel` launch through the C entry point that carries the given extras."""
+    if solver is not None:
+        ops.cfg_dpm_step(eps, lat, scratch, table, solver, prev_x0, do_cfg=False, ctr=ctr)
+    elif seeds is not None:
+        ops.cfg_sampler_step_noise(eps, lat, scratch, table, seeds, kind, do_cfg=False, ctr=ctr)
+    else:
+        ops.cfg_sampler_step(eps, lat, scratch, table, kind, do_cfg=False, ctr=ctr)
+
+
+# Euler / DDIM: the SDXL configuration as defaults, and nothing but it accepted
+_SDXL = dict(num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", steps_offset=1,
+             timestep_spacing="leading", prediction_type="epsilon")
+_SDXL_ONLY = {"beta_schedule": ("scaled_linear",), "timestep_spacing": ("leading",), "prediction_type": ("epsilon",),
+              "trained_betas": (None,), "rescale_betas_zero_snr": (False,), "use_karras_sigmas": (False,),
+              "use_exponential_sigmas": (False,), "use_beta_sigmas": (False,), "interpolation_type": ("linear",),
+              "final_sigmas_type": ("zero",), "timestep_type": ("discrete",), "sigma_min": (None,), "sigma_max": (None,),
+              "clip_sample": (False,), "set_alpha_to_one": (False,), "thresholding": (False,)}
+
+
+class EulerDiscreteScheduler(_Scheduler):
     """diffusers EulerDiscreteScheduler [3P] (deterministic: s_churn = 0, final sigma 0, linear interpolation)."""
     kind = KIND_EULER
-    _CONFIG_FIXED = ("trained_betas", "use_karras_sigmas", "use_exponential_sigmas", "use_beta_sigmas",
-                     "interpolation_type", "sigma_min", "sigma_max", "timestep_type", "rescale_betas_zero_snr",
-                     "final_sigmas_type")
+    _DEFAULTS = dict(_SDXL, trained_betas=None, use_karras_sigmas=False, use_exponential_sigmas=False,
+                     use_beta_sigmas=False, interpolation_type="linear", sigma_min=None, sigma_max=None,
+                     timestep_type="discrete", rescale_betas_zero_snr=False, final_sigmas_type="zero")
+    _SUPPORTED = _SDXL_ONLY
 
     def set_timesteps(self, num_inference_steps: int, device=None):
-        n = num_inference_steps
-        step_ratio = self.T // n
-        ts = (np.arange(0, n) * step_ratio).round()[::-1].copy().astype(np.float32) + self.steps_offset
-        ac = self.alphas_cumprod.numpy()
-        sig = np.array(((1 - ac) / ac) ** 0.5)
-        sig = np.interp(ts, np.arange(0, len(sig)), sig)
-        self.sigmas = np.concatenate([sig, [0.0]]).astype(np.float32)
-        self.timesteps_np = ts
-        self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
-        self.num_inference_steps = n
+        ts = _timestep_grid("leading", self.T, num_inference_steps, self.steps_offset)
+        self.sigmas = np.concatenate([self._interp_sigmas(ts), [0.0]]).astype(np.float32)
         self.init_noise_sigma = float((self.sigmas.max() ** 2 + 1) ** 0.5)
-        self._step_index = 0
+        self._set_grid(ts, device)
 
     def coef_table(self, guidance_scale: float) -> np.ndarray:
-        n = self.num_inference_steps
-        tab = np.zeros((n, 8), dtype=np.float32)
-        s = self.sigmas.astype(np.float32)
-        div = ((s ** 2 + 1) ** 0.5).astype(np.float32)   # fp32 like the 0-dim sigma tensor arithmetic in diffusers
-        tab[:, 0] = self.timesteps_np
-        tab[:, 1] = div[:n]
-        tab[:, 2] = s[:n]
-        tab[:, 3] = s[1:n + 1]
-        tab[:, 6] = div[1:n + 1]
-        tab[:, 7] = guidance_scale
+        tab = self._coef_frame(guidance_scale, self.sigmas)
+        tab[:, 3] = self.sigmas[1:]
         return tab
 
 
-class DDIMScheduler(_SchedulerBase):
+class DDIMScheduler(_Scheduler):
     """diffusers DDIMScheduler [3P], eta = 0, clip_sample False, set_alpha_to_one False."""
     kind = KIND_DDIM
-    _CONFIG_FIXED = ("trained_betas", "clip_sample", "set_alpha_to_one", "thresholding", "rescale_betas_zero_snr")
     init_noise_sigma = 1.0
+    _DEFAULTS = dict(_SDXL, trained_betas=None, clip_sample=False, set_alpha_to_one=False, thresholding=False,
+                     rescale_betas_zero_snr=False)
+    _SUPPORTED = _SDXL_ONLY
 
     def set_timesteps(self, num_inference_steps: int, device=None):
-        n = num_inference_steps
-        step_ratio = self.T // n
-        ts = (np.arange(0, n) * step_ratio).round()[::-1].copy().astype(np.int64) + self.steps_offset
-        self.timesteps_np = ts
-        self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
-        self.num_inference_steps = n
-        self._step_index = 0
+        ts = _timestep_grid("leading", self.T, num_inference_steps, self.steps_offset)
+        self._set_grid(ts.astype(np.int64), device)
 
     def coef_table(self, guidance_scale: float) -> np.ndarray:
         n = self.num_inference_steps
@@ -196,7 +234,15 @@ class DDIMScheduler(_SchedulerBase):
         return tab
 
 
-class DPMSolverMultistepScheduler(_ConfigMixin):
+# DPM-Solver++ / Euler Ancestral: diffusers' own constructor defaults (linear betas: NOT the SDXL schedule, so a bare config
+# is refused; the usual way in is `from_config` of the pipeline's scheduler), and any of the three spacings
+_DIFFUSERS = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                  prediction_type="epsilon", timestep_spacing="linspace", steps_offset=0, rescale_betas_zero_snr=False)
+_DIFFUSERS_SUPPORTED = {"beta_schedule": ("scaled_linear",), "trained_betas": (None,), "prediction_type": ("epsilon",),
+                        "timestep_spacing": ("leading", "linspace", "trailing"), "rescale_betas_zero_snr": (False,)}
+
+
+class DPMSolverMultistepScheduler(_Scheduler):
     """diffusers DPMSolverMultistepScheduler [3P]: DPM-Solver++ (algorithm_type "dpmsolver++"), multistep, solver_order
     1 or 2, solver_type "midpoint" or "heun", epsilon prediction, deterministic.
 
@@ -206,50 +252,34 @@ class DPMSolverMultistepScheduler(_ConfigMixin):
     is decided here, per row, so a captured step graph needs no host logic.  Scalars are 0-dim fp32 torch values
     computed in diffusers' order; the last row of a zero final sigma gives a = 0, b = -1 (lambda_t = +inf, no NaN)."""
     kind = KIND_DPM
-    order = 1
     init_noise_sigma = 1.0
-    # diffusers' constructor defaults for this class (linear betas: NOT the SDXL schedule, so a bare config is refused)
-    _DEFAULTS = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
-                     trained_betas=None, solver_order=2, prediction_type="epsilon", thresholding=False,
-                     dynamic_thresholding_ratio=0.995, sample_max_value=1.0, algorithm_type="dpmsolver++",
-                     solver_type="midpoint", lower_order_final=True, euler_at_final=False, use_karras_sigmas=False,
-                     use_exponential_sigmas=False, use_beta_sigmas=False, use_lu_lambdas=False, use_flow_sigmas=False,
-                     flow_shift=1.0, final_sigmas_type="zero", lambda_min_clipped=-float("inf"), variance_type=None,
-                     timestep_spacing="linspace", steps_offset=0, rescale_betas_zero_snr=False)
-    # keys whose other values change the schedule or the update rule: only what the device kernel implements is accepted
-    _SUPPORTED = {"beta_schedule": ("scaled_linear",), "trained_betas": (None,), "solver_order": (1, 2),
-                  "prediction_type": ("epsilon",), "thresholding": (False,), "algorithm_type": ("dpmsolver++",),
-                  "solver_type": ("midpoint", "heun"), "use_exponential_sigmas": (False,), "use_beta_sigmas": (False,),
-                  "use_lu_lambdas": (False,), "use_flow_sigmas": (False,), "final_sigmas_type": ("zero", "sigma_min"),
-                  "variance_type": (None,), "timestep_spacing": ("leading", "linspace", "trailing"),
-                  "rescale_betas_zero_snr": (False,)}
+    _DEFAULTS = dict(_DIFFUSERS, solver_order=2, thresholding=False, dynamic_thresholding_ratio=0.995, sample_max_value=1.0,
+                     algorithm_type="dpmsolver++", solver_type="midpoint", lower_order_final=True, euler_at_final=False,
+                     use_karras_sigmas=False, use_exponential_sigmas=False, use_beta_sigmas=False, use_lu_lambdas=False,
+                     use_flow_sigmas=False, flow_shift=1.0, final_sigmas_type="zero", lambda_min_clipped=-float("inf"),
+                     variance_type=None)
+    _SUPPORTED = dict(_DIFFUSERS_SUPPORTED, solver_order=(1, 2), thresholding=(False,), algorithm_type=("dpmsolver++",),
+                      solver_type=("midpoint", "heun"), use_exponential_sigmas=(False,), use_beta_sigmas=(False,),
+                      use_lu_lambdas=(False,), use_flow_sigmas=(False,), final_sigmas_type=("zero", "sigma_min"),
+                      variance_type=(None,))
 
     def __init__(self, **kwargs):
-        cfg = _Config(self._DEFAULTS)
-        cfg.update({k: v for k, v in kwargs.items() if k in self._DEFAULTS})   # other keys: not this class's (ignored)
-        for key, ok in self._SUPPORTED.items():
-            if isinstance(cfg[key], (list, tuple)) or cfg[key] not in ok:
-                raise NotImplementedError(f"scheduler config {key}={cfg[key]!r}: the MI355X DPM-Solver++ kernel "
-                                          f"implements {key} in {ok} only")
-        lmc = float(cfg["lambda_min_clipped"])
+        super().__init__(**kwargs)
+        # the one key judged by value, not by membership: whatever `float` reads as -inf (JSON's -Infinity included)
+        lmc = float(self.config["lambda_min_clipped"])
         if not (math.isinf(lmc) and lmc < 0):
             raise NotImplementedError(f"scheduler config lambda_min_clipped={lmc!r}: only -inf (no clipping)")
-        self.config = cfg
-        self.T = int(cfg["num_train_timesteps"])
-        self.alphas_cumprod = _alphas_cumprod(self.T, cfg["beta_start"], cfg["beta_end"])
-        self.timesteps = None
         self.sigmas = None
-        self.num_inference_steps = None
         self.lower_order_nums = 0
-        self._step_index = None
         self._prev_x0 = None
 
-    @classmethod
-    def _config_keys(cls):
-        return tuple(cls._DEFAULTS)
+    def _train_sigmas(self) -> np.ndarray:
+        ac = self.alphas_cumprod    # torch arithmetic, where diffusers' class has it: an ulp from numpy's at a few t
+        return np.array(((1 - ac) / ac) ** 0.5)
 
     def set_timesteps(self, num_inference_steps: int, device=None):
-        """diffusers `set_timesteps` (lambda_min_clipped = -inf, so the last usable timestep is num_train_timesteps)."""
+        """diffusers `set_timesteps` (lambda_min_clipped = -inf, so the last usable timestep is num_train_timesteps).
+        This class's grid is its own: n + 1 points with the last dropped, and rounding AFTER the Karras map."""
         cfg, n, T = self.config, int(num_inference_steps), self.T
         if cfg.timestep_spacing == "linspace":
             ts = np.linspace(0, T - 1, n + 1).round()[::-1][:-1].copy().astype(np.int64)
@@ -260,26 +290,19 @@ class DPMSolverMultistepScheduler(_ConfigMixin):
         else:  # trailing
             ts = np.arange(T, 0, -T / n).round().copy().astype(np.int64)
             ts -= 1
-        ac = self.alphas_cumprod
-        sigmas = np.array(((1 - ac) / ac) ** 0.5)
-        log_sigmas = np.log(sigmas)
+        train = self._train_sigmas()
         if cfg.use_karras_sigmas:
-            sigmas = np.flip(sigmas).copy()
-            rho, s_min, s_max = 7.0, sigmas[-1].item(), sigmas[0].item()
+            rho, s_min, s_max = 7.0, train[0].item(), train[-1].item()
             ramp = np.linspace(0, 1, n)
             sigmas = (s_max ** (1 / rho) + ramp * (s_min ** (1 / rho) - s_max ** (1 / rho))) ** rho
-            ts = _sigma_to_t(sigmas, log_sigmas).round()
+            ts = _sigma_to_t(sigmas, np.log(train)).round().astype(np.int64)
         else:
-            sigmas = np.interp(ts, np.arange(0, len(sigmas)), sigmas)
-        last = float(((1 - ac[0]) / ac[0]) ** 0.5) if cfg.final_sigmas_type == "sigma_min" else 0.0
+            sigmas = self._interp_sigmas(ts)
+        last = float(train[0]) if cfg.final_sigmas_type == "sigma_min" else 0.0
         self.sigmas = torch.from_numpy(np.concatenate([sigmas, [last]]).astype(np.float32))
-        self.timesteps_np = np.asarray(ts).astype(np.int64)
-        self.timesteps = torch.from_numpy(self.timesteps_np.copy())
-        if device is not None:
-            self.timesteps = self.timesteps.to(device)
-        self.num_inference_steps = len(self.timesteps_np)
+        self._set_grid(ts, device)
         self.lower_order_nums = 0
-        self._step_index = None
+        self._step_index = None     # diffusers: looked up at the first `step`, then counted
 
     # -- which rows run first order (diffusers `step`: lower_order_nums < 1, lower_order_final)
     def _order(self, i: int, lower_order_nums: int) -> int:
@@ -322,47 +345,26 @@ class DPMSolverMultistepScheduler(_ConfigMixin):
         return np.stack([self._solver_row(i, int(o)) for i, o in enumerate(orders)])
 
     def coef_table(self, guidance_scale: float) -> np.ndarray:
-        n = self.num_inference_steps
-        tab = np.zeros((n, 8), dtype=np.float32)
-        tab[:, 0] = self.timesteps_np
-        tab[:, 1] = 1.0
-        tab[:, 6] = 1.0
-        tab[:, 7] = guidance_scale
-        return tab
+        return self._coef_frame(guidance_scale)
 
-    # -- stand-alone protocol (one kernel launch per step; the pipeline's fused loop does not go through these)
+    # -- stand-alone protocol
     def scale_model_input(self, sample: torch.Tensor, timestep=None) -> torch.Tensor:
         return sample
 
-    def _index_for_timestep(self, timestep) -> int:
-        """diffusers `index_for_timestep`: the second match when a timestep repeats, the last row when none matches."""
-        idx = np.nonzero(self.timesteps_np == int(round(float(timestep))))[0]
-        if len(idx) == 0:
-            return self.num_inference_steps - 1
-        return int(idx[1] if len(idx) > 1 else idx[0])
-
-    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, return_dict: bool = True, **kw):
-        """model_output: the (already CFG-combined) noise prediction, NCHW like `sample`; keeps the previous x0 on the
-        device between calls.  Computes in fp16 like the pipeline's fused loop."""
-        if self.num_inference_steps is None:
-            raise RuntimeError("call set_timesteps first")
+    def _step_row(self, timestep) -> int:
         if self._step_index is None:
-            self._step_index = self._index_for_timestep(timestep)
-        i = self._step_index
-        order = self._order(i, self.lower_order_nums)
-        dev = sample.device
-        solver = torch.from_numpy(self._solver_row(i, order)[None]).to(dev)
-        table = torch.tensor([[0, 1, 0, 0, 0, 0, 1, 1]], dtype=torch.float32, device=dev)
-        ns, c, h, w = sample.shape
-        eps = ops.nchw_to_nhwc(model_output.to(torch.float16).reshape(ns, c, h * w).contiguous())
-        lat = sample.to(torch.float16).contiguous().clone()
+            self._step_index = self._index_of(timestep, self.num_inference_steps - 1)
+        return self._step_index
+
+    def _step_extras(self, i: int, lat: torch.Tensor, generator) -> dict:
+        """Row i at the order the run so far allows (a run may start mid-schedule; this step is counted here), and the
+        previous x0, which stays on the device between calls."""
+        rows = np.zeros((self.num_inference_steps, 8), dtype=np.float32)
+        rows[i] = self._solver_row(i, self._order(i, self.lower_order_nums))
         if self._prev_x0 is None or self._prev_x0.shape != lat.shape or self._prev_x0.device != lat.device:
             self._prev_x0 = torch.empty_like(lat)
-        scratch = torch.empty((ns, h * w, c), dtype=torch.float16, device=dev)
-        ops.cfg_dpm_step(eps, lat, scratch, table, solver, self._prev_x0, do_cfg=False)
         self.lower_order_nums = min(self.lower_order_nums + 1, self.config.solver_order)
-        self._step_index = i + 1
-        return (lat,) if not return_dict else {"prev_sample": lat}
+        return dict(solver=torch.from_numpy(rows).to(lat.device), prev_x0=self._prev_x0)
 
 
 def draw_noise_seeds(num_samples: int, generator=None) -> list:
@@ -379,7 +381,7 @@ def draw_noise_seeds(num_samples: int, generator=None) -> list:
     return [int(v) for v in torch.randint(0, hi, (num_samples,), generator=generator, device=generator.device).tolist()]
 
 
-class EulerAncestralDiscreteScheduler(_ConfigMixin):
+class EulerAncestralDiscreteScheduler(_Scheduler):
     """diffusers EulerAncestralDiscreteScheduler [3P] ("Euler a"), epsilon prediction: an Euler step from sigma_from down
     to sigma_down, then fresh noise of std sigma_up, with sigma_up^2 + sigma_down^2 = sigma_to^2.
 
@@ -389,37 +391,15 @@ class EulerAncestralDiscreteScheduler(_ConfigMixin):
     replays and a panel's noise does not depend on the batch it runs in.  Scalars are 0-dim fp32 torch values computed
     in diffusers' order; the last row (sigma_to = 0) has sigma_up = sigma_down = 0."""
     kind = KIND_EULER_ANCESTRAL
-    order = 1
-    stochastic = True   # the pipeline draws `noise_seeds` for such a scheduler (after the initial latents)
-    # diffusers' constructor defaults for this class (linear betas: NOT the SDXL schedule, so a bare config is refused)
-    _DEFAULTS = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
-                     trained_betas=None, prediction_type="epsilon", timestep_spacing="linspace", steps_offset=0,
-                     rescale_betas_zero_snr=False)
-    # keys whose other values change the schedule or the update rule: only what the device kernel implements is accepted
-    _SUPPORTED = {"beta_schedule": ("scaled_linear",), "trained_betas": (None,), "prediction_type": ("epsilon",),
-                  "timestep_spacing": ("leading", "linspace", "trailing"), "rescale_betas_zero_snr": (False,)}
+    stochastic = True
+    _DEFAULTS = _DIFFUSERS
+    _SUPPORTED = _DIFFUSERS_SUPPORTED
 
     def __init__(self, **kwargs):
-        cfg = _Config(self._DEFAULTS)
-        cfg.update({k: v for k, v in kwargs.items() if k in self._DEFAULTS})   # other keys: not this class's (ignored)
-        for key, ok in self._SUPPORTED.items():
-            if isinstance(cfg[key], (list, tuple)) or cfg[key] not in ok:
-                raise NotImplementedError(f"scheduler config {key}={cfg[key]!r}: the MI355X Euler Ancestral kernel "
-                                          f"implements {key} in {ok} only")
-        self.config = cfg
-        self.T = int(cfg["num_train_timesteps"])
-        self.alphas_cumprod = _alphas_cumprod(self.T, cfg["beta_start"], cfg["beta_end"])
-        ac = self.alphas_cumprod.numpy()
-        self.sigmas = torch.from_numpy(np.concatenate([np.array(((1 - ac) / ac) ** 0.5)[::-1], [0.0]]).astype(np.float32))
-        self.timesteps = None
-        self.num_inference_steps = None
-        self._step_index = 0
+        super().__init__(**kwargs)
+        # like diffusers, the training sigmas until `set_timesteps`: `init_noise_sigma` is read before it
+        self.sigmas = torch.from_numpy(np.concatenate([self._train_sigmas()[::-1], [0.0]]).astype(np.float32))
         self._seeds = None
-        self._dev = None
-
-    @classmethod
-    def _config_keys(cls):
-        return tuple(cls._DEFAULTS)
 
     @property
     def init_noise_sigma(self) -> float:
@@ -429,27 +409,11 @@ class EulerAncestralDiscreteScheduler(_ConfigMixin):
         return float((smax ** 2 + 1) ** 0.5)
 
     def set_timesteps(self, num_inference_steps: int, device=None):
-        cfg, n, T = self.config, int(num_inference_steps), self.T
-        if cfg.timestep_spacing == "linspace":
-            ts = np.linspace(0, T - 1, n, dtype=np.float32)[::-1].copy()
-        elif cfg.timestep_spacing == "leading":
-            step_ratio = T // n
-            ts = (np.arange(0, n) * step_ratio).round()[::-1].copy().astype(np.float32)
-            ts += cfg.steps_offset
-        else:  # trailing
-            step_ratio = T / n
-            ts = (np.arange(T, 0, -step_ratio)).round().copy().astype(np.float32)
-            ts -= 1
-        ac = self.alphas_cumprod.numpy()
-        sig = np.array(((1 - ac) / ac) ** 0.5)
-        sig = np.interp(ts, np.arange(0, len(sig)), sig)
-        self.sigmas = torch.from_numpy(np.concatenate([sig, [0.0]]).astype(np.float32))
-        self.timesteps_np = ts
-        self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
-        self.num_inference_steps = n
-        self._step_index = 0
+        cfg = self.config
+        ts = _timestep_grid(cfg.timestep_spacing, self.T, int(num_inference_steps), cfg.steps_offset)
+        self.sigmas = torch.from_numpy(np.concatenate([self._interp_sigmas(ts), [0.0]]).astype(np.float32))
+        self._set_grid(ts, device)
         self._seeds = None      # the stand-alone `step` draws new seeds for a new run
-        self._dev = None
 
     def sigma_up_down(self, i: int):
         """(sigma_up, sigma_down) of row i, 0-dim fp32 tensors in diffusers' order of operations."""
@@ -459,68 +423,29 @@ class EulerAncestralDiscreteScheduler(_ConfigMixin):
         return sigma_up, sigma_down
 
     def coef_table(self, guidance_scale: float) -> np.ndarray:
-        if self.num_inference_steps is None:
-            raise RuntimeError("call set_timesteps first")
-        n = self.num_inference_steps
-        tab = np.zeros((n, 8), dtype=np.float32)
-        s = self.sigmas.numpy()
-        div = ((s ** 2 + 1) ** 0.5).astype(np.float32)   # fp32 like the 0-dim sigma tensor arithmetic in diffusers
-        tab[:, 0] = self.timesteps_np
-        tab[:, 1] = div[:n]
-        tab[:, 2] = s[:n]
-        for i in range(n):
+        tab = self._coef_frame(guidance_scale, self.sigmas.numpy())
+        for i in range(len(tab)):
             up, down = self.sigma_up_down(i)
             tab[i, 3], tab[i, 4] = float(down), float(up)
-        tab[:, 6] = div[1:n + 1]
-        tab[:, 7] = guidance_scale
         return tab
 
-    def solver_table(self) -> Optional[np.ndarray]:
-        return None
-
-    # -- stand-alone protocol (one kernel launch each; the pipeline's fused loop does not go through these)
-    def _index_of(self, t) -> int:
-        idx = np.nonzero(np.isclose(np.asarray(self.timesteps_np, dtype=np.float64), float(t)))[0]
-        return int(idx[0]) if len(idx) else self._step_index
-
-    def scale_model_input(self, sample: torch.Tensor, timestep) -> torch.Tensor:
-        i = self._index_of(timestep)
-        div = float(self.coef_table(1.0)[i, 1])
-        ns, c, h, w = sample.shape
-        table = torch.tensor([[0, div, 0, 0, 0, 0, 1, 1]], dtype=torch.float32, device=sample.device)
-        tmp = torch.empty((ns, h * w, c), dtype=torch.float16, device=sample.device)
-        ops.prepare_model_input(sample.contiguous(), tmp, table, do_cfg=False)
-        return ops.nhwc_to_nchw(tmp).reshape(ns, c, h, w)
-
-    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, generator=None,
-             return_dict: bool = True, **kw):
-        """model_output: the (already CFG-combined) noise prediction, NCHW like `sample`.  The per-panel seeds are drawn
-        once per run (`draw_noise_seeds(batch, generator)` at the first step after `set_timesteps`, kept in
-        `noise_seeds`); the noise of step i is the device's Philox draw for (seed, pixel, i)."""
-        if self.num_inference_steps is None:
-            raise RuntimeError("call set_timesteps first")
-        i = self._index_of(timestep)
-        ns, c, h, w = sample.shape
-        dev = sample.device
-        if self._seeds is None or len(self._seeds) != ns:
-            self._seeds = draw_noise_seeds(ns, generator)
-            self._dev = None
-        if self._dev is None or self._dev[0].device != dev:
-            self._dev = (torch.from_numpy(self.coef_table(1.0)).to(dev),
-                         torch.tensor(self._seeds, dtype=torch.int64, device=dev))
-        table, seeds = self._dev
-        ctr = torch.tensor([i], dtype=torch.int32, device=dev)
-        eps = ops.nchw_to_nhwc(model_output.to(torch.float16).reshape(ns, c, h * w).contiguous())
-        lat = sample.to(torch.float16).contiguous().clone()
-        scratch = torch.empty((ns, h * w, c), dtype=torch.float16, device=dev)
-        ops.cfg_sampler_step_noise(eps, lat, scratch, table, seeds, self.kind, do_cfg=False, ctr=ctr)
-        self._step_index = i + 1
-        return (lat,) if not return_dict else {"prev_sample": lat}
+    # -- stand-alone protocol
+    def _step_extras(self, i: int, lat: torch.Tensor, generator) -> dict:
+        """The per-panel seeds, drawn once per run (`draw_noise_seeds(batch, generator)` at the first step after
+        `set_timesteps`, kept in `noise_seeds`); the noise of step i is the device's Philox draw for (seed, pixel, i)."""
+        if self._seeds is None or len(self._seeds) != lat.shape[0]:
+            self._seeds = draw_noise_seeds(lat.shape[0], generator)
+        return dict(seeds=torch.tensor(self._seeds, dtype=torch.int64, device=lat.device))
 
     @property
     def noise_seeds(self):
         """The seeds of the current stand-alone run (None before its first `step`)."""
         return None if self._seeds is None else list(self._seeds)
+
+
+# scheduler_config.json `_class_name` -> class
+SCHEDULERS = {c.__name__: c for c in (EulerDiscreteScheduler, DDIMScheduler, DPMSolverMultistepScheduler,
+                                      EulerAncestralDiscreteScheduler)}
 
 
 def _sigma_to_t(sigmas: np.ndarray, log_sigmas: np.ndarray) -> np.ndarray:

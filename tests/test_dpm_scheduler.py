@@ -12,9 +12,8 @@ import pytest
 import torch
 
 from tests._dpm_ref import DPMSolverOracle
+from tests._sampler_common import SDXL
 
-SDXL = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", steps_offset=1,
-            timestep_spacing="leading")
 
 
 def _dpm(**kw):

@@ -11,9 +11,8 @@ import torch
 
 from tests._euler_a_ref import EulerAncestralOracle
 from tests._philox_ref import MOMENT_HW, MOMENT_SEEDS, moment_conditions, philox4x32_10, philox_normal, philox_u32, uniforms
+from tests._sampler_common import SDXL
 
-SDXL = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", steps_offset=1,
-            timestep_spacing="leading")
 SPACINGS = ("leading", "linspace", "trailing")
 
 

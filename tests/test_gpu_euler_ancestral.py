@@ -14,13 +14,10 @@ import torch
 from tests._euler_a_ref import EulerAncestralOracle
 from tests._gates import gate
 from tests._philox_ref import MOMENT_HW, MOMENT_SEEDS, moment_conditions, philox_normal, philox_u32
-from tests.test_gpu_dpm import DIALOG, IP_BBOX, _close, _nhwc, _pipe, _rel, parts  # noqa: F401  (`parts`: the fixture)
+from tests._sampler_common import DEV, DIALOG, IP_BBOX, SDXL, _close, _nhwc, _pipe, _rel, hq
+from tests._sampler_common import parts  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-hq = lambda t: t.half().float()
-SDXL = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", steps_offset=1,
-            timestep_spacing="leading")
 SEEDS3 = [0, 2 ** 63 - 2, 0x0123456789ABCDEF]
 
 
