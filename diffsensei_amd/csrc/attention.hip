@@ -252,18 +252,27 @@ __global__ __launch_bounds__(256, 2) void self_attn_kernel(const SelfAttnParams 
 // Region test of the reference mask builder, evaluated per query token.
 // reference src/models/attention_processor.py:145-163: grid = torch.linspace(0,1,W) x linspace(0,1,H)
 // (inclusive end points), token idx -> (row idx / W, col idx % W); inside box k iff x1<=x<=x2 && y1<=y<=y2.
-// torch.linspace (fp32): step = 1/(n-1); v[i] = i<n/2 ? i*step : 1 - (n-1-i)*step  (no fma).
+// torch.linspace (fp32): step = 1/(n-1) correctly rounded; v[i] = i<n/2 ? step*i : fma(-step, n-1-i, 1) - the second half is ONE
+// rounding (torch's CPU and device kernels are built with contraction on).  The step comes from the host (linspace_step): this
+// library is built with -freciprocal-math, under which a device-side 1.0f / x is v_rcp_f32 (1 ulp: off for n - 1 = 6, so a box
+// edge lying exactly on a grid coordinate - x1 == x2 on one token - missed its token).
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float linspace01(int i, int n) {
+__device__ __forceinline__ float linspace01(int i, int n, float step) {
     if (n <= 1) return 0.f;
-    const float step = __fdiv_rn(1.0f, (float)(n - 1));
-    return (i < n / 2) ? __fmul_rn(step, (float)i) : __fsub_rn(1.0f, __fmul_rn(step, (float)(n - 1 - i)));
+    return (i < n / 2) ? __fmul_rn(step, (float)i) : __builtin_fmaf(-step, (float)(n - 1 - i), 1.0f);
+}
+// 1/(n-1) rounded to nearest fp32.  Through a double quotient: 1/m is never within 2^-54 of an fp32 rounding boundary for the
+// grid sizes there are (|1 - m c| >= 1/(m 2^25) for every 25-bit c), so rounding twice equals rounding once.
+static float linspace_step(int n) {
+    if (n <= 1) return 0.f;
+    volatile double m = (double)(n - 1);   // volatile: the quotient is a real division whatever the math flags allow
+    return (float)(1.0 / m);
 }
 // bit k set <=> token inside box k
 __device__ __forceinline__ unsigned region_flags(const float* __restrict__ bbox_b, int max_ips, int idx, int mh,
-                                                 int mw) {
+                                                 int mw, float step_x, float step_y) {
     const int yi = idx / mw, xi = idx - yi * mw;
-    const float x = linspace01(xi, mw), y = linspace01(yi, mh);
+    const float x = linspace01(xi, mw, step_x), y = linspace01(yi, mh, step_y);
     unsigned f = 0;
     for (int k = 0; k < max_ips; ++k) {
         const float x1 = bbox_b[4 * k + 0], y1 = bbox_b[4 * k + 1], x2 = bbox_b[4 * k + 2], y2 = bbox_b[4 * k + 3];
@@ -272,11 +281,12 @@ __device__ __forceinline__ unsigned region_flags(const float* __restrict__ bbox_
     return f;
 }
 
-__global__ void ip_region_flags_kernel(const float* bbox, uint8_t* flags, int B, int N, int max_ips, int mh, int mw) {
+__global__ void ip_region_flags_kernel(const float* bbox, uint8_t* flags, int B, int N, int max_ips, int mh, int mw,
+                                       float step_x, float step_y) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * N) return;
     const int b = i / N, idx = i - b * N;
-    flags[i] = (uint8_t)region_flags(bbox + (long)b * max_ips * 4, max_ips, idx, mh, mw);
+    flags[i] = (uint8_t)region_flags(bbox + (long)b * max_ips * 4, max_ips, idx, mh, mw, step_x, step_y);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -462,7 +472,7 @@ __global__ __launch_bounds__(NW * 64, 2) void ip_attn_kernel(const IPAttnParams 
         unsigned inside = 0;  // bit k set <=> the token lies in box k (region_flags() with the boxes in registers)
         {
             const int yi = qidx / p.mask_w, xi = qidx - yi * p.mask_w;
-            const float x = linspace01(xi, p.mask_w), y = linspace01(yi, p.mask_h);
+            const float x = linspace01(xi, p.mask_w, p.step_x), y = linspace01(yi, p.mask_h, p.step_y);
 #pragma unroll
             for (int k = 0; k < 8; ++k)
                 inside |= (unsigned)((x >= box[k][0]) & (x <= box[k][2]) & (y >= box[k][1]) & (y <= box[k][3])) << k;
@@ -830,6 +840,7 @@ int ds_launch_ip_attn(const IPAttnParams& p0, hipStream_t stream) {
     if (p.ldk == 0) p.ldk = p.C;
     if (p.sk == 0) p.sk = (long)LP * p.C;
     if (p.sv == 0) p.sv = (long)LP * p.C;
+    p.step_x = linspace_step(p.mask_w), p.step_y = linspace_step(p.mask_h);
     DS_REQUIRE(p.ldk % 8 == 0 && p.sk % 8 == 0 && p.sv % 8 == 0, "ip_attn: key/value panel strides must be multiples of 8");
     DS_REQUIRE(p.B > 0 && p.heads > 0 && p.N > 0, "ip_attn: empty problem");
     DS_REQUIRE(p.LP == LP, "ip_attn: key panels must be padded to %d rows (got %d)", LP, p.LP);
@@ -880,7 +891,7 @@ int ds_launch_ip_region_flags(const float* bbox, uint8_t* flags, int B, int N, i
                               hipStream_t stream) {
     DS_REQUIRE(mask_h * mask_w == N, "region_flags: grid %dx%d != N %d", mask_h, mask_w, N);
     hipLaunchKernelGGL(ip_region_flags_kernel, dim3((B * N + 255) / 256), dim3(256), 0, stream, bbox, flags, B, N,
-                       max_ips, mask_h, mask_w);
+                       max_ips, mask_h, mask_w, linspace_step(mask_w), linspace_step(mask_h));
     DS_LAUNCH_CHECK();
     return 0;
 }

@@ -153,6 +153,7 @@ struct IPAttnParams {
     int Lt = 77, Li = 80, LP = 96;
     int n_dummy = 16, tok_per_ip = 16, max_ips = 4;
     int mask_h = 0, mask_w = 0;    // grid the reference infers from (N, aspect_ratio)
+    float step_x = 0.f, step_y = 0.f;   // 1/(mask_w-1), 1/(mask_h-1) correctly rounded: filled in by ds_launch_ip_attn
     float qk_scale = 0.125f, ip_scale = 1.0f;
     const float* ip_scale_ptr = nullptr;  // device scalar; overrides ip_scale when set (graph-replay safe)
 };

@@ -265,16 +265,45 @@ def self_attention(q: Tensor, k: Tensor, vt: Tensor, heads: int, scale: Optional
 
 def masked_ip_attention(q: Tensor, kt: Tensor, vtt: Tensor, ki: Tensor, vti: Tensor, bbox: Tensor, heads: int,
                         mask_hw: Tuple[int, int], ip_scale: float, Lt: int = 77, Li: int = 80, n_dummy: int = 16,
-                        tok_per_ip: int = 16, qk_scale: float = 0.125) -> Tensor:
-    """q: [B,N,C]; kt/ki: [B,96,C]; vtt/vti: [B,C,96]; bbox: [B,max_ips,4] fp32."""
-    _chk(q, kt, vtt, ki, vti)
+                        tok_per_ip: int = 16, qk_scale: float = 0.125, out: Optional[Tensor] = None,
+                        ldq: Optional[int] = None, ldo: Optional[int] = None, ldk: Optional[int] = None,
+                        sk: Optional[int] = None, sv: Optional[int] = None,
+                        ip_scale_dev: Optional[Tensor] = None) -> Tensor:
+    """q: [B,N,C]; kt/ki: [B,96,C]; vtt/vti: [B,C,96]; bbox: [B,max_ips,4] fp32.
+
+    The strides of the C ABI (include/diffsensei_hip.h) are taken from the tensors, so column slices of wider buffers work as
+    they are: q / out `buf[:, :, c0:c0+C]` (row stride ldq / ldo, batch stride N rows), key panels `stacked[:, :, c0:c0+C]`
+    (ldk, sk), value panels `stacked_t[:, c0:c0+C, :]` (sv).  `ldq, ldo, ldk, sk, sv` override what the tensors say;
+    `ip_scale_dev` (one fp32 on the device) replaces `ip_scale`."""
+    for t in (q, kt, vtt, ki, vti, out):
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise _lib.DiffSenseiHipError("diffsensei_amd ops need CUDA(HIP) tensors — there is no CPU path")
+        bind_device(t.device)
+        if t.dtype != torch.float16 or t.dim() != 3 or t.stride(2) != 1:
+            raise _lib.DiffSenseiHipError("masked_ip_attention: fp16 [*,*,*] tensors with unit stride in the last dimension")
     _chk(bbox, dtype=torch.float32)
+    _chk(ip_scale_dev, dtype=torch.float32)
     B, N, Cc = q.shape
-    o = torch.empty_like(q)
-    check(_lib.load().ds_masked_ip_attn_f16(_p(q), Cc, _p(kt), _p(vtt), _p(ki), _p(vti), _p(bbox), _p(o), Cc, B, heads,
+    if out is None:
+        out = torch.empty((B, N, Cc), dtype=torch.float16, device=q.device)
+    if out.shape != q.shape:
+        raise _lib.DiffSenseiHipError(f"masked_ip_attention: out {tuple(out.shape)} != q {tuple(q.shape)}")
+    ldq = q.stride(1) if ldq is None else ldq
+    ldo = out.stride(1) if ldo is None else ldo
+    if B > 1 and (q.stride(0) != N * ldq or out.stride(0) != N * ldo):
+        raise _lib.DiffSenseiHipError("masked_ip_attention: q / out batch stride must be N rows")
+    if kt.stride() != ki.stride() or vtt.stride() != vti.stride() or vtt.stride(1) != vtt.shape[2]:
+        raise _lib.DiffSenseiHipError("masked_ip_attention: text and IP panels must share strides; value rows are dense")
+    ldk = kt.stride(1) if ldk is None else ldk
+    sk = kt.stride(0) if sk is None else sk
+    sv = vtt.stride(0) if sv is None else sv
+    check(_lib.load().ds_masked_ip_attn_f16(_p(q), ldq, _p(kt), _p(vtt), _p(ki), _p(vti), _p(bbox), _p(out), ldo, B, heads,
                                             N, Lt, Li, n_dummy, tok_per_ip, bbox.shape[1], mask_hw[0], mask_hw[1],
-                                            qk_scale, ip_scale, None, 0, 0, 0, _stream()), "ds_masked_ip_attn_f16")
-    return o
+                                            qk_scale, ip_scale, _p(ip_scale_dev), ldk, sk, sv, _stream()),
+          "ds_masked_ip_attn_f16")
+    return out
 
 
 def ip_region_flags(bbox: Tensor, N: int, mask_hw: Tuple[int, int]) -> Tensor:

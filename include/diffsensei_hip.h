@@ -245,7 +245,9 @@ int ds_self_attn_f16(const void* q, int64_t ldq, int64_t sq, const void* k, int6
 /* Fused text + region-masked IP cross-attention core of MaskedIPAttnProcessor2_0
  * (reference src/models/attention_processor.py:235-258 incl. prepare_attention_mask_ip :115-169):
  *   o = softmax(q kt^T * s) vt  +  ip_scale * softmax(q ki^T * s + M(bbox)) vi
- * kt/ki: [B,96,C] key panels (rows >= Lt / Li are padding), vtt/vti: [B,C,96] transposed value panels,
+ * kt/ki: [B,96,C] key panels (rows >= Lt / Li are padding), vtt/vti: [B,C,96] transposed value panels (columns >= Lt / Li
+ * are padding).  The padding may hold anything finite: those keys get probability exactly 0 and never reach the output
+ * (Inf / NaN there would, as 0 * Inf).  q / o: [B,N,ldq] / [B,N,ldo] with head h at column h*64 (batch stride N rows).
  * bbox: [B,max_ips,4] fp32 relative boxes, (mask_h, mask_w): the grid the reference infers from (N, aspect_ratio).
  * ip_scale_dev: optional device float overriding ip_scale (lets a captured graph follow set_ip_scale).
  * ldk/sk: row / batch stride of the key panels, sv: batch stride of the value panels (elements; 0 = dense) —

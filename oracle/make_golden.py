@@ -2,7 +2,8 @@
 
 Run in the build container only (needs /root/reference, which does not exist on the GPU box):
 
-    python -m oracle.make_golden
+    python -m oracle.make_golden            # every fixture
+    python -m oracle.make_golden layouts    # only ip_region_masks_layouts.npz
 
 Imports reference src/models/attention_processor.py and src/models/resampler.py unmodified (they depend
 only on torch), drives them with seeded inputs through a duck-typed `attn` stub that has exactly the
@@ -52,12 +53,37 @@ MASK_CASES = [
     ("tiny8x12", 8, 12, [[[0.0, 0.0, 0.45, 1.0], [0.46, 0.0, 1.0, 1.0], [0.2, 0.2, 0.8, 0.8], [0.0, 0.5, 1.0, 0.5]]]),
 ]
 
+# token layouts other than the model's 16 + 4 x 16: (num_dummy_tokens, tokens per character, max_num_ips); the first is the
+# reference's constructor default (num_ip_tokens = 4, num_dummy_tokens = 4)
+LAYOUT_CASES = [(4, 1, 4), (8, 8, 4), (16, 8, 8), (16, 20, 4)]
+LAYOUT_GRIDS = [(7, 9), (18, 13)]
+
+
+def write_layout_masks(processor_cls):
+    """tests/golden/ip_region_masks_layouts.npz: the reference's prepare_attention_mask_ip at LAYOUT_CASES x LAYOUT_GRIDS on the
+    box sets of oracle/ip_box_cases.py (three batch items, one head), int8 "masked" flags [3, N, num_dummy + num_ip]."""
+    from oracle.ip_box_cases import box_cases
+    out = {}
+    for nd, tpi, k in LAYOUT_CASES:
+        proc = processor_cls(hidden_size=64, cross_attention_dim=32, num_ip_tokens=k * tpi, num_dummy_tokens=nd)
+        for h, w in LAYOUT_GRIDS:
+            bbox = box_cases(h, w, k, 3)
+            m = proc.prepare_attention_mask_ip(bbox, torch.zeros(3, h * w, 64), 1, h / w)
+            name = f"d{nd}_t{tpi}_k{k}_{h}x{w}"
+            out[name + "_bbox"] = bbox.numpy()
+            out[name + "_layout"] = np.array([nd, tpi, k, h, w], dtype=np.int32)
+            out[name + "_masked"] = (m[:, 0] < -1.0).numpy().astype(np.int8)
+    np.savez_compressed(os.path.join(OUT, "ip_region_masks_layouts.npz"), **out)
+
 
 def main():
     sys.path.insert(0, REF)
     from src.models.attention_processor import AttnProcessor2_0, MaskedIPAttnProcessor2_0
     from src.models.resampler import Resampler
     os.makedirs(OUT, exist_ok=True)
+    if sys.argv[1:] == ["layouts"]:   # only the layout masks (no random numbers involved; the other fixtures stay as they are)
+        write_layout_masks(MaskedIPAttnProcessor2_0)
+        return
     torch.manual_seed(0)
 
     # ---- 1. region masks (reference prepare_attention_mask_ip), stored as uint8 "masked" flags
@@ -114,6 +140,9 @@ def main():
     for k, v in rs.state_dict().items():
         d["sd." + k] = v.numpy()
     np.savez_compressed(os.path.join(OUT, "resampler.npz"), **d)
+
+    # ---- 5. region masks at other token layouts
+    write_layout_masks(MaskedIPAttnProcessor2_0)
     print("wrote", sorted(os.listdir(OUT)))
 
 
