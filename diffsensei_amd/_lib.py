@@ -67,6 +67,8 @@ SIGNATURES = {
     "ds_self_attn_f16": (i32, [vp, i64, i64, vp, i64, i64, vp, i64, vp, i64, i64, i32, i32, i32, i32, f32, vp]),
     "ds_masked_ip_attn_f16": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32,
                                     i32, f32, f32, vp, i64, i64, i64, vp]),
+    "ds_masked_ip_attn_rows_f16": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32,
+                                         i32, f32, vp, i64, i64, i64, vp]),
     "ds_ip_region_flags": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "ds_small_attn_f16": (i32, [vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, i32, f32,
                                 vp]),
@@ -80,6 +82,7 @@ SIGNATURES = {
     "ds_cfg_sampler_step_f16": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "ds_cfg_dpm_step_f16": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "ds_cfg_sampler_step_noise_f16": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "ds_cfg_sampler_step_panels_f16": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "ds_philox_u32": (i32, [vp, i32, i32, vp, i32, i32, vp]),
     "ds_philox_normal_f32": (i32, [vp, i32, i32, vp, i32, i32, vp]),
     "ds_prepare_model_input_f16": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),

@@ -437,7 +437,11 @@ __global__ __launch_bounds__(NW * 64, 2) void ip_attn_kernel(const IPAttnParams 
 #pragma unroll
             for (int c4 = 0; c4 < 4; ++c4) box[k][c4] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bv[c4]), k));
     }
-    const float ip_scale = p.ip_scale_ptr ? *p.ip_scale_ptr : p.ip_scale;
+    // The IP scale, ONCE per block as well: the batch's device scalar (ip_scale_rows = 0) or element b of a [B] vector
+    // (ip_scale_rows = 1), a scalar load at a block-uniform index.  (Hoisted up to the box request above, or loaded
+    // unconditionally from a dummy address with a select behind it, it cost one more VGPR for its spilled SGPR on both
+    // four-wave instantiations; here every instantiation keeps the register counts it had with the single scalar.)
+    const float ip_scale = p.ip_scale_ptr ? p.ip_scale_ptr[b * p.ip_scale_rows] : p.ip_scale;
     for (int it = 0; it < qt; ++it) {
         const int q0 = (blockIdx.x * qt + it) * ROWS + wave * 32;
         if constexpr (RING) {
@@ -849,6 +853,8 @@ int ds_launch_ip_attn(const IPAttnParams& p0, hipStream_t stream) {
     DS_REQUIRE(p.max_ips >= 1 && p.max_ips <= 8 && p.tok_per_ip > 0, "ip_attn: bad ip token layout");
     DS_REQUIRE(p.n_dummy + p.max_ips * p.tok_per_ip == p.Li, "ip_attn: Li (%d) != n_dummy + max_ips*tok_per_ip", p.Li);
     DS_REQUIRE(p.mask_h * p.mask_w == p.N, "ip_attn: mask grid %dx%d != N %d", p.mask_h, p.mask_w, p.N);
+    DS_REQUIRE(p.ip_scale_rows == 0 || (p.ip_scale_rows == 1 && p.ip_scale_ptr),
+               "ip_attn: ip_scale_rows must be 0, or 1 with a device vector of B scales");
     DS_REQUIRE(p.ldq % 8 == 0 && p.ldo % 8 == 0, "ip_attn: ldq (%ld) and ldo (%ld) must be multiples of 8 (16-byte row pieces)", (long)p.ldq, (long)p.ldo);
     // walk several query tiles per block once there are plenty of blocks (amortises the K/V panel staging)
     // The 8-wave LDS-DMA ring variant, 256 query rows per block and tile: g_ip_variant 2 only (see below).

@@ -367,6 +367,19 @@ int ds_masked_ip_attn_f16(const void* q, int64_t ldq, const void* kt, const void
     return ds_launch_ip_attn(p, S(stream));
 }
 
+int ds_masked_ip_attn_rows_f16(const void* q, int64_t ldq, const void* kt, const void* vtt, const void* ki,
+                               const void* vti, const float* bbox, void* o, int64_t ldo, int B, int heads, int N, int Lt,
+                               int Li, int n_dummy, int tok_per_ip, int max_ips, int mask_h, int mask_w, float qk_scale,
+                               const float* ip_scale_rows_dev, int64_t ldk, int64_t sk, int64_t sv, void* stream) {
+    IPAttnParams p;
+    p.ldk = ldk; p.sk = sk; p.sv = sv;
+    p.q = H(q); p.kt = H(kt); p.vtt = H(vtt); p.ki = H(ki); p.vti = H(vti); p.bbox = bbox; p.o = HM(o);
+    p.ldq = ldq; p.ldo = ldo; p.B = B; p.heads = heads; p.N = N; p.C = heads * 64;
+    p.Lt = Lt; p.Li = Li; p.LP = 96; p.n_dummy = n_dummy; p.tok_per_ip = tok_per_ip; p.max_ips = max_ips;
+    p.mask_h = mask_h; p.mask_w = mask_w; p.qk_scale = qk_scale; p.ip_scale_ptr = ip_scale_rows_dev; p.ip_scale_rows = 1;
+    return ds_launch_ip_attn(p, S(stream));
+}
+
 int ds_ip_region_flags(const float* bbox, uint8_t* flags, int B, int N, int max_ips, int mask_h, int mask_w,
                        void* stream) {
     return ds_launch_ip_region_flags(bbox, flags, B, N, max_ips, mask_h, mask_w, S(stream));
@@ -514,6 +527,17 @@ int ds_cfg_sampler_step_noise_f16(const void* eps, void* latents, void* model_in
     return ds_launch_sampler_step(p, step_ctr, S(stream));
 }
 
+int ds_cfg_sampler_step_panels_f16(const void* eps, void* latents, void* model_in, const float* table,
+                                   const float* guidance, const float* solver, void* prev_x0, const int64_t* seeds,
+                                   const int32_t* step_ctr, int ns, int HW, int kind, int do_cfg, void* stream) {
+    SamplerStepParams p;
+    p.eps = H(eps); p.latents = HM(latents); p.model_in = HM(model_in); p.coef = table;
+    p.guidance = guidance; p.solver = solver; p.prev_x0 = HM(prev_x0);
+    p.seeds = reinterpret_cast<const long long*>(seeds);
+    p.ns = ns; p.HW = HW; p.kind = kind; p.do_cfg = do_cfg;
+    return ds_launch_sampler_step(p, step_ctr, S(stream));
+}
+
 int ds_philox_u32(const int64_t* seeds, int step, int stream_id, uint32_t* out, int ns, int HW, void* stream) {
     return ds_launch_philox_u32(reinterpret_cast<const long long*>(seeds), step, stream_id, out, ns, HW, S(stream));
 }
@@ -593,7 +617,7 @@ static int run_op(const ds_op& o, hipStream_t st) {
             a.ldq = l[0]; a.ldo = l[1]; a.ldk = l[2]; a.sk = l[3]; a.sv = l[4];
             a.B = i[0]; a.heads = i[1]; a.N = i[2]; a.C = i[1] * 64; a.Lt = i[3]; a.Li = i[4]; a.LP = 96;
             a.n_dummy = i[5]; a.tok_per_ip = i[6]; a.max_ips = i[7]; a.mask_h = i[8]; a.mask_w = i[9];
-            a.qk_scale = o.f[0]; a.ip_scale = o.f[1];
+            a.qk_scale = o.f[0]; a.ip_scale = o.f[1]; a.ip_scale_rows = i[10];
             return ds_launch_ip_attn(a, st);
         }
         case DS_OP_CONV_IN:
@@ -613,6 +637,7 @@ static int run_op(const ds_op& o, hipStream_t st) {
             s.eps = H(p[0]); s.latents = HM(p[1]); s.model_in = HM(p[2]); s.coef = reinterpret_cast<const float*>(p[3]);
             s.prev_x0 = HM(p[5]); s.solver = reinterpret_cast<const float*>(p[6]);
             s.seeds = reinterpret_cast<const long long*>(p[7]);
+            s.guidance = reinterpret_cast<const float*>(p[8]);
             s.ns = i[0]; s.HW = i[1]; s.kind = i[2]; s.do_cfg = i[3];
             return ds_launch_sampler_step(s, reinterpret_cast<const int*>(p[4]), st);
         }

@@ -156,6 +156,8 @@ struct IPAttnParams {
     float step_x = 0.f, step_y = 0.f;   // 1/(mask_w-1), 1/(mask_h-1) correctly rounded: filled in by ds_launch_ip_attn
     float qk_scale = 0.125f, ip_scale = 1.0f;
     const float* ip_scale_ptr = nullptr;  // device scalar; overrides ip_scale when set (graph-replay safe)
+    int ip_scale_rows = 0;         // 1: ip_scale_ptr is [B] floats, batch row b reads element b (under CFG rows n and ns + n
+                                   // both belong to panel n: the caller writes that panel's scale into both)
 };
 int ds_launch_ip_attn(const IPAttnParams& p, hipStream_t stream);
 int ds_launch_small_attn(const half_t* q, const half_t* k, const half_t* v, half_t* o, long ldq, long ldk, long ldv,
@@ -187,6 +189,7 @@ struct SamplerStepParams {
     half_t* prev_x0 = nullptr;      // kind 2: NCHW [ns,4,H,W] x0 of the previous step (read, then overwritten)
     const float* solver = nullptr;  // kind 2: per-step solver rows [n_steps,8] (include/diffsensei_hip.h)
     const long long* seeds = nullptr;  // kind 3: int64 [ns], one Philox key per panel (noise = f(seed, pixel, *ctr))
+    const float* guidance = nullptr;   // fp32 [ns], one guidance scale per panel in place of column 7 (null: column 7)
     int ns = 0, HW = 0, C = 4;
     int kind = 0;                   // 0 Euler, 1 DDIM, 2 DPM-Solver++ (multistep, order 1|2 per row), 3 Euler Ancestral
     int do_cfg = 1;

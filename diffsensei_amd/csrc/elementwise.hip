@@ -293,6 +293,10 @@ __global__ __launch_bounds__(256) void philox_normal_kernel(const long long* __r
 // Euler Ancestral (kind 3) is diffusers' EulerAncestralDiscreteScheduler [3P]: the Euler update towards sigma_down in
 // fp32, then sigma_up * noise with the noise drawn in the model output's dtype (fp16) and the product an fp16 tensor.
 // The noise is this thread's own Philox draw for (seed[n], pixel, *ctr): nothing is read for it but the seed.
+// GV: the guidance scale of panel n is p.guidance[n] instead of column 7 of the table row - the same product at the same
+// rounding points.  An instantiation of its own, so that the one-scalar launch stays the kernel it was (34 SGPRs; the
+// vector's pointer costs 4 more: profiles/per_panel_scales_resource_usage_*.txt).
+template <bool GV>
 __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p, const int* ctr) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     const long total = (long)p.ns * p.HW;
@@ -304,10 +308,11 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p, 
     h4 e = eu;
     if (p.do_cfg) {
         const h4 ec = *reinterpret_cast<const h4*>(p.eps + ((long)(p.ns + n) * p.HW + pix) * 4);
+        const float g = GV ? p.guidance[n] : cf[7];   // per panel, or the table's one value for the batch
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const half_t d = (half_t)((float)ec[c] - (float)eu[c]);
-            const half_t gd = (half_t)(cf[7] * (float)d);
+            const half_t gd = (half_t)(g * (float)d);
             e[c] = (half_t)((float)eu[c] + (float)gd);
         }
     }
@@ -525,7 +530,9 @@ int ds_launch_sampler_step(const SamplerStepParams& p, const int* ctr, hipStream
     DS_REQUIRE(p.kind != 2 || (p.prev_x0 && p.solver), "sampler_step: kind 2 needs prev_x0 and the solver rows");
     DS_REQUIRE(p.kind != 3 || p.seeds, "sampler_step: kind 3 needs the per-panel seeds");
     const long total = (long)p.ns * p.HW;
-    hipLaunchKernelGGL(sampler_step_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p, ctr);
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (p.guidance) hipLaunchKernelGGL(sampler_step_kernel<true>, grid, dim3(256), 0, stream, p, ctr);
+    else hipLaunchKernelGGL(sampler_step_kernel<false>, grid, dim3(256), 0, stream, p, ctr);
     DS_LAUNCH_CHECK();
     return 0;
 }

@@ -381,17 +381,19 @@ def run_sharded(requests: Sequence[PanelRequest], worker: Callable[[PanelRequest
 
 
 def run_sharded_batched(requests: Sequence[PanelRequest], pipe, max_panels: int = 16, max_pixels: Optional[int] = None,
-                        output_type: str = "pil", gather: bool = True, as_pil: Optional[bool] = None):
+                        output_type: str = "pil", gather: bool = True, as_pil: Optional[bool] = None,
+                        mix_scales: bool = False):
     """`run_sharded` for a whole queue: every rank pushes its shard through a `serving.BucketBatcher`, so requests of
     one (size, steps, guidance) bucket share UNet batches on that rank (BASELINE.json configs[3]: mixed-resolution
     queue over the GPUs of a node).  `PanelRequest.payload` holds the other `__call__` keyword arguments.  With
     `gather`, rank 0 receives every request's images (moved as uint8 arrays; `as_pil` as in `run_sharded`: by default the
-    result has the types `output_type` asked for, on one rank or on eight)."""
+    result has the types `output_type` asked for, on one rank or on eight).  `mix_scales`: as in `serving.BucketBatcher` -
+    requests that differ only in guidance_scale / ip_scale share a batch."""
     from .serving import BucketBatcher
     rank = dist.get_rank() if dist.is_initialized() else 0
     world = dist.get_world_size() if dist.is_initialized() else 1
     mine = shard_requests(requests, world)[rank]
-    batcher = BucketBatcher(pipe, max_panels=max_panels, max_pixels=max_pixels)
+    batcher = BucketBatcher(pipe, max_panels=max_panels, max_pixels=max_pixels, mix_scales=mix_scales)
     for r in mine:
         batcher.submit(height=r.height, width=r.width, num_inference_steps=r.num_inference_steps,
                        num_samples=r.num_samples, **r.payload)

@@ -310,6 +310,12 @@ def _ptr(x) -> Optional[int]:
     return x.data_ptr()
 
 
+def _is_number(v) -> bool:
+    """A Python / numpy real or a 0-dim tensor - whatever `float(v)` took before the sliders could also be sequences."""
+    import numbers
+    return isinstance(v, numbers.Real) or (hasattr(v, "ndim") and v.ndim == 0)
+
+
 def make_op(code: str, i=(), f=(), l=(), p=()) -> DsOp:
     op = DsOp()
     op.code = OP[code]
@@ -396,8 +402,15 @@ class UNetEngine:
         self.bbox = E(B, cfg.max_num_ips, 4, dtype=torch.float32)
         self.dialog_boxes = E(B, cfg.max_num_dialogs, 4, dtype=torch.int32)
         self.dialog_boxes.zero_()
-        self.ip_scale = E(1, dtype=torch.float32)
+        # One IP scale per batch row and (build_sampler) one guidance scale per panel, both static buffers.  Which of them
+        # the kernels index is part of the PLAN (`per_panel`): an engine starts uniform - IP_ATTN reads element 0 of
+        # `ip_scale` (all B are written equal), SAMPLER_STEP reads column 7 of the table, op for op the plan of a
+        # one-scalar engine - and the first request whose values differ switches it, once and for good
+        # (`enable_per_panel`): a later uniform request writes equal values into the vectors.
+        self.ip_scale = E(B, dtype=torch.float32)
         self.ip_scale.fill_(1.0)
+        self.per_panel = False
+        self.guidance = None                                    # per-panel mode: fp32 [ns]
         self.table = E(1024, 8, dtype=torch.float32)            # per-step scalars (see include/diffsensei_hip.h)
         self.table.zero_()
         self.ctr = E(1, dtype=torch.int32)
@@ -811,22 +824,64 @@ class UNetEngine:
             if self.noise_seeds is None or self.noise_seeds.shape[0] != ns:
                 self.noise_seeds = self._alloc((ns,), torch.int64)
                 self.noise_seeds.zero_()
+        if self.guidance is None or self.guidance.shape[0] != ns:   # ns floats, whichever mode the plans are in
+            self.guidance = self._alloc((ns,), torch.float32)
+            self.guidance.fill_(1.0)
+        self._sampler_key, self.sampler_kind = key, kind
+        self._build_step_plan()
+
+    def _build_step_plan(self):
+        """The step plan of the built sampler over the buffers `build_sampler` allocated (nothing is allocated here)."""
+        ns, kind, do_cfg = self._sampler_key
         prev_x0, solver = (self.prev_x0, self.solver) if kind == KIND_DPM else (None, None)
         noise_seeds = self.noise_seeds if kind == KIND_EULER_ANCESTRAL else None
         step_ops = list(self.forward_ops) + [
-            make_op("SAMPLER_STEP", i=(ns, HW, kind, int(do_cfg)),
-                    p=(self.eps, self.latents, self.x_in, self.table, self.ctr, prev_x0, solver, noise_seeds)),
+            make_op("SAMPLER_STEP", i=(ns, self.H * self.W, kind, int(do_cfg)),
+                    p=(self.eps, self.latents, self.x_in, self.table, self.ctr, prev_x0, solver, noise_seeds,
+                       self.guidance if self.per_panel else None)),
             make_op("ADVANCE", p=(self.ctr,)),
         ]
         self.step_plan = Plan(step_ops, self.keep)
-        self._sampler_key, self.sampler_kind = key, kind
 
-    def load_schedule(self, table_rows: Tensor, solver_rows: Optional[Tensor] = None, noise_seeds=None):
+    def enable_per_panel(self):
+        """Switch the plans to one IP scale per batch row and one guidance scale per panel (see `__init__`): the IP_ATTN
+        ops get their per-row flag and the forward plan and the step plan of a built sampler are made again over the same
+        buffers - latents, prev_x0, seeds, guidance and everything the host has written into them stay - so a captured
+        step graph is captured once more.  The engine stays in this mode."""
+        if self.per_panel:
+            return
+        self.per_panel = True
+        for op in self.forward_ops:
+            if op.code == OP["IP_ATTN"]:
+                op.i[10] = 1
+        self.forward_plan = Plan(self.forward_ops, self.keep)
+        if self._sampler_key is not None:
+            self._build_step_plan()
+
+    @staticmethod
+    def _scale_values(values, n: int, what: str) -> Optional[List[float]]:
+        """None for a single number, else the `n` floats of a sequence / tensor."""
+        if _is_number(values):
+            return None
+        vals = [float(v) for v in (values.reshape(-1).tolist() if torch.is_tensor(values) else values)]
+        if len(vals) != n:
+            raise ValueError(f"{what}: a number or {n} values are needed, got {len(vals)}")
+        return vals
+
+    def load_schedule(self, table_rows: Tensor, solver_rows: Optional[Tensor] = None, noise_seeds=None, guidance=None):
         """table_rows: fp32 [n_steps, 8]; solver_rows: fp32 [n_steps, 8], the DPM-Solver++ rows (kind 2 only);
         noise_seeds: one non-negative int64 per panel, the Euler Ancestral Philox keys (kind 3 only)
         (see include/diffsensei_hip.h); resets the device step counter.  The seed buffer is static: a captured step
-        graph replays with the new seeds and, through the device step counter, new noise every step."""
+        graph replays with the new seeds and, through the device step counter, new noise every step.
+        guidance: one guidance scale per panel (`ns` values) in place of column 7 of the table; values that differ
+        switch the engine to per-panel plans (`enable_per_panel`).  The buffer is static like the seeds."""
         n = table_rows.shape[0]
+        g = None
+        if guidance is not None:
+            if self._sampler_key is None:
+                raise ValueError("load_schedule: a guidance vector needs a built sampler (build_sampler)")
+            ns = self._sampler_key[0]
+            g = self._scale_values(guidance, ns, "guidance") or [float(guidance)] * ns
         if n > self.table.shape[0]:
             raise ValueError("too many steps for the scalar table")
         kind = self.sampler_kind
@@ -834,21 +889,34 @@ class UNetEngine:
             raise ValueError(f"solver rows are given exactly for a DPM-Solver++ sampler (built kind: {kind})")
         if (noise_seeds is not None) != (kind == KIND_EULER_ANCESTRAL):
             raise ValueError(f"noise seeds are given exactly for an Euler Ancestral sampler (built kind: {kind})")
+        seeds = None
         if noise_seeds is not None:
             seeds = torch.as_tensor(noise_seeds, dtype=torch.int64).reshape(-1)
             if seeds.shape != self.noise_seeds.shape:
                 raise ValueError(f"{seeds.shape[0]} noise seeds for {self.noise_seeds.shape[0]} panels")
+        if solver_rows is not None and tuple(solver_rows.shape) != (n, 8):
+            raise ValueError(f"solver rows {tuple(solver_rows.shape)} do not match the {n} table rows")
+        # everything is checked: only now is anything switched or written
+        if g is not None and len(set(g)) > 1:
+            self.enable_per_panel()
+        if seeds is not None:
             self.noise_seeds.copy_(seeds.to(self.dev))
         self.table[:n].copy_(table_rows.to(self.dev, torch.float32))
+        if self.per_panel and self._sampler_key is not None:
+            # the step reads the vector, not column 7: also for equal values, and for none given (column 7 for every panel)
+            g = g if g is not None else [float(table_rows[0, 7])] * self._sampler_key[0]
+            self.guidance.copy_(torch.tensor(g, dtype=torch.float32))
+        elif g is not None:
+            self.table[:n, 7] = g[0]                      # equal values on a uniform plan: column 7 is what the step reads
         if solver_rows is not None:
-            if tuple(solver_rows.shape) != (n, 8):
-                raise ValueError(f"solver rows {tuple(solver_rows.shape)} do not match the {n} table rows")
             self.solver[:n].copy_(solver_rows.to(self.dev, torch.float32))
         self.ctr.zero_()
 
     # -- host-side setters (tiny H2D copies; never inside a captured graph)
     def set_request(self, encoder_hidden_states: Tensor, text_embeds: Tensor, time_ids: Tensor, bbox: Tensor,
-                    dialog_boxes: Optional[Tensor], ip_scale: float):
+                    dialog_boxes: Optional[Tensor], ip_scale):
+        """ip_scale: a number, or one value per batch row (`B` values; under CFG rows n and ns + n belong to panel n and
+        carry the same value).  Values that differ switch the engine to per-panel plans (`enable_per_panel`)."""
         self.enc.copy_(encoder_hidden_states.to(self.dev, torch.float16).reshape(self.enc.shape))
         self.text_embeds.copy_(text_embeds.to(self.dev, torch.float16).reshape(self.text_embeds.shape))
         self.time_ids.copy_(time_ids.to(self.dev, torch.float16).reshape(self.time_ids.shape))
@@ -857,5 +925,10 @@ class UNetEngine:
             self.dialog_boxes.zero_()
         else:
             self.dialog_boxes.copy_(dialog_boxes.to(self.dev, torch.int32).reshape(self.dialog_boxes.shape))
-        self.ip_scale.fill_(float(ip_scale))
+        s = self._scale_values(ip_scale, self.B, "ip_scale")
+        if s is None or len(set(s)) == 1:
+            self.ip_scale.fill_(float(ip_scale) if s is None else s[0])
+        else:
+            self.enable_per_panel()
+            self.ip_scale.copy_(torch.tensor(s, dtype=torch.float32))
         self.prepare_plan.run()

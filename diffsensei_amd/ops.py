@@ -274,7 +274,8 @@ def masked_ip_attention(q: Tensor, kt: Tensor, vtt: Tensor, ki: Tensor, vti: Ten
     The strides of the C ABI (include/diffsensei_hip.h) are taken from the tensors, so column slices of wider buffers work as
     they are: q / out `buf[:, :, c0:c0+C]` (row stride ldq / ldo, batch stride N rows), key panels `stacked[:, :, c0:c0+C]`
     (ldk, sk), value panels `stacked_t[:, c0:c0+C, :]` (sv).  `ldq, ldo, ldk, sk, sv` override what the tensors say;
-    `ip_scale_dev` (one fp32 on the device) replaces `ip_scale`."""
+    `ip_scale_dev` (fp32 on the device) replaces `ip_scale`: shape [1] is one scale for the batch, shape [B] one per batch
+    row (under CFG rows n and ns + n belong to panel n and carry the same value).  With B = 1 the two mean the same."""
     for t in (q, kt, vtt, ki, vti, out):
         if t is None:
             continue
@@ -286,6 +287,9 @@ def masked_ip_attention(q: Tensor, kt: Tensor, vtt: Tensor, ki: Tensor, vti: Ten
     _chk(bbox, dtype=torch.float32)
     _chk(ip_scale_dev, dtype=torch.float32)
     B, N, Cc = q.shape
+    if ip_scale_dev is not None and (ip_scale_dev.device != q.device or tuple(ip_scale_dev.shape) not in ((1,), (B,))):
+        raise _lib.DiffSenseiHipError(f"masked_ip_attention: ip_scale_dev {tuple(ip_scale_dev.shape)} on {ip_scale_dev.device}: "
+                                      f"(1,) or ({B},) on {q.device} is needed")
     if out is None:
         out = torch.empty((B, N, Cc), dtype=torch.float16, device=q.device)
     if out.shape != q.shape:
@@ -299,6 +303,12 @@ def masked_ip_attention(q: Tensor, kt: Tensor, vtt: Tensor, ki: Tensor, vti: Ten
     ldk = kt.stride(1) if ldk is None else ldk
     sk = kt.stride(0) if sk is None else sk
     sv = vtt.stride(0) if sv is None else sv
+    if ip_scale_dev is not None and ip_scale_dev.shape[0] > 1:
+        check(_lib.load().ds_masked_ip_attn_rows_f16(_p(q), ldq, _p(kt), _p(vtt), _p(ki), _p(vti), _p(bbox), _p(out), ldo, B,
+                                                     heads, N, Lt, Li, n_dummy, tok_per_ip, bbox.shape[1], mask_hw[0],
+                                                     mask_hw[1], qk_scale, _p(ip_scale_dev), ldk, sk, sv, _stream()),
+              "ds_masked_ip_attn_rows_f16")
+        return out
     check(_lib.load().ds_masked_ip_attn_f16(_p(q), ldq, _p(kt), _p(vtt), _p(ki), _p(vti), _p(bbox), _p(out), ldo, B, heads,
                                             N, Lt, Li, n_dummy, tok_per_ip, bbox.shape[1], mask_hw[0], mask_hw[1],
                                             qk_scale, ip_scale, _p(ip_scale_dev), ldk, sk, sv, _stream()),
@@ -416,10 +426,14 @@ def _chk_seeds(seeds: Optional[Tensor], ns: int) -> None:
 
 
 def _sampler_step_dims(eps: Tensor, latents: Tensor, model_in: Tensor, table: Tensor, solver: Optional[Tensor] = None,
-                       prev_x0: Optional[Tensor] = None, seeds: Optional[Tensor] = None) -> Tuple[int, int]:
-    """The checks the three entry points of `sampler_step_kernel` share; returns (ns, HW)."""
+                       prev_x0: Optional[Tensor] = None, seeds: Optional[Tensor] = None,
+                       guidance: Optional[Tensor] = None) -> Tuple[int, int]:
+    """The checks the entry points of `sampler_step_kernel` share; returns (ns, HW)."""
     _chk(eps, latents, model_in, prev_x0)
-    _chk(table, solver, dtype=torch.float32)
+    _chk(table, solver, guidance, dtype=torch.float32)
+    if guidance is not None and (tuple(guidance.shape) != (latents.shape[0],) or guidance.device != latents.device):
+        raise _lib.DiffSenseiHipError(f"guidance {tuple(guidance.shape)} on {guidance.device}: one fp32 per panel, "
+                                      f"({latents.shape[0]},), on {latents.device} is needed")
     if prev_x0 is not None and prev_x0.shape != latents.shape:
         raise ValueError(f"prev_x0 {tuple(prev_x0.shape)} must have the latents' shape {tuple(latents.shape)}")
     ns = latents.shape[0]
@@ -427,28 +441,47 @@ def _sampler_step_dims(eps: Tensor, latents: Tensor, model_in: Tensor, table: Te
     return ns, latents.shape[2] * latents.shape[3]
 
 
+def _step_panels(eps, latents, model_in, table, guidance, solver, prev_x0, seeds, ctr, ns, HW, kind, do_cfg) -> None:
+    """Every kind with one guidance scale per panel (`guidance`: fp32 [ns] in place of column 7 of the table)."""
+    check(_lib.load().ds_cfg_sampler_step_panels_f16(_p(eps), _p(latents), _p(model_in), _p(table), _p(guidance), _p(solver),
+                                                     _p(prev_x0), _p(seeds), _p(ctr), ns, HW, kind, int(do_cfg), _stream()),
+          "ds_cfg_sampler_step_panels_f16")
+
+
 def cfg_sampler_step(eps: Tensor, latents: Tensor, model_in: Tensor, table: Tensor, kind: int, do_cfg: bool = True,
-                     ctr: Optional[Tensor] = None) -> None:
-    """eps: [2ns,HW,4] NHWC; latents: [ns,4,H,W] NCHW (in place); model_in: [2ns,HW,4]."""
-    ns, HW = _sampler_step_dims(eps, latents, model_in, table)
+                     ctr: Optional[Tensor] = None, guidance: Optional[Tensor] = None) -> None:
+    """eps: [2ns,HW,4] NHWC; latents: [ns,4,H,W] NCHW (in place); model_in: [2ns,HW,4].  `guidance`: fp32 [ns], one
+    scale per panel (rows n and ns + n of eps) in place of column 7 of the table; None: column 7."""
+    ns, HW = _sampler_step_dims(eps, latents, model_in, table, guidance=guidance)
+    if guidance is not None:
+        if kind not in (0, 1):
+            raise _lib.DiffSenseiHipError("cfg_sampler_step: kind 0 or 1 (2: cfg_dpm_step, 3: cfg_sampler_step_noise)")
+        return _step_panels(eps, latents, model_in, table, guidance, None, None, None, ctr, ns, HW, kind, do_cfg)
     check(_lib.load().ds_cfg_sampler_step_f16(_p(eps), _p(latents), _p(model_in), _p(table), _p(ctr), ns, HW, kind,
                                               int(do_cfg), _stream()), "ds_cfg_sampler_step_f16")
 
 
 def cfg_dpm_step(eps: Tensor, latents: Tensor, model_in: Tensor, table: Tensor, solver: Tensor, prev_x0: Tensor,
-                 do_cfg: bool = True, ctr: Optional[Tensor] = None) -> None:
+                 do_cfg: bool = True, ctr: Optional[Tensor] = None, guidance: Optional[Tensor] = None) -> None:
     """DPM-Solver++ step: eps [2ns,HW,4] NHWC; latents, prev_x0: [ns,4,H,W] NCHW (both in place); model_in: [2ns,HW,4];
-    solver: fp32 rows [n,8] (include/diffsensei_hip.h)."""
-    ns, HW = _sampler_step_dims(eps, latents, model_in, table, solver=solver, prev_x0=prev_x0)
+    solver: fp32 rows [n,8] (include/diffsensei_hip.h); `guidance`: as in `cfg_sampler_step`."""
+    ns, HW = _sampler_step_dims(eps, latents, model_in, table, solver=solver, prev_x0=prev_x0, guidance=guidance)
+    if guidance is not None:
+        return _step_panels(eps, latents, model_in, table, guidance, solver, prev_x0, None, ctr, ns, HW, 2, do_cfg)
     check(_lib.load().ds_cfg_dpm_step_f16(_p(eps), _p(latents), _p(model_in), _p(table), _p(solver), _p(prev_x0),
                                           _p(ctr), ns, HW, int(do_cfg), _stream()), "ds_cfg_dpm_step_f16")
 
 
 def cfg_sampler_step_noise(eps: Tensor, latents: Tensor, model_in: Tensor, table: Tensor, seeds: Optional[Tensor],
-                           kind: int, do_cfg: bool = True, ctr: Optional[Tensor] = None) -> None:
+                           kind: int, do_cfg: bool = True, ctr: Optional[Tensor] = None,
+                           guidance: Optional[Tensor] = None) -> None:
     """`cfg_sampler_step` with the per-panel Philox seeds (int64 [ns]) that kind 3, Euler Ancestral, draws its noise
     from: the noise of panel n at this launch is a function of (seeds[n], pixel, *ctr) only."""
-    ns, HW = _sampler_step_dims(eps, latents, model_in, table, seeds=seeds)
+    ns, HW = _sampler_step_dims(eps, latents, model_in, table, seeds=seeds, guidance=guidance)
+    if guidance is not None:
+        if kind == 2:
+            raise _lib.DiffSenseiHipError("cfg_sampler_step_noise: kind 2 needs solver rows and prev_x0 (cfg_dpm_step)")
+        return _step_panels(eps, latents, model_in, table, guidance, None, None, seeds, ctr, ns, HW, kind, do_cfg)
     check(_lib.load().ds_cfg_sampler_step_noise_f16(_p(eps), _p(latents), _p(model_in), _p(table), _p(seeds), _p(ctr),
                                                     ns, HW, kind, int(do_cfg), _stream()),
           "ds_cfg_sampler_step_noise_f16")

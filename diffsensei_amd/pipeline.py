@@ -23,6 +23,7 @@ from typing import Any, List, Optional, Sequence, Tuple, Union
 
 import torch
 
+from .engine import _is_number
 from .encoders import ClipTextEngine, ClipVisionEngine, ViTMAEEngine
 from .schedulers import draw_noise_seeds
 from .unet import UNetMangaModel, dialog_pixel_boxes
@@ -324,7 +325,12 @@ class DiffSenseiPipeline:
 
         `noise_seeds` (stochastic samplers only, i.e. `EulerAncestralDiscreteScheduler`): `num_samples` non-negative
         int64 seeds, one per panel, that the step kernel draws its noise from; by default they are drawn from `generator`
-        after the initial latents (`schedulers.draw_noise_seeds`).  The seeds used are in `last_run_info["noise_seeds"]`."""
+        after the initial latents (`schedulers.draw_noise_seeds`).  The seeds used are in `last_run_info["noise_seeds"]`.
+
+        `guidance_scale` and `ip_scale` are a number, as in the reference, or a sequence of `num_samples` numbers, one per
+        sample (a slider sweep in one pass: the kernels take both per panel).  Classifier-free guidance is on or off
+        for the whole batch, so a sequence is all > 1 or all <= 1.  `last_run_info["guidance_scales"]` /
+        `["ip_scales"]` list what every panel used."""
         bad = [k for k in callback_on_step_end_tensor_inputs if k != "latents"]
         if bad:
             raise ValueError(f"`callback_on_step_end_tensor_inputs` has to be in ['latents'], but found {bad}")
@@ -334,7 +340,7 @@ class DiffSenseiPipeline:
                                   target_size, ip_images, ip_image_embeds, ip_bbox, ip_scale, dialog_bbox, latents,
                                   prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds,
                                   negative_pooled_prompt_embeds, noise_seeds)
-        out_latents = self._denoise([cond], num_inference_steps, guidance_scale, ip_scale, callback_on_step_end)
+        out_latents = self._denoise([cond], num_inference_steps, callback_on_step_end)
         return StableDiffusionXLPipelineOutput(images=self._postprocess(out_latents, output_type))
 
     # ---- one request's conditioning tensors (reference :205-309), `num_samples` rows each, conditional and negative
@@ -349,9 +355,13 @@ class DiffSenseiPipeline:
         self.check_inputs(prompt, prompt_2, ip_images, ip_image_embeds, ip_bbox)
         if height % self.vae_scale_factor or width % self.vae_scale_factor:
             raise ValueError(f"`height` and `width` have to be divisible by {self.vae_scale_factor} but are {height} and {width}.")
-        self._guidance_scale = guidance_scale
+        num_samples = 1 if num_samples is None else num_samples
+        guidance = self._panel_values(guidance_scale, num_samples, "guidance_scale")
+        ip_scales = self._panel_values(ip_scale, num_samples, "ip_scale")
+        self._cfg_side(guidance)
+        self._guidance_scale = guidance_scale if _is_number(guidance_scale) else guidance[0]
         device = self._execution_device
-        self.set_ip_scale(ip_scale)
+        self.set_ip_scale(ip_scale if _is_number(ip_scale) else ip_scales[-1])
         do_cfg = self.do_classifier_free_guidance
 
         if prompt_embeds is None:
@@ -388,14 +398,37 @@ class DiffSenseiPipeline:
         neg_dialog, dialog = self.prepare_dialog_bbox(list(dialog_bbox), num_samples)
         to = lambda t: t.to(device)
         return {"n": num_samples, "lat": lat, "time_ids": add_time_ids, "noise_seeds": seeds,
+                "guidance": guidance, "ip_scales": ip_scales,
                 "pos": (to(prompt_embeds), to(pooled_prompt_embeds), to(img), to(bbox), to(dialog)),
                 "neg": (to(negative_prompt_embeds), to(negative_pooled_prompt_embeds), to(neg_img), to(neg_bbox),
                         to(neg_dialog))}
 
     # ---- the denoising loop over one UNet batch assembled from >= 1 requests of the same shape (reference :310-337)
-    def _denoise(self, conds, num_inference_steps, guidance_scale, ip_scale, callback_on_step_end=None) -> Tensor:
+    @staticmethod
+    def _panel_values(value, num_samples: int, name: str) -> List[float]:
+        """`guidance_scale` / `ip_scale` as one float per sample: a number for all of them, or `num_samples` numbers."""
+        if _is_number(value):
+            return [float(value)] * num_samples
+        vals = [float(v) for v in (value.reshape(-1).tolist() if torch.is_tensor(value) else value)]
+        if len(vals) != num_samples:
+            raise ValueError(f"`{name}`: a number or {num_samples} numbers (num_samples) are needed, got {len(vals)}")
+        return vals
+
+    @staticmethod
+    def _cfg_side(guidance: List[float]) -> bool:
+        """Classifier-free guidance changes the batch layout, so it is on (every value > 1) or off for a whole batch."""
+        on = [g > 1 for g in guidance]
+        if any(on) != all(on):
+            raise ValueError(f"guidance scales {guidance} mix classifier-free guidance on (> 1) and off (<= 1) in one "
+                             f"UNet batch; run them in separate calls (serving: separate buckets)")
+        return all(on)
+
+    def _denoise(self, conds, num_inference_steps, callback_on_step_end=None) -> Tensor:
         device = self._execution_device
-        self._guidance_scale = guidance_scale
+        guidance = [g for c in conds for g in c["guidance"]]          # per panel, in batch order
+        ip_scales = [s for c in conds for s in c["ip_scales"]]
+        self._cfg_side(guidance)
+        self._guidance_scale = guidance[-1]
         do_cfg = self.do_classifier_free_guidance
         self.scheduler.set_timesteps(num_inference_steps, device=device)
         lat = torch.cat([c["lat"] for c in conds], dim=0)
@@ -424,12 +457,14 @@ class DiffSenseiPipeline:
         B = enc.shape[0]
         eng = self.unet.engine(B, H, W, aspect_ratio)
         eng.build_sampler(num_samples, self.scheduler.kind, do_cfg)
-        eng.set_request(enc, add_text_embeds, add_time_ids, bbox, dialog_pixel_boxes(dialog, H, W), float(ip_scale))
+        # rows n and ns + n of a CFG batch are panel n: both carry its IP scale
+        eng.set_request(enc, add_text_embeds, add_time_ids, bbox, dialog_pixel_boxes(dialog, H, W),
+                        ip_scales + ip_scales if do_cfg else ip_scales)
         solver = self.scheduler.solver_table()             # DPM-Solver++ rows; None for Euler / DDIM
         # the panels' own seeds, in batch order: a panel's noise does not depend on the requests batched beside it
         seeds = [v for c in conds for v in c["noise_seeds"]] if self.scheduler.stochastic else None
-        eng.load_schedule(torch.from_numpy(self.scheduler.coef_table(float(guidance_scale))),
-                          None if solver is None else torch.from_numpy(solver), seeds)
+        eng.load_schedule(torch.from_numpy(self.scheduler.coef_table(guidance[0])),
+                          None if solver is None else torch.from_numpy(solver), seeds, guidance=guidance)
         eng.latents.copy_(lat)
         if self._stream is None:
             self._stream = torch.cuda.Stream(device=device)
@@ -469,7 +504,7 @@ class DiffSenseiPipeline:
                     hook(i)
         torch.cuda.current_stream(device).wait_stream(st)
         self.last_run_info = {"graph": graph, "ops_per_step": eng.step_plan.n, "batch": B, "latent_hw": (H, W),
-                              "noise_seeds": seeds}
+                              "noise_seeds": seeds, "guidance_scales": guidance, "ip_scales": ip_scales}
         return eng.latents.clone()
 
     # ---- reference :339-367: VAE decode + image_processor.postprocess
@@ -547,16 +582,20 @@ class DiffSenseiPipeline:
     # ---- several requests of one shape in ONE UNet batch (serving front-end)
     @torch.no_grad()
     def generate_batch(self, requests: List[dict], output_type: str = "pil") -> List[Any]:
-        """Each request: the keyword arguments of `__call__` (without `output_type`).  All must share height, width,
-        num_inference_steps, guidance_scale and ip_scale (`serving.bucket_key`); prompts, character references, boxes,
-        seeds and `num_samples` are per request.  Returns one `.images`-like object per request, in order."""
+        """Each request: the keyword arguments of `__call__` (without `output_type`).  All must share height, width and
+        num_inference_steps (`serving.bucket_key`), and their guidance scales lie on one side of 1 (classifier-free
+        guidance is on or off for the whole UNet batch); prompts, character references, boxes, seeds, `num_samples`,
+        `guidance_scale` and `ip_scale` are per request.  Returns one `.images`-like object per request, in order."""
         if not requests:
             return []
         self._interrupt = False          # like `__call__` (reference :226): an earlier interrupted call must not leak into this one
-        key = lambda r: (r.get("height"), r.get("width"), r.get("num_inference_steps", 40), r.get("guidance_scale", 5.0),
-                         r.get("ip_scale", 1.0))
+        key = lambda r: (r.get("height"), r.get("width"), r.get("num_inference_steps", 40))
         if any(key(r) != key(requests[0]) for r in requests):
-            raise ValueError("generate_batch: requests must share height/width/steps/guidance_scale/ip_scale")
+            raise ValueError("generate_batch: requests must share height/width/steps")
+        sides = [self._cfg_side(self._panel_values(r.get("guidance_scale", 5.0), r.get("num_samples", 1) or 1, "guidance_scale"))
+                 for r in requests]                 # before any encoder runs
+        if any(s != sides[0] for s in sides):
+            raise ValueError("generate_batch: requests mix classifier-free guidance on (guidance_scale > 1) and off (<= 1)")
         names = ("prompt", "prompt_2", "height", "width", "num_inference_steps", "guidance_scale", "negative_prompt",
                  "negative_prompt_2", "num_samples", "generator", "original_size", "crops_coords_top_left", "target_size",
                  "ip_images", "ip_image_embeds", "ip_bbox", "ip_scale", "dialog_bbox", "latents", "prompt_embeds",
@@ -572,8 +611,7 @@ class DiffSenseiPipeline:
             if unknown:
                 raise TypeError(f"generate_batch: unknown request fields {sorted(unknown)}")
             conds.append(self._conditioning(*[r[n] if n in r else defaults[n] for n in names]))
-        r0 = requests[0]
-        out = self._denoise(conds, r0.get("num_inference_steps", 40), r0.get("guidance_scale", 5.0), r0.get("ip_scale", 1.0))
+        out = self._denoise(conds, requests[0].get("num_inference_steps", 40))
         images = self._postprocess(out, output_type)
         res, off = [], 0
         for c in conds:

@@ -12,7 +12,13 @@ Here the same idea is applied to inference, because one UNet launch plan / hipGr
 
 Requests that share (height, width, steps, guidance_scale, ip_scale) are concatenated into one UNet batch of at most
 `max_panels` panels (`DiffSenseiPipeline.generate_batch`: per-request prompts, character references, boxes, seeds);
-buckets run largest-resolution first.  Multi-GPU: shard the request list with `distributed.shard_requests` (LPT by
+buckets run largest-resolution first.
+
+`mix_scales=True` (`bucket_key`, `plan_batches`, `BucketBatcher`) drops the two sliders from that key: guidance and IP
+scale are per-panel vectors in the kernels, so requests that differ only in them share a batch, a launch plan and a
+captured hipGraph, and every panel still gets its own values.  What stays in the key is which side of 1 the guidance is
+on: classifier-free guidance doubles the UNet batch, so it is on or off for a whole batch.  The default, False, is the
+five-value key above.  Multi-GPU: shard the request list with `distributed.shard_requests` (LPT by
 pixel count, no data-path collective) and run one batcher per rank.
 """
 from __future__ import annotations
@@ -20,13 +26,32 @@ from __future__ import annotations
 from typing import Any, Dict, List, Optional, Tuple
 
 
-def bucket_key(request: dict) -> Tuple:
-    """What must agree for two requests to share a UNet batch."""
-    return (request.get("height"), request.get("width"), request.get("num_inference_steps", 40),
-            float(request.get("guidance_scale", 5.0)), float(request.get("ip_scale", 1.0)))
+def _scale_key(v):
+    """A slider value as a hashable: a float (anything `float()` takes, as before), or a tuple of floats for the
+    one-value-per-sample form."""
+    try:
+        return float(v)
+    except (TypeError, ValueError):
+        return tuple(float(x) for x in v)
 
 
-def plan_batches(requests: List[dict], max_panels: int, max_pixels: Optional[int] = None) -> List[List[int]]:
+def bucket_key(request: dict, mix_scales: bool = False) -> Tuple:
+    """What must agree for two requests to share a UNet batch.  mix_scales: (height, width, steps, guidance > 1) - the
+    sliders travel per panel, only classifier-free guidance on / off is a property of the batch.  A request whose own
+    guidance values lie on both sides of 1 fits no batch and is a ValueError here, so that it cannot take the requests
+    bucketed with it down (`BucketBatcher.submit` checks every request this way)."""
+    g = _scale_key(request.get("guidance_scale", 5.0))
+    if mix_scales:
+        on = {x > 1 for x in (g if isinstance(g, tuple) else (g,))}
+        if len(on) != 1:
+            raise ValueError(f"guidance_scale {list(g)} mixes classifier-free guidance on (> 1) and off (<= 1) in one request")
+        return (request.get("height"), request.get("width"), request.get("num_inference_steps", 40), on.pop())
+    return (request.get("height"), request.get("width"), request.get("num_inference_steps", 40), g,
+            _scale_key(request.get("ip_scale", 1.0)))
+
+
+def plan_batches(requests: List[dict], max_panels: int, max_pixels: Optional[int] = None,
+                 mix_scales: bool = False) -> List[List[int]]:
     """Indices of `requests` grouped into batches: same bucket, at most `max_panels` panels (sum of num_samples) per
     batch - and at most `max_pixels` output pixels if given, so small resolutions get proportionally larger batches (a
     single request above the pixel cap but within `max_panels` runs alone; only `num_samples > max_panels` is an error) -
@@ -35,7 +60,7 @@ def plan_batches(requests: List[dict], max_panels: int, max_pixels: Optional[int
         raise ValueError("max_panels must be >= 1")
     buckets: Dict[Tuple, List[int]] = {}
     for i, r in enumerate(requests):
-        buckets.setdefault(bucket_key(r), []).append(i)
+        buckets.setdefault(bucket_key(r, mix_scales), []).append(i)
     order = sorted(buckets, key=lambda k: -((k[0] or 0) * (k[1] or 0)))
     batches: List[List[int]] = []
     for k in order:
@@ -68,13 +93,15 @@ def plan_batches(requests: List[dict], max_panels: int, max_pixels: Optional[int
 class BucketBatcher:
     """Collects requests, then runs them bucket by bucket through `pipe.generate_batch`."""
 
-    def __init__(self, pipe, max_panels: int = 32, max_pixels: Optional[int] = 32 * 1024 * 1024):
+    def __init__(self, pipe, max_panels: int = 32, max_pixels: Optional[int] = 32 * 1024 * 1024,
+                 mix_scales: bool = False):
         # defaults = the benchmark's operating point (bench.py: 32 panels of 1024 x 1024 per call = UNet batch 64, where every
         # projection of the level-2 transformers is a whole number of 256-tile rounds); the pixel cap scales the panel count
         # down for larger images and lets smaller ones use the full 32
         self.pipe = pipe
         self.max_panels = max_panels
         self.max_pixels = max_pixels
+        self.mix_scales = mix_scales         # requests that differ only in guidance_scale / ip_scale share a batch
         self._pending: List[dict] = []
         self.last_plan: List[List[int]] = []
 
@@ -82,6 +109,7 @@ class BucketBatcher:
         """Queue one request (keyword arguments of `DiffSenseiPipeline.__call__`, without `output_type`); returns its ticket."""
         if "output_type" in request:
             raise TypeError("output_type is chosen per run(), not per request")
+        bucket_key(request, True)            # a request no batch can hold is refused here, not when its batch runs
         self._pending.append(request)
         return len(self._pending) - 1
 
@@ -91,7 +119,7 @@ class BucketBatcher:
     def run(self, output_type: str = "pil") -> List[Any]:
         """Run everything queued; returns the per-request outputs indexed by ticket and empties the queue."""
         reqs, self._pending = self._pending, []
-        self.last_plan = plan_batches(reqs, self.max_panels, self.max_pixels)
+        self.last_plan = plan_batches(reqs, self.max_panels, self.max_pixels, self.mix_scales)
         results: List[Any] = [None] * len(reqs)
         for batch in self.last_plan:
             outs = self.pipe.generate_batch([reqs[i] for i in batch], output_type=output_type)

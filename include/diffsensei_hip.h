@@ -257,6 +257,15 @@ int ds_masked_ip_attn_f16(const void* q, int64_t ldq, const void* kt, const void
                           int Li, int n_dummy, int tok_per_ip, int max_ips, int mask_h, int mask_w, float qk_scale,
                           float ip_scale, const float* ip_scale_dev, int64_t ldk, int64_t sk, int64_t sv,
                           void* stream);
+/* ds_masked_ip_attn_f16 with one IP scale per batch row: ip_scale_rows_dev is a device fp32 vector [B] and row b uses
+ * element b,  w = (ip part ? ip_scale_rows_dev[b] : 1) / sum  - the scalar call's arithmetic with that row's value.
+ * Panel <-> row rule: a classifier-free-guidance batch of ns panels is B = 2 ns rows, all negative rows first, so rows n
+ * and ns + n both belong to panel n and the caller writes that panel's scale into both elements.  The vector is read at
+ * launch time by every block (a captured graph follows what was last written to it). */
+int ds_masked_ip_attn_rows_f16(const void* q, int64_t ldq, const void* kt, const void* vtt, const void* ki,
+                               const void* vti, const float* bbox, void* o, int64_t ldo, int B, int heads, int N, int Lt,
+                               int Li, int n_dummy, int tok_per_ip, int max_ips, int mask_h, int mask_w, float qk_scale,
+                               const float* ip_scale_rows_dev, int64_t ldk, int64_t sk, int64_t sv, void* stream);
 /* debug/test hook: bit k of flags[b*N+i] = token i inside box k (the reference's inside_bbox_mask) */
 int ds_ip_region_flags(const float* bbox, uint8_t* flags, int B, int N, int max_ips, int mask_h, int mask_w,
                        void* stream);
@@ -336,6 +345,14 @@ int ds_philox_normal_f32(const int64_t* seeds, int step, int stream_id, float* o
 int ds_cfg_sampler_step_noise_f16(const void* eps, void* latents, void* model_in, const float* table,
                                   const int64_t* seeds, const int32_t* step_ctr, int ns, int HW, int kind, int do_cfg,
                                   void* stream);
+/* The sampler step with one guidance scale per panel, for every kind (0 Euler, 1 DDIM, 2 DPM-Solver++, 3 Euler
+ * Ancestral): the superset of the three calls above.  guidance: device fp32 [ns]; panel n - eps rows n (negative) and
+ * ns + n (conditional), latents / prev_x0 / seeds element n - uses guidance[n] where the calls above use column 7 of the
+ * table row:  gd = fp16(guidance[n] * fp16(ec - eu)),  e = fp16(eu + gd).  NULL = column 7, i.e. exactly the calls above.
+ * Not read when do_cfg = 0.  solver / prev_x0: kind 2 only, seeds: kind 3 only (NULL otherwise). */
+int ds_cfg_sampler_step_panels_f16(const void* eps, void* latents, void* model_in, const float* table,
+                                   const float* guidance, const float* solver, void* prev_x0, const int64_t* seeds,
+                                   const int32_t* step_ctr, int ns, int HW, int kind, int do_cfg, void* stream);
 int ds_prepare_model_input_f16(const void* latents, void* model_in, const float* table, const int32_t* step_ctr,
                                int ns, int HW, int do_cfg, void* stream);
 int ds_nhwc_to_nchw_f16(const void* x, void* y, int B, int HW, int C, void* stream);
@@ -431,14 +448,16 @@ enum ds_opcode {
     DS_OP_LAYERNORM = 4,     /* p: x, y, gamma, beta                      i: rows C                   f: eps */
     DS_OP_SELF_ATTN = 5,     /* p: q, k, vt, o   l: ldq ldk ldv ldo sq sk so   i: B heads Nq Nk       f: scale */
     DS_OP_IP_ATTN = 6,       /* p: q, kt, vtt, ki, vti, bbox, o, ip_scale_dev   l: ldq ldo ldk sk sv
-                                i: B heads N Lt Li n_dummy tok_per_ip max_ips mask_h mask_w   f: qk_scale ip_scale */
+                                i: B heads N Lt Li n_dummy tok_per_ip max_ips mask_h mask_w; i[10] = 1: ip_scale_dev is a
+                                   [B] vector, one scale per batch row (ds_masked_ip_attn_rows_f16); 0: one device scalar
+                                f: qk_scale ip_scale */
     DS_OP_CONV_IN = 7,       /* p: x, w, bias, boxes, demb, y             i: B H W Cin Cout ndialog */
     DS_OP_CONV_OUT = 8,      /* p: x, w, bias, y                          i: B H W Cin Cout */
     DS_OP_SKINNY = 9,        /* p: x, w, bias, addend, y                  i: M N K silu_in silu_out */
     DS_OP_TIMESTEP_EMBED = 10, /* p: table, ctr, out                      i: B dim flip               f: freq_shift */
     DS_OP_ADD_TIME_IDS = 11, /* p: text_embeds, time_ids, out             i: B pooled n_ids dim flip  f: freq_shift */
     DS_OP_SAMPLER_STEP = 12, /* p: eps, latents, model_in, table, ctr, prev_x0, solver (these two: kind 2 only),
-                                   seeds (kind 3 only)
+                                   seeds (kind 3 only), guidance (p[8]: fp32 [ns], one per panel; NULL = column 7 of the table)
                                 i: ns HW kind (0 Euler, 1 DDIM, 2 DPM-Solver++, 3 Euler Ancestral) do_cfg */
     DS_OP_PREP_INPUT = 13,   /* p: latents, model_in, table, ctr          i: ns HW do_cfg */
     DS_OP_ADVANCE = 14,      /* p: ctr */
