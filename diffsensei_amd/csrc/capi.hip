@@ -424,21 +424,21 @@ int ds_skinny_linear_f16(const void* x, const void* w, const void* bias, const v
 // ---- MLLM pre-pass (llm.hip): LLaMA greedy decoding
 static int llm_gemv_impl(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, const void* residual,
                          int64_t ldr, int M, int N, int K, int rms, int swiglu, float eps, hipStream_t st,
-                         const void* rms_gain = nullptr) {
+                         const void* rms_gain = nullptr, bool gemm16 = false) {
     LlmGemvParams g;
     g.x = H(x); g.w = H(w); g.y = HM(y); g.residual = H(residual); g.gain = rms ? H(rms_gain) : nullptr;
     g.ldx = ldx; g.ldy = ldy; g.ldr = ldr; g.M = M; g.N = N; g.K = K; g.rms = rms; g.swiglu = swiglu; g.eps = eps;
-    return ds_launch_llm_gemv(g, st);
+    return gemm16 ? ds_launch_llm_gemm16(g, st) : ds_launch_llm_gemv(g, st);
 }
 
 static int llm_attn_impl(const void* qkv, int64_t ldqkv, void* kc, void* vc, int64_t ldc, const float* rope_cos,
                          const float* rope_sin, void* out, int64_t ldo, const int32_t* state, int M, int heads,
-                         int kv_heads, int D, int T_max, float scale, hipStream_t st) {
+                         int kv_heads, int D, int T_max, float scale, hipStream_t st, int64_t slot_stride = -1) {
     LlmAttnParams a;
     a.qkv = H(qkv); a.kc = HM(kc); a.vc = HM(vc); a.rope_cos = rope_cos; a.rope_sin = rope_sin; a.out = HM(out);
     a.state = state; a.ldqkv = ldqkv; a.ldc = ldc; a.ldo = ldo;
     a.M = M; a.heads = heads; a.kv_heads = kv_heads; a.D = D; a.T_max = T_max; a.scale = scale;
-    return ds_launch_llm_attn(a, st);
+    return slot_stride >= 0 ? ds_launch_llm_attn_slots(a, (long)slot_stride, st) : ds_launch_llm_attn(a, st);
 }
 
 int ds_llm_gemv_f16(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, const void* residual,
@@ -471,6 +471,35 @@ int ds_llm_advance(int32_t* state, int rows, void* stream) { return ds_launch_ll
 
 int ds_llm_swiglu_f16(const void* gate_up, void* act, int M, int I, void* stream) {
     return ds_launch_llm_swiglu(H(gate_up), HM(act), M, I, S(stream));
+}
+
+// ---- batched decode: up to 16 sequences per weight pass
+int ds_llm_gemm16(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, const void* residual, int64_t ldr,
+                  int M, int N, int K, int rms, const void* rms_gain, int swiglu, float eps, void* stream) {
+    return llm_gemv_impl(x, ldx, w, y, ldy, residual, ldr, M, N, K, rms, swiglu, eps, S(stream), rms_gain, true);
+}
+
+int ds_llm_attn_slots_f16(const void* qkv, int64_t ldqkv, void* k_cache, void* v_cache, int64_t ldc, int64_t slot_stride,
+                          const float* rope_cos, const float* rope_sin, void* out, int64_t ldo, const int32_t* state,
+                          int slots, int heads, int kv_heads, int D, int T_max, float scale, void* stream) {
+    DS_REQUIRE(slot_stride >= 0, "llm_attn_slots: negative slot stride");
+    return llm_attn_impl(qkv, ldqkv, k_cache, v_cache, ldc, rope_cos, rope_sin, out, ldo, state, slots, heads, kv_heads, D,
+                         T_max, scale, S(stream), slot_stride);
+}
+
+int ds_llm_rmsnorm_slots_f16(const void* x, int64_t ldx, const void* gamma, void* y, int64_t ldy, void* feat,
+                             const int32_t* state, int slots, int Hd, int max_out, float eps, void* stream) {
+    return ds_launch_llm_rmsnorm_slots(H(x), ldx, H(gamma), HM(y), ldy, HM(feat), state, slots, Hd, max_out, eps, S(stream));
+}
+
+int ds_llm_embed_slots_f16(const void* table, const int32_t* state, void* out, int64_t ldo, int slots, int Hd, int vocab,
+                           void* stream) {
+    return ds_launch_llm_embed_slots(H(table), state, HM(out), ldo, slots, Hd, vocab, S(stream));
+}
+
+int ds_llm_select_slots_f16(const void* logits, int64_t ldl, int V, const int32_t* chain, int n_chain, int out_cap, int adv,
+                            int32_t* state, int32_t* out_ids, int slots, void* stream) {
+    return ds_launch_llm_select_slots(H(logits), ldl, V, chain, n_chain, out_cap, adv, state, out_ids, slots, S(stream));
 }
 
 int ds_resize_h_u8(const uint8_t* src, int H_, int W_, const int32_t* first, const int32_t* count, const int32_t* taps,
@@ -671,6 +700,23 @@ static int run_op(const ds_op& o, hipStream_t st) {
                                         reinterpret_cast<int*>(p[2]), reinterpret_cast<int*>(p[3]), st);
         case DS_OP_LLM_ADVANCE:
             return ds_launch_llm_advance(reinterpret_cast<int*>(p[0]), i[0], st);
+        case DS_OP_LLM_GEMM16:
+            return llm_gemv_impl(p[0], l[0], p[1], p[2], l[1], p[3], l[2], i[0], i[1], i[2], i[3], i[4], o.f[0], st, p[4],
+                                 true);
+        case DS_OP_LLM_ATTN_SLOTS:
+            DS_REQUIRE(l[3] >= 0, "llm_attn_slots: negative slot stride");
+            return llm_attn_impl(p[0], l[0], p[1], p[2], l[1], reinterpret_cast<const float*>(p[3]),
+                                 reinterpret_cast<const float*>(p[4]), p[5], l[2], reinterpret_cast<const int32_t*>(p[6]),
+                                 i[0], i[1], i[2], i[3], i[4], o.f[0], st, l[3]);
+        case DS_OP_LLM_RMSNORM_SLOTS:
+            return ds_launch_llm_rmsnorm_slots(H(p[0]), l[0], H(p[1]), HM(p[2]), l[1], HM(p[3]),
+                                               reinterpret_cast<const int*>(p[4]), i[0], i[1], i[2], o.f[0], st);
+        case DS_OP_LLM_EMBED_SLOTS:
+            return ds_launch_llm_embed_slots(H(p[0]), reinterpret_cast<const int*>(p[1]), HM(p[2]), l[0], i[0], i[1], i[2],
+                                             st);
+        case DS_OP_LLM_SELECT_SLOTS:
+            return ds_launch_llm_select_slots(H(p[0]), l[0], i[0], reinterpret_cast<const int*>(p[1]), i[1], i[2], i[3],
+                                              reinterpret_cast<int*>(p[2]), reinterpret_cast<int*>(p[3]), i[4], st);
         default:
             ds_set_error("plan: unknown opcode %d", o.code);
             return -4;
@@ -736,7 +782,15 @@ int ds_op_describe(const ds_op* op, char* name, int name_len, double* flops, dou
             fl = 2.0 * i[0] * (double)i[1] * i[2] * (i[4] ? 2 : 1);
             by = 2.0 * ((double)i[1] * i[2] * (i[4] ? 2 : 1) + (double)i[0] * i[2] + (double)i[0] * i[1]);
             break;
+        case DS_OP_LLM_GEMM16:   // W + x + y bytes: the weights are read once for all M rows
+            nm = "llm_gemm16_kernel";
+            fl = 2.0 * i[0] * (double)i[1] * i[2] * (i[4] ? 2 : 1);
+            by = 2.0 * ((double)i[1] * i[2] * (i[4] ? 2 : 1) + (double)i[0] * i[2] + (double)i[0] * i[1]);
+            break;
         case DS_OP_LLM_ATTN: nm = "llm_attn_kernel"; break;
+        case DS_OP_LLM_ATTN_SLOTS: nm = "llm_attn_slots_kernel"; break;
+        case DS_OP_LLM_RMSNORM_SLOTS: nm = "llm_rmsnorm_slots_kernel"; by = 4.0 * i[0] * (double)i[1]; break;
+        case DS_OP_LLM_SELECT_SLOTS: nm = "llm_select_slots_kernel"; by = 2.0 * i[0] * (double)i[4]; break;
         case DS_OP_LLM_RMSNORM: nm = "llm_rmsnorm_kernel"; by = 4.0 * i[0] * (double)i[1]; break;
         case DS_OP_LLM_SELECT: nm = "llm_select_kernel"; by = 2.0 * i[0]; break;
         default: break;

@@ -252,6 +252,17 @@ int ds_launch_llm_select(const half_t* logits, int V, const int* chain, int n_ch
 int ds_launch_llm_advance(int* state, int rows, hipStream_t stream);
 int ds_launch_blend(const half_t* a, const half_t* b, half_t* out, long n, float s, hipStream_t stream);
 int ds_launch_llm_swiglu(const half_t* gu, half_t* act, int M, int I, hipStream_t stream);
+// batched decode: M <= 16 sequences per weight pass (matrix pipe), and the per-slot forms of the kernels above over a
+// state block int32 [S][8], caches [S][T_max][kv_heads*D] per layer (slot_stride elements apart), feat [S][max_out][H],
+// out_ids [S][out_cap]
+int ds_launch_llm_gemm16(const LlmGemvParams& p, hipStream_t stream);
+int ds_launch_llm_attn_slots(const LlmAttnParams& p, long slot_stride, hipStream_t stream);   // p.M = slots, one row each
+int ds_launch_llm_rmsnorm_slots(const half_t* x, long ldx, const half_t* gamma, half_t* y, long ldy, half_t* feat,
+                                const int* state, int S, int H, int max_out, float eps, hipStream_t stream);
+int ds_launch_llm_embed_slots(const half_t* table, const int* state, half_t* out, long ldo, int S, int H, int vocab,
+                              hipStream_t stream);
+int ds_launch_llm_select_slots(const half_t* logits, long ldl, int V, const int* chain, int n_chain, int out_cap, int adv,
+                               int* state, int* out_ids, int S, hipStream_t stream);
 
 // ---- character-reference pre-processing (preprocess.hip): Pillow's 8-bit separable resize + crop + normalise ----
 int ds_launch_resize_h(const uint8_t* src, int H, int W, const int* first, const int* count, const int* taps, int ksize,

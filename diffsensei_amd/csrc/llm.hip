@@ -141,13 +141,12 @@ __device__ __forceinline__ void rope_chunk(const half_t* row, int c, const float
 constexpr int ATT_WAVES = 16;  // one key group per wavefront per iteration: the loop is a chain of dependent loads
 
 template <int D>
-__global__ __launch_bounds__(64 * ATT_WAVES) void llm_attn_kernel(LlmAttnParams p) {
+__device__ __forceinline__ void llm_attn_body(const LlmAttnParams& p, const int h, const int r) {
     constexpr int LPK = D / 8, KPW = 64 / LPK, HALF = D / 2;
     extern __shared__ float sm[];
     float* sc = sm;                    // [T_max] scores, then probabilities
     float* red = sm + p.T_max;         // [ATT_WAVES][D]
     float* misc = red + ATT_WAVES * D;  // [2 * ATT_WAVES]
-    const int h = blockIdx.x, r = blockIdx.y;
     const int hkv = h / (p.heads / p.kv_heads);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane % LPK, ks = lane / LPK;
@@ -251,19 +250,36 @@ __global__ __launch_bounds__(64 * ATT_WAVES) void llm_attn_kernel(LlmAttnParams 
     }
 }
 
+template <int D>
+__global__ __launch_bounds__(64 * ATT_WAVES) void llm_attn_kernel(LlmAttnParams p) {
+    llm_attn_body<D>(p, blockIdx.x, blockIdx.y);
+}
+
+// Batched decode: block (head h, slot s) runs the same body on row s of qkv / out, on slot s's own cache
+// (kc + s * slot_stride) and its own state row (state + 8 s), so its length state[s][0] sets its rotary position.
+// A finished (or never started) slot returns before it touches anything.
+template <int D>
+__global__ __launch_bounds__(64 * ATT_WAVES) void llm_attn_slots_kernel(LlmAttnParams p, long slot_stride) {
+    const int s = blockIdx.y;
+    p.state += 8 * s;
+    if (p.state[2]) return;
+    p.qkv += (long)s * p.ldqkv;
+    p.out += (long)s * p.ldo;
+    p.kc += (long)s * slot_stride;
+    p.vc += (long)s * slot_stride;
+    llm_attn_body<D>(p, blockIdx.x, 0);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // y[m] = g * (x[m] / rms(x[m]))  (LlamaRMSNorm: normalise in fp32, cast to fp16, then multiply by the gain).
 // `feat` (token loop only, M = 1): the same row is also stored as row state[1]-1 of the per-token feature buffer —
 // the hidden state seed_x.py:143 collects for every generated token that was fed back.
 // ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void llm_rmsnorm_kernel(const half_t* __restrict__ x, long ldx,
-                                                          const half_t* __restrict__ gamma, half_t* __restrict__ y,
-                                                          long ldy, half_t* __restrict__ feat,
-                                                          const int* __restrict__ state, int H, int max_out,
-                                                          float eps) {
+// `fr` = the feature row this block also writes (null: none)
+__device__ __forceinline__ void llm_rmsnorm_row(const half_t* __restrict__ xr, const half_t* __restrict__ gamma,
+                                                half_t* __restrict__ yr, half_t* __restrict__ fr, int H, float eps) {
     __shared__ float part[4];
-    const int m = blockIdx.x, tid = threadIdx.x;
-    const half_t* xr = x + (long)m * ldx;
+    const int tid = threadIdx.x;
     float ss = 0.f;
     for (int k = tid * 8; k < H; k += 2048) {
         const h8 v = *reinterpret_cast<const h8*>(xr + k);
@@ -273,20 +289,46 @@ __global__ __launch_bounds__(256) void llm_rmsnorm_kernel(const half_t* __restri
     if ((tid & 63) == 0) part[tid >> 6] = ss;
     __syncthreads();
     const float r = __builtin_amdgcn_rsqf((part[0] + part[1] + part[2] + part[3]) / (float)H + eps);
-    half_t* fr = nullptr;
-    if (feat) {
-        const int row = state[1] - 1 + m;
-        if (row >= 0 && row < max_out && !state[2]) fr = feat + (long)row * H;
-    }
     for (int k = tid * 8; k < H; k += 2048) {
         const h8 v = *reinterpret_cast<const h8*>(xr + k);
         const h8 g = *reinterpret_cast<const h8*>(gamma + k);
         h8 o;
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] = (half_t)((float)g[e] * (float)(half_t)((float)v[e] * r));
-        *reinterpret_cast<h8*>(y + (long)m * ldy + k) = o;
+        *reinterpret_cast<h8*>(yr + k) = o;
         if (fr) *reinterpret_cast<h8*>(fr + k) = o;
     }
+}
+
+__global__ __launch_bounds__(256) void llm_rmsnorm_kernel(const half_t* __restrict__ x, long ldx,
+                                                          const half_t* __restrict__ gamma, half_t* __restrict__ y,
+                                                          long ldy, half_t* __restrict__ feat,
+                                                          const int* __restrict__ state, int H, int max_out,
+                                                          float eps) {
+    const int m = blockIdx.x;
+    half_t* fr = nullptr;
+    if (feat) {
+        const int row = state[1] - 1 + m;
+        if (row >= 0 && row < max_out && !state[2]) fr = feat + (long)row * H;
+    }
+    llm_rmsnorm_row(x + (long)m * ldx, gamma, y + (long)m * ldy, fr, H, eps);
+}
+
+// Batched decode: row s belongs to slot s; its tap goes to row state[s][1]-1 of feat[s] ([S][max_out][H]).
+__global__ __launch_bounds__(256) void llm_rmsnorm_slots_kernel(const half_t* __restrict__ x, long ldx,
+                                                                const half_t* __restrict__ gamma,
+                                                                half_t* __restrict__ y, long ldy,
+                                                                half_t* __restrict__ feat,
+                                                                const int* __restrict__ state, int H, int max_out,
+                                                                float eps) {
+    const int s = blockIdx.x;
+    const int* st = state + 8 * s;
+    half_t* fr = nullptr;
+    if (feat) {
+        const int row = st[1] - 1;
+        if (row >= 0 && row < max_out && !st[2]) fr = feat + ((long)s * max_out + row) * H;
+    }
+    llm_rmsnorm_row(x + (long)s * ldx, gamma, y + (long)s * ldy, fr, H, eps);
 }
 
 // h[0,:] = embed_tokens[state[3]]
@@ -297,6 +339,16 @@ __global__ __launch_bounds__(256) void llm_embed_kernel(const half_t* __restrict
     if (k < H) *reinterpret_cast<h8*>(out + k) = *reinterpret_cast<const h8*>(table + (long)tok * H + k);
 }
 
+// Batched decode: h[s,:] = embed_tokens[state[s][3]]
+__global__ __launch_bounds__(256) void llm_embed_slots_kernel(const half_t* __restrict__ table,
+                                                              const int* __restrict__ state, half_t* __restrict__ out,
+                                                              long ldo, int H, int vocab) {
+    const int s = blockIdx.y;
+    const int tok = min(max(state[8 * s + 3], 0), vocab - 1);
+    const int k = (blockIdx.x * 256 + threadIdx.x) * 8;
+    if (k < H) *reinterpret_cast<h8*>(out + (long)s * ldo + k) = *reinterpret_cast<const h8*>(table + (long)tok * H + k);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Greedy choice with the reference's AutoImageTokenGenerationProcessor folded in (generation.py:19-30):
 //   chain = [<img>, <img_00000> .. <img_{n-1}>, </img>];  previous token in chain[:-1] -> the next chain id wins
@@ -304,10 +356,9 @@ __global__ __launch_bounds__(256) void llm_embed_kernel(const half_t* __restrict
 // argmax ties go to the lowest id (torch.argmax).  Then: append the id, make it the current token, advance the cache
 // length by `adv` rows, and raise `finished` on EOS (state[5]) or when state[4] ids are out.  One block.
 // ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void llm_select_kernel(const half_t* __restrict__ logits, int V,
-                                                          const int* __restrict__ chain, int n_chain, int out_cap,
-                                                          int adv, int* __restrict__ state,
-                                                          int* __restrict__ out_ids) {
+__device__ __forceinline__ void llm_select_body(const half_t* __restrict__ logits, int V,
+                                                const int* __restrict__ chain, int n_chain, int out_cap, int adv,
+                                                int* __restrict__ state, int* __restrict__ out_ids) {
     __shared__ float bv[16];
     __shared__ int bi[16];
     __shared__ int forced, lo, hi;
@@ -367,6 +418,23 @@ __global__ __launch_bounds__(1024) void llm_select_kernel(const half_t* __restri
         state[0] += adv;
         if (next == eos || n_out + 1 >= max_new) state[2] = 1;
     }
+}
+
+__global__ __launch_bounds__(1024) void llm_select_kernel(const half_t* __restrict__ logits, int V,
+                                                          const int* __restrict__ chain, int n_chain, int out_cap,
+                                                          int adv, int* __restrict__ state,
+                                                          int* __restrict__ out_ids) {
+    llm_select_body(logits, V, chain, n_chain, out_cap, adv, state, out_ids);
+}
+
+// Batched decode: one block per slot over logits[s] (row stride ldl), with the slot's own state row (its eos and
+// max_new live there) and its own out_ids[s] ([S][out_cap]).
+__global__ __launch_bounds__(1024) void llm_select_slots_kernel(const half_t* __restrict__ logits, long ldl, int V,
+                                                                const int* __restrict__ chain, int n_chain,
+                                                                int out_cap, int adv, int* __restrict__ state,
+                                                                int* __restrict__ out_ids) {
+    const int s = blockIdx.x;
+    llm_select_body(logits + (long)s * ldl, V, chain, n_chain, out_cap, adv, state + 8 * s, out_ids + (long)s * out_cap);
 }
 
 // act[m][n] = silu(gu[m][n]) * gu[m][I+n]  (prompt pass: the gate|up projection comes out of the MFMA GEMM as [M,2I])
@@ -609,6 +677,147 @@ __global__ __launch_bounds__(256) void llm_gemv_pipe_kernel(LlmGemvParams p) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Batched decode (up to 16 sequences per weight pass): y[M <= 16, N] = x'[M, K] w[N, K]^T on the matrix pipe, same
+// prologues / epilogues and fp16 rounding points as the kernels above.  At 16 rows the fdot2 form needs 64 fdot2 and
+// 256 B of x per 16-byte weight load and lane, which a CU cannot feed at the HBM rate; one v_mfma_f32_16x16x32_f16 does
+// the 16 rows x 16 columns x 32 k of a 1 KB weight fragment.
+//   A operand = x, padded to 16 rows with zeros: lane l holds x[l & 15][k + 8 (l >> 4) .. + 8]
+//   B operand = 16 weight rows:                  lane l holds w[n0 + (l & 15)][k + 8 (l >> 4) .. + 8]
+//   C:                                           lane l holds y[4 (l >> 4) + reg][n0 + (l & 15)]
+// Weights go HBM -> VGPR in that layout with 16-byte loads, no LDS.  A block owns one 16-column tile at a time; its
+// four wavefronts split K in interleaved blocks of 32 U halves (U MFMA steps), so a wavefront consumes U / 2 whole
+// 128-byte lines of each of its 16 weight rows per iteration and has U KB of weights in flight: the loads of the next
+// k-block (or of the next tile's first one) are issued before the MFMAs of the current one.  The four partial tiles
+// are added in wavefront order 0..3 through LDS (no atomics), by the thread that then writes the element.
+// x: read from L2 in the fragment layout, prefetched with the weights (16 x 13824 x 2 B does not fit LDS).  Staging x
+// in LDS by K chunks pays only when a staged chunk serves several column tiles; the o / down projections have 320
+// tiles for 256 CUs, so a block has one tile and a staged chunk would move the same bytes from L2 as the fragments do,
+// plus an LDS round trip and two barriers per chunk.  Only the RMSNorm gain [K] is kept in LDS (read per k-step).
+// A row's result depends on that row of x alone: rows >= M are zero fragments, the k order is fixed by (K, lane), the
+// row scale is computed by a fixed wavefront, and an MFMA output row takes nothing from other A rows.
+// ---------------------------------------------------------------------------------------------------------------
+template <int SWIGLU>
+__global__ __launch_bounds__(256) void llm_gemm16_kernel(LlmGemvParams p) {
+    constexpr int U = SWIGLU ? 4 : 8;   // MFMA steps (= 16-byte weight loads per lane and matrix) per iteration
+    constexpr int KB = 32 * U;          // halves of K per wavefront iteration
+    constexpr int NACC = SWIGLU ? 2 : 1;
+    extern __shared__ char smem_raw[];
+    float* red = reinterpret_cast<float*>(smem_raw);                   // [2 tiles in flight][NACC][4 wavefronts][256]
+    float* rs = red + 2 * NACC * 4 * 256;                              // [16] row scales
+    half_t* gl = reinterpret_cast<half_t*>(rs + 16);                   // [K] RMSNorm gain (with p.gain)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c = lane & 15, g = lane >> 4;
+    const int K = p.K, N = p.N, M = p.M;
+    const int NT = (N + 15) / 16, NIT = (K + 4 * KB - 1) / (4 * KB);
+    const h8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+    h8 wa[U], ua[U], wb[U], ub[U], xa[U], xb[U];
+    auto issue_w = [&](int tile, int it, h8(&wv)[U], h8(&uv)[U]) {
+        const long col = min(tile * 16 + c, N - 1);   // ragged last tile: re-read the last row, never stored
+        const half_t* wg = p.w + col * K;
+        const half_t* wu = p.w + (col + N) * K;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int k = min((it * 4 + wave) * KB + 32 * u + 8 * g, K - 8);   // ragged K: clamped, x is zero there
+            wv[u] = *reinterpret_cast<const h8*>(wg + k);
+            if (SWIGLU) uv[u] = *reinterpret_cast<const h8*>(wu + k);
+        }
+    };
+    const half_t* xr = p.x + (long)min(c, M - 1) * p.ldx;
+    auto issue_x = [&](int it, h8(&xv)[U]) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int k = (it * 4 + wave) * KB + 32 * u + 8 * g;
+            const h8 v = *reinterpret_cast<const h8*>(xr + min(k, K - 8));
+            xv[u] = (c < M && k < K) ? v : zero;
+        }
+    };
+    int tile = blockIdx.x;
+    if (tile < NT) issue_w(tile, 0, wa, ua);
+    // ---- row scales (wavefront w: rows 4w .. 4w+3) and the gain vector
+    if (p.rms) {
+#pragma unroll
+        for (int mm = 0; mm < 4; ++mm) {
+            const int m = wave * 4 + mm;
+            float ss = 0.f;
+            if (m < M) {
+                const half_t* row = p.x + (long)m * p.ldx;
+                for (int k = lane * 8; k < K; k += 512) {
+                    const h8 v = *reinterpret_cast<const h8*>(row + k);
+                    ss = dot8(v, v, ss);
+                }
+            }
+            ss = wave_sum(ss);
+            if (lane == 0) rs[m] = m < M ? __builtin_amdgcn_rsqf(ss / (float)K + p.eps) : 1.0f;
+        }
+        if (p.gain)
+            for (int k = tid * 8; k < K; k += 2048) *reinterpret_cast<h8*>(gl + k) = *reinterpret_cast<const h8*>(p.gain + k);
+    } else if (tid < 16) {
+        rs[tid] = 1.0f;
+    }
+    __syncthreads();
+    const bool gain = p.rms && p.gain;
+    const float ra = rs[c];
+    if (tile < NT) issue_x(0, xa);
+    int par = 0;
+    while (tile < NT) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acu = {0.f, 0.f, 0.f, 0.f};
+        for (int it = 0; it < NIT; ++it) {
+            const bool last = it + 1 == NIT;
+            const int ntile = last ? tile + (int)gridDim.x : tile, nit = last ? 0 : it + 1;
+            if (ntile < NT) {
+                issue_x(nit, xb);
+                issue_w(ntile, nit, wb, ub);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                h8 a = xa[u];
+                if (gain) {   // the fragment becomes the RMSNorm OUTPUT at the reference's roundings (zero stays zero)
+                    const int k = min((it * 4 + wave) * KB + 32 * u + 8 * g, K - 8);
+                    a = rms_gain8(a, *reinterpret_cast<const h8*>(gl + k), ra);
+                }
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, wa[u], acc, 0, 0, 0);
+                if (SWIGLU) acu = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, ua[u], acu, 0, 0, 0);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                wa[u] = wb[u];
+                xa[u] = xb[u];
+                if (SWIGLU) ua[u] = ub[u];
+            }
+        }
+        // ---- split-K reduction in wavefront order, then the epilogue: thread (wave = reg, lane) owns one element
+        float* rp = red + par * NACC * 1024;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            rp[wave * 256 + q * 64 + lane] = acc[q];
+            if (SWIGLU) rp[1024 + wave * 256 + q * 64 + lane] = acu[q];
+        }
+        __syncthreads();   // one barrier per tile: the next tile writes the other half of `red`
+        {
+            const int m = 4 * g + wave, n = tile * 16 + c;
+            float a = ((rp[tid] + rp[256 + tid]) + rp[512 + tid]) + rp[768 + tid];
+            const float rr = gain ? 1.0f : rs[m];   // with a gain the scale is already inside x'
+            a *= rr;
+            if (m < M && n < N) {
+                float o;
+                if (SWIGLU) {  // fp16 roundings of the reference: act_fn(gate_proj(x)) * up_proj(x)
+                    float b = ((rp[1024 + tid] + rp[1280 + tid]) + rp[1536 + tid]) + rp[1792 + tid];
+                    b *= rr;
+                    const float gt = (float)(half_t)a, up = (float)(half_t)b;
+                    o = (float)(half_t)ds_silu(gt) * up;
+                } else {
+                    o = (float)(half_t)a;
+                    if (p.residual) o += (float)p.residual[(long)m * p.ldr + n];
+                }
+                p.y[(long)m * p.ldy + n] = (half_t)o;
+            }
+        }
+        par ^= 1;
+        tile += gridDim.x;
+    }
+}
+
 static thread_local int g_llm_gemv_variant = 0;  // 0 auto (pipelined), 1 one-column-per-wavefront kernel, 2 un-pipelined streaming kernel
 
 template <int MC, int SWIGLU>
@@ -657,6 +866,27 @@ int launch_gemv(const LlmGemvParams& p, hipStream_t stream) {
     return 0;
 }
 
+constexpr int GEMM16_BLOCKS_PER_CU = 3;
+
+int launch_gemm16(const LlmGemvParams& p, hipStream_t stream) {
+    static int cus = 0;
+    if (!cus) {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        DS_HIP(hipGetDevice(&dev));
+        DS_HIP(hipGetDeviceProperties(&prop, dev));
+        cus = prop.multiProcessorCount;
+    }
+    const size_t lds = (size_t)(2 * (p.swiglu ? 2 : 1) * 4 * 256 + 16) * sizeof(float) + (p.rms && p.gain ? (size_t)p.K * 2 : 0);
+    // the resident set, as launch_gemv_stream sizes it: GEMM16_BLOCKS_PER_CU blocks of 4 wavefronts by registers
+    const int per_cu = (int)min((size_t)GEMM16_BLOCKS_PER_CU, (size_t)(160 * 1024) / (lds + 512));
+    const int blocks = min((p.N + 15) / 16, cus * max(per_cu, 1));
+    if (p.swiglu) hipLaunchKernelGGL(llm_gemm16_kernel<1>, dim3(blocks), dim3(256), lds, stream, p);
+    else hipLaunchKernelGGL(llm_gemm16_kernel<0>, dim3(blocks), dim3(256), lds, stream, p);
+    DS_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace
 
 void ds_llm_gemv_set_variant(int v) { g_llm_gemv_variant = v; }
@@ -669,7 +899,17 @@ int ds_launch_llm_gemv(const LlmGemvParams& p, hipStream_t stream) {
     return p.swiglu ? launch_gemv<1>(p, stream) : launch_gemv<0>(p, stream);
 }
 
-int ds_launch_llm_attn(const LlmAttnParams& p, hipStream_t stream) {
+int ds_launch_llm_gemm16(const LlmGemvParams& p, hipStream_t stream) {
+    DS_REQUIRE(p.M > 0 && p.M <= 16 && p.N > 0 && p.K >= 8 && p.K % 8 == 0, "llm_gemm16: bad shape M=%d (1..16) N=%d K=%d",
+               p.M, p.N, p.K);
+    DS_REQUIRE(p.ldx % 8 == 0 && p.ldx >= p.K, "llm_gemm16: ldx %ld must be a multiple of 8 and >= K", p.ldx);
+    DS_REQUIRE(p.x && p.w && p.y, "llm_gemm16: null operand");
+    DS_REQUIRE(!(p.swiglu && p.residual), "llm_gemm16: the SwiGLU epilogue takes no residual");
+    DS_REQUIRE(!(p.rms && p.gain) || p.K <= 20480, "llm_gemm16: K %d too long for the gain vector in LDS (20480)", p.K);
+    return launch_gemm16(p, stream);
+}
+
+static int check_llm_attn(const LlmAttnParams& p) {
     DS_REQUIRE(p.D == 64 || p.D == 128, "llm_attn: head_dim %d unsupported (64 or 128)", p.D);
     DS_REQUIRE(p.M > 0 && p.M <= 16, "llm_attn: %d rows per pass (1..16)", p.M);
     DS_REQUIRE(p.heads > 0 && p.kv_heads > 0 && p.heads % p.kv_heads == 0, "llm_attn: heads %d / kv_heads %d", p.heads,
@@ -677,10 +917,61 @@ int ds_launch_llm_attn(const LlmAttnParams& p, hipStream_t stream) {
     DS_REQUIRE(p.T_max > 0 && p.T_max <= 8192, "llm_attn: cache length %d (max 8192)", p.T_max);
     DS_REQUIRE(p.ldqkv % 8 == 0 && p.ldc % 8 == 0, "llm_attn: row strides must be multiples of 8");
     DS_REQUIRE(p.qkv && p.kc && p.vc && p.rope_cos && p.rope_sin && p.out && p.state, "llm_attn: null operand");
+    return 0;
+}
+
+int ds_launch_llm_attn(const LlmAttnParams& p, hipStream_t stream) {
+    if (const int rc = check_llm_attn(p)) return rc;
     const size_t lds = (size_t)(p.T_max + ATT_WAVES * p.D + 2 * ATT_WAVES) * sizeof(float);
     const dim3 grid(p.heads, p.M);
     if (p.D == 128) hipLaunchKernelGGL(llm_attn_kernel<128>, grid, dim3(64 * ATT_WAVES), lds, stream, p);
     else hipLaunchKernelGGL(llm_attn_kernel<64>, grid, dim3(64 * ATT_WAVES), lds, stream, p);
+    DS_LAUNCH_CHECK();
+    return 0;
+}
+
+// p.M = number of slots (one row each); slot s: caches at kc / vc + s * slot_stride, state row state + 8 s
+int ds_launch_llm_attn_slots(const LlmAttnParams& p, long slot_stride, hipStream_t stream) {
+    if (const int rc = check_llm_attn(p)) return rc;
+    DS_REQUIRE(slot_stride % 8 == 0 && slot_stride >= (long)p.T_max * p.ldc, "llm_attn_slots: slot stride %ld < T_max * ldc",
+               slot_stride);
+    const size_t lds = (size_t)(p.T_max + ATT_WAVES * p.D + 2 * ATT_WAVES) * sizeof(float);
+    const dim3 grid(p.heads, p.M);
+    if (p.D == 128) hipLaunchKernelGGL(llm_attn_slots_kernel<128>, grid, dim3(64 * ATT_WAVES), lds, stream, p, slot_stride);
+    else hipLaunchKernelGGL(llm_attn_slots_kernel<64>, grid, dim3(64 * ATT_WAVES), lds, stream, p, slot_stride);
+    DS_LAUNCH_CHECK();
+    return 0;
+}
+
+int ds_launch_llm_rmsnorm_slots(const half_t* x, long ldx, const half_t* gamma, half_t* y, long ldy, half_t* feat,
+                                const int* state, int S, int H, int max_out, float eps, hipStream_t stream) {
+    DS_REQUIRE(S > 0 && H >= 8 && H % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0, "llm_rmsnorm_slots: bad shape S=%d H=%d", S, H);
+    DS_REQUIRE(x && gamma && y && (!feat || state), "llm_rmsnorm_slots: null operand");
+    hipLaunchKernelGGL(llm_rmsnorm_slots_kernel, dim3(S), dim3(256), 0, stream, x, ldx, gamma, y, ldy, feat, state, H,
+                       max_out, eps);
+    DS_LAUNCH_CHECK();
+    return 0;
+}
+
+int ds_launch_llm_embed_slots(const half_t* table, const int* state, half_t* out, long ldo, int S, int H, int vocab,
+                              hipStream_t stream) {
+    DS_REQUIRE(S > 0 && H % 8 == 0 && vocab > 0 && ldo % 8 == 0 && ldo >= H, "llm_embed_slots: bad shape S=%d H=%d vocab=%d", S,
+               H, vocab);
+    DS_REQUIRE(table && state && out, "llm_embed_slots: null operand");
+    hipLaunchKernelGGL(llm_embed_slots_kernel, dim3((H / 8 + 255) / 256, S), dim3(256), 0, stream, table, state, out, ldo,
+                       H, vocab);
+    DS_LAUNCH_CHECK();
+    return 0;
+}
+
+int ds_launch_llm_select_slots(const half_t* logits, long ldl, int V, const int* chain, int n_chain, int out_cap, int adv,
+                               int* state, int* out_ids, int S, hipStream_t stream) {
+    DS_REQUIRE(S > 0 && V > 0 && ldl >= V && n_chain >= 0 && n_chain <= 1024 && out_cap > 0 && adv >= 0,
+               "llm_select_slots: bad arguments");
+    DS_REQUIRE(n_chain == 0 || chain, "llm_select_slots: chain ids missing");
+    DS_REQUIRE(logits && state && out_ids, "llm_select_slots: null operand");
+    hipLaunchKernelGGL(llm_select_slots_kernel, dim3(S), dim3(1024), 0, stream, logits, ldl, V, chain, n_chain, out_cap,
+                       adv, state, out_ids);
     DS_LAUNCH_CHECK();
     return 0;
 }

@@ -19,6 +19,15 @@ applied in the GEMV prologue at the reference's rounding points (normalise in fp
 folding them into the fp16 weights would round once instead of twice and can flip greedy near-ties); QwenResampler: the constant query projection and the position-embedding contribution to the keys are
 precomputed (they depend on weights only).  There is no CPU/PyTorch execution path: without the HIP library every call
 raises.
+
+Batched decode (`LlamaDecodeEngine(max_sequences=S)`, `generate_batch`, `ContinuousLVLM.generate_batch`,
+`mllm_prepass_batch`): the token loop is HBM-bound on the weights, and a step for up to 16 sequences reads the same
+weights as a step for one.  The engine then owns S cache slots, an int32 [S][8] state block, and per-slot id and feature
+buffers; one token step is one static launch list over all S rows (`llm_gemm16_kernel` for every projection, the
+per-slot attention / norm / pick kernels), whatever number of slots is in use, so a sequence's ids and hidden states do
+not depend on what the other slots hold or on the slot it sits in.  A finished or unused slot is skipped by every
+kernel that writes per-slot state.  KV memory: a slot is 2 x layers x T_max x kv_heads x head_dim fp16 = 0.84 GB at
+13B dimensions and T_max 1024 (13.4 GB for 16 slots, next to 26 GB of weights).
 """
 from __future__ import annotations
 
@@ -98,8 +107,15 @@ class LlamaDecodeEngine:
     """Device-resident LLaMA decoder + KV cache + the captured one-token launch plan."""
 
     def __init__(self, cfg: LlamaConfig, sd: Dict[str, Tensor], device, max_positions: int = 1024,
-                 max_new_tokens: int = 512, use_graph: bool = True, poll_every: int = 8, prompt_path: str = "mfma"):
+                 max_new_tokens: int = 512, use_graph: bool = True, poll_every: int = 8, prompt_path: str = "mfma",
+                 max_sequences: int = 1):
+        """max_sequences S > 1: `generate_batch` decodes up to S sequences per weight pass; the engine then holds S KV-cache
+        slots (each 2 x layers x max_positions x kv_heads x head_dim fp16: 0.84 GB at 13B dimensions and 1024 positions)
+        and [S] id / feature / logits buffers.  With 1 nothing extra is allocated."""
         _lib.load()
+        if not 1 <= int(max_sequences) <= CHUNK:
+            raise ValueError(f"max_sequences {max_sequences} outside [1, {CHUNK}] (rows of one weight pass)")
+        self.max_sequences = S = int(max_sequences)
         if prompt_path not in ("mfma", "chunks"):
             raise ValueError("prompt_path: 'mfma' (GEMM projections) or 'chunks' (16-row passes of the token kernels)")
         self.cfg, self.dev = cfg, torch.device(device)
@@ -134,8 +150,10 @@ class LlamaDecodeEngine:
         self.qkv_dim = (Hq + 2 * Hkv) * D
         self.h, self.qkv, self.att = E(CHUNK, H), E(CHUNK, self.qkv_dim), E(CHUNK, Hq * D)
         self.act, self.hn, self.logits = E(CHUNK, I), E(1, H), E(V)
-        self.kc = [E(self.T_max, Hkv * D) for _ in range(L)]
-        self.vc = [E(self.T_max, Hkv * D) for _ in range(L)]
+        # [S, T_max, kv_heads*D] per layer; `generate` uses slot 0
+        self.kcs = [E(S, self.T_max, Hkv * D) for _ in range(L)]
+        self.vcs = [E(S, self.T_max, Hkv * D) for _ in range(L)]
+        self.kc, self.vc = [t[0] for t in self.kcs], [t[0] for t in self.vcs]
         inv_freq = 1.0 / (cfg.rope_theta ** (torch.arange(0, D, 2, dtype=torch.float32) / D))
         fr = torch.outer(torch.arange(self.T_max, dtype=torch.float32), inv_freq)      # rotary table (weights-like)
         self.rope_cos, self.rope_sin = fr.cos().to(dev).contiguous(), fr.sin().to(dev).contiguous()
@@ -144,6 +162,11 @@ class LlamaDecodeEngine:
         self.prompt_path = prompt_path
         self.out_ids = E(self.cap, dtype=torch.int32)
         self.feat = E(self.cap, H)
+        if S > 1:
+            self.state_b = E(S, 8, dtype=torch.int32)
+            self.state_b[:, 2] = 1                          # no slot started: every per-slot kernel skips it
+            self.out_ids_b, self.feat_b = E(S, self.cap, dtype=torch.int32), E(S, self.cap, H)
+            self.hn_b, self.logits_b = E(S, H), E(S, V)
         self.chain = E(1, dtype=torch.int32)
         self.n_chain = 0
         self._plans: Dict[tuple, Plan] = {}
@@ -198,14 +221,46 @@ class LlamaDecodeEngine:
                             p=(self.logits, self.chain if self.n_chain else None, self.state, self.out_ids)))
         return ops_
 
+    def _ops_batch(self) -> list:
+        """One token step for all S slots: the `token` list of `_ops` with every projection on `llm_gemm16_kernel` (M = S
+        whatever number of slots is in use) and the per-slot embed / attention / final norm / pick kernels."""
+        c, S = self.cfg, self.max_sequences
+        H, I, V = c.hidden_size, c.intermediate_size, c.vocab_size
+        D, Hq, Hkv = c.head_dim, c.num_attention_heads, c.kv_heads
+        eps, scale = c.rms_norm_eps, 1.0 / math.sqrt(D)
+        ops_ = [make_op("LLM_EMBED_SLOTS", i=(S, H, V), l=(H,), p=(self.embed, self.state_b, self.h))]
+        for l in range(c.num_hidden_layers):
+            ops_.append(make_op("LLM_GEMM16", i=(S, self.qkv_dim, H, 1, 0), f=(eps,), l=(H, self.qkv_dim, 0),
+                                p=(self.h, self.wqkv[l], self.qkv, None, self.g_in[l])))
+            ops_.append(make_op("LLM_ATTN_SLOTS", i=(S, Hq, Hkv, D, self.T_max), f=(scale,),
+                                l=(self.qkv_dim, Hkv * D, Hq * D, self.kcs[l].stride(0)),
+                                p=(self.qkv, self.kcs[l], self.vcs[l], self.rope_cos, self.rope_sin, self.att,
+                                   self.state_b)))
+            ops_.append(make_op("LLM_GEMM16", i=(S, H, Hq * D, 0, 0), f=(eps,), l=(Hq * D, H, H),
+                                p=(self.att, self.wo[l], self.h, self.h)))
+            ops_.append(make_op("LLM_GEMM16", i=(S, I, H, 1, 1), f=(eps,), l=(H, I, 0),
+                                p=(self.h, self.wgu[l], self.act, None, self.g_post[l])))
+            ops_.append(make_op("LLM_GEMM16", i=(S, H, I, 0, 0), f=(eps,), l=(I, H, H),
+                                p=(self.act, self.wdown[l], self.h, self.h)))
+        ops_.append(make_op("LLM_RMSNORM_SLOTS", i=(S, H, self.cap), f=(eps,), l=(H, H),
+                            p=(self.h, self.norm_g, self.hn_b, self.feat_b, self.state_b)))
+        ops_.append(make_op("LLM_GEMM16", i=(S, V, H, 0, 0), f=(eps,), l=(H, V, 0),
+                            p=(self.hn_b, self.lm_head, self.logits_b, None)))
+        ops_.append(make_op("LLM_SELECT_SLOTS", i=(V, self.n_chain, self.cap, 1, S), l=(V,),
+                            p=(self.logits_b, self.chain if self.n_chain else None, self.state_b, self.out_ids_b)))
+        return ops_
+
     def weights_changed(self) -> None:
-        """The weight tensors moved or changed (multi-GPU broadcast into the weight arena): cached launch plans hold raw
-        pointers and are rebuilt on next use."""
+        """The weight tensors moved or changed (multi-GPU broadcast into the weight arena): cached launch plans - the
+        one-sequence ones and the batched token step - hold raw pointers and are rebuilt on next use."""
         self._plans.clear()
 
     def _plan(self, M: int, kind: str) -> Plan:
         key = (M, kind, self.n_chain, self.chain.data_ptr())
         pl = self._plans.get(key)
+        if pl is None and kind == "token_batch":
+            pl = Plan(self._ops_batch(), keep=[self])
+            self._plans[key] = pl
         if pl is None:
             pl = Plan(self._ops(M, kind), keep=[self])
             self._plans[key] = pl
@@ -302,6 +357,110 @@ class LlamaDecodeEngine:
         ops.llm_rmsnorm(h[T0 - 1:T0], self.norm_g, eps, out=self.hn)
         ops.llm_gemv(self.hn, self.lm_head, out=self.logits.view(1, -1))
         ops.llm_select(self.logits, self.chain if self.n_chain else None, T0, self.state, self.out_ids)
+
+    # ---- batched generation -----------------------------------------------------------------------------
+    @torch.no_grad()
+    def generate_batch(self, inputs_embeds: Sequence[Tensor], last_prompt_ids: Sequence[int], eos_token_ids,
+                       max_new_tokens, slots: Optional[Sequence[int]] = None) -> List[dict]:
+        """`generate` for 1 <= n <= max_sequences sequences of different prompt lengths in one decode loop.
+        `eos_token_ids` / `max_new_tokens`: one value for all, or one per sequence.  `slots`: the cache slot of each
+        sequence (default 0..n-1); results do not depend on it.  Returns one {"ids", "hidden"} per sequence."""
+        S, H = self.max_sequences, self.cfg.hidden_size
+        embs = list(inputs_embeds)
+        n = len(embs)
+        if S < 2:
+            raise ValueError("generate_batch needs an engine built with max_sequences > 1")
+        if not 1 <= n <= S:
+            raise ValueError(f"{n} sequences: the engine has {S} slots")
+        per = lambda v, what: [int(x) for x in v] if isinstance(v, (list, tuple)) else [int(v)] * n
+        last, eos, max_new = per(list(last_prompt_ids), "last"), per(eos_token_ids, "eos"), per(max_new_tokens, "max_new")
+        slots = list(range(n)) if slots is None else [int(x) for x in slots]
+        if not len(last) == len(eos) == len(max_new) == len(slots) == n:
+            raise ValueError("one last_prompt_id / eos / max_new_tokens / slot per sequence is needed")
+        if len(set(slots)) != n or min(slots) < 0 or max(slots) >= S:
+            raise ValueError(f"slots {slots}: {n} different values in [0, {S}) are needed")
+        T0s = []
+        for e, mn in zip(embs, max_new):
+            if e.dim() != 2 or e.shape[1] != H or e.dtype != torch.float16 or not e.is_cuda:
+                raise ValueError("inputs_embeds must be fp16 device tensors [T, hidden]")
+            if not 0 < mn <= self.cap:
+                raise ValueError(f"max_new_tokens {mn} outside (0, {self.cap}] (engine capacity)")
+            T0 = int(e.shape[0])
+            if T0 < 1 or T0 + mn > self.T_max:
+                raise ValueError(f"prompt {T0} + max_new_tokens {mn} exceeds the KV cache ({self.T_max} positions)")
+            T0s.append(T0)
+        dev = self.dev
+        if self._stream is None:
+            self._stream = torch.cuda.Stream(device=dev)
+        st = self._stream
+        st.wait_stream(torch.cuda.current_stream(dev))
+        graph, steps = False, 0
+        rows = [[0, 0, 1, 0, 0, 0, 0, 0] for _ in range(S)]      # unused slots: finished
+        for i, s in enumerate(slots):                            # the cache length starts at the prompt length (the pick adds 0)
+            rows[s] = [T0s[i], 0, 0, last[i], max_new[i], eos[i], 0, 0]
+        with torch.cuda.stream(st):
+            self.state_b.copy_(torch.tensor(rows, dtype=torch.int32), non_blocking=False)
+            self._prompt_batch(embs, slots)
+            tok = self._plan(S, "token_batch")
+            done, most = False, max(max_new) - 1
+            while not done and steps < most:
+                burst = min(self.poll_every, most - steps)
+                for _ in range(burst):
+                    if self.use_graph and not tok.captured:
+                        tok.run(st.cuda_stream)       # first step eager, then capture the launch list once
+                        tok.capture(st.cuda_stream)
+                    elif self.use_graph:
+                        tok.replay(st.cuda_stream)
+                        graph = True
+                    else:
+                        tok.run(st.cuda_stream)
+                steps += burst
+                done = bool(self.state_b.cpu()[:, 2].all())     # every slot's flag in one copy (every `poll_every` steps)
+            state = self.state_b.cpu()
+            out = []
+            for s in slots:
+                k = int(state[s, 1])
+                out.append({"ids": self.out_ids_b[s, :k].to(torch.int64), "hidden": self.feat_b[s, :max(k - 1, 0)].clone()})
+        torch.cuda.current_stream(dev).wait_stream(st)
+        self.last_run_info = {"graph": graph, "sequences": n, "prompt_tokens": T0s, "new_tokens": [len(o["ids"]) for o in out],
+                              "token_steps_launched": steps, "ops_per_token": tok.n}
+        return out
+
+    def _prompt_batch(self, embs: List[Tensor], slots: List[int]) -> None:
+        """`_prompt_mfma` over the concatenated rows of all prompts: one pass per layer, so the weights are read once per
+        layer for the whole batch; only the attention walks each sequence's rows in chunks of 16 into that sequence's
+        slot.  Ends with the final norm of each sequence's last row, lm_head through `llm_gemm16_kernel` over all S rows
+        and the first pick per slot."""
+        c = self.cfg
+        Hq, Hkv, eps = c.num_attention_heads, c.kv_heads, c.rms_norm_eps
+        scale = 1.0 / math.sqrt(c.head_dim)
+        pf = self.state_pf
+        h = torch.cat([e.contiguous() for e in embs], 0)
+        starts = [0]
+        for e in embs:
+            starts.append(starts[-1] + int(e.shape[0]))
+        att = torch.empty((starts[-1], Hq * c.head_dim), dtype=torch.float16, device=self.dev)
+        for l in range(c.num_hidden_layers):
+            xn = ops.llm_rmsnorm(h, self.g_in[l], eps)
+            qkv = ops.gemm(xn, self.wqkv[l])
+            for i, s in enumerate(slots):
+                pf.zero_()                                                   # chunk cursor of this slot's cache
+                for r0 in range(starts[i], starts[i + 1], CHUNK):
+                    m = min(CHUNK, starts[i + 1] - r0)
+                    ops.llm_attention(qkv[r0:r0 + m], self.kcs[l][s], self.vcs[l][s], self.rope_cos, self.rope_sin, pf,
+                                      Hq, Hkv, scale, out=att[r0:r0 + m])
+                    ops.llm_advance(pf, m)
+            h = ops.gemm(att, self.wo[l], residual=h)
+            xn = ops.llm_rmsnorm(h, self.g_post[l], eps)
+            act = ops.llm_swiglu(ops.gemm(xn, self.wgu[l]))
+            h = ops.gemm(act, self.wdown[l], residual=h)
+        idx = torch.tensor([starts[i + 1] - 1 for i in range(len(embs))], dtype=torch.long, device=self.dev)
+        self.h.zero_()
+        self.h[torch.tensor(slots, dtype=torch.long, device=self.dev)] = h.index_select(0, idx)
+        S = self.max_sequences
+        ops.llm_rmsnorm_slots(self.h[:S], self.norm_g, eps, out=self.hn_b)
+        ops.llm_gemm16(self.hn_b, self.lm_head, out=self.logits_b)
+        ops.llm_select_slots(self.logits_b, self.chain if self.n_chain else None, 0, self.state_b, self.out_ids_b)
 
     def embed_tokens(self, input_ids: Tensor) -> Tensor:
         """Row gather from the embedding table (data movement only)."""
@@ -441,10 +600,10 @@ class ContinuousLVLM:
         self.input_resampler.weights_changed()
         self.output_resampler.weights_changed()
 
-    @torch.no_grad()
-    def generate(self, tokenizer=None, prompt=None, input_ids=None, image_embeds=None, ids_cmp_mask=None,
+    def _prepare(self, tokenizer=None, prompt=None, input_ids=None, image_embeds=None, ids_cmp_mask=None,
                  logits_processor=None, num_img_gen_tokens=64, temperature=0.7, num_beams=1, max_new_tokens=120,
                  top_p=0.5, img_ids_list: Optional[Sequence[int]] = None, eos_token_id: Optional[int] = None) -> dict:
+        """Argument handling of `generate` up to the token ids (no device work)."""
         if logits_processor is not None:
             raise NotImplementedError("the image-token processor is built into the pick kernel; custom processors "
                                       "have no device implementation")
@@ -459,32 +618,92 @@ class ContinuousLVLM:
             input_ids = tokenizer(prompt, return_tensors="pt").input_ids
         if isinstance(input_ids, list):
             input_ids = torch.tensor(input_ids)
-        ids = input_ids.view(-1)
-        llm = self.llm
-        emb = llm.embed_tokens(ids)
         if image_embeds is not None:
             assert ids_cmp_mask is not None
+        return {"tokenizer": tokenizer, "ids": input_ids.view(-1), "image_embeds": image_embeds, "ids_cmp_mask": ids_cmp_mask,
+                "chain": img_ids_list, "eoi": eoi_token_id, "gen_ids": image_gen_id_list, "eos": int(eos_token_id),
+                "max_new": int(max_new_tokens), "n_img": int(num_img_gen_tokens)}
+
+    @staticmethod
+    def _image_blocks(q: dict, g: dict):
+        """`generate`'s bookkeeping after decoding: ids with the image blocks rewritten, their mask, the hidden-state
+        block of every complete <img> .. </img> run (seed_x.py:139-160)."""
+        generate_ids, last_hidden_states = g["ids"].clone(), g["hidden"]
+        n_img = q["n_img"]
+        image_gen_ids = torch.tensor(q["gen_ids"], dtype=generate_ids.dtype, device=generate_ids.device)
+        eoi_indices = torch.where(generate_ids == q["eoi"])[0].tolist()
+        ids_gen_mask = torch.zeros_like(generate_ids, dtype=torch.bool)
+        feats = []
+        for e in eoi_indices:
+            if e >= n_img:
+                feats.append(last_hidden_states[e - n_img:e])
+                generate_ids[e - n_img:e] = image_gen_ids
+                ids_gen_mask[e - n_img:e] = True
+        return generate_ids, ids_gen_mask, len(eoi_indices), feats
+
+    @torch.no_grad()
+    def generate(self, tokenizer=None, prompt=None, input_ids=None, image_embeds=None, ids_cmp_mask=None,
+                 logits_processor=None, num_img_gen_tokens=64, temperature=0.7, num_beams=1, max_new_tokens=120,
+                 top_p=0.5, img_ids_list: Optional[Sequence[int]] = None, eos_token_id: Optional[int] = None) -> dict:
+        q = self._prepare(tokenizer, prompt, input_ids, image_embeds, ids_cmp_mask, logits_processor, num_img_gen_tokens,
+                          temperature, num_beams, max_new_tokens, top_p, img_ids_list, eos_token_id)
+        ids, llm = q["ids"], self.llm
+        emb = llm.embed_tokens(ids)
+        if image_embeds is not None:
             lm = self.input_resampler(image_embeds)
             emb[ids_cmp_mask.view(-1).to(emb.device)] = lm.reshape(-1, emb.shape[-1])
-        llm.set_image_token_chain(img_ids_list)
-        g = llm.generate(emb, int(ids[-1]), int(eos_token_id), int(max_new_tokens))
-        generate_ids, last_hidden_states = g["ids"].clone(), g["hidden"]
-        image_gen_ids = torch.tensor(image_gen_id_list, dtype=generate_ids.dtype, device=generate_ids.device)
-        eoi_indices = torch.where(generate_ids == eoi_token_id)[0].tolist()
-        num_gen_imgs = len(eoi_indices)
-        ids_gen_mask = torch.zeros_like(generate_ids, dtype=torch.bool)
+        llm.set_image_token_chain(q["chain"])
+        g = llm.generate(emb, int(ids[-1]), q["eos"], q["max_new"])
+        generate_ids, ids_gen_mask, num_gen_imgs, feats = self._image_blocks(q, g)
         img_gen_feat = None
         if num_gen_imgs > 0:
-            feats = []
-            for e in eoi_indices:
-                if e >= num_img_gen_tokens:
-                    feats.append(last_hidden_states[e - num_img_gen_tokens:e])
-                    generate_ids[e - num_img_gen_tokens:e] = image_gen_ids
-                    ids_gen_mask[e - num_img_gen_tokens:e] = True
             img_gen_feat = self.output_resampler(torch.stack(feats)).contiguous()
         text = tokenizer.decode(generate_ids, skip_special_tokens=True) if tokenizer is not None else None
         return {"text": text, "output_ids": generate_ids, "img_gen_feat": img_gen_feat, "num_gen_imgs": num_gen_imgs,
                 "ids_gen_mask": ids_gen_mask}
+
+    @torch.no_grad()
+    def generate_batch(self, requests: Sequence[dict]) -> List[dict]:
+        """`generate` for up to `llm.max_sequences` requests (each the keyword arguments of `generate`) in one decode
+        loop: the input resampler runs once over the stacked `image_embeds`, the decoder once over all sequences, the
+        output resampler once over all image blocks.  All requests must share `img_ids_list` (the processor chain is one
+        per launch plan) and `num_img_gen_tokens`."""
+        qs = [self._prepare(**r) for r in requests]
+        if not qs:
+            return []
+        if any(q["chain"] != qs[0]["chain"] or q["n_img"] != qs[0]["n_img"] for q in qs):
+            raise ValueError("generate_batch: all requests must share img_ids_list and num_img_gen_tokens")
+        llm = self.llm
+        embs = [llm.embed_tokens(q["ids"]) for q in qs]
+        with_img = [i for i, q in enumerate(qs) if q["image_embeds"] is not None]
+        if with_img:
+            imgs = [qs[i]["image_embeds"] for i in with_img]
+            if len({tuple(t.shape[1:]) for t in imgs}) == 1:
+                lm = self.input_resampler(torch.cat([t.to(llm.dev) for t in imgs], 0))
+                parts = lm.split([int(t.shape[0]) for t in imgs], 0)
+            else:                                  # different token grids: the position table is per length
+                parts = [self.input_resampler(t) for t in imgs]
+            for i, part in zip(with_img, parts):
+                emb = embs[i]
+                emb[qs[i]["ids_cmp_mask"].view(-1).to(emb.device)] = part.reshape(-1, emb.shape[-1])
+        llm.set_image_token_chain(qs[0]["chain"])
+        gs = llm.generate_batch(embs, [int(q["ids"][-1]) for q in qs], [q["eos"] for q in qs], [q["max_new"] for q in qs])
+        blocks = [self._image_blocks(q, g) for q, g in zip(qs, gs)]
+        all_feats = [f for b in blocks for f in b[3]]
+        res = self.output_resampler(torch.stack(all_feats)).contiguous() if all_feats else None
+        outs, at = [], 0
+        for q, (generate_ids, ids_gen_mask, num_gen_imgs, feats) in zip(qs, blocks):
+            img_gen_feat = None
+            if num_gen_imgs > 0:
+                if not feats:
+                    raise RuntimeError("</img> was generated without a whole image block in front of it")
+                img_gen_feat = res[at:at + len(feats)].contiguous()
+                at += len(feats)
+            tok = q["tokenizer"]
+            text = tok.decode(generate_ids, skip_special_tokens=True) if tok is not None else None
+            outs.append({"text": text, "output_ids": generate_ids, "img_gen_feat": img_gen_feat,
+                         "num_gen_imgs": num_gen_imgs, "ids_gen_mask": ids_gen_mask})
+        return outs
 
 
 @torch.no_grad()
@@ -505,3 +724,26 @@ def mllm_prepass(pipeline, agent: ContinuousLVLM, input_ids: Tensor, ids_cmp_mas
     gen = out["img_gen_feat"].view(n_ip, nv, -1)
     base = image_embeds.reshape(n_ip, nv, -1).to(gen.dtype)
     return ops.blend(gen, base, float(mllm_scale))
+
+
+@torch.no_grad()
+def mllm_prepass_batch(pipeline, agent: ContinuousLVLM, requests: Sequence[dict], tokenizer=None,
+                       img_ids_list: Optional[Sequence[int]] = None, eos_token_id: Optional[int] = None,
+                       max_new_tokens: int = 500) -> List[Tensor]:
+    """`mllm_prepass` for up to `agent.llm.max_sequences` requests in one decode loop.  Each request is a dict with
+    `input_ids`, `ids_cmp_mask`, `ip_images` and `mllm_scale`; returns one blended `ip_image_embeds` per request."""
+    cfg = pipeline.unet.config
+    nv, n_ip = cfg.num_vision_tokens, cfg.max_num_ips
+    image_embeds = [pipeline.encode_ip_tokens(r["ip_images"])[:, nv:, :] for r in requests]
+    outs = agent.generate_batch([
+        dict(tokenizer=tokenizer, input_ids=r["input_ids"].unsqueeze(0), image_embeds=e,
+             ids_cmp_mask=r["ids_cmp_mask"].unsqueeze(0), max_new_tokens=max_new_tokens,
+             num_img_gen_tokens=agent.output_resampler.num_queries, img_ids_list=img_ids_list, eos_token_id=eos_token_id)
+        for r, e in zip(requests, image_embeds)])
+    blended = []
+    for r, e, out in zip(requests, image_embeds, outs):
+        if out["img_gen_feat"] is None:
+            raise RuntimeError("the MLLM produced no image block")
+        gen = out["img_gen_feat"].view(n_ip, nv, -1)
+        blended.append(ops.blend(gen, e.reshape(n_ip, nv, -1).to(gen.dtype), float(r["mllm_scale"])))
+    return blended

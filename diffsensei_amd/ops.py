@@ -737,6 +737,89 @@ def llm_swiglu(gate_up: Tensor, out: Optional[Tensor] = None) -> Tensor:
     return out
 
 
+# ---- batched decode: up to 16 sequences per weight pass (csrc/llm.hip) ----------------------------------------
+def llm_gemm16(x: Tensor, w: Tensor, out: Optional[Tensor] = None, residual: Optional[Tensor] = None, rms: bool = False,
+               swiglu: bool = False, eps: float = 1e-6, gain: Optional[Tensor] = None, M: Optional[int] = None,
+               N: Optional[int] = None) -> Tensor:
+    """`llm_gemv` for M <= 16 rows on the matrix pipe: the weights are streamed once for all rows.  `out` / `residual`
+    may be larger than [M, N] (their row stride is used; rows past M and columns past N stay untouched); `M` / `N`
+    restrict the call to the first rows of `x` / weight rows of `w` (swiglu: `w` must then hold exactly 2N rows)."""
+    _chk(x, w, residual, gain)
+    K = x.shape[1]
+    M = x.shape[0] if M is None else int(M)
+    rows = w.shape[0] // (2 if swiglu else 1)
+    N = rows if N is None else int(N)
+    assert w.shape[1] == K and 0 < M <= x.shape[0] and 0 < N <= rows and (not swiglu or N == rows)
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float16, device=x.device)
+    _chk(out)
+    assert out.dim() == 2 and out.stride(1) == 1 and out.shape[0] >= M and out.shape[1] >= N
+    ldr = 0
+    if residual is not None:
+        assert residual.dim() == 2 and residual.stride(1) == 1 and residual.shape[0] >= M and residual.shape[1] >= N
+        ldr = residual.stride(0)
+    check(_lib.load().ds_llm_gemm16(_p(x), x.stride(0), _p(w), _p(out), out.stride(0), _p(residual), ldr, M, N, K,
+                                    int(rms), _p(gain), int(swiglu), eps, _stream()), "ds_llm_gemm16")
+    return out
+
+
+def llm_attention_slots(qkv: Tensor, k_cache: Tensor, v_cache: Tensor, rope_cos: Tensor, rope_sin: Tensor, state: Tensor,
+                        heads: int, kv_heads: int, scale: float, out: Optional[Tensor] = None) -> Tensor:
+    """One new row per slot: qkv [S,(heads+2*kv_heads)*D]; caches [S, T_max, kv_heads*D]; state int32 [S, 8].  Slot s
+    appends at state[s][0] in its own cache; a slot with state[s][2] set is left alone."""
+    _chk(qkv, k_cache, v_cache)
+    _chk(rope_cos, rope_sin, dtype=torch.float32)
+    _chk(state, dtype=torch.int32)
+    S = qkv.shape[0]
+    D = qkv.shape[1] // (heads + 2 * kv_heads)
+    T_max = k_cache.shape[1]
+    assert k_cache.shape == v_cache.shape == (S, T_max, kv_heads * D) and state.shape == (S, 8)
+    assert rope_cos.shape == (T_max, D // 2)
+    if out is None:
+        out = torch.empty((S, heads * D), dtype=torch.float16, device=qkv.device)
+    check(_lib.load().ds_llm_attn_slots_f16(_p(qkv), qkv.shape[1], _p(k_cache), _p(v_cache), k_cache.shape[2],
+                                            k_cache.stride(0), _p(rope_cos), _p(rope_sin), _p(out), heads * D, _p(state),
+                                            S, heads, kv_heads, D, T_max, scale, _stream()), "ds_llm_attn_slots_f16")
+    return out
+
+
+def llm_rmsnorm_slots(x: Tensor, gamma: Tensor, eps: float, out: Optional[Tensor] = None, feat: Optional[Tensor] = None,
+                      state: Optional[Tensor] = None) -> Tensor:
+    """x [S,H]; feat [S, max_out, H] (optional) receives row s at state[s][1]-1 unless slot s is finished."""
+    _chk(x, gamma, feat)
+    S, H = x.shape
+    if out is None:
+        out = torch.empty_like(x)
+    if feat is not None:
+        _chk(state, dtype=torch.int32)
+        assert feat.shape[0] == S and feat.shape[2] == H and state.shape == (S, 8)
+    check(_lib.load().ds_llm_rmsnorm_slots_f16(_p(x), H, _p(gamma), _p(out), H, _p(feat), _p(state), S, H,
+                                               0 if feat is None else feat.shape[1], eps, _stream()),
+          "ds_llm_rmsnorm_slots_f16")
+    return out
+
+
+def llm_embed_slots(table: Tensor, state: Tensor, out: Tensor) -> Tensor:
+    _chk(table, out)
+    _chk(state, dtype=torch.int32)
+    S = state.shape[0]
+    assert state.shape == (S, 8) and out.shape == (S, table.shape[1])
+    check(_lib.load().ds_llm_embed_slots_f16(_p(table), _p(state), _p(out), out.stride(0), S, table.shape[1],
+                                             table.shape[0], _stream()), "ds_llm_embed_slots_f16")
+    return out
+
+
+def llm_select_slots(logits: Tensor, chain: Optional[Tensor], adv: int, state: Tensor, out_ids: Tensor) -> None:
+    """`llm_select` per slot: logits [S,V], state int32 [S,8] (eos and max_new per slot), out_ids int32 [S,cap]."""
+    _chk(logits)
+    _chk(chain, state, out_ids, dtype=torch.int32)
+    S, V = logits.shape
+    assert state.shape == (S, 8) and out_ids.shape[0] == S
+    check(_lib.load().ds_llm_select_slots_f16(_p(logits), logits.stride(0), V, _p(chain),
+                                              0 if chain is None else chain.numel(), out_ids.shape[1], adv, _p(state),
+                                              _p(out_ids), S, _stream()), "ds_llm_select_slots_f16")
+
+
 def image_to_u8(image: Tensor) -> Tensor:
     """[B,3,H,W] fp32 in [0,1] -> [B,H,W,3] uint8 = (x*255).round() (half to even), the PIL tail of `postprocess`."""
     _chk(image, dtype=torch.float32)

@@ -20,6 +20,11 @@ captured hipGraph, and every panel still gets its own values.  What stays in the
 on: classifier-free guidance doubles the UNet batch, so it is on or off for a whole batch.  The default, False, is the
 five-value key above.  Multi-GPU: shard the request list with `distributed.shard_requests` (LPT by
 pixel count, no data-path collective) and run one batcher per rank.
+
+MLLM-conditioned requests: `BucketBatcher(pipe, agent=agent)` and `submit(..., ip_images=[...], mllm={"input_ids",
+"ids_cmp_mask", "mllm_scale", ...})`.  `run()` first turns every such request into an `ip_image_embeds` request through
+`mllm.mllm_prepass_batch`, in groups of at most `agent.llm.max_sequences` (one decode loop per group: a token step for 16
+sequences reads the weights once), then plans the UNet batches as above.
 """
 from __future__ import annotations
 
@@ -94,7 +99,7 @@ class BucketBatcher:
     """Collects requests, then runs them bucket by bucket through `pipe.generate_batch`."""
 
     def __init__(self, pipe, max_panels: int = 32, max_pixels: Optional[int] = 32 * 1024 * 1024,
-                 mix_scales: bool = False):
+                 mix_scales: bool = False, agent=None, prepass=None):
         # defaults = the benchmark's operating point (bench.py: 32 panels of 1024 x 1024 per call = UNet batch 64, where every
         # projection of the level-2 transformers is a whole number of 256-tile rounds); the pixel cap scales the panel count
         # down for larger images and lets smaller ones use the full 32
@@ -102,23 +107,72 @@ class BucketBatcher:
         self.max_panels = max_panels
         self.max_pixels = max_pixels
         self.mix_scales = mix_scales         # requests that differ only in guidance_scale / ip_scale share a batch
+        self.agent = agent                   # mllm.ContinuousLVLM: resolves requests submitted with `mllm=...`
+        self.prepass = prepass               # what decodes one group (None: mllm.mllm_prepass_batch)
         self._pending: List[dict] = []
         self.last_plan: List[List[int]] = []
+        self.last_prepass: List[List[int]] = []   # tickets of each MLLM pre-pass batch of the last run()
 
     def submit(self, **request) -> int:
         """Queue one request (keyword arguments of `DiffSenseiPipeline.__call__`, without `output_type`); returns its ticket."""
         if "output_type" in request:
             raise TypeError("output_type is chosen per run(), not per request")
         bucket_key(request, True)            # a request no batch can hold is refused here, not when its batch runs
+        m = request.get("mllm")
+        if m is not None:
+            if self.agent is None:
+                raise ValueError("a request with `mllm` needs a BucketBatcher built with `agent=`")
+            missing = [k for k in ("input_ids", "ids_cmp_mask", "mllm_scale") if k not in m]
+            if missing:
+                raise ValueError(f"mllm: {missing} missing (input_ids, ids_cmp_mask and mllm_scale are needed)")
+            if request.get("ip_image_embeds") is not None:
+                raise ValueError("`mllm` produces ip_image_embeds; pass one or the other")
         self._pending.append(request)
         return len(self._pending) - 1
 
     def __len__(self) -> int:
         return len(self._pending)
 
+    _MLLM_SHARED = ("tokenizer", "img_ids_list", "eos_token_id", "max_new_tokens")   # one value per pre-pass batch
+
+    def _resolve_mllm(self, reqs: List[dict]) -> List[dict]:
+        """Requests with `mllm` -> the same requests with `ip_image_embeds` (and no `ip_images`), decoded in groups of at
+        most `agent.llm.max_sequences` that agree on the shared decode arguments; the others are passed through."""
+        self.last_prepass = []
+        groups: Dict[Tuple, List[int]] = {}
+        for i, r in enumerate(reqs):
+            m = r.get("mllm")
+            if m is not None:
+                shared = tuple((k, id(m[k]) if k == "tokenizer" else (tuple(m[k]) if k == "img_ids_list" else m[k]))
+                               for k in self._MLLM_SHARED if m.get(k) is not None)
+                groups.setdefault(shared, []).append(i)
+        if not groups:
+            return reqs
+        prepass = self.prepass
+        if prepass is None:
+            from .mllm import mllm_prepass_batch as prepass
+        out = list(reqs)
+        cap = max(1, int(self.agent.llm.max_sequences))
+        for idx in groups.values():
+            m0 = reqs[idx[0]]["mllm"]
+            kw = {k: m0[k] for k in self._MLLM_SHARED if m0.get(k) is not None}
+            for c0 in range(0, len(idx), cap):
+                part = idx[c0:c0 + cap]
+                embeds = prepass(self.pipe, self.agent,
+                                 [dict(input_ids=reqs[i]["mllm"]["input_ids"], ids_cmp_mask=reqs[i]["mllm"]["ids_cmp_mask"],
+                                       mllm_scale=reqs[i]["mllm"]["mllm_scale"], ip_images=reqs[i].get("ip_images", []))
+                                  for i in part], **kw)
+                self.last_prepass.append(part)
+                for i, e in zip(part, embeds):
+                    r = {k: v for k, v in reqs[i].items() if k != "mllm"}
+                    r["ip_images"], r["ip_image_embeds"] = [], e
+                    out[i] = r
+        return out
+
     def run(self, output_type: str = "pil") -> List[Any]:
         """Run everything queued; returns the per-request outputs indexed by ticket and empties the queue."""
         reqs, self._pending = self._pending, []
+        reqs = self._resolve_mllm(reqs)
         self.last_plan = plan_batches(reqs, self.max_panels, self.max_pixels, self.mix_scales)
         results: List[Any] = [None] * len(reqs)
         for batch in self.last_plan:

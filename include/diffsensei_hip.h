@@ -408,6 +408,32 @@ int ds_blend_f16(const void* a, const void* b, void* out, int64_t n, float scale
  * (LlamaMLP.forward, modeling_llama_xformer.py:166-167) */
 int ds_llm_swiglu_f16(const void* gate_up, void* act, int M, int I, void* stream);
 
+/* Batched decode: up to 16 sequences share one pass over the weights.  The state block becomes int32 [S][8], one row
+ * per sequence slot with the eight fields above; every slot has its own KV cache ([S][T_max][kv_heads*D] per layer),
+ * feature buffer ([S][max_out][H]) and id list ([S][out_cap]).  A slot whose finished flag is set (a sequence that
+ * ended, or a slot that was never started: the host sets the flag) has nothing written to its cache, ids, features or
+ * counters; its rows of the projections still compute (finite, unused) values. */
+/* ds_llm_gemv_f16 for M <= 16 on the matrix pipe (llm_gemm16_kernel: v_mfma_f32_16x16x32_f16, x = A padded to 16
+ * rows, 16 weight rows = B, weights streamed HBM -> VGPR once for all rows).  Same prologues, epilogues and fp16
+ * rounding points; any N, K % 8 == 0 (with rms_gain: K <= 20480).  A row of y depends on that row of x only - not on M,
+ * on the other rows or on the padding - and the K split inside a block is reduced in a fixed order (no atomics). */
+int ds_llm_gemm16(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, const void* residual, int64_t ldr,
+                  int M, int N, int K, int rms, const void* rms_gain, int swiglu, float eps, void* stream);
+/* ds_llm_attn_f16 for one new row per slot: row s of qkv / out belongs to slot s, its caches start slot_stride
+ * elements after slot s-1's, its position is state[s][0]. */
+int ds_llm_attn_slots_f16(const void* qkv, int64_t ldqkv, void* k_cache, void* v_cache, int64_t ldc, int64_t slot_stride,
+                          const float* rope_cos, const float* rope_sin, void* out, int64_t ldo, const int32_t* state,
+                          int slots, int heads, int kv_heads, int D, int T_max, float scale, void* stream);
+/* row s normalised as ds_llm_rmsnorm_f16 does; `feat` (may be NULL): also stored as row state[s][1]-1 of feat[s] */
+int ds_llm_rmsnorm_slots_f16(const void* x, int64_t ldx, const void* gamma, void* y, int64_t ldy, void* feat,
+                             const int32_t* state, int slots, int H, int max_out, float eps, void* stream);
+/* out[s,:] = embed_tokens[state[s][3]] */
+int ds_llm_embed_slots_f16(const void* table, const int32_t* state, void* out, int64_t ldo, int slots, int H, int vocab,
+                           void* stream);
+/* ds_llm_select_f16 per slot: logits row s (stride ldl), state row s (with its own eos and max_new), out_ids[s] */
+int ds_llm_select_slots_f16(const void* logits, int64_t ldl, int V, const int32_t* chain, int n_chain, int out_cap, int adv,
+                            int32_t* state, int32_t* out_ids, int slots, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Character-reference pre-processing on the device.  Replaces the Pillow resize that
  * `CLIPImageProcessor()` / `ViTImageProcessor()` run on the host (reference src/pipelines/pipeline_diffsensei.py:125-126)
@@ -473,7 +499,12 @@ enum ds_opcode {
     DS_OP_LLM_SELECT = 23,   /* p: logits, chain, state, out_ids             i: V n_chain out_cap adv */
     DS_OP_LLM_ADVANCE = 24,  /* p: state                                     i: rows */
     /* 25, 26: retired (fp8 attention, rounds 2-5) */
-    DS_OP_LN_FINALIZE = 27   /* p: partial, stats                            i: M strips C               f: eps */
+    DS_OP_LN_FINALIZE = 27,  /* p: partial, stats                            i: M strips C               f: eps */
+    DS_OP_LLM_GEMM16 = 28,   /* as DS_OP_LLM_GEMV, M <= 16, on the matrix pipe (ds_llm_gemm16) */
+    DS_OP_LLM_ATTN_SLOTS = 29,    /* as DS_OP_LLM_ATTN with i[0] = slots and l[3] = slot_stride (ds_llm_attn_slots_f16) */
+    DS_OP_LLM_RMSNORM_SLOTS = 30, /* p: x, gamma, y, feat, state l: ldx ldy     i: slots H max_out       f: eps */
+    DS_OP_LLM_EMBED_SLOTS = 31,   /* p: table, state, out        l: ldo         i: slots H vocab */
+    DS_OP_LLM_SELECT_SLOTS = 32   /* p: logits, chain, state, out_ids  l: ldl   i: V n_chain out_cap adv slots */
 };
 
 typedef struct ds_op {

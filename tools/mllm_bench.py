@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """MLLM pre-pass decode rate at LLaMA-2-13B dimensions (random weights): tokens/s of the captured one-token plan and
 the HBM roofline fraction (algorithmic bytes = every layer matrix + lm_head once per token).
-    python tools/mllm_bench.py [--layers 40] [--prompt 96] [--new 192]
+    python tools/mllm_bench.py [--layers 40] [--prompt 96] [--new 192] [--sequences S]
+--sequences S > 1: the batched decode (`generate_batch`, S sequences per weight pass): ms per step, tokens/s over all
+sequences, the HBM fraction of a step, and the per-launch time of `llm_gemm16_kernel` at the projection shapes.
 """
 import argparse
 import json
@@ -19,6 +21,7 @@ ap.add_argument("--prompt", type=int, default=96)
 ap.add_argument("--new", type=int, default=192)
 ap.add_argument("--graph", choices=["both", "on", "off"], default="both")
 ap.add_argument("--gemv-variant", type=int, default=0, help="0 pipelined, 1 one column per wavefront, 2 streaming")
+ap.add_argument("--sequences", type=int, default=1, help="sequences per weight pass (1: the one-sequence token loop)")
 a = ap.parse_args()
 dev = torch.device("cuda", 0)
 from diffsensei_amd import _lib
@@ -26,11 +29,71 @@ assert _lib.load().ds_set_option(b"llm_gemv_variant", a.gemv_variant) == 0
 cfg = LlamaConfig(num_hidden_layers=a.layers)
 t0 = time.perf_counter()
 sd = random_llama_state_dict(cfg, dev, 0)
-eng = LlamaDecodeEngine(cfg, sd, dev, max_positions=a.prompt + a.new + 8, max_new_tokens=a.new, poll_every=16)
+eng = LlamaDecodeEngine(cfg, sd, dev, max_positions=a.prompt + a.new + 8, max_new_tokens=a.new, poll_every=16,
+                        max_sequences=a.sequences)
 del sd
 torch.cuda.synchronize()
 init_s = time.perf_counter() - t0
 emb = (torch.randn(a.prompt, cfg.hidden_size, device=dev) * 0.5).half()
+
+
+def batched(S):
+    from diffsensei_amd import ops
+    embs = [(torch.randn(a.prompt, cfg.hidden_size, device=dev) * 0.5).half() for _ in range(S)]
+    rows = []
+    for graph in {"both": (True, False), "on": (True,), "off": (False,)}[a.graph]:
+        eng.use_graph = graph
+        for rep in range(2):                               # rep 0 warms up (and captures)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = eng.generate_batch(embs, [1] * S, -1, a.new)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+        assert all(o["ids"].numel() == a.new and torch.isfinite(o["hidden"].float()).all() for o in out)
+        rows.append({"graph": graph, "seconds": round(dt, 4), "new_tokens": a.new})
+    for rep in range(2):                                   # prompt pass alone (max_new_tokens = 1)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        eng.generate_batch(embs, [1] * S, -1, 1)
+        torch.cuda.synchronize()
+        prompt_ms = round((time.perf_counter() - t0) * 1e3, 2)
+    for r in rows:
+        r["ms_per_step"] = round((r["seconds"] * 1e3 - prompt_ms) / (a.new - 1), 4)
+    best = min(r["ms_per_step"] for r in rows)
+    gbs = eng.weight_bytes_per_token() / (best * 1e-3) / 1e9
+    # per-launch times of the new kernel, M = 16, back to back (event pair around 20 launches after 3 warm-up launches)
+    H, I, V = cfg.hidden_size, cfg.intermediate_size, cfg.vocab_size
+    x5, x13 = (torch.randn(16, H, device=dev) * 0.5).half(), (torch.randn(16, I, device=dev) * 0.5).half()
+    y = torch.zeros(16, max(eng.qkv_dim, I, V), dtype=torch.float16, device=dev)
+    shapes = {"qkv": (x5, eng.wqkv[0], eng.qkv_dim, dict(rms=True, gain=eng.g_in[0])), "o": (x5, eng.wo[0], H, {}),
+              "gate_up": (x5, eng.wgu[0], I, dict(rms=True, swiglu=True, gain=eng.g_post[0])),
+              "down": (x13, eng.wdown[0], H, {}), "lm_head": (x5, eng.lm_head, V, {})}
+    kern = {}
+    for name, (x, w, N, kw) in shapes.items():
+        run = lambda: ops.llm_gemm16(x, w, out=y, N=N, **kw)
+        for _ in range(3):
+            run()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(20):
+            run()
+        e1.record()
+        torch.cuda.synchronize()
+        us = e0.elapsed_time(e1) * 1e3 / 20
+        kern[name] = {"N": N, "K": int(x.shape[1]), "us": round(us, 2), "GBps": round(2.0 * w.numel() / us / 1e3, 1)}
+    print(json.dumps({"workload": f"LLaMA-2-13B dims x {a.layers} layers, {S} sequences greedy, prompt {a.prompt} + {a.new} new tokens",
+                      "init_s": round(init_s, 1), "sequences": S, "runs": rows, "prompt_ms": prompt_ms,
+                      "weight_bytes_per_step": eng.weight_bytes_per_token(), "ms_per_step": best,
+                      "decode_tokens_per_s": round(S * 1e3 / best, 2),
+                      "roofline": {"bound": "hbm", "kernel": "llm_gemm16_kernel", "achieved": round(gbs, 1), "peak": 8000.0,
+                                   "unit": "GB/s", "frac": round(gbs / 8000.0, 4),
+                                   "note": "whole token step priced against the weight bytes, read once for all sequences"},
+                      "ops_per_step": eng.last_run_info["ops_per_token"], "gemm16_launches_m16": kern}))
+
+
+if a.sequences > 1:
+    batched(a.sequences)
+    sys.exit(0)
 rows = []
 for graph in {"both": (True, False), "on": (True,), "off": (False,)}[a.graph]:
     eng.use_graph = graph
