@@ -25,7 +25,7 @@ void ds_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* ds_last_error(void) { return g_err; }
-int ds_version(void) { return 103; }
+int ds_version(void) { return 104; }
 
 int ds_device_info(int* cu_count, int* lds_bytes, char* arch_name, int arch_name_len) {
     int dev = 0;
@@ -567,6 +567,27 @@ int ds_cfg_sampler_step_panels_f16(const void* eps, void* latents, void* model_i
     return ds_launch_sampler_step(p, step_ctr, S(stream));
 }
 
+int ds_cfg_sampler_step_redraw_f16(const void* eps, void* latents, void* model_in, const float* table,
+                                   const float* guidance, const float* solver, void* prev_x0, const int64_t* seeds,
+                                   const void* redraw, const int32_t* step_ctr, int ns, int HW, int kind, int do_cfg,
+                                   void* stream) {
+    SamplerStepParams p;
+    p.eps = H(eps); p.latents = HM(latents); p.model_in = HM(model_in); p.coef = table;
+    p.guidance = guidance; p.solver = solver; p.prev_x0 = HM(prev_x0);
+    p.seeds = reinterpret_cast<const long long*>(seeds);
+    p.redraw = redraw; p.redraw_on = 1;
+    p.ns = ns; p.HW = HW; p.kind = kind; p.do_cfg = do_cfg;
+    return ds_launch_sampler_step(p, step_ctr, S(stream));
+}
+
+int64_t ds_redraw_buffer_bytes(int ns, int HW) {
+    return (int64_t)ds_redraw_f32_offset(ns, HW) + (int64_t)sizeof(float) * (4 + 2 * DS_REDRAW_MAX_ROWS);
+}
+
+int ds_redraw_start_f16(const void* redraw, void* latents, int ns, int HW, void* stream) {
+    return ds_launch_redraw_start(redraw, HM(latents), ns, HW, S(stream));
+}
+
 int ds_philox_u32(const int64_t* seeds, int step, int stream_id, uint32_t* out, int ns, int HW, void* stream) {
     return ds_launch_philox_u32(reinterpret_cast<const long long*>(seeds), step, stream_id, out, ns, HW, S(stream));
 }
@@ -667,9 +688,12 @@ static int run_op(const ds_op& o, hipStream_t st) {
             s.prev_x0 = HM(p[5]); s.solver = reinterpret_cast<const float*>(p[6]);
             s.seeds = reinterpret_cast<const long long*>(p[7]);
             s.guidance = reinterpret_cast<const float*>(p[8]);
+            s.redraw = p[9]; s.redraw_on = i[4];
             s.ns = i[0]; s.HW = i[1]; s.kind = i[2]; s.do_cfg = i[3];
             return ds_launch_sampler_step(s, reinterpret_cast<const int*>(p[4]), st);
         }
+        case DS_OP_REDRAW_START:
+            return ds_launch_redraw_start(p[0], HM(p[1]), i[0], i[1], st);
         case DS_OP_PREP_INPUT:
             return ds_launch_prepare_model_input(H(p[0]), HM(p[1]), reinterpret_cast<const float*>(p[2]),
                                                  reinterpret_cast<const int*>(p[3]), i[0], i[1], 4, i[2], st);
@@ -777,6 +801,7 @@ int ds_op_describe(const ds_op* op, char* name, int name_len, double* flops, dou
         case DS_OP_CONV_OUT: nm = "conv_out_kernel"; fl = 2.0 * i[0] * (double)i[1] * i[2] * 9 * i[3] * i[4]; break;
         case DS_OP_SKINNY: nm = "skinny_linear_kernel"; fl = 2.0 * i[0] * (double)i[1] * i[2]; by = 2.0 * i[1] * (double)i[2]; break;
         case DS_OP_SAMPLER_STEP: nm = "sampler_step_kernel"; break;
+        case DS_OP_REDRAW_START: nm = "redraw_start_kernel"; by = 2.0 * 3.0 * i[0] * 4.0 * i[1]; break;
         case DS_OP_LLM_GEMV:
             nm = "llm_gemv_kernel";
             fl = 2.0 * i[0] * (double)i[1] * i[2] * (i[4] ? 2 : 1);

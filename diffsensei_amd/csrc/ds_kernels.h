@@ -190,11 +190,30 @@ struct SamplerStepParams {
     const float* solver = nullptr;  // kind 2: per-step solver rows [n_steps,8] (include/diffsensei_hip.h)
     const long long* seeds = nullptr;  // kind 3: int64 [ns], one Philox key per panel (noise = f(seed, pixel, *ctr))
     const float* guidance = nullptr;   // fp32 [ns], one guidance scale per panel in place of column 7 (null: column 7)
+    const void* redraw = nullptr;      // region redraw: the packed buffer below (read when redraw_on is set)
     int ns = 0, HW = 0, C = 4;
     int kind = 0;                   // 0 Euler, 1 DDIM, 2 DPM-Solver++ (multistep, order 1|2 per row), 3 Euler Ancestral
     int do_cfg = 1;
+    int redraw_on = 0;              // 1: blend with the kept latents after the step (a launch without the buffer is refused)
 };
 int ds_launch_sampler_step(const SamplerStepParams& p, const int* ctr, hipStream_t stream);
+// Region redraw: ONE device buffer (16-byte aligned) whose offsets follow from ns and HW (include/diffsensei_hip.h):
+//   x0k fp16 [ns,4,HW] | noise fp16 [ns,4,HW] | mask fp16 [ns,HW] | pad to 16 bytes |
+//   header fp32 [4] = {full strength, init_noise_sigma, 0, 0} | renoise rows fp32 [DS_REDRAW_MAX_ROWS][2] = {ka, kb}
+constexpr int DS_REDRAW_MAX_ROWS = 1025;
+struct RedrawView {
+    const half_t *x0k, *noise, *mask;
+    const float *hdr, *rows;
+};
+__host__ __device__ inline long ds_redraw_f32_offset(int ns, int HW) {   // bytes
+    return ((long)ns * HW * 9 * 2 + 15) & ~15L;
+}
+__host__ __device__ inline RedrawView ds_redraw_view(const void* buf, int ns, int HW) {
+    const half_t* h = static_cast<const half_t*>(buf);
+    const float* f = reinterpret_cast<const float*>(static_cast<const char*>(buf) + ds_redraw_f32_offset(ns, HW));
+    return RedrawView{h, h + (long)ns * 4 * HW, h + (long)ns * 8 * HW, f, f + 4};
+}
+int ds_launch_redraw_start(const void* redraw, half_t* latents, int ns, int HW, hipStream_t stream);
 // Philox4x32-10 keyed per panel, counter (pixel, 0, step, stream_id): raw words [ns,HW,4] / Box-Muller normals [ns,4,HW]
 int ds_launch_philox_u32(const long long* seeds, int step, int stream_id, unsigned* out, int ns, int HW,
                          hipStream_t stream);

@@ -296,13 +296,29 @@ __global__ __launch_bounds__(256) void philox_normal_kernel(const long long* __r
 // GV: the guidance scale of panel n is p.guidance[n] instead of column 7 of the table row - the same product at the same
 // rounding points.  An instantiation of its own, so that the one-scalar launch stays the kernel it was (34 SGPRs; the
 // vector's pointer costs 4 more: profiles/per_panel_scales_resource_usage_*.txt).
-template <bool GV>
+// RD: region redraw (include/diffsensei_hip.h, "region redraw").  After the step, a pixel whose mask m is not 1 is
+// pulled back to the kept latents re-noised to the NEXT state's noise level, known = ka * x0k + kb * nz with {ka, kb} =
+// renoise row *ctr + 1, and the stored latent is half(m * half(xn) + (1 - m) * half(known)) - the blend of diffusers'
+// 4-channel inpainting loop [3P], one launch with the step.  m == 1 is a branch, not a weight: such a pixel stores the
+// bits the RD == false kernel stores, and x0k / nz are not read for it.  m == 0 stores half(known), whatever xn is.
+// prev_x0 (kind 2) is the unblended x0 of this step; model_in is formed from the blended value.  Like GV, instantiations
+// of their own: the RD == false kernels are the ones they were (profiles/redraw_resource_usage_*.txt).
+template <bool GV, bool RD>
 __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p, const int* ctr) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     const long total = (long)p.ns * p.HW;
     if (i >= total) return;
     const int n = (int)(i / p.HW), pix = (int)(i - (long)n * p.HW);
     const float* cf = coef_row(p.coef, ctr);
+    float m = 1.0f, ka = 0.f, kb = 0.f;
+    const half_t *x0k = nullptr, *nz = nullptr;
+    if constexpr (RD) {
+        const RedrawView rv = ds_redraw_view(p.redraw, p.ns, p.HW);
+        const float* rr = rv.rows + 2 * ((ctr ? *ctr : 0) + 1);   // the state this step produces
+        ka = rr[0]; kb = rr[1];
+        x0k = rv.x0k; nz = rv.noise;
+        m = (float)rv.mask[(long)n * p.HW + pix];
+    }
     const float* sv = p.kind == 2 ? coef_row(p.solver, ctr) : nullptr;
     const h4 eu = *reinterpret_cast<const h4*>(p.eps + ((long)n * p.HW + pix) * 4);
     h4 e = eu;
@@ -349,12 +365,31 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p, 
             }
             *pp = x0;
         }
-        const half_t xh = (half_t)xn;
+        half_t xh = (half_t)xn;
+        if constexpr (RD) {
+            if (m != 1.0f) {
+                const long o = ((long)n * 4 + c) * p.HW + pix;
+                const half_t kh = (half_t)(ka * (float)x0k[o] + kb * (float)nz[o]);
+                xh = m == 0.0f ? kh : (half_t)(m * (float)xh + (1.0f - m) * (float)kh);
+            }
+        }
         *lp = xh;
         xin[c] = (half_t)((float)xh / cf[6]);
     }
     *reinterpret_cast<h4*>(p.model_in + ((long)n * p.HW + pix) * 4) = xin;
     if (p.do_cfg) *reinterpret_cast<h4*>(p.model_in + ((long)(p.ns + n) * p.HW + pix) * 4) = xin;
+}
+
+// Region redraw, the state a run starts from: latents = half(ka0 * x0k + kb0 * nz), {ka0, kb0} = renoise row 0, fp32 with
+// one rounding - or, when the header says full strength, half(nz * init_noise_sigma): the fp16 product the pipeline's
+// `prepare_latents` makes, so that a full-strength redraw starts from the latents of a plain call bit for bit.
+__global__ __launch_bounds__(256) void redraw_start_kernel(const void* redraw, half_t* latents, int ns, int HW) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)ns * 4 * HW) return;
+    const RedrawView rv = ds_redraw_view(redraw, ns, HW);
+    const float z = (float)rv.noise[i];
+    if (rv.hdr[0] != 0.0f) latents[i] = (half_t)(z * rv.hdr[1]);
+    else latents[i] = (half_t)(rv.rows[0] * (float)rv.x0k[i] + rv.rows[1] * z);
 }
 
 __global__ __launch_bounds__(256) void prepare_model_input_kernel(const half_t* latents, half_t* model_in,
@@ -529,10 +564,28 @@ int ds_launch_sampler_step(const SamplerStepParams& p, const int* ctr, hipStream
                "sampler_step: kind must be 0 (Euler), 1 (DDIM), 2 (DPM-Solver++) or 3 (Euler Ancestral)");
     DS_REQUIRE(p.kind != 2 || (p.prev_x0 && p.solver), "sampler_step: kind 2 needs prev_x0 and the solver rows");
     DS_REQUIRE(p.kind != 3 || p.seeds, "sampler_step: kind 3 needs the per-panel seeds");
+    DS_REQUIRE(!p.redraw_on || p.redraw, "sampler_step: the redraw flag is set without the redraw buffer");
+    DS_REQUIRE(!p.redraw_on || ((uintptr_t)p.redraw & 15) == 0, "sampler_step: the redraw buffer must be 16-byte aligned");
     const long total = (long)p.ns * p.HW;
     const dim3 grid((unsigned)((total + 255) / 256));
-    if (p.guidance) hipLaunchKernelGGL(sampler_step_kernel<true>, grid, dim3(256), 0, stream, p, ctr);
-    else hipLaunchKernelGGL(sampler_step_kernel<false>, grid, dim3(256), 0, stream, p, ctr);
+    if (p.redraw_on) {
+        if (p.guidance) hipLaunchKernelGGL((sampler_step_kernel<true, true>), grid, dim3(256), 0, stream, p, ctr);
+        else hipLaunchKernelGGL((sampler_step_kernel<false, true>), grid, dim3(256), 0, stream, p, ctr);
+    } else if (p.guidance) {
+        hipLaunchKernelGGL((sampler_step_kernel<true, false>), grid, dim3(256), 0, stream, p, ctr);
+    } else {
+        hipLaunchKernelGGL((sampler_step_kernel<false, false>), grid, dim3(256), 0, stream, p, ctr);
+    }
+    DS_LAUNCH_CHECK();
+    return 0;
+}
+
+int ds_launch_redraw_start(const void* redraw, half_t* latents, int ns, int HW, hipStream_t stream) {
+    DS_REQUIRE(redraw && latents && ns > 0 && HW > 0, "redraw_start: bad arguments");
+    DS_REQUIRE(((uintptr_t)redraw & 15) == 0, "redraw_start: the redraw buffer must be 16-byte aligned");
+    const long total = (long)ns * 4 * HW;
+    hipLaunchKernelGGL(redraw_start_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, redraw, latents,
+                       ns, HW);
     DS_LAUNCH_CHECK();
     return 0;
 }

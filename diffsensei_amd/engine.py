@@ -18,7 +18,7 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import OP, DsOp, check
 from .attention_processor import mask_grid_size
 from .schedulers import KIND_DPM, KIND_EULER_ANCESTRAL
@@ -415,12 +415,14 @@ class UNetEngine:
         self.table.zero_()
         self.ctr = E(1, dtype=torch.int32)
         self.ctr.zero_()
-        # ---- sampler (`build_sampler`): the built (ns, kind, do_cfg) and the buffers only some kinds have
+        # ---- sampler (`build_sampler`): the built (ns, kind, do_cfg, redraw) and the buffers only some kinds have
         self._sampler_key = None
         self.sampler_kind = None
         self.prev_x0 = None                                     # DPM-Solver++: the previous step's x0
         self.solver = None                                      # DPM-Solver++: the per-step solver rows
         self.noise_seeds = None                                 # Euler Ancestral: one Philox seed per panel
+        self.redraw = None                                      # region redraw: x0k | noise | mask | renoise rows, one buffer
+        self._redraw_ns = None
         # ---- request-level derived tensors
         self.enc_txt = E(B, LP, xdim)
         self.enc_ip = E(B, LP, xdim)
@@ -802,17 +804,27 @@ class UNetEngine:
         return ops
 
     # -- sampling: forward + CFG + scheduler step + counter advance as ONE replayable plan
-    def build_sampler(self, ns: int, kind: int, do_cfg: bool = True):
-        """reference src/pipelines/pipeline_diffsensei.py:310-337, one loop iteration per `step_plan.run()`."""
+    def build_sampler(self, ns: int, kind: int, do_cfg: bool = True, redraw: bool = False):
+        """reference src/pipelines/pipeline_diffsensei.py:310-337, one loop iteration per `step_plan.run()`.
+        redraw: the region-redraw sampler - the prep plan first writes the start state out of the redraw buffer
+        (`load_redraw`) and every step blends the kept region back in; part of the key, so a plain sampler built
+        afterwards has plans that never touch the buffer."""
         if self.B != (2 * ns if do_cfg else ns):
             raise ValueError(f"engine batch {self.B} does not match num_samples {ns} (cfg={do_cfg})")
-        key = (ns, kind, do_cfg)
+        key = (ns, kind, do_cfg, bool(redraw))
         if self._sampler_key == key:
             return
         HW = self.H * self.W
         self.latents = self._alloc((ns, self.cfg.in_channels, self.H, self.W), torch.float16)
-        self.prep_plan = Plan([make_op("PREP_INPUT", i=(ns, HW, int(do_cfg)),
-                                       p=(self.latents, self.x_in, self.table, self.ctr))], self.keep)
+        prep = []
+        if redraw:
+            if self.redraw is None or self._redraw_ns != ns:      # once per shape, kept when a plain sampler is built in between
+                self.redraw = ops.redraw_buffer(ns, self.H, self.W, self.dev)
+                self.keep.append(self.redraw)
+                self._redraw_ns = ns
+            prep.append(make_op("REDRAW_START", i=(ns, HW), p=(self.redraw, self.latents)))
+        prep.append(make_op("PREP_INPUT", i=(ns, HW, int(do_cfg)), p=(self.latents, self.x_in, self.table, self.ctr)))
+        self.prep_plan = Plan(prep, self.keep)
         # the buffers of this kind, allocated once per shape and kept when another kind is built in between
         if kind == KIND_DPM:
             if self.prev_x0 is None or self.prev_x0.shape != self.latents.shape:
@@ -832,13 +844,13 @@ class UNetEngine:
 
     def _build_step_plan(self):
         """The step plan of the built sampler over the buffers `build_sampler` allocated (nothing is allocated here)."""
-        ns, kind, do_cfg = self._sampler_key
+        ns, kind, do_cfg, redraw = self._sampler_key
         prev_x0, solver = (self.prev_x0, self.solver) if kind == KIND_DPM else (None, None)
         noise_seeds = self.noise_seeds if kind == KIND_EULER_ANCESTRAL else None
         step_ops = list(self.forward_ops) + [
-            make_op("SAMPLER_STEP", i=(ns, self.H * self.W, kind, int(do_cfg)),
+            make_op("SAMPLER_STEP", i=(ns, self.H * self.W, kind, int(do_cfg), int(redraw)),
                     p=(self.eps, self.latents, self.x_in, self.table, self.ctr, prev_x0, solver, noise_seeds,
-                       self.guidance if self.per_panel else None)),
+                       self.guidance if self.per_panel else None, self.redraw if redraw else None)),
             make_op("ADVANCE", p=(self.ctr,)),
         ]
         self.step_plan = Plan(step_ops, self.keep)
@@ -911,6 +923,20 @@ class UNetEngine:
         if solver_rows is not None:
             self.solver[:n].copy_(solver_rows.to(self.dev, torch.float32))
         self.ctr.zero_()
+
+    def load_redraw(self, x0: Tensor, noise: Tensor, mask: Tensor, renoise_rows: Tensor, full_strength: bool = False,
+                    init_noise_sigma: float = 1.0):
+        """Region redraw: copy the kept latents x0 [ns,4,H,W], the start noise [ns,4,H,W] (unit variance), the mask
+        [ns,H,W] (1 = repaint) and the renoise rows [n_run + 1, 2] of THIS run - the caller slices `[t_start:]`, like
+        the rows it gives `load_schedule`, whose counter still starts at 0 - into the static buffer.  A captured step
+        graph replays with the new contents, like seeds and guidance.  full_strength: the prep plan starts from
+        noise * init_noise_sigma, the latents of a plain run, instead of renoise row 0."""
+        if self._sampler_key is None or not self._sampler_key[3]:
+            raise ValueError("load_redraw: the built sampler is not a redraw sampler (build_sampler(..., redraw=True))")
+        ns = self._sampler_key[0]
+        if tuple(x0.shape) != (ns, 4, self.H, self.W):
+            raise ValueError(f"load_redraw: x0 {tuple(x0.shape)}, ({ns}, 4, {self.H}, {self.W}) is needed")
+        ops.redraw_load(self.redraw, x0, noise, mask, renoise_rows, full_strength, init_noise_sigma)
 
     # -- host-side setters (tiny H2D copies; never inside a captured graph)
     def set_request(self, encoder_hidden_states: Tensor, text_embeds: Tensor, time_ids: Tensor, bbox: Tensor,

@@ -487,6 +487,83 @@ def cfg_sampler_step_noise(eps: Tensor, latents: Tensor, model_in: Tensor, table
           "ds_cfg_sampler_step_noise_f16")
 
 
+# ---- region redraw: the packed buffer of include/diffsensei_hip.h ("Region redraw") and the two launches that read it
+REDRAW_MAX_ROWS = 1025
+
+
+def redraw_buffer(ns: int, H: int, W: int, device) -> Tensor:
+    """The zeroed uint8 device buffer `x0k | noise | mask | header | renoise rows` for `ns` panels of H x W latents."""
+    n = int(_lib.load().ds_redraw_buffer_bytes(int(ns), int(H) * int(W)))
+    return torch.zeros(n, dtype=torch.uint8, device=device)
+
+
+def redraw_views(buf: Tensor, ns: int, H: int, W: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """Views of a redraw buffer: x0k fp16 [ns,4,H,W], noise fp16 [ns,4,H,W], mask fp16 [ns,H,W], header fp32 [4]
+    ({full strength, init_noise_sigma, 0, 0}), renoise rows fp32 [REDRAW_MAX_ROWS, 2]."""
+    HW = H * W
+    if buf.dtype != torch.uint8 or buf.dim() != 1 or not buf.is_contiguous() or buf.data_ptr() % 16:
+        raise _lib.DiffSenseiHipError("redraw buffer: a contiguous, 16-byte aligned uint8 vector is needed")
+    if buf.numel() != int(_lib.load().ds_redraw_buffer_bytes(ns, HW)):
+        raise _lib.DiffSenseiHipError(f"redraw buffer: {buf.numel()} bytes do not fit ns={ns}, HW={HW}")
+    n4 = ns * 4 * HW
+    off = (18 * ns * HW + 15) & ~15
+    half = buf[:18 * ns * HW].view(torch.float16)
+    f32 = buf[off:].view(torch.float32)
+    return (half[:n4].view(ns, 4, H, W), half[n4:2 * n4].view(ns, 4, H, W), half[2 * n4:].view(ns, H, W), f32[:4],
+            f32[4:].view(REDRAW_MAX_ROWS, 2))
+
+
+def redraw_load(buf: Tensor, x0: Tensor, noise: Tensor, mask: Tensor, renoise_rows: Tensor, full_strength: bool = False,
+                init_noise_sigma: float = 1.0) -> None:
+    """Fill a redraw buffer.  x0, noise: [ns,4,H,W]; mask: [ns,H,W] in [0, 1] (1 = repaint; checked here, on the host -
+    the kernel takes it as given); renoise_rows: fp32 [n_run + 1, 2], one {ka, kb} per state of the run."""
+    if x0.dim() != 4 or x0.shape[1] != 4 or noise.shape != x0.shape:
+        raise ValueError(f"redraw: x0 {tuple(x0.shape)} and noise {tuple(noise.shape)} must both be [ns,4,H,W]")
+    ns, _, H, W = x0.shape
+    if tuple(mask.shape) != (ns, H, W):
+        raise ValueError(f"redraw: mask {tuple(mask.shape)}, ({ns}, {H}, {W}) is needed")
+    rows = torch.as_tensor(renoise_rows, dtype=torch.float32)
+    if rows.dim() != 2 or rows.shape[1] != 2 or not 2 <= rows.shape[0] <= REDRAW_MAX_ROWS:
+        raise ValueError(f"redraw: renoise rows {tuple(rows.shape)}, [n_run + 1, 2] with n_run + 1 <= {REDRAW_MAX_ROWS} is needed")
+    mh = mask.to(torch.float16)
+    lo, hi = float(mh.min()), float(mh.max())
+    if not (lo >= 0.0 and hi <= 1.0):      # also refuses NaN
+        raise _lib.DiffSenseiHipError(f"redraw: mask values must lie in [0, 1], got [{lo}, {hi}]")
+    vx, vn, vm, hdr, vr = redraw_views(buf, ns, H, W)
+    vx.copy_(x0.to(torch.float16))
+    vn.copy_(noise.to(torch.float16))
+    vm.copy_(mh)
+    hdr.copy_(torch.tensor([1.0 if full_strength else 0.0, float(init_noise_sigma), 0.0, 0.0], dtype=torch.float32))
+    vr[:rows.shape[0]].copy_(rows)
+
+
+def cfg_sampler_step_redraw(eps: Tensor, latents: Tensor, model_in: Tensor, table: Tensor, redraw: Optional[Tensor],
+                            kind: int, do_cfg: bool = True, ctr: Optional[Tensor] = None,
+                            guidance: Optional[Tensor] = None, solver: Optional[Tensor] = None,
+                            prev_x0: Optional[Tensor] = None, seeds: Optional[Tensor] = None) -> None:
+    """The sampler step of any kind (`solver` + `prev_x0`: kind 2, `seeds`: kind 3, `guidance`: per panel) followed in
+    the same launch by the region-redraw blend out of `redraw` (`redraw_buffer` / `redraw_load`): pixels whose mask is
+    1 get exactly the step's result, the others are pulled to the kept latents re-noised with renoise row *ctr + 1."""
+    ns, HW = _sampler_step_dims(eps, latents, model_in, table, solver=solver, prev_x0=prev_x0, seeds=seeds,
+                                guidance=guidance)
+    if redraw is not None:
+        _chk(redraw, dtype=torch.uint8)
+        redraw_views(redraw, ns, latents.shape[2], latents.shape[3])
+    check(_lib.load().ds_cfg_sampler_step_redraw_f16(_p(eps), _p(latents), _p(model_in), _p(table), _p(guidance), _p(solver),
+                                                     _p(prev_x0), _p(seeds), _p(redraw), _p(ctr), ns, HW, kind, int(do_cfg),
+                                                     _stream()), "ds_cfg_sampler_step_redraw_f16")
+
+
+def redraw_start(redraw: Tensor, latents: Tensor) -> None:
+    """latents [ns,4,H,W] = the start state of a redraw run out of `redraw`: half(ka0 * x0k + kb0 * noise), or
+    half(noise * init_noise_sigma) when the buffer's header says full strength."""
+    _chk(latents)
+    _chk(redraw, dtype=torch.uint8)
+    ns, _, H, W = latents.shape
+    redraw_views(redraw, ns, H, W)
+    check(_lib.load().ds_redraw_start_f16(_p(redraw), _p(latents), ns, H * W, _stream()), "ds_redraw_start_f16")
+
+
 def philox_u32(seeds: Tensor, step: int, HW: int, stream_id: int = 0) -> Tensor:
     """Raw Philox4x32-10 words, int32 [ns,HW,4] holding the uint32 bit patterns (include/diffsensei_hip.h)."""
     ns = seeds.shape[0]

@@ -42,6 +42,20 @@ def _black_image():
     return Image.new("RGB", (224, 224), (0, 0, 0))
 
 
+def redraw_mask_from_boxes(boxes, h: int, w: int) -> Tensor:
+    """fp32 [h, w], 1 inside the union of the normalised boxes [x1, y1, x2, y2] and 0 outside: latent pixel (y, x) is
+    repainted iff x1 <= (x + 0.5) / w < x2 and y1 <= (y + 0.5) / h < y2 - its centre lies in the half-open box (float64)."""
+    cx = (torch.arange(w, dtype=torch.float64) + 0.5) / w
+    cy = (torch.arange(h, dtype=torch.float64) + 0.5) / h
+    m = torch.zeros(h, w, dtype=torch.bool)
+    for b in boxes:
+        if len(b) != 4:
+            raise ValueError(f"`redraw_bbox`: boxes are [x1, y1, x2, y2], got {list(b)}")
+        x1, y1, x2, y2 = (float(v) for v in b)
+        m |= ((cy >= y1) & (cy < y2))[:, None] & ((cx >= x1) & (cx < x2))[None, :]
+    return m.to(torch.float32)
+
+
 class DiffSenseiPipeline:
     def __init__(self, vae, text_encoder, text_encoder_2, tokenizer, tokenizer_2, scheduler, unet: UNetMangaModel,
                  image_encoder, feature_extractor=None, force_zeros_for_empty_prompt: bool = True):
@@ -291,13 +305,71 @@ class DiffSenseiPipeline:
         return rep(pe), rep(ne), rep(pp), rep(npool)
 
     def prepare_latents(self, batch_size, num_channels, height, width, dtype, device, generator, latents=None):
+        return self._draw_noise(batch_size, num_channels, height, width, dtype, device, generator, latents) \
+            * self.scheduler.init_noise_sigma
+
+    def _draw_noise(self, batch_size, num_channels, height, width, dtype, device, generator, latents=None):
+        """The unit-variance draw of `prepare_latents` (or the `latents` given in its place), before the scaling."""
         shape = (batch_size, num_channels, int(height) // self.vae_scale_factor, int(width) // self.vae_scale_factor)
         if latents is None:
             gdev = generator.device if generator is not None and not isinstance(generator, list) else torch.device(device)
             latents = torch.randn(shape, generator=generator, device=gdev, dtype=dtype).to(device)
         else:
             latents = latents.to(device=device, dtype=dtype)
-        return latents * self.scheduler.init_noise_sigma
+        return latents
+
+    # ---- region redraw: the request's kept latents and mask, checked on the host before anything runs
+    def _redraw_inputs(self, redraw_latents, redraw_bbox, redraw_mask, strength, num_samples, height, width):
+        """None for a plain request, else {"x0": fp16 [ns,4,h,w], "mask": fp32 [ns,h,w] (1 = repaint), "strength"}.
+        ValueError for a mask or boxes without `redraw_latents` or the reverse, wrong shapes, mask values outside
+        [0, 1] and `strength` outside (0, 1]."""
+        import numbers
+        if isinstance(strength, bool) or not isinstance(strength, numbers.Real) or not 0.0 < float(strength) <= 1.0:
+            raise ValueError(f"`strength` has to be in (0, 1], got {strength!r}")
+        has_region = redraw_mask is not None or (redraw_bbox is not None and len(redraw_bbox) > 0)
+        if redraw_latents is None:
+            if has_region:
+                raise ValueError("`redraw_bbox` / `redraw_mask` say where to repaint; `redraw_latents` (the latents to keep) is missing")
+            if float(strength) != 1.0:
+                raise ValueError("`strength` shortens a redraw; without `redraw_latents` the whole schedule runs")
+            return None
+        if not has_region:
+            raise ValueError("`redraw_latents` given without `redraw_bbox` or `redraw_mask`: nothing says where to repaint")
+        h, w = int(height) // self.vae_scale_factor, int(width) // self.vae_scale_factor
+        x0 = redraw_latents
+        if not torch.is_tensor(x0) or x0.dim() != 4 or tuple(x0.shape[1:]) != (4, h, w) or x0.shape[0] not in (1, num_samples):
+            raise ValueError(f"`redraw_latents`: [1 or {num_samples}, 4, {h}, {w}] is needed, got "
+                             f"{tuple(x0.shape) if torch.is_tensor(x0) else type(x0)}")
+        x0 = x0.detach().to("cpu", torch.float16)
+        if not torch.isfinite(x0).all():
+            raise ValueError("`redraw_latents` holds non-finite values")
+        if x0.shape[0] == 1 and num_samples > 1:
+            x0 = x0.repeat(num_samples, 1, 1, 1)
+        mask = torch.zeros(num_samples, h, w, dtype=torch.float32)
+        if redraw_bbox is not None and len(redraw_bbox) > 0:
+            mask = torch.maximum(mask, redraw_mask_from_boxes(redraw_bbox, h, w)[None])
+        if redraw_mask is not None:
+            m = redraw_mask
+            if not torch.is_tensor(m) or m.dim() not in (2, 3, 4) or (m.dim() == 4 and m.shape[1] != 1):
+                raise ValueError("`redraw_mask`: a tensor [h,w], [ns,h,w] or [ns,1,h,w] is needed")
+            m = m.detach().to("cpu", torch.float32)
+            m = m.reshape((1, 1) + tuple(m.shape)) if m.dim() == 2 else (m[:, None] if m.dim() == 3 else m)
+            if m.shape[0] not in (1, num_samples):
+                raise ValueError(f"`redraw_mask`: {m.shape[0]} masks for {num_samples} samples")
+            if tuple(m.shape[2:]) == (int(height), int(width)) and (h, w) != (int(height), int(width)):
+                m = torch.nn.functional.interpolate(m, size=(h, w))          # nearest, like diffusers' prepare_mask_latents [3P]
+            elif tuple(m.shape[2:]) != (h, w):
+                raise ValueError(f"`redraw_mask`: {tuple(m.shape[2:])} is neither the latent size {(h, w)} nor the "
+                                 f"image size {(int(height), int(width))}")
+            if not bool(((m >= 0) & (m <= 1)).all()):
+                raise ValueError("`redraw_mask` values have to lie in [0, 1]")
+            mask = torch.maximum(mask, m[:, 0].expand(num_samples, h, w))
+        return {"x0": x0, "mask": mask.contiguous(), "strength": float(strength)}
+
+    def decode_latents(self, latents: Tensor, output_type: str = "pil"):
+        """Latents (a call with `output_type="latent"`, which are also what `redraw_latents` takes) -> images, exactly
+        as `__call__` post-processes its own."""
+        return self._postprocess(latents, output_type)
 
     # ---- reference :180-372
     @torch.no_grad()
@@ -315,7 +387,9 @@ class DiffSenseiPipeline:
                  negative_prompt_embeds: Optional[Tensor] = None, pooled_prompt_embeds: Optional[Tensor] = None,
                  negative_pooled_prompt_embeds: Optional[Tensor] = None, output_type: str = "pil",
                  callback_on_step_end=None, callback_on_step_end_tensor_inputs: Sequence[str] = ("latents",),
-                 noise_seeds: Optional[Sequence[int]] = None):
+                 noise_seeds: Optional[Sequence[int]] = None, redraw_latents: Optional[Tensor] = None,
+                 redraw_bbox: Optional[List[List[float]]] = None, redraw_mask: Optional[Tensor] = None,
+                 strength: float = 1.0):
         """`callback_on_step_end(pipe, step_index, timestep, {"latents": device tensor}) -> dict | None` is diffusers'
         SDXL-pipeline hook [3P]; together with `pipe._interrupt = True` it is the reference's early exit: the loop
         `continue`s over the remaining steps (reference :314-315) and the call still decodes and post-processes.  Latents
@@ -330,7 +404,16 @@ class DiffSenseiPipeline:
         `guidance_scale` and `ip_scale` are a number, as in the reference, or a sequence of `num_samples` numbers, one per
         sample (a slider sweep in one pass: the kernels take both per panel).  Classifier-free guidance is on or off
         for the whole batch, so a sequence is all > 1 or all <= 1.  `last_run_info["guidance_scales"]` /
-        `["ip_scales"]` list what every panel used."""
+        `["ip_scales"]` list what every panel used.
+
+        Region redraw: `redraw_latents` [1 or num_samples, 4, H/8, W/8] - the latents of an earlier
+        call with `output_type="latent"`; one row gives `num_samples` variants - are kept outside the region and
+        repainted inside it.  The region is the union of the normalised `redraw_bbox` boxes (a latent pixel is in when
+        its centre is) and / or `redraw_mask` ([h,w], [ns,h,w] or [ns,1,h,w] in [0, 1], latent or image resolution, soft
+        values allowed), combined by maximum.  `strength` in (0, 1] runs the last int(steps * strength) steps from the
+        kept latents noised to that level; 1.0 starts from pure noise.  The noise is the draw of a plain call (or
+        `latents=`); the callback gets the run-relative step index and the true timestep;
+        `last_run_info["redraw"]` = {"t_start", "steps_run", "repaint_fraction"}."""
         bad = [k for k in callback_on_step_end_tensor_inputs if k != "latents"]
         if bad:
             raise ValueError(f"`callback_on_step_end_tensor_inputs` has to be in ['latents'], but found {bad}")
@@ -339,7 +422,8 @@ class DiffSenseiPipeline:
                                   negative_prompt_2, num_samples, generator, original_size, crops_coords_top_left,
                                   target_size, ip_images, ip_image_embeds, ip_bbox, ip_scale, dialog_bbox, latents,
                                   prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds,
-                                  negative_pooled_prompt_embeds, noise_seeds)
+                                  negative_pooled_prompt_embeds, noise_seeds, redraw_latents, redraw_bbox, redraw_mask,
+                                  strength)
         out_latents = self._denoise([cond], num_inference_steps, callback_on_step_end)
         return StableDiffusionXLPipelineOutput(images=self._postprocess(out_latents, output_type))
 
@@ -347,7 +431,8 @@ class DiffSenseiPipeline:
     def _conditioning(self, prompt, prompt_2, height, width, num_inference_steps, guidance_scale, negative_prompt,
                       negative_prompt_2, num_samples, generator, original_size, crops_coords_top_left, target_size,
                       ip_images, ip_image_embeds, ip_bbox, ip_scale, dialog_bbox, latents, prompt_embeds,
-                      negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, noise_seeds=None):
+                      negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, noise_seeds=None,
+                      redraw_latents=None, redraw_bbox=None, redraw_mask=None, strength=1.0):
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         original_size = original_size or (height, width)
@@ -356,6 +441,10 @@ class DiffSenseiPipeline:
         if height % self.vae_scale_factor or width % self.vae_scale_factor:
             raise ValueError(f"`height` and `width` have to be divisible by {self.vae_scale_factor} but are {height} and {width}.")
         num_samples = 1 if num_samples is None else num_samples
+        redraw = self._redraw_inputs(redraw_latents, redraw_bbox, redraw_mask, strength, num_samples, height, width)
+        if redraw is not None:                                   # "no step would run" is a ValueError before any encoder too
+            self.scheduler.set_timesteps(num_inference_steps, device=self._execution_device)
+            self.scheduler.start_index(redraw["strength"])
         guidance = self._panel_values(guidance_scale, num_samples, "guidance_scale")
         ip_scales = self._panel_values(ip_scale, num_samples, "ip_scale")
         self._cfg_side(guidance)
@@ -381,8 +470,9 @@ class DiffSenseiPipeline:
                 negative_pooled_prompt_embeds = negative_pooled_prompt_embeds.repeat(num_samples, 1)
 
         self.scheduler.set_timesteps(num_inference_steps, device=device)
-        lat = self.prepare_latents(num_samples, self.unet.config.in_channels, height, width, torch.float16, device,
-                                   generator, latents)
+        # a redraw keeps the draw unscaled: the start kernel makes the start state from it (the same fp16 product at strength 1)
+        lat = (self.prepare_latents if redraw is None else self._draw_noise)(
+            num_samples, self.unet.config.in_channels, height, width, torch.float16, device, generator, latents)
         # a stochastic sampler's per-panel Philox seeds, drawn AFTER the initial latents: a deterministic scheduler
         # consumes the generator exactly as before, and a given generator starts Euler Ancestral from Euler's latents
         seeds = None
@@ -398,7 +488,7 @@ class DiffSenseiPipeline:
         neg_dialog, dialog = self.prepare_dialog_bbox(list(dialog_bbox), num_samples)
         to = lambda t: t.to(device)
         return {"n": num_samples, "lat": lat, "time_ids": add_time_ids, "noise_seeds": seeds,
-                "guidance": guidance, "ip_scales": ip_scales,
+                "guidance": guidance, "ip_scales": ip_scales, "redraw": redraw,
                 "pos": (to(prompt_embeds), to(pooled_prompt_embeds), to(img), to(bbox), to(dialog)),
                 "neg": (to(negative_prompt_embeds), to(negative_pooled_prompt_embeds), to(neg_img), to(neg_bbox),
                         to(neg_dialog))}
@@ -456,16 +546,36 @@ class DiffSenseiPipeline:
         # one plan replay per step
         B = enc.shape[0]
         eng = self.unet.engine(B, H, W, aspect_ratio)
-        eng.build_sampler(num_samples, self.scheduler.kind, do_cfg)
+        redraw = [c.get("redraw") for c in conds]
+        if any(r is None for r in redraw) and any(r is not None for r in redraw):
+            raise ValueError("a UNet batch is all region redraw or all plain sampling, not a mix")
+        redraw = None if redraw[0] is None else redraw
+        t_start = 0
+        if redraw is not None:
+            if len({r["strength"] for r in redraw}) != 1:
+                raise ValueError("the redraw requests of one UNet batch must share `strength` (one schedule per batch)")
+            t_start = self.scheduler.start_index(redraw[0]["strength"])
+        steps_run = num_inference_steps - t_start
+        eng.build_sampler(num_samples, self.scheduler.kind, do_cfg, redraw=redraw is not None)
         # rows n and ns + n of a CFG batch are panel n: both carry its IP scale
         eng.set_request(enc, add_text_embeds, add_time_ids, bbox, dialog_pixel_boxes(dialog, H, W),
                         ip_scales + ip_scales if do_cfg else ip_scales)
-        solver = self.scheduler.solver_table()             # DPM-Solver++ rows; None for Euler / DDIM
+        # DPM-Solver++ rows; None for Euler / DDIM.  A redraw that starts mid-schedule runs its first row first order
+        solver = self.scheduler.solver_table() if not t_start else self.scheduler.solver_table(start=t_start)
         # the panels' own seeds, in batch order: a panel's noise does not depend on the requests batched beside it
         seeds = [v for c in conds for v in c["noise_seeds"]] if self.scheduler.stochastic else None
-        eng.load_schedule(torch.from_numpy(self.scheduler.coef_table(guidance[0])),
+        # a redraw loads the rows [t_start:] of every table; the device counter still starts at 0, so Euler Ancestral's
+        # Philox step index is the run-relative step
+        eng.load_schedule(torch.from_numpy(self.scheduler.coef_table(guidance[0])[t_start:]),
                           None if solver is None else torch.from_numpy(solver), seeds, guidance=guidance)
-        eng.latents.copy_(lat)
+        if redraw is None:
+            eng.latents.copy_(lat)
+        else:                                              # the prep plan writes the start state out of this buffer
+            mask = torch.cat([r["mask"] for r in redraw], dim=0)
+            eng.load_redraw(torch.cat([r["x0"] for r in redraw], dim=0), lat, mask,
+                            torch.from_numpy(self.scheduler.renoise_table()[t_start:]),
+                            full_strength=redraw[0]["strength"] == 1.0,
+                            init_noise_sigma=self.scheduler.init_noise_sigma)
         if self._stream is None:
             self._stream = torch.cuda.Stream(device=device)
         st = self._stream
@@ -480,7 +590,7 @@ class DiffSenseiPipeline:
                     n0 = 1
                     eng.step_plan.capture(st.cuda_stream)
                 graph = True
-            timesteps = self.scheduler.timesteps
+            timesteps = self.scheduler.timesteps[t_start:]     # a callback gets the run-relative index and the true timestep
 
             def hook(i):
                 # diffusers' contract [3P]: `latents = callback_outputs.pop("latents", latents)` - a callback may return a
@@ -493,7 +603,7 @@ class DiffSenseiPipeline:
 
             if n0 and callback_on_step_end is not None:
                 hook(0)
-            for i in range(n0, num_inference_steps):
+            for i in range(n0, steps_run):
                 if self._interrupt:                               # reference :314-315 `if self.interrupt: continue`
                     continue
                 if graph:
@@ -505,6 +615,9 @@ class DiffSenseiPipeline:
         torch.cuda.current_stream(device).wait_stream(st)
         self.last_run_info = {"graph": graph, "ops_per_step": eng.step_plan.n, "batch": B, "latent_hw": (H, W),
                               "noise_seeds": seeds, "guidance_scales": guidance, "ip_scales": ip_scales}
+        if redraw is not None:
+            self.last_run_info["redraw"] = {"t_start": t_start, "steps_run": steps_run,
+                                            "repaint_fraction": float(mask.mean())}
         return eng.latents.clone()
 
     # ---- reference :339-367: VAE decode + image_processor.postprocess
@@ -585,7 +698,9 @@ class DiffSenseiPipeline:
         """Each request: the keyword arguments of `__call__` (without `output_type`).  All must share height, width and
         num_inference_steps (`serving.bucket_key`), and their guidance scales lie on one side of 1 (classifier-free
         guidance is on or off for the whole UNet batch); prompts, character references, boxes, seeds, `num_samples`,
-        `guidance_scale` and `ip_scale` are per request.  Returns one `.images`-like object per request, in order."""
+        `guidance_scale` and `ip_scale` are per request.  A batch is all region redraw (`redraw_latents`, each request with
+        its own kept latents and mask, one shared `strength`) or all plain.  Returns one `.images`-like object per request,
+        in order."""
         if not requests:
             return []
         self._interrupt = False          # like `__call__` (reference :226): an earlier interrupted call must not leak into this one
@@ -596,15 +711,27 @@ class DiffSenseiPipeline:
                  for r in requests]                 # before any encoder runs
         if any(s != sides[0] for s in sides):
             raise ValueError("generate_batch: requests mix classifier-free guidance on (guidance_scale > 1) and off (<= 1)")
+        rd = [r.get("redraw_latents") is not None for r in requests]
+        if any(rd) != all(rd):
+            raise ValueError("generate_batch: a batch is all region redraw (`redraw_latents`) or all plain, not a mix")
+        for r in requests:                          # every request's redraw fields, before any encoder runs
+            h = r.get("height") or self.default_sample_size * self.vae_scale_factor
+            w = r.get("width") or self.default_sample_size * self.vae_scale_factor
+            self._redraw_inputs(r.get("redraw_latents"), r.get("redraw_bbox"), r.get("redraw_mask"),
+                                r.get("strength", 1.0), r.get("num_samples", 1) or 1, h, w)
+        if all(rd) and len({float(r.get("strength", 1.0)) for r in requests}) != 1:
+            raise ValueError("generate_batch: the redraw requests of one batch must share `strength`")
         names = ("prompt", "prompt_2", "height", "width", "num_inference_steps", "guidance_scale", "negative_prompt",
                  "negative_prompt_2", "num_samples", "generator", "original_size", "crops_coords_top_left", "target_size",
                  "ip_images", "ip_image_embeds", "ip_bbox", "ip_scale", "dialog_bbox", "latents", "prompt_embeds",
-                 "negative_prompt_embeds", "pooled_prompt_embeds", "negative_pooled_prompt_embeds", "noise_seeds")
+                 "negative_prompt_embeds", "pooled_prompt_embeds", "negative_pooled_prompt_embeds", "noise_seeds",
+                 "redraw_latents", "redraw_bbox", "redraw_mask", "strength")
         defaults = dict(prompt_2=None, height=None, width=None, num_inference_steps=40, guidance_scale=5.0,
                         negative_prompt=None, negative_prompt_2=None, num_samples=1, generator=None, original_size=None,
                         crops_coords_top_left=(0, 0), target_size=None, ip_images=[], ip_image_embeds=None, ip_bbox=[],
                         ip_scale=1.0, dialog_bbox=[], latents=None, prompt_embeds=None, negative_prompt_embeds=None,
-                        pooled_prompt_embeds=None, negative_pooled_prompt_embeds=None, noise_seeds=None)
+                        pooled_prompt_embeds=None, negative_pooled_prompt_embeds=None, noise_seeds=None,
+                        redraw_latents=None, redraw_bbox=None, redraw_mask=None, strength=1.0)
         conds = []
         for r in requests:
             unknown = set(r) - set(names)

@@ -121,8 +121,38 @@ class _Scheduler:
         return tab
 
     # -- second per-step table (DPM-Solver++ only; see include/diffsensei_hip.h)
-    def solver_table(self) -> Optional[np.ndarray]:
+    def solver_table(self, start: int = 0) -> Optional[np.ndarray]:
         return None
+
+    # -- region redraw (include/diffsensei_hip.h, "Region redraw"): where a shortened run starts, and what a kept latent
+    #    looks like at the noise level of every state
+    def start_index(self, strength: float) -> int:
+        """diffusers' img2img `get_timesteps` [3P]: a run of `strength` in (0, 1] skips the first `t_start` of the n
+        steps, init = min(int(n * strength), n), t_start = max(n - init, 0).  ValueError outside (0, 1] or when no step
+        would run."""
+        if self.num_inference_steps is None:
+            raise RuntimeError("call set_timesteps first")
+        if not _is_real(strength) or not 0.0 < float(strength) <= 1.0:
+            raise ValueError(f"`strength` has to be in (0, 1], got {strength!r}")
+        n = self.num_inference_steps
+        t_start = max(n - min(int(n * float(strength)), n), 0)
+        if t_start >= n:
+            raise ValueError(f"strength {strength} of {n} steps runs no step at all (int({n} * {strength}) = 0)")
+        return t_start
+
+    def renoise_table(self) -> np.ndarray:
+        """fp32 [n + 1, 2]: row i = {ka, kb} with ka * x0 + kb * noise the kept latents x0 at the noise level of the
+        state that enters step i; row n, the final state, is {1, 0} for every sampler."""
+        raise NotImplementedError
+
+    def _renoise_rows(self, ka, kb) -> np.ndarray:
+        if self.num_inference_steps is None:
+            raise RuntimeError("call set_timesteps first")
+        n = self.num_inference_steps
+        rows = np.zeros((n + 1, 2), dtype=np.float32)
+        rows[:n, 0], rows[:n, 1] = np.asarray(ka, dtype=np.float32)[:n], np.asarray(kb, dtype=np.float32)[:n]
+        rows[n] = (1.0, 0.0)
+        return rows
 
     # -- stand-alone protocol (one kernel launch each; the pipeline's fused loop does not go through these)
     def _index_of(self, timestep, default: int) -> int:
@@ -170,6 +200,11 @@ class _Scheduler:
         return (lat,) if not return_dict else {"prev_sample": lat}
 
 
+def _is_real(v) -> bool:
+    import numbers
+    return isinstance(v, numbers.Real) and not isinstance(v, bool)
+
+
 def _launch_step(eps, lat, scratch, table, kind, ctr, solver=None, prev_x0=None, seeds=None):
     """One `sampler_step_kernel` launch through the C entry point that carries the given extras."""
     if solver is not None:
@@ -209,6 +244,9 @@ class EulerDiscreteScheduler(_Scheduler):
         tab[:, 3] = self.sigmas[1:]
         return tab
 
+    def renoise_table(self) -> np.ndarray:
+        return self._renoise_rows(np.ones_like(self.sigmas), self.sigmas)      # x0 + sigma_i * noise
+
 
 class DDIMScheduler(_Scheduler):
     """diffusers DDIMScheduler [3P], eta = 0, clip_sample False, set_alpha_to_one False."""
@@ -232,6 +270,10 @@ class DDIMScheduler(_Scheduler):
             a_p = ac[prev] if prev >= 0 else ac[0]
             tab[i] = [float(t), 1.0, a_t ** 0.5, (1 - a_t) ** 0.5, a_p ** 0.5, (1 - a_p) ** 0.5, 1.0, guidance_scale]
         return tab
+
+    def renoise_table(self) -> np.ndarray:
+        a = self.alphas_cumprod.numpy().astype(np.float32)[np.asarray(self.timesteps_np, dtype=np.int64)]
+        return self._renoise_rows(a ** 0.5, (1 - a) ** 0.5)                    # diffusers `add_noise` [3P]
 
 
 # DPM-Solver++ / Euler Ancestral: diffusers' own constructor defaults (linear betas: NOT the SDXL schedule, so a bare config
@@ -337,12 +379,24 @@ class DPMSolverMultistepScheduler(_Scheduler):
             row[6] = 0.5 * b if self.config.solver_type == "midpoint" else -(alpha_t * ((torch.exp(-h) - 1.0) / h + 1.0))
         return np.array([float(v) for v in row], dtype=np.float32)
 
-    def solver_table(self) -> np.ndarray:
-        """fp32 [n_steps, 8] solver rows {order, sigma_s, alpha_s, a, b, 1/r0, c, 0} (include/diffsensei_hip.h)."""
+    def solver_table(self, start: int = 0) -> np.ndarray:
+        """fp32 [n_steps - start, 8] solver rows {order, sigma_s, alpha_s, a, b, 1/r0, c, 0} (include/diffsensei_hip.h)
+        of a run that begins at step `start` (region redraw with strength < 1): its first row is first order - there is
+        no previous x0 yet - and the later ones are the rows of the whole schedule."""
         if self.num_inference_steps is None:
             raise RuntimeError("call set_timesteps first")
-        orders = self.step_orders()
-        return np.stack([self._solver_row(i, int(o)) for i, o in enumerate(orders)])
+        n = self.num_inference_steps
+        if not 0 <= int(start) < n:
+            raise ValueError(f"solver_table: start {start} outside the {n} steps")
+        if start == 0:
+            orders = self.step_orders()
+        else:
+            orders = [self._order(i, min(i - start, self.config.solver_order)) for i in range(start, n)]
+        return np.stack([self._solver_row(start + k, int(o)) for k, o in enumerate(orders)])
+
+    def renoise_table(self) -> np.ndarray:
+        alpha = 1 / ((self.sigmas ** 2 + 1) ** 0.5)                              # the arithmetic of `_solver_row`
+        return self._renoise_rows(alpha.numpy(), (self.sigmas * alpha).numpy())
 
     def coef_table(self, guidance_scale: float) -> np.ndarray:
         return self._coef_frame(guidance_scale)
@@ -428,6 +482,10 @@ class EulerAncestralDiscreteScheduler(_Scheduler):
             up, down = self.sigma_up_down(i)
             tab[i, 3], tab[i, 4] = float(down), float(up)
         return tab
+
+    def renoise_table(self) -> np.ndarray:
+        sig = self.sigmas.numpy()
+        return self._renoise_rows(np.ones_like(sig), sig)                       # x0 + sigma_i * noise
 
     # -- stand-alone protocol
     def _step_extras(self, i: int, lat: torch.Tensor, generator) -> dict:

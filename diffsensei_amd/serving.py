@@ -10,8 +10,9 @@ Here the same idea is applied to inference, because one UNet launch plan / hipGr
     tickets = [batcher.submit(**request_kwargs) for ...]      # the keyword arguments of DiffSenseiPipeline.__call__
     results = batcher.run(output_type="pil")                   # results[ticket] = that request's images
 
-Requests that share (height, width, steps, guidance_scale, ip_scale) are concatenated into one UNet batch of at most
-`max_panels` panels (`DiffSenseiPipeline.generate_batch`: per-request prompts, character references, boxes, seeds);
+Requests that share (height, width, steps, guidance_scale, ip_scale) - and, for region-redraw requests
+(`redraw_latents`), `strength`; a redraw never shares a batch with a plain request - are concatenated into one UNet batch
+of at most `max_panels` panels (`DiffSenseiPipeline.generate_batch`: per-request prompts, character references, boxes, seeds);
 buckets run largest-resolution first.
 
 `mix_scales=True` (`bucket_key`, `plan_batches`, `BucketBatcher`) drops the two sliders from that key: guidance and IP
@@ -46,13 +47,16 @@ def bucket_key(request: dict, mix_scales: bool = False) -> Tuple:
     guidance values lie on both sides of 1 fits no batch and is a ValueError here, so that it cannot take the requests
     bucketed with it down (`BucketBatcher.submit` checks every request this way)."""
     g = _scale_key(request.get("guidance_scale", 5.0))
+    # a region-redraw request (`redraw_latents`) runs a shortened schedule with another step kernel: it shares a batch
+    # only with redraws of the same strength.  A plain request's key is what it was.
+    redraw = () if request.get("redraw_latents") is None else (("redraw", float(request.get("strength", 1.0))),)
     if mix_scales:
         on = {x > 1 for x in (g if isinstance(g, tuple) else (g,))}
         if len(on) != 1:
             raise ValueError(f"guidance_scale {list(g)} mixes classifier-free guidance on (> 1) and off (<= 1) in one request")
-        return (request.get("height"), request.get("width"), request.get("num_inference_steps", 40), on.pop())
+        return (request.get("height"), request.get("width"), request.get("num_inference_steps", 40), on.pop()) + redraw
     return (request.get("height"), request.get("width"), request.get("num_inference_steps", 40), g,
-            _scale_key(request.get("ip_scale", 1.0)))
+            _scale_key(request.get("ip_scale", 1.0))) + redraw
 
 
 def plan_batches(requests: List[dict], max_panels: int, max_pixels: Optional[int] = None,

@@ -353,6 +353,38 @@ int ds_cfg_sampler_step_noise_f16(const void* eps, void* latents, void* model_in
 int ds_cfg_sampler_step_panels_f16(const void* eps, void* latents, void* model_in, const float* table,
                                    const float* guidance, const float* solver, void* prev_x0, const int64_t* seeds,
                                    const int32_t* step_ctr, int ns, int HW, int kind, int do_cfg, void* stream);
+/* Region redraw: masked, strength-based sampling from kept latents.  The step of ds_cfg_sampler_step_panels_f16 (all its
+ * arguments, same meaning) followed, in the same launch, by the blend of diffusers' 4-channel inpainting loop [3P]: the
+ * kept region is reset to the original latents re-noised to the noise level of the state the step produced.
+ * `redraw`: ONE device buffer, 16-byte aligned, ds_redraw_buffer_bytes(ns, HW) bytes, offsets from ns and HW alone:
+ *   x0k    fp16 NCHW [ns,4,HW]   the kept latents (the final latents of an earlier run)          at byte 0
+ *   noise  fp16 NCHW [ns,4,HW]   the fixed start noise, unit variance                            at byte 8*ns*HW
+ *   mask   fp16 [ns,HW]          one value per panel and pixel in [0, 1]; 1 = repaint            at byte 16*ns*HW
+ *   (pad to the next multiple of 16 bytes: F = (18*ns*HW + 15) & ~15)
+ *   header fp32 [4]              {full strength (0 | 1), init_noise_sigma, 0, 0}                 at byte F
+ *   rows   fp32 [1025][2]        the renoise table, row r = {ka, kb} of STATE r                  at byte F + 16
+ * Renoise table: state r is what enters step r of the run (r = 0: the start) and state n_run is the result; a kept
+ * latent at the noise level of state r is ka * x0k + kb * noise:
+ *   Euler, Euler Ancestral  {1, sigma_r}                     DDIM  {sqrt(a_r), sqrt(1 - a_r)}
+ *   DPM-Solver++            {alpha_r, sigma_r * alpha_r}, alpha = 1 / sqrt(sigma^2 + 1)      final state, every kind  {1, 0}
+ * The table does not depend on `kind` inside the kernel.  A run that starts mid-schedule (strength < 1) loads the rows
+ * of its own states: row 0 is its start state, and step_ctr counts from 0 (kind 3 therefore draws its Philox noise for
+ * the run-relative step).  Per pixel (one thread, 4 channels), with m = mask[n][pix], xn the step's result in fp32:
+ *   m == 1:  latent = fp16(xn)                              bit for bit the call above; x0k / noise are not read
+ *   else     known  = fp16(ka * x0k + kb * noise)           fp32 arithmetic (one contraction), {ka, kb} = row *step_ctr + 1
+ *   m == 0:  latent = known                                 on the last row {1, 0}: x0k bit for bit
+ *   else     latent = fp16(m * fp16(xn) + (1 - m) * known)  fp32 arithmetic
+ * prev_x0 (kind 2) receives the step's own x0, before the blend; model_in is formed from the blended latent for both
+ * CFG halves.  The mask's range is the caller's to check (no kernel reads it twice); a NULL `redraw` is refused. */
+int ds_cfg_sampler_step_redraw_f16(const void* eps, void* latents, void* model_in, const float* table,
+                                   const float* guidance, const float* solver, void* prev_x0, const int64_t* seeds,
+                                   const void* redraw, const int32_t* step_ctr, int ns, int HW, int kind, int do_cfg,
+                                   void* stream);
+int64_t ds_redraw_buffer_bytes(int ns, int HW);
+/* The state a redraw run starts from, out of the same buffer: latents[ns,4,HW] = fp16(ka0 * x0k + kb0 * noise) with
+ * {ka0, kb0} = renoise row 0 (fp32, one rounding); with the header's full-strength flag set, fp16(noise *
+ * init_noise_sigma) instead - the product a plain run starts from, so strength 1 with an all-ones mask IS the plain run. */
+int ds_redraw_start_f16(const void* redraw, void* latents, int ns, int HW, void* stream);
 int ds_prepare_model_input_f16(const void* latents, void* model_in, const float* table, const int32_t* step_ctr,
                                int ns, int HW, int do_cfg, void* stream);
 int ds_nhwc_to_nchw_f16(const void* x, void* y, int B, int HW, int C, void* stream);
@@ -484,7 +516,9 @@ enum ds_opcode {
     DS_OP_ADD_TIME_IDS = 11, /* p: text_embeds, time_ids, out             i: B pooled n_ids dim flip  f: freq_shift */
     DS_OP_SAMPLER_STEP = 12, /* p: eps, latents, model_in, table, ctr, prev_x0, solver (these two: kind 2 only),
                                    seeds (kind 3 only), guidance (p[8]: fp32 [ns], one per panel; NULL = column 7 of the table)
-                                i: ns HW kind (0 Euler, 1 DDIM, 2 DPM-Solver++, 3 Euler Ancestral) do_cfg */
+                                   p[9]: the region-redraw buffer (ds_cfg_sampler_step_redraw_f16), read when i[4] = 1
+                                i: ns HW kind (0 Euler, 1 DDIM, 2 DPM-Solver++, 3 Euler Ancestral) do_cfg redraw (i[4]: 0 | 1;
+                                   1 without p[9] fails the launch) */
     DS_OP_PREP_INPUT = 13,   /* p: latents, model_in, table, ctr          i: ns HW do_cfg */
     DS_OP_ADVANCE = 14,      /* p: ctr */
     DS_OP_NHWC2NCHW = 15,    /* p: x, y                                   i: B HW C */
@@ -504,7 +538,8 @@ enum ds_opcode {
     DS_OP_LLM_ATTN_SLOTS = 29,    /* as DS_OP_LLM_ATTN with i[0] = slots and l[3] = slot_stride (ds_llm_attn_slots_f16) */
     DS_OP_LLM_RMSNORM_SLOTS = 30, /* p: x, gamma, y, feat, state l: ldx ldy     i: slots H max_out       f: eps */
     DS_OP_LLM_EMBED_SLOTS = 31,   /* p: table, state, out        l: ldo         i: slots H vocab */
-    DS_OP_LLM_SELECT_SLOTS = 32   /* p: logits, chain, state, out_ids  l: ldl   i: V n_chain out_cap adv slots */
+    DS_OP_LLM_SELECT_SLOTS = 32,  /* p: logits, chain, state, out_ids  l: ldl   i: V n_chain out_cap adv slots */
+    DS_OP_REDRAW_START = 33       /* p: redraw buffer, latents                  i: ns HW   (ds_redraw_start_f16) */
 };
 
 typedef struct ds_op {
