@@ -18,14 +18,9 @@ def _h(shape, g, scale=1.0):
 
 def _ref_attention_row(q, k, v, theta=10000.0):
     """fp32: the last of T rows attends to rows 0..T-1 (rotate_half rotary); q [heads,D], k/v [T,heads,D]."""
-    from oracle import llama_ref as R
-    T, Hh, D = k.shape
-    cos, sin = R.rope_tables(D, T, theta)
-    kr = R.apply_rope(k.float(), cos, sin).half().float()                       # the cache holds fp16 rotated keys
-    qr = R.apply_rope(q.float()[None], cos[T - 1:T], sin[T - 1:T])[0]
-    s = torch.einsum("hd,shd->hs", qr, kr) / math.sqrt(D)
-    p = s.softmax(-1).half().float()
-    return torch.einsum("hs,shd->hd", p, v.float()).reshape(Hh * D), kr
+    from tests._llm_attn_ref import causal_attention_ref
+    out, kr = causal_attention_ref(q[None], k, v, k.shape[0] - 1, theta=theta)
+    return out[0], kr
 
 
 @pytest.mark.parametrize("D,heads,kv_heads", [(128, 3, 3), (64, 4, 2)])

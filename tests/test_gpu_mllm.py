@@ -71,15 +71,9 @@ def test_llm_gemv_swiglu(hip_lib, M, N, K):
 
 def _ref_attention(q, k, v, pos_q, theta=10000.0):
     """fp32: rotary (rotate_half form) + causal softmax attention; q/k/v [T, heads, D]; keys at positions 0..T-1."""
-    from oracle import llama_ref as R
-    T, Hh, D = k.shape
-    cos, sin = R.rope_tables(D, T, theta)
-    kr = R.apply_rope(k.float(), cos, sin).half().float()                       # the cache holds fp16 rotated keys
-    qr = R.apply_rope(q.float(), cos[pos_q], sin[pos_q])
-    s = torch.einsum("thd,shd->hts", qr, kr) / math.sqrt(D)
-    keep = torch.arange(T)[None, :] <= pos_q[:, None]
-    p = s.masked_fill(~keep[None], float("-inf")).softmax(-1).half().float()
-    return torch.einsum("hts,shd->thd", p, v.float()).reshape(len(pos_q), Hh * D), kr
+    from tests._llm_attn_ref import causal_attention_ref
+    assert pos_q.tolist() == list(range(k.shape[0]))
+    return causal_attention_ref(q, k, v, 0, theta=theta)
 
 
 @pytest.mark.parametrize("D,heads,kv_heads", [(128, 3, 3), (64, 4, 2)])
