@@ -62,6 +62,13 @@ SIGNATURES = {
     "ds_wide_attn_f16": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, vp]),
     "ds_vae_conv_in_f16": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp]),
     "ds_vae_conv_out_f16": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "ds_conv3x3_down_f16": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "ds_conv3x3_down_bf16": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "ds_vae_enc_conv_in_f16": (i32, [vp, i32, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "ds_vae_enc_conv_in_bf16": (i32, [vp, i32, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "ds_vae_enc_conv_out_f16": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "ds_vae_enc_conv_out_bf16": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "ds_vae_latents_f16": (i32, [vp, vp, C.POINTER(f32), C.POINTER(f32), vp, i32, i32, vp]),
     "ds_groupnorm_workspace_bytes": (sz, [i32, i32]),
     "ds_groupnorm_f16": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp]),
     "ds_layernorm_f16": (i32, [vp, vp, vp, vp, i32, i32, f32, vp]),

@@ -328,6 +328,58 @@ int ds_vae_conv_out_f16(const void* x, const void* w, const void* bias, float* i
     return ds_launch_vae_conv_out(x, w, bias, image, B, H_, W_, C, denormalize, DS_DTYPE_F16, S(stream));
 }
 
+// ---- VAE encoder (diffsensei_amd/vae.py VaeEncoderEngine)
+static int conv3x3_down_impl(const void* x, const void* w, const void* bias, void* y, int B, int H_, int W_, int Cin, int Cout,
+                             int dtype, hipStream_t stream) {
+    DS_REQUIRE(B > 0 && H_ >= 2 && W_ >= 2, "conv3x3_down: B (%d) > 0 and H, W (%d, %d) >= 2 are needed", B, H_, W_);
+    GemmParams p;
+    p.conv = 1;
+    p.A = H(x); p.W = H(w); p.ldw = 9L * Cin; p.bias = H(bias); p.C = HM(y); p.ldc = Cout;
+    p.Hin = H_; p.Win = W_; p.Cin = Cin; p.cstride = 2; p.pad_lo = 0;
+    p.Hout = H_ / 2; p.Wout = W_ / 2;
+    DS_REQUIRE((long)B * H_ * W_ * Cin <= 2147483647L, "conv3x3_down: the input (%d x %d x %d x %d) exceeds 32-bit element offsets", B, H_, W_, Cin);
+    p.M = B * p.Hout * p.Wout; p.N = Cout; p.K = 9 * Cin; p.K1 = p.K;
+    p.rows_per_group = p.Hout * p.Wout;
+    p.dtype = dtype;
+    return ds_launch_gemm(p, 1, stream);
+}
+
+int ds_conv3x3_down_f16(const void* x, const void* w, const void* bias, void* y, int B, int H_, int W_, int Cin, int Cout,
+                        void* stream) {
+    return conv3x3_down_impl(x, w, bias, y, B, H_, W_, Cin, Cout, DS_DTYPE_F16, S(stream));
+}
+
+int ds_conv3x3_down_bf16(const void* x, const void* w, const void* bias, void* y, int B, int H_, int W_, int Cin, int Cout,
+                         void* stream) {
+    return conv3x3_down_impl(x, w, bias, y, B, H_, W_, Cin, Cout, DS_DTYPE_BF16, S(stream));
+}
+
+int ds_vae_enc_conv_in_f16(const void* image, int image_is_u8, const void* w, const void* bias, void* y, int B, int H_, int W_,
+                           int C, void* stream) {
+    return ds_launch_vae_enc_conv_in(image, image_is_u8, w, bias, y, B, H_, W_, C, DS_DTYPE_F16, S(stream));
+}
+
+int ds_vae_enc_conv_in_bf16(const void* image, int image_is_u8, const void* w, const void* bias, void* y, int B, int H_, int W_,
+                            int C, void* stream) {
+    return ds_launch_vae_enc_conv_in(image, image_is_u8, w, bias, y, B, H_, W_, C, DS_DTYPE_BF16, S(stream));
+}
+
+int ds_vae_enc_conv_out_f16(const void* x, const void* w, const float* bias, float* moments, int B, int H_, int W_, int C,
+                            void* stream) {
+    return ds_launch_vae_enc_conv_out(x, w, bias, moments, B, H_, W_, C, DS_DTYPE_F16, S(stream));
+}
+
+int ds_vae_enc_conv_out_bf16(const void* x, const void* w, const float* bias, float* moments, int B, int H_, int W_, int C,
+                             void* stream) {
+    return ds_launch_vae_enc_conv_out(x, w, bias, moments, B, H_, W_, C, DS_DTYPE_BF16, S(stream));
+}
+
+int ds_vae_latents_f16(const float* moments, const int64_t* seeds, const float* shift4, const float* scale4, void* latents,
+                       int B, int HW, void* stream) {
+    return ds_launch_vae_latents(moments, reinterpret_cast<const long long*>(seeds), shift4, scale4, HM(latents), B, HW,
+                                 S(stream));
+}
+
 size_t ds_groupnorm_workspace_bytes(int B, int C) { return ds_groupnorm_ws_floats(B, C) * sizeof(float); }
 
 int ds_groupnorm_f16(const void* x1, const void* x2, void* y, const void* gamma, const void* beta, void* ws, int B,

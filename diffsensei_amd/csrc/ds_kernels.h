@@ -52,6 +52,9 @@ struct GemmParams {
                                        //   launch requires it to equal ds_conv_halo_gn_chunks of the kernel it picks (0: not stated)
     int dtype = DS_DTYPE_F16;  // element type of A / W / C / bias / residual (the pointers are 2-byte opaque): bf16 = VAE path
     int debug = 0;  // ablation only (ds_set_option "gemm_debug"): 1 skip MFMA, 2 skip tile loads — results are garbage
+    int pad_lo = 1;  // conv: zero padding on the top / left side.  0 (with cstride 2): diffusers' Downsample2D(padding=0), F.pad(x, (0,1,0,1)) +
+                     //   stride 2 - output (Y, X) reads rows 2Y + ky, columns 2X + kx, Hout = Hin / 2 (ds_conv3x3_down_f16 / _bf16).
+                     //   Host dispatch only (a template argument of the kernels); last, so that no other field moves
 };
 int ds_launch_gemm(const GemmParams& p, int batch, hipStream_t stream);
 int ds_gemm_conv_gn_chunks(const GemmParams& p);  // gemm.hip: GroupNorm partial chunks per image the conv dispatch would emit (0: none)
@@ -92,6 +95,13 @@ int ds_launch_vae_conv_in(const float* lat, const float* wpq, const float* bpq, 
                           int B, int H, int W, int C, float scaling_factor, int dtype, hipStream_t stream);
 int ds_launch_vae_conv_out(const void* x, const void* w, const void* bias, float* img, int B, int H, int W, int C,
                            int denorm, int dtype, hipStream_t stream);
+// ---- VAE encoder only (vae.hip) ---------------------------------------------------------------------
+int ds_launch_vae_enc_conv_in(const void* img, int is_u8, const void* w, const void* bias, void* y, int B, int H, int W,
+                              int C, int dtype, hipStream_t stream);   // img: uint8 NHWC [B,H,W,3] or fp32 NCHW [B,3,H,W] in [-1, 1]
+int ds_launch_vae_enc_conv_out(const void* x, const void* w, const float* bias, float* moments, int B, int H, int W, int C,
+                               int dtype, hipStream_t stream);         // w [8,3,3,C] (quant_conv folded in), bias fp32 [8]
+int ds_launch_vae_latents(const float* moments, const long long* seeds, const float* shift4, const float* scale4,
+                          half_t* out, int B, int HW, hipStream_t stream);   // shift4 / scale4: HOST floats (shift4 may be null)
 
 // ---- normalisation ---------------------------------------------------------------------------------
 struct GroupNormParams {

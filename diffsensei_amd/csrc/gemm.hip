@@ -41,29 +41,29 @@ __device__ __attribute__((aligned(256))) char g_zero_page[256];  // zero-initial
 __device__ __forceinline__ int swz(int row, int chunk) { return ((chunk ^ ((row >> 1) & 7)) << 4); }
 
 // ---------------------------------------------------------------------------------------------- MFMA over one k-tile
-template <int WR, int WC = 64>  // rows / columns of the block tile owned by one wave (32 * MI, 32 * NI)
+template <int WR, int WC = 64, typename T = half_t>  // rows / columns of the block tile owned by one wave (32 * MI, 32 * NI); element type
 __device__ __forceinline__ void mma_tile(const char* cA, const char* cB, f32x16 (&acc)[WR / 32][WC / 32], int wm,
                                          int wn, int l31, int lhi) {
     constexpr int MI = WR / 32, NI = WC / 32;
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
-        h8 af[MI], bf[NI];
+        typename Elt<T>::v8 af[MI], bf[NI];
         const int ch = kk * 2 + lhi;
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) {
             const int r = wm * WR + mi * 32 + l31;
-            af[mi] = *reinterpret_cast<const h8*>(cA + r * 128 + swz(r, ch));
+            af[mi] = *reinterpret_cast<const typename Elt<T>::v8*>(cA + r * 128 + swz(r, ch));
         }
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) {
             const int r = wn * WC + ni * 32 + l31;
-            bf[ni] = *reinterpret_cast<const h8*>(cB + r * 128 + swz(r, ch));
+            bf[ni] = *reinterpret_cast<const typename Elt<T>::v8*>(cB + r * 128 + swz(r, ch));
         }
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
             for (int ni = 0; ni < NI; ++ni)
-                acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf[ni], af[mi], acc[mi][ni], 0, 0, 0);
+                acc[mi][ni] = Elt<T>::mfma(bf[ni], af[mi], acc[mi][ni]);
     }
 }
 
@@ -362,7 +362,10 @@ __device__ __forceinline__ void epilogue(const GemmParams& p, f32x16 (&acc)[WR /
 // one-buffer kernel spends every k-tile waiting out the full L2/HBM latency.  Equal to the one-buffer kernel when the
 // operands are MALL-hot (profiles/r02_small_batch_gemm_ab.txt), 6 % faster per launch inside the sampler where every weight
 // is read cold from HBM (31.2 vs 33.3 us, +4.8 % panels/s at num_samples 1: profiles/r02_ring_in_pipeline_ab.txt).
-template <int BM, bool CONV, int STAGES = 2>
+// PAD: low-side zero padding of the convolution gather (rows / columns < 0 read as zero; the high side is bounded by the
+// input size either way).  1 = the symmetric pad of every UNet convolution; 0 = diffusers' Downsample2D(padding=0) of the VAE
+// encoder, F.pad(x, (0,1,0,1)) + a stride-2 convolution: output (Y, X) reads rows 2Y + ky, columns 2X + kx (GemmParams::pad_lo).
+template <int BM, bool CONV, int STAGES = 2, int PAD = 1>
 __global__ __launch_bounds__(256, (BM > 128 ? 1 : (STAGES >= 4 ? 1 : (STAGES == 1 ? (BM == 64 ? 4 : 3) : 2)))) void gemm_glds_kernel(const GemmParams p) {
     constexpr int MI = BM / 64;
     constexpr int ASEG = BM / 32;  // 1-KiB (8-row) A segments per wave per k-tile
@@ -434,8 +437,8 @@ __global__ __launch_bounds__(256, (BM > 128 ? 1 : (STAGES >= 4 ? 1 : (STAGES == 
                     iy = nearest_src(uy, p.up_sy, p.Hin);
                     ix = nearest_src(ux, p.up_sx, p.Win);
                 } else {
-                    iy = a_oy[j] * p.cstride + ky - 1;
-                    ix = a_ox[j] * p.cstride + kx - 1;
+                    iy = a_oy[j] * p.cstride + ky - PAD;
+                    ix = a_ox[j] * p.cstride + kx - PAD;
                     ok = (iy >= 0) & (iy < p.Hin) & (ix >= 0) & (ix < p.Win);
                 }
                 const long off = ((long)a_pb[j] + (long)iy * p.Win + ix) * p.Cin + ci0 + a_ch[j];
@@ -589,7 +592,32 @@ __global__ __launch_bounds__(256, (BM > 128 ? 1 : (STAGES >= 4 ? 1 : (STAGES == 
 }
 
 // ---------------------------------------------------------------------------------------------- register staging
-template <int BM, bool CONV>
+// T != half_t (bf16: the VAE encoder's downsample in its bf16 mode) runs the same gather and main loop with the bf16 MFMA and
+// the plain store below in place of the f16 epilogue.
+template <int BM, int WR, typename T>
+__device__ __forceinline__ void epilogue_plain(const GemmParams& p, f32x16 (&acc)[WR / 32][2], int m0, int n0, int wm, int wn,
+                                               int l31, int lhi) {
+    typedef typename Elt<T>::v4 V4;
+    T* Cg = reinterpret_cast<T*>(p.C);
+    const T* bias = reinterpret_cast<const T*>(p.bias);
+#pragma unroll
+    for (int mi = 0; mi < WR / 32; ++mi) {
+        const int m = m0 + wm * WR + mi * 32 + l31;
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int n = n0 + wn * 64 + ni * 32 + 8 * g + 4 * lhi;   // N % 8 == 0: n < N covers n + 3
+                if (m >= p.M || n >= p.N) continue;
+                V4 o;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = (T)(acc[mi][ni][4 * g + e] + (bias ? (float)bias[n + e] : 0.f));
+                *reinterpret_cast<V4*>(Cg + (long)m * p.ldc + n) = o;
+            }
+    }
+}
+
+template <int BM, bool CONV, int PAD = 1, typename T = half_t>
 __global__ __launch_bounds__(256, 2) void gemm_f16_kernel(const GemmParams p) {
     constexpr int MI = BM / 64;   // 32-row fragments per wave along M
     constexpr int ACH = BM / 32;  // 16-byte A chunks per thread per k-tile
@@ -662,8 +690,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_kernel(const GemmParams p) {
                     iy = nearest_src(uy, p.up_sy, p.Hin);
                     ix = nearest_src(ux, p.up_sx, p.Win);
                 } else {
-                    iy = a_oy[j] * p.cstride + ky - 1;
-                    ix = a_ox[j] * p.cstride + kx - 1;
+                    iy = a_oy[j] * p.cstride + ky - PAD;
+                    ix = a_ox[j] * p.cstride + kx - PAD;
                     ok = (iy >= 0) & (iy < p.Hin) & (ix >= 0) & (ix < p.Win);
                 }
                 ok = ok & a_ok[j] & k_ok;
@@ -712,11 +740,14 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_kernel(const GemmParams p) {
     for (int kt = 0; kt < nk; ++kt) {
         const int buf = kt & 1;
         if (kt + 1 < nk) load_tile(kt + 1);
-        mma_tile<BM / 2>(sA + buf * BM * 128, sB + buf * BN * 128, acc, wm, wn, l31, lhi);
+        mma_tile<BM / 2, 64, T>(sA + buf * BM * 128, sB + buf * BN * 128, acc, wm, wn, l31, lhi);
         if (kt + 1 < nk) store_tile(buf ^ 1);
         __syncthreads();
     }
-    epilogue<BM, BM / 2, 256>(p, acc, smem, m0, n0, bz, wm, wn, l31, lhi, tid);
+    if constexpr (sizeof(T) == 2 && __is_same(T, half_t))
+        epilogue<BM, BM / 2, 256>(p, acc, smem, m0, n0, bz, wm, wn, l31, lhi, tid);
+    else
+        epilogue_plain<BM, BM / 2, T>(p, acc, m0, n0, wm, wn, l31, lhi);
 }
 
 template <int BM, bool CONV, bool GLDS>
@@ -737,14 +768,33 @@ int launch(const GemmParams& p0, int batch, hipStream_t stream) {
     return 0;
 }
 
-template <int BM, bool CONV>
+template <int BM, bool CONV, int PAD = 1>
 int launch_glds1(const GemmParams& p0, int batch, hipStream_t stream) {
     GemmParams p = p0;
     p.tiles_m = (p.M + BM - 1) / BM;
     p.tiles_n = (p.N + BN - 1) / BN;
     const size_t lds = 128 * CS_STRIDE + 1024;  // >= (BM + BN) * 128: the epilogue staging tile is the larger tenant (+ the column statistics of the fused LayerNorm's operand-swapped form)
     dim3 grid(p.tiles_m * p.tiles_n, 1, batch);
-    hipLaunchKernelGGL((gemm_glds_kernel<BM, CONV, 1>), grid, dim3(256), lds, stream, p);
+    hipLaunchKernelGGL((gemm_glds_kernel<BM, CONV, 1, PAD>), grid, dim3(256), lds, stream, p);
+    DS_LAUNCH_CHECK();
+    return 0;
+}
+
+// the VAE encoder's downsample in bf16 storage: register-staged gather (the LDS-DMA kernels and their epilogue are f16 only)
+int launch_down_bf16(const GemmParams& p0, hipStream_t stream) {
+    constexpr int BM = 64;
+    GemmParams p = p0;
+    p.tiles_m = (p.M + BM - 1) / BM;
+    p.tiles_n = (p.N + BN - 1) / BN;
+    const size_t lds = 2 * BM * 128 + 2 * BN * 128;
+    auto kern = gemm_f16_kernel<BM, true, 0, bf16_t>;
+    static unsigned long long attr_devs = 0;
+    if (ds_first_on_device(attr_devs)) {
+        DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)lds));
+    }
+    dim3 grid(p.tiles_m * p.tiles_n, 1, 1);
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, p);
     DS_LAUNCH_CHECK();
     return 0;
 }
@@ -903,6 +953,7 @@ const char* ds_gemm_kernel_name(const GemmParams& p, int batch) {
     // the fused-LayerNorm instantiations of gemm_pp_kernel are kernels of their own in a rocprofv3 trace (template argument FUSE)
     if (p.ln_stats && !p.ln_partial) return p.ln_swapped ? "gemm_pp_kernel<0,4>" : p.epi == EPI_GEGLU ? "gemm_pp_kernel<0,9>" : "gemm_pp_kernel<0,1>";
     if (p.stats_out && ds_gemm_ln_kind(p.M, p.N, p.K, batch, p.epi) == 1) return "gemm_pp_kernel<0,2>";
+    if (p.conv && p.pad_lo == 0) return p.dtype == DS_DTYPE_F16 ? "gemm_glds_kernel<64,true,1,0>" : "gemm_f16_kernel<64,true,0,bf16>";
     Choice c = choose(p, batch);
     const bool conv = p.conv != 0;
     if (conv && p.up_fold) c.kind = K_HALO;   // folded phase weights: the halo-patch kernels are the only readers of that layout
@@ -949,6 +1000,17 @@ int ds_launch_gemm(const GemmParams& p_in, int batch, hipStream_t stream) {
     if (p.epi == EPI_GEGLU320) {   // W packed in 320-row groups (engine.pack_geglu320): one kernel reads that layout
         DS_REQUIRE(ds_gemm_g320_possible(p, batch), "geglu320: plain f16 GEMM, batch 1, N %% 320 == 0, K %% 64 == 0, no residual (M=%d N=%d K=%d)", p.M, p.N, p.K);
         return ds_launch_gemm_g320(p, stream);
+    }
+    if (conv && p.pad_lo != 1) {
+        // Downsample2D(padding=0) of the VAE encoder: one instantiation per storage type, no A/B families (gemm_glds_kernel<.., PAD>)
+        DS_REQUIRE(p.pad_lo == 0 && p.cstride == 2 && !p.upsample && !p.rowbias && !p.gn_partial && p.epi == EPI_NONE &&
+                       !p.ln_stats && !p.ln_c && !p.stats_out,
+                   "conv3x3: pad_lo = %d serves the plain stride-2 convolution with padding (0,1,0,1) only", p.pad_lo);
+        DS_REQUIRE(p.Hout == p.Hin / 2 && p.Wout == p.Win / 2 && p.Hout > 0 && p.Wout > 0,
+                   "conv3x3 down: output %d x %d is not floor(%d / 2) x floor(%d / 2)", p.Hout, p.Wout, p.Hin, p.Win);
+        if (p.dtype == DS_DTYPE_F16) return launch_glds1<64, true, 0>(p, 1, stream);
+        DS_REQUIRE(!p.residual, "conv3x3 down bf16: no residual");
+        return launch_down_bf16(p, stream);
     }
     Choice c = choose(p, batch);
     if (conv && p.up_fold) {   // folded phase weights [4][N][4 Cin]: only the halo-patch kernels read that layout, whatever A/B knob is set

@@ -12,8 +12,17 @@
 //                       reduction and no score matrix in HBM (it would be 1 GB per image in fp32).
 //   vae_conv_in_kernel  post_quant_conv (1x1, 4 -> 4) + 1/scaling_factor + conv_in (3x3, 4 -> C) on the fp32 NCHW latents
 //   vae_conv_out_kernel conv_out (3x3, C -> 3) of the normalised activations -> fp32 NCHW image
+//
+// and for the encoder (diffusers AutoencoderKL.encode [3P]: what turns a picture into the latents region redraw keeps) the
+// three ops at its two ends - everything between them is the decoder's kernels, plus the pad-(0,1,0,1) stride-2 mode of the
+// gather kernels in gemm.hip:
+//   vae_enc_conv_in_kernel   2 u / 255 - 1 (uint8 NHWC input) or the fp32 NCHW image as it is, then conv_in (3x3, 3 -> C)
+//   vae_enc_conv_out_kernel  conv_out (3x3, C -> 8) with quant_conv (1x1, 8 -> 8) folded into its weights -> fp32 NCHW
+//                            posterior moments: 4 x mean, 4 x logvar clamped to [-30, 20]
+//   vae_latents_kernel       moments -> the pipeline's fp16 latents: mode or mean + std * Philox normal, shifted and scaled
 #include "ds_common.h"
 #include "ds_kernels.h"
+#include "ds_philox.h"
 
 namespace {
 
@@ -301,6 +310,155 @@ __global__ __launch_bounds__(256) void vae_conv_out_kernel(const T* __restrict__
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Encoder conv_in: 3x3, 3 -> C, pad 1, on the NORMALISED image - a padded tap contributes 0, not -1.  The image is uint8
+// NHWC [B,H,W,3] (what a PIL image is; x = fma(u, 2/255, -1) in fp32) or fp32 NCHW [B,3,H,W] already in [-1, 1].  y NHWC T.
+// The work split of vae_conv_in_kernel: one thread = one pixel x 8 output channels, the 27 C weights (fp32) in LDS.
+// ---------------------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void vae_enc_conv_in_kernel(const void* __restrict__ img, int is_u8,
+                                                              const T* __restrict__ w, const T* __restrict__ bias,
+                                                              T* __restrict__ y, int B, int H, int W, int C,
+                                                              int px_per_block) {
+    typedef typename Elt<T>::v8 V8;
+    extern __shared__ float sw[];  // [C][27] weights (ky, kx, ci) + [C] bias
+    for (int i = threadIdx.x; i < C * 27; i += 256) sw[i] = (float)w[i];
+    for (int i = threadIdx.x; i < C; i += 256) sw[C * 27 + i] = (float)bias[i];
+    __syncthreads();
+    const uint8_t* u8 = static_cast<const uint8_t*>(img);
+    const float* f32 = static_cast<const float*>(img);
+    const int groups = C / 8;
+    const int ppb = 256 / groups;
+    const int cg = threadIdx.x % groups, pl = threadIdx.x / groups;
+    const long plane = (long)H * W, total = (long)B * plane;
+    const long first = (long)blockIdx.x * px_per_block;
+    for (long base = first; base < first + px_per_block && base < total; base += ppb) {
+        const long pix = base + pl;
+        if (pl >= ppb || pix >= total) continue;
+        const int b = (int)(pix / plane);
+        const int rem = (int)(pix - (long)b * plane);
+        const int oy = rem / W, ox = rem - oy * W;
+        float acc[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] = sw[C * 27 + cg * 8 + e];
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) {
+                const int iy = oy + ky - 1, ix = ox + kx - 1;
+                if (iy < 0 || iy >= H || ix < 0 || ix >= W) continue;
+                float v[3];
+                if (is_u8) {
+                    const uint8_t* pp = u8 + ((long)b * plane + (long)iy * W + ix) * 3;
+#pragma unroll
+                    for (int ci = 0; ci < 3; ++ci) v[ci] = fmaf((float)pp[ci], 2.0f / 255.0f, -1.0f);
+                } else {
+#pragma unroll
+                    for (int ci = 0; ci < 3; ++ci) v[ci] = f32[((long)b * 3 + ci) * plane + (long)iy * W + ix];
+                }
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float* wr = sw + (cg * 8 + e) * 27 + (ky * 3 + kx) * 3;
+                    acc[e] += wr[0] * v[0] + wr[1] * v[1] + wr[2] * v[2];
+                }
+            }
+        V8 ov;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) ov[e] = (T)acc[e];
+        *reinterpret_cast<V8*>(y + pix * C + cg * 8) = ov;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Encoder conv_out with quant_conv folded in (vae.fold_quant_conv: W' = Wq Wc, b' = Wq bc + bq, in fp32 at load time):
+// 3x3, C -> 8, NHWC T in, fp32 NCHW moments out - channels 0..3 the posterior mean, 4..7 its logvar clamped to [-30, 20]
+// (diffusers DiagonalGaussianDistribution [3P]).  The lane split of vae_conv_out_kernel with 8 sums instead of 3: lane s of a
+// pixel's eight takes the 16-byte channel chunks s, s + 8, ..., and after the fold over the 8 lanes lane s writes channel s.
+// ---------------------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void vae_enc_conv_out_kernel(const T* __restrict__ x, const T* __restrict__ w,
+                                                               const float* __restrict__ bias, float* __restrict__ mom,
+                                                               int B, int H, int W, int C) {
+    typedef typename Elt<T>::v8 V8;
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    T* sw = reinterpret_cast<T*>(smem_raw);  // [8][9][C]
+    for (int i = threadIdx.x; i < 72 * C / 8; i += 256) reinterpret_cast<V8*>(sw)[i] = reinterpret_cast<const V8*>(w)[i];
+    __syncthreads();
+    const int sub = threadIdx.x & 7;
+    const long plane = (long)H * W, npix = (long)B * plane;
+    const float bsel = bias[sub];
+    for (long pix0 = (long)blockIdx.x * 32; pix0 < npix; pix0 += (long)gridDim.x * 32) {
+        const long pix = pix0 + (threadIdx.x >> 3);
+        const bool live = pix < npix;
+        const long pc = live ? pix : 0;
+        const int b = (int)(pc / plane);
+        const int rem = (int)(pc - (long)b * plane);
+        const int oy = rem / W, ox = rem - oy * W;
+        float acc[8];
+#pragma unroll
+        for (int co = 0; co < 8; ++co) acc[co] = 0.f;
+        for (int tap = 0; tap < 9; ++tap) {
+            const int ky = tap / 3, kx = tap - 3 * ky;
+            const int iy = oy + ky - 1, ix = ox + kx - 1;
+            if (iy < 0 || iy >= H || ix < 0 || ix >= W) continue;
+            const T* xp = x + (((long)b * H + iy) * W + ix) * C;
+            for (int c = sub * 8; c < C; c += 64) {
+                const V8 xv = *reinterpret_cast<const V8*>(xp + c);
+#pragma unroll
+                for (int co = 0; co < 8; ++co) {
+                    const V8 wv = *reinterpret_cast<const V8*>(sw + (co * 9 + tap) * C + c);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) acc[co] = fmaf((float)xv[e], (float)wv[e], acc[co]);
+                }
+            }
+        }
+        float mine = 0.f;
+#pragma unroll
+        for (int co = 0; co < 8; ++co) {
+            acc[co] += __shfl_xor(acc[co], 1, 64);
+            acc[co] += __shfl_xor(acc[co], 2, 64);
+            acc[co] += __shfl_xor(acc[co], 4, 64);
+            if (sub == co) mine = acc[co];
+        }
+        if (live) {
+            float v = mine + bsel;
+            if (sub >= 4) v = fminf(fmaxf(v, -30.0f), 20.0f);
+            mom[((long)b * 8 + sub) * plane + rem] = v;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Posterior moments fp32 [B,8,HW] -> the pipeline's latents fp16 [B,4,HW] (what `redraw_latents` takes).  One thread = one
+// pixel, four channels (the sampler kernel's split, so one Philox call serves the thread):
+//   z = mean                                  (seeds == null: the mode)
+//   z = mean + exp(0.5 logvar) * n            n = the normals of ds_philox.h for (seeds[b], pixel, step 0, stream_id 1)
+//   out = fp16((z - shift[c]) * scale[c])     shift = latents_mean or 0, scale = scaling_factor (/ latents_std), host fp32
+// An image's noise depends on its own seed only, never on its row in the batch.
+// ---------------------------------------------------------------------------------------------------------------
+struct LatentsAffine {
+    float shift[4], scale[4];
+};
+
+__global__ __launch_bounds__(256) void vae_latents_kernel(const float* __restrict__ mom, const long long* __restrict__ seeds,
+                                                          half_t* __restrict__ out, int B, int HW, LatentsAffine aff) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)B * HW) return;
+    const int b = (int)(i / HW), pix = (int)(i - (long)b * HW);
+    const float* mp = mom + (long)b * 8 * HW + pix;
+    float z[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) z[c] = mp[(long)c * HW];
+    if (seeds) {
+        float n[4];
+        panel_normals(seeds[b], pix, 0, 1, n);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) z[c] = fmaf(__expf(0.5f * mp[(long)(4 + c) * HW]), n[c], z[c]);
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) out[((long)b * 4 + c) * HW + pix] = (half_t)((z[c] - aff.shift[c]) * aff.scale[c]);
+}
+
 }  // namespace
 
 int ds_launch_wide_attn(const void* q, const void* k, const void* vt, void* o, int B, int N, int n_valid, int dtype,
@@ -368,6 +526,74 @@ int ds_launch_vae_conv_out(const void* x, const void* w, const void* bias, float
     else
         hipLaunchKernelGGL(vae_conv_out_kernel<half_t>, grid, dim3(256), lds, stream, (const half_t*)x, (const half_t*)w,
                            (const half_t*)bias, img, B, H, W, C, denorm);
+    DS_LAUNCH_CHECK();
+    return 0;
+}
+
+int ds_launch_vae_enc_conv_in(const void* img, int is_u8, const void* w, const void* bias, void* y, int B, int H, int W,
+                              int C, int dtype, hipStream_t stream) {
+    DS_REQUIRE(img && w && bias && y && B > 0 && H > 0 && W > 0, "vae_enc_conv_in: bad arguments");
+    DS_REQUIRE(C >= 8 && C % 8 == 0 && C / 8 <= 256 && 256 % (C / 8) == 0,
+               "vae_enc_conv_in: C (%d) must be 8 x a divisor of 256", C);
+    const size_t lds = (size_t)(C * 27 + C) * sizeof(float);
+    DS_REQUIRE(lds <= 160 * 1024, "vae_enc_conv_in: weights (%zu B) exceed LDS", lds);
+    static unsigned long long attr_devs = 0;
+    if (ds_first_on_device(attr_devs)) {
+        DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(vae_enc_conv_in_kernel<bf16_t>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(vae_enc_conv_in_kernel<half_t>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    }
+    const int ppb = 256 / (C / 8);
+    const int px_per_block = ppb * 16;  // the weight stage-in is amortised over 16 passes
+    const long total = (long)B * H * W;
+    dim3 grid((unsigned)((total + px_per_block - 1) / px_per_block));
+    if (dtype == DS_DTYPE_BF16)
+        hipLaunchKernelGGL(vae_enc_conv_in_kernel<bf16_t>, grid, dim3(256), lds, stream, img, is_u8, (const bf16_t*)w,
+                           (const bf16_t*)bias, (bf16_t*)y, B, H, W, C, px_per_block);
+    else
+        hipLaunchKernelGGL(vae_enc_conv_in_kernel<half_t>, grid, dim3(256), lds, stream, img, is_u8, (const half_t*)w,
+                           (const half_t*)bias, (half_t*)y, B, H, W, C, px_per_block);
+    DS_LAUNCH_CHECK();
+    return 0;
+}
+
+int ds_launch_vae_enc_conv_out(const void* x, const void* w, const float* bias, float* moments, int B, int H, int W, int C,
+                               int dtype, hipStream_t stream) {
+    DS_REQUIRE(x && w && bias && moments && B > 0 && H > 0 && W > 0, "vae_enc_conv_out: bad arguments");
+    DS_REQUIRE(C % 8 == 0 && C > 0, "vae_enc_conv_out: C (%d) must be a multiple of 8", C);
+    const size_t lds = (size_t)72 * C * 2;
+    DS_REQUIRE(lds <= 144 * 1024, "vae_enc_conv_out: weights (%zu B) exceed 144 KiB of LDS", lds);
+    static unsigned long long attr_devs = 0;
+    if (ds_first_on_device(attr_devs)) {
+        DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(vae_enc_conv_out_kernel<bf16_t>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
+        DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(vae_enc_conv_out_kernel<half_t>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
+    }
+    const long groups = ((long)B * H * W + 31) / 32;
+    dim3 grid((unsigned)(groups < 2048 ? groups : 2048));
+    if (dtype == DS_DTYPE_BF16)
+        hipLaunchKernelGGL(vae_enc_conv_out_kernel<bf16_t>, grid, dim3(256), lds, stream, (const bf16_t*)x, (const bf16_t*)w,
+                           bias, moments, B, H, W, C);
+    else
+        hipLaunchKernelGGL(vae_enc_conv_out_kernel<half_t>, grid, dim3(256), lds, stream, (const half_t*)x, (const half_t*)w,
+                           bias, moments, B, H, W, C);
+    DS_LAUNCH_CHECK();
+    return 0;
+}
+
+int ds_launch_vae_latents(const float* moments, const long long* seeds, const float* shift4, const float* scale4,
+                          half_t* out, int B, int HW, hipStream_t stream) {
+    DS_REQUIRE(moments && scale4 && out && B > 0 && HW > 0, "vae_latents: bad arguments");
+    LatentsAffine aff;
+    for (int c = 0; c < 4; ++c) {
+        aff.shift[c] = shift4 ? shift4[c] : 0.f;
+        aff.scale[c] = scale4[c];
+    }
+    const long total = (long)B * HW;
+    hipLaunchKernelGGL(vae_latents_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, moments, seeds, out,
+                       B, HW, aff);
     DS_LAUNCH_CHECK();
     return 0;
 }

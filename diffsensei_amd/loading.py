@@ -86,7 +86,7 @@ def load_vae(folder: str, device):
     cfg = VaeConfig(tuple(c.get("block_out_channels", (128, 256, 512, 512))), int(c.get("layers_per_block", 2)),
                     int(c.get("latent_channels", 4)), int(c.get("out_channels", 3)), int(c.get("norm_num_groups", 32)),
                     float(c.get("scaling_factor", 0.13025)), bool(c.get("force_upcast", True)), c.get("latents_mean"),
-                    c.get("latents_std"))
+                    c.get("latents_std"), in_channels=int(c.get("in_channels", 3)))
     return VaeDecoderEngine.from_state_dict(load_weights(folder), cfg, device)
 
 

@@ -6,7 +6,7 @@ Layouts: activations fp16 channels-last — images [B, H*W, C] (or [B,H,W,C]), t
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import Optional, Sequence, Tuple
 
 import torch
 
@@ -702,6 +702,81 @@ def vae_conv_out(x: Tensor, w: Tensor, bias: Tensor, denormalize: bool = False) 
     fn, name = (L.ds_vae_conv_out_bf16, "ds_vae_conv_out_bf16") if x.dtype == _BF else (L.ds_vae_conv_out_f16, "ds_vae_conv_out_f16")
     check(fn(_p(x), _p(w), _p(bias), _p(img), B, H, W, C, int(denormalize), _stream()), name)
     return img
+
+
+# ---- VAE encoder (vae.py VaeEncoderEngine): the four ops the decoder has no counterpart of
+def conv3x3_down(x: Tensor, w: Tensor, bias: Tensor) -> Tensor:
+    """diffusers' Downsample2D(padding=0): F.pad(x, (0,1,0,1)) + 3x3 conv, stride 2.  x [B,H,W,Cin] NHWC f16 or bf16,
+    w [Cout,3,3,Cin] -> [B,H//2,W//2,Cout]."""
+    _chk(x, w, bias, dtype=x.dtype)
+    B, H, W, Cin = x.shape
+    Cout = w.shape[0]
+    if H < 2 or W < 2 or tuple(w.shape[1:]) != (3, 3, Cin):
+        raise ValueError(f"conv3x3_down: x {tuple(x.shape)}, w {tuple(w.shape)}")
+    y = torch.empty((B, H // 2, W // 2, Cout), dtype=x.dtype, device=x.device)
+    L = _lib.load()
+    fn, name = (L.ds_conv3x3_down_bf16, "ds_conv3x3_down_bf16") if x.dtype == _BF else (L.ds_conv3x3_down_f16, "ds_conv3x3_down_f16")
+    check(fn(_p(x), _p(w), _p(bias), _p(y), B, H, W, Cin, Cout, _stream()), name)
+    return y
+
+
+def vae_enc_conv_in(image: Tensor, w: Tensor, bias: Tensor) -> Tensor:
+    """image: uint8 NHWC [B,H,W,3] (normalised to 2 u / 255 - 1 in the kernel) or fp32 NCHW [B,3,H,W] in [-1, 1];
+    w [C,3,3,3], bias [C] f16 or bf16 -> [B,H,W,C] in that type."""
+    _chk(w, bias, dtype=w.dtype)
+    if image.dtype == torch.uint8:
+        _chk(image, dtype=torch.uint8)
+        if image.dim() != 4 or image.shape[3] != 3:
+            raise ValueError(f"vae_enc_conv_in: uint8 image [B,H,W,3] expected, got {tuple(image.shape)}")
+        B, H, W, _ = image.shape
+    else:
+        _chk(image, dtype=torch.float32)
+        if image.dim() != 4 or image.shape[1] != 3:
+            raise ValueError(f"vae_enc_conv_in: fp32 image [B,3,H,W] expected, got {tuple(image.shape)}")
+        B, _, H, W = image.shape
+    C = w.shape[0]
+    if tuple(w.shape[1:]) != (3, 3, 3):
+        raise ValueError(f"vae_enc_conv_in: w [C,3,3,3] expected, got {tuple(w.shape)}")
+    y = torch.empty((B, H, W, C), dtype=w.dtype, device=image.device)
+    L = _lib.load()
+    fn, name = (L.ds_vae_enc_conv_in_bf16, "ds_vae_enc_conv_in_bf16") if w.dtype == _BF else (L.ds_vae_enc_conv_in_f16, "ds_vae_enc_conv_in_f16")
+    check(fn(_p(image), int(image.dtype == torch.uint8), _p(w), _p(bias), _p(y), B, H, W, C, _stream()), name)
+    return y
+
+
+def vae_enc_conv_out(x: Tensor, w: Tensor, bias: Tensor) -> Tensor:
+    """x [B,H,W,C] f16 or bf16, w [8,3,3,C] same type (quant_conv folded in: vae.fold_quant_conv), bias fp32 [8] ->
+    posterior moments fp32 NCHW [B,8,H,W]: 4 x mean, 4 x logvar clamped to [-30, 20]."""
+    _chk(x, w, dtype=x.dtype)
+    _chk(bias, dtype=torch.float32)
+    B, H, W, C = x.shape
+    if tuple(w.shape) != (8, 3, 3, C) or bias.numel() != 8:
+        raise ValueError(f"vae_enc_conv_out: w [8,3,3,{C}] and bias [8] expected, got {tuple(w.shape)}, {tuple(bias.shape)}")
+    mom = torch.empty((B, 8, H, W), dtype=torch.float32, device=x.device)
+    L = _lib.load()
+    fn, name = (L.ds_vae_enc_conv_out_bf16, "ds_vae_enc_conv_out_bf16") if x.dtype == _BF else (L.ds_vae_enc_conv_out_f16, "ds_vae_enc_conv_out_f16")
+    check(fn(_p(x), _p(w), _p(bias), _p(mom), B, H, W, C, _stream()), name)
+    return mom
+
+
+def vae_latents(moments: Tensor, scale: Sequence[float], shift: Optional[Sequence[float]] = None,
+                seeds: Optional[Tensor] = None) -> Tensor:
+    """moments fp32 [B,8,h,w] -> fp16 latents [B,4,h,w] = fp16((z - shift[c]) * scale[c]); z = mean, or with `seeds` (device
+    int64 [B]) mean + exp(0.5 logvar) * Philox normal (seeds[b], pixel, step 0, stream_id 1).  scale / shift: 4 host floats."""
+    import ctypes
+    _chk(moments, dtype=torch.float32)
+    if moments.dim() != 4 or moments.shape[1] != 8:
+        raise ValueError(f"vae_latents: moments [B,8,h,w] expected, got {tuple(moments.shape)}")
+    B, _, h, w = moments.shape
+    if seeds is not None:
+        _chk_seeds(seeds, B)
+    if len(scale) != 4 or (shift is not None and len(shift) != 4):
+        raise ValueError("vae_latents: scale and shift hold one value per latent channel (4)")
+    sc = (ctypes.c_float * 4)(*[float(v) for v in scale])
+    sh = (ctypes.c_float * 4)(*[float(v) for v in shift]) if shift is not None else None
+    out = torch.empty((B, 4, h, w), dtype=torch.float16, device=moments.device)
+    check(_lib.load().ds_vae_latents_f16(_p(moments), _p(seeds), sh, sc, _p(out), B, h * w, _stream()), "ds_vae_latents_f16")
+    return out
 
 
 # ---- f16 twins used by the decoder's scaled-fp16 mode (vae.py)

@@ -366,6 +366,77 @@ class DiffSenseiPipeline:
             mask = torch.maximum(mask, m[:, 0].expand(num_samples, h, w))
         return {"x0": x0, "mask": mask.contiguous(), "strength": float(strength)}
 
+    # ---- region redraw from a picture: the VAE encoder in front of the `redraw_latents` path
+    @staticmethod
+    def _image_tensor(image) -> Tensor:
+        """A PIL image or a list of them (converted to RGB), a uint8 array / tensor [H,W,3] or [B,H,W,3], or a float tensor
+        [B,3,H,W] in [0, 1] -> what `VaeEncoderEngine.encode` takes, on the host: uint8 [B,H,W,3] or fp32 [B,3,H,W] in
+        [-1, 1].  No resize: a side that is not a multiple of 8 is a ValueError."""
+        import numpy as np
+        if hasattr(image, "convert"):                               # one PIL image
+            image = [image]
+        if isinstance(image, (list, tuple)):
+            if not image or not all(hasattr(im, "convert") for im in image):
+                raise ValueError("`redraw_image`: a list holds PIL images")
+            arrs = [np.asarray(im.convert("RGB")) for im in image]
+            if any(a.shape != arrs[0].shape for a in arrs):
+                raise ValueError(f"`redraw_image`: the images differ in size: {[a.shape[:2] for a in arrs]}")
+            image = np.stack(arrs)
+        if isinstance(image, np.ndarray):
+            image = torch.from_numpy(np.ascontiguousarray(image))
+        if not torch.is_tensor(image):
+            raise ValueError(f"`redraw_image`: a PIL image, a uint8 array or a tensor is needed, got {type(image)}")
+        x = image.detach()
+        if x.dtype == torch.uint8:
+            x = x[None] if x.dim() == 3 else x
+            if x.dim() != 4 or x.shape[3] != 3:
+                raise ValueError(f"`redraw_image`: uint8 pixels are [H,W,3] or [B,H,W,3], got {tuple(image.shape)}")
+            H, W = int(x.shape[1]), int(x.shape[2])
+        elif x.is_floating_point():
+            if x.dim() != 4 or x.shape[1] != 3:
+                raise ValueError(f"`redraw_image`: a float tensor is [B,3,H,W] in [0, 1], got {tuple(image.shape)}")
+            x = x.to("cpu", torch.float32)
+            if not bool(((x >= 0) & (x <= 1)).all()):
+                raise ValueError("`redraw_image`: float pixels have to lie in [0, 1]")
+            x = x * 2.0 - 1.0
+            H, W = int(x.shape[2]), int(x.shape[3])
+        else:
+            raise ValueError(f"`redraw_image`: uint8 or float pixels are needed, got {x.dtype}")
+        if x.shape[0] == 0 or H == 0 or W == 0 or H % 8 or W % 8:
+            raise ValueError(f"`redraw_image`: sides must be multiples of 8 (there is no resize), got {H} x {W}")
+        return x.to("cpu").contiguous()
+
+    def _vae_encoder(self):
+        enc = getattr(self.vae, "encoder", None)
+        if enc is None:
+            raise ValueError("`redraw_image` / `encode_image` need a VAE with encoder weights (`encoder.*` and `quant_conv.*` in "
+                             "its state dict); this one decodes only - pass `redraw_latents` instead")
+        return enc
+
+    def _redraw_image_input(self, redraw_image, redraw_latents, num_samples, height, width) -> Optional[Tensor]:
+        """None without `redraw_image`, else the host tensor `_image_tensor` makes of it.  ValueError - before any encoder
+        runs - when `redraw_latents` is given too, the VAE has no encoder, or the size is not `height` x `width`."""
+        if redraw_image is None:
+            return None
+        if redraw_latents is not None:
+            raise ValueError("`redraw_image` and `redraw_latents` both say what to keep: give one of them")
+        self._vae_encoder()
+        x = self._image_tensor(redraw_image)
+        H, W = (x.shape[1], x.shape[2]) if x.dtype == torch.uint8 else (x.shape[2], x.shape[3])
+        if (H, W) != (int(height), int(width)):
+            raise ValueError(f"`redraw_image` is {H} x {W} (height x width), the call is {int(height)} x {int(width)}: there is no resize")
+        if x.shape[0] not in (1, num_samples):
+            raise ValueError(f"`redraw_image`: 1 or {num_samples} images are needed, got {x.shape[0]}")
+        return x
+
+    @torch.no_grad()
+    def encode_image(self, image, seeds: Optional[Sequence[int]] = None) -> Tensor:
+        """Picture -> the fp16 latents [B,4,H/8,W/8] that `redraw_latents` takes (and `output_type="latent"` returns): the
+        mode of the VAE posterior, scaled like the pipeline's latents, or with `seeds` (one int64 per image) a sample.
+        `image`: see `_image_tensor`."""
+        enc = self._vae_encoder()
+        return enc.encode_latents(self._image_tensor(image), seeds)
+
     def decode_latents(self, latents: Tensor, output_type: str = "pil"):
         """Latents (a call with `output_type="latent"`, which are also what `redraw_latents` takes) -> images, exactly
         as `__call__` post-processes its own."""
@@ -389,7 +460,7 @@ class DiffSenseiPipeline:
                  callback_on_step_end=None, callback_on_step_end_tensor_inputs: Sequence[str] = ("latents",),
                  noise_seeds: Optional[Sequence[int]] = None, redraw_latents: Optional[Tensor] = None,
                  redraw_bbox: Optional[List[List[float]]] = None, redraw_mask: Optional[Tensor] = None,
-                 strength: float = 1.0):
+                 strength: float = 1.0, redraw_image=None, redraw_image_seeds: Optional[Sequence[int]] = None):
         """`callback_on_step_end(pipe, step_index, timestep, {"latents": device tensor}) -> dict | None` is diffusers'
         SDXL-pipeline hook [3P]; together with `pipe._interrupt = True` it is the reference's early exit: the loop
         `continue`s over the remaining steps (reference :314-315) and the call still decodes and post-processes.  Latents
@@ -413,7 +484,10 @@ class DiffSenseiPipeline:
         values allowed), combined by maximum.  `strength` in (0, 1] runs the last int(steps * strength) steps from the
         kept latents noised to that level; 1.0 starts from pure noise.  The noise is the draw of a plain call (or
         `latents=`); the callback gets the run-relative step index and the true timestep;
-        `last_run_info["redraw"]` = {"t_start", "steps_run", "repaint_fraction"}."""
+        `last_run_info["redraw"]` = {"t_start", "steps_run", "repaint_fraction"}.  `redraw_image` (a PIL image or a list, a
+        uint8 array / tensor [H,W,3] or [B,H,W,3], a float tensor [B,3,H,W] in [0, 1]; exactly `height` x `width`, no resize)
+        takes the place of `redraw_latents`: it goes through the VAE encoder (`encode_image`: the posterior's mode, or a
+        sample when `redraw_image_seeds` gives one int64 per image) and then follows the same path."""
         bad = [k for k in callback_on_step_end_tensor_inputs if k != "latents"]
         if bad:
             raise ValueError(f"`callback_on_step_end_tensor_inputs` has to be in ['latents'], but found {bad}")
@@ -423,7 +497,7 @@ class DiffSenseiPipeline:
                                   target_size, ip_images, ip_image_embeds, ip_bbox, ip_scale, dialog_bbox, latents,
                                   prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds,
                                   negative_pooled_prompt_embeds, noise_seeds, redraw_latents, redraw_bbox, redraw_mask,
-                                  strength)
+                                  strength, redraw_image, redraw_image_seeds)
         out_latents = self._denoise([cond], num_inference_steps, callback_on_step_end)
         return StableDiffusionXLPipelineOutput(images=self._postprocess(out_latents, output_type))
 
@@ -432,7 +506,8 @@ class DiffSenseiPipeline:
                       negative_prompt_2, num_samples, generator, original_size, crops_coords_top_left, target_size,
                       ip_images, ip_image_embeds, ip_bbox, ip_scale, dialog_bbox, latents, prompt_embeds,
                       negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, noise_seeds=None,
-                      redraw_latents=None, redraw_bbox=None, redraw_mask=None, strength=1.0):
+                      redraw_latents=None, redraw_bbox=None, redraw_mask=None, strength=1.0, redraw_image=None,
+                      redraw_image_seeds=None):
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         original_size = original_size or (height, width)
@@ -441,10 +516,20 @@ class DiffSenseiPipeline:
         if height % self.vae_scale_factor or width % self.vae_scale_factor:
             raise ValueError(f"`height` and `width` have to be divisible by {self.vae_scale_factor} but are {height} and {width}.")
         num_samples = 1 if num_samples is None else num_samples
+        # a picture to keep: its own checks first, then every other redraw field against latents of the right shape - all
+        # before any encoder runs, the VAE's included
+        image = self._redraw_image_input(redraw_image, redraw_latents, num_samples, height, width)
+        if image is not None:
+            redraw_latents = torch.zeros(1, 4, height // self.vae_scale_factor, width // self.vae_scale_factor)
+        elif redraw_image_seeds is not None:
+            raise ValueError("`redraw_image_seeds` seed the encoding of `redraw_image`, which is missing")
         redraw = self._redraw_inputs(redraw_latents, redraw_bbox, redraw_mask, strength, num_samples, height, width)
         if redraw is not None:                                   # "no step would run" is a ValueError before any encoder too
             self.scheduler.set_timesteps(num_inference_steps, device=self._execution_device)
             self.scheduler.start_index(redraw["strength"])
+        if image is not None:                                    # from here on it is the `redraw_latents` path, unchanged
+            redraw = self._redraw_inputs(self._vae_encoder().encode_latents(image, redraw_image_seeds), redraw_bbox,
+                                         redraw_mask, strength, num_samples, height, width)
         guidance = self._panel_values(guidance_scale, num_samples, "guidance_scale")
         ip_scales = self._panel_values(ip_scale, num_samples, "ip_scale")
         self._cfg_side(guidance)
@@ -692,14 +777,43 @@ class DiffSenseiPipeline:
         drain(0)
         return images
 
+    def _encode_request_images(self, requests: List[dict], images: List[Optional[Tensor]]) -> List[dict]:
+        """The `redraw_image` requests of a batch with `redraw_latents` in the picture's place: all pictures go through the
+        VAE encoder in ONE `encode_latents` call (they share height and width).  Seeds: all picture requests or none."""
+        idx = [i for i, im in enumerate(images) if im is not None]
+        clean = [{k: v for k, v in r.items() if k not in ("redraw_image", "redraw_image_seeds")} for r in requests]
+        if not idx:
+            return clean
+        if len({images[i].dtype for i in idx}) != 1:
+            raise ValueError("generate_batch: the `redraw_image`s of one batch are all uint8 or all float")
+        seeded = [requests[i].get("redraw_image_seeds") is not None for i in idx]
+        if any(seeded) != all(seeded):
+            raise ValueError("generate_batch: `redraw_image_seeds` for every `redraw_image` of the batch, or for none")
+        seeds = None
+        if all(seeded):
+            seeds = []
+            for i in idx:
+                s = [int(v) for v in requests[i]["redraw_image_seeds"]]
+                if len(s) != images[i].shape[0]:
+                    raise ValueError(f"generate_batch: {images[i].shape[0]} `redraw_image_seeds` are needed, got {len(s)}")
+                seeds += s
+        lat = self._vae_encoder().encode_latents(torch.cat([images[i] for i in idx]), seeds)
+        off = 0
+        for i in idx:
+            n = images[i].shape[0]
+            clean[i]["redraw_latents"] = lat[off:off + n]
+            off += n
+        return clean
+
     # ---- several requests of one shape in ONE UNet batch (serving front-end, SURVEY.md 8f row 4)
     @torch.no_grad()
     def generate_batch(self, requests: List[dict], output_type: str = "pil") -> List[Any]:
         """Each request: the keyword arguments of `__call__` (without `output_type`).  All must share height, width and
         num_inference_steps (`serving.bucket_key`), and their guidance scales lie on one side of 1 (classifier-free
         guidance is on or off for the whole UNet batch); prompts, character references, boxes, seeds, `num_samples`,
-        `guidance_scale` and `ip_scale` are per request.  A batch is all region redraw (`redraw_latents`, each request with
-        its own kept latents and mask, one shared `strength`) or all plain.  Returns one `.images`-like object per request,
+        `guidance_scale` and `ip_scale` are per request.  A batch is all region redraw (`redraw_latents` or `redraw_image`, each
+        request with its own kept latents / picture and mask, one shared `strength`) or all plain; the pictures of a batch are
+        encoded in one pass.  Returns one `.images`-like object per request,
         in order."""
         if not requests:
             return []
@@ -711,16 +825,26 @@ class DiffSenseiPipeline:
                  for r in requests]                 # before any encoder runs
         if any(s != sides[0] for s in sides):
             raise ValueError("generate_batch: requests mix classifier-free guidance on (guidance_scale > 1) and off (<= 1)")
-        rd = [r.get("redraw_latents") is not None for r in requests]
+        rd = [r.get("redraw_latents") is not None or r.get("redraw_image") is not None for r in requests]
         if any(rd) != all(rd):
-            raise ValueError("generate_batch: a batch is all region redraw (`redraw_latents`) or all plain, not a mix")
+            raise ValueError("generate_batch: a batch is all region redraw (`redraw_latents` / `redraw_image`) or all plain, not a mix")
+        images = []
         for r in requests:                          # every request's redraw fields, before any encoder runs
             h = r.get("height") or self.default_sample_size * self.vae_scale_factor
             w = r.get("width") or self.default_sample_size * self.vae_scale_factor
-            self._redraw_inputs(r.get("redraw_latents"), r.get("redraw_bbox"), r.get("redraw_mask"),
-                                r.get("strength", 1.0), r.get("num_samples", 1) or 1, h, w)
+            ns = r.get("num_samples", 1) or 1
+            img = self._redraw_image_input(r.get("redraw_image"), r.get("redraw_latents"), ns, h, w)
+            if img is None and r.get("redraw_image_seeds") is not None:
+                raise ValueError("generate_batch: `redraw_image_seeds` without `redraw_image`")
+            images.append(img)
+            x0 = r.get("redraw_latents") if img is None else torch.zeros(1, 4, h // self.vae_scale_factor, w // self.vae_scale_factor)
+            self._redraw_inputs(x0, r.get("redraw_bbox"), r.get("redraw_mask"), r.get("strength", 1.0), ns, h, w)
         if all(rd) and len({float(r.get("strength", 1.0)) for r in requests}) != 1:
             raise ValueError("generate_batch: the redraw requests of one batch must share `strength`")
+        if any(im is not None for im in images):    # "no step would run" is a ValueError before the VAE encoder too
+            self.scheduler.set_timesteps(requests[0].get("num_inference_steps", 40), device=self._execution_device)
+            self.scheduler.start_index(float(requests[0].get("strength", 1.0)))
+        requests = self._encode_request_images(requests, images)
         names = ("prompt", "prompt_2", "height", "width", "num_inference_steps", "guidance_scale", "negative_prompt",
                  "negative_prompt_2", "num_samples", "generator", "original_size", "crops_coords_top_left", "target_size",
                  "ip_images", "ip_image_embeds", "ip_bbox", "ip_scale", "dialog_bbox", "latents", "prompt_embeds",

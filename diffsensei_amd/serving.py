@@ -11,7 +11,7 @@ Here the same idea is applied to inference, because one UNet launch plan / hipGr
     results = batcher.run(output_type="pil")                   # results[ticket] = that request's images
 
 Requests that share (height, width, steps, guidance_scale, ip_scale) - and, for region-redraw requests
-(`redraw_latents`), `strength`; a redraw never shares a batch with a plain request - are concatenated into one UNet batch
+(`redraw_latents` or `redraw_image`), `strength`; a redraw never shares a batch with a plain request - are concatenated into one UNet batch
 of at most `max_panels` panels (`DiffSenseiPipeline.generate_batch`: per-request prompts, character references, boxes, seeds);
 buckets run largest-resolution first.
 
@@ -47,9 +47,10 @@ def bucket_key(request: dict, mix_scales: bool = False) -> Tuple:
     guidance values lie on both sides of 1 fits no batch and is a ValueError here, so that it cannot take the requests
     bucketed with it down (`BucketBatcher.submit` checks every request this way)."""
     g = _scale_key(request.get("guidance_scale", 5.0))
-    # a region-redraw request (`redraw_latents`) runs a shortened schedule with another step kernel: it shares a batch
+    # a region-redraw request (`redraw_latents` or `redraw_image`) runs a shortened schedule with another step kernel: it shares a batch
     # only with redraws of the same strength.  A plain request's key is what it was.
-    redraw = () if request.get("redraw_latents") is None else (("redraw", float(request.get("strength", 1.0))),)
+    is_redraw = request.get("redraw_latents") is not None or request.get("redraw_image") is not None
+    redraw = (("redraw", float(request.get("strength", 1.0))),) if is_redraw else ()
     if mix_scales:
         on = {x > 1 for x in (g if isinstance(g, tuple) else (g,))}
         if len(on) != 1:

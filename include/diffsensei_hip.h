@@ -197,6 +197,36 @@ int ds_vae_conv_in_f16(const float* latents, const float* post_quant_w, const fl
 int ds_vae_conv_out_f16(const void* x, const void* w, const void* bias, float* image, int B, int H, int W, int C,
                         int denormalize, void* stream);
 
+/* ---- VAE encoder: replaces AutoencoderKL.encode (diffusers [3P]) so that region redraw can start from a picture
+ * (diffsensei_amd/vae.py VaeEncoderEngine).  Resnets, GroupNorms, the 1x1 shortcuts and the dim-512 attention are the decoder's
+ * entry points above, in either storage mode; these are the four ops that have no decoder counterpart. */
+/* Downsample2D(padding=0): F.pad(x, (0,1,0,1)) then a 3x3 convolution with stride 2 and no padding.  x [B,H,W,Cin] NHWC,
+ * w [Cout,3,3,Cin], y [B,H/2,W/2,Cout] (floor): output (Y, X) reads rows 2Y + ky, columns 2X + kx; rows >= H and columns >= W
+ * read as zero.  Cin % 64 == 0.  ds_conv3x3_f16 with stride 2 pads 1 on every side instead (the UNet's downsamplers). */
+int ds_conv3x3_down_f16(const void* x, const void* w, const void* bias, void* y, int B, int H, int W, int Cin, int Cout,
+                        void* stream);
+int ds_conv3x3_down_bf16(const void* x, const void* w, const void* bias, void* y, int B, int H, int W, int Cin, int Cout,
+                         void* stream);
+/* y[B,H,W,C] = conv_in(image), 3x3, 3 -> C, pad 1 (zero padding of the NORMALISED image).  image_is_u8 != 0: image is uint8
+ * NHWC [B,H,W,3] and the kernel computes fma(u, 2/255, -1) in fp32; else fp32 NCHW [B,3,H,W] already in [-1, 1].
+ * w [C,3,3,3], bias [C] in the storage type (f16 / bf16), as is y. */
+int ds_vae_enc_conv_in_f16(const void* image, int image_is_u8, const void* w, const void* bias, void* y, int B, int H, int W,
+                           int C, void* stream);
+int ds_vae_enc_conv_in_bf16(const void* image, int image_is_u8, const void* w, const void* bias, void* y, int B, int H, int W,
+                            int C, void* stream);
+/* moments fp32 NCHW [B,8,H,W] = quant_conv(conv_out(x[B,H,W,C])): w [8,3,3,C] in the storage type with quant_conv folded in
+ * (W' = Wq Wc), bias fp32 [8] (b' = Wq bc + bq); channels 0..3 = mean, 4..7 = logvar clamped to [-30, 20]. */
+int ds_vae_enc_conv_out_f16(const void* x, const void* w, const float* bias, float* moments, int B, int H, int W, int C,
+                            void* stream);
+int ds_vae_enc_conv_out_bf16(const void* x, const void* w, const float* bias, float* moments, int B, int H, int W, int C,
+                             void* stream);
+/* latents fp16 NCHW [B,4,HW] = fp16((z - shift[c]) * scale[c]) with z = mean (seeds == NULL: the mode) or
+ * z = mean + exp(0.5 logvar) * n, n = the device noise below for (seeds[b], pixel, step 0, stream_id 1); seeds: device int64 [B].
+ * shift4 (may be NULL = 0) and scale4 are HOST pointers to 4 floats: latents_mean and scaling_factor / latents_std, or 0 and
+ * scaling_factor. */
+int ds_vae_latents_f16(const float* moments, const int64_t* seeds, const float* shift4, const float* scale4, void* latents,
+                       int B, int HW, void* stream);
+
 /* 3x3 convolution, pad 1, NHWC: y[B,Ho,Wo,Cout] = conv(x[B,H,W,Cin], w[Cout,3,3,Cin]) + bias
  * (+ rowbias[b, :] per image — the resnet time_emb_proj term) (+ residual).  stride in {1,2};
  * upsample != 0 fuses a nearest x2 upsample in front (diffusers Upsample2D).  Cin % 64 == 0.
@@ -331,7 +361,8 @@ int ds_cfg_dpm_step_f16(const void* eps, void* latents, void* model_in, const fl
  *   counter = (pixel, 0, step, stream_id)                pixel = 0 .. HW-1 inside the panel
  *   x0..x3  = the four latent channels of that pixel;  u_k = x_k * 2^-32 + 2^-33 in fp32 (never 0)
  *   channels 0,1 = sqrt(-2 ln u0) * {cos, sin}(2 pi u1);  channels 2,3 the same from (u2, u3)
- * stream_id 0 = sampler-step noise; 1.. are reserved (initial latents, other samplers) and unused so far.
+ * stream_id 0 = sampler-step noise; 1 = the VAE encoder's posterior sample (ds_vae_latents_f16, step 0); 2.. are reserved
+ * (initial latents, other samplers) and unused so far.
  * ds_philox_u32: the raw words, uint32 [ns,HW,4].  ds_philox_normal_f32: the normals, fp32 NCHW [ns,4,HW]. */
 int ds_philox_u32(const int64_t* seeds, int step, int stream_id, uint32_t* out, int ns, int HW, void* stream);
 int ds_philox_normal_f32(const int64_t* seeds, int step, int stream_id, float* out, int ns, int HW, void* stream);
