@@ -476,9 +476,12 @@ int ds_skinny_linear_f16(const void* x, const void* w, const void* bias, const v
 // ---- MLLM pre-pass (llm.hip): LLaMA greedy decoding
 static int llm_gemv_impl(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, const void* residual,
                          int64_t ldr, int M, int N, int K, int rms, int swiglu, float eps, hipStream_t st,
-                         const void* rms_gain = nullptr, bool gemm16 = false) {
+                         const void* rms_gain = nullptr, bool gemm16 = false, const float* w_scale = nullptr,
+                         bool w8 = false) {
+    DS_REQUIRE(!w8 || w_scale, "%s: int8 weights need their scale vector", gemm16 ? "llm_gemm16_w8" : "llm_gemv_w8");
     LlmGemvParams g;
-    g.x = H(x); g.w = H(w); g.y = HM(y); g.residual = H(residual); g.gain = rms ? H(rms_gain) : nullptr;
+    g.w_scale = w_scale;
+    g.x = H(x); g.w = w; g.y = HM(y); g.residual = H(residual); g.gain = rms ? H(rms_gain) : nullptr;
     g.ldx = ldx; g.ldy = ldy; g.ldr = ldr; g.M = M; g.N = N; g.K = K; g.rms = rms; g.swiglu = swiglu; g.eps = eps;
     return gemm16 ? ds_launch_llm_gemm16(g, st) : ds_launch_llm_gemv(g, st);
 }
@@ -523,6 +526,25 @@ int ds_llm_advance(int32_t* state, int rows, void* stream) { return ds_launch_ll
 
 int ds_llm_swiglu_f16(const void* gate_up, void* act, int M, int I, void* stream) {
     return ds_launch_llm_swiglu(H(gate_up), HM(act), M, I, S(stream));
+}
+
+// ---- int8 weight-only (W8A16) forms: w int8 [N,K] (K % 16 == 0), w_scale fp32 [N] (SwiGLU [2N])
+int ds_llm_gemv_w8(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, const void* residual, int64_t ldr,
+                   int M, int N, int K, int rms, const void* rms_gain, int swiglu, float eps, const float* w_scale,
+                   void* stream) {
+    return llm_gemv_impl(x, ldx, w, y, ldy, residual, ldr, M, N, K, rms, swiglu, eps, S(stream), rms_gain, false, w_scale,
+                         true);
+}
+
+int ds_llm_gemm16_w8(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, const void* residual, int64_t ldr,
+                     int M, int N, int K, int rms, const void* rms_gain, int swiglu, float eps, const float* w_scale,
+                     void* stream) {
+    return llm_gemv_impl(x, ldx, w, y, ldy, residual, ldr, M, N, K, rms, swiglu, eps, S(stream), rms_gain, true, w_scale,
+                         true);
+}
+
+int ds_llm_dequant_w8(const void* q, const float* w_scale, void* w16, int64_t N, int K, void* stream) {
+    return ds_launch_llm_dequant_w8(reinterpret_cast<const int8_t*>(q), w_scale, HM(w16), (long)N, K, S(stream));
 }
 
 // ---- batched decode: up to 16 sequences per weight pass
@@ -779,6 +801,12 @@ static int run_op(const ds_op& o, hipStream_t st) {
         case DS_OP_LLM_GEMM16:
             return llm_gemv_impl(p[0], l[0], p[1], p[2], l[1], p[3], l[2], i[0], i[1], i[2], i[3], i[4], o.f[0], st, p[4],
                                  true);
+        case DS_OP_LLM_GEMV_W8:
+            return llm_gemv_impl(p[0], l[0], p[1], p[2], l[1], p[3], l[2], i[0], i[1], i[2], i[3], i[4], o.f[0], st, p[4],
+                                 false, reinterpret_cast<const float*>(p[5]), true);
+        case DS_OP_LLM_GEMM16_W8:
+            return llm_gemv_impl(p[0], l[0], p[1], p[2], l[1], p[3], l[2], i[0], i[1], i[2], i[3], i[4], o.f[0], st, p[4],
+                                 true, reinterpret_cast<const float*>(p[5]), true);
         case DS_OP_LLM_ATTN_SLOTS:
             DS_REQUIRE(l[3] >= 0, "llm_attn_slots: negative slot stride");
             return llm_attn_impl(p[0], l[0], p[1], p[2], l[1], reinterpret_cast<const float*>(p[3]),
@@ -863,6 +891,16 @@ int ds_op_describe(const ds_op* op, char* name, int name_len, double* flops, dou
             nm = "llm_gemm16_kernel";
             fl = 2.0 * i[0] * (double)i[1] * i[2] * (i[4] ? 2 : 1);
             by = 2.0 * ((double)i[1] * i[2] * (i[4] ? 2 : 1) + (double)i[0] * i[2] + (double)i[0] * i[1]);
+            break;
+        case DS_OP_LLM_GEMV_W8:     // int8 weights: 1 byte per weight + the fp32 row scales, x and y fp16
+            nm = "llm_gemv_kernel";
+            fl = 2.0 * i[0] * (double)i[1] * i[2] * (i[4] ? 2 : 1);
+            by = (double)i[1] * (i[4] ? 2 : 1) * (i[2] + 4.0) + 2.0 * ((double)i[0] * i[2] + (double)i[0] * i[1]);
+            break;
+        case DS_OP_LLM_GEMM16_W8:
+            nm = "llm_gemm16_kernel";
+            fl = 2.0 * i[0] * (double)i[1] * i[2] * (i[4] ? 2 : 1);
+            by = (double)i[1] * (i[4] ? 2 : 1) * (i[2] + 4.0) + 2.0 * ((double)i[0] * i[2] + (double)i[0] * i[1]);
             break;
         case DS_OP_LLM_ATTN: nm = "llm_attn_kernel"; break;
         case DS_OP_LLM_ATTN_SLOTS: nm = "llm_attn_slots_kernel"; break;

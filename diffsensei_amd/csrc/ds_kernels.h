@@ -245,7 +245,7 @@ int ds_launch_pad_rows(const half_t* x, half_t* y, int B, int rows_in, int rows_
 //                                      max_new_tokens, eos id, spare, spare}
 struct LlmGemvParams {
     const half_t* x = nullptr;         // [M,K] rows (ldx)
-    const half_t* w = nullptr;         // [N,K] row-major; SwiGLU: [2N,K] = gate rows then up rows
+    const void* w = nullptr;           // [N,K] row-major fp16 (int8 with w_scale); SwiGLU: [2N,K] = gate rows then up rows
     half_t* y = nullptr;               // [M,N] rows (ldy)
     const half_t* residual = nullptr;  // [M,N] rows (ldr) added after the fp16 rounding; may alias y
     long ldx = 0, ldy = 0, ldr = 0;
@@ -256,6 +256,8 @@ struct LlmGemvParams {
                                        // w; null: the caller folded the gain into w and only r is applied to the dot
     int swiglu = 0;                    // y = silu(x.w[n]) * (x.w[n+N])
     float eps = 1e-6f;
+    const float* w_scale = nullptr;    // null: fp16 weights.  Given: w is int8 (K % 16 == 0) and w_scale fp32 [N] (SwiGLU [2N]),
+                                       // one scale per weight row: y = (x' . q[n]) * w_scale[n], scaled in fp32 before the fp16 rounding
 };
 int ds_launch_llm_gemv(const LlmGemvParams& p, hipStream_t stream);
 void ds_llm_gemv_set_variant(int v);   // 0 auto (pipelined), 1 one column per wavefront, 2 streaming without pipelining
@@ -285,6 +287,8 @@ int ds_launch_llm_swiglu(const half_t* gu, half_t* act, int M, int I, hipStream_
 // state block int32 [S][8], caches [S][T_max][kv_heads*D] per layer (slot_stride elements apart), feat [S][max_out][H],
 // out_ids [S][out_cap]
 int ds_launch_llm_gemm16(const LlmGemvParams& p, hipStream_t stream);
+// w16[n][k] = f16(f32(q[n][k]) * scale[n]): an int8 weight matrix back to fp16 for the prompt pass's MFMA GEMMs
+int ds_launch_llm_dequant_w8(const int8_t* q, const float* scale, half_t* w16, long N, int K, hipStream_t stream);
 int ds_launch_llm_attn_slots(const LlmAttnParams& p, long slot_stride, hipStream_t stream);   // p.M = slots, one row each
 int ds_launch_llm_rmsnorm_slots(const half_t* x, long ldx, const half_t* gamma, half_t* y, long ldy, half_t* feat,
                                 const int* state, int S, int H, int max_out, float eps, hipStream_t stream);

@@ -14,6 +14,9 @@
 // HBM layout: weights [N,K] row-major fp16 (one wavefront streams one row); the RMSNorm gains are folded into the
 // following projection on the host (W' = W diag(g)), so a projection only needs the row's 1/rms, which every wavefront
 // recomputes from the x it reads anyway; KV cache [T_max, kv_heads*D] fp16 per layer, keys stored rotated.
+// int8 weight-only decoding (W8A16): the projection weights may instead be int8 [N,K] with one fp32 scale per row; the
+// GEMV / gemm16 kernels are templated on the weight element type (WLoad below) and share every line but the unpack and the
+// row scale in the epilogue.  Activations, KV cache, embedding, lm_head and gains stay fp16.
 #include "ds_common.h"
 #include "ds_kernels.h"
 
@@ -37,14 +40,55 @@ __device__ __forceinline__ h8 rms_gain8(const h8& x, const h8& g, float r) {
     return o;
 }
 
+// One 16-byte weight load per lane and what it holds: 8 fp16 weights, or 16 int8 weights (W8A16: int8 weights with one
+// fp32 scale per output row, fp16 activations).  `halves` turns a load into NH fragments of 8 halves; int8 -> f16 is exact
+// (|q| <= 127).  Per 32-bit word: q ^ 0x80 = q + 128 as an unsigned byte, v_perm_b32 puts it under the exponent byte 0x64
+// (f16 0x6400 + u = 1024 + u, ulp 1 there), a packed subtract of 1152 leaves q: 5 VALU instructions per 4 weights.
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+template <typename WT>
+struct WLoad;
+template <>
+struct WLoad<half_t> {
+    typedef h8 raw;
+    static constexpr int E = 8, NH = 1;
+    static constexpr int PIPE_WAVES = 1;   // llm_gemv_pipe_kernel, M = 1: wavefronts per SIMD asked of the compiler (1 = no request)
+    static __device__ __forceinline__ void halves(const raw& r, h8 (&o)[1]) { o[0] = r; }
+};
+template <>
+struct WLoad<int8_t> {
+    typedef i32x4 raw;
+    static constexpr int E = 16, NH = 2;
+    static constexpr int PIPE_WAVES = 5;   // the unpack temporaries must not cost the fifth resident block (launch_gemv_stream)
+    static __device__ __forceinline__ void halves(const raw& r, h8 (&o)[2]) {
+        const h2 bias = {(half_t)1152.0f, (half_t)1152.0f};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const unsigned u = (unsigned)r[j] ^ 0x80808080u;
+            const h2 lo = __builtin_bit_cast(h2, __builtin_amdgcn_perm(0x64646464u, u, 0x04010400u)) - bias;
+            const h2 hi = __builtin_bit_cast(h2, __builtin_amdgcn_perm(0x64646464u, u, 0x04030402u)) - bias;
+            h8& d = o[j >> 1];
+            const int e = 4 * (j & 1);
+            d[e] = lo[0];
+            d[e + 1] = lo[1];
+            d[e + 2] = hi[0];
+            d[e + 3] = hi[1];
+        }
+    }
+};
+
 // ---------------------------------------------------------------------------------------------------------------
 // y[m][n] = r_m * sum_k x[m][k] w[n][k]  (+ residual[m][n]),  r_m = rsqrt(mean_k x[m][k]^2 + eps) if rms else 1
 // (with p.gain: y[m][n] = sum_k f16(gain[k] * f16(x[m][k] r_m)) w[n][k], the reference's RMSNorm roundings)
 // SWIGLU:  y[m][n] = silu(r_m * x.w[n]) * (r_m * x.w[n+N])     (gate rows [0,N), up rows [N,2N))
 // One wavefront per output column; MC rows of x per pass (x comes from L1/L2, it is MC*K*2 bytes).
 // ---------------------------------------------------------------------------------------------------------------
-template <int MC, int SWIGLU>
+// WT = int8_t: w is int8 [N,K] (K % 16 == 0) and the wave's sum is multiplied by p.w_scale[n] (SwiGLU: [n] for the gate
+// row, [n + N] for the up row) before the fp16 rounding; every other rounding point is the fp16 kernel's.
+template <typename WT, int MC, int SWIGLU>
 __global__ __launch_bounds__(256) void llm_gemv_kernel(LlmGemvParams p) {
+    typedef WLoad<WT> WL;
+    constexpr int E = WL::E, NH = WL::NH;
+    constexpr bool W8 = sizeof(WT) == 1;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n = blockIdx.x * 4 + wave;
     const int m0 = blockIdx.y * MC;
@@ -70,38 +114,53 @@ __global__ __launch_bounds__(256) void llm_gemv_kernel(LlmGemvParams p) {
     float acc[MC], acu[MC];
 #pragma unroll
     for (int m = 0; m < MC; ++m) acc[m] = acu[m] = 0.f;
-    const half_t* wg = p.w + (long)n * K;
-    const half_t* wu = p.w + ((long)n + p.N) * K;
+    const WT* wg = reinterpret_cast<const WT*>(p.w) + (long)n * K;
+    const WT* wu = reinterpret_cast<const WT*>(p.w) + ((long)n + p.N) * K;
     constexpr int U = (MC <= 4) ? 4 : 2;  // independent 16-byte loads in flight per lane
-    for (int k0 = lane * 8; k0 < K; k0 += 512 * U) {
-        h8 wv[U], uv[U];
+    for (int k0 = lane * E; k0 < K; k0 += 64 * E * U) {
+        typename WL::raw wv[U], uv[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int k = min(k0 + 512 * u, K - 8);  // clamped re-read past the end, masked below
-            wv[u] = *reinterpret_cast<const h8*>(wg + k);
-            if (SWIGLU) uv[u] = *reinterpret_cast<const h8*>(wu + k);
+            const int k = min(k0 + 64 * E * u, K - E);  // clamped re-read past the end, masked below
+            wv[u] = *reinterpret_cast<const typename WL::raw*>(wg + k);
+            if (SWIGLU) uv[u] = *reinterpret_cast<const typename WL::raw*>(wu + k);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int k = k0 + 512 * u;
+            const int k = k0 + 64 * E * u;
             if (k < K) {
+                h8 wh[NH], uh[NH];
+                WL::halves(wv[u], wh);
+                if (SWIGLU) WL::halves(uv[u], uh);
 #pragma unroll
                 for (int m = 0; m < MC; ++m) {
                     if (m0 + m < p.M) {
-                        h8 xv = *reinterpret_cast<const h8*>(p.x + (long)(m0 + m) * p.ldx + k);
-                        if (p.gain) xv = rms_gain8(xv, *reinterpret_cast<const h8*>(p.gain + k), r[m]);
-                        acc[m] = dot8(xv, wv[u], acc[m]);
-                        if (SWIGLU) acu[m] = dot8(xv, uv[u], acu[m]);
+#pragma unroll
+                        for (int j = 0; j < NH; ++j) {
+                            h8 xv = *reinterpret_cast<const h8*>(p.x + (long)(m0 + m) * p.ldx + k + 8 * j);
+                            if (p.gain) xv = rms_gain8(xv, *reinterpret_cast<const h8*>(p.gain + k + 8 * j), r[m]);
+                            acc[m] = dot8(xv, wh[j], acc[m]);
+                            if (SWIGLU) acu[m] = dot8(xv, uh[j], acu[m]);
+                        }
                     }
                 }
             }
         }
+    }
+    float sg = 1.0f, su = 1.0f;
+    if constexpr (W8) {
+        sg = p.w_scale[n];
+        if (SWIGLU) su = p.w_scale[n + p.N];
     }
 #pragma unroll
     for (int m = 0; m < MC; ++m) {
         const float rr = p.gain ? 1.0f : r[m];  // with a gain the scale is already inside x'
         acc[m] = wave_sum(acc[m]) * rr;
         if (SWIGLU) acu[m] = wave_sum(acu[m]) * rr;
+        if constexpr (W8) {
+            acc[m] *= sg;
+            if (SWIGLU) acu[m] *= su;
+        }
     }
     if (lane == 0) {
 #pragma unroll
@@ -519,8 +578,8 @@ __global__ __launch_bounds__(256) void llm_gemv_stream_kernel(LlmGemvParams p) {
         float acc[MC], acu[MC];
 #pragma unroll
         for (int m = 0; m < MC; ++m) acc[m] = acu[m] = 0.f;
-        const half_t* wg = p.w + (long)n * K;
-        const half_t* wu = p.w + ((long)n + p.N) * K;
+        const half_t* wg = reinterpret_cast<const half_t*>(p.w) + (long)n * K;
+        const half_t* wu = reinterpret_cast<const half_t*>(p.w) + ((long)n + p.N) * K;
         for (int k0 = lane * 8; k0 < K; k0 += 512 * U) {
             h8 wv[U], uv[U];
 #pragma unroll
@@ -569,26 +628,31 @@ __global__ __launch_bounds__(256) void llm_gemv_stream_kernel(LlmGemvParams p) {
 // Same data path, software-pipelined: the weight loads of the NEXT k-block (or of the next column's first k-block) are
 // issued before the dot products of the current one, and the first block is requested before x is staged, so a
 // wavefront always has 8 KB of weights in flight - no load bubble at block start, between k-blocks or between columns.
-template <int MC, int SWIGLU>
-__global__ __launch_bounds__(256) void llm_gemv_pipe_kernel(LlmGemvParams p) {
+// WT = int8_t: 16 weights per load, so a lane's k-stride is 16 and a k-block is twice as long; x stays fp16 in LDS.
+template <typename WT, int MC, int SWIGLU>
+__global__ __launch_bounds__(256, MC == 1 ? WLoad<WT>::PIPE_WAVES : 1) void llm_gemv_pipe_kernel(LlmGemvParams p) {
+    typedef WLoad<WT> WL;
+    typedef typename WL::raw wraw;
+    constexpr int E = WL::E, NH = WL::NH;
+    constexpr bool W8 = sizeof(WT) == 1;
     extern __shared__ char smem_raw[];
     half_t* xs = reinterpret_cast<half_t*>(smem_raw);
     float* rs = reinterpret_cast<float*>(smem_raw + (size_t)MC * p.K * 2);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int K = p.K, N = p.N;
     constexpr int U = SWIGLU ? 4 : 8;
-    const int NIT = (K + 512 * U - 1) / (512 * U);
+    const int NIT = (K + 64 * E * U - 1) / (64 * E * U);
     const int stride = gridDim.x * 4;
     int n = blockIdx.x * 4 + wave;
-    h8 wa[U], ua[U], wb[U], ub[U];
-    auto issue = [&](int col, int it, h8(&wv)[U], h8(&uv)[U]) {
-        const half_t* wg = p.w + (long)col * K;
-        const half_t* wu = p.w + ((long)col + N) * K;
+    wraw wa[U], ua[U], wb[U], ub[U];
+    auto issue = [&](int col, int it, wraw(&wv)[U], wraw(&uv)[U]) {
+        const WT* wg = reinterpret_cast<const WT*>(p.w) + (long)col * K;
+        const WT* wu = reinterpret_cast<const WT*>(p.w) + ((long)col + N) * K;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int k = min(it * 512 * U + 512 * u + lane * 8, K - 8);
-            wv[u] = *reinterpret_cast<const h8*>(wg + k);
-            if (SWIGLU) uv[u] = *reinterpret_cast<const h8*>(wu + k);
+            const int k = min(it * 64 * E * U + 64 * E * u + lane * E, K - E);
+            wv[u] = *reinterpret_cast<const wraw*>(wg + k);
+            if (SWIGLU) uv[u] = *reinterpret_cast<const wraw*>(wu + k);
         }
     };
     if (n < N) issue(n, 0, wa, ua);
@@ -636,13 +700,19 @@ __global__ __launch_bounds__(256) void llm_gemv_pipe_kernel(LlmGemvParams p) {
             if (ncol < N) issue(ncol, last ? 0 : it + 1, wb, ub);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                const int k = it * 512 * U + 512 * u + lane * 8;
+                const int k = it * 64 * E * U + 64 * E * u + lane * E;
                 if (k < K) {
+                    h8 wh[NH], uh[NH];
+                    WL::halves(wa[u], wh);
+                    if (SWIGLU) WL::halves(ua[u], uh);
 #pragma unroll
                     for (int m = 0; m < MC; ++m) {
-                        const h8 xv = *reinterpret_cast<const h8*>(xs + (long)m * K + k);
-                        acc[m] = dot8(xv, wa[u], acc[m]);
-                        if (SWIGLU) acu[m] = dot8(xv, ua[u], acu[m]);
+#pragma unroll
+                        for (int j = 0; j < NH; ++j) {
+                            const h8 xv = *reinterpret_cast<const h8*>(xs + (long)m * K + k + 8 * j);
+                            acc[m] = dot8(xv, wh[j], acc[m]);
+                            if (SWIGLU) acu[m] = dot8(xv, uh[j], acu[m]);
+                        }
                     }
                 }
             }
@@ -656,6 +726,10 @@ __global__ __launch_bounds__(256) void llm_gemv_pipe_kernel(LlmGemvParams p) {
         for (int m = 0; m < MC; ++m) {
             acc[m] = wave_sum(acc[m]) * rs[m];
             if (SWIGLU) acu[m] = wave_sum(acu[m]) * rs[m];
+            if constexpr (W8) {   // the row scales, after the wave's sum and before the fp16 rounding
+                acc[m] *= p.w_scale[n];
+                if (SWIGLU) acu[m] *= p.w_scale[n + N];
+            }
         }
         if (lane == 0) {
 #pragma unroll
@@ -697,9 +771,19 @@ __global__ __launch_bounds__(256) void llm_gemv_pipe_kernel(LlmGemvParams p) {
 // A row's result depends on that row of x alone: rows >= M are zero fragments, the k order is fixed by (K, lane), the
 // row scale is computed by a fixed wavefront, and an MFMA output row takes nothing from other A rows.
 // ---------------------------------------------------------------------------------------------------------------
-template <int SWIGLU>
+// WT = int8_t: one 16-byte load holds 16 weights of a row and feeds two MFMA steps.  Lane l's load covers
+// k + 16 (l >> 4) .. + 16 of a 64-wide k-block; step 2v takes its first 8 weights, step 2v + 1 the last 8, and the lane's x
+// fragments of those two steps are read at the same k indices (any assignment of k to lanes is a valid MFMA as long as
+// A and B agree).  K % 16 == 0, so a load is inside K or wholly past it: past it the x fragments are zero, whatever number
+// of 16-weight groups the last block has.  The row scale w_scale[n] is applied in the epilogue by the writing thread.
+template <typename WT, int SWIGLU>
 __global__ __launch_bounds__(256) void llm_gemm16_kernel(LlmGemvParams p) {
-    constexpr int U = SWIGLU ? 4 : 8;   // MFMA steps (= 16-byte weight loads per lane and matrix) per iteration
+    typedef WLoad<WT> WL;
+    typedef typename WL::raw wraw;
+    constexpr int E = WL::E, NH = WL::NH;
+    constexpr bool W8 = sizeof(WT) == 1;
+    constexpr int U = SWIGLU ? 4 : 8;   // MFMA steps per iteration
+    constexpr int UL = U / NH;          // 16-byte weight loads per lane and matrix per iteration
     constexpr int KB = 32 * U;          // halves of K per wavefront iteration
     constexpr int NACC = SWIGLU ? 2 : 1;
     extern __shared__ char smem_raw[];
@@ -711,23 +795,28 @@ __global__ __launch_bounds__(256) void llm_gemm16_kernel(LlmGemvParams p) {
     const int K = p.K, N = p.N, M = p.M;
     const int NT = (N + 15) / 16, NIT = (K + 4 * KB - 1) / (4 * KB);
     const h8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
-    h8 wa[U], ua[U], wb[U], ub[U], xa[U], xb[U];
-    auto issue_w = [&](int tile, int it, h8(&wv)[U], h8(&uv)[U]) {
+    wraw wa[UL], ua[UL], wb[UL], ub[UL];
+    h8 xa[U], xb[U];
+    // first k of MFMA step u of this lane in iteration `it`
+    auto kof = [&](int it, int u) {
+        return (it * 4 + wave) * KB + (NH == 1 ? 32 * u + 8 * g : 64 * (u >> 1) + 16 * g + 8 * (u & 1));
+    };
+    auto issue_w = [&](int tile, int it, wraw(&wv)[UL], wraw(&uv)[UL]) {
         const long col = min(tile * 16 + c, N - 1);   // ragged last tile: re-read the last row, never stored
-        const half_t* wg = p.w + col * K;
-        const half_t* wu = p.w + (col + N) * K;
+        const WT* wg = reinterpret_cast<const WT*>(p.w) + col * K;
+        const WT* wu = reinterpret_cast<const WT*>(p.w) + (col + N) * K;
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int k = min((it * 4 + wave) * KB + 32 * u + 8 * g, K - 8);   // ragged K: clamped, x is zero there
-            wv[u] = *reinterpret_cast<const h8*>(wg + k);
-            if (SWIGLU) uv[u] = *reinterpret_cast<const h8*>(wu + k);
+        for (int u = 0; u < UL; ++u) {
+            const int k = min(kof(it, u * NH), K - E);   // ragged K: clamped, x is zero there
+            wv[u] = *reinterpret_cast<const wraw*>(wg + k);
+            if (SWIGLU) uv[u] = *reinterpret_cast<const wraw*>(wu + k);
         }
     };
     const half_t* xr = p.x + (long)min(c, M - 1) * p.ldx;
     auto issue_x = [&](int it, h8(&xv)[U]) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int k = (it * 4 + wave) * KB + 32 * u + 8 * g;
+            const int k = kof(it, u);
             const h8 v = *reinterpret_cast<const h8*>(xr + min(k, K - 8));
             xv[u] = (c < M && k < K) ? v : zero;
         }
@@ -770,19 +859,27 @@ __global__ __launch_bounds__(256) void llm_gemm16_kernel(LlmGemvParams p) {
                 issue_w(ntile, nit, wb, ub);
             }
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                h8 a = xa[u];
-                if (gain) {   // the fragment becomes the RMSNorm OUTPUT at the reference's roundings (zero stays zero)
-                    const int k = min((it * 4 + wave) * KB + 32 * u + 8 * g, K - 8);
-                    a = rms_gain8(a, *reinterpret_cast<const h8*>(gl + k), ra);
+            for (int v = 0; v < UL; ++v) {
+                h8 wh[NH], uh[NH];
+                WL::halves(wa[v], wh);
+                if (SWIGLU) WL::halves(ua[v], uh);
+#pragma unroll
+                for (int j = 0; j < NH; ++j) {
+                    const int u = v * NH + j;
+                    h8 a = xa[u];
+                    if (gain) {   // the fragment becomes the RMSNorm OUTPUT at the reference's roundings (zero stays zero)
+                        const int k = min(kof(it, u), K - 8);
+                        a = rms_gain8(a, *reinterpret_cast<const h8*>(gl + k), ra);
+                    }
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, wh[j], acc, 0, 0, 0);
+                    if (SWIGLU) acu = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, uh[j], acu, 0, 0, 0);
                 }
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, wa[u], acc, 0, 0, 0);
-                if (SWIGLU) acu = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, ua[u], acu, 0, 0, 0);
             }
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
+            for (int u = 0; u < U; ++u) xa[u] = xb[u];
+#pragma unroll
+            for (int u = 0; u < UL; ++u) {
                 wa[u] = wb[u];
-                xa[u] = xb[u];
                 if (SWIGLU) ua[u] = ub[u];
             }
         }
@@ -800,10 +897,12 @@ __global__ __launch_bounds__(256) void llm_gemm16_kernel(LlmGemvParams p) {
             const float rr = gain ? 1.0f : rs[m];   // with a gain the scale is already inside x'
             a *= rr;
             if (m < M && n < N) {
+                if constexpr (W8) a *= p.w_scale[n];   // row scale: after the reduction, before the fp16 rounding
                 float o;
                 if (SWIGLU) {  // fp16 roundings of the reference: act_fn(gate_proj(x)) * up_proj(x)
                     float b = ((rp[1024 + tid] + rp[1280 + tid]) + rp[1536 + tid]) + rp[1792 + tid];
                     b *= rr;
+                    if constexpr (W8) b *= p.w_scale[n + N];
                     const float gt = (float)(half_t)a, up = (float)(half_t)b;
                     o = (float)(half_t)ds_silu(gt) * up;
                 } else {
@@ -818,9 +917,32 @@ __global__ __launch_bounds__(256) void llm_gemm16_kernel(LlmGemvParams p) {
     }
 }
 
+// w16[n][k] = f16(f32(q[n][k]) * s[n]): the prompt pass dequantises the matrix it is about to hand to the MFMA GEMMs.
+// One thread per 16 weights (K % 16 == 0: all of one row); one fp32 multiply and one round-to-nearest-even per element.
+__global__ __launch_bounds__(256) void llm_dequant_w8_kernel(const int8_t* __restrict__ q, const float* __restrict__ s,
+                                                             half_t* __restrict__ w16, long groups, int K) {
+    const long gi = (long)blockIdx.x * 256 + threadIdx.x;
+    if (gi >= groups) return;
+    const long e0 = gi * 16;
+    const float sc = s[e0 / K];
+    const i32x4 v = *reinterpret_cast<const i32x4*>(q + e0);
+    h8 o[2];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            float f = (float)(int8_t)(v[j] >> (8 * b)) * sc;
+            asm("" : "+v"(f));   // the fp32 product stays a value of its own: the fp16 rounding is a second, separate step
+            o[j >> 1][4 * (j & 1) + b] = (half_t)f;
+        }
+    }
+    *reinterpret_cast<h8*>(w16 + e0) = o[0];
+    *reinterpret_cast<h8*>(w16 + e0 + 8) = o[1];
+}
+
 static thread_local int g_llm_gemv_variant = 0;  // 0 auto (pipelined), 1 one-column-per-wavefront kernel, 2 un-pipelined streaming kernel
 
-template <int MC, int SWIGLU>
+template <typename WT, int MC, int SWIGLU>
 int launch_gemv_stream(const LlmGemvParams& p, hipStream_t stream) {
     static int cus = 0;
     if (!cus) {
@@ -839,28 +961,34 @@ int launch_gemv_stream(const LlmGemvParams& p, hipStream_t stream) {
     // with 2-4 columns each to pipeline were measured and are slower: 5.03 -> 5.13 / 5.22 / 5.56 ms per token,
     // profiles/r02_mllm_min_cols_ab.jsonl - resident wavefronts matter more than per-wavefront prefetch here.)
     const int blocks = min((p.N + 3) / 4, cus * max(per_cu, 1));
-    if (g_llm_gemv_variant == 2) hipLaunchKernelGGL((llm_gemv_stream_kernel<MC, SWIGLU>), dim3(blocks), dim3(256), lds, stream, p);
-    else hipLaunchKernelGGL((llm_gemv_pipe_kernel<MC, SWIGLU>), dim3(blocks), dim3(256), lds, stream, p);
+    if constexpr (sizeof(WT) == 2) {
+        if (g_llm_gemv_variant == 2) {
+            hipLaunchKernelGGL((llm_gemv_stream_kernel<MC, SWIGLU>), dim3(blocks), dim3(256), lds, stream, p);
+            DS_LAUNCH_CHECK();
+            return 0;
+        }
+    }
+    hipLaunchKernelGGL((llm_gemv_pipe_kernel<WT, MC, SWIGLU>), dim3(blocks), dim3(256), lds, stream, p);
     DS_LAUNCH_CHECK();
     return 0;
 }
 
-template <int SWIGLU>
+template <typename WT, int SWIGLU>
 int launch_gemv(const LlmGemvParams& p, hipStream_t stream) {
     const int mcs = p.M == 1 ? 1 : p.M == 2 ? 2 : 4;  // LDS copy of x must fit the default 64 KiB dynamic limit
     if (p.M <= 4 && g_llm_gemv_variant != 1 && (size_t)mcs * p.K * 2 + 128 <= 64 * 1024) {
-        if (p.M == 1) return launch_gemv_stream<1, SWIGLU>(p, stream);
-        if (p.M == 2) return launch_gemv_stream<2, SWIGLU>(p, stream);
-        return launch_gemv_stream<4, SWIGLU>(p, stream);
+        if (p.M == 1) return launch_gemv_stream<WT, 1, SWIGLU>(p, stream);
+        if (p.M == 2) return launch_gemv_stream<WT, 2, SWIGLU>(p, stream);
+        return launch_gemv_stream<WT, 4, SWIGLU>(p, stream);
     }
     const int mc = p.M <= 1 ? 1 : p.M <= 2 ? 2 : p.M <= 4 ? 4 : p.M <= 8 ? 8 : 16;
     const dim3 grid((p.N + 3) / 4, (p.M + mc - 1) / mc);
     switch (mc) {
-        case 1: hipLaunchKernelGGL((llm_gemv_kernel<1, SWIGLU>), grid, dim3(256), 0, stream, p); break;
-        case 2: hipLaunchKernelGGL((llm_gemv_kernel<2, SWIGLU>), grid, dim3(256), 0, stream, p); break;
-        case 4: hipLaunchKernelGGL((llm_gemv_kernel<4, SWIGLU>), grid, dim3(256), 0, stream, p); break;
-        case 8: hipLaunchKernelGGL((llm_gemv_kernel<8, SWIGLU>), grid, dim3(256), 0, stream, p); break;
-        default: hipLaunchKernelGGL((llm_gemv_kernel<16, SWIGLU>), grid, dim3(256), 0, stream, p); break;
+        case 1: hipLaunchKernelGGL((llm_gemv_kernel<WT, 1, SWIGLU>), grid, dim3(256), 0, stream, p); break;
+        case 2: hipLaunchKernelGGL((llm_gemv_kernel<WT, 2, SWIGLU>), grid, dim3(256), 0, stream, p); break;
+        case 4: hipLaunchKernelGGL((llm_gemv_kernel<WT, 4, SWIGLU>), grid, dim3(256), 0, stream, p); break;
+        case 8: hipLaunchKernelGGL((llm_gemv_kernel<WT, 8, SWIGLU>), grid, dim3(256), 0, stream, p); break;
+        default: hipLaunchKernelGGL((llm_gemv_kernel<WT, 16, SWIGLU>), grid, dim3(256), 0, stream, p); break;
     }
     DS_LAUNCH_CHECK();
     return 0;
@@ -868,6 +996,7 @@ int launch_gemv(const LlmGemvParams& p, hipStream_t stream) {
 
 constexpr int GEMM16_BLOCKS_PER_CU = 3;
 
+template <typename WT>
 int launch_gemm16(const LlmGemvParams& p, hipStream_t stream) {
     static int cus = 0;
     if (!cus) {
@@ -881,8 +1010,8 @@ int launch_gemm16(const LlmGemvParams& p, hipStream_t stream) {
     // the resident set, as launch_gemv_stream sizes it: GEMM16_BLOCKS_PER_CU blocks of 4 wavefronts by registers
     const int per_cu = (int)min((size_t)GEMM16_BLOCKS_PER_CU, (size_t)(160 * 1024) / (lds + 512));
     const int blocks = min((p.N + 15) / 16, cus * max(per_cu, 1));
-    if (p.swiglu) hipLaunchKernelGGL(llm_gemm16_kernel<1>, dim3(blocks), dim3(256), lds, stream, p);
-    else hipLaunchKernelGGL(llm_gemm16_kernel<0>, dim3(blocks), dim3(256), lds, stream, p);
+    if (p.swiglu) hipLaunchKernelGGL((llm_gemm16_kernel<WT, 1>), dim3(blocks), dim3(256), lds, stream, p);
+    else hipLaunchKernelGGL((llm_gemm16_kernel<WT, 0>), dim3(blocks), dim3(256), lds, stream, p);
     DS_LAUNCH_CHECK();
     return 0;
 }
@@ -891,12 +1020,23 @@ int launch_gemm16(const LlmGemvParams& p, hipStream_t stream) {
 
 void ds_llm_gemv_set_variant(int v) { g_llm_gemv_variant = v; }
 
+// int8 weights (p.w_scale given): 16 weights per 16-byte load, so K % 16 == 0; the scale vector is fp32 [N] (SwiGLU [2N])
+static int check_llm_w8(const LlmGemvParams& p, const char* what) {
+    DS_REQUIRE(p.K >= 16 && p.K % 16 == 0, "%s: int8 weights need K %% 16 == 0 (K=%d)", what, p.K);
+    return 0;
+}
+
 int ds_launch_llm_gemv(const LlmGemvParams& p, hipStream_t stream) {
     DS_REQUIRE(p.M > 0 && p.N > 0 && p.K >= 8 && p.K % 8 == 0, "llm_gemv: bad shape M=%d N=%d K=%d", p.M, p.N, p.K);
     DS_REQUIRE(p.ldx % 8 == 0 && p.ldx >= p.K, "llm_gemv: ldx %ld must be a multiple of 8 and >= K", p.ldx);
     DS_REQUIRE(p.x && p.w && p.y, "llm_gemv: null operand");
     DS_REQUIRE(!(p.swiglu && p.residual), "llm_gemv: the SwiGLU epilogue takes no residual");
-    return p.swiglu ? launch_gemv<1>(p, stream) : launch_gemv<0>(p, stream);
+    if (p.w_scale) {
+        if (const int rc = check_llm_w8(p, "llm_gemv")) return rc;
+        DS_REQUIRE(g_llm_gemv_variant != 2, "llm_gemv: llm_gemv_variant 2 (un-pipelined streaming kernel) has no int8-weight form");
+        return p.swiglu ? launch_gemv<int8_t, 1>(p, stream) : launch_gemv<int8_t, 0>(p, stream);
+    }
+    return p.swiglu ? launch_gemv<half_t, 1>(p, stream) : launch_gemv<half_t, 0>(p, stream);
 }
 
 int ds_launch_llm_gemm16(const LlmGemvParams& p, hipStream_t stream) {
@@ -906,7 +1046,22 @@ int ds_launch_llm_gemm16(const LlmGemvParams& p, hipStream_t stream) {
     DS_REQUIRE(p.x && p.w && p.y, "llm_gemm16: null operand");
     DS_REQUIRE(!(p.swiglu && p.residual), "llm_gemm16: the SwiGLU epilogue takes no residual");
     DS_REQUIRE(!(p.rms && p.gain) || p.K <= 20480, "llm_gemm16: K %d too long for the gain vector in LDS (20480)", p.K);
-    return launch_gemm16(p, stream);
+    if (p.w_scale) {
+        if (const int rc = check_llm_w8(p, "llm_gemm16")) return rc;
+        return launch_gemm16<int8_t>(p, stream);
+    }
+    return launch_gemm16<half_t>(p, stream);
+}
+
+int ds_launch_llm_dequant_w8(const int8_t* q, const float* scale, half_t* w16, long N, int K, hipStream_t stream) {
+    DS_REQUIRE(N > 0 && K >= 16 && K % 16 == 0, "llm_dequant_w8: bad shape N=%ld K=%d (K %% 16 == 0)", N, K);
+    DS_REQUIRE(q && scale && w16, "llm_dequant_w8: null operand");
+    const long groups = N * (long)K / 16;
+    DS_REQUIRE((groups + 255) / 256 <= 0x7fffffffL, "llm_dequant_w8: matrix too large");
+    hipLaunchKernelGGL(llm_dequant_w8_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, stream, q, scale, w16,
+                       groups, K);
+    DS_LAUNCH_CHECK();
+    return 0;
 }
 
 static int check_llm_attn(const LlmAttnParams& p) {

@@ -28,6 +28,13 @@ per-slot attention / norm / pick kernels), whatever number of slots is in use, s
 not depend on what the other slots hold or on the slot it sits in.  A finished or unused slot is skipped by every
 kernel that writes per-slot state.  KV memory: a slot is 2 x layers x T_max x kv_heads x head_dim fp16 = 0.84 GB at
 13B dimensions and T_max 1024 (13.4 GB for 16 slots, next to 26 GB of weights).
+
+int8 weight-only decoding (`LlamaDecodeEngine(weight_dtype="int8")`, W8A16): the four projection groups of every layer
+are stored as int8 with one fp32 scale per output row (`quantize_rows_int8`), activations stay fp16, and the token step
+runs the int8 forms of the same kernels (`DS_OP_LLM_GEMV_W8` / `DS_OP_LLM_GEMM16_W8`: exact int8 -> f16 unpack in
+registers, fp32 accumulation, the row scale in the epilogue), so a step streams about half the bytes.  The embedding,
+`lm_head` and every RMSNorm gain stay fp16.  The prompt pass dequantises one matrix at a time into a reusable fp16
+scratch (`llm_dequant_w8_kernel`) and keeps the MFMA GEMMs.  Opt-in: the default stays fp16, bit for bit.
 """
 from __future__ import annotations
 
@@ -103,16 +110,41 @@ def random_llama_state_dict(cfg: LlamaConfig, device, seed: int = 0) -> Dict[str
     return sd
 
 
+def quantize_rows_int8(w: Tensor):
+    """Per-row symmetric int8 of a weight matrix [N, K] -> (q int8 [N, K], s fp32 [N]) with w ~ q * s[:, None].
+    `w` is first rounded to fp16 (what the engine holds today), then: s[n] = max_k |w[n, k]| / 127 in fp32 (1 for an
+    all-zero row), q = clamp(round_half_even(w / s), -127, 127).  Works on host and device tensors; the scales are per
+    output row, so quantising stacked matrices (q|k|v, gate|up) equals stacking the quantised ones."""
+    if w.dim() != 2:
+        raise ValueError(f"quantize_rows_int8 takes a matrix [N, K], got {tuple(w.shape)}")
+    w = w.detach().to(torch.float16).to(torch.float32)
+    amax = w.abs().amax(dim=1)
+    s = torch.where(amax > 0, amax / 127.0, torch.ones_like(amax))
+    q = torch.clamp(torch.round(w / s[:, None]), -127, 127).to(torch.int8)      # torch.round: half to even
+    return q.contiguous(), s.contiguous()
+
+
+def dequantize_rows_int8(q: Tensor, s: Tensor) -> Tensor:
+    """fp32 [N, K] = q * s[:, None] (one fp32 multiply per element: what the int8 kernels compute with)."""
+    return q.to(torch.float32) * s.to(torch.float32)[:, None]
+
+
 class LlamaDecodeEngine:
     """Device-resident LLaMA decoder + KV cache + the captured one-token launch plan."""
 
     def __init__(self, cfg: LlamaConfig, sd: Dict[str, Tensor], device, max_positions: int = 1024,
                  max_new_tokens: int = 512, use_graph: bool = True, poll_every: int = 8, prompt_path: str = "mfma",
-                 max_sequences: int = 1):
+                 max_sequences: int = 1, weight_dtype: str = "float16"):
         """max_sequences S > 1: `generate_batch` decodes up to S sequences per weight pass; the engine then holds S KV-cache
         slots (each 2 x layers x max_positions x kv_heads x head_dim fp16: 0.84 GB at 13B dimensions and 1024 positions)
-        and [S] id / feature / logits buffers.  With 1 nothing extra is allocated."""
+        and [S] id / feature / logits buffers.  With 1 nothing extra is allocated.
+        weight_dtype "int8": the q|k|v, o, gate|up and down matrices are held as int8 with fp32 row scales (W8A16, see
+        `quantize_rows_int8`); the embedding, lm_head and the RMSNorm gains stay fp16."""
         _lib.load()
+        if weight_dtype not in ("float16", "int8"):
+            raise ValueError(f"weight_dtype {weight_dtype!r}: 'float16' or 'int8'")
+        self.weight_dtype = weight_dtype
+        w8 = weight_dtype == "int8"
         if not 1 <= int(max_sequences) <= CHUNK:
             raise ValueError(f"max_sequences {max_sequences} outside [1, {CHUNK}] (rows of one weight pass)")
         self.max_sequences = S = int(max_sequences)
@@ -127,6 +159,9 @@ class LlamaDecodeEngine:
             raise ValueError(f"head_dim {D}: the decode attention kernel is built for 64 and 128")
         if H % 8 or I % 8:
             raise ValueError("hidden and intermediate sizes must be multiples of 8")
+        if w8 and (H % 16 or I % 16 or (Hq * D) % 16):
+            raise ValueError("weight_dtype='int8': K of every quantised matrix (hidden, heads * head_dim, intermediate size) "
+                             "must be a multiple of 16")
         dev = self.dev
         f16 = lambda t: t.detach().to(device=dev, dtype=torch.float16).contiguous()
 
@@ -138,14 +173,27 @@ class LlamaDecodeEngine:
         # q|k|v and gate|up are stacked (one weight stream per projection group); the RMSNorm gains stay separate vectors
         # applied in the GEMV prologue with the reference's rounding points (normalise, round to fp16, times the fp16 gain)
         self.wqkv, self.wo, self.wgu, self.wdown, self.g_in, self.g_post = [], [], [], [], [], []
+        # int8: the fp32 row scales of the four groups (empty lists with fp16 weights)
+        self.sqkv, self.so, self.sgu, self.sdown = [], [], [], []
+
+        def put(ws: list, ss: list, w16: Tensor) -> None:
+            """one matrix at a time: its fp16 copy is dropped as soon as it is quantised"""
+            if not w8:
+                ws.append(w16)
+                return
+            q, s = quantize_rows_int8(w16)
+            ws.append(q)
+            ss.append(s)
+
         for i in range(L):
             p = f"model.layers.{i}."
-            self.wqkv.append(stack([sd[p + f"self_attn.{n}_proj.weight"] for n in "qkv"]))
+            put(self.wqkv, self.sqkv, stack([sd[p + f"self_attn.{n}_proj.weight"] for n in "qkv"]))
             self.g_in.append(f16(sd[p + "input_layernorm.weight"]))
-            self.wo.append(f16(sd[p + "self_attn.o_proj.weight"]))
-            self.wgu.append(stack([sd[p + "mlp.gate_proj.weight"], sd[p + "mlp.up_proj.weight"]]))
+            put(self.wo, self.so, f16(sd[p + "self_attn.o_proj.weight"]))
+            put(self.wgu, self.sgu, stack([sd[p + "mlp.gate_proj.weight"], sd[p + "mlp.up_proj.weight"]]))
             self.g_post.append(f16(sd[p + "post_attention_layernorm.weight"]))
-            self.wdown.append(f16(sd[p + "mlp.down_proj.weight"]))
+            put(self.wdown, self.sdown, f16(sd[p + "mlp.down_proj.weight"]))
+        self._w16: Optional[Tensor] = None                  # int8: fp16 scratch of the prompt pass (largest group), on first use
         E = lambda *s, dtype=torch.float16: torch.zeros(s, dtype=dtype, device=dev)
         self.qkv_dim = (Hq + 2 * Hkv) * D
         self.h, self.qkv, self.att = E(CHUNK, H), E(CHUNK, self.qkv_dim), E(CHUNK, Hq * D)
@@ -180,14 +228,32 @@ class LlamaDecodeEngine:
 
     def weight_bytes_per_token(self) -> int:
         """Algorithmic HBM bytes of one decode step: every layer matrix + lm_head once (+ one embedding row)."""
-        n = sum(w.numel() for ws in (self.wqkv, self.wo, self.wgu, self.wdown) for w in ws) + self.lm_head.numel()
-        return 2 * (n + self.cfg.hidden_size)
+        n = sum(w.numel() for ws in (self.wqkv, self.wo, self.wgu, self.wdown) for w in ws)
+        if self.weight_dtype == "int8":                     # 1 byte per quantised weight + 4 per row scale; lm_head is fp16
+            ns = sum(s.numel() for ss in (self.sqkv, self.so, self.sgu, self.sdown) for s in ss)
+            return n + 4 * ns + 2 * (self.lm_head.numel() + self.cfg.hidden_size)
+        return 2 * (n + self.lm_head.numel() + self.cfg.hidden_size)
 
     def tensors(self) -> List[Tensor]:
         """Frozen weights in kernel layout (the multi-GPU weight broadcast list)."""
-        return [self.embed, self.lm_head, self.norm_g] + self.wqkv + self.wo + self.wgu + self.wdown + self.g_in + self.g_post
+        return ([self.embed, self.lm_head, self.norm_g] + self.wqkv + self.wo + self.wgu + self.wdown + self.g_in + self.g_post
+                + self.sqkv + self.so + self.sgu + self.sdown)
 
     # ---- launch lists ------------------------------------------------------------------------------------
+    def _proj(self, code: str, w: Tensor, scale: Optional[Tensor], i, l, p) -> object:
+        """One projection launch: `code` (LLM_GEMV / LLM_GEMM16) as it is with fp16 weights, its _W8 form with p[5] = the
+        row scales for an int8 matrix.  p = (x, y, residual, gain)."""
+        x, y, residual, gain = p
+        if scale is None:
+            return make_op(code, i=i, f=(self.cfg.rms_norm_eps,), l=l, p=(x, w, y, residual) + ((gain,) if gain is not None else ()))
+        return make_op(code + "_W8", i=i, f=(self.cfg.rms_norm_eps,), l=l, p=(x, w, y, residual, gain, scale))
+
+    def _scales(self, l: int):
+        """(qkv, o, gate|up, down) row scales of layer l; None each with fp16 weights"""
+        if self.weight_dtype != "int8":
+            return None, None, None, None
+        return self.sqkv[l], self.so[l], self.sgu[l], self.sdown[l]
+
     def _ops(self, M: int, kind: str) -> list:
         """kind: 'chunk' (prompt rows, more follow), 'last' (final prompt chunk -> first token), 'token' (1 row)."""
         c = self.cfg
@@ -198,17 +264,18 @@ class LlamaDecodeEngine:
         if kind == "token":
             ops_.append(make_op("LLM_EMBED", i=(H, V), p=(self.embed, self.state, self.h)))
         for l in range(c.num_hidden_layers):
-            ops_.append(make_op("LLM_GEMV", i=(M, self.qkv_dim, H, 1, 0), f=(eps,), l=(H, self.qkv_dim, 0),
-                                p=(self.h, self.wqkv[l], self.qkv, None, self.g_in[l])))
+            sq, so, sg, sd_ = self._scales(l)
+            ops_.append(self._proj("LLM_GEMV", self.wqkv[l], sq, (M, self.qkv_dim, H, 1, 0), (H, self.qkv_dim, 0),
+                                   (self.h, self.qkv, None, self.g_in[l])))
             ops_.append(make_op("LLM_ATTN", i=(M, Hq, Hkv, D, self.T_max), f=(scale,), l=(self.qkv_dim, Hkv * D, Hq * D),
                                 p=(self.qkv, self.kc[l], self.vc[l], self.rope_cos, self.rope_sin, self.att,
                                    self.state)))
-            ops_.append(make_op("LLM_GEMV", i=(M, H, Hq * D, 0, 0), f=(eps,), l=(Hq * D, H, H),
-                                p=(self.att, self.wo[l], self.h, self.h)))
-            ops_.append(make_op("LLM_GEMV", i=(M, I, H, 1, 1), f=(eps,), l=(H, I, 0),
-                                p=(self.h, self.wgu[l], self.act, None, self.g_post[l])))
-            ops_.append(make_op("LLM_GEMV", i=(M, H, I, 0, 0), f=(eps,), l=(I, H, H),
-                                p=(self.act, self.wdown[l], self.h, self.h)))
+            ops_.append(self._proj("LLM_GEMV", self.wo[l], so, (M, H, Hq * D, 0, 0), (Hq * D, H, H),
+                                   (self.att, self.h, self.h, None)))
+            ops_.append(self._proj("LLM_GEMV", self.wgu[l], sg, (M, I, H, 1, 1), (H, I, 0),
+                                   (self.h, self.act, None, self.g_post[l])))
+            ops_.append(self._proj("LLM_GEMV", self.wdown[l], sd_, (M, H, I, 0, 0), (I, H, H),
+                                   (self.act, self.h, self.h, None)))
         if kind == "chunk":
             ops_.append(make_op("LLM_ADVANCE", i=(M,), p=(self.state,)))
             return ops_
@@ -230,18 +297,19 @@ class LlamaDecodeEngine:
         eps, scale = c.rms_norm_eps, 1.0 / math.sqrt(D)
         ops_ = [make_op("LLM_EMBED_SLOTS", i=(S, H, V), l=(H,), p=(self.embed, self.state_b, self.h))]
         for l in range(c.num_hidden_layers):
-            ops_.append(make_op("LLM_GEMM16", i=(S, self.qkv_dim, H, 1, 0), f=(eps,), l=(H, self.qkv_dim, 0),
-                                p=(self.h, self.wqkv[l], self.qkv, None, self.g_in[l])))
+            sq, so, sg, sd_ = self._scales(l)
+            ops_.append(self._proj("LLM_GEMM16", self.wqkv[l], sq, (S, self.qkv_dim, H, 1, 0), (H, self.qkv_dim, 0),
+                                   (self.h, self.qkv, None, self.g_in[l])))
             ops_.append(make_op("LLM_ATTN_SLOTS", i=(S, Hq, Hkv, D, self.T_max), f=(scale,),
                                 l=(self.qkv_dim, Hkv * D, Hq * D, self.kcs[l].stride(0)),
                                 p=(self.qkv, self.kcs[l], self.vcs[l], self.rope_cos, self.rope_sin, self.att,
                                    self.state_b)))
-            ops_.append(make_op("LLM_GEMM16", i=(S, H, Hq * D, 0, 0), f=(eps,), l=(Hq * D, H, H),
-                                p=(self.att, self.wo[l], self.h, self.h)))
-            ops_.append(make_op("LLM_GEMM16", i=(S, I, H, 1, 1), f=(eps,), l=(H, I, 0),
-                                p=(self.h, self.wgu[l], self.act, None, self.g_post[l])))
-            ops_.append(make_op("LLM_GEMM16", i=(S, H, I, 0, 0), f=(eps,), l=(I, H, H),
-                                p=(self.act, self.wdown[l], self.h, self.h)))
+            ops_.append(self._proj("LLM_GEMM16", self.wo[l], so, (S, H, Hq * D, 0, 0), (Hq * D, H, H),
+                                   (self.att, self.h, self.h, None)))
+            ops_.append(self._proj("LLM_GEMM16", self.wgu[l], sg, (S, I, H, 1, 1), (H, I, 0),
+                                   (self.h, self.act, None, self.g_post[l])))
+            ops_.append(self._proj("LLM_GEMM16", self.wdown[l], sd_, (S, H, I, 0, 0), (I, H, H),
+                                   (self.act, self.h, self.h, None)))
         ops_.append(make_op("LLM_RMSNORM_SLOTS", i=(S, H, self.cap), f=(eps,), l=(H, H),
                             p=(self.h, self.norm_g, self.hn_b, self.feat_b, self.state_b)))
         ops_.append(make_op("LLM_GEMM16", i=(S, V, H, 0, 0), f=(eps,), l=(H, V, 0),
@@ -330,6 +398,16 @@ class LlamaDecodeEngine:
                               "ops_per_token": tok.n}
         return {"ids": ids, "hidden": hidden}
 
+    def _w(self, ws: list, ss: list, l: int) -> Tensor:
+        """The fp16 matrix a prompt-pass GEMM reads: the weight itself, or - int8 - its dequantised copy in the one
+        reusable scratch (sized for the largest group, gate|up; stream order keeps the previous user ahead of the rewrite)."""
+        if self.weight_dtype != "int8":
+            return ws[l]
+        if self._w16 is None:
+            n = max(w.numel() for group in (self.wqkv, self.wo, self.wgu, self.wdown) for w in group[:1])
+            self._w16 = torch.empty(n, dtype=torch.float16, device=self.dev)
+        return ops.llm_dequant_w8(ws[l], ss[l], out=self._w16)
+
     def _prompt_mfma(self, inputs_embeds: Tensor) -> None:
         """Whole prompt in one pass per layer: the projections are [T0,K] x [N,K]^T MFMA GEMMs (weights streamed once
         per layer instead of once per 16-row chunk); only the attention walks the rows in chunks of 16 (causal inside
@@ -343,17 +421,17 @@ class LlamaDecodeEngine:
         att = torch.empty((T0, Hq * c.head_dim), dtype=torch.float16, device=self.dev)
         for l in range(c.num_hidden_layers):
             xn = ops.llm_rmsnorm(h, self.g_in[l], eps)                       # LlamaRMSNorm incl. its gain, then the plain GEMM
-            qkv = ops.gemm(xn, self.wqkv[l])
+            qkv = ops.gemm(xn, self._w(self.wqkv, self.sqkv, l))
             pf.zero_()                                                       # chunk cursor of this layer's cache
             for r0 in range(0, T0, CHUNK):
                 m = min(CHUNK, T0 - r0)
                 ops.llm_attention(qkv[r0:r0 + m], self.kc[l], self.vc[l], self.rope_cos, self.rope_sin, pf, Hq, Hkv,
                                   scale, out=att[r0:r0 + m])
                 ops.llm_advance(pf, m)
-            h = ops.gemm(att, self.wo[l], residual=h)
+            h = ops.gemm(att, self._w(self.wo, self.so, l), residual=h)
             xn = ops.llm_rmsnorm(h, self.g_post[l], eps)
-            act = ops.llm_swiglu(ops.gemm(xn, self.wgu[l]))
-            h = ops.gemm(act, self.wdown[l], residual=h)
+            act = ops.llm_swiglu(ops.gemm(xn, self._w(self.wgu, self.sgu, l)))
+            h = ops.gemm(act, self._w(self.wdown, self.sdown, l), residual=h)
         ops.llm_rmsnorm(h[T0 - 1:T0], self.norm_g, eps, out=self.hn)
         ops.llm_gemv(self.hn, self.lm_head, out=self.logits.view(1, -1))
         ops.llm_select(self.logits, self.chain if self.n_chain else None, T0, self.state, self.out_ids)
@@ -442,7 +520,7 @@ class LlamaDecodeEngine:
         att = torch.empty((starts[-1], Hq * c.head_dim), dtype=torch.float16, device=self.dev)
         for l in range(c.num_hidden_layers):
             xn = ops.llm_rmsnorm(h, self.g_in[l], eps)
-            qkv = ops.gemm(xn, self.wqkv[l])
+            qkv = ops.gemm(xn, self._w(self.wqkv, self.sqkv, l))
             for i, s in enumerate(slots):
                 pf.zero_()                                                   # chunk cursor of this slot's cache
                 for r0 in range(starts[i], starts[i + 1], CHUNK):
@@ -450,10 +528,10 @@ class LlamaDecodeEngine:
                     ops.llm_attention(qkv[r0:r0 + m], self.kcs[l][s], self.vcs[l][s], self.rope_cos, self.rope_sin, pf,
                                       Hq, Hkv, scale, out=att[r0:r0 + m])
                     ops.llm_advance(pf, m)
-            h = ops.gemm(att, self.wo[l], residual=h)
+            h = ops.gemm(att, self._w(self.wo, self.so, l), residual=h)
             xn = ops.llm_rmsnorm(h, self.g_post[l], eps)
-            act = ops.llm_swiglu(ops.gemm(xn, self.wgu[l]))
-            h = ops.gemm(act, self.wdown[l], residual=h)
+            act = ops.llm_swiglu(ops.gemm(xn, self._w(self.wgu, self.sgu, l)))
+            h = ops.gemm(act, self._w(self.wdown, self.sdown, l), residual=h)
         idx = torch.tensor([starts[i + 1] - 1 for i in range(len(embs))], dtype=torch.long, device=self.dev)
         self.h.zero_()
         self.h[torch.tensor(slots, dtype=torch.long, device=self.dev)] = h.index_select(0, idx)

@@ -915,6 +915,72 @@ def llm_gemm16(x: Tensor, w: Tensor, out: Optional[Tensor] = None, residual: Opt
     return out
 
 
+# ---- int8 weight-only decoding (W8A16): the twins of llm_gemv / llm_gemm16 with int8 weights + fp32 row scales -----------
+def _chk_w8(x: Tensor, w: Tensor, w_scale: Tensor, swiglu: bool) -> None:
+    _chk(w, dtype=torch.int8)
+    _chk(w_scale, dtype=torch.float32)
+    if w.dim() != 2 or w.shape[1] != x.shape[1] or w.shape[1] % 16:
+        raise ValueError(f"int8 weights must be [N, K] with K = {x.shape[1]} a multiple of 16, got {tuple(w.shape)}")
+    if swiglu and w.shape[0] % 2:
+        raise ValueError("SwiGLU weights hold gate rows then up rows: an even number of rows")
+    if w_scale.dim() != 1 or w_scale.shape[0] != w.shape[0]:
+        raise ValueError(f"w_scale must be fp32 [{w.shape[0]}] (one scale per weight row), got {tuple(w_scale.shape)}")
+
+
+def llm_gemv_w8(x: Tensor, w: Tensor, w_scale: Tensor, out: Optional[Tensor] = None, residual: Optional[Tensor] = None,
+                rms: bool = False, swiglu: bool = False, eps: float = 1e-6, gain: Optional[Tensor] = None) -> Tensor:
+    """`llm_gemv` with int8 weights: w int8 [N,K] (swiglu: [2N,K]), w_scale fp32 [N] ([2N]); y = (x' . q[n]) * w_scale[n]."""
+    _chk(x, residual, gain)
+    _chk_w8(x, w, w_scale, swiglu)
+    M, K = x.shape
+    N = w.shape[0] // (2 if swiglu else 1)
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float16, device=x.device)
+    _chk(out)
+    check(_lib.load().ds_llm_gemv_w8(_p(x), K, _p(w), _p(out), N, _p(residual), N, M, N, K, int(rms), _p(gain),
+                                     int(swiglu), eps, _p(w_scale), _stream()), "ds_llm_gemv_w8")
+    return out
+
+
+def llm_gemm16_w8(x: Tensor, w: Tensor, w_scale: Tensor, out: Optional[Tensor] = None, residual: Optional[Tensor] = None,
+                  rms: bool = False, swiglu: bool = False, eps: float = 1e-6, gain: Optional[Tensor] = None,
+                  M: Optional[int] = None, N: Optional[int] = None) -> Tensor:
+    """`llm_gemm16` with int8 weights and fp32 row scales (`N` restricts the call to the first N rows of w / w_scale)."""
+    _chk(x, residual, gain)
+    _chk_w8(x, w, w_scale, swiglu)
+    K = x.shape[1]
+    M = x.shape[0] if M is None else int(M)
+    rows = w.shape[0] // (2 if swiglu else 1)
+    N = rows if N is None else int(N)
+    assert 0 < M <= x.shape[0] and 0 < N <= rows and (not swiglu or N == rows)
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float16, device=x.device)
+    _chk(out)
+    assert out.dim() == 2 and out.stride(1) == 1 and out.shape[0] >= M and out.shape[1] >= N
+    ldr = 0
+    if residual is not None:
+        assert residual.dim() == 2 and residual.stride(1) == 1 and residual.shape[0] >= M and residual.shape[1] >= N
+        ldr = residual.stride(0)
+    check(_lib.load().ds_llm_gemm16_w8(_p(x), x.stride(0), _p(w), _p(out), out.stride(0), _p(residual), ldr, M, N, K,
+                                       int(rms), _p(gain), int(swiglu), eps, _p(w_scale), _stream()), "ds_llm_gemm16_w8")
+    return out
+
+
+def llm_dequant_w8(w: Tensor, w_scale: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """f16(f32(w) * w_scale[:, None]) for int8 w [N,K] (K % 16 == 0); `out`: fp16, at least N*K elements, contiguous."""
+    _chk(w, dtype=torch.int8)
+    _chk(w_scale, dtype=torch.float32)
+    N, K = w.shape
+    if K % 16 or w_scale.shape != (N,):
+        raise ValueError(f"int8 weights [N, K % 16 == 0] with fp32 scales [N] are needed, got {tuple(w.shape)} / {tuple(w_scale.shape)}")
+    if out is None:
+        out = torch.empty((N, K), dtype=torch.float16, device=w.device)
+    _chk(out)
+    assert out.numel() >= N * K
+    check(_lib.load().ds_llm_dequant_w8(_p(w), _p(w_scale), _p(out), N, K, _stream()), "ds_llm_dequant_w8")
+    return out.view(-1)[:N * K].view(N, K)
+
+
 def llm_attention_slots(qkv: Tensor, k_cache: Tensor, v_cache: Tensor, rope_cos: Tensor, rope_sin: Tensor, state: Tensor,
                         heads: int, kv_heads: int, scale: float, out: Optional[Tensor] = None) -> Tensor:
     """One new row per slot: qkv [S,(heads+2*kv_heads)*D]; caches [S, T_max, kv_heads*D]; state int32 [S, 8].  Slot s

@@ -482,6 +482,21 @@ int ds_llm_swiglu_f16(const void* gate_up, void* act, int M, int I, void* stream
  * on the other rows or on the padding - and the K split inside a block is reduced in a fixed order (no atomics). */
 int ds_llm_gemm16(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, const void* residual, int64_t ldr,
                   int M, int N, int K, int rms, const void* rms_gain, int swiglu, float eps, void* stream);
+/* int8 weight-only decoding (W8A16): ds_llm_gemv_f16 / ds_llm_gemm16 with w as int8 [N,K] (two's complement, row-major;
+ * SwiGLU [2N,K]) and w_scale fp32 [N] (SwiGLU [2N]: gate scales, then up scales), one scale per weight row:
+ *   y[m][n] = f16( (sum_k x'[m][k] q[n][k]) * r_m * w_scale[n] )  - the int8 -> f16 unpack is exact, the sum is fp32, the
+ * scale is applied in fp32 before the one fp16 rounding; every other rounding point is that of the fp16 form.
+ * K % 16 == 0 (a 16-byte load holds 16 weights).  ds_llm_gemv_w8 runs llm_gemv_pipe_kernel (M <= 4) or llm_gemv_kernel;
+ * with the option "llm_gemv_variant" = 2 it fails (that kernel has no int8 form). */
+int ds_llm_gemv_w8(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, const void* residual, int64_t ldr,
+                   int M, int N, int K, int rms, const void* rms_gain, int swiglu, float eps, const float* w_scale,
+                   void* stream);
+int ds_llm_gemm16_w8(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, const void* residual, int64_t ldr,
+                     int M, int N, int K, int rms, const void* rms_gain, int swiglu, float eps, const float* w_scale,
+                     void* stream);
+/* w16[n][k] = f16(f32(q[n][k]) * w_scale[n]) for q int8 [N,K], K % 16 == 0 (one fp32 multiply, one round to nearest even):
+ * the prompt pass hands the result to ds_gemm_f16 */
+int ds_llm_dequant_w8(const void* q, const float* w_scale, void* w16, int64_t N, int K, void* stream);
 /* ds_llm_attn_f16 for one new row per slot: row s of qkv / out belongs to slot s, its caches start slot_stride
  * elements after slot s-1's, its position is state[s][0]. */
 int ds_llm_attn_slots_f16(const void* qkv, int64_t ldqkv, void* k_cache, void* v_cache, int64_t ldc, int64_t slot_stride,
@@ -570,7 +585,9 @@ enum ds_opcode {
     DS_OP_LLM_RMSNORM_SLOTS = 30, /* p: x, gamma, y, feat, state l: ldx ldy     i: slots H max_out       f: eps */
     DS_OP_LLM_EMBED_SLOTS = 31,   /* p: table, state, out        l: ldo         i: slots H vocab */
     DS_OP_LLM_SELECT_SLOTS = 32,  /* p: logits, chain, state, out_ids  l: ldl   i: V n_chain out_cap adv slots */
-    DS_OP_REDRAW_START = 33       /* p: redraw buffer, latents                  i: ns HW   (ds_redraw_start_f16) */
+    DS_OP_REDRAW_START = 33,      /* p: redraw buffer, latents                  i: ns HW   (ds_redraw_start_f16) */
+    DS_OP_LLM_GEMV_W8 = 34,       /* DS_OP_LLM_GEMV with int8 weights in p[1] and p[5] = w_scale (ds_llm_gemv_w8) */
+    DS_OP_LLM_GEMM16_W8 = 35      /* DS_OP_LLM_GEMM16 with int8 weights in p[1] and p[5] = w_scale (ds_llm_gemm16_w8) */
 };
 
 typedef struct ds_op {
