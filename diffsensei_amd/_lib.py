@@ -149,6 +149,11 @@ def load() -> C.CDLL:
         raise DiffSenseiHipError(
             f"{LIB_PATH} is missing: the HIP kernel library is the only execution path of diffsensei_amd. "
             f"Build it with `python -m diffsensei_amd.build` (hipcc, --offload-arch=gfx950).")
+    # One HIP runtime per process: every pointer and stream handed to the library comes from torch, whose wheel carries its own
+    # libamdhip64.  Loaded before torch, the library binds to the system runtime instead and its launches fail with "no
+    # ROCm-capable device is detected" (`build()` followed by `smoke()` in one process did); with torch's runtime already in the
+    # process the dependency resolves to it.
+    import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch, also loud

@@ -445,6 +445,7 @@ class UNetEngine:
         self.gn_ws = self._alloc((_lib.load().ds_groupnorm_workspace_bytes(B, 4 * cfg.block_out_channels[-1]),),
                                  torch.uint8)
         self.scratch: Dict[Tuple[str, int], Tensor] = {}
+        self.zero_scratch: set = set()      # keys of `scratch` allocated with zero=True: their slack rows are read, never written
         self.prepare_plan = self._build_prepare()
         self.forward_ops = self._build_forward()
         self.forward_plan = Plan(self.forward_ops, self.keep)
@@ -478,6 +479,7 @@ class UNetEngine:
             t = self._alloc((need,), torch.float16)
             if zero:
                 t.zero_()
+                self.zero_scratch.add(key)
             self.scratch[key] = t
         return t
 
