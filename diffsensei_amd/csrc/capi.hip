@@ -690,6 +690,19 @@ int ds_pad_rows_f16(const void* x, void* y, int B, int rows_in, int rows_out, in
 }
 
 // ---------------------------------------------------------------------------------------- plan executor
+static LoraMergeParams lora_merge_params(const ds_op& o) {
+    const int32_t* i = o.i;
+    const int64_t* l = o.l;
+    void* const* p = o.p;
+    LoraMergeParams m;
+    m.W = H(p[0]); m.out = HM(p[1]); m.A = H(p[2]); m.B = H(p[3]);
+    m.seg = reinterpret_cast<const int*>(p[4]); m.s = reinterpret_cast<const float*>(p[5]);
+    m.map = reinterpret_cast<const int*>(p[6]); m.colscale = H(p[7]); m.out2 = HM(p[8]);
+    m.N = i[0]; m.K = i[1]; m.R = i[2]; m.nseg = i[3];
+    m.ldw = l[0]; m.ldo = l[1]; m.lda = l[2]; m.ldb = l[3]; m.ldo2 = l[4];
+    return m;
+}
+
 static int run_op(const ds_op& o, hipStream_t st) {
     const int32_t* i = o.i;
     const int64_t* l = o.l;
@@ -821,6 +834,8 @@ static int run_op(const ds_op& o, hipStream_t st) {
         case DS_OP_LLM_SELECT_SLOTS:
             return ds_launch_llm_select_slots(H(p[0]), l[0], i[0], reinterpret_cast<const int*>(p[1]), i[1], i[2], i[3],
                                               reinterpret_cast<int*>(p[2]), reinterpret_cast<int*>(p[3]), i[4], st);
+        case DS_OP_LORA_MERGE:
+            return ds_launch_lora_merge(lora_merge_params(o), st);
         default:
             ds_set_error("plan: unknown opcode %d", o.code);
             return -4;
@@ -908,6 +923,11 @@ int ds_op_describe(const ds_op* op, char* name, int name_len, double* flops, dou
         case DS_OP_LLM_SELECT_SLOTS: nm = "llm_select_slots_kernel"; by = 2.0 * i[0] * (double)i[4]; break;
         case DS_OP_LLM_RMSNORM: nm = "llm_rmsnorm_kernel"; by = 4.0 * i[0] * (double)i[1]; break;
         case DS_OP_LLM_SELECT: nm = "llm_select_kernel"; by = 2.0 * i[0]; break;
+        case DS_OP_LORA_MERGE:   // W in, out (and out2) out, A and B once; the adapters' products
+            nm = "lora_merge_kernel";
+            fl = 2.0 * i[0] * (double)i[1] * i[2];
+            by = 2.0 * ((op->p[8] ? 3.0 : 2.0) * i[0] * (double)i[1] + (double)i[2] * ((double)i[0] + i[1]));
+            break;
         default: break;
     }
     if (name && name_len > 0) {
@@ -943,7 +963,22 @@ int ds_plan_num_ops(const ds_plan* plan) { return plan ? (int)plan->ops.size() :
 int ds_plan_run(ds_plan* plan, void* stream) {
     DS_REQUIRE(plan, "ds_plan_run: null plan");
     for (size_t k = 0; k < plan->ops.size(); ++k) {
-        const int rc = run_op(plan->ops[k], S(stream));
+        int rc;
+        if (plan->ops[k].code == DS_OP_LORA_MERGE) {
+            // consecutive merges are independent (each writes its own matrix from read-only inputs): one launch per group
+            LoraMergeParams grp[DS_LORA_GROUP];
+            int n = 0;
+            while (n < DS_LORA_GROUP && k + n < plan->ops.size() && plan->ops[k + n].code == DS_OP_LORA_MERGE) {
+                grp[n] = lora_merge_params(plan->ops[k + n]);
+                ++n;
+            }
+            rc = ds_launch_lora_merge_group(grp, n, S(stream));
+            if (rc == 0) {
+                k += n - 1;
+                continue;
+            }
+        } else
+            rc = run_op(plan->ops[k], S(stream));
         if (rc != 0) {
             char msg[600];
             snprintf(msg, sizeof(msg), "plan op %zu (code %d): %s", k, plan->ops[k].code, g_err);

@@ -240,6 +240,26 @@ int ds_launch_embed_tokens(const int* ids, const half_t* tok_emb, const half_t* 
 int ds_launch_pad_rows(const half_t* x, half_t* y, int B, int rows_in, int rows_out, int row_off, int total_rows,
                        int C, hipStream_t stream);
 
+// ---- LoRA merge into a packed weight buffer (lora.hip) ------------------------------------------------
+#define DS_LORA_MAX_SEGMENTS 16   // the host merges at most 8 adapters at once (lora.py); empty segments may pad the list
+struct LoraMergeParams {
+    const half_t* W = nullptr;         // [N,K] base weight rows (ldw), read only: never `out` or `out2`
+    half_t* out = nullptr;             // [N,K] rows (ldo): f16(f32(W[map(n)]) + sum_i s_i (B_i A_i)[map(n)])
+    const half_t* A = nullptr;         // [R,K] rows (lda): the adapters' down matrices, concatenated along the rank
+    const half_t* B = nullptr;         // [N,R] rows (ldb): the up matrices, same concatenation
+    const int* seg = nullptr;          // device int32 [nseg + 1]: rank offsets, one segment per adapter (empty ones are legal)
+    const float* s = nullptr;          // device fp32 [nseg]: strength of each adapter
+    const int* map = nullptr;          // optional device int32 [N]: output row n reads row map[n] of W and B
+    const half_t* colscale = nullptr;  // with out2: f16 [K]
+    half_t* out2 = nullptr;            // optional [N,K] rows (ldo2): f16(f32(out) * f32(colscale[k]))
+    long ldw = 0, ldo = 0, lda = 0, ldb = 0, ldo2 = 0;
+    int N = 0, K = 0, R = 0, nseg = 0;
+};
+int ds_launch_lora_merge(const LoraMergeParams& p, hipStream_t stream);
+#define DS_LORA_GROUP 24   // matrices per launch: 24 x 128 bytes of parameters fit the 4 KiB of kernel arguments
+// `count` (1..DS_LORA_GROUP) independent merges in ONE launch; the plan executor groups consecutive DS_OP_LORA_MERGE ops
+int ds_launch_lora_merge_group(const LoraMergeParams* ps, int count, hipStream_t stream);
+
 // ---- MLLM pre-pass: LLaMA greedy decoding (llm.hip) ---------------------------------------------------
 // device-side state block (int32[8]): {tokens in the KV cache, tokens generated, finished, current token,
 //                                      max_new_tokens, eos id, spare, spare}

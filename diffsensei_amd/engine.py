@@ -59,20 +59,40 @@ def pack_geglu320(t: Tensor) -> Tensor:
     return torch.stack([t[:half].reshape(g, 160, *t.shape[1:]), t[half:].reshape(g, 160, *t.shape[1:])], dim=1).reshape(t.shape).contiguous()
 
 
+def _matvec(wf: Tensor, v: Tensor) -> Tensor:
+    """wf [N,K] @ v [K], or one such product per leading index: wf [G,N,K], v [G,K] -> [G,N]."""
+    return wf @ v if wf.dim() == 2 else torch.bmm(wf, v[:, :, None])[:, :, 0]
+
+
+def ln_fused_cb(gw: Tensor, w: Tensor, bias: Optional[Tensor], beta: Tensor, wf: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """(c2 f16 [N,2] = (-c hi, -c lo), b' f16 [N]) of `pack_ln_fused` from gw = f16(gamma (.) W).  Every argument may carry
+    one leading index (several matrices of one shape at once: the refresh after a LoRA merge).  wf: w.double(), if the caller has it."""
+    nc = (-gw.double().sum(-1)).float()
+    hi = nc.to(torch.float16)
+    lo = (nc - hi.float()).to(torch.float16)
+    bp = _matvec(w.double() if wf is None else wf, beta.double())
+    if bias is not None:
+        bp = bp + bias.double()
+    return torch.stack([hi, lo], dim=-1).contiguous(), bp.to(torch.float16).contiguous()
+
+
+def ln_fused_vb(w: Tensor, beta: Tensor) -> Tensor:
+    """b' = W beta of the operand-swapped form (to_v) as an f16 (hi, lo) pair, [N,2]."""
+    bf = _matvec(w.double(), beta.double()).float()
+    bh = bf.to(torch.float16)
+    bl = (bf - bh.float()).to(torch.float16)
+    return torch.stack([bh, bl], dim=-1)
+
+
 def pack_ln_fused(w: Tensor, bias: Optional[Tensor], gamma: Tensor, beta: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
     """LayerNorm folded into the linear that consumes it (csrc/gemm_pp.hip, "LayerNorm"):
     LN(x) W^T + b = rstd (x (gamma (.) W)^T - mean c) + b',  c_n = sum_k (gamma (.) W)_nk,  b' = b + W beta.
     Returns (gw f16 [N,K], c2 f16 [N,2] = (-c hi, -c lo), b' f16 [N]).  c is summed from the f16-ROUNDED gw - the values
     the MFMA contracts - so the rank-1 correction cancels the mean exactly; the (hi, lo) pair keeps it to 2^-22."""
     wf = w.double()
-    gw = (wf * gamma.double()[None, :]).to(torch.float16)
-    nc = (-gw.double().sum(1)).float()
-    hi = nc.to(torch.float16)
-    lo = (nc - hi.float()).to(torch.float16)
-    bp = wf @ beta.double()
-    if bias is not None:
-        bp = bp + bias.double()
-    return gw.contiguous(), torch.stack([hi, lo], dim=1).contiguous(), bp.to(torch.float16).contiguous()
+    gw = (wf * gamma.double()[None, :]).to(torch.float16).contiguous()
+    c2, bp = ln_fused_cb(gw, w, bias, beta, wf)
+    return gw, c2, bp
 
 
 # Upsample2D at exactly x2: the taps of the 3x3 kernel that meet the same input pixel, per output phase (py or px) and 2x2 tap
@@ -235,37 +255,82 @@ class PackedUNet:
                     # (with DIFFSENSEI_LN_FUSION=0 in the environment at LOAD time the +2.1 GB of copies are not made
                     # at all; a plan built later simply finds none and keeps the LayerNorm launches.  With the default - on -
                     # they are packed once here and the plan builder decides per level and batch which set it uses.)
-                    # fused-LayerNorm copies for norm1 -> q|k (row form) and -> to_v, produced transposed (operand-swapped form:
-                    # (-c, b') per output row)
-                    gw, c2, b2 = pack_ln_fused(self.w[f"{t}.attn1.qk.weight"], None, dv(f"{t}.norm1.weight"), dv(f"{t}.norm1.bias"))
-                    put(f"{t}.attn1.qk.weight_ln", gw)
-                    put(f"{t}.attn1.qk.c_ln", c2)
-                    put(f"{t}.attn1.qk.bias_ln", b2)
-                    gw, c2, b2 = pack_ln_fused(dv(f"{t}.attn1.to_v.weight"), None, dv(f"{t}.norm1.weight"), dv(f"{t}.norm1.bias"))
-                    bf = (dv(f"{t}.attn1.to_v.weight").double() @ dv(f"{t}.norm1.bias").double()).float()   # b' as an f16 (hi, lo) pair
-                    bh = bf.to(torch.float16)
-                    bl = (bf - bh.float()).to(torch.float16)
-                    put(f"{t}.attn1.to_v.weight_ln", gw)
-                    put(f"{t}.attn1.to_v.cb_ln", torch.cat([c2, torch.stack([bh, bl], dim=1)], dim=1).contiguous())
-                    # norm2 -> attn2.to_q, norm3 -> GEGLU projection.  Both kernel families implement every form (the 128-wide
-                    # producers need whole 64-column strips in a 128-column tile), so every SDXL block gets the copies (+2.1 GB)
-                    gw, c2, b2 = pack_ln_fused(dv(f"{t}.attn2.to_q.weight"), None, dv(f"{t}.norm2.weight"), dv(f"{t}.norm2.bias"))
-                    put(f"{t}.attn2.to_q.weight_ln", gw)
-                    put(f"{t}.attn2.to_q.c_ln", c2)
-                    put(f"{t}.attn2.to_q.bias_ln", b2)
-                    gw, c2, b2 = pack_ln_fused(dv(f"{t}.ff.net.0.proj.weight"), dv(f"{t}.ff.net.0.proj.bias"),
-                                               dv(f"{t}.norm3.weight"), dv(f"{t}.norm3.bias"))
-                    gwp, b2p = pack_geglu(gw, b2)
-                    half = c2.shape[0] // 2
-                    c2p = torch.stack([c2[:half].reshape(-1, 64, 2), c2[half:].reshape(-1, 64, 2)], dim=1).reshape(-1, 2)
-                    put(f"{t}.ff.net.0.proj.weight_ln", gwp)
-                    put(f"{t}.ff.net.0.proj.c_ln", c2p)
-                    put(f"{t}.ff.net.0.proj.bias_ln", b2p)
+                    for n, v in self.ln_fused(t, dv).items():
+                        put(n, v)
                 put(f"{t}.ff.net.2.weight", sd[f"{t}.ff.net.2.weight"])
                 put(f"{t}.ff.net.2.bias", sd[f"{t}.ff.net.2.bias"])
         self.kv_total = off
         for name, lst in (("xattn.k_text", kt), ("xattn.v_text", vt), ("xattn.k_ip", ki), ("xattn.v_ip", vi)):
             put(name, torch.cat([t.to(device) for t in lst], 0))
+
+    LN_PARTS = ("qk", "v", "q2", "ff")
+
+    def ln_fused(self, t: str, get, parts=LN_PARTS) -> Dict[str, Tensor]:
+        """The fused-LayerNorm tensors of transformer block `t`, by name, in packing order.  `get(name)` supplies the
+        diffusers-layout tensors they derive from (q|k comes stacked out of `self.w`): the state dict when the block is packed,
+        the merged buffers when a LoRA merge has rewritten them (`refresh_derived`) - one definition for both.
+        parts: "qk" norm1 -> q|k (row form), "v" norm1 -> to_v, produced transposed (operand-swapped form: (-c, b') per
+        output row), "q2" norm2 -> attn2.to_q, "ff" norm3 -> GEGLU projection.  Both kernel families implement every form (the
+        128-wide producers need whole 64-column strips in a 128-column tile), so every SDXL block gets the copies (+2.1 GB)."""
+        out: Dict[str, Tensor] = {}
+        if "qk" in parts:
+            gw, c2, b2 = pack_ln_fused(self.w[f"{t}.attn1.qk.weight"], None, get(f"{t}.norm1.weight"), get(f"{t}.norm1.bias"))
+            out[f"{t}.attn1.qk.weight_ln"], out[f"{t}.attn1.qk.c_ln"], out[f"{t}.attn1.qk.bias_ln"] = gw, c2, b2
+        if "v" in parts:
+            wv = get(f"{t}.attn1.to_v.weight")
+            gw, c2, b2 = pack_ln_fused(wv, None, get(f"{t}.norm1.weight"), get(f"{t}.norm1.bias"))
+            out[f"{t}.attn1.to_v.weight_ln"] = gw
+            out[f"{t}.attn1.to_v.cb_ln"] = torch.cat([c2, ln_fused_vb(wv, get(f"{t}.norm1.bias"))], dim=1).contiguous()
+        if "q2" in parts:
+            gw, c2, b2 = pack_ln_fused(get(f"{t}.attn2.to_q.weight"), None, get(f"{t}.norm2.weight"), get(f"{t}.norm2.bias"))
+            out[f"{t}.attn2.to_q.weight_ln"], out[f"{t}.attn2.to_q.c_ln"], out[f"{t}.attn2.to_q.bias_ln"] = gw, c2, b2
+        if "ff" in parts:
+            gw, c2, b2 = pack_ln_fused(get(f"{t}.ff.net.0.proj.weight"), get(f"{t}.ff.net.0.proj.bias"),
+                                       get(f"{t}.norm3.weight"), get(f"{t}.norm3.bias"))
+            gwp, b2p = pack_geglu(gw, b2)
+            half = c2.shape[0] // 2
+            c2p = torch.stack([c2[:half].reshape(-1, 64, 2), c2[half:].reshape(-1, 64, 2)], dim=1).reshape(-1, 2)
+            out[f"{t}.ff.net.0.proj.weight_ln"], out[f"{t}.ff.net.0.proj.c_ln"], out[f"{t}.ff.net.0.proj.bias_ln"] = gwp, c2p, b2p
+        return out
+
+    def refresh_derived(self, blocks: Dict[str, set]) -> None:
+        """After weights of the transformer blocks `blocks` ({block: parts of LN_PARTS}) were rewritten in place (LoRA merge):
+        re-derive, INTO the existing storage, what packing derives from them - the c / b' vectors of the fused LayerNorms,
+        from the gamma (.) W copies the merge wrote as its second output, with the functions packing uses (`ln_fused_cb`,
+        `ln_fused_vb`), all blocks of one width in one call - and the lazily made 320-row GEGLU copies.  Pointers do not
+        change, so plans and graphs stay valid."""
+        w = self.w
+        groups: Dict[Tuple, List[str]] = {}
+        for t, parts in blocks.items():
+            if f"{t}.attn1.qk.weight_ln" not in w:
+                continue
+            for part in parts:
+                groups.setdefault((part, tuple(w[f"{t}.attn2.to_q.weight"].shape)), []).append(t)
+        st = lambda ts, name: torch.stack([w[f"{t}.{name}"] for t in ts])
+        dst, src = [], []
+        for (part, _), ts in groups.items():
+            if part == "v":
+                wv, beta = st(ts, "attn1.to_v.weight"), st(ts, "norm1.bias")
+                c2, _ = ln_fused_cb(st(ts, "attn1.to_v.weight_ln"), wv, None, beta)
+                cb = torch.cat([c2, ln_fused_vb(wv, beta)], dim=-1)
+                dst += [w[f"{t}.attn1.to_v.cb_ln"] for t in ts]
+                src += list(cb.unbind(0))
+                continue
+            lin, norm = {"qk": ("attn1.qk", "norm1"), "q2": ("attn2.to_q", "norm2"), "ff": ("ff.net.0.proj", "norm3")}[part]
+            # the GEGLU projection stays in its 64 + 64 row packing: c and b' are per row, and its bias is packed alike
+            c2, bp = ln_fused_cb(st(ts, lin + ".weight_ln"), st(ts, lin + ".weight"), st(ts, lin + ".bias") if part == "ff" else None,
+                                 st(ts, norm + ".bias"))
+            dst += [w[f"{t}.{lin}.c_ln"] for t in ts] + [w[f"{t}.{lin}.bias_ln"] for t in ts]
+            src += list(c2.unbind(0)) + list(bp.unbind(0))
+        if dst:
+            torch._foreach_copy_(dst, src)
+        for t, parts in blocks.items():
+            if "ff" not in parts:
+                continue
+            for name in ("weight", "bias", "weight_ln", "bias_ln", "c_ln"):
+                key = f"{t}.ff.net.0.proj.{name}.g320"
+                if key in w:
+                    w[key].copy_(pack_geglu320(unpack_geglu(w[f"{t}.ff.net.0.proj.{name}"])))
 
     def geglu320(self, t: str, ln: bool) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
         """(weight, bias, c) of transformer block `t`'s GEGLU projection re-packed in 320-row groups for gemm_g320_kernel - made

@@ -1047,3 +1047,74 @@ def image_to_u8(image: Tensor) -> Tensor:
     out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=image.device)
     check(_lib.load().ds_image_f32_to_u8_nhwc(_p(image), _p(out), B, H, W, _stream()), "ds_image_f32_to_u8_nhwc")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ LoRA merge
+def _chk_rows(t: Optional[Tensor], what: str) -> None:
+    """An f16 matrix whose rows are contiguous (a row or column slice of a larger buffer is fine: the row stride travels
+    as the leading dimension)."""
+    if t is None:
+        return
+    if not t.is_cuda:
+        raise _lib.DiffSenseiHipError("diffsensei_amd ops need CUDA(HIP) tensors — there is no CPU path")
+    bind_device(t.device)
+    if t.dtype != torch.float16 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise _lib.DiffSenseiHipError(f"lora_merge: {what} must be an fp16 matrix with contiguous rows")
+
+
+def lora_merge_op(W: Tensor, out: Tensor, A: Optional[Tensor] = None, B: Optional[Tensor] = None,
+                  seg: Optional[Tensor] = None, s: Optional[Tensor] = None, map: Optional[Tensor] = None,
+                  colscale: Optional[Tensor] = None, out2: Optional[Tensor] = None, nseg: Optional[int] = None) -> _lib.DsOp:
+    """The DS_OP_LORA_MERGE plan op of `lora_merge` (same operands; `seg` / `s` / `map` are device tensors here)."""
+    _chk_rows(W, "W"), _chk_rows(out, "out"), _chk_rows(A, "A"), _chk_rows(B, "B"), _chk_rows(out2, "out2")
+    _chk(seg, map, dtype=torch.int32)
+    _chk(s, dtype=torch.float32)
+    _chk(colscale)
+    N, K = W.shape
+    n = 0 if seg is None else (seg.numel() - 1 if nseg is None else int(nseg))
+    R = 0 if A is None else A.shape[0]
+    if tuple(out.shape) != (N, K) or (out2 is not None and tuple(out2.shape) != (N, K)):
+        raise ValueError(f"lora_merge: out / out2 must be [{N}, {K}] like W")
+    if n > 0:
+        if A is None or B is None or s is None or A.shape[1] != K or tuple(B.shape) != (N, R):
+            raise ValueError(f"lora_merge: A must be [R, {K}] and B [{N}, R] with seg [n + 1] and s [n]")
+        if seg.numel() < n + 1 or s.numel() < n:
+            raise ValueError(f"lora_merge: {n} adapters need seg [{n + 1}] and s [{n}]")
+    if map is not None and map.numel() != N:
+        raise ValueError(f"lora_merge: map must be int32 [{N}]")
+    if (colscale is None) != (out2 is None) or (colscale is not None and colscale.numel() != K):
+        raise ValueError(f"lora_merge: out2 comes with colscale fp16 [{K}]")
+    op = _lib.DsOp()
+    op.code = _lib.OP["LORA_MERGE"]
+    for k, v in enumerate((N, K, R, n)):
+        op.i[k] = int(v)
+    ld = lambda t: 0 if t is None else int(t.stride(0))
+    for k, v in enumerate((ld(W), ld(out), ld(A), ld(B), ld(out2))):
+        op.l[k] = v
+    for k, t in enumerate((W, out, A if n else None, B if n else None, seg if n else None, s if n else None, map, colscale, out2)):
+        op.p[k] = _p(t)
+    return op
+
+
+def lora_merge(W: Tensor, A: Optional[Tensor] = None, B: Optional[Tensor] = None, seg=None, s=None,
+               out: Optional[Tensor] = None, map: Optional[Tensor] = None, colscale: Optional[Tensor] = None,
+               out2: Optional[Tensor] = None) -> Tensor:
+    """out[n] = f16(f32(W[map[n]]) + sum_i s[i] * B[map[n], seg[i]:seg[i+1]] @ A[seg[i]:seg[i+1]]) (lora_merge_kernel through
+    DS_OP_LORA_MERGE; there is no exported entry point).  W [N,K] is the base weight and is never written: `out` must be
+    another buffer.  A [R,K] / B [N,R]: up to 8 adapters concatenated along the rank; `seg` (n + 1 offsets) and `s` (n
+    strengths) may be sequences or device tensors; none: `out` gets the bits of W.  `out` / `out2` may be row or column slices of
+    larger buffers.  out2 = f16(f32(out) * f32(colscale)), the fused-LayerNorm copy (`engine.pack_ln_fused`'s gw)."""
+    _chk_rows(W, "W")
+    dev = W.device
+    if seg is not None and not torch.is_tensor(seg):
+        seg = torch.tensor([int(v) for v in seg], dtype=torch.int32).to(dev)
+    if s is not None and not torch.is_tensor(s):
+        s = torch.tensor([float(v) for v in s], dtype=torch.float32).to(dev)
+    if seg is not None and seg.numel() < 2:
+        seg = s = None
+    if out is None:
+        out = torch.empty((W.shape[0], W.shape[1]), dtype=torch.float16, device=dev)
+    op = lora_merge_op(W, out, A, B, seg, s, map, colscale, out2)
+    import ctypes
+    check(_lib.load().ds_op_run(ctypes.byref(op), _stream()), "ds_op_run(LORA_MERGE)")
+    return out

@@ -85,6 +85,7 @@ class DiffSenseiPipeline:
         self._stream = None
         self.use_graph = os.environ.get("DIFFSENSEI_GRAPH", "1") != "0"
         self.last_run_info = {}
+        self._keep_adapters_until = None     # set inside `hold_adapters()`: the adapter state to restore at its end
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, unet: Optional[UNetMangaModel] = None, image_encoder=None,
@@ -805,9 +806,82 @@ class DiffSenseiPipeline:
             off += n
         return clean
 
+    # ---- LoRA adapters of the UNet (diffusers protocol names; lora.py)
+    def load_lora_weights(self, path_or_dict, adapter_name: str = "default", alpha: Optional[float] = None,
+                          unet_only: bool = False) -> int:
+        """Load a UNet LoRA (`.safetensors`, `.bin` / `.pth` read with weights_only=True, or a state dict; peft or diffusers key
+        names) under `adapter_name`; `set_adapters` activates it.  Adapters of the text encoders are not merged: their keys are
+        refused like every other unknown key unless `unet_only=True`, which drops them.  Returns how many keys were dropped."""
+        from .lora import drop_text_encoder_keys, read_lora_file
+        sd = path_or_dict if isinstance(path_or_dict, dict) else read_lora_file(path_or_dict)
+        dropped = 0
+        if unet_only:
+            sd, dropped = drop_text_encoder_keys(sd)
+        self.unet.load_lora_adapter(sd, adapter_name, alpha)
+        self.last_lora_dropped_keys = dropped
+        return dropped
+
+    def set_adapters(self, adapter_names, adapter_weights=1.0):
+        self.unet.set_adapters(adapter_names, adapter_weights)
+
+    def delete_adapters(self, adapter_names):
+        self.unet.delete_adapters(adapter_names)
+
+    def unload_lora_weights(self):
+        """Back to the base weights; every loaded adapter is dropped."""
+        self.unet.set_adapters([])
+        self.unet.delete_adapters(self.unet.loaded_adapters())
+
     # ---- several requests of one shape in ONE UNet batch (serving front-end, SURVEY.md 8f row 4)
-    @torch.no_grad()
     def generate_batch(self, requests: List[dict], output_type: str = "pil") -> List[Any]:
+        """`_generate_batch` under the adapter state the requests ask for.  A request may carry `lora={name: weight, ...}`
+        ({} = no adapter; names as loaded with `load_lora_weights`); without the field it runs on whatever is set.  The merged
+        weights are a property of the whole UNet batch, so a batch that mixes states is refused (`serving.bucket_key` keeps
+        them apart); the state is set for the batch and the previous one restored afterwards, also on an exception."""
+        absent = object()
+        states = [r.get("lora", absent) for r in requests]
+        norm = lambda st: st if st is absent else tuple(sorted((str(k), float(v)) for k, v in dict(st or {}).items()))
+        if len({norm(st) for st in states}) > 1:
+            raise ValueError("generate_batch: requests of one batch must share their `lora` adapters and weights")
+        held = self._keep_adapters_until                  # inside `hold_adapters()`: the state from before the run
+        if not requests or (states[0] is absent and held is None):
+            return self._generate_batch(requests, output_type)
+        # adapters are merged in sorted-name order for a request (its dict has no order to rely on); a batch without the
+        # field inside a held run goes back to the state from before the run, in that state's own order
+        want = list(held.items()) if states[0] is absent else list(norm(states[0]))
+        before = self.unet.adapter_weights()
+        requests = [{k: v for k, v in r.items() if k != "lora"} for r in requests]
+        if want == list(before.items()):                  # already the state asked for: no switch, nothing to restore
+            return self._generate_batch(requests, output_type)
+        self.unet.set_adapters([k for k, _ in want], [v for _, v in want])
+        try:
+            return self._generate_batch(requests, output_type)
+        finally:
+            if held is None:
+                self.unet.set_adapters(list(before), list(before.values()))
+
+    def hold_adapters(self):
+        """Context manager for a run of `generate_batch` calls (`BucketBatcher.run`): inside it a batch leaves its adapter
+        state set - the next batch switches only if it wants another one - and the state from before is restored once, at
+        the end, also on an exception."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def hold():
+            if self._keep_adapters_until is not None:      # nested: the outer one restores
+                yield
+                return
+            self._keep_adapters_until = before = self.unet.adapter_weights()
+            try:
+                yield
+            finally:
+                self._keep_adapters_until = None
+                if list(self.unet.adapter_weights().items()) != list(before.items()):
+                    self.unet.set_adapters(list(before), list(before.values()))
+        return hold()
+
+    @torch.no_grad()
+    def _generate_batch(self, requests: List[dict], output_type: str = "pil") -> List[Any]:
         """Each request: the keyword arguments of `__call__` (without `output_type`).  All must share height, width and
         num_inference_steps (`serving.bucket_key`), and their guidance scales lie on one side of 1 (classifier-free
         guidance is on or off for the whole UNet batch); prompts, character references, boxes, seeds, `num_samples`,

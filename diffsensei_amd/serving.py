@@ -51,6 +51,10 @@ def bucket_key(request: dict, mix_scales: bool = False) -> Tuple:
     # only with redraws of the same strength.  A plain request's key is what it was.
     is_redraw = request.get("redraw_latents") is not None or request.get("redraw_image") is not None
     redraw = (("redraw", float(request.get("strength", 1.0))),) if is_redraw else ()
+    # `lora={name: weight}`: the merged UNet weights are one state per batch.  Only a request that carries the field gets the
+    # element, so every other key is what it was; {} (no adapter) is a state of its own, distinct from "whatever is set"
+    if "lora" in request:
+        redraw = redraw + (("lora", tuple(sorted((str(k), float(v)) for k, v in dict(request["lora"] or {}).items()))),)
     if mix_scales:
         on = {x > 1 for x in (g if isinstance(g, tuple) else (g,))}
         if len(on) != 1:
@@ -180,8 +184,13 @@ class BucketBatcher:
         reqs = self._resolve_mllm(reqs)
         self.last_plan = plan_batches(reqs, self.max_panels, self.max_pixels, self.mix_scales)
         results: List[Any] = [None] * len(reqs)
-        for batch in self.last_plan:
-            outs = self.pipe.generate_batch([reqs[i] for i in batch], output_type=output_type)
-            for i, o in zip(batch, outs):
-                results[i] = o
+        import contextlib
+        # requests with `lora`: a batch leaves its adapters set, so consecutive batches of one state switch once, and the state
+        # from before the run comes back once, at the end
+        hold = self.pipe.hold_adapters() if any("lora" in r for r in reqs) else contextlib.nullcontext()
+        with hold:
+            for batch in self.last_plan:
+                outs = self.pipe.generate_batch([reqs[i] for i in batch], output_type=output_type)
+                for i, o in zip(batch, outs):
+                    results[i] = o
         return results

@@ -15,6 +15,7 @@ import torch
 from . import ops
 from .attention_processor import AttnProcessor2_0, MaskedIPAttnProcessor2_0
 from .engine import PackedUNet, UNetEngine
+from .lora import LoraState
 from .unet_config import (UNetMangaConfig, attn_processor_names, param_shapes, random_state_dict,
                           sdxl_config)
 
@@ -53,6 +54,7 @@ class UNetMangaModel:
         self._sd: Dict[str, Tensor] = {}
         self._packed: Optional[PackedUNet] = None
         self._engines: Dict[Tuple, UNetEngine] = {}
+        self._lora = LoraState(self.config)
         self._attn_processors: Dict[str, Any] = {n: AttnProcessor2_0() for n in attn_processor_names(self.config)}
         self._manga = False
         # "fp16": the reference's arithmetic - the only value (the e4m3 variant of rounds 2-5 was retired in round 6)
@@ -120,6 +122,53 @@ class UNetMangaModel:
     def _invalidate(self):
         self._packed = None
         self._engines.clear()
+        self._lora.invalidate()      # merge plans name the dropped buffers; `packed()` re-applies the active adapters
+
+    # ---- LoRA adapters (diffusers / peft protocol names; lora.py)
+    def load_lora_adapter(self, sd_or_path, adapter_name: str = "default", alpha: Optional[float] = None):
+        """Load one adapter (a state dict in peft or diffusers format, or a .safetensors / .bin / .pth file) onto the device.
+        It takes effect with `set_adapters`.  `alpha`: overrides the dict's own / the default alpha = rank."""
+        self._lora.load(sd_or_path, adapter_name, alpha, self.device)
+        if self._packed is not None and self._lora.dealias(self._packed, self._sd, self._lora.adapters[adapter_name]):
+            # once per newly targeted matrix: its packed copy moved off the state dict's storage, so what names the old
+            # address goes (set_adapters itself never does this)
+            self._engines.clear()
+            self._lora.plans.clear()
+
+    def set_adapters(self, names, weights=1.0):
+        """Make `names` (a name or a list; [] = none) the active adapters, each at its weight: the packed weights become
+        W + sum weight * alpha / r * B A, merged in place from the base weights by one launch plan.  Engines, launch plans and
+        captured graphs stay as they are; `state_dict()` stays the base."""
+        active = self._lora.resolve(names, weights)
+        if self._packed is None:
+            self._lora.active = active          # applied when the weights are packed
+        else:
+            self._lora.apply(self._packed, self._sd, active)
+
+    def delete_adapters(self, names):
+        names = [names] if isinstance(names, str) else list(names)
+        unknown = [n for n in names if n not in self._lora.adapters]
+        if unknown:
+            raise ValueError(f"delete_adapters: {unknown} not loaded (loaded: {list(self._lora.adapters)})")
+        left = [(n, w) for n, w in self._lora.active if n not in names]
+        if len(left) != len(self._lora.active):
+            self.set_adapters([n for n, _ in left], [w for _, w in left])
+        for n in names:
+            del self._lora.adapters[n]
+        self._lora.plans = {k: v for k, v in self._lora.plans.items() if not set(k[0]) & set(names)}
+        if self._lora.last_plan is not None and self._lora.last_plan not in self._lora.plans.values():
+            self._lora.last_plan = None
+
+    def active_adapters(self):
+        """Names of the active adapters, in merge order."""
+        return [n for n, _ in self._lora.active]
+
+    def adapter_weights(self) -> Dict[str, float]:
+        """{active adapter: its weight}, in merge order."""
+        return dict(self._lora.active)
+
+    def loaded_adapters(self):
+        return list(self._lora.adapters)
 
     def state_dict(self) -> Dict[str, Tensor]:
         return dict(self._sd)
@@ -161,6 +210,7 @@ class UNetMangaModel:
         if device is not None and torch.device(device) != self.device:
             self.device = torch.device(device)
             self._sd = {k: v.to(self.device) for k, v in self._sd.items()}
+            self._lora.to(self.device)
             self._invalidate()
         return self
 
@@ -205,6 +255,9 @@ class UNetMangaModel:
             if self.device.type != "cuda":
                 raise RuntimeError("UNetMangaModel runs on an MI355X only (device must be cuda/hip); no CPU fallback")
             self._packed = PackedUNet(self.config, self._sd, self.device)
+            self._lora.dealias(self._packed, self._sd, self._lora.touched(self._lora.adapters))
+            if self._lora.active:
+                self._lora.apply(self._packed, self._sd, self._lora.active)
         return self._packed
 
     # Launch plans are cached per (batch, latent size): each owns its activation buffers, K/V panels and a captured

@@ -587,7 +587,16 @@ enum ds_opcode {
     DS_OP_LLM_SELECT_SLOTS = 32,  /* p: logits, chain, state, out_ids  l: ldl   i: V n_chain out_cap adv slots */
     DS_OP_REDRAW_START = 33,      /* p: redraw buffer, latents                  i: ns HW   (ds_redraw_start_f16) */
     DS_OP_LLM_GEMV_W8 = 34,       /* DS_OP_LLM_GEMV with int8 weights in p[1] and p[5] = w_scale (ds_llm_gemv_w8) */
-    DS_OP_LLM_GEMM16_W8 = 35      /* DS_OP_LLM_GEMM16 with int8 weights in p[1] and p[5] = w_scale (ds_llm_gemm16_w8) */
+    DS_OP_LLM_GEMM16_W8 = 35,     /* DS_OP_LLM_GEMM16 with int8 weights in p[1] and p[5] = w_scale (ds_llm_gemm16_w8) */
+    DS_OP_LORA_MERGE = 36         /* p: W, out, A, B, seg, s, map, colscale, out2   l: ldw ldo lda ldb ldo2   i: N K R nseg
+                                     out[n,k] = f16(f32(W[map(n),k]) + sum_i s[i] * sum_{r in [seg[i], seg[i+1])} B[map(n),r] A[r,k]):
+                                     W [N,K] f16 is the base weight, read only - the launch fails when it is out or out2; A [R,K]
+                                     and B [N,R] f16 hold the adapters concatenated along the rank (any rank, any boundary; nseg <= 16, empty segments legal);
+                                     seg int32 [nseg+1] and s fp32 [nseg] are DEVICE arrays, so a plan is replayed with new
+                                     strengths after a host write; nseg = 0 copies W.  Each adapter is accumulated in fp32, scaled in
+                                     fp32, added in order, rounded once.  map (optional int32 [N]) permutes the rows of W and B alike;
+                                     out2 (optional, with colscale f16 [K]) = f16(f32(out) * f32(colscale[k])), the fused-LayerNorm
+                                     copy.  N, K multiples of 8; ldw, ldo, lda, ldo2 multiples of 8; no exported entry point */
 };
 
 typedef struct ds_op {
