@@ -193,19 +193,15 @@ int ds_gemm_f16_batched(const void* x, int64_t ldx, int64_t sx, const void* w, i
     return ds_launch_gemm(p, batch, S(stream));
 }
 
-static int conv3x3_impl(const void* x, const void* w, const void* bias, const void* rowbias, int64_t rowbias_ld,
-                        const void* residual, void* y, int B, int H_, int W_, int Cin, int Cout, int stride,
-                        int upsample, hipStream_t stream, int dtype = DS_DTYPE_F16, int out_h = 0, int out_w = 0,
-                        float* gn_partial = nullptr, int* gn_chunks_out = nullptr, int gn_chunks_planned = 0) {
-    DS_REQUIRE(stride == 1 || stride == 2, "conv3x3: stride must be 1 or 2");
-    DS_REQUIRE(!(upsample && stride != 1), "conv3x3: upsample with stride 2 is not a thing");
+// The GemmParams of a 3x3 convolution: the one decode behind the ds_conv3x3_* entry points, the plan's CONV3X3 op (launch and
+// ds_op_describe) and ds_conv3x3_gn_chunks.  `p` is filled even where an argument is refused (-1).
+static int conv3x3_params(GemmParams& p, const void* x, const void* w, const void* bias, const void* rowbias, int64_t rowbias_ld,
+                          const void* residual, void* y, int B, int H_, int W_, int Cin, int Cout, int stride, int upsample,
+                          int dtype = DS_DTYPE_F16, int out_h = 0, int out_w = 0, float* gn_partial = nullptr,
+                          int gn_chunks_planned = 0) {
     // upsample == 2: exact x2, `w` holds the four folded 2 x 2 phase weights [4][Cout][4 Cin] (ds_fold_upsample2x_f16)
     const bool fold = upsample == 2;
-    DS_REQUIRE(!fold || (dtype == DS_DTYPE_F16 && (out_h == 0 || out_h == 2 * H_) && (out_w == 0 || out_w == 2 * W_)),
-               "conv3x3: folded upsample weights serve the exact x2 f16 case only");
-    DS_REQUIRE((out_h == 0 && out_w == 0) || (upsample && out_h > 0 && out_w > 0),
-               "conv3x3: an explicit output size needs the upsample flag");
-    GemmParams p;
+    p = GemmParams();
     p.conv = 1;
     p.A = H(x); p.W = H(w); p.ldw = (fold ? 4L : 9L) * Cin; p.bias = H(bias); p.rowbias = H(rowbias); p.rowbias_ld = (int)rowbias_ld;
     p.residual = H(residual); p.ldr = Cout; p.C = HM(y); p.ldc = Cout;
@@ -221,18 +217,36 @@ static int conv3x3_impl(const void* x, const void* w, const void* bias, const vo
     p.dtype = dtype;
     p.gn_partial = gn_partial;
     p.gn_chunks = gn_chunks_planned;   // checked against the kernel the launch picks (conv_halo.hip)
-    if (gn_chunks_out) {   // host query only (ds_conv3x3_gn_chunks): no launch
-        *gn_chunks_out = ds_gemm_conv_gn_chunks(p);
-        return 0;
-    }
+    DS_REQUIRE(stride == 1 || stride == 2, "conv3x3: stride must be 1 or 2");
+    DS_REQUIRE(!(upsample && stride != 1), "conv3x3: upsample with stride 2 is not a thing");
+    DS_REQUIRE(!fold || (dtype == DS_DTYPE_F16 && (out_h == 0 || out_h == 2 * H_) && (out_w == 0 || out_w == 2 * W_)),
+               "conv3x3: folded upsample weights serve the exact x2 f16 case only");
+    DS_REQUIRE((out_h == 0 && out_w == 0) || (upsample && out_h > 0 && out_w > 0),
+               "conv3x3: an explicit output size needs the upsample flag");
+    return 0;
+}
+
+static int conv3x3_params(GemmParams& p, const ds_op& o) {
+    const int32_t* i = o.i;
+    void* const* q = o.p;
+    return conv3x3_params(p, q[0], q[1], q[3], q[4], i[7], q[5], q[2], i[0], i[1], i[2], i[3], i[4], i[5], i[6], DS_DTYPE_F16, i[8],
+                          i[9], reinterpret_cast<float*>(q[6]), i[10]);
+}
+
+static int conv3x3_impl(const void* x, const void* w, const void* bias, const void* rowbias, int64_t rowbias_ld,
+                        const void* residual, void* y, int B, int H_, int W_, int Cin, int Cout, int stride,
+                        int upsample, hipStream_t stream, int dtype = DS_DTYPE_F16, int out_h = 0, int out_w = 0) {
+    GemmParams p;
+    if (conv3x3_params(p, x, w, bias, rowbias, rowbias_ld, residual, y, B, H_, W_, Cin, Cout, stride, upsample, dtype, out_h, out_w))
+        return -1;
     return ds_launch_gemm(p, 1, stream);
 }
 
 int ds_conv3x3_gn_chunks(int B, int H_, int W_, int Cin, int Cout) {
-    int n = 0;
+    GemmParams p;
     if (B <= 0 || H_ <= 0 || W_ <= 0 || Cin <= 0 || Cout <= 0) return 0;
-    conv3x3_impl(nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, B, H_, W_, Cin, Cout, 1, 0, nullptr, DS_DTYPE_F16, 0, 0, nullptr, &n);
-    return n;
+    if (conv3x3_params(p, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, B, H_, W_, Cin, Cout, 1, 0)) return 0;
+    return ds_gemm_conv_gn_chunks(p);
 }
 
 int ds_conv3x3_f16(const void* x, const void* w, const void* bias, const void* rowbias, int64_t rowbias_ld,
@@ -703,32 +717,42 @@ static LoraMergeParams lora_merge_params(const ds_op& o) {
     return m;
 }
 
+// The GemmParams of a DS_OP_GEMM: the one decode of its slots (include/diffsensei_hip.h), for the launch and for ds_op_describe
+static GemmParams gemm_params(const ds_op& o) {
+    const int32_t* i = o.i;
+    const int64_t* l = o.l;
+    void* const* p = o.p;
+    GemmParams g;
+    g.A = H(p[0]); g.A2 = H(p[1]); g.W = H(p[2]); g.C = HM(p[3]); g.bias = H(p[4]); g.rowbias = H(p[5]);
+    g.residual = H(p[6]);
+    g.lda = l[0]; g.lda2 = l[1]; g.ldw = l[2]; g.ldc = l[3]; g.ldr = l[4];
+    g.sA = l[5]; g.sA2 = l[6]; g.sW = l[7]; g.sC = l[8]; g.sR = l[9];
+    g.M = i[0]; g.N = i[1]; g.K = i[2]; g.K1 = g.A2 ? i[3] : i[2];
+    g.epi = i[4];
+    g.rowbias_ld = i[6]; g.rows_per_group = i[7] > 0 ? i[7] : 1;
+    g.ln_stats = reinterpret_cast<const float*>(p[7]); g.ln_c = H(p[8]); g.stats_out = reinterpret_cast<float*>(p[9]);
+    g.ln_swapped = i[8]; g.ln_bstride = l[10];
+    g.ln_partial = i[9]; g.ln_eps = i[9] ? o.f[0] : g.ln_eps; g.ln_rows = l[11];
+    g.ln_nstrips = i[10]; g.stats_strip = i[11];
+    return g;
+}
+static int gemm_batch(const ds_op& o) { return o.i[5] > 0 ? o.i[5] : 1; }
+
 static int run_op(const ds_op& o, hipStream_t st) {
     const int32_t* i = o.i;
     const int64_t* l = o.l;
     void* const* p = o.p;
     switch (o.code) {
-        case DS_OP_GEMM: {
-            GemmParams g;
-            g.A = H(p[0]); g.A2 = H(p[1]); g.W = H(p[2]); g.C = HM(p[3]); g.bias = H(p[4]); g.rowbias = H(p[5]);
-            g.residual = H(p[6]);
-            g.lda = l[0]; g.lda2 = l[1]; g.ldw = l[2]; g.ldc = l[3]; g.ldr = l[4];
-            g.sA = l[5]; g.sA2 = l[6]; g.sW = l[7]; g.sC = l[8]; g.sR = l[9];
-            g.M = i[0]; g.N = i[1]; g.K = i[2]; g.K1 = g.A2 ? i[3] : i[2];
-            g.epi = i[4];
-            g.rowbias_ld = i[6]; g.rows_per_group = i[7] > 0 ? i[7] : 1;
-            g.ln_stats = reinterpret_cast<const float*>(p[7]); g.ln_c = H(p[8]); g.stats_out = reinterpret_cast<float*>(p[9]);
-            g.ln_swapped = i[8]; g.ln_bstride = l[10];
-            g.ln_partial = i[9]; g.ln_eps = i[9] ? o.f[0] : g.ln_eps; g.ln_rows = l[11];
-            g.ln_nstrips = i[10]; g.stats_strip = i[11];
-            return ds_launch_gemm(g, i[5] > 0 ? i[5] : 1, st);
-        }
+        case DS_OP_GEMM:
+            return ds_launch_gemm(gemm_params(o), gemm_batch(o), st);
         case DS_OP_LN_FINALIZE:
             return ds_launch_ln_finalize(reinterpret_cast<const float*>(p[0]), reinterpret_cast<float*>(p[1]), i[0], i[1], i[2],
                                          o.f[0], st);
-        case DS_OP_CONV3X3:
-            return conv3x3_impl(p[0], p[1], p[3], p[4], i[7], p[5], p[2], i[0], i[1], i[2], i[3], i[4], i[5], i[6], st,
-                                DS_DTYPE_F16, i[8], i[9], reinterpret_cast<float*>(p[6]), nullptr, i[10]);
+        case DS_OP_CONV3X3: {
+            GemmParams g;
+            if (conv3x3_params(g, o)) return -1;
+            return ds_launch_gemm(g, 1, st);
+        }
         case DS_OP_GROUPNORM: {
             GroupNormParams g;
             g.x1 = H(p[0]); g.x2 = H(p[1]); g.y = HM(p[2]); g.gamma = H(p[3]); g.beta = H(p[4]);
@@ -851,28 +875,15 @@ int ds_op_describe(const ds_op* op, char* name, int name_len, double* flops, dou
     double fl = 0, by = 0;
     switch (op->code) {
         case DS_OP_GEMM: {
-            GemmParams g;
-            g.M = i[0]; g.N = i[1]; g.K = i[2];
-            g.ln_stats = reinterpret_cast<const float*>(op->p[7]); g.stats_out = reinterpret_cast<float*>(op->p[9]);
-            g.ln_c = H(op->p[8]); g.residual = H(op->p[6]);
-            g.ln_swapped = i[8]; g.epi = i[4]; g.ln_partial = i[9]; g.stats_strip = i[11];
-            g.A2 = H(op->p[1]); g.rowbias = H(op->p[5]);
-            g.lda = g.ldw = g.K1 = g.K; g.ldc = g.N;
-            const int batch = i[5] > 0 ? i[5] : 1;
-            nm = ds_gemm_kernel_name(g, batch);
+            const int batch = gemm_batch(*op);
+            nm = ds_gemm_kernel_name(gemm_params(*op), batch);
             fl = 2.0 * i[0] * (double)i[1] * i[2] * batch;
             by = 2.0 * batch * ((double)i[0] * i[2] + (double)i[1] * i[2] + (double)i[0] * (i[4] == 1 || i[4] == 4 ? i[1] / 2 : i[1]));
             break;
         }
         case DS_OP_CONV3X3: {
             GemmParams g;
-            const int Ho = i[6] ? (i[8] ? i[8] : 2 * i[1]) : (i[5] == 2 ? (i[1] + 1) / 2 : i[1]);
-            const int Wo = i[6] ? (i[9] ? i[9] : 2 * i[2]) : (i[5] == 2 ? (i[2] + 1) / 2 : i[2]);
-            g.M = i[0] * Ho * Wo; g.N = i[4]; g.K = 9 * i[3];
-            g.conv = 1;
-            g.Hin = i[1]; g.Win = i[2]; g.Cin = i[3]; g.Hout = Ho; g.Wout = Wo; g.cstride = i[5]; g.upsample = i[6] != 0;
-            g.up_fold = i[6] == 2;
-            nm = ds_gemm_kernel_name(g, 1);
+            nm = conv3x3_params(g, *op) == 0 ? ds_gemm_kernel_name(g, 1) : "refused";
             // i[6] == 2 (folded x2 upsample, 4 taps executed): still the ALGORITHMIC work of the nearest x2 + 3 x 3 it replaces
             fl = 2.0 * g.M * (double)g.N * g.K;
             by = 2.0 * ((double)i[0] * i[1] * i[2] * i[3] + (double)g.N * g.K + (double)g.M * g.N);

@@ -56,10 +56,13 @@ struct GemmParams {
                      //   stride 2 - output (Y, X) reads rows 2Y + ky, columns 2X + kx, Hout = Hin / 2 (ds_conv3x3_down_f16 / _bf16).
                      //   Host dispatch only (a template argument of the kernels); last, so that no other field moves
 };
+// gemm.hip's route() is the one authority on which kernel serves a GEMM / 3x3 convolution: the launch, the name and the two
+// planner queries below all read its answer (a problem no kernel serves: the launch fails, the name is "refused")
 int ds_launch_gemm(const GemmParams& p, int batch, hipStream_t stream);
-int ds_gemm_conv_gn_chunks(const GemmParams& p);  // gemm.hip: GroupNorm partial chunks per image the conv dispatch would emit (0: none)
-int ds_gemm_ln_kind(int M, int N, int K, int batch, int epi);  // fused LayerNorm: 1 = gemm_pp_kernel, 2 = 128-wide kernels, 0 = none
+int ds_gemm_conv_gn_chunks(const GemmParams& p);  // GroupNorm partial chunks per image the routed conv kernel would emit (0: none)
+int ds_gemm_ln_kind(int M, int N, int K, int batch, int epi);  // fused LayerNorm, the role-free problem's route: 1 = gemm_pp_kernel, 2 = 128-wide kernels, 0 = none
 bool ds_gemm_pp_applicable(const GemmParams& p);  // gemm_pp.hip: 256 x 256 ping-pong kernel takes this shape
+bool ds_gemm_pp_fused_tiles(int M, int N, int epi, bool swapped, int debug);  // ... and its fused-LayerNorm epilogues these tiles
 int ds_launch_gemm_pp(const GemmParams& p, int batch, hipStream_t stream);
 bool ds_conv_halo_applicable(const GemmParams& p);  // conv_halo.hip: halo-patch 3x3 convolution takes this shape
 int ds_launch_conv_halo(const GemmParams& p, hipStream_t stream);
@@ -68,7 +71,7 @@ int ds_conv_halo_gn_chunks(const GemmParams& p);  // pixel tiles per image of th
 int ds_launch_fold_upsample2x(const half_t* w, half_t* out, int Cout, int Cin, hipStream_t stream);  // [Cout][9 Cin] -> [4][Cout][4 Cin]
 void ds_conv_halo_set_variant(int v);  // 0 auto, 1 8x16-pixel blocks, 2 16x16-pixel blocks, 3 ring-buffered 8x16 blocks, 4 auto without the ring-buffered kernel
 void ds_conv_halo_set_deep_blocks(int v);  // the ring-buffered 8x16 kernel takes grids of <= v blocks per CU (default 1)
-const char* ds_gemm_kernel_name(const GemmParams& p, int batch);  // the instantiation ds_launch_gemm dispatches to
+const char* ds_gemm_kernel_name(const GemmParams& p, int batch);  // route(p, batch).name: the instantiation ds_launch_gemm runs, or "refused"
 void ds_gemm_set_debug(int v);
 void ds_gemm_set_ring(int v);     // 0 auto (ring-buffered kernel for small grids), 1 never
 void ds_gemm_set_pp_narrow(int v);  // 0 auto, 1: N, K <= 640 projections never on gemm_pp_kernel (A/B)
@@ -126,7 +129,6 @@ int ds_launch_layernorm(const half_t* x, half_t* y, const half_t* gamma, const h
                         float eps, hipStream_t stream);
 // row statistics of a fused LayerNorm: partial [strips][M] float2 (sum, sum of squares) -> stats [M] float2 (mean, rstd)
 int ds_launch_ln_finalize(const float* partial, float* stats, int M, int strips, int C, float eps, hipStream_t stream);
-bool ds_gemm_pp_fast_path(int M, int N, int K, int batch, int epi);  // gemm.hip: such a GEMM runs gemm_pp_kernel's branch-free epilogues
 
 // ---- attention -------------------------------------------------------------------------------------
 struct SelfAttnParams {

@@ -820,7 +820,7 @@ int launch_ring(const GemmParams& p0, int batch, hipStream_t stream) {
     return 0;
 }
 
-enum Kind { K_REG, K_GLDS2, K_GLDS1, K_PP, K_HALO, K_RING, K_T160, K_G320 };
+enum Kind { K_REG, K_GLDS2, K_GLDS1, K_PP, K_HALO, K_RING, K_T160, K_G320, K_DOWN, K_DOWN_BF16 };
 struct Choice {
     Kind kind;
     int bm;   // rows of the block tile
@@ -917,68 +917,138 @@ Choice choose(const GemmParams& p, int batch) {
     return c;
 }
 
-}  // namespace
 
-// Would ds_launch_gemm run this plain f16 GEMM on gemm_pp_kernel with every tile on a branch-free epilogue?  (The launch-plan
-// builder asks before it replaces a LayerNorm launch by the fused producer / consumer pair.)
-bool ds_gemm_pp_fast_path(int M, int N, int K, int batch, int epi) {
-    return ds_gemm_ln_kind(M, N, K, batch, epi) == 1;
-}
+// ---------------------------------------------------------------------------------------------- the route
+// THE decision which kernel serves a problem - the launch, its name (ds_gemm_kernel_name -> ds_op_describe, the roofline table,
+// the tests' kernel assertions) and the planner's queries (ds_gemm_ln_kind, ds_gemm_conv_gn_chunks) all read this one answer.
+// choose() above is the automatic rule for a problem without a role; the roles a problem names (packed layouts, fused LayerNorm,
+// element type, statistics format) then keep, move or refuse that choice.  Pure host logic under the calling thread's knobs:
+// no launch, no error set; `refusal` is a format string over (M, N, K), null when the problem is served.
+struct Route {
+    Kind kind;
+    int bm;   // tile rows, or ring depth for K_RING
+    const char* name;
+    const char* refusal;
+};
 
-// Which fused-LayerNorm implementation would ds_launch_gemm use for this plain f16 GEMM: 1 = gemm_pp_kernel (every tile on
-// a branch-free epilogue: M, N multiples of 256; consumers read the (mean, rstd) of ds_launch_ln_finalize), 2 = the 128-wide
-// LDS-DMA kernels (their shared epilogue; consumers finalise the partial sums themselves: GemmParams::ln_partial), 0 = neither
-// (register-staged fallback, ragged N, a forced A/B family).
-int ds_gemm_ln_kind(int M, int N, int K, int batch, int epi) {
-    GemmParams p;
-    p.M = M; p.N = N; p.K = K; p.lda = K; p.ldw = K; p.ldc = N; p.epi = epi; p.K1 = K;
-    // the 320-packed GEGLU projection (gemm_g320_kernel) consumes partial sums like the 128-wide kernels
-    if (epi == EPI_GEGLU320) return (M > 0 && batch == 1 && N > 0 && N % 320 == 0 && K > 0 && K % 64 == 0) ? 2 : 0;
-    if (M <= 0 || N <= 0 || K <= 0 || batch < 1 || (epi != EPI_NONE && epi != EPI_GEGLU)) return 0;
-    // gemm_pp_kernel's fused epilogues: whole 256-row tiles; whole 256-column tiles, or - plain epilogue, unbatched (the batched
-    // problem is the operand-swapped consumer, whose statistics run along the tile columns) - whole 64-column strips
-    const bool cols_ok = N % 256 == 0 || (N % 64 == 0 && epi == EPI_NONE && batch == 1 && (g_gemm_debug & 4096) == 0);
-    // (rows: whole tiles; the operand-swapped consumer - the batched problem - skips 32-row pieces past M)
-    const bool rows_ok = M % 256 == 0 || (batch > 1 && M % 32 == 0);
-    if (g_gemm_variant == 3) return (rows_ok && cols_ok && ds_gemm_pp_applicable(p)) ? 1 : 0;
-    if (g_gemm_variant != 0) return 0;
-    const Kind k = choose(p, batch).kind;
-    if (k == K_PP) return (rows_ok && cols_ok) ? 1 : 0;
-    if ((k == K_GLDS1 || k == K_GLDS2 || k == K_RING || k == K_T160 || k == K_G320) && K % 64 == 0) return 2;   // (a PRODUCER also needs N % 128 == 0 and no batch)
-    return 0;
-}
+bool wide_kind(Kind k) { return k == K_GLDS1 || k == K_GLDS2 || k == K_RING || k == K_T160 || k == K_G320; }
 
-const char* ds_gemm_kernel_name(const GemmParams& p, int batch) {
-    if (p.epi == EPI_GEGLU320) return "gemm_g320_kernel";
-    // the fused-LayerNorm instantiations of gemm_pp_kernel are kernels of their own in a rocprofv3 trace (template argument FUSE)
-    if (p.ln_stats && !p.ln_partial) return p.ln_swapped ? "gemm_pp_kernel<0,4>" : p.epi == EPI_GEGLU ? "gemm_pp_kernel<0,9>" : "gemm_pp_kernel<0,1>";
-    if (p.stats_out && ds_gemm_ln_kind(p.M, p.N, p.K, batch, p.epi) == 1) return "gemm_pp_kernel<0,2>";
-    if (p.conv && p.pad_lo == 0) return p.dtype == DS_DTYPE_F16 ? "gemm_glds_kernel<64,true,1,0>" : "gemm_f16_kernel<64,true,0,bf16>";
-    Choice c = choose(p, batch);
+// the instantiation as a rocprofv3 kernel trace spells it (gemm_pp_kernel's fused-LayerNorm forms are its template argument FUSE)
+const char* kernel_name(const GemmParams& p, int batch, Kind kind, int bm) {
     const bool conv = p.conv != 0;
-    if (conv && p.up_fold) c.kind = K_HALO;   // folded phase weights: the halo-patch kernels are the only readers of that layout
-    switch (c.kind) {
-        case K_PP: return "gemm_pp_kernel<0,0>";
+    switch (kind) {
+        case K_PP:
+            if (p.ln_stats) return p.ln_swapped ? "gemm_pp_kernel<0,4>" : p.epi == EPI_GEGLU ? "gemm_pp_kernel<0,9>" : "gemm_pp_kernel<0,1>";
+            return p.stats_out ? "gemm_pp_kernel<0,2>" : "gemm_pp_kernel<0,0>";
         case K_HALO: return ds_conv_halo_kernel_name(p);
-        case K_RING: return c.bm == 4 ? "gemm_glds_kernel<64,false,4>" : "gemm_glds_kernel<64,false,3>";
+        case K_RING: return bm == 4 ? "gemm_glds_kernel<64,false,4>" : "gemm_glds_kernel<64,false,3>";
         case K_T160: return ds_gemm_t160_rows(p.M, p.N, p.K, batch) == 128 ? "gemm_t160_kernel<128 rows>" : "gemm_t160_kernel";
-        case K_G320: return "gemm_g320_kernel<plain>";
+        case K_G320: return p.epi == EPI_GEGLU320 ? "gemm_g320_kernel" : "gemm_g320_kernel<plain>";
+        case K_DOWN: return "gemm_glds_kernel<64,true,1,0>";
+        case K_DOWN_BF16: return "gemm_f16_kernel<64,true,0,bf16>";
         case K_GLDS1:
-            if (c.bm == 128) return conv ? "gemm_glds_kernel<128,true,1>" : "gemm_glds_kernel<128,false,1>";
+            if (bm == 128) return conv ? "gemm_glds_kernel<128,true,1>" : "gemm_glds_kernel<128,false,1>";
             return conv ? "gemm_glds_kernel<64,true,1>" : "gemm_glds_kernel<64,false,1>";
         case K_GLDS2:
-            if (c.bm == 128) return conv ? "gemm_glds_kernel<128,true,2>" : "gemm_glds_kernel<128,false,2>";
+            if (bm == 128) return conv ? "gemm_glds_kernel<128,true,2>" : "gemm_glds_kernel<128,false,2>";
             return conv ? "gemm_glds_kernel<64,true,2>" : "gemm_glds_kernel<64,false,2>";
         default:
-            if (c.bm == 128) return conv ? "gemm_f16_kernel<128,true>" : "gemm_f16_kernel<128,false>";
+            if (bm == 128) return conv ? "gemm_f16_kernel<128,true>" : "gemm_f16_kernel<128,false>";
             return conv ? "gemm_f16_kernel<64,true>" : "gemm_f16_kernel<64,false>";
     }
 }
 
-// GroupNorm statistics out of a 3x3 convolution: only the halo-patch kernels emit them, so the answer follows the dispatch
+// the kernel kind alone; *refusal is set where no kernel serves what the problem names
+Choice route_kind(const GemmParams& p, int batch, const char** refusal) {
+    const bool conv = p.conv != 0;
+    // W packed in 320-row groups (engine.pack_geglu320): one kernel reads that layout
+    if (p.epi == EPI_GEGLU320) return {K_G320, 256};
+    // Downsample2D(padding=0) of the VAE encoder: one instantiation per storage type, no A/B families (gemm_glds_kernel<.., PAD>;
+    // bf16: register-staged gather, the LDS-DMA kernels and their epilogue are f16 only)
+    if (conv && p.pad_lo != 1) return {p.dtype == DS_DTYPE_F16 ? K_DOWN : K_DOWN_BF16, 64};
+    Choice c = choose(p, batch);
+    if (conv && p.up_fold) {   // folded phase weights [4][N][4 Cin]: only the halo-patch kernels read that layout, whatever A/B knob is set
+        if (!ds_conv_halo_applicable(p)) *refusal = "conv3x3: the folded x2 upsample needs the halo-patch kernels (stride 1, Cin %% 64 == 0)";
+        c.kind = K_HALO;
+    }
+    if (p.ln_stats || p.ln_c || p.stats_out) {
+        // Fused LayerNorm.  The planner asks ds_gemm_ln_fusable which form the dispatch gives a shape and builds the pair
+        // accordingly; a direct call is served by whichever family implements the role it names:
+        //   consumer of finalised statistics, operand-swapped consumer: gemm_pp_kernel (whole 256 x 256 tiles);
+        //   consumer of partial sums: the 128-wide kernels (shared epilogue of this file);
+        //   producer: the consumer's family if the call is both, else what the dispatch picks, else whichever can.
+        const bool pp_ok = ds_gemm_pp_applicable(p) && ds_gemm_pp_fused_tiles(p.M, p.N, p.epi, p.ln_swapped != 0, g_gemm_debug);
+        const bool wide_ok = batch == 1 && p.N % 128 == 0 && p.K % 64 == 0;
+        const bool was_wide = wide_kind(c.kind);
+        auto force_wide = [&]() {
+            if (!was_wide) c = {K_GLDS1, (long)((p.M + 127) / 128) * ((p.N + 127) / 128) < 384 ? 64 : 128};
+        };
+        const char* no_stats = "gemm: LayerNorm statistics cannot be emitted for M=%d N=%d K=%d";
+        if (p.ln_stats && p.ln_partial) {
+            force_wide();
+        } else if (p.ln_stats) {
+            if (!(pp_ok && p.ln_c)) *refusal = "gemm: a consumer of finalised LayerNorm statistics needs the 256 x 256 kernel (M=%d N=%d K=%d)";
+            c.kind = K_PP;
+        }
+        if (p.stats_out && !*refusal) {
+            if (p.epi != EPI_NONE || p.ln_swapped) {
+                *refusal = "gemm: LayerNorm statistics come out of the plain epilogue only";
+            } else if (p.ln_stats) {
+                if (c.kind != K_PP && !wide_ok) *refusal = no_stats;
+            } else if (c.kind == K_PP ? !pp_ok : !(was_wide && wide_ok)) {
+                if (!pp_ok && !wide_ok) *refusal = no_stats;
+                if (pp_ok) c.kind = K_PP; else force_wide();
+            }
+        }
+    }
+    if (p.dtype != DS_DTYPE_F16 && !*refusal) {  // bf16 (VAE decoder): only the two kernels that are templated on the element type
+        if (conv) {
+            if (!ds_conv_halo_applicable(p)) *refusal = "conv3x3 bf16: needs stride 1 and Cin %% 64 == 0";
+            c.kind = K_HALO;
+        } else {
+            if (!ds_gemm_pp_applicable(p)) *refusal = "gemm bf16: needs M, N %% 16 == 0 and K %% 128 == 0 (M=%d N=%d K=%d)";
+            c.kind = K_PP;
+        }
+    }
+    // The statistics format is the planner's request: 160 (three entries per 160-column tile) only because ds_gemm_t160_fits said
+    // yes at plan time.  Any other kernel writes one entry per 64 columns - N / 64 of the 3 N / 160 its consumers add - so a
+    // launch that lands elsewhere (an A/B knob set on the launching thread since) is refused instead of leaving wrong statistics.
+    if (p.stats_out && !*refusal && !(p.stats_strip == 160 ? c.kind == K_T160 : (p.stats_strip == 0 || p.stats_strip == 64)))
+        *refusal = "gemm: LayerNorm statistics format (stats_strip) is not what the dispatched kernel emits (M=%d N=%d K=%d)";
+    return c;
+}
+
+Route route(const GemmParams& p, int batch) {
+    const char* refusal = nullptr;
+    const Choice c = route_kind(p, batch, &refusal);
+    return {c.kind, c.bm, refusal ? "refused" : kernel_name(p, batch, c.kind, c.bm), refusal};
+}
+
+}  // namespace
+
+// Which fused-LayerNorm implementation the route gives this plain f16 GEMM (asked without roles, before the pair is built):
+// 1 = gemm_pp_kernel (every tile on a fused epilogue: ds_gemm_pp_fused_tiles; consumers read the (mean, rstd) of
+// ds_launch_ln_finalize), 2 = the 128-wide LDS-DMA kernels (their shared epilogue; consumers finalise the partial sums themselves:
+// GemmParams::ln_partial; a PRODUCER also needs N % 128 == 0 and no batch), 0 = neither (register-staged fallback, ragged N, a
+// forced A/B family other than gemm_variant 3).
+int ds_gemm_ln_kind(int M, int N, int K, int batch, int epi) {
+    // the 320-packed GEGLU projection (gemm_g320_kernel) consumes partial sums like the 128-wide kernels
+    if (epi == EPI_GEGLU320) return (M > 0 && batch == 1 && N > 0 && N % 320 == 0 && K > 0 && K % 64 == 0) ? 2 : 0;
+    if (M <= 0 || N <= 0 || K <= 0 || batch < 1 || (epi != EPI_NONE && epi != EPI_GEGLU)) return 0;
+    GemmParams p;
+    p.M = M; p.N = N; p.K = K; p.lda = K; p.ldw = K; p.ldc = N; p.epi = epi; p.K1 = K;
+    const Kind k = route(p, batch).kind;
+    // (the batched problem is the operand-swapped consumer, whose statistics run along the tile columns)
+    if (k == K_PP) return ds_gemm_pp_fused_tiles(M, N, epi, batch > 1, g_gemm_debug) ? 1 : 0;
+    return g_gemm_variant == 0 && wide_kind(k) ? 2 : 0;
+}
+
+const char* ds_gemm_kernel_name(const GemmParams& p, int batch) { return route(p, batch).name; }
+
+// GroupNorm statistics out of a 3x3 convolution: only the halo-patch kernels emit them, so the answer follows the route
 int ds_gemm_conv_gn_chunks(const GemmParams& p) {
-    if (!p.conv || choose(p, 1).kind != K_HALO) return 0;
-    return ds_conv_halo_gn_chunks(p);
+    const Route r = route(p, 1);
+    return p.conv && !r.refusal && r.kind == K_HALO ? ds_conv_halo_gn_chunks(p) : 0;
 }
 
 int ds_launch_gemm(const GemmParams& p_in, int batch, hipStream_t stream) {
@@ -997,92 +1067,43 @@ int ds_launch_gemm(const GemmParams& p_in, int batch, hipStream_t stream) {
         DS_REQUIRE(p.A2 == nullptr || (p.K1 % 64 == 0 && p.lda2 % 8 == 0), "gemm: split-A needs K1 %% 64 == 0");
     }
     if (p.epi == EPI_GEGLU) DS_REQUIRE(p.N % 128 == 0, "geglu: packed N (%d) must be a multiple of 128", p.N);
-    if (p.epi == EPI_GEGLU320) {   // W packed in 320-row groups (engine.pack_geglu320): one kernel reads that layout
+    if (p.epi == EPI_GEGLU320)
         DS_REQUIRE(ds_gemm_g320_possible(p, batch), "geglu320: plain f16 GEMM, batch 1, N %% 320 == 0, K %% 64 == 0, no residual (M=%d N=%d K=%d)", p.M, p.N, p.K);
-        return ds_launch_gemm_g320(p, stream);
-    }
     if (conv && p.pad_lo != 1) {
-        // Downsample2D(padding=0) of the VAE encoder: one instantiation per storage type, no A/B families (gemm_glds_kernel<.., PAD>)
         DS_REQUIRE(p.pad_lo == 0 && p.cstride == 2 && !p.upsample && !p.rowbias && !p.gn_partial && p.epi == EPI_NONE &&
                        !p.ln_stats && !p.ln_c && !p.stats_out,
                    "conv3x3: pad_lo = %d serves the plain stride-2 convolution with padding (0,1,0,1) only", p.pad_lo);
         DS_REQUIRE(p.Hout == p.Hin / 2 && p.Wout == p.Win / 2 && p.Hout > 0 && p.Wout > 0,
                    "conv3x3 down: output %d x %d is not floor(%d / 2) x floor(%d / 2)", p.Hout, p.Wout, p.Hin, p.Win);
-        if (p.dtype == DS_DTYPE_F16) return launch_glds1<64, true, 0>(p, 1, stream);
-        DS_REQUIRE(!p.residual, "conv3x3 down bf16: no residual");
-        return launch_down_bf16(p, stream);
+        DS_REQUIRE(p.dtype == DS_DTYPE_F16 || !p.residual, "conv3x3 down bf16: no residual");
     }
-    Choice c = choose(p, batch);
-    if (conv && p.up_fold) {   // folded phase weights [4][N][4 Cin]: only the halo-patch kernels read that layout, whatever A/B knob is set
-        DS_REQUIRE(ds_conv_halo_applicable(p), "conv3x3: the folded x2 upsample needs the halo-patch kernels (stride 1, Cin %% 64 == 0)");
-        c.kind = K_HALO;
-    }
-    DS_REQUIRE(!p.gn_partial || (conv && c.kind == K_HALO && p.dtype == DS_DTYPE_F16),
-               "conv3x3: GroupNorm statistics come out of the halo-patch kernels only (ask ds_conv3x3_gn_chunks first)");
-    if (p.ln_stats || p.ln_c || p.stats_out) {
-        // Fused LayerNorm.  The planner asks ds_gemm_ln_fusable which form the dispatch gives a shape and builds the pair
-        // accordingly; a direct call is served by whichever family implements the role it names:
-        //   consumer of finalised statistics, operand-swapped consumer: gemm_pp_kernel (whole 256 x 256 tiles);
-        //   consumer of partial sums: the 128-wide kernels (shared epilogue of this file);
-        //   producer: the consumer's family if the call is both, else what the dispatch picks, else whichever can.
+    if (p.ln_stats || p.ln_c || p.stats_out) {   // what a fused-LayerNorm role needs of its arguments, whichever kernel serves it
         DS_REQUIRE(!conv && p.dtype == DS_DTYPE_F16 && !p.A2 && !p.rowbias, "gemm: fused LayerNorm is a plain f16 GEMM feature");
-        const bool pp_ok = ds_gemm_pp_applicable(p) &&
-                           (p.ln_swapped || (p.M % 256 == 0 && (p.N % 256 == 0 || (p.N % 64 == 0 && p.epi == EPI_NONE && (g_gemm_debug & 4096) == 0))));
-        const bool wide_ok = batch == 1 && p.N % 128 == 0 && p.K % 64 == 0;
-        const bool wide_kind = c.kind == K_GLDS1 || c.kind == K_GLDS2 || c.kind == K_RING || c.kind == K_T160 || c.kind == K_G320;
-        auto force_wide = [&]() {
-            if (!wide_kind) { c.kind = K_GLDS1; c.bm = (long)((p.M + 127) / 128) * ((p.N + 127) / 128) < 384 ? 64 : 128; }
-        };
-        if (p.ln_stats && p.ln_partial) {
+        if (p.ln_stats && p.ln_partial)
             DS_REQUIRE(p.K % 64 == 0 && p.ln_c && (p.ln_swapped ? (p.ln_rows > 0 && p.ln_bstride > 0 && !p.bias) : batch == 1),
                        "gemm: a consumer of partial LayerNorm sums needs K %% 64 == 0 (M=%d N=%d K=%d)", p.M, p.N, p.K);
-            force_wide();
-        } else if (p.ln_stats) {
-            DS_REQUIRE(pp_ok && p.ln_c, "gemm: a consumer of finalised LayerNorm statistics needs the 256 x 256 kernel (M=%d N=%d K=%d)", p.M, p.N, p.K);
-            c.kind = K_PP;
-        }
-        if (p.stats_out) {
-            DS_REQUIRE(p.epi == EPI_NONE && !p.ln_swapped, "gemm: LayerNorm statistics come out of the plain epilogue only");
-            if (p.ln_stats) {
-                DS_REQUIRE(c.kind == K_PP || wide_ok, "gemm: LayerNorm statistics cannot be emitted for M=%d N=%d K=%d", p.M, p.N, p.K);
-            } else if (c.kind == K_PP ? !pp_ok : !(wide_kind && wide_ok)) {
-                DS_REQUIRE(pp_ok || wide_ok, "gemm: LayerNorm statistics cannot be emitted for M=%d N=%d K=%d", p.M, p.N, p.K);
-                if (pp_ok) c.kind = K_PP; else force_wide();
-            }
-        }
     }
-    if (p.dtype != DS_DTYPE_F16) {  // bf16 (VAE decoder): only the two kernels that are templated on the element type
-        if (conv) {
-            DS_REQUIRE(ds_conv_halo_applicable(p), "conv3x3 bf16: needs stride 1 and Cin %% 64 == 0");
-            c.kind = K_HALO;
-        } else {
-            DS_REQUIRE(ds_gemm_pp_applicable(p), "gemm bf16: needs M, N %% 16 == 0 and K %% 128 == 0 (M=%d N=%d K=%d)", p.M, p.N, p.K);
-            c.kind = K_PP;
-        }
-    }
-    if (p.stats_out) {
-        // The statistics format is the planner's request: 160 (three entries per 160-column tile) only because ds_gemm_t160_fits said
-        // yes at plan time.  Any other kernel writes one entry per 64 columns - N / 64 of the 3 N / 160 its consumers add - so a
-        // launch that lands elsewhere (an A/B knob set on the launching thread since) is refused instead of leaving wrong statistics.
-        DS_REQUIRE(p.stats_strip == 160 ? c.kind == K_T160 : (p.stats_strip == 0 || p.stats_strip == 64),
-                   "gemm: LayerNorm statistics format stats_strip = %d is not what the dispatched kernel emits (M=%d N=%d K=%d)",
-                   p.stats_strip, p.M, p.N, p.K);
-    }
-    switch (c.kind) {
+    const Route r = route(p, batch);
+    DS_REQUIRE(!r.refusal, r.refusal, p.M, p.N, p.K);
+    DS_REQUIRE(!p.gn_partial || (r.kind == K_HALO && p.dtype == DS_DTYPE_F16),
+               "conv3x3: GroupNorm statistics come out of the halo-patch kernels only (ask ds_conv3x3_gn_chunks first)");
+    switch (r.kind) {
         case K_PP: return ds_launch_gemm_pp(p, batch, stream);
         case K_HALO: return ds_launch_conv_halo(p, stream);
-        case K_RING: return c.bm == 4 ? launch_ring<4>(p, batch, stream) : launch_ring<3>(p, batch, stream);
+        case K_RING: return r.bm == 4 ? launch_ring<4>(p, batch, stream) : launch_ring<3>(p, batch, stream);
         case K_T160: return ds_launch_gemm_t160(p, stream);
         case K_G320: return ds_launch_gemm_g320(p, stream);
+        case K_DOWN: return launch_glds1<64, true, 0>(p, 1, stream);
+        case K_DOWN_BF16: return launch_down_bf16(p, stream);
         case K_GLDS1:
-            if (c.bm == 128)
+            if (r.bm == 128)
                 return conv ? launch_glds1<128, true>(p, batch, stream) : launch_glds1<128, false>(p, batch, stream);
             return conv ? launch_glds1<64, true>(p, batch, stream) : launch_glds1<64, false>(p, batch, stream);
         case K_GLDS2:
-            if (c.bm == 128) return conv ? launch<128, true, true>(p, batch, stream) : launch<128, false, true>(p, batch, stream);
+            if (r.bm == 128) return conv ? launch<128, true, true>(p, batch, stream) : launch<128, false, true>(p, batch, stream);
             return conv ? launch<64, true, true>(p, batch, stream) : launch<64, false, true>(p, batch, stream);
         default:
-            if (c.bm == 128) return conv ? launch<128, true, false>(p, batch, stream) : launch<128, false, false>(p, batch, stream);
+            if (r.bm == 128) return conv ? launch<128, true, false>(p, batch, stream) : launch<128, false, false>(p, batch, stream);
             return conv ? launch<64, true, false>(p, batch, stream) : launch<64, false, false>(p, batch, stream);
     }
 }

@@ -1013,13 +1013,20 @@ bool ds_gemm_pp_applicable(const GemmParams& p) {
            (p.epi != EPI_GEGLU || p.N % 128 == 0) && p.lda * 15 + 64 < (1L << 30) && p.ldw * 15 + 64 < (1L << 30);
 }
 
+// Shapes its fused-LayerNorm epilogues take, the one statement of the rule (route() and ds_gemm_ln_kind in gemm.hip, the launch
+// below): whole 256-row tiles (operand-swapped consumer: whole 32-row pieces, the rest of a tile is skipped); whole 256-column
+// tiles, or whole 64-column strips on the plain, unbatched, un-swapped epilogue; gemm_debug & 4096 switches the strips off.
+// `swapped` is the caller's: the planner, which has no roles, passes batch > 1 - the only batched fused problem is that consumer.
+bool ds_gemm_pp_fused_tiles(int M, int N, int epi, bool swapped, int debug) {
+    return (swapped ? M % 32 == 0 : M % 256 == 0) &&
+           (N % 256 == 0 || (N % 64 == 0 && epi == EPI_NONE && !swapped && (debug & 4096) == 0));
+}
+
 int ds_launch_gemm_pp(const GemmParams& p0, int batch, hipStream_t stream) {
     GemmParams p = p0;
     DS_REQUIRE(ds_gemm_pp_applicable(p), "gemm_pp: shape M=%d N=%d K=%d not supported", p.M, p.N, p.K);
     if (p.ln_stats || p.ln_c || p.stats_out) {  // fused LayerNorm: only the branch-free epilogues implement it
-        DS_REQUIRE((p.ln_swapped ? p.M % 32 == 0 : p.M % 256 == 0) &&
-                       (p.N % 256 == 0 || (p.N % 64 == 0 && p.epi == EPI_NONE && !p.ln_swapped && (p.debug & 4096) == 0)) &&
-                       !p.rowbias && (p.epi == EPI_NONE || p.epi == EPI_GEGLU),
+        DS_REQUIRE(ds_gemm_pp_fused_tiles(p.M, p.N, p.epi, p.ln_swapped != 0, p.debug) && !p.rowbias && (p.epi == EPI_NONE || p.epi == EPI_GEGLU),
                    "gemm_pp: fused LayerNorm needs whole 256-row tiles (operand-swapped: whole 32-row pieces), whole 256-column tiles (plain epilogue: whole 64-column strips) and no row bias (M=%d N=%d epi=%d)", p.M, p.N, p.epi);
         DS_REQUIRE(batch == 1 || (p.ln_swapped && p.ln_stats), "gemm_pp: only the operand-swapped fused consumer is batched");
         DS_REQUIRE((p.ln_stats != nullptr) == (p.ln_c != nullptr), "gemm_pp: ln_stats and ln_c come as a pair");

@@ -609,7 +609,9 @@ typedef struct ds_op {
 
 typedef struct ds_plan ds_plan;
 int ds_op_run(const ds_op* op, void* stream); /* run one op immediately */
-/* roofline accounting: kernel the op dispatches to (rocprofv3 spelling), algorithmic flops (2*MAC) and HBM bytes */
+/* roofline accounting: kernel the op's launch runs under the calling thread's options (rocprofv3 spelling), algorithmic flops
+ * (2*MAC) and HBM bytes.  A GEMM / CONV3X3 op that no kernel serves (ds_op_run of it fails) is named "refused"; the call still
+ * returns 0 with the op's flops and bytes. */
 int ds_op_describe(const ds_op* op, char* name, int name_len, double* flops, double* bytes);
 int ds_plan_create(const ds_op* ops, int n_ops, ds_plan** out);
 int ds_plan_num_ops(const ds_plan* plan);

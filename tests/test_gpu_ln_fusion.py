@@ -181,9 +181,50 @@ def test_consumer_swapped_vs_layernorm_linear(hip_lib, Z, N, C):
 
 
 # ---- the same pair on the 128-wide LDS-DMA kernels (csrc/gemm.hip "Fused LayerNorm"): small batches and the 640-channel level
-@pytest.mark.parametrize("M,N,K,res", [(2048, 1280, 1280, True), (8192, 640, 640, True), (2048, 1280, 5120, True),
-                                       (1000, 640, 2560, False), (154, 1280, 1280, True)])
-def test_wide_producer_row_statistics(hip_lib, M, N, K, res):
+def _knob_cases(cases, forced):
+    """The cases under the automatic dispatch (ids as pytest would spell them) + `forced`: (values..., gemm_variant) cases whose
+    role moves the launch OFF the kernel that knob picks for the role-free problem."""
+    return ([pytest.param(*c, 0, id="-".join(str(v) for v in c)) for c in cases] +
+            [pytest.param(*c, id="-".join(str(v) for v in c[:-1]) + f"-gemm_variant{c[-1]}") for c in forced])
+
+
+class _forced_route:
+    """`with _forced_route(variant, **slots)`: gemm_variant set on this thread (reset on exit), after checking that ds_op_describe
+    of the equivalent DS_OP_GEMM names the 64-row one-buffer kernel the role is moved to - the launch that really happens."""
+
+    def __init__(self, variant, M, N, K, **slots):
+        self.variant, self.shape, self.slots = variant, (M, N, K), slots
+
+    def __enter__(self):
+        import ctypes as C
+        from diffsensei_amd import _lib
+        from diffsensei_amd.engine import make_op
+        self.lib = _lib.load()
+        if not self.variant:
+            return self
+        M, N, K = self.shape
+        s = self.slots
+        op = make_op("GEMM", i=(M, N, K, K, 0, 1, 0, 1, 0, int(s.get("ln_partial", 0))), f=(1e-5,), l=(K, 0, K, N, N),
+                     p=(4096, None, 4096, 4096, 4096, None, s.get("residual"), s.get("ln_stats"), s.get("ln_c"), s.get("stats_out")))
+        name = C.create_string_buffer(96)
+        assert self.lib.ds_set_option(b"gemm_variant", self.variant) == 0
+        try:
+            assert self.lib.ds_op_describe(C.byref(op), name, 96, None, None) == 0
+            assert name.value.decode() == "gemm_glds_kernel<64,false,1>", name.value.decode()
+        except BaseException:
+            self.lib.ds_set_option(b"gemm_variant", 0)
+            raise
+        return self
+
+    def __exit__(self, *exc):
+        self.lib.ds_set_option(b"gemm_variant", 0)
+
+
+# (272, 256, 128) under gemm_variant 3: the role-free choice is the ping-pong kernel, M is no multiple of 256 -> the 128-wide kernel
+@pytest.mark.parametrize("M,N,K,res,variant", _knob_cases([(2048, 1280, 1280, True), (8192, 640, 640, True), (2048, 1280, 5120, True),
+                                                           (1000, 640, 2560, False), (154, 1280, 1280, True)],
+                                                          [(272, 256, 128, False, 3)]))
+def test_wide_producer_row_statistics(hip_lib, M, N, K, res, variant):
     """Producer on the 64 x 128 / 128 x 128 kernels (ring-buffered and one-buffer variants, ragged M): same statistics format
     as gemm_pp_kernel's, the stored output bit-identical to the GEMM without statistics."""
     from diffsensei_amd import ops
@@ -192,7 +233,8 @@ def test_wide_producer_row_statistics(hip_lib, M, N, K, res):
     x, w, b = _r((M, K), g), _r((N, K), g, 1 / math.sqrt(K)), _r((N,), g)
     r = (_r((M, N), g) * 3 + 1.5).half() if res else None
     dv = lambda t: None if t is None else t.to(DEV)
-    y, part = ops.gemm_ln(dv(x), dv(w), dv(b), residual=dv(r), emit_stats=True)
+    with _forced_route(variant, M, N, K, stats_out=4096):
+        y, part = ops.gemm_ln(dv(x), dv(w), dv(b), residual=dv(r), emit_stats=True)
     assert torch.equal(y, ops.gemm(dv(x), dv(w), dv(b), dv(r))), "statistics emission changed the stored output"
     yf = y.float().cpu()
     strips = yf.view(M, N // 64, 64)
@@ -200,9 +242,11 @@ def test_wide_producer_row_statistics(hip_lib, M, N, K, res):
     assert torch.allclose(part[..., 1].t().cpu(), (strips * strips).sum(-1), rtol=1e-5, atol=1e-3)
 
 
-@pytest.mark.parametrize("M,N,K,offset", [(2048, 1280, 1280, 0.0), (8192, 640, 640, 0.3), (1000, 1280, 640, 0.0),
-                                          (2048, 2560, 1280, 8.0), (64, 128, 64, 0.0)])
-def test_wide_consumer_plain_vs_layernorm_linear(hip_lib, M, N, K, offset):
+# (272, 256, 128) under gemm_variant 1 (register staging) and 3 (ping-pong): a consumer of partial sums runs the 128-wide kernel all the same
+@pytest.mark.parametrize("M,N,K,offset,variant", _knob_cases([(2048, 1280, 1280, 0.0), (8192, 640, 640, 0.3), (1000, 1280, 640, 0.0),
+                                                              (2048, 2560, 1280, 8.0), (64, 128, 64, 0.0)],
+                                                             [(272, 256, 128, 0.0, 1), (272, 256, 128, 0.0, 3)]))
+def test_wide_consumer_plain_vs_layernorm_linear(hip_lib, M, N, K, offset, variant):
     """Consumer that sums the partials of its own rows (no finalize launch) vs fp32 LayerNorm + linear, and vs the 256 x 256
     consumer fed by the finalize launch where that one takes the shape: the two agree to the last bits of an f16 almost
     everywhere (same statistics bits by construction; the rank-1 term is an fp32 fma here, an f16 (hi, lo) MFMA there)."""
@@ -215,7 +259,8 @@ def test_wide_consumer_plain_vs_layernorm_linear(hip_lib, M, N, K, offset):
     gw, c2, b2 = _pack(w, b, gamma, beta)
     xs = x.float().view(M, K // 64, 64)
     part = torch.stack([xs.sum(-1).t(), (xs * xs).sum(-1).t()], dim=-1).contiguous().to(DEV)
-    got = ops.gemm_ln_partial(x.to(DEV), gw, b2, c2, part)
+    with _forced_route(variant, M, N, K, ln_stats=4096, ln_c=4096, ln_partial=1):
+        got = ops.gemm_ln_partial(x.to(DEV), gw, b2, c2, part)
     e = _relmax(got, ref)
     line = f"LN -> linear (128-wide kernels) M={M} N={N} K={K} mean/std {offset}: {e:.2e}"
     if M % 256 == 0 and N % 256 == 0 and K % 128 == 0:
