@@ -32,8 +32,6 @@ typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float NEG_BIG = -1.0e30f;
 
-__device__ __forceinline__ int swz(int row, int chunk) { return ((chunk ^ ((row >> 1) & 7)) << 4); }
-
 // 2^x as ONE v_exp_f32.  exp2f() adds a denormal-range rescue (compare, select, ldexp: five more VALU slots per score);
 // softmax arguments are <= 0 and anything below 2^-126 may flush to zero.  The softmax of the flash kernels is VALU
 // bound (32 scores per lane per 16 MFMAs), so every slot per score shows up in the kernel time.

@@ -26,10 +26,7 @@
 //
 // K order: channel slices outer, taps inner (k = tap*Cin + ci in the weight rows) - the sum is the same set of
 // products as the tap-major kernel's, in a different order, so results agree to fp32-accumulation rounding.
-#include <type_traits>
-
-#include "ds_common.h"
-#include "ds_kernels.h"
+#include "ds_epilogue.h"
 
 namespace {
 
@@ -43,8 +40,6 @@ typedef __attribute__((address_space(3))) void lds_void;
 typedef const __attribute__((address_space(1))) void glb_void;
 
 __device__ __attribute__((aligned(256))) char g_halo_zero_page[256];
-
-__device__ __forceinline__ int swz(int row, int chunk) { return ((chunk ^ ((row >> 1) & 7)) << 4); }
 
 // GroupNorm statistics of the block's output tile (GemmParams::gn_partial).  Stage 2 of the epilogue gives thread t the 8
 // channels of chunk t & 15 on rows (t >> 4) + 16 j: it sums the values it STORES (f16, after the residual) and their squares in
@@ -169,15 +164,7 @@ __device__ __forceinline__ void conv_halo_epilogue8(const GemmParams& p, f32x16 
             const int id = tid + 256 * (j0 + u);
             const int row = id >> 4, c = id & 15;
             V8 v = *reinterpret_cast<const V8*>(sC + row * CS_STRIDE + c * 16);
-            if (Rp) {
-                // f16: one v_pk_add_f16 per two values - the same number as (f16)((float)a + (float)b), which never rounds twice
-                // (tests/test_f16_add_equivalence.py); bf16 (VAE decoder) keeps the f32 form
-                if constexpr (std::is_same<T, half_t>::value) v = v + rv[u];
-                else {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = (T)((float)v[e] + (float)rv[u][e]);
-                }
-            }
+            if (Rp) v = add_residual8<T>(v, rv[u]);
             if (ok[u]) *reinterpret_cast<V8*>(reinterpret_cast<T*>(p.C) + mrow[u] * p.ldc + ncol[u]) = v;
             if (p.gn_partial && ok[u]) gn_accumulate(v, gs, gq);
         }
@@ -563,11 +550,6 @@ constexpr int PBYTES2 = PPW2 * 4 * 1024;   // 44 KiB
 
 static_assert(256 * CS_STRIDE + 4096 <= PBYTES2 + 2 * BN * 128, "conv_halo256_kernel: staging tile + GroupNorm partials exceed its LDS");
 
-template <int V>
-struct IC2 {
-    static constexpr int value = V;
-};
-
 template <typename T, int TPS = 9>
 __global__ __launch_bounds__(256, 2) void conv_halo256_kernel(const GemmParams p) {
     constexpr bool FOLD = TPS == 4;
@@ -783,8 +765,8 @@ __global__ __launch_bounds__(256, 2) void conv_halo256_kernel(const GemmParams p
                 }
         }
     };
-    if (p.N - n0 <= 64 && (p.debug & 2048) == 0) body(IC2<1>{});   // gemm_debug bit 11: A/B, tail tiles as full tiles
-    else body(IC2<0>{});
+    if (p.N - n0 <= 64 && (p.debug & 2048) == 0) body(IC<1>{});   // gemm_debug bit 11: A/B, tail tiles as full tiles
+    else body(IC<0>{});
     __syncthreads();
     const T* const Rp = reinterpret_cast<const T*>(p.residual);
     float gs[8], gq[8];
@@ -814,15 +796,7 @@ __global__ __launch_bounds__(256, 2) void conv_halo256_kernel(const GemmParams p
             const int id = tid + 256 * (j0 + u);
             const int row = id >> 4, c = id & 15;
             V8 v = *reinterpret_cast<const V8*>(sC + row * CS_STRIDE + c * 16);
-            if (Rp) {
-                // f16: one v_pk_add_f16 per two values - the same number as (f16)((float)a + (float)b), which never rounds twice
-                // (tests/test_f16_add_equivalence.py); bf16 (VAE decoder) keeps the f32 form
-                if constexpr (std::is_same<T, half_t>::value) v = v + rv[u];
-                else {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = (T)((float)v[e] + (float)rv[u][e]);
-                }
-            }
+            if (Rp) v = add_residual8<T>(v, rv[u]);
             if (ok[u]) *reinterpret_cast<V8*>(reinterpret_cast<T*>(p.C) + mrow[u] * p.ldc + ncol[u]) = v;
             if (p.gn_partial && ok[u]) gn_accumulate(v, gs, gq);
         }

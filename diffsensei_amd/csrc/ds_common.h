@@ -154,6 +154,16 @@ __device__ __forceinline__ float ds_dpp_f32(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
 }
 
+// byte offset of 16-byte chunk `chunk` in a 128-byte LDS row (64 k of f16): the eight chunks of a row XOR-swizzled by the row
+// index, so every ds_read_b128 lane group hits 16 distinct slots
+__device__ __forceinline__ int swz(int row, int chunk) { return ((chunk ^ ((row >> 1) & 7)) << 4); }
+
+// a compile-time integer handed to a generic lambda as an argument (decltype(arg)::value)
+template <int V>
+struct IC {
+    static constexpr int value = V;
+};
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -18,8 +18,7 @@
 // The epilogue is staged through LDS so global stores are full 16 B/lane rows.  Convolution gathers its A tile
 // straight from the NHWC tensor (zero halo, optional stride 2, optional fused nearest x2 upsample) — no im2col
 // buffer ever exists in HBM.
-#include "ds_common.h"
-#include "ds_kernels.h"
+#include "ds_epilogue.h"
 
 static thread_local int g_gemm_variant = 0;  // 0 auto; A/B: 1 register staging, 2 two-buffer glds, 3 ping-pong 256x256, 7 two-buffer BM 64, 8/9 one-buffer glds (BM 128/64), 10 halo conv, 11 64x160 tiles (gemm_t160.hip)
 void ds_gemm_set_variant(int v) { g_gemm_variant = v; }
@@ -37,8 +36,6 @@ constexpr int BK = 64;
 constexpr int CS_STRIDE = 272;  // bytes per row of the epilogue staging tile (128 f16 + 8 pad)
 
 __device__ __attribute__((aligned(256))) char g_zero_page[256];  // zero-initialised: conv halo source
-
-__device__ __forceinline__ int swz(int row, int chunk) { return ((chunk ^ ((row >> 1) & 7)) << 4); }
 
 // ---------------------------------------------------------------------------------------------- MFMA over one k-tile
 template <int WR, int WC = 64, typename T = half_t>  // rows / columns of the block tile owned by one wave (32 * MI, 32 * NI); element type
@@ -79,8 +76,8 @@ __device__ __forceinline__ void mma_tile(const char* cA, const char* cB, f32x16 
 //     (sum, sum of squares) per row and 64-column strip - a 3-step butterfly over the 8 lanes of a strip - go to
 //     stats_out[(n / 64) * M + m] (float2).  Needs N % 128 == 0 (every strip complete).
 //   consumer (p.ln_stats with p.ln_partial): the lane owns tile ROW m in stage 1, so it sums the row's K / 64 partials itself
-//     (the order of ln_finalize_kernel: four interleaved chains, then (0 + 1) + (2 + 3) - the same bits as the finalize
-//     launch the 256 x 256 consumers use) and applies y = rstd (acc - mean c_n) + b'_n in fp32 where the bias add was:
+//     (ds_epilogue.h has the order: the same bits as the finalize launch the 256 x 256 consumers use) and applies
+//     y = rstd (acc - mean c_n) + b'_n in fp32 where the bias add was:
 //     no finalize launch, no LayerNorm launch.  c_n comes as the negated f16 (hi, lo) pair the 256 x 256 kernel uses.
 template <int BM, int WR, int NT, bool LNF = false>  // block rows, rows per wave, threads per block, fused-LayerNorm code compiled in
 __device__ __forceinline__ void epilogue(const GemmParams& p, f32x16 (&acc)[WR / 32][2], char* smem, int m0, int n0,
@@ -110,9 +107,7 @@ __device__ __forceinline__ void epilogue(const GemmParams& p, f32x16 (&acc)[WR /
     const bool ln_col = ln_any && p.ln_swapped;    // operand-swapped form (V^T = Wv X_b^T): they are the tile COLUMNS
     // consumer: (mean, rstd) of the lane's rows from the producer's partial sums.  Every load of every row is in flight at
     // once - ONE round trip to L2 (a chain of loads per row, row after row, cost 15 us per launch: ten round trips in the
-    // epilogue of every block).  The two half-waves hold the same rows: lanes 0..31 sum chains 0 and 1 of ln_finalize_kernel's
-    // four interleaved chains, lanes 32..63 chains 2 and 3, and one cross-half exchange gives (0 + 1) + (2 + 3) - the very
-    // bits of the finalize launch (fp32 addition commutes).
+    // epilogue of every block).  Summation order: ds_epilogue.h.
     float ln_mean[MI], ln_rstd[MI];
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) ln_mean[mi] = 0.f, ln_rstd[mi] = 1.f;
@@ -125,37 +120,10 @@ __device__ __forceinline__ void epilogue(const GemmParams& p, f32x16 (&acc)[WR /
             constexpr int JJ = MI == 1 ? 6 : 3;   // strips per chain and round: 24 (K = 1280 in one round, 20 or 24 entries) or, with two rows per lane, 12
             for (int base = 0; base < strips; base += 4 * JJ) {
                 f32x2 t[MI][2][JJ];
-#pragma unroll
-                for (int mi = 0; mi < MI; ++mi) {
-                    const int m = min(m0 + wm * WR + mi * 32 + l31, p.M - 1);
-                    const f32x2* part = reinterpret_cast<const f32x2*>(p.ln_stats) + m;
-#pragma unroll
-                    for (int cc = 0; cc < 2; ++cc)
-#pragma unroll
-                        for (int jj = 0; jj < JJ; ++jj) {
-                            const int j = base + 2 * lhi + cc + 4 * jj;
-                            t[mi][cc][jj] = part[(long)min(j, strips - 1) * p.M];
-                        }
-                }
-#pragma unroll
-                for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-                    for (int cc = 0; cc < 2; ++cc)
-#pragma unroll
-                        for (int jj = 0; jj < JJ; ++jj) {
-                            const bool in = base + 2 * lhi + cc + 4 * jj < strips;
-                            sa[mi][cc] += in ? t[mi][cc][jj][0] : 0.f;
-                            qa[mi][cc] += in ? t[mi][cc][jj][1] : 0.f;
-                        }
+                ln_part_load<MI, JJ>(t, p.ln_stats, m0 + wm * WR + l31, p.M, base, lhi, strips);
+                ln_part_add<MI, JJ>(sa, qa, t, base, lhi, strips);
             }
-            const float inv_c = 1.0f / (float)p.K;
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi) {
-                const float s2 = sa[mi][0] + sa[mi][1], q2 = qa[mi][0] + qa[mi][1];
-                const float s = s2 + __shfl_xor(s2, 32, 64), q = q2 + __shfl_xor(q2, 32, 64);
-                ln_mean[mi] = s * inv_c;
-                ln_rstd[mi] = rsqrtf(fmaxf(fmaf(-ln_mean[mi], ln_mean[mi], q * inv_c), 0.f) + p.ln_eps);
-            }
+            ln_part_finish<MI>(sa, qa, 1.0f / (float)p.K, p.ln_eps, ln_mean, ln_rstd);
         }
     }
     // operand-swapped form: the statistics of the block's 128 columns = rows bz * ln_bstride + n0 .. of the normalised matrix are
@@ -183,10 +151,7 @@ __device__ __forceinline__ void epilogue(const GemmParams& p, f32x16 (&acc)[WR /
                             qa[q] += in ? t[q][jj][1] : 0.f;
                         }
                 }
-                const float inv_c = 1.0f / (float)p.K;
-                const float mean = ((sa[0] + sa[1]) + (sa[2] + sa[3])) * inv_c;
-                const float var = fmaxf(fmaf(-mean, mean, ((qa[0] + qa[1]) + (qa[2] + qa[3])) * inv_c), 0.f);
-                ln_tab[tid] = f32x2{mean, rsqrtf(var + p.ln_eps)};
+                ln_tab[tid] = ln_mean_rstd((sa[0] + sa[1]) + (sa[2] + sa[3]), (qa[0] + qa[1]) + (qa[2] + qa[3]), 1.0f / (float)p.K, p.ln_eps);
             }
             __syncthreads();
         }
@@ -228,14 +193,11 @@ __device__ __forceinline__ void epilogue(const GemmParams& p, f32x16 (&acc)[WR /
                     const int n = n0 + nl;
                     float v[4];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = acc[mi][ni][4 * g + e] + (float)bq[ni][g][e];
+                    for (int e = 0; e < 4; ++e) v[e] = bias_apply(acc[mi][ni][4 * g + e], bq[ni][g][e]);
                     if constexpr (LNF) {
                         if (ln_in) {
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                const float nc = (float)cq[ni][g][2 * e] + (float)cq[ni][g][2 * e + 1];   // -c_n
-                                v[e] = fmaf(fmaf(mean, nc, acc[mi][ni][4 * g + e]), rstd, (float)bq[ni][g][e]);
-                            }
+                            for (int e = 0; e < 4; ++e) v[e] = ln_apply(acc[mi][ni][4 * g + e], mean, rstd, cq[ni][g][2 * e], cq[ni][g][2 * e + 1], bq[ni][g][e]);
                         }
                         if (ln_col) {
                             const f32x4 t0 = *reinterpret_cast<const f32x4*>(ln_tab + nl), t1 = *reinterpret_cast<const f32x4*>(ln_tab + nl + 2);
@@ -272,14 +234,7 @@ __device__ __forceinline__ void epilogue(const GemmParams& p, f32x16 (&acc)[WR /
                 if (m < p.M && n < (p.N >> 1)) {
                     const h8 hv = *reinterpret_cast<const h8*>(sC + row * CS_STRIDE + c * 16);
                     const h8 gv = *reinterpret_cast<const h8*>(sC + row * CS_STRIDE + 128 + c * 16);
-                    h8 o;
-#pragma unroll
-                    for (int e = 0; e < 8; e += 2) {
-                        const f32x2 ge = ds_gelu_erf2(f32x2{(float)gv[e], (float)gv[e + 1]});
-                        o[e] = (half_t)((float)hv[e] * (float)(half_t)ge[0]);
-                        o[e + 1] = (half_t)((float)hv[e + 1] * (float)(half_t)ge[1]);
-                    }
-                    *reinterpret_cast<h8*>(Cg + (long)m * p.ldc + n) = o;
+                    *reinterpret_cast<h8*>(Cg + (long)m * p.ldc + n) = geglu8(hv, gv);
                 }
             }
         } else {
@@ -317,31 +272,16 @@ __device__ __forceinline__ void epilogue(const GemmParams& p, f32x16 (&acc)[WR /
                             v[e] = (half_t)(f / (1.0f + __expf(-1.702f * f)));
                         }
                     }
-                    if (Rg) {
-                        const h8 rv = rvs[j];
-                        v = v + rv;   // v_pk_add_f16: the same number as (f16)((float)a + (float)b) (tests/test_f16_add_equivalence.py)
-                    }
+                    if (Rg) v = add_residual8<half_t>(v, rvs[j]);
                     *reinterpret_cast<h8*>(Cg + (long)m * p.ldc + n) = v;
                     if constexpr (LNF) {
-                        if (p.stats_out) {
-                            float s1 = 0.f, q1 = 0.f;
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) {
-                                const float f = (float)v[e];
-                                s1 += f;
-                                q1 = fmaf(f, f, q1);
-                            }
-                            sv = s1, qv = q1;
-                        }
+                        if (p.stats_out) sum_sq8(v, sv, qv);
                     }
                 }
                 if constexpr (LNF) {
                     // the 8 lanes c & 7 of a row's 64-column strip: every lane of the wave takes part (rows past M carry zeros)
                     if (p.stats_out) {
-                        sv += ds_dpp_f32<0xB1>(sv);   // lane ^ 1, lane ^ 2, then lane j <-> 7 - j of every 8
-                        qv += ds_dpp_f32<0xB1>(qv);
-                        sv += ds_dpp_f32<0x4E>(sv);
-                        qv += ds_dpp_f32<0x4E>(qv);
+                        quad_sum2(sv, qv);   // lane ^ 1, lane ^ 2, then lane j <-> 7 - j of every 8
                         sv += ds_dpp_f32<0x141>(sv);
                         qv += ds_dpp_f32<0x141>(qv);
                         if ((c & 7) == 0 && m < p.M && n < p.N) {

@@ -37,8 +37,7 @@
 // The tile's bias and (-c hi, -c lo) slices are LDS-DMA pieces of the prologue; the consumer's row statistics (the producer's
 // partial sums, the format of gemm.hip / gemm_t160.hip) are summed in the prologue under the first k-tile's round trip - four
 // floats per lane live across the k-loop.
-#include "ds_common.h"
-#include "ds_kernels.h"
+#include "ds_epilogue.h"
 
 static thread_local int g_g320 = 0;  // 0 auto, 1 never (A/B: ds_set_option "gemm_g320")
 void ds_gemm_set_g320(int v) { g_g320 = v; }
@@ -56,11 +55,6 @@ static_assert(128 * CS <= 2 * STAGE_B, "gemm_g320: the 128-row staging tile lies
 typedef __attribute__((address_space(3))) void lds_void;
 
 constexpr int NWAVES = 8;
-template <int V>
-struct IC3 {
-    static constexpr int value = V;
-};
-
 // GEGLU = false (added at the end of round 6): the same main loop with a PLAIN epilogue (bias or the fused-LayerNorm consumer form,
 // 320 output columns per tile, natural weight order) for the one plain projection whose 256 x 320 grid is exactly one block per CU:
 // q|k at M = 8192, N = 2560 (UNet batch 8 at 1024 x 1024 = BASELINE configs[2]; batch 2 at 2048 x 2048 = configs[4]), 320 tiles of
@@ -132,9 +126,9 @@ __global__ __launch_bounds__(NWAVES * 64, 1) void gemm_g320_kernel(const GemmPar
 
     // ---- prologue: k-tile 0, the tile's bias / c slices (waves 0..2, one piece each; lanes past the slice re-read its last chunk),
     // then the consumer's row statistics - their round trip runs beside the first k-tile's
-    typedef IC3<0> I0;
-    typedef IC3<1> I1;
-    typedef IC3<2> I2;
+    typedef IC<0> I0;
+    typedef IC<1> I1;
+    typedef IC<2> I2;
     issue3(0, 0, I0{});
     issue3(0, 0, I1{});
     issue3(0, 0, I2{});
@@ -143,42 +137,16 @@ __global__ __launch_bounds__(NWAVES * 64, 1) void gemm_g320_kernel(const GemmPar
     if (ln_in && (wave == 1 || wave == 2)) lds_dma16_v(p.ln_c + 2 * n0 + min((wave - 1) * 64 + lane, 79) * 8, lds0 + C_OFF + (wave - 1) * 1024);
     float ln_mean[2] = {0.f, 0.f}, ln_rstd[2] = {1.f, 1.f};
     if (ln_in) {
-        // (mean, rstd) of the lane's two rows from the producer's partial sums, every load in flight at once; the summation
-        // order is the one of gemm.hip's consumer / ln_finalize_kernel (four interleaved chains, (0 + 1) + (2 + 3)): the two
-        // half-waves hold the same rows and take two chains each
+        // (mean, rstd) of the lane's two rows from the producer's partial sums, every load in flight at once (ds_epilogue.h)
         const int strips = p.ln_nstrips > 0 ? p.ln_nstrips : (p.K >> 6);
         constexpr int JJ = 6;
         float sa[2][2] = {{0.f, 0.f}, {0.f, 0.f}}, qa[2][2] = {{0.f, 0.f}, {0.f, 0.f}};
         for (int base = 0; base < strips; base += 4 * JJ) {
             f32x2 t[2][2][JJ];
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) {
-                const int m = min(m0 + wm * 64 + mi * 32 + l31, p.M - 1);
-                const f32x2* part = reinterpret_cast<const f32x2*>(p.ln_stats) + m;
-#pragma unroll
-                for (int cc = 0; cc < 2; ++cc)
-#pragma unroll
-                    for (int jj = 0; jj < JJ; ++jj) t[mi][cc][jj] = part[(long)min(base + 2 * lhi + cc + 4 * jj, strips - 1) * p.M];
-            }
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int cc = 0; cc < 2; ++cc)
-#pragma unroll
-                    for (int jj = 0; jj < JJ; ++jj) {
-                        const bool in = base + 2 * lhi + cc + 4 * jj < strips;
-                        sa[mi][cc] += in ? t[mi][cc][jj][0] : 0.f;
-                        qa[mi][cc] += in ? t[mi][cc][jj][1] : 0.f;
-                    }
+            ln_part_load<2, JJ>(t, p.ln_stats, m0 + wm * 64 + l31, p.M, base, lhi, strips);
+            ln_part_add<2, JJ>(sa, qa, t, base, lhi, strips);
         }
-        const float inv_c = 1.0f / (float)p.K;
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi) {
-            const float s2 = sa[mi][0] + sa[mi][1], q2 = qa[mi][0] + qa[mi][1];
-            const float s = s2 + __shfl_xor(s2, 32, 64), q = q2 + __shfl_xor(q2, 32, 64);
-            ln_mean[mi] = s * inv_c;
-            ln_rstd[mi] = rsqrtf(fmaxf(fmaf(-ln_mean[mi], ln_mean[mi], q * inv_c), 0.f) + p.ln_eps);
-        }
+        ln_part_finish<2>(sa, qa, 1.0f / (float)p.K, p.ln_eps, ln_mean, ln_rstd);
     }
 
     const int nk = p.K / 64;
@@ -242,13 +210,10 @@ __global__ __launch_bounds__(NWAVES * 64, 1) void gemm_g320_kernel(const GemmPar
                         float v[4];
                         if (ln_in) {
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                const float nc = (float)cq[2 * e] + (float)cq[2 * e + 1];   // -c_n
-                                v[e] = fmaf(fmaf(ln_mean[mi], nc, acc[mi][ni][4 * g + e]), ln_rstd[mi], (float)bq[e]);
-                            }
+                            for (int e = 0; e < 4; ++e) v[e] = ln_apply(acc[mi][ni][4 * g + e], ln_mean[mi], ln_rstd[mi], cq[2 * e], cq[2 * e + 1], bq[e]);
                         } else {
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] = acc[mi][ni][4 * g + e] + (float)bq[e];
+                            for (int e = 0; e < 4; ++e) v[e] = bias_apply(acc[mi][ni][4 * g + e], bq[e]);
                         }
                         h4 o;
 #pragma unroll
@@ -278,13 +243,7 @@ __global__ __launch_bounds__(NWAVES * 64, 1) void gemm_g320_kernel(const GemmPar
             const int m = m0 + pass * 128 + row;
             const h8 hv = *reinterpret_cast<const h8*>(sC + row * CS + c * 16);
             const h8 gv = *reinterpret_cast<const h8*>(sC + row * CS + 320 + c * 16);
-            h8 o;
-#pragma unroll
-            for (int e = 0; e < 8; e += 2) {
-                const f32x2 ge = ds_gelu_erf2(f32x2{(float)gv[e], (float)gv[e + 1]});
-                o[e] = (half_t)((float)hv[e] * (float)(half_t)ge[0]);
-                o[e + 1] = (half_t)((float)hv[e + 1] * (float)(half_t)ge[1]);
-            }
+            const h8 o = geglu8(hv, gv);
             if (m < p.M) *reinterpret_cast<h8*>(Cg + (long)m * p.ldc + (n0 >> 1) + c * 8) = o;
         }
     }

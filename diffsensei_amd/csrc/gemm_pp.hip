@@ -85,18 +85,6 @@ static_assert(EX_MAX >= 0 && EX_MAX <= 16, "PP_EX: no epilogue path leaves more 
 typedef __attribute__((address_space(3))) void lds_void;
 typedef const __attribute__((address_space(1))) void glb_void;
 
-template <int V>
-struct IC {
-    static constexpr int value = V;
-};
-
-// v_mov_b32 with a DPP control: 0xB1 = quad_perm [1,0,3,2] (lane ^ 1), 0x4E = quad_perm [2,3,0,1] (lane ^ 2),
-// 0x141 = row_half_mirror (lane j of every 8 <-> lane 7 - j)
-template <int CTRL>
-__device__ __forceinline__ float dpp_f32(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-
 // v_permlane32_swap_b32 vdst, src: lanes 32..63 of vdst <-> lanes 0..31 of src.  Inline asm: through the builtin hipcc has folded
 // uses of the second result away (attention_sp.hip, cross_max); the s_nop covers the VALU-write -> permlane-read hazard.
 __device__ __forceinline__ void swap32(unsigned& vdst, unsigned& src) {
@@ -815,12 +803,12 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
                                 s1 = __builtin_amdgcn_fdot2(pr, h2v{(_Float16)1.f, (_Float16)1.f}, s1, false);
                                 q1 = __builtin_amdgcn_fdot2(pr, pr, q1, false);
                             }
-                            s1 += dpp_f32<0xB1>(s1);
-                            q1 += dpp_f32<0xB1>(q1);
-                            s1 += dpp_f32<0x4E>(s1);
-                            q1 += dpp_f32<0x4E>(q1);
-                            s1 += dpp_f32<0x141>(s1);
-                            q1 += dpp_f32<0x141>(q1);
+                            s1 += ds_dpp_f32<0xB1>(s1);
+                            q1 += ds_dpp_f32<0xB1>(q1);
+                            s1 += ds_dpp_f32<0x4E>(s1);
+                            q1 += ds_dpp_f32<0x4E>(q1);
+                            s1 += ds_dpp_f32<0x141>(s1);
+                            q1 += ds_dpp_f32<0x141>(q1);
                             if ((lane_e & 7) == i) sv = s1, qv = q1;
                         }
                     }

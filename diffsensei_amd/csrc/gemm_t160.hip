@@ -35,8 +35,7 @@
 // planner (GemmParams::stats_strip = 160), and consumers are told the entry count (GemmParams::ln_nstrips); the consumer form
 // finalises its own rows from the partial sums like the 128-wide kernels (gemm.hip).  (First version: five 32-column entries
 // per tile = 40 per row - the consumers' epilogues then needed twice the load rounds: +0.3 ms per batch-2 forward.)
-#include "ds_common.h"
-#include "ds_kernels.h"
+#include "ds_epilogue.h"
 
 static thread_local int g_t160 = 0;  // 0 auto, 1 never, 2 never the 128-row tile, 3 128-row tiles wherever the kernel runs (A/B, tests: ds_set_option "gemm_t160")
 void ds_gemm_set_t160(int v) { g_t160 = v; }
@@ -46,8 +45,6 @@ namespace {
 constexpr int TN = 160;
 constexpr int CS = 336;                    // bytes per row of the epilogue staging tile (160 f16 + 8 pad)
 typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ int swz(int row, int chunk) { return ((chunk ^ ((row >> 1) & 7)) << 4); }
 
 constexpr int NWAVES = 8, NCOMP = 5;   // waves per block / of them computing (one per 32-column strip)
 
@@ -153,17 +150,7 @@ __global__ __launch_bounds__(NWAVES * 64, 1) void gemm_t160_kernel(const GemmPar
             }
         }
         if (ln_in) {
-            if constexpr (PRE) {
-#pragma unroll
-                for (int mi = 0; mi < 2; ++mi) {
-                    const int m = min(m0 + mi * 32 + l31, p.M - 1);
-                    const f32x2* part = reinterpret_cast<const f32x2*>(p.ln_stats) + m;
-#pragma unroll
-                    for (int cc = 0; cc < 2; ++cc)
-#pragma unroll
-                        for (int jj = 0; jj < JJ; ++jj) t0[mi][cc][jj] = part[(long)min(2 * lhi + cc + 4 * jj, strips - 1) * p.M];
-                }
-            }
+            if constexpr (PRE) ln_part_load<2, JJ>(t0, p.ln_stats, m0 + l31, p.M, 0, lhi, strips);
 #pragma unroll
             for (int g = 0; g < 4; ++g) cq[g] = *reinterpret_cast<const h8*>(p.ln_c + 2 * (nw + 8 * g + 4 * lhi));
         }
@@ -174,9 +161,7 @@ __global__ __launch_bounds__(NWAVES * 64, 1) void gemm_t160_kernel(const GemmPar
 #pragma unroll
     for (int s = 0; s < STAGES - 1; ++s)
         if (s < nk) issue(s, s);
-    // consumer: (mean, rstd) of the lane's rows from the producer's partial sums, every load in flight at once; the summation
-    // order is the one of gemm.hip's consumer / ln_finalize_kernel (four interleaved chains, (0 + 1) + (2 + 3)): the two
-    // half-waves hold the same rows and take two chains each
+    // consumer: (mean, rstd) of the lane's rows from the producer's partial sums, every load in flight at once (ds_epilogue.h)
     float ln_mean[TMI], ln_rstd[TMI];
 #pragma unroll
     for (int mi = 0; mi < TMI; ++mi) ln_mean[mi] = 0.f, ln_rstd[mi] = 1.f;
@@ -184,39 +169,25 @@ __global__ __launch_bounds__(NWAVES * 64, 1) void gemm_t160_kernel(const GemmPar
 #pragma unroll
         for (int m2 = 0; m2 < TMI; m2 += 2) {   // two rows per lane and round of loads
             float sa[2][2] = {{0.f, 0.f}, {0.f, 0.f}}, qa[2][2] = {{0.f, 0.f}, {0.f, 0.f}};
-            for (int base = 0; base < strips; base += 4 * JJ) {
-                f32x2 t[2][2][JJ];
-#pragma unroll
-                for (int mi = 0; mi < 2; ++mi) {
-                    const int m = min(m0 + (m2 + mi) * 32 + l31, p.M - 1);
-                    const f32x2* part = reinterpret_cast<const f32x2*>(p.ln_stats) + m;
-#pragma unroll
-                    for (int cc = 0; cc < 2; ++cc)
-#pragma unroll
-                        for (int jj = 0; jj < JJ; ++jj) {
-                            const int j = base + 2 * lhi + cc + 4 * jj;
-                            if (PRE && base == 0) t[mi][cc][jj] = t0[PRE ? mi : 0][cc][jj];
-                            else t[mi][cc][jj] = part[(long)min(j, strips - 1) * p.M];
-                        }
-                }
-#pragma unroll
-                for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                    for (int cc = 0; cc < 2; ++cc)
-#pragma unroll
-                        for (int jj = 0; jj < JJ; ++jj) {
-                            const bool in = base + 2 * lhi + cc + 4 * jj < strips;
-                            sa[mi][cc] += in ? t[mi][cc][jj][0] : 0.f;
-                            qa[mi][cc] += in ? t[mi][cc][jj][1] : 0.f;
-                        }
+            int base = 0;
+            if constexpr (PRE) {   // (the first round has been in t0 since the top of the kernel)
+                ln_part_add<2, JJ>(sa, qa, t0, 0, lhi, strips);
+                base = 4 * JJ;
             }
+            for (; base < strips; base += 4 * JJ) {
+                f32x2 t[2][2][JJ];
+                ln_part_load<2, JJ>(t, p.ln_stats, m0 + m2 * 32 + l31, p.M, base, lhi, strips);
+                ln_part_add<2, JJ>(sa, qa, t, base, lhi, strips);
+            }
+            // ln_part_finish spelled out: through the helper gemm_t160_kernel<4, 4> came out with 226 VGPRs instead of 230
+            // (profiles/epilogue_header_resource_usage.txt)
             const float inv_c = 1.0f / (float)p.K;
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi) {
                 const float s2 = sa[mi][0] + sa[mi][1], q2 = qa[mi][0] + qa[mi][1];
-                const float s = s2 + __shfl_xor(s2, 32, 64), q = q2 + __shfl_xor(q2, 32, 64);
-                ln_mean[m2 + mi] = s * inv_c;
-                ln_rstd[m2 + mi] = rsqrtf(fmaxf(fmaf(-ln_mean[m2 + mi], ln_mean[m2 + mi], q * inv_c), 0.f) + p.ln_eps);
+                const f32x2 mr = ln_mean_rstd(s2 + __shfl_xor(s2, 32, 64), q2 + __shfl_xor(q2, 32, 64), inv_c, p.ln_eps);
+                ln_mean[m2 + mi] = mr[0];
+                ln_rstd[m2 + mi] = mr[1];
             }
         }
     };
@@ -280,13 +251,10 @@ __global__ __launch_bounds__(NWAVES * 64, 1) void gemm_t160_kernel(const GemmPar
             float v[4];
             if (ln_in) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float nc = (float)cq[g][2 * e] + (float)cq[g][2 * e + 1];   // -c_n
-                    v[e] = fmaf(fmaf(ln_mean[mi], nc, acc[mi][4 * g + e]), ln_rstd[mi], (float)bq[g][e]);
-                }
+                for (int e = 0; e < 4; ++e) v[e] = ln_apply(acc[mi][4 * g + e], ln_mean[mi], ln_rstd[mi], cq[g][2 * e], cq[g][2 * e + 1], bq[g][e]);
             } else {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = acc[mi][4 * g + e] + (float)bq[g][e];
+                for (int e = 0; e < 4; ++e) v[e] = bias_apply(acc[mi][4 * g + e], bq[g][e]);
             }
             h4 o;
 #pragma unroll
@@ -303,22 +271,14 @@ __global__ __launch_bounds__(NWAVES * 64, 1) void gemm_t160_kernel(const GemmPar
     for (int j = 0; j < TM / 16; ++j) {
         const int row = r16 + 16 * j, m = m0 + row;
         h8 v = *reinterpret_cast<const h8*>(sC + row * CS + c * 16);
-        if (p.residual) v = v + rv[j];   // v_pk_add_f16: the same number as (f16)((float)a + (float)b) (tests/test_f16_add_equivalence.py)
+        if (p.residual) v = add_residual8<half_t>(v, rv[j]);
         if (m < p.M) *reinterpret_cast<h8*>(p.C + (long)m * p.ldc + n) = v;
         if (p.stats_out) {
             // producer: (sum, sum of squares) of the 32-column piece c >> 2 of this row = the four lanes of a quad (20 lanes per
             // row: quads are the largest lane groups that never straddle a row or a wave) -> LDS behind the staging tile
-            float s1 = 0.f, q1 = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float f = (float)v[e];
-                s1 += f;
-                q1 = fmaf(f, f, q1);
-            }
-            s1 += ds_dpp_f32<0xB1>(s1);
-            q1 += ds_dpp_f32<0xB1>(q1);
-            s1 += ds_dpp_f32<0x4E>(s1);
-            q1 += ds_dpp_f32<0x4E>(q1);
+            float s1, q1;
+            sum_sq8(v, s1, q1);
+            quad_sum2(s1, q1);
             if ((c & 3) == 0) *reinterpret_cast<f32x2*>(smem + RED_OFF + (row * 5 + (c >> 2)) * 8) = f32x2{s1, q1};
         }
     }

@@ -9,8 +9,7 @@
 // (3) y = silu(a*x + s).  The input may be the channel-concat of two tensors (UNet up-path skip joins,
 // reference src/models/unet.py:304-332 -> torch.cat in diffusers up blocks) — the concat is never
 // materialised un-normalised.
-#include "ds_common.h"
-#include "ds_kernels.h"
+#include "ds_epilogue.h"
 
 namespace {
 
@@ -216,8 +215,8 @@ __global__ __launch_bounds__(512) void gn_apply_kernel(GroupNormParams p, int nc
 __global__ __launch_bounds__(256) void ln_finalize_kernel(const f32x2* __restrict__ part, f32x2* __restrict__ stats, int M,
                                                           int strips, float inv_c, float eps) {
     // four lanes per row (lane & 3 = which strips: q, q + 4, ...), all of a lane's loads independent and in flight together;
-    // the four partial sums meet in a 2-step DPP butterfly - a fixed order, so the result does not depend on anything but
-    // the data (one thread per row walking 20 strips four at a time took 8 us per launch, 1.5 ms per forward)
+    // the four partial sums meet in a 2-step butterfly - the fixed order of ds_epilogue.h, which the consumer epilogues that sum
+    // the partials themselves repeat bit for bit (one thread per row walking 20 strips four at a time took 8 us per launch, 1.5 ms per forward)
     const int t = blockIdx.x * 256 + threadIdx.x;
     const int row = t >> 2, q = t & 3;
     float s = 0.f, ss = 0.f;
@@ -233,12 +232,7 @@ __global__ __launch_bounds__(256) void ln_finalize_kernel(const f32x2* __restric
     ss += __shfl_xor(ss, 1, 64);
     s += __shfl_xor(s, 2, 64);
     ss += __shfl_xor(ss, 2, 64);
-    if (row < M && q == 0) {
-        const float mean = s * inv_c;
-        const float var = fmaxf(fmaf(-mean, mean, ss * inv_c), 0.f);
-        f32x2 o = {mean, rsqrtf(var + eps)};
-        stats[row] = o;
-    }
+    if (row < M && q == 0) stats[row] = ln_mean_rstd(s, ss, inv_c, eps);
 }
 
 // LayerNorm: one wavefront per row, the row lives in registers (two-pass variance, like torch).

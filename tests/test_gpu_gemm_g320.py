@@ -191,7 +191,10 @@ PLAN_SHAPES = [
 ]
 
 
-@pytest.mark.parametrize("name,M,N,K,form", [s for s in PLAN_SHAPES if s[4] != "geglu-ln"])
+# beside the plans' shapes: K = 1600 = 25 partial-sum entries per row, one more than the consumer loads per round (every plan has
+# K <= 1280: one round), at the smallest M the dispatch rule sends an N = 640 problem here (86 row tiles, the last one ragged)
+@pytest.mark.parametrize("name,M,N,K,form", [s for s in PLAN_SHAPES if s[4] != "geglu-ln"] +
+                         [("gemm_g320_kernel<plain>", 21800, 640, 1600, "ln")])
 def test_g320_plain_at_the_shapes_the_plans_send_it(hip_lib, name, M, N, K, form):
     """Automatic dispatch picks the plain gemm_g320_kernel at (M, N, K) in the plan's form; vs an fp64 reference of the same f16
     inputs (<= 2e-3 of max|ref|, 3e-3 behind the fused LayerNorm) and bit for bit vs the kernel the rule replaces (gemm_g320 = 1)."""

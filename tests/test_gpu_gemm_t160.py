@@ -102,8 +102,13 @@ def test_t160_is_the_automatic_choice_at_the_batch1_shapes_only(hip_lib):
         lib.ds_set_option(b"gemm_t160", 0)
 
 
-@pytest.mark.parametrize("M,K", [(2048, 1280), (2048, 5120), (1999, 1280)])
-def test_t160_producer_statistics_and_consumer_chain(hip_lib, M, K):
+# 96-320-1920-320: a 1920-wide stream = 36 entries per row; the consumers load 24 per round, so theirs is a second, ragged round
+# (Cc = 1280 everywhere else: 24 entries, one round).  1920 is the smallest width past 1280 a producer emits this format for (a
+# multiple of 128 and of 160); M, K, Nq the smallest that still span two row tiles and two column tiles.  (25 entries of the
+# 64-column format at K = 1600: test_gpu_ln_fusion.py::test_wide_consumer_plain_vs_layernorm_linear[96-640-1600-0.0].)
+@pytest.mark.parametrize("M,K,Cc,Nq", [pytest.param(2048, 1280, 1280, 1280, id="2048-1280"), pytest.param(2048, 5120, 1280, 1280, id="2048-5120"),
+                                       pytest.param(1999, 1280, 1280, 1280, id="1999-1280"), (96, 320, 1920, 320)])
+def test_t160_producer_statistics_and_consumer_chain(hip_lib, M, K, Cc, Nq):
     """The launch plan's sequence at UNet batch 2: out-projection + residual emitting gemm_t160_kernel's statistics format
     (i[11] = 160: entries of 64 | 64 | 32 columns per tile) -> attn2.to_q consuming the 24 entries per row (i[10] = 24), on
     gemm_t160_kernel both; and the same partials consumed by the 128-wide kernels (q|k / GEGLU consumers at this batch).  vs fp32 LayerNorm + linear; the stored producer output must be
@@ -112,10 +117,9 @@ def test_t160_producer_statistics_and_consumer_chain(hip_lib, M, K):
     from diffsensei_amd.engine import pack_ln_fused
     lib = _lib.load()
     g = torch.Generator().manual_seed(M + K)
-    Cc = 1280
     a, wo, bo = _r((M, K), g), _r((Cc, K), g, 1 / math.sqrt(K)), _r((Cc,), g)
     h0 = (_r((M, Cc), g) * 2 + 0.5).half()
-    wq, gamma, beta = _r((Cc, Cc), g, 1 / math.sqrt(Cc)), (1 + 0.2 * torch.randn(Cc, generator=g)).half(), _r((Cc,), g, 0.2)
+    wq, gamma, beta = _r((Nq, Cc), g, 1 / math.sqrt(Cc)), (1 + 0.2 * torch.randn(Cc, generator=g)).half(), _r((Cc,), g, 0.2)
     dv = lambda t: t.to(DEV)
     h, part, name = _forced(lib, 11 if M % 64 else 0, lambda: _gemm_op(lib, dv(a), dv(wo), dv(bo), dv(h0), stats_strip=160))
     assert name == "gemm_t160_kernel" or M % 64

@@ -243,8 +243,10 @@ def test_wide_producer_row_statistics(hip_lib, M, N, K, res, variant):
 
 
 # (272, 256, 128) under gemm_variant 1 (register staging) and 3 (ping-pong): a consumer of partial sums runs the 128-wide kernel all the same
+# (96, 640, 1600): 25 partial-sum entries per row on a 64-row tile, whose epilogue loads 24 per round - the one case with a second,
+# ragged round of that loop (K <= 1280 everywhere else; the 128-row tiles load 12 per round and pass two rounds at K = 1280)
 @pytest.mark.parametrize("M,N,K,offset,variant", _knob_cases([(2048, 1280, 1280, 0.0), (8192, 640, 640, 0.3), (1000, 1280, 640, 0.0),
-                                                              (2048, 2560, 1280, 8.0), (64, 128, 64, 0.0)],
+                                                              (2048, 2560, 1280, 8.0), (64, 128, 64, 0.0), (96, 640, 1600, 0.0)],
                                                              [(272, 256, 128, 0.0, 1), (272, 256, 128, 0.0, 3)]))
 def test_wide_consumer_plain_vs_layernorm_linear(hip_lib, M, N, K, offset, variant):
     """Consumer that sums the partials of its own rows (no finalize launch) vs fp32 LayerNorm + linear, and vs the 256 x 256
@@ -263,6 +265,14 @@ def test_wide_consumer_plain_vs_layernorm_linear(hip_lib, M, N, K, offset, varia
         got = ops.gemm_ln_partial(x.to(DEV), gw, b2, c2, part)
     e = _relmax(got, ref)
     line = f"LN -> linear (128-wide kernels) M={M} N={N} K={K} mean/std {offset}: {e:.2e}"
+    if variant == 0 and N % 160 == 0:   # the 64 x 160 family sums the same partials to the same bits (csrc/ds_epilogue.h)
+        lib = __import__("diffsensei_amd._lib", fromlist=["x"]).load()
+        assert lib.ds_set_option(b"gemm_variant", 11) == 0
+        try:
+            t160 = ops.gemm_ln_partial(x.to(DEV), gw, b2, c2, part)
+        finally:
+            lib.ds_set_option(b"gemm_variant", 0)
+        assert torch.equal(got, t160), "the 128-wide and the 64 x 160 consumer differ"
     if M % 256 == 0 and N % 256 == 0 and K % 128 == 0:
         pp = ops.gemm_ln(x.to(DEV), gw, b2, c2, ops.ln_finalize(part, K, 1e-5))
         d = (got.float() - pp.float()).abs().max().item()
