@@ -500,14 +500,20 @@ static int llm_gemv_impl(const void* x, int64_t ldx, const void* w, void* y, int
     return gemm16 ? ds_launch_llm_gemm16(g, st) : ds_launch_llm_gemv(g, st);
 }
 
+// The four per-row kernels take both row forms (ds_kernels.h): SEQ for the one-sequence entry points and ops, SLOTS for
+// the *_slots ones - the state stride is the only thing that tells the two families apart below.
+constexpr int SEQ = 0, SLOTS = 8;
+
 static int llm_attn_impl(const void* qkv, int64_t ldqkv, void* kc, void* vc, int64_t ldc, const float* rope_cos,
                          const float* rope_sin, void* out, int64_t ldo, const int32_t* state, int M, int heads,
-                         int kv_heads, int D, int T_max, float scale, hipStream_t st, int64_t slot_stride = -1) {
+                         int kv_heads, int D, int T_max, float scale, hipStream_t st, int state_stride = SEQ,
+                         int64_t slot_stride = 0) {
     LlmAttnParams a;
     a.qkv = H(qkv); a.kc = HM(kc); a.vc = HM(vc); a.rope_cos = rope_cos; a.rope_sin = rope_sin; a.out = HM(out);
     a.state = state; a.ldqkv = ldqkv; a.ldc = ldc; a.ldo = ldo;
     a.M = M; a.heads = heads; a.kv_heads = kv_heads; a.D = D; a.T_max = T_max; a.scale = scale;
-    return slot_stride >= 0 ? ds_launch_llm_attn_slots(a, (long)slot_stride, st) : ds_launch_llm_attn(a, st);
+    a.state_stride = state_stride; a.slot_stride = (long)slot_stride;
+    return ds_launch_llm_attn(a, st);
 }
 
 int ds_llm_gemv_f16(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, const void* residual,
@@ -524,16 +530,16 @@ int ds_llm_attn_f16(const void* qkv, int64_t ldqkv, void* k_cache, void* v_cache
 
 int ds_llm_rmsnorm_f16(const void* x, int64_t ldx, const void* gamma, void* y, int64_t ldy, void* feat,
                        const int32_t* state, int M, int Hd, int max_out, float eps, void* stream) {
-    return ds_launch_llm_rmsnorm(H(x), ldx, H(gamma), HM(y), ldy, HM(feat), state, M, Hd, max_out, eps, S(stream));
+    return ds_launch_llm_rmsnorm(H(x), ldx, H(gamma), HM(y), ldy, HM(feat), state, SEQ, M, Hd, max_out, eps, S(stream));
 }
 
 int ds_llm_embed_f16(const void* table, const int32_t* state, void* out, int Hd, int vocab, void* stream) {
-    return ds_launch_llm_embed(H(table), state, HM(out), Hd, vocab, S(stream));
+    return ds_launch_llm_embed(H(table), state, SEQ, HM(out), Hd, 1, Hd, vocab, S(stream));
 }
 
 int ds_llm_select_f16(const void* logits, int V, const int32_t* chain, int n_chain, int out_cap, int adv,
                       int32_t* state, int32_t* out_ids, void* stream) {
-    return ds_launch_llm_select(H(logits), V, chain, n_chain, out_cap, adv, state, out_ids, S(stream));
+    return ds_launch_llm_select(H(logits), V, V, chain, n_chain, out_cap, adv, state, SEQ, out_ids, 1, S(stream));
 }
 
 int ds_llm_advance(int32_t* state, int rows, void* stream) { return ds_launch_llm_advance(state, rows, S(stream)); }
@@ -570,24 +576,23 @@ int ds_llm_gemm16(const void* x, int64_t ldx, const void* w, void* y, int64_t ld
 int ds_llm_attn_slots_f16(const void* qkv, int64_t ldqkv, void* k_cache, void* v_cache, int64_t ldc, int64_t slot_stride,
                           const float* rope_cos, const float* rope_sin, void* out, int64_t ldo, const int32_t* state,
                           int slots, int heads, int kv_heads, int D, int T_max, float scale, void* stream) {
-    DS_REQUIRE(slot_stride >= 0, "llm_attn_slots: negative slot stride");
     return llm_attn_impl(qkv, ldqkv, k_cache, v_cache, ldc, rope_cos, rope_sin, out, ldo, state, slots, heads, kv_heads, D,
-                         T_max, scale, S(stream), slot_stride);
+                         T_max, scale, S(stream), SLOTS, slot_stride);
 }
 
 int ds_llm_rmsnorm_slots_f16(const void* x, int64_t ldx, const void* gamma, void* y, int64_t ldy, void* feat,
                              const int32_t* state, int slots, int Hd, int max_out, float eps, void* stream) {
-    return ds_launch_llm_rmsnorm_slots(H(x), ldx, H(gamma), HM(y), ldy, HM(feat), state, slots, Hd, max_out, eps, S(stream));
+    return ds_launch_llm_rmsnorm(H(x), ldx, H(gamma), HM(y), ldy, HM(feat), state, SLOTS, slots, Hd, max_out, eps, S(stream));
 }
 
 int ds_llm_embed_slots_f16(const void* table, const int32_t* state, void* out, int64_t ldo, int slots, int Hd, int vocab,
                            void* stream) {
-    return ds_launch_llm_embed_slots(H(table), state, HM(out), ldo, slots, Hd, vocab, S(stream));
+    return ds_launch_llm_embed(H(table), state, SLOTS, HM(out), ldo, slots, Hd, vocab, S(stream));
 }
 
 int ds_llm_select_slots_f16(const void* logits, int64_t ldl, int V, const int32_t* chain, int n_chain, int out_cap, int adv,
                             int32_t* state, int32_t* out_ids, int slots, void* stream) {
-    return ds_launch_llm_select_slots(H(logits), ldl, V, chain, n_chain, out_cap, adv, state, out_ids, slots, S(stream));
+    return ds_launch_llm_select(H(logits), ldl, V, chain, n_chain, out_cap, adv, state, SLOTS, out_ids, slots, S(stream));
 }
 
 int ds_resize_h_u8(const uint8_t* src, int H_, int W_, const int32_t* first, const int32_t* count, const int32_t* taps,
@@ -827,12 +832,12 @@ static int run_op(const ds_op& o, hipStream_t st) {
                                  i[0], i[1], i[2], i[3], i[4], o.f[0], st);
         case DS_OP_LLM_RMSNORM:
             return ds_launch_llm_rmsnorm(H(p[0]), l[0], H(p[1]), HM(p[2]), l[1], HM(p[3]),
-                                         reinterpret_cast<const int*>(p[4]), i[0], i[1], i[2], o.f[0], st);
+                                         reinterpret_cast<const int*>(p[4]), SEQ, i[0], i[1], i[2], o.f[0], st);
         case DS_OP_LLM_EMBED:
-            return ds_launch_llm_embed(H(p[0]), reinterpret_cast<const int*>(p[1]), HM(p[2]), i[0], i[1], st);
+            return ds_launch_llm_embed(H(p[0]), reinterpret_cast<const int*>(p[1]), SEQ, HM(p[2]), i[0], 1, i[0], i[1], st);
         case DS_OP_LLM_SELECT:
-            return ds_launch_llm_select(H(p[0]), i[0], reinterpret_cast<const int*>(p[1]), i[1], i[2], i[3],
-                                        reinterpret_cast<int*>(p[2]), reinterpret_cast<int*>(p[3]), st);
+            return ds_launch_llm_select(H(p[0]), i[0], i[0], reinterpret_cast<const int*>(p[1]), i[1], i[2], i[3],
+                                        reinterpret_cast<int*>(p[2]), SEQ, reinterpret_cast<int*>(p[3]), 1, st);
         case DS_OP_LLM_ADVANCE:
             return ds_launch_llm_advance(reinterpret_cast<int*>(p[0]), i[0], st);
         case DS_OP_LLM_GEMM16:
@@ -845,19 +850,17 @@ static int run_op(const ds_op& o, hipStream_t st) {
             return llm_gemv_impl(p[0], l[0], p[1], p[2], l[1], p[3], l[2], i[0], i[1], i[2], i[3], i[4], o.f[0], st, p[4],
                                  true, reinterpret_cast<const float*>(p[5]), true);
         case DS_OP_LLM_ATTN_SLOTS:
-            DS_REQUIRE(l[3] >= 0, "llm_attn_slots: negative slot stride");
             return llm_attn_impl(p[0], l[0], p[1], p[2], l[1], reinterpret_cast<const float*>(p[3]),
                                  reinterpret_cast<const float*>(p[4]), p[5], l[2], reinterpret_cast<const int32_t*>(p[6]),
-                                 i[0], i[1], i[2], i[3], i[4], o.f[0], st, l[3]);
+                                 i[0], i[1], i[2], i[3], i[4], o.f[0], st, SLOTS, l[3]);
         case DS_OP_LLM_RMSNORM_SLOTS:
-            return ds_launch_llm_rmsnorm_slots(H(p[0]), l[0], H(p[1]), HM(p[2]), l[1], HM(p[3]),
-                                               reinterpret_cast<const int*>(p[4]), i[0], i[1], i[2], o.f[0], st);
+            return ds_launch_llm_rmsnorm(H(p[0]), l[0], H(p[1]), HM(p[2]), l[1], HM(p[3]),
+                                         reinterpret_cast<const int*>(p[4]), SLOTS, i[0], i[1], i[2], o.f[0], st);
         case DS_OP_LLM_EMBED_SLOTS:
-            return ds_launch_llm_embed_slots(H(p[0]), reinterpret_cast<const int*>(p[1]), HM(p[2]), l[0], i[0], i[1], i[2],
-                                             st);
+            return ds_launch_llm_embed(H(p[0]), reinterpret_cast<const int*>(p[1]), SLOTS, HM(p[2]), l[0], i[0], i[1], i[2], st);
         case DS_OP_LLM_SELECT_SLOTS:
-            return ds_launch_llm_select_slots(H(p[0]), l[0], i[0], reinterpret_cast<const int*>(p[1]), i[1], i[2], i[3],
-                                              reinterpret_cast<int*>(p[2]), reinterpret_cast<int*>(p[3]), i[4], st);
+            return ds_launch_llm_select(H(p[0]), l[0], i[0], reinterpret_cast<const int*>(p[1]), i[1], i[2], i[3],
+                                        reinterpret_cast<int*>(p[2]), SLOTS, reinterpret_cast<int*>(p[3]), i[4], st);
         case DS_OP_LORA_MERGE:
             return ds_launch_lora_merge(lora_merge_params(o), st);
         default:
@@ -928,11 +931,11 @@ int ds_op_describe(const ds_op* op, char* name, int name_len, double* flops, dou
             fl = 2.0 * i[0] * (double)i[1] * i[2] * (i[4] ? 2 : 1);
             by = (double)i[1] * (i[4] ? 2 : 1) * (i[2] + 4.0) + 2.0 * ((double)i[0] * i[2] + (double)i[0] * i[1]);
             break;
-        case DS_OP_LLM_ATTN: nm = "llm_attn_kernel"; break;
-        case DS_OP_LLM_ATTN_SLOTS: nm = "llm_attn_slots_kernel"; break;
-        case DS_OP_LLM_RMSNORM_SLOTS: nm = "llm_rmsnorm_slots_kernel"; by = 4.0 * i[0] * (double)i[1]; break;
-        case DS_OP_LLM_SELECT_SLOTS: nm = "llm_select_slots_kernel"; by = 2.0 * i[0] * (double)i[4]; break;
-        case DS_OP_LLM_RMSNORM: nm = "llm_rmsnorm_kernel"; by = 4.0 * i[0] * (double)i[1]; break;
+        case DS_OP_LLM_ATTN:
+        case DS_OP_LLM_ATTN_SLOTS: nm = "llm_attn_kernel"; break;
+        case DS_OP_LLM_RMSNORM:
+        case DS_OP_LLM_RMSNORM_SLOTS: nm = "llm_rmsnorm_kernel"; by = 4.0 * i[0] * (double)i[1]; break;
+        case DS_OP_LLM_SELECT_SLOTS: nm = "llm_select_kernel"; by = 2.0 * i[0] * (double)i[4]; break;
         case DS_OP_LLM_SELECT: nm = "llm_select_kernel"; by = 2.0 * i[0]; break;
         case DS_OP_LORA_MERGE:   // W in, out (and out2) out, A and B once; the adapters' products
             nm = "lora_merge_kernel";

@@ -284,6 +284,13 @@ struct LlmGemvParams {
 int ds_launch_llm_gemv(const LlmGemvParams& p, hipStream_t stream);
 void ds_llm_gemv_set_variant(int v);   // 0 auto (pipelined), 1 one column per wavefront, 2 streaming without pipelining
 
+// Row forms of the four per-row kernels below (attention, RMSNorm with tap, embed, pick).  A launch is `rows` rows; row m
+// reads its state at state + m * state_stride and its cache at kc / vc + m * slot_stride:
+//   one-sequence form  state_stride = 0, slot_stride = 0: all rows belong to one sequence, row m sits at position
+//                      state[0] + m and sees the rows before it in the same launch (prompt chunks, M <= 16)
+//   slot form          state_stride = 8: every row is its own sequence - row m of qkv / out / logits, state row m of an
+//                      int32 [S][8] block, cache slot m of [S][T_max][kv_heads*D], feat[m] of [S][max_out][H],
+//                      out_ids[m] of [S][out_cap]; a finished (or never started) slot is skipped
 struct LlmAttnParams {
     const half_t* qkv = nullptr;       // [M, (heads + 2 kv_heads) * D] rows (ldqkv): q | k | v, not yet rotated
     half_t* kc = nullptr;              // key cache   [T_max, kv_heads*D] rows (ldc), rotated keys
@@ -295,29 +302,23 @@ struct LlmAttnParams {
     long ldqkv = 0, ldc = 0, ldo = 0;
     int M = 0, heads = 0, kv_heads = 0, D = 0, T_max = 0;
     float scale = 1.0f;
+    long slot_stride = 0;              // elements between the caches of two rows (slot form; 0 in the one-sequence form)
+    int state_stride = 0;              // 0 | 8, see above
 };
 int ds_launch_llm_attn(const LlmAttnParams& p, hipStream_t stream);
 int ds_launch_llm_rmsnorm(const half_t* x, long ldx, const half_t* gamma, half_t* y, long ldy, half_t* feat,
-                          const int* state, int M, int H, int max_out, float eps, hipStream_t stream);
-int ds_launch_llm_embed(const half_t* table, const int* state, half_t* out, int H, int vocab, hipStream_t stream);
-int ds_launch_llm_select(const half_t* logits, int V, const int* chain, int n_chain, int out_cap, int adv, int* state,
-                         int* out_ids, hipStream_t stream);
+                          const int* state, int state_stride, int M, int H, int max_out, float eps, hipStream_t stream);
+int ds_launch_llm_embed(const half_t* table, const int* state, int state_stride, half_t* out, long ldo, int M, int H,
+                        int vocab, hipStream_t stream);
+int ds_launch_llm_select(const half_t* logits, long ldl, int V, const int* chain, int n_chain, int out_cap, int adv,
+                         int* state, int state_stride, int* out_ids, int M, hipStream_t stream);
 int ds_launch_llm_advance(int* state, int rows, hipStream_t stream);
 int ds_launch_blend(const half_t* a, const half_t* b, half_t* out, long n, float s, hipStream_t stream);
 int ds_launch_llm_swiglu(const half_t* gu, half_t* act, int M, int I, hipStream_t stream);
-// batched decode: M <= 16 sequences per weight pass (matrix pipe), and the per-slot forms of the kernels above over a
-// state block int32 [S][8], caches [S][T_max][kv_heads*D] per layer (slot_stride elements apart), feat [S][max_out][H],
-// out_ids [S][out_cap]
+// batched decode: M <= 16 sequences per weight pass (matrix pipe)
 int ds_launch_llm_gemm16(const LlmGemvParams& p, hipStream_t stream);
 // w16[n][k] = f16(f32(q[n][k]) * scale[n]): an int8 weight matrix back to fp16 for the prompt pass's MFMA GEMMs
 int ds_launch_llm_dequant_w8(const int8_t* q, const float* scale, half_t* w16, long N, int K, hipStream_t stream);
-int ds_launch_llm_attn_slots(const LlmAttnParams& p, long slot_stride, hipStream_t stream);   // p.M = slots, one row each
-int ds_launch_llm_rmsnorm_slots(const half_t* x, long ldx, const half_t* gamma, half_t* y, long ldy, half_t* feat,
-                                const int* state, int S, int H, int max_out, float eps, hipStream_t stream);
-int ds_launch_llm_embed_slots(const half_t* table, const int* state, half_t* out, long ldo, int S, int H, int vocab,
-                              hipStream_t stream);
-int ds_launch_llm_select_slots(const half_t* logits, long ldl, int V, const int* chain, int n_chain, int out_cap, int adv,
-                               int* state, int* out_ids, int S, hipStream_t stream);
 
 // ---- character-reference pre-processing (preprocess.hip): Pillow's 8-bit separable resize + crop + normalise ----
 int ds_launch_resize_h(const uint8_t* src, int H, int W, const int* first, const int* count, const int* taps, int ksize,

@@ -202,6 +202,11 @@ constexpr int ATT_WAVES = 16;  // one key group per wavefront per iteration: the
 template <int D>
 __device__ __forceinline__ void llm_attn_body(const LlmAttnParams& p, const int h, const int r) {
     constexpr int LPK = D / 8, KPW = 64 / LPK, HALF = D / 2;
+    // The state row first: the length every block starts from and, beside it, the flag only the slot form uses - one round
+    // trip for both.  The fence keeps the two loads in front of the index arithmetic below, which then hides their latency
+    // (left to itself the scheduler issues them behind the first division and the block waits with nothing to do).
+    const int pos0 = p.state[0], finished = p.state[2];
+    __builtin_amdgcn_sched_barrier(0);
     extern __shared__ float sm[];
     float* sc = sm;                    // [T_max] scores, then probabilities
     float* red = sm + p.T_max;         // [ATT_WAVES][D]
@@ -209,9 +214,11 @@ __device__ __forceinline__ void llm_attn_body(const LlmAttnParams& p, const int 
     const int hkv = h / (p.heads / p.kv_heads);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane % LPK, ks = lane / LPK;
-    const int pos0 = p.state[0];
     const int T = pos0 + r + 1;
-    if (T > p.T_max) return;  // the host sizes the cache; never write past it
+    // never write past the cache (the host sizes it); slot form only: a finished (or never started) slot is left alone.
+    // One branch for both: a branch on the flag in front of the length's load would make every launch of the token step
+    // wait for the state row twice.
+    if ((T > p.T_max) | ((p.state_stride != 0) & (finished != 0))) return;
     const long kcol = (long)(p.heads + hkv) * D, vcol = (long)(p.heads + p.kv_heads + hkv) * D;
     const half_t* qrow = p.qkv + (long)r * p.ldqkv;
 
@@ -309,24 +316,21 @@ __device__ __forceinline__ void llm_attn_body(const LlmAttnParams& p, const int 
     }
 }
 
+// Block (head h, row m), both row forms (ds_kernels.h).  One-sequence form (state_stride = 0): row m of the chunk, on the one
+// cache and state block.  Slot form: the block moves to row m of qkv / out, to slot m's own cache (kc + m * slot_stride) and
+// state row (state + 8 m) and runs the body on row 0 there, so the slot's length state[m][0] sets its rotary position.
+// Only the slot form looks at the finished flag - a finished (or never started) slot returns before it touches anything;
+// the one-sequence form never did (the prompt cursor has the flag at zero), hence the `state_stride != 0 &` in the body's
+// early-out.
 template <int D>
 __global__ __launch_bounds__(64 * ATT_WAVES) void llm_attn_kernel(LlmAttnParams p) {
-    llm_attn_body<D>(p, blockIdx.x, blockIdx.y);
-}
-
-// Batched decode: block (head h, slot s) runs the same body on row s of qkv / out, on slot s's own cache
-// (kc + s * slot_stride) and its own state row (state + 8 s), so its length state[s][0] sets its rotary position.
-// A finished (or never started) slot returns before it touches anything.
-template <int D>
-__global__ __launch_bounds__(64 * ATT_WAVES) void llm_attn_slots_kernel(LlmAttnParams p, long slot_stride) {
-    const int s = blockIdx.y;
-    p.state += 8 * s;
-    if (p.state[2]) return;
+    const int s = p.state_stride ? blockIdx.y : 0;   // rows in front of this block's row that are other sequences
+    p.state += p.state_stride * s;
     p.qkv += (long)s * p.ldqkv;
     p.out += (long)s * p.ldo;
-    p.kc += (long)s * slot_stride;
-    p.vc += (long)s * slot_stride;
-    llm_attn_body<D>(p, blockIdx.x, 0);
+    p.kc += (long)s * p.slot_stride;
+    p.vc += (long)s * p.slot_stride;
+    llm_attn_body<D>(p, blockIdx.x, blockIdx.y - s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -359,53 +363,32 @@ __device__ __forceinline__ void llm_rmsnorm_row(const half_t* __restrict__ xr, c
     }
 }
 
+// Row m, both row forms.  The tap: one-sequence form (state_stride = 0) row state[1]-1+m of feat ([max_out][H]); slot form
+// row state[m][1]-1 of feat[m] ([S][max_out][H]).
 __global__ __launch_bounds__(256) void llm_rmsnorm_kernel(const half_t* __restrict__ x, long ldx,
                                                           const half_t* __restrict__ gamma, half_t* __restrict__ y,
                                                           long ldy, half_t* __restrict__ feat,
-                                                          const int* __restrict__ state, int H, int max_out,
-                                                          float eps) {
+                                                          const int* __restrict__ state, int state_stride, int H,
+                                                          int max_out, float eps) {
     const int m = blockIdx.x;
     half_t* fr = nullptr;
     if (feat) {
-        const int row = state[1] - 1 + m;
-        if (row >= 0 && row < max_out && !state[2]) fr = feat + (long)row * H;
+        const int s = state_stride ? m : 0;
+        const int* st = state + state_stride * s;
+        const int row = st[1] - 1 + (m - s);
+        if (row >= 0 && row < max_out && !st[2]) fr = feat + ((long)s * max_out + row) * H;
     }
     llm_rmsnorm_row(x + (long)m * ldx, gamma, y + (long)m * ldy, fr, H, eps);
 }
 
-// Batched decode: row s belongs to slot s; its tap goes to row state[s][1]-1 of feat[s] ([S][max_out][H]).
-__global__ __launch_bounds__(256) void llm_rmsnorm_slots_kernel(const half_t* __restrict__ x, long ldx,
-                                                                const half_t* __restrict__ gamma,
-                                                                half_t* __restrict__ y, long ldy,
-                                                                half_t* __restrict__ feat,
-                                                                const int* __restrict__ state, int H, int max_out,
-                                                                float eps) {
-    const int s = blockIdx.x;
-    const int* st = state + 8 * s;
-    half_t* fr = nullptr;
-    if (feat) {
-        const int row = st[1] - 1;
-        if (row >= 0 && row < max_out && !st[2]) fr = feat + ((long)s * max_out + row) * H;
-    }
-    llm_rmsnorm_row(x + (long)s * ldx, gamma, y + (long)s * ldy, fr, H, eps);
-}
-
-// h[0,:] = embed_tokens[state[3]]
+// h[m,:] = embed_tokens[state[m][3]]  (one-sequence form: one row, h[0,:] = embed_tokens[state[3]])
 __global__ __launch_bounds__(256) void llm_embed_kernel(const half_t* __restrict__ table, const int* __restrict__ state,
-                                                        half_t* __restrict__ out, int H, int vocab) {
-    const int tok = min(max(state[3], 0), vocab - 1);
+                                                        int state_stride, half_t* __restrict__ out, long ldo, int H,
+                                                        int vocab) {
+    const int m = blockIdx.y;
+    const int tok = min(max(state[state_stride * m + 3], 0), vocab - 1);
     const int k = (blockIdx.x * 256 + threadIdx.x) * 8;
-    if (k < H) *reinterpret_cast<h8*>(out + k) = *reinterpret_cast<const h8*>(table + (long)tok * H + k);
-}
-
-// Batched decode: h[s,:] = embed_tokens[state[s][3]]
-__global__ __launch_bounds__(256) void llm_embed_slots_kernel(const half_t* __restrict__ table,
-                                                              const int* __restrict__ state, half_t* __restrict__ out,
-                                                              long ldo, int H, int vocab) {
-    const int s = blockIdx.y;
-    const int tok = min(max(state[8 * s + 3], 0), vocab - 1);
-    const int k = (blockIdx.x * 256 + threadIdx.x) * 8;
-    if (k < H) *reinterpret_cast<h8*>(out + (long)s * ldo + k) = *reinterpret_cast<const h8*>(table + (long)tok * H + k);
+    if (k < H) *reinterpret_cast<h8*>(out + (long)m * ldo + k) = *reinterpret_cast<const h8*>(table + (long)tok * H + k);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -479,21 +462,15 @@ __device__ __forceinline__ void llm_select_body(const half_t* __restrict__ logit
     }
 }
 
-__global__ __launch_bounds__(1024) void llm_select_kernel(const half_t* __restrict__ logits, int V,
+// One block per row m over logits[m] (row stride ldl), with the row's own state (its eos and max_new live there) and its
+// own out_ids[m] ([S][out_cap]).  The one-sequence form is one row.
+__global__ __launch_bounds__(1024) void llm_select_kernel(const half_t* __restrict__ logits, long ldl, int V,
                                                           const int* __restrict__ chain, int n_chain, int out_cap,
-                                                          int adv, int* __restrict__ state,
+                                                          int adv, int* __restrict__ state, int state_stride,
                                                           int* __restrict__ out_ids) {
-    llm_select_body(logits, V, chain, n_chain, out_cap, adv, state, out_ids);
-}
-
-// Batched decode: one block per slot over logits[s] (row stride ldl), with the slot's own state row (its eos and
-// max_new live there) and its own out_ids[s] ([S][out_cap]).
-__global__ __launch_bounds__(1024) void llm_select_slots_kernel(const half_t* __restrict__ logits, long ldl, int V,
-                                                                const int* __restrict__ chain, int n_chain,
-                                                                int out_cap, int adv, int* __restrict__ state,
-                                                                int* __restrict__ out_ids) {
-    const int s = blockIdx.x;
-    llm_select_body(logits + (long)s * ldl, V, chain, n_chain, out_cap, adv, state + 8 * s, out_ids + (long)s * out_cap);
+    const int m = blockIdx.x;
+    llm_select_body(logits + (long)m * ldl, V, chain, n_chain, out_cap, adv, state + state_stride * m,
+                    out_ids + (long)m * out_cap);
 }
 
 // act[m][n] = silu(gu[m][n]) * gu[m][I+n]  (prompt pass: the gate|up projection comes out of the MFMA GEMM as [M,2I])
@@ -1064,7 +1041,9 @@ int ds_launch_llm_dequant_w8(const int8_t* q, const float* scale, half_t* w16, l
     return 0;
 }
 
-static int check_llm_attn(const LlmAttnParams& p) {
+// ---- the four per-row kernels: one launcher and one argument check per kind, both row forms (ds_kernels.h; the callers in
+// capi.hip pass state_stride 0 or 8, and one row to the one-sequence embed and pick)
+int ds_launch_llm_attn(const LlmAttnParams& p, hipStream_t stream) {
     DS_REQUIRE(p.D == 64 || p.D == 128, "llm_attn: head_dim %d unsupported (64 or 128)", p.D);
     DS_REQUIRE(p.M > 0 && p.M <= 16, "llm_attn: %d rows per pass (1..16)", p.M);
     DS_REQUIRE(p.heads > 0 && p.kv_heads > 0 && p.heads % p.kv_heads == 0, "llm_attn: heads %d / kv_heads %d", p.heads,
@@ -1072,11 +1051,10 @@ static int check_llm_attn(const LlmAttnParams& p) {
     DS_REQUIRE(p.T_max > 0 && p.T_max <= 8192, "llm_attn: cache length %d (max 8192)", p.T_max);
     DS_REQUIRE(p.ldqkv % 8 == 0 && p.ldc % 8 == 0, "llm_attn: row strides must be multiples of 8");
     DS_REQUIRE(p.qkv && p.kc && p.vc && p.rope_cos && p.rope_sin && p.out && p.state, "llm_attn: null operand");
-    return 0;
-}
-
-int ds_launch_llm_attn(const LlmAttnParams& p, hipStream_t stream) {
-    if (const int rc = check_llm_attn(p)) return rc;
+    if (p.state_stride)   // a negative stride fails here too
+        DS_REQUIRE(p.slot_stride % 8 == 0 && p.slot_stride >= (long)p.T_max * p.ldc, "llm_attn: slot stride %ld < T_max * ldc",
+                   p.slot_stride);
+    else DS_REQUIRE(p.slot_stride == 0, "llm_attn: the one-sequence form has one cache (slot stride %ld)", p.slot_stride);
     const size_t lds = (size_t)(p.T_max + ATT_WAVES * p.D + 2 * ATT_WAVES) * sizeof(float);
     const dim3 grid(p.heads, p.M);
     if (p.D == 128) hipLaunchKernelGGL(llm_attn_kernel<128>, grid, dim3(64 * ATT_WAVES), lds, stream, p);
@@ -1085,75 +1063,36 @@ int ds_launch_llm_attn(const LlmAttnParams& p, hipStream_t stream) {
     return 0;
 }
 
-// p.M = number of slots (one row each); slot s: caches at kc / vc + s * slot_stride, state row state + 8 s
-int ds_launch_llm_attn_slots(const LlmAttnParams& p, long slot_stride, hipStream_t stream) {
-    if (const int rc = check_llm_attn(p)) return rc;
-    DS_REQUIRE(slot_stride % 8 == 0 && slot_stride >= (long)p.T_max * p.ldc, "llm_attn_slots: slot stride %ld < T_max * ldc",
-               slot_stride);
-    const size_t lds = (size_t)(p.T_max + ATT_WAVES * p.D + 2 * ATT_WAVES) * sizeof(float);
-    const dim3 grid(p.heads, p.M);
-    if (p.D == 128) hipLaunchKernelGGL(llm_attn_slots_kernel<128>, grid, dim3(64 * ATT_WAVES), lds, stream, p, slot_stride);
-    else hipLaunchKernelGGL(llm_attn_slots_kernel<64>, grid, dim3(64 * ATT_WAVES), lds, stream, p, slot_stride);
-    DS_LAUNCH_CHECK();
-    return 0;
-}
-
-int ds_launch_llm_rmsnorm_slots(const half_t* x, long ldx, const half_t* gamma, half_t* y, long ldy, half_t* feat,
-                                const int* state, int S, int H, int max_out, float eps, hipStream_t stream) {
-    DS_REQUIRE(S > 0 && H >= 8 && H % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0, "llm_rmsnorm_slots: bad shape S=%d H=%d", S, H);
-    DS_REQUIRE(x && gamma && y && (!feat || state), "llm_rmsnorm_slots: null operand");
-    hipLaunchKernelGGL(llm_rmsnorm_slots_kernel, dim3(S), dim3(256), 0, stream, x, ldx, gamma, y, ldy, feat, state, H,
+int ds_launch_llm_rmsnorm(const half_t* x, long ldx, const half_t* gamma, half_t* y, long ldy, half_t* feat,
+                          const int* state, int state_stride, int M, int H, int max_out, float eps, hipStream_t stream) {
+    DS_REQUIRE(M > 0 && H >= 8 && H % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0, "llm_rmsnorm: bad shape M=%d H=%d", M, H);
+    DS_REQUIRE(x && gamma && y && (!feat || state), "llm_rmsnorm: null operand");
+    DS_REQUIRE(!feat || state_stride || M == 1, "llm_rmsnorm: the feature tap of one sequence is for the 1-row token loop");
+    hipLaunchKernelGGL(llm_rmsnorm_kernel, dim3(M), dim3(256), 0, stream, x, ldx, gamma, y, ldy, feat, state, state_stride, H,
                        max_out, eps);
     DS_LAUNCH_CHECK();
     return 0;
 }
 
-int ds_launch_llm_embed_slots(const half_t* table, const int* state, half_t* out, long ldo, int S, int H, int vocab,
-                              hipStream_t stream) {
-    DS_REQUIRE(S > 0 && H % 8 == 0 && vocab > 0 && ldo % 8 == 0 && ldo >= H, "llm_embed_slots: bad shape S=%d H=%d vocab=%d", S,
-               H, vocab);
-    DS_REQUIRE(table && state && out, "llm_embed_slots: null operand");
-    hipLaunchKernelGGL(llm_embed_slots_kernel, dim3((H / 8 + 255) / 256, S), dim3(256), 0, stream, table, state, out, ldo,
-                       H, vocab);
+int ds_launch_llm_embed(const half_t* table, const int* state, int state_stride, half_t* out, long ldo, int M, int H,
+                        int vocab, hipStream_t stream) {
+    DS_REQUIRE(M > 0 && H % 8 == 0 && vocab > 0 && ldo % 8 == 0 && ldo >= H, "llm_embed: bad shape M=%d H=%d vocab=%d", M, H,
+               vocab);
+    DS_REQUIRE(table && state && out, "llm_embed: null operand");
+    hipLaunchKernelGGL(llm_embed_kernel, dim3((H / 8 + 255) / 256, M), dim3(256), 0, stream, table, state, state_stride, out,
+                       ldo, H, vocab);
     DS_LAUNCH_CHECK();
     return 0;
 }
 
-int ds_launch_llm_select_slots(const half_t* logits, long ldl, int V, const int* chain, int n_chain, int out_cap, int adv,
-                               int* state, int* out_ids, int S, hipStream_t stream) {
-    DS_REQUIRE(S > 0 && V > 0 && ldl >= V && n_chain >= 0 && n_chain <= 1024 && out_cap > 0 && adv >= 0,
-               "llm_select_slots: bad arguments");
-    DS_REQUIRE(n_chain == 0 || chain, "llm_select_slots: chain ids missing");
-    DS_REQUIRE(logits && state && out_ids, "llm_select_slots: null operand");
-    hipLaunchKernelGGL(llm_select_slots_kernel, dim3(S), dim3(1024), 0, stream, logits, ldl, V, chain, n_chain, out_cap,
-                       adv, state, out_ids);
-    DS_LAUNCH_CHECK();
-    return 0;
-}
-
-int ds_launch_llm_rmsnorm(const half_t* x, long ldx, const half_t* gamma, half_t* y, long ldy, half_t* feat,
-                          const int* state, int M, int H, int max_out, float eps, hipStream_t stream) {
-    DS_REQUIRE(M > 0 && H >= 8 && H % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0, "llm_rmsnorm: bad shape M=%d H=%d", M, H);
-    DS_REQUIRE(!feat || (state && M == 1), "llm_rmsnorm: the feature tap is for the 1-row token loop");
-    hipLaunchKernelGGL(llm_rmsnorm_kernel, dim3(M), dim3(256), 0, stream, x, ldx, gamma, y, ldy, feat, state, H, max_out,
-                       eps);
-    DS_LAUNCH_CHECK();
-    return 0;
-}
-
-int ds_launch_llm_embed(const half_t* table, const int* state, half_t* out, int H, int vocab, hipStream_t stream) {
-    DS_REQUIRE(H % 8 == 0 && vocab > 0, "llm_embed: bad shape H=%d vocab=%d", H, vocab);
-    hipLaunchKernelGGL(llm_embed_kernel, dim3((H / 8 + 255) / 256), dim3(256), 0, stream, table, state, out, H, vocab);
-    DS_LAUNCH_CHECK();
-    return 0;
-}
-
-int ds_launch_llm_select(const half_t* logits, int V, const int* chain, int n_chain, int out_cap, int adv, int* state,
-                         int* out_ids, hipStream_t stream) {
-    DS_REQUIRE(V > 0 && n_chain >= 0 && n_chain <= 1024 && out_cap > 0 && adv >= 0, "llm_select: bad arguments");
+int ds_launch_llm_select(const half_t* logits, long ldl, int V, const int* chain, int n_chain, int out_cap, int adv,
+                         int* state, int state_stride, int* out_ids, int M, hipStream_t stream) {
+    DS_REQUIRE(M > 0 && V > 0 && ldl >= V && n_chain >= 0 && n_chain <= 1024 && out_cap > 0 && adv >= 0,
+               "llm_select: bad arguments");
     DS_REQUIRE(n_chain == 0 || chain, "llm_select: chain ids missing");
-    hipLaunchKernelGGL(llm_select_kernel, dim3(1), dim3(1024), 0, stream, logits, V, chain, n_chain, out_cap, adv, state,
-                       out_ids);
+    DS_REQUIRE(logits && state && out_ids, "llm_select: null operand");
+    hipLaunchKernelGGL(llm_select_kernel, dim3(M), dim3(1024), 0, stream, logits, ldl, V, chain, n_chain, out_cap, adv,
+                       state, state_stride, out_ids);
     DS_LAUNCH_CHECK();
     return 0;
 }

@@ -22,11 +22,13 @@ raises.
 
 Batched decode (`LlamaDecodeEngine(max_sequences=S)`, `generate_batch`, `ContinuousLVLM.generate_batch`,
 `mllm_prepass_batch`): the token loop is HBM-bound on the weights, and a step for up to 16 sequences reads the same
-weights as a step for one.  The engine then owns S cache slots, an int32 [S][8] state block, and per-slot id and feature
-buffers; one token step is one static launch list over all S rows (`llm_gemm16_kernel` for every projection, the
-per-slot attention / norm / pick kernels), whatever number of slots is in use, so a sequence's ids and hidden states do
-not depend on what the other slots hold or on the slot it sits in.  A finished or unused slot is skipped by every
-kernel that writes per-slot state.  KV memory: a slot is 2 x layers x T_max x kv_heads x head_dim fp16 = 0.84 GB at
+weights as a step for one.  The engine owns S cache slots, an int32 [S][8] state block, and per-slot id and feature
+buffers; a sequence is a batch of one slot, so both entries are one decode loop (`_decode`) over one token plan built at
+a width: width 1 for `generate` (slot 0, projections on the `llm_gemv` kernels), width S for `generate_batch` (one static
+launch list over all S rows, `llm_gemm16_kernel` for every projection, whatever number of slots is in use); embed,
+attention, final norm and pick are the slot-form ops in both.  A sequence's ids and hidden states do not depend on what
+the other slots hold or on the slot it sits in.  A finished or unused slot is skipped by every kernel that writes
+per-slot state.  KV memory: a slot is 2 x layers x T_max x kv_heads x head_dim fp16 = 0.84 GB at
 13B dimensions and T_max 1024 (13.4 GB for 16 slots, next to 26 GB of weights).
 
 int8 weight-only decoding (`LlamaDecodeEngine(weight_dtype="int8")`, W8A16): the four projection groups of every layer
@@ -137,7 +139,8 @@ class LlamaDecodeEngine:
                  max_sequences: int = 1, weight_dtype: str = "float16"):
         """max_sequences S > 1: `generate_batch` decodes up to S sequences per weight pass; the engine then holds S KV-cache
         slots (each 2 x layers x max_positions x kv_heads x head_dim fp16: 0.84 GB at 13B dimensions and 1024 positions)
-        and [S] id / feature / logits buffers.  With 1 nothing extra is allocated.
+        and [S] state / id / feature / logits rows.  `generate` is one sequence in slot 0, whatever S is.
+        prompt_path applies to `generate` only: `generate_batch` always takes the MFMA prompt pass.
         weight_dtype "int8": the q|k|v, o, gate|up and down matrices are held as int8 with fp32 row scales (W8A16, see
         `quantize_rows_int8`); the embedding, lm_head and the RMSNorm gains stay fp16."""
         _lib.load()
@@ -197,24 +200,21 @@ class LlamaDecodeEngine:
         E = lambda *s, dtype=torch.float16: torch.zeros(s, dtype=dtype, device=dev)
         self.qkv_dim = (Hq + 2 * Hkv) * D
         self.h, self.qkv, self.att = E(CHUNK, H), E(CHUNK, self.qkv_dim), E(CHUNK, Hq * D)
-        self.act, self.hn, self.logits = E(CHUNK, I), E(1, H), E(V)
-        # [S, T_max, kv_heads*D] per layer; `generate` uses slot 0
+        self.act = E(CHUNK, I)
+        # per slot: KV cache [S, T_max, kv_heads*D] per layer, state block, generated ids, fed-back hidden states, final-norm
+        # row and logits.  `generate` uses slot 0.
         self.kcs = [E(S, self.T_max, Hkv * D) for _ in range(L)]
         self.vcs = [E(S, self.T_max, Hkv * D) for _ in range(L)]
-        self.kc, self.vc = [t[0] for t in self.kcs], [t[0] for t in self.vcs]
+        self.state = E(S, 8, dtype=torch.int32)
+        self.state[:, 2] = 1                                # no slot started: every per-slot kernel skips it
+        self.out_ids, self.feats = E(S, self.cap, dtype=torch.int32), E(S, self.cap, H)
+        self.feat = self.feats[0]                           # slot 0's rows: what `generate` fills
+        self.hn, self.logits = E(S, H), E(S, V)
         inv_freq = 1.0 / (cfg.rope_theta ** (torch.arange(0, D, 2, dtype=torch.float32) / D))
         fr = torch.outer(torch.arange(self.T_max, dtype=torch.float32), inv_freq)      # rotary table (weights-like)
         self.rope_cos, self.rope_sin = fr.cos().to(dev).contiguous(), fr.sin().to(dev).contiguous()
-        self.state = E(8, dtype=torch.int32)
         self.state_pf = E(8, dtype=torch.int32)             # prompt pass: per-layer chunk cursor (see _prompt_mfma)
         self.prompt_path = prompt_path
-        self.out_ids = E(self.cap, dtype=torch.int32)
-        self.feat = E(self.cap, H)
-        if S > 1:
-            self.state_b = E(S, 8, dtype=torch.int32)
-            self.state_b[:, 2] = 1                          # no slot started: every per-slot kernel skips it
-            self.out_ids_b, self.feat_b = E(S, self.cap, dtype=torch.int32), E(S, self.cap, H)
-            self.hn_b, self.logits_b = E(S, H), E(S, V)
         self.chain = E(1, dtype=torch.int32)
         self.n_chain = 0
         self._plans: Dict[tuple, Plan] = {}
@@ -254,83 +254,71 @@ class LlamaDecodeEngine:
             return None, None, None, None
         return self.sqkv[l], self.so[l], self.sgu[l], self.sdown[l]
 
-    def _ops(self, M: int, kind: str) -> list:
-        """kind: 'chunk' (prompt rows, more follow), 'last' (final prompt chunk -> first token), 'token' (1 row)."""
+    def _layer_ops(self, l: int, M: int, proj: str, slots: bool) -> list:
+        """The five launches of layer l over M rows.  slots: every row is its own sequence (slot-form attention on the
+        row's cache slot and state row); otherwise the rows are M positions of the sequence in slot 0."""
         c = self.cfg
-        H, I, V = c.hidden_size, c.intermediate_size, c.vocab_size
-        D, Hq, Hkv = c.head_dim, c.num_attention_heads, c.kv_heads
-        eps, scale = c.rms_norm_eps, 1.0 / math.sqrt(D)
-        ops_ = []
-        if kind == "token":
-            ops_.append(make_op("LLM_EMBED", i=(H, V), p=(self.embed, self.state, self.h)))
+        H, I, D, Hq, Hkv = c.hidden_size, c.intermediate_size, c.head_dim, c.num_attention_heads, c.kv_heads
+        sq, so, sg, sd_ = self._scales(l)
+        return [
+            self._proj(proj, self.wqkv[l], sq, (M, self.qkv_dim, H, 1, 0), (H, self.qkv_dim, 0),
+                       (self.h, self.qkv, None, self.g_in[l])),
+            make_op("LLM_ATTN_SLOTS" if slots else "LLM_ATTN", i=(M, Hq, Hkv, D, self.T_max), f=(1.0 / math.sqrt(D),),
+                    l=(self.qkv_dim, Hkv * D, Hq * D) + ((self.kcs[l].stride(0),) if slots else ()),
+                    p=(self.qkv, self.kcs[l], self.vcs[l], self.rope_cos, self.rope_sin, self.att, self.state)),
+            self._proj(proj, self.wo[l], so, (M, H, Hq * D, 0, 0), (Hq * D, H, H), (self.att, self.h, self.h, None)),
+            self._proj(proj, self.wgu[l], sg, (M, I, H, 1, 1), (H, I, 0), (self.h, self.act, None, self.g_post[l])),
+            self._proj(proj, self.wdown[l], sd_, (M, H, I, 0, 0), (I, H, H), (self.act, self.h, self.h, None)),
+        ]
+
+    def _token_ops(self, width: int) -> list:
+        """One token step for the first `width` slots, one row each: slot-form embed / attention / final norm with tap /
+        pick, and every projection on `llm_gemv` kernels at width 1 (`generate`), on `llm_gemm16_kernel` at the engine's
+        width S (`generate_batch`, whatever number of slots is in use)."""
+        c = self.cfg
+        H, V, eps = c.hidden_size, c.vocab_size, c.rms_norm_eps
+        proj = "LLM_GEMV" if width == 1 else "LLM_GEMM16"
+        ops_ = [make_op("LLM_EMBED_SLOTS", i=(width, H, V), l=(H,), p=(self.embed, self.state, self.h))]
         for l in range(c.num_hidden_layers):
-            sq, so, sg, sd_ = self._scales(l)
-            ops_.append(self._proj("LLM_GEMV", self.wqkv[l], sq, (M, self.qkv_dim, H, 1, 0), (H, self.qkv_dim, 0),
-                                   (self.h, self.qkv, None, self.g_in[l])))
-            ops_.append(make_op("LLM_ATTN", i=(M, Hq, Hkv, D, self.T_max), f=(scale,), l=(self.qkv_dim, Hkv * D, Hq * D),
-                                p=(self.qkv, self.kc[l], self.vc[l], self.rope_cos, self.rope_sin, self.att,
-                                   self.state)))
-            ops_.append(self._proj("LLM_GEMV", self.wo[l], so, (M, H, Hq * D, 0, 0), (Hq * D, H, H),
-                                   (self.att, self.h, self.h, None)))
-            ops_.append(self._proj("LLM_GEMV", self.wgu[l], sg, (M, I, H, 1, 1), (H, I, 0),
-                                   (self.h, self.act, None, self.g_post[l])))
-            ops_.append(self._proj("LLM_GEMV", self.wdown[l], sd_, (M, H, I, 0, 0), (I, H, H),
-                                   (self.act, self.h, self.h, None)))
+            ops_ += self._layer_ops(l, width, proj, slots=True)
+        ops_.append(make_op("LLM_RMSNORM_SLOTS", i=(width, H, self.cap), f=(eps,), l=(H, H),
+                            p=(self.h, self.norm_g, self.hn, self.feats, self.state)))
+        ops_.append(make_op(proj, i=(width, V, H, 0, 0), f=(eps,), l=(H, V, 0), p=(self.hn, self.lm_head, self.logits, None)))
+        ops_.append(make_op("LLM_SELECT_SLOTS", i=(V, self.n_chain, self.cap, 1, width), l=(V,),
+                            p=(self.logits, self.chain if self.n_chain else None, self.state, self.out_ids)))
+        return ops_
+
+    def _chunk_ops(self, M: int, kind: str) -> list:
+        """M <= 16 prompt rows of the sequence in slot 0 through the token kernels.  kind: 'chunk' (more rows follow),
+        'last' (final prompt chunk -> first token)."""
+        c = self.cfg
+        H, V, eps = c.hidden_size, c.vocab_size, c.rms_norm_eps
+        ops_ = []
+        for l in range(c.num_hidden_layers):
+            ops_ += self._layer_ops(l, M, "LLM_GEMV", slots=False)
         if kind == "chunk":
             ops_.append(make_op("LLM_ADVANCE", i=(M,), p=(self.state,)))
             return ops_
         last_row = self.h.data_ptr() + (M - 1) * H * 2
         ops_.append(make_op("LLM_RMSNORM", i=(1, H, self.cap), f=(eps,), l=(H, H),
-                            p=(last_row, self.norm_g, self.hn, self.feat if kind == "token" else None, self.state)))
+                            p=(last_row, self.norm_g, self.hn, None, self.state)))
         ops_.append(make_op("LLM_GEMV", i=(1, V, H, 0, 0), f=(eps,), l=(H, V, 0),
                             p=(self.hn, self.lm_head, self.logits, None)))
         ops_.append(make_op("LLM_SELECT", i=(V, self.n_chain, self.cap, M),
                             p=(self.logits, self.chain if self.n_chain else None, self.state, self.out_ids)))
         return ops_
 
-    def _ops_batch(self) -> list:
-        """One token step for all S slots: the `token` list of `_ops` with every projection on `llm_gemm16_kernel` (M = S
-        whatever number of slots is in use) and the per-slot embed / attention / final norm / pick kernels."""
-        c, S = self.cfg, self.max_sequences
-        H, I, V = c.hidden_size, c.intermediate_size, c.vocab_size
-        D, Hq, Hkv = c.head_dim, c.num_attention_heads, c.kv_heads
-        eps, scale = c.rms_norm_eps, 1.0 / math.sqrt(D)
-        ops_ = [make_op("LLM_EMBED_SLOTS", i=(S, H, V), l=(H,), p=(self.embed, self.state_b, self.h))]
-        for l in range(c.num_hidden_layers):
-            sq, so, sg, sd_ = self._scales(l)
-            ops_.append(self._proj("LLM_GEMM16", self.wqkv[l], sq, (S, self.qkv_dim, H, 1, 0), (H, self.qkv_dim, 0),
-                                   (self.h, self.qkv, None, self.g_in[l])))
-            ops_.append(make_op("LLM_ATTN_SLOTS", i=(S, Hq, Hkv, D, self.T_max), f=(scale,),
-                                l=(self.qkv_dim, Hkv * D, Hq * D, self.kcs[l].stride(0)),
-                                p=(self.qkv, self.kcs[l], self.vcs[l], self.rope_cos, self.rope_sin, self.att,
-                                   self.state_b)))
-            ops_.append(self._proj("LLM_GEMM16", self.wo[l], so, (S, H, Hq * D, 0, 0), (Hq * D, H, H),
-                                   (self.att, self.h, self.h, None)))
-            ops_.append(self._proj("LLM_GEMM16", self.wgu[l], sg, (S, I, H, 1, 1), (H, I, 0),
-                                   (self.h, self.act, None, self.g_post[l])))
-            ops_.append(self._proj("LLM_GEMM16", self.wdown[l], sd_, (S, H, I, 0, 0), (I, H, H),
-                                   (self.act, self.h, self.h, None)))
-        ops_.append(make_op("LLM_RMSNORM_SLOTS", i=(S, H, self.cap), f=(eps,), l=(H, H),
-                            p=(self.h, self.norm_g, self.hn_b, self.feat_b, self.state_b)))
-        ops_.append(make_op("LLM_GEMM16", i=(S, V, H, 0, 0), f=(eps,), l=(H, V, 0),
-                            p=(self.hn_b, self.lm_head, self.logits_b, None)))
-        ops_.append(make_op("LLM_SELECT_SLOTS", i=(V, self.n_chain, self.cap, 1, S), l=(V,),
-                            p=(self.logits_b, self.chain if self.n_chain else None, self.state_b, self.out_ids_b)))
-        return ops_
-
     def weights_changed(self) -> None:
-        """The weight tensors moved or changed (multi-GPU broadcast into the weight arena): cached launch plans - the
-        one-sequence ones and the batched token step - hold raw pointers and are rebuilt on next use."""
+        """The weight tensors moved or changed (multi-GPU broadcast into the weight arena): cached launch plans hold raw
+        pointers and are rebuilt on next use."""
         self._plans.clear()
 
     def _plan(self, M: int, kind: str) -> Plan:
+        """kind 'token': the token step at width M; 'chunk' / 'last': M prompt rows"""
         key = (M, kind, self.n_chain, self.chain.data_ptr())
         pl = self._plans.get(key)
-        if pl is None and kind == "token_batch":
-            pl = Plan(self._ops_batch(), keep=[self])
-            self._plans[key] = pl
         if pl is None:
-            pl = Plan(self._ops(M, kind), keep=[self])
+            pl = Plan(self._token_ops(M) if kind == "token" else self._chunk_ops(M, kind), keep=[self])
             self._plans[key] = pl
         return pl
 
@@ -349,114 +337,40 @@ class LlamaDecodeEngine:
     def generate(self, inputs_embeds: Tensor, last_prompt_id: int, eos_token_id: int, max_new_tokens: int) -> dict:
         """Greedy decoding from prompt embeddings [T0, hidden] (fp16, device).  Returns the new ids [n] (int64, device)
         and `hidden` [n-1, hidden]: the post-final-norm state of every generated token that was fed back."""
-        T0 = int(inputs_embeds.shape[0])
-        H = self.cfg.hidden_size
-        if inputs_embeds.shape[1] != H or inputs_embeds.dtype != torch.float16 or not inputs_embeds.is_cuda:
-            raise ValueError("inputs_embeds must be a fp16 device tensor [T, hidden]")
-        max_new = int(max_new_tokens)
-        if not 0 < max_new <= self.cap:
-            raise ValueError(f"max_new_tokens {max_new} outside (0, {self.cap}] (engine capacity)")
-        if T0 < 1 or T0 + max_new > self.T_max:
-            raise ValueError(f"prompt {T0} + max_new_tokens {max_new} exceeds the KV cache ({self.T_max} positions)")
-        dev = self.dev
-        if self._stream is None:
-            self._stream = torch.cuda.Stream(device=dev)
-        st = self._stream
-        st.wait_stream(torch.cuda.current_stream(dev))
-        graph = False
-        steps = 0
-        with torch.cuda.stream(st):
-            self.state.copy_(torch.tensor([0, 0, 0, int(last_prompt_id), max_new, int(eos_token_id), 0, 0],
-                                          dtype=torch.int32), non_blocking=False)
-            if T0 > CHUNK and self.prompt_path == "mfma":
-                self._prompt_mfma(inputs_embeds)
-            else:
-                for r0 in range(0, T0, CHUNK):
-                    m = min(CHUNK, T0 - r0)
-                    self.h[:m].copy_(inputs_embeds[r0:r0 + m])
-                    self._plan(m, "last" if r0 + m == T0 else "chunk").run(st.cuda_stream)
-            tok = self._plan(1, "token")
-            done = False
-            while not done and steps < max_new - 1:
-                burst = min(self.poll_every, max_new - 1 - steps)
-                for _ in range(burst):
-                    if self.use_graph and not tok.captured:
-                        tok.run(st.cuda_stream)       # first token eager, then capture the launch list once
-                        tok.capture(st.cuda_stream)
-                    elif self.use_graph:
-                        tok.replay(st.cuda_stream)
-                        graph = True
-                    else:
-                        tok.run(st.cuda_stream)
-                steps += burst
-                done = bool(self.state[2].item())     # the only host<->device sync of the loop (every `poll_every`)
-            n = int(self.state[1].item())
-            ids = self.out_ids[:n].to(torch.int64)
-            hidden = self.feat[:max(n - 1, 0)].clone()
-        torch.cuda.current_stream(dev).wait_stream(st)
-        self.last_run_info = {"graph": graph, "prompt_tokens": T0, "new_tokens": n, "token_steps_launched": steps,
-                              "ops_per_token": tok.n}
-        return {"ids": ids, "hidden": hidden}
+        out = self._decode([inputs_embeds], [int(last_prompt_id)], [int(eos_token_id)], [int(max_new_tokens)], [0], width=1)
+        info = self.last_run_info
+        self.last_run_info = {"graph": info["graph"], "prompt_tokens": info["prompt_tokens"][0], "new_tokens": info["new_tokens"][0],
+                              "token_steps_launched": info["token_steps_launched"], "ops_per_token": info["ops_per_token"]}
+        return out[0]
 
-    def _w(self, ws: list, ss: list, l: int) -> Tensor:
-        """The fp16 matrix a prompt-pass GEMM reads: the weight itself, or - int8 - its dequantised copy in the one
-        reusable scratch (sized for the largest group, gate|up; stream order keeps the previous user ahead of the rewrite)."""
-        if self.weight_dtype != "int8":
-            return ws[l]
-        if self._w16 is None:
-            n = max(w.numel() for group in (self.wqkv, self.wo, self.wgu, self.wdown) for w in group[:1])
-            self._w16 = torch.empty(n, dtype=torch.float16, device=self.dev)
-        return ops.llm_dequant_w8(ws[l], ss[l], out=self._w16)
-
-    def _prompt_mfma(self, inputs_embeds: Tensor) -> None:
-        """Whole prompt in one pass per layer: the projections are [T0,K] x [N,K]^T MFMA GEMMs (weights streamed once
-        per layer instead of once per 16-row chunk); only the attention walks the rows in chunks of 16 (causal inside
-        a chunk, cache rows before it).  Ends like the chunked path: final norm of the last row, lm_head, first pick."""
-        c = self.cfg
-        T0 = int(inputs_embeds.shape[0])
-        Hq, Hkv, eps = c.num_attention_heads, c.kv_heads, c.rms_norm_eps
-        scale = 1.0 / math.sqrt(c.head_dim)
-        pf = self.state_pf
-        h = inputs_embeds.contiguous().clone()
-        att = torch.empty((T0, Hq * c.head_dim), dtype=torch.float16, device=self.dev)
-        for l in range(c.num_hidden_layers):
-            xn = ops.llm_rmsnorm(h, self.g_in[l], eps)                       # LlamaRMSNorm incl. its gain, then the plain GEMM
-            qkv = ops.gemm(xn, self._w(self.wqkv, self.sqkv, l))
-            pf.zero_()                                                       # chunk cursor of this layer's cache
-            for r0 in range(0, T0, CHUNK):
-                m = min(CHUNK, T0 - r0)
-                ops.llm_attention(qkv[r0:r0 + m], self.kc[l], self.vc[l], self.rope_cos, self.rope_sin, pf, Hq, Hkv,
-                                  scale, out=att[r0:r0 + m])
-                ops.llm_advance(pf, m)
-            h = ops.gemm(att, self._w(self.wo, self.so, l), residual=h)
-            xn = ops.llm_rmsnorm(h, self.g_post[l], eps)
-            act = ops.llm_swiglu(ops.gemm(xn, self._w(self.wgu, self.sgu, l)))
-            h = ops.gemm(act, self._w(self.wdown, self.sdown, l), residual=h)
-        ops.llm_rmsnorm(h[T0 - 1:T0], self.norm_g, eps, out=self.hn)
-        ops.llm_gemv(self.hn, self.lm_head, out=self.logits.view(1, -1))
-        ops.llm_select(self.logits, self.chain if self.n_chain else None, T0, self.state, self.out_ids)
-
-    # ---- batched generation -----------------------------------------------------------------------------
     @torch.no_grad()
     def generate_batch(self, inputs_embeds: Sequence[Tensor], last_prompt_ids: Sequence[int], eos_token_ids,
                        max_new_tokens, slots: Optional[Sequence[int]] = None) -> List[dict]:
         """`generate` for 1 <= n <= max_sequences sequences of different prompt lengths in one decode loop.
         `eos_token_ids` / `max_new_tokens`: one value for all, or one per sequence.  `slots`: the cache slot of each
         sequence (default 0..n-1); results do not depend on it.  Returns one {"ids", "hidden"} per sequence."""
-        S, H = self.max_sequences, self.cfg.hidden_size
+        S = self.max_sequences
         embs = list(inputs_embeds)
         n = len(embs)
         if S < 2:
             raise ValueError("generate_batch needs an engine built with max_sequences > 1")
         if not 1 <= n <= S:
             raise ValueError(f"{n} sequences: the engine has {S} slots")
-        per = lambda v, what: [int(x) for x in v] if isinstance(v, (list, tuple)) else [int(v)] * n
-        last, eos, max_new = per(list(last_prompt_ids), "last"), per(eos_token_ids, "eos"), per(max_new_tokens, "max_new")
+        per = lambda v: [int(x) for x in v] if isinstance(v, (list, tuple)) else [int(v)] * n
+        last, eos, max_new = per(list(last_prompt_ids)), per(eos_token_ids), per(max_new_tokens)
         slots = list(range(n)) if slots is None else [int(x) for x in slots]
         if not len(last) == len(eos) == len(max_new) == len(slots) == n:
             raise ValueError("one last_prompt_id / eos / max_new_tokens / slot per sequence is needed")
         if len(set(slots)) != n or min(slots) < 0 or max(slots) >= S:
             raise ValueError(f"slots {slots}: {n} different values in [0, {S}) are needed")
+        return self._decode(embs, last, eos, max_new, slots, width=S)
+
+    def _decode(self, embs: List[Tensor], last: List[int], eos: List[int], max_new: List[int], slots: List[int],
+                width: int) -> List[dict]:
+        """The decode loop of both entries: sequence i in cache slot slots[i], the token step over the first `width` slots
+        (1: `generate`, slot 0; S: `generate_batch`).  Writes the state rows, runs the prompt pass, runs and captures the
+        token plan, replays it in bursts of `poll_every`, polls the finished flags and reads back per slot."""
+        S, H = self.max_sequences, self.cfg.hidden_size
         T0s = []
         for e, mn in zip(embs, max_new):
             if e.dim() != 2 or e.shape[1] != H or e.dtype != torch.float16 or not e.is_cuda:
@@ -467,6 +381,9 @@ class LlamaDecodeEngine:
             if T0 < 1 or T0 + mn > self.T_max:
                 raise ValueError(f"prompt {T0} + max_new_tokens {mn} exceeds the KV cache ({self.T_max} positions)")
             T0s.append(T0)
+        # which kernels compute the prompt decides its bits: one sequence of at most one chunk, or prompt_path "chunks",
+        # goes through the token kernels 16 rows at a time; everything else (every batch) takes the MFMA pass
+        chunks = width == 1 and (T0s[0] <= CHUNK or self.prompt_path == "chunks")
         dev = self.dev
         if self._stream is None:
             self._stream = torch.cuda.Stream(device=dev)
@@ -474,12 +391,18 @@ class LlamaDecodeEngine:
         st.wait_stream(torch.cuda.current_stream(dev))
         graph, steps = False, 0
         rows = [[0, 0, 1, 0, 0, 0, 0, 0] for _ in range(S)]      # unused slots: finished
-        for i, s in enumerate(slots):                            # the cache length starts at the prompt length (the pick adds 0)
-            rows[s] = [T0s[i], 0, 0, last[i], max_new[i], eos[i], 0, 0]
+        for i, s in enumerate(slots):     # cache length: the chunk lists advance it, the MFMA pass leaves it to us (its pick adds 0)
+            rows[s] = [0 if chunks else T0s[i], 0, 0, last[i], max_new[i], eos[i], 0, 0]
         with torch.cuda.stream(st):
-            self.state_b.copy_(torch.tensor(rows, dtype=torch.int32), non_blocking=False)
-            self._prompt_batch(embs, slots)
-            tok = self._plan(S, "token_batch")
+            self.state.copy_(torch.tensor(rows, dtype=torch.int32), non_blocking=False)
+            if chunks:
+                for r0 in range(0, T0s[0], CHUNK):
+                    m = min(CHUNK, T0s[0] - r0)
+                    self.h[:m].copy_(embs[0][r0:r0 + m])
+                    self._plan(m, "last" if r0 + m == T0s[0] else "chunk").run(st.cuda_stream)
+            else:
+                self._prompt_mfma(embs, slots, width)
+            tok = self._plan(width, "token")
             done, most = False, max(max_new) - 1
             while not done and steps < most:
                 burst = min(self.poll_every, most - steps)
@@ -493,33 +416,45 @@ class LlamaDecodeEngine:
                     else:
                         tok.run(st.cuda_stream)
                 steps += burst
-                done = bool(self.state_b.cpu()[:, 2].all())     # every slot's flag in one copy (every `poll_every` steps)
-            state = self.state_b.cpu()
+                # the only host<->device sync of the loop (every `poll_every` steps): every slot's flag in one copy
+                done = bool(self.state.cpu()[:, 2].all())
+            state = self.state.cpu()
             out = []
             for s in slots:
                 k = int(state[s, 1])
-                out.append({"ids": self.out_ids_b[s, :k].to(torch.int64), "hidden": self.feat_b[s, :max(k - 1, 0)].clone()})
+                out.append({"ids": self.out_ids[s, :k].to(torch.int64), "hidden": self.feats[s, :max(k - 1, 0)].clone()})
         torch.cuda.current_stream(dev).wait_stream(st)
-        self.last_run_info = {"graph": graph, "sequences": n, "prompt_tokens": T0s, "new_tokens": [len(o["ids"]) for o in out],
+        self.last_run_info = {"graph": graph, "sequences": len(embs), "prompt_tokens": T0s, "new_tokens": [len(o["ids"]) for o in out],
                               "token_steps_launched": steps, "ops_per_token": tok.n}
         return out
 
-    def _prompt_batch(self, embs: List[Tensor], slots: List[int]) -> None:
-        """`_prompt_mfma` over the concatenated rows of all prompts: one pass per layer, so the weights are read once per
-        layer for the whole batch; only the attention walks each sequence's rows in chunks of 16 into that sequence's
-        slot.  Ends with the final norm of each sequence's last row, lm_head through `llm_gemm16_kernel` over all S rows
-        and the first pick per slot."""
+    def _w(self, ws: list, ss: list, l: int) -> Tensor:
+        """The fp16 matrix a prompt-pass GEMM reads: the weight itself, or - int8 - its dequantised copy in the one
+        reusable scratch (sized for the largest group, gate|up; stream order keeps the previous user ahead of the rewrite)."""
+        if self.weight_dtype != "int8":
+            return ws[l]
+        if self._w16 is None:
+            n = max(w.numel() for group in (self.wqkv, self.wo, self.wgu, self.wdown) for w in group[:1])
+            self._w16 = torch.empty(n, dtype=torch.float16, device=self.dev)
+        return ops.llm_dequant_w8(ws[l], ss[l], out=self._w16)
+
+    def _prompt_mfma(self, embs: List[Tensor], slots: List[int], width: int) -> None:
+        """The prompts of n >= 1 sequences in one pass per layer over their concatenated rows: the projections are
+        [rows,K] x [N,K]^T MFMA GEMMs (weights streamed once per layer for the whole batch instead of once per 16-row
+        chunk); only the attention walks each sequence's rows in chunks of 16 (causal inside a chunk, cache rows before
+        it) into that sequence's slot.  Ends like the chunked path, per slot: final norm of each sequence's last row,
+        lm_head (`llm_gemv` at width 1, `llm_gemm16_kernel` over all S rows otherwise) and the first pick."""
         c = self.cfg
         Hq, Hkv, eps = c.num_attention_heads, c.kv_heads, c.rms_norm_eps
         scale = 1.0 / math.sqrt(c.head_dim)
         pf = self.state_pf
-        h = torch.cat([e.contiguous() for e in embs], 0)
+        h = torch.cat([e.contiguous() for e in embs], 0) if width > 1 else embs[0].contiguous().clone()
         starts = [0]
         for e in embs:
             starts.append(starts[-1] + int(e.shape[0]))
         att = torch.empty((starts[-1], Hq * c.head_dim), dtype=torch.float16, device=self.dev)
         for l in range(c.num_hidden_layers):
-            xn = ops.llm_rmsnorm(h, self.g_in[l], eps)
+            xn = ops.llm_rmsnorm(h, self.g_in[l], eps)                       # LlamaRMSNorm incl. its gain, then the plain GEMM
             qkv = ops.gemm(xn, self._w(self.wqkv, self.sqkv, l))
             for i, s in enumerate(slots):
                 pf.zero_()                                                   # chunk cursor of this slot's cache
@@ -532,13 +467,16 @@ class LlamaDecodeEngine:
             xn = ops.llm_rmsnorm(h, self.g_post[l], eps)
             act = ops.llm_swiglu(ops.gemm(xn, self._w(self.wgu, self.sgu, l)))
             h = ops.gemm(act, self._w(self.wdown, self.sdown, l), residual=h)
-        idx = torch.tensor([starts[i + 1] - 1 for i in range(len(embs))], dtype=torch.long, device=self.dev)
-        self.h.zero_()
-        self.h[torch.tensor(slots, dtype=torch.long, device=self.dev)] = h.index_select(0, idx)
-        S = self.max_sequences
-        ops.llm_rmsnorm_slots(self.h[:S], self.norm_g, eps, out=self.hn_b)
-        ops.llm_gemm16(self.hn_b, self.lm_head, out=self.logits_b)
-        ops.llm_select_slots(self.logits_b, self.chain if self.n_chain else None, 0, self.state_b, self.out_ids_b)
+        if width == 1:
+            last_rows = h[-1:]
+        else:                                                                # row s = the last prompt row of the sequence in slot s
+            idx = torch.tensor([starts[i + 1] - 1 for i in range(len(embs))], dtype=torch.long, device=self.dev)
+            self.h.zero_()
+            self.h[torch.tensor(slots, dtype=torch.long, device=self.dev)] = h.index_select(0, idx)
+            last_rows = self.h[:width]
+        ops.llm_rmsnorm(last_rows, self.norm_g, eps, out=self.hn[:width])
+        (ops.llm_gemv if width == 1 else ops.llm_gemm16)(self.hn[:width], self.lm_head, out=self.logits[:width])
+        ops.llm_select_slots(self.logits[:width], self.chain if self.n_chain else None, 0, self.state[:width], self.out_ids[:width])
 
     def embed_tokens(self, input_ids: Tensor) -> Tensor:
         """Row gather from the embedding table (data movement only)."""
@@ -725,20 +663,7 @@ class ContinuousLVLM:
                  top_p=0.5, img_ids_list: Optional[Sequence[int]] = None, eos_token_id: Optional[int] = None) -> dict:
         q = self._prepare(tokenizer, prompt, input_ids, image_embeds, ids_cmp_mask, logits_processor, num_img_gen_tokens,
                           temperature, num_beams, max_new_tokens, top_p, img_ids_list, eos_token_id)
-        ids, llm = q["ids"], self.llm
-        emb = llm.embed_tokens(ids)
-        if image_embeds is not None:
-            lm = self.input_resampler(image_embeds)
-            emb[ids_cmp_mask.view(-1).to(emb.device)] = lm.reshape(-1, emb.shape[-1])
-        llm.set_image_token_chain(q["chain"])
-        g = llm.generate(emb, int(ids[-1]), q["eos"], q["max_new"])
-        generate_ids, ids_gen_mask, num_gen_imgs, feats = self._image_blocks(q, g)
-        img_gen_feat = None
-        if num_gen_imgs > 0:
-            img_gen_feat = self.output_resampler(torch.stack(feats)).contiguous()
-        text = tokenizer.decode(generate_ids, skip_special_tokens=True) if tokenizer is not None else None
-        return {"text": text, "output_ids": generate_ids, "img_gen_feat": img_gen_feat, "num_gen_imgs": num_gen_imgs,
-                "ids_gen_mask": ids_gen_mask}
+        return self._generate([q], batch=False)[0]
 
     @torch.no_grad()
     def generate_batch(self, requests: Sequence[dict]) -> List[dict]:
@@ -747,25 +672,28 @@ class ContinuousLVLM:
         output resampler once over all image blocks.  All requests must share `img_ids_list` (the processor chain is one
         per launch plan) and `num_img_gen_tokens`."""
         qs = [self._prepare(**r) for r in requests]
-        if not qs:
-            return []
+        return self._generate(qs, batch=True) if qs else []
+
+    def _generate(self, qs: List[dict], batch: bool) -> List[dict]:
+        """Both entries: input resampler, image-token chain, decode, image blocks, output resampler, result dicts.
+        batch: the sequences go through `llm.generate_batch`; otherwise `qs` is one request for `llm.generate`."""
         if any(q["chain"] != qs[0]["chain"] or q["n_img"] != qs[0]["n_img"] for q in qs):
             raise ValueError("generate_batch: all requests must share img_ids_list and num_img_gen_tokens")
         llm = self.llm
         embs = [llm.embed_tokens(q["ids"]) for q in qs]
         with_img = [i for i, q in enumerate(qs) if q["image_embeds"] is not None]
-        if with_img:
-            imgs = [qs[i]["image_embeds"] for i in with_img]
-            if len({tuple(t.shape[1:]) for t in imgs}) == 1:
-                lm = self.input_resampler(torch.cat([t.to(llm.dev) for t in imgs], 0))
-                parts = lm.split([int(t.shape[0]) for t in imgs], 0)
-            else:                                  # different token grids: the position table is per length
-                parts = [self.input_resampler(t) for t in imgs]
-            for i, part in zip(with_img, parts):
-                emb = embs[i]
-                emb[qs[i]["ids_cmp_mask"].view(-1).to(emb.device)] = part.reshape(-1, emb.shape[-1])
+        imgs = [qs[i]["image_embeds"] for i in with_img]
+        if len(imgs) > 1 and len({tuple(t.shape[1:]) for t in imgs}) == 1:
+            lm = self.input_resampler(torch.cat([t.to(llm.dev) for t in imgs], 0))
+            parts = lm.split([int(t.shape[0]) for t in imgs], 0)
+        else:                                      # one request, or different token grids: the position table is per length
+            parts = [self.input_resampler(t) for t in imgs]
+        for i, part in zip(with_img, parts):
+            emb = embs[i]
+            emb[qs[i]["ids_cmp_mask"].view(-1).to(emb.device)] = part.reshape(-1, emb.shape[-1])
         llm.set_image_token_chain(qs[0]["chain"])
-        gs = llm.generate_batch(embs, [int(q["ids"][-1]) for q in qs], [q["eos"] for q in qs], [q["max_new"] for q in qs])
+        last, eos, max_new = [int(q["ids"][-1]) for q in qs], [q["eos"] for q in qs], [q["max_new"] for q in qs]
+        gs = llm.generate_batch(embs, last, eos, max_new) if batch else [llm.generate(embs[0], last[0], eos[0], max_new[0])]
         blocks = [self._image_blocks(q, g) for q, g in zip(qs, gs)]
         all_feats = [f for b in blocks for f in b[3]]
         res = self.output_resampler(torch.stack(all_feats)).contiguous() if all_feats else None
@@ -784,24 +712,35 @@ class ContinuousLVLM:
         return outs
 
 
+def _prepass(pipeline, agent: ContinuousLVLM, requests: Sequence[dict], batch: bool, tokenizer, img_ids_list, eos_token_id,
+             max_new_tokens) -> List[Tensor]:
+    """reference scripts/demo/gradio.py:85-109 for every request (`input_ids`, `ids_cmp_mask`, `ip_images`, `mllm_scale`):
+    character tokens -> MLLM -> blended `ip_image_embeds`.  batch: one decode loop for all (`agent.generate_batch`)."""
+    cfg = pipeline.unet.config
+    nv, n_ip = cfg.num_vision_tokens, cfg.max_num_ips
+    image_embeds = [pipeline.encode_ip_tokens(r["ip_images"])[:, nv:, :] for r in requests]      # each [1, n_ip*nv, dim]
+    kws = [dict(tokenizer=tokenizer, input_ids=r["input_ids"].unsqueeze(0), image_embeds=e,
+                ids_cmp_mask=r["ids_cmp_mask"].unsqueeze(0), max_new_tokens=max_new_tokens,
+                num_img_gen_tokens=agent.output_resampler.num_queries, img_ids_list=img_ids_list, eos_token_id=eos_token_id)
+           for r, e in zip(requests, image_embeds)]
+    outs = agent.generate_batch(kws) if batch else [agent.generate(**kw) for kw in kws]
+    blended = []
+    for r, e, out in zip(requests, image_embeds, outs):
+        if out["img_gen_feat"] is None:
+            raise RuntimeError("the MLLM produced no image block")
+        gen = out["img_gen_feat"].view(n_ip, nv, -1)
+        blended.append(ops.blend(gen, e.reshape(n_ip, nv, -1).to(gen.dtype), float(r["mllm_scale"])))
+    return blended
+
+
 @torch.no_grad()
 def mllm_prepass(pipeline, agent: ContinuousLVLM, input_ids: Tensor, ids_cmp_mask: Tensor, ip_images: list,
                  mllm_scale: float, tokenizer=None, img_ids_list: Optional[Sequence[int]] = None,
                  eos_token_id: Optional[int] = None, max_new_tokens: int = 500) -> Tensor:
     """reference scripts/demo/gradio.py:85-109: character tokens -> MLLM -> blended `ip_image_embeds`
     [max_num_ips, num_vision_tokens, dim] to pass to `pipeline(ip_images=[], ip_image_embeds=...)`."""
-    cfg = pipeline.unet.config
-    nv, n_ip = cfg.num_vision_tokens, cfg.max_num_ips
-    image_embeds = pipeline.encode_ip_tokens(ip_images)[:, nv:, :]                   # [1, n_ip*nv, dim]
-    out = agent.generate(tokenizer=tokenizer, input_ids=input_ids.unsqueeze(0), image_embeds=image_embeds,
-                         ids_cmp_mask=ids_cmp_mask.unsqueeze(0), max_new_tokens=max_new_tokens,
-                         num_img_gen_tokens=agent.output_resampler.num_queries, img_ids_list=img_ids_list,
-                         eos_token_id=eos_token_id)
-    if out["img_gen_feat"] is None:
-        raise RuntimeError("the MLLM produced no image block")
-    gen = out["img_gen_feat"].view(n_ip, nv, -1)
-    base = image_embeds.reshape(n_ip, nv, -1).to(gen.dtype)
-    return ops.blend(gen, base, float(mllm_scale))
+    request = dict(input_ids=input_ids, ids_cmp_mask=ids_cmp_mask, ip_images=ip_images, mllm_scale=mllm_scale)
+    return _prepass(pipeline, agent, [request], False, tokenizer, img_ids_list, eos_token_id, max_new_tokens)[0]
 
 
 @torch.no_grad()
@@ -810,18 +749,4 @@ def mllm_prepass_batch(pipeline, agent: ContinuousLVLM, requests: Sequence[dict]
                        max_new_tokens: int = 500) -> List[Tensor]:
     """`mllm_prepass` for up to `agent.llm.max_sequences` requests in one decode loop.  Each request is a dict with
     `input_ids`, `ids_cmp_mask`, `ip_images` and `mllm_scale`; returns one blended `ip_image_embeds` per request."""
-    cfg = pipeline.unet.config
-    nv, n_ip = cfg.num_vision_tokens, cfg.max_num_ips
-    image_embeds = [pipeline.encode_ip_tokens(r["ip_images"])[:, nv:, :] for r in requests]
-    outs = agent.generate_batch([
-        dict(tokenizer=tokenizer, input_ids=r["input_ids"].unsqueeze(0), image_embeds=e,
-             ids_cmp_mask=r["ids_cmp_mask"].unsqueeze(0), max_new_tokens=max_new_tokens,
-             num_img_gen_tokens=agent.output_resampler.num_queries, img_ids_list=img_ids_list, eos_token_id=eos_token_id)
-        for r, e in zip(requests, image_embeds)])
-    blended = []
-    for r, e, out in zip(requests, image_embeds, outs):
-        if out["img_gen_feat"] is None:
-            raise RuntimeError("the MLLM produced no image block")
-        gen = out["img_gen_feat"].view(n_ip, nv, -1)
-        blended.append(ops.blend(gen, e.reshape(n_ip, nv, -1).to(gen.dtype), float(r["mllm_scale"])))
-    return blended
+    return _prepass(pipeline, agent, requests, True, tokenizer, img_ids_list, eos_token_id, max_new_tokens)

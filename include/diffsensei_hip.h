@@ -497,7 +497,10 @@ int ds_llm_gemm16_w8(const void* x, int64_t ldx, const void* w, void* y, int64_t
 /* w16[n][k] = f16(f32(q[n][k]) * w_scale[n]) for q int8 [N,K], K % 16 == 0 (one fp32 multiply, one round to nearest even):
  * the prompt pass hands the result to ds_gemm_f16 */
 int ds_llm_dequant_w8(const void* q, const float* w_scale, void* w16, int64_t N, int K, void* stream);
-/* ds_llm_attn_f16 for one new row per slot: row s of qkv / out belongs to slot s, its caches start slot_stride
+/* The slot forms of ds_llm_attn_f16 / _rmsnorm_ / _embed_ / _select_: the same four kernels with every row a sequence of
+ * its own (state row s of an int32 [S][8] block) instead of the next position of one sequence.  The attention, the feature
+ * tap and the pick leave a slot with state[s][2] set (finished, or never started) alone.
+ * ds_llm_attn_f16 for one new row per slot: row s of qkv / out belongs to slot s, its caches start slot_stride
  * elements after slot s-1's, its position is state[s][0]. */
 int ds_llm_attn_slots_f16(const void* qkv, int64_t ldqkv, void* k_cache, void* v_cache, int64_t ldc, int64_t slot_stride,
                           const float* rope_cos, const float* rope_sin, void* out, int64_t ldo, const int32_t* state,

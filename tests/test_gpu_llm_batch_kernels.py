@@ -1,6 +1,7 @@
-"""GPU: the per-slot decode kernels of the batched MLLM pre-pass (csrc/llm.hip: llm_attn_slots_kernel,
-llm_select_slots_kernel, llm_rmsnorm_slots_kernel, llm_embed_slots_kernel) - one row, one KV cache, one state row, one
-feature buffer and one id list per sequence slot; a finished slot is left alone."""
+"""GPU: the slot form of the per-row decode kernels of the MLLM pre-pass (csrc/llm.hip: llm_attn_kernel, llm_select_kernel,
+llm_rmsnorm_kernel, llm_embed_kernel with state_stride = 8, through the `ops.llm_*_slots` functions) - one row, one KV cache,
+one state row, one feature buffer and one id list per sequence slot; a finished slot is left alone.  The comparisons with
+the one-sequence `ops.llm_*` functions test the stride handling of one kernel: both forms launch the same `__global__`."""
 import math
 
 import pytest
@@ -70,6 +71,38 @@ def test_attention_slots(hip_lib, D, heads, kv_heads):
         assert torch.equal(vc[s, :T].cpu(), h[:, (heads + kv_heads) * D:]), "value cache must be a bit copy"
         assert torch.equal(kc[s, :T - 1], kc0[s, :T - 1]), "rows before the new one were rewritten"
         assert not kc[s, T:].any() and not vc[s, T:].any(), "rows past the slot's length were written"
+
+
+@pytest.mark.parametrize("D,heads,kv_heads", [(128, 3, 3), (64, 4, 2)])
+def test_one_sequence_rows_match_one_row_slot_launches(hip_lib, D, heads, kv_heads):
+    """One launch of the one-sequence form with rows = 3 at pos0 = 7 (row m at position pos0 + m, the keys of the same
+    launch read un-rotated from qkv) against three one-row launches of the slot form on one slot whose cache length is
+    advanced by hand in between (every key read from the cache): outputs and cache rows are bit-equal."""
+    from diffsensei_amd import ops
+    g = torch.Generator().manual_seed(7 * D + heads)
+    T_max, pos0, rows = 40, 7, 3
+    W, scale = (heads + 2 * kv_heads) * D, 1.0 / math.sqrt(D)
+    inv = 1.0 / (10000.0 ** (torch.arange(0, D, 2).float() / D))
+    fr = torch.outer(torch.arange(T_max).float(), inv)
+    cos, sin = fr.cos().to(DEV).contiguous(), fr.sin().to(DEV).contiguous()
+    hist = _h((pos0 + rows, W), g).to(DEV)
+    kc = torch.zeros(1, T_max, kv_heads * D, dtype=torch.float16, device=DEV)
+    vc = torch.zeros_like(kc)
+    one = torch.zeros(8, dtype=torch.int32, device=DEV)
+    ops.llm_attention(hist[:pos0], kc[0], vc[0], cos, sin, one, heads, kv_heads, scale)        # the 7 rows in front
+    ops.llm_advance(one, pos0)
+    kc_seq, vc_seq, kc_slot, vc_slot = kc.clone(), vc.clone(), kc.clone(), vc.clone()
+    out_seq = ops.llm_attention(hist[pos0:], kc_seq[0], vc_seq[0], cos, sin, one, heads, kv_heads, scale)
+    assert int(one[0]) == pos0, "attention must not move the counters"
+    state = torch.tensor([[pos0, 1, 0, 0, 9, 2, 0, 0]], dtype=torch.int32, device=DEV)
+    out_slot = torch.zeros_like(out_seq)
+    for m in range(rows):
+        ops.llm_attention_slots(hist[pos0 + m:pos0 + m + 1], kc_slot, vc_slot, cos, sin, state, heads, kv_heads, scale,
+                                out=out_slot[m:m + 1])
+        state[0, 0] += 1
+    assert torch.equal(out_seq, out_slot), "row m of one launch differs from the same position decoded alone"
+    assert torch.equal(kc_seq, kc_slot) and torch.equal(vc_seq, vc_slot), "the appended cache rows differ"
+    assert kc_seq[0, pos0:pos0 + rows].any() and not kc_seq[0, pos0 + rows:].any() and torch.equal(kc_seq[0, :pos0], kc[0, :pos0])
 
 
 def test_select_slots_match_the_one_slot_kernel(hip_lib):

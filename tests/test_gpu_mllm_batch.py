@@ -85,8 +85,19 @@ def env(hip_lib):
 
     first = decode(agent.llm, [0, 1, 2, 3])                 # the shared reference run: all four, graph engine, slots 0..3
     info = dict(agent.llm.last_run_info)
+    engines = {}
+
+    def engine(S, weights="float16", graph=True):
+        """one engine per (slots, weight type, graph), shared by the tests below"""
+        key = (S, weights, graph)
+        if key not in engines:
+            engines[key] = LlamaDecodeEngine(cfg, sd, DEV, max_positions=96, max_new_tokens=40, use_graph=graph, poll_every=4,
+                                             max_sequences=S, weight_dtype=weights)
+            engines[key].set_image_token_chain(G.IMG_IDS)
+        return engines[key]
+
     return {"G": G, "mk": mk, "agent": agent, "prompts": prompts, "refs": refs, "decode": decode, "first": first,
-            "info": info, "gold": dict(np.load(GOLD))}
+            "info": info, "gold": dict(np.load(GOLD)), "embs": embs, "engine": engine}
 
 
 def test_batch_of_four_matches_the_oracle(env):
@@ -215,3 +226,45 @@ def test_mllm_prepass_batch_matches_per_request_prepass(env):
         ref = mllm_prepass(Pipe, agent, r["input_ids"], r["ids_cmp_mask"], r["ip_images"], r["mllm_scale"], **kw)
         assert got[k].shape == ref.shape == (1, G.N_IMG, G.RES_IN["kv_dim"])
         gate(f"blended ip_image_embeds, request {k}", _rel(got[k], ref), 3e-2)
+
+
+@pytest.mark.parametrize("graph", [True, False])
+@pytest.mark.parametrize("weights", ["float16", "int8"])
+@pytest.mark.parametrize("T0", [5, 16, 17, 40])            # chunk lists (16: a full chunk) | MFMA pass, 1 row and chunks past it
+def test_generate_does_not_depend_on_max_sequences(env, T0, weights, graph):
+    """`generate` is slot 0 at width 1 whatever the engine was built for: the same weights and prompt on an engine with one
+    slot and on one with four give the same ids and hidden states, bit for bit."""
+    G = env["G"]
+    ids = env["prompts"][1][0]
+    emb = env["embs"]([1])[0][:T0].contiguous()
+    outs = []
+    for S in (1, 4):
+        eng = env["engine"](S, weights, graph)
+        outs.append(eng.generate(emb, int(ids[T0 - 1]), EOS, G.MAX_NEW))
+        info = eng.last_run_info
+        assert info["prompt_tokens"] == T0 and info["new_tokens"] == len(outs[-1]["ids"]) > 1
+        assert info["ops_per_token"] == 5 * eng.cfg.num_hidden_layers + 4
+    assert torch.equal(outs[0]["ids"], outs[1]["ids"]), "the ids depend on max_sequences"
+    assert outs[0]["hidden"].shape[0] == len(outs[0]["ids"]) - 1 and torch.equal(outs[0]["hidden"], outs[1]["hidden"])
+
+
+def test_generate_and_generate_batch_share_an_engine(env):
+    """The two forms share every buffer.  `generate` after `generate_batch` (slots 1..3 hold finished sequences, the tap
+    rows those of another prompt) and `generate_batch` after `generate` give the bits of a fresh engine: all ids and all
+    hidden rows, for a prompt on the MFMA pass and one on the chunk lists."""
+    G, used, first = env["G"], env["agent"].llm, env["first"]
+    ids = env["prompts"][1][0]
+    emb = env["embs"]([1])[0]
+    fresh = type(used)(used.cfg, G.tiny_weights(), DEV, max_positions=96, max_new_tokens=40, use_graph=True, poll_every=4,
+                       max_sequences=4)
+    fresh.set_image_token_chain(G.IMG_IDS)
+    for T0 in (len(ids), 16):
+        e = emb[:T0].contiguous()
+        want = fresh.generate(e, int(ids[T0 - 1]), EOS, G.MAX_NEW)
+        assert "sequences" not in fresh.last_run_info and fresh.last_run_info["new_tokens"] == len(want["ids"]) > 1
+        env["decode"](used, [0, 1, 2, 3])
+        got = used.generate(e, int(ids[T0 - 1]), EOS, G.MAX_NEW)
+        assert torch.equal(got["ids"], want["ids"]) and torch.equal(got["hidden"], want["hidden"]), f"generate after a batch, T0={T0}"
+        again = env["decode"](fresh, [0, 1, 2, 3])          # ... and the reverse, on the engine that has only run `generate`
+        for k, (a, b) in enumerate(zip(again, first)):
+            assert torch.equal(a["ids"], b["ids"]) and torch.equal(a["hidden"], b["hidden"]), f"batch after generate, T0={T0}, {k}"

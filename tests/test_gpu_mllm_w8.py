@@ -138,7 +138,7 @@ def test_int8_generate_batch_matches_each_prompts_oracle(tiny):
             what = f"batch prompt {k}/rep={rep}"
             n_same = _check_ids(out["output_ids"].tolist(), ref["output_ids"].tolist(), ref["margins"].tolist(), what)
             assert n_same > G.N_IMG, "the forced image chain and </img> must always match"
-            gate(f"int8 hidden states, {what}", _rel(agent.llm.feat_b[k, :n_same - 1], ref["hidden"][:n_same - 1]), 3e-2)
+            gate(f"int8 hidden states, {what}", _rel(agent.llm.feats[k, :n_same - 1], ref["hidden"][:n_same - 1]), 3e-2)
             assert out["num_gen_imgs"] >= 1 and bool(out["ids_gen_mask"][:G.N_IMG].all())
             gate(f"int8 img_gen_feat, {what}", _rel(out["img_gen_feat"][0], ref["img_gen_feat"][0]), 3e-2)
     assert agent.llm.last_run_info["graph"]

@@ -1586,8 +1586,8 @@ def test_llama_engine_buffers_carry_nothing_into_a_run(hip_lib, weights, path):
             if weights == "int8":
                 eng._w(eng.wqkv, eng.sqkv, 0)                     # the prompt pass's dequant scratch: allocated on first use
                 assert eng._w16 is not None
-            bufs = [eng.h, eng.qkv, eng.att, eng.act, eng.hn, eng.logits, eng.feat, eng.out_ids, eng.hn_b, eng.logits_b, eng.feat_b,
-                    eng.out_ids_b] + eng.kcs + eng.vcs + ([eng._w16] if eng._w16 is not None else [])
+            bufs = [eng.h, eng.qkv, eng.att, eng.act, eng.hn, eng.logits, eng.feats, eng.out_ids] + eng.kcs + eng.vcs + (
+                [eng._w16] if eng._w16 is not None else [])
             for t in bufs:
                 _poison_(t)
         one = eng.generate(eng.embed_tokens(prompts[3]), int(prompts[3][-1]), 2, G.MAX_NEW)

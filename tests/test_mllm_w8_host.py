@@ -86,19 +86,19 @@ def test_int8_engine_op_lists_use_the_w8_ops_except_for_lm_head():
     cfg, eng = _engine("int8")
     L = cfg.num_hidden_layers
     code = lambda ops_: [int(o.code) for o in ops_]
-    tok = eng._ops(1, "token")
+    tok = eng._token_ops(1)
     assert code(tok).count(_lib.OP["LLM_GEMV_W8"]) == 4 * L
     assert code(tok).count(_lib.OP["LLM_GEMV"]) == 1, "lm_head stays fp16"
     w8 = [o for o in tok if int(o.code) == _lib.OP["LLM_GEMV_W8"]]
     assert w8[0].p[1] == eng.wqkv[0].data_ptr() and w8[0].p[5] == eng.sqkv[0].data_ptr()
     assert w8[2].p[1] == eng.wgu[0].data_ptr() and w8[2].p[5] == eng.sgu[0].data_ptr() and w8[2].p[4] == eng.g_post[0].data_ptr()
     assert w8[3].p[1] == eng.wdown[0].data_ptr() and w8[3].p[5] == eng.sdown[0].data_ptr() and not w8[3].p[4]
-    chunk = eng._ops(16, "chunk")
+    chunk = eng._chunk_ops(16, "chunk")
     assert code(chunk).count(_lib.OP["LLM_GEMV_W8"]) == 4 * L and _lib.OP["LLM_GEMV"] not in code(chunk)
     _, eng4 = _engine("int8", num_hidden_layers=1)
     eng4 = M.LlamaDecodeEngine(eng4.cfg, _sd(eng4.cfg), "cpu", max_positions=32, max_new_tokens=8, max_sequences=4,
                                weight_dtype="int8")
-    batch = eng4._ops_batch()
+    batch = eng4._token_ops(4)
     assert code(batch).count(_lib.OP["LLM_GEMM16_W8"]) == 4 and code(batch).count(_lib.OP["LLM_GEMM16"]) == 1
 
 
@@ -127,10 +127,10 @@ def test_fp16_engine_is_unchanged():
     cfg, eng = _engine()
     assert eng.weight_dtype == "float16"
     assert len(eng.tensors()) == 3 + 6 * cfg.num_hidden_layers and all(t.dtype == torch.float16 for t in eng.tensors())
-    codes = [int(o.code) for o in eng._ops(1, "token")]
+    codes = [int(o.code) for o in eng._token_ops(1)]
     assert _lib.OP["LLM_GEMV_W8"] not in codes and _lib.OP["LLM_GEMM16_W8"] not in codes
     assert codes.count(_lib.OP["LLM_GEMV"]) == 4 * cfg.num_hidden_layers + 1
-    first = eng._ops(1, "token")[1]
+    first = eng._token_ops(1)[1]
     assert first.p[1] == eng.wqkv[0].data_ptr() and first.p[4] == eng.g_in[0].data_ptr() and not first.p[5]
     _, explicit = _engine("float16")
     assert torch.equal(explicit.wqkv[0], eng.wqkv[0])
