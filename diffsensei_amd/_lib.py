@@ -26,7 +26,7 @@ OP = dict(GEMM=1, CONV3X3=2, GROUPNORM=3, LAYERNORM=4, SELF_ATTN=5, IP_ATTN=6, C
           TIMESTEP_EMBED=10, ADD_TIME_IDS=11, SAMPLER_STEP=12, PREP_INPUT=13, ADVANCE=14, NHWC2NCHW=15, NCHW2NHWC=16,
           PAD_ROWS=17, SMALL_ATTN=18, LLM_GEMV=19, LLM_ATTN=20, LLM_RMSNORM=21, LLM_EMBED=22, LLM_SELECT=23,
           LLM_ADVANCE=24, LN_FINALIZE=27, LLM_GEMM16=28, LLM_ATTN_SLOTS=29, LLM_RMSNORM_SLOTS=30,
-          LLM_EMBED_SLOTS=31, LLM_SELECT_SLOTS=32, REDRAW_START=33, LLM_GEMV_W8=34, LLM_GEMM16_W8=35, LORA_MERGE=36)
+          LLM_EMBED_SLOTS=31, LLM_SELECT_SLOTS=32, REDRAW_START=33, LLM_GEMV_W8=34, LLM_GEMM16_W8=35, LORA_MERGE=36, SLOT_START=37)
 
 # name -> (restype, argtypes).  Every symbol declared in include/diffsensei_hip.h appears here;
 # tests/test_capi_symbols.py checks the two lists against each other.
@@ -94,6 +94,11 @@ SIGNATURES = {
     "ds_cfg_sampler_step_redraw_f16": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "ds_redraw_buffer_bytes": (i64, [i32, i32]),
     "ds_redraw_start_f16": (i32, [vp, vp, i32, i32, vp]),
+    "ds_panel_schedule_bytes": (i64, [i32]),
+    "ds_panel_slot_load": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, i32, f32, vp]),
+    "ds_cfg_sampler_step_slots_f16": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "ds_timestep_embed_slots_f16": (i32, [vp, vp, vp, i32, i32, i32, f32, i32, vp]),
+    "ds_panel_slot_start_f16": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "ds_philox_u32": (i32, [vp, i32, i32, vp, i32, i32, vp]),
     "ds_philox_normal_f32": (i32, [vp, i32, i32, vp, i32, i32, vp]),
     "ds_prepare_model_input_f16": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),

@@ -25,7 +25,7 @@ void ds_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* ds_last_error(void) { return g_err; }
-int ds_version(void) { return 104; }
+int ds_version(void) { return 105; }
 
 int ds_device_info(int* cu_count, int* lds_bytes, char* arch_name, int arch_name_len) {
     int dev = 0;
@@ -681,6 +681,49 @@ int ds_redraw_start_f16(const void* redraw, void* latents, int ns, int HW, void*
     return ds_launch_redraw_start(redraw, HM(latents), ns, HW, S(stream));
 }
 
+// ---- panel schedules (continuous batching)
+int64_t ds_panel_schedule_bytes(int ns) { return ns > 0 ? (int64_t)ds_panel_bytes(ns) : 0; }
+
+int ds_panel_slot_load(void* panel, int ns, int slot, int start, int steps, const float* coef_rows, const float* solver_rows,
+                       const float* renoise_rows, int start_mode, float init_noise_sigma, void* stream) {
+    DS_REQUIRE(panel != nullptr, "panel_slot_load: null panel-schedule buffer");
+    DS_REQUIRE(((uintptr_t)panel & 15) == 0, "panel_slot_load: the panel-schedule buffer must be 16-byte aligned");
+    DS_REQUIRE(ns > 0 && slot >= 0 && slot < ns, "panel_slot_load: slot %d outside the %d panels", slot, ns);
+    DS_REQUIRE(steps >= 0 && steps <= DS_PANEL_MAX_ROWS, "panel_slot_load: steps[%d] = %d exceeds the row capacity %d", slot, steps,
+               DS_PANEL_MAX_ROWS);
+    DS_REQUIRE(start >= 0, "panel_slot_load: start %d is negative", start);
+    DS_REQUIRE((((uintptr_t)coef_rows | (uintptr_t)solver_rows | (uintptr_t)renoise_rows) & 3) == 0,
+               "panel_slot_load: the rows are fp32 arrays, 4-byte aligned");
+    DS_REQUIRE(steps == 0 || coef_rows, "panel_slot_load: %d steps without coefficient rows", steps);
+    DS_REQUIRE(start_mode >= DS_PANEL_START_RENOISE && start_mode <= DS_PANEL_START_KEEP, "panel_slot_load: start mode %d", start_mode);
+    DS_REQUIRE(start_mode != DS_PANEL_START_RENOISE || renoise_rows || steps == 0,
+               "panel_slot_load: start mode 0 (renoise row 0) without renoise rows");
+    return ds_launch_panel_slot_load(panel, ns, slot, start, steps, coef_rows, solver_rows, renoise_rows, start_mode,
+                                     init_noise_sigma, S(stream));
+}
+
+int ds_cfg_sampler_step_slots_f16(const void* eps, void* latents, void* model_in, const void* panel, const float* guidance,
+                                  void* prev_x0, const int64_t* seeds, const void* redraw, const int32_t* step_ctr, int ns,
+                                  int HW, int kind, int do_cfg, void* stream) {
+    SamplerStepParams p;
+    p.eps = H(eps); p.latents = HM(latents); p.model_in = HM(model_in); p.coef = reinterpret_cast<const float*>(panel);
+    p.guidance = guidance; p.prev_x0 = HM(prev_x0);
+    p.seeds = reinterpret_cast<const long long*>(seeds);
+    p.redraw = redraw; p.redraw_on = redraw != nullptr;
+    p.ns = ns; p.HW = HW; p.kind = kind; p.do_cfg = do_cfg;
+    return ds_launch_sampler_step_panels(p, step_ctr, S(stream));
+}
+
+int ds_timestep_embed_slots_f16(const void* panel, const int32_t* step_ctr, void* out, int B, int dim, int flip,
+                                float freq_shift, int ns, void* stream) {
+    return ds_launch_timestep_embed_panels(panel, step_ctr, HM(out), B, dim, flip, freq_shift, ns, S(stream));
+}
+
+int ds_panel_slot_start_f16(const void* panel, const void* redraw, void* latents, void* model_in, int ns, int HW, int do_cfg,
+                            int slot0, int nslots, void* stream) {
+    return ds_launch_panel_slot_start(panel, redraw, HM(latents), HM(model_in), ns, HW, do_cfg, slot0, nslots, S(stream));
+}
+
 int ds_philox_u32(const int64_t* seeds, int step, int stream_id, uint32_t* out, int ns, int HW, void* stream) {
     return ds_launch_philox_u32(reinterpret_cast<const long long*>(seeds), step, stream_id, out, ns, HW, S(stream));
 }
@@ -794,6 +837,9 @@ static int run_op(const ds_op& o, hipStream_t st) {
         case DS_OP_SKINNY:
             return ds_launch_skinny_linear(H(p[0]), H(p[1]), H(p[2]), H(p[3]), HM(p[4]), i[0], i[1], i[2], i[3], i[4], st);
         case DS_OP_TIMESTEP_EMBED:
+            if (i[3] > 0)   // panel schedules: p[0] is the panel-schedule buffer, i[3] = ns
+                return ds_launch_timestep_embed_panels(p[0], reinterpret_cast<const int*>(p[1]), HM(p[2]), i[0], i[1], i[2],
+                                                       o.f[0], i[3], st);
             return ds_launch_timestep_embed(reinterpret_cast<const float*>(p[0]), reinterpret_cast<const int*>(p[1]),
                                             HM(p[2]), i[0], i[1], i[2], o.f[0], st);
         case DS_OP_ADD_TIME_IDS:
@@ -806,10 +852,16 @@ static int run_op(const ds_op& o, hipStream_t st) {
             s.guidance = reinterpret_cast<const float*>(p[8]);
             s.redraw = p[9]; s.redraw_on = i[4];
             s.ns = i[0]; s.HW = i[1]; s.kind = i[2]; s.do_cfg = i[3];
+            if (i[5]) {     // panel schedules: p[3] is the panel-schedule buffer, the solver rows live in it
+                s.solver = nullptr;
+                return ds_launch_sampler_step_panels(s, reinterpret_cast<const int*>(p[4]), st);
+            }
             return ds_launch_sampler_step(s, reinterpret_cast<const int*>(p[4]), st);
         }
         case DS_OP_REDRAW_START:
             return ds_launch_redraw_start(p[0], HM(p[1]), i[0], i[1], st);
+        case DS_OP_SLOT_START:
+            return ds_launch_panel_slot_start(p[0], p[1], HM(p[2]), HM(p[3]), i[0], i[1], i[2], i[3], i[4], st);
         case DS_OP_PREP_INPUT:
             return ds_launch_prepare_model_input(H(p[0]), HM(p[1]), reinterpret_cast<const float*>(p[2]),
                                                  reinterpret_cast<const int*>(p[3]), i[0], i[1], 4, i[2], st);
@@ -909,7 +961,9 @@ int ds_op_describe(const ds_op* op, char* name, int name_len, double* flops, dou
         case DS_OP_CONV_IN: nm = "conv_in_kernel"; fl = 2.0 * i[0] * (double)i[1] * i[2] * 9 * i[3] * i[4]; break;
         case DS_OP_CONV_OUT: nm = "conv_out_kernel"; fl = 2.0 * i[0] * (double)i[1] * i[2] * 9 * i[3] * i[4]; break;
         case DS_OP_SKINNY: nm = "skinny_linear_kernel"; fl = 2.0 * i[0] * (double)i[1] * i[2]; by = 2.0 * i[1] * (double)i[2]; break;
-        case DS_OP_SAMPLER_STEP: nm = "sampler_step_kernel"; break;
+        case DS_OP_TIMESTEP_EMBED: nm = i[3] > 0 ? "timestep_embed_panels_kernel" : "other"; break;   // (the one-table launch keeps the name it had)
+        case DS_OP_SAMPLER_STEP: nm = "sampler_step_kernel"; break;    // every instantiation, panel schedules (i[5]) included
+        case DS_OP_SLOT_START: nm = "panel_slot_start_kernel"; by = 2.0 * 3.0 * i[4] * 4.0 * i[1]; break;
         case DS_OP_REDRAW_START: nm = "redraw_start_kernel"; by = 2.0 * 3.0 * i[0] * 4.0 * i[1]; break;
         case DS_OP_LLM_GEMV:
             nm = "llm_gemv_kernel";

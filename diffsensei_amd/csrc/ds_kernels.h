@@ -226,6 +226,40 @@ __host__ __device__ inline RedrawView ds_redraw_view(const void* buf, int ns, in
     return RedrawView{h, h + (long)ns * 4 * HW, h + (long)ns * 8 * HW, f, f + 4};
 }
 int ds_launch_redraw_start(const void* redraw, half_t* latents, int ns, int HW, hipStream_t stream);
+// Panel schedules (continuous batching): ONE device buffer (16-byte aligned) whose offsets follow from ns alone
+// (include/diffsensei_hip.h, "Panel schedules"); R = DS_PANEL_MAX_ROWS:
+//   start int32 [ns] | steps int32 [ns] | pad to 16 bytes | mode fp32 [ns][4] = {start mode, init_noise_sigma, 0, 0} |
+//   coef fp32 [ns][R][8] | solver fp32 [ns][R][8] | renoise fp32 [ns][R + 1][2]
+// With s = *ctr panel n is at its row j = s - start[n] and active iff 0 <= j < steps[n].
+#ifndef DS_PANEL_MAX_ROWS
+#define DS_PANEL_MAX_ROWS 1024   // include/diffsensei_hip.h states the same value
+#endif
+enum { DS_PANEL_START_RENOISE = 0, DS_PANEL_START_FULL = 1, DS_PANEL_START_KEEP = 2 };
+struct PanelView {
+    const int *start, *steps;
+    const float *mode, *coef, *solver, *renoise;
+};
+__host__ __device__ inline long ds_panel_f32_offset(int ns) {   // bytes
+    return ((long)ns * 8 + 15) & ~15L;
+}
+__host__ __device__ inline long ds_panel_bytes(int ns) {
+    return ds_panel_f32_offset(ns) + (long)sizeof(float) * ns * (4 + 16L * DS_PANEL_MAX_ROWS + 2L * (DS_PANEL_MAX_ROWS + 1));
+}
+__host__ __device__ inline PanelView ds_panel_view(const void* buf, int ns) {
+    const int* s = static_cast<const int*>(buf);
+    const float* f = reinterpret_cast<const float*>(static_cast<const char*>(buf) + ds_panel_f32_offset(ns));
+    const float* coef = f + (long)ns * 4;
+    const float* solver = coef + (long)ns * DS_PANEL_MAX_ROWS * 8;
+    return PanelView{s, s + ns, f, coef, solver, solver + (long)ns * DS_PANEL_MAX_ROWS * 8};
+}
+// `panel` = true: p.coef is the panel-schedule buffer (p.solver unused, p.guidance required under CFG), see sampler_step_kernel
+int ds_launch_sampler_step_panels(const SamplerStepParams& p, const int* ctr, hipStream_t stream);
+int ds_launch_panel_slot_load(void* panel, int ns, int slot, int start, int steps, const float* coef, const float* solver,
+                              const float* renoise, int start_mode, float init_noise_sigma, hipStream_t stream);
+int ds_launch_timestep_embed_panels(const void* panel, const int* ctr, half_t* out, int B, int dim, int flip,
+                                    float freq_shift, int ns, hipStream_t stream);
+int ds_launch_panel_slot_start(const void* panel, const void* redraw, half_t* latents, half_t* model_in, int ns, int HW,
+                               int do_cfg, int slot0, int nslots, hipStream_t stream);
 // Philox4x32-10 keyed per panel, counter (pixel, 0, step, stream_id): raw words [ns,HW,4] / Box-Muller normals [ns,4,HW]
 int ds_launch_philox_u32(const long long* seeds, int step, int stream_id, unsigned* out, int ns, int HW,
                          hipStream_t stream);

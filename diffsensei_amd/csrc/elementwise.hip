@@ -263,23 +263,42 @@ __global__ __launch_bounds__(256) void philox_normal_kernel(const long long* __r
 // bits the RD == false kernel stores, and x0k / nz are not read for it.  m == 0 stores half(known), whatever xn is.
 // prev_x0 (kind 2) is the unblended x0 of this step; model_in is formed from the blended value.  Like GV, instantiations
 // of their own: the RD == false kernels are the ones they were (profiles/redraw_resource_usage_*.txt).
-template <bool GV, bool RD>
+// PS: panel schedules (include/diffsensei_hip.h, "Panel schedules").  p.coef is the panel-schedule buffer: panel n reads row
+// j = *ctr - start[n] of ITS OWN coefficient, solver and renoise rows and is active iff 0 <= j < steps[n]; a thread of an
+// inactive panel (empty slot, not yet started, finished) returns before its first store, so latents, prev_x0 and model_in
+// of that panel keep their bits.  Guidance is always the per-panel vector, and Euler Ancestral draws its Philox noise for
+// step j: a panel's noise depends on neither its slot nor the moment it was admitted.  The arithmetic below is shared with
+// the PS == false kernels - per panel the same instructions on the same operands - which stay the kernels they were
+// (profiles/panel_schedule_resource_usage.txt).
+template <bool GV, bool RD, bool PS = false>
 __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p, const int* ctr) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     const long total = (long)p.ns * p.HW;
     if (i >= total) return;
     const int n = (int)(i / p.HW), pix = (int)(i - (long)n * p.HW);
-    const float* cf = coef_row(p.coef, ctr);
+    int j = 0;                      // PS: the row this thread's panel is at
+    const float *pcf = nullptr, *psv = nullptr, *prr = nullptr;
+    if constexpr (PS) {
+        const PanelView pv = ds_panel_view(p.coef, p.ns);
+        const int cap = pv.steps[n] < DS_PANEL_MAX_ROWS ? pv.steps[n] : DS_PANEL_MAX_ROWS;
+        j = *ctr - pv.start[n];
+        if (j < 0 || j >= cap) return;
+        const long row = (long)n * DS_PANEL_MAX_ROWS + j;
+        pcf = pv.coef + row * 8;
+        psv = pv.solver + row * 8;
+        prr = pv.renoise + 2 * ((long)n * (DS_PANEL_MAX_ROWS + 1) + j + 1);
+    }
+    const float* cf = PS ? pcf : coef_row(p.coef, ctr);
     float m = 1.0f, ka = 0.f, kb = 0.f;
     const half_t *x0k = nullptr, *nz = nullptr;
     if constexpr (RD) {
         const RedrawView rv = ds_redraw_view(p.redraw, p.ns, p.HW);
-        const float* rr = rv.rows + 2 * ((ctr ? *ctr : 0) + 1);   // the state this step produces
+        const float* rr = PS ? prr : rv.rows + 2 * ((ctr ? *ctr : 0) + 1);   // the state this step produces
         ka = rr[0]; kb = rr[1];
         x0k = rv.x0k; nz = rv.noise;
         m = (float)rv.mask[(long)n * p.HW + pix];
     }
-    const float* sv = p.kind == 2 ? coef_row(p.solver, ctr) : nullptr;
+    const float* sv = p.kind == 2 ? (PS ? psv : coef_row(p.solver, ctr)) : nullptr;
     const h4 eu = *reinterpret_cast<const h4*>(p.eps + ((long)n * p.HW + pix) * 4);
     h4 e = eu;
     if (p.do_cfg) {
@@ -293,7 +312,7 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p, 
         }
     }
     float z[4] = {0.f, 0.f, 0.f, 0.f};
-    if (p.kind == 3) panel_normals(p.seeds[n], pix, ctr ? *ctr : 0, 0, z);   // stream 0 = sampler-step noise
+    if (p.kind == 3) panel_normals(p.seeds[n], pix, PS ? j : (ctr ? *ctr : 0), 0, z);   // stream 0 = sampler-step noise
     h4 xin;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -364,6 +383,86 @@ __global__ __launch_bounds__(256) void prepare_model_input_kernel(const half_t* 
     for (int c = 0; c < 4; ++c) xin[c] = (half_t)((float)latents[((long)n * 4 + c) * HW + pix] / div);
     *reinterpret_cast<h4*>(model_in + ((long)n * HW + pix) * 4) = xin;
     if (do_cfg) *reinterpret_cast<h4*>(model_in + ((long)(ns + n) * HW + pix) * 4) = xin;
+}
+
+// Panel schedules: the time embedding with one timestep per batch row.  Row b belongs to panel b % ns (both CFG halves of
+// a panel are rows n and ns + n) and reads column 0 of that panel's row clamp(j, 0, steps - 1); an empty slot reads 0, so
+// every row is finite whatever the rows of an unused slot hold.
+__global__ void timestep_embed_panels_kernel(const void* panel, const int* ctr, half_t* out, int B, int dim, int flip,
+                                             float freq_shift, int ns) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * dim) return;
+    const int n = (i / dim) % ns;
+    const PanelView pv = ds_panel_view(panel, ns);
+    const int cap = pv.steps[n] < DS_PANEL_MAX_ROWS ? pv.steps[n] : DS_PANEL_MAX_ROWS;
+    float t = 0.f;
+    if (cap > 0) {
+        int j = *ctr - pv.start[n];
+        j = j < 0 ? 0 : (j >= cap ? cap - 1 : j);
+        t = pv.coef[((long)n * DS_PANEL_MAX_ROWS + j) * 8];
+    }
+    out[i] = (half_t)sinusoid(t, i % dim, dim, flip, freq_shift);
+}
+
+// Panel schedules: the state slots [slot0, slot0 + nslots) start from, redraw_start_kernel + prepare_model_input_kernel for
+// those panels alone (one thread per panel pixel, 4 channels).  Start mode (mode[n][0]) 0: latents = half(ka0 * x0k + kb0 *
+// nz) with {ka0, kb0} = the panel's own renoise row 0; 1: half(nz * init_noise_sigma), mode[n][1]; 2 - or no redraw buffer -:
+// the latents are the host's (a plain panel).  Then model_in = latents / c_in_div of the panel's row 0, both CFG halves.
+// An empty slot (steps = 0) has no row 0 to divide by: nothing of it is written.
+__global__ __launch_bounds__(256) void panel_slot_start_kernel(const void* panel, const void* redraw, half_t* latents,
+                                                               half_t* model_in, int ns, int HW, int do_cfg, int slot0,
+                                                               int nslots) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)nslots * HW) return;
+    const int n = slot0 + (int)(i / HW), pix = (int)(i % HW);
+    const PanelView pv = ds_panel_view(panel, ns);
+    if (pv.steps[n] <= 0) return;
+    const float* md = pv.mode + (long)n * 4;
+    const int mode = redraw ? (int)md[0] : DS_PANEL_START_KEEP;
+    const float div = pv.coef[(long)n * DS_PANEL_MAX_ROWS * 8 + 1];
+    h4 xin;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const long o = ((long)n * 4 + c) * HW + pix;
+        half_t x;
+        if (mode == DS_PANEL_START_KEEP) {
+            x = latents[o];
+        } else {
+            const RedrawView rv = ds_redraw_view(redraw, ns, HW);
+            const float* rr = pv.renoise + 2 * (long)n * (DS_PANEL_MAX_ROWS + 1);
+            const float z = (float)rv.noise[o];
+            if (mode == DS_PANEL_START_FULL) x = (half_t)(z * md[1]);
+            else x = (half_t)(rr[0] * (float)rv.x0k[o] + rr[1] * z);
+            latents[o] = x;
+        }
+        xin[c] = (half_t)((float)x / div);
+    }
+    *reinterpret_cast<h4*>(model_in + ((long)n * HW + pix) * 4) = xin;
+    if (do_cfg) *reinterpret_cast<h4*>(model_in + ((long)(ns + n) * HW + pix) * 4) = xin;
+}
+
+// Panel schedules: one slot's part of the buffer out of DEVICE rows (coef / solver [steps][8], renoise [steps + 1][2]; the
+// last two may be null: that region keeps what it holds) and the slot's clock and start mode.  Stream-ordered like every
+// launch, so the replay that follows sees the whole slot; no other slot is touched.
+__global__ __launch_bounds__(256) void panel_slot_load_kernel(void* panel, int ns, int slot, int start, int steps,
+                                                              const float* __restrict__ coef, const float* __restrict__ solver,
+                                                              const float* __restrict__ renoise, float mode, float sigma) {
+    const PanelView pv = ds_panel_view(panel, ns);
+    float* dc = const_cast<float*>(pv.coef) + (long)slot * DS_PANEL_MAX_ROWS * 8;
+    float* ds = const_cast<float*>(pv.solver) + (long)slot * DS_PANEL_MAX_ROWS * 8;
+    float* dr = const_cast<float*>(pv.renoise) + (long)slot * (DS_PANEL_MAX_ROWS + 1) * 2;
+    for (int k = blockIdx.x * 256 + threadIdx.x; k < steps * 8; k += gridDim.x * 256) {
+        dc[k] = coef[k];
+        if (solver) ds[k] = solver[k];
+    }
+    if (renoise && steps > 0)
+        for (int k = blockIdx.x * 256 + threadIdx.x; k < (steps + 1) * 2; k += gridDim.x * 256) dr[k] = renoise[k];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const_cast<int*>(pv.start)[slot] = start;
+        const_cast<int*>(pv.steps)[slot] = steps;
+        float* md = const_cast<float*>(pv.mode) + (long)slot * 4;
+        md[0] = mode; md[1] = sigma; md[2] = 0.f; md[3] = 0.f;
+    }
 }
 
 __global__ void advance_counter_kernel(int* ctr) {
@@ -536,6 +635,62 @@ int ds_launch_sampler_step(const SamplerStepParams& p, const int* ctr, hipStream
     } else {
         hipLaunchKernelGGL((sampler_step_kernel<false, false>), grid, dim3(256), 0, stream, p, ctr);
     }
+    DS_LAUNCH_CHECK();
+    return 0;
+}
+
+int ds_launch_sampler_step_panels(const SamplerStepParams& p, const int* ctr, hipStream_t stream) {
+    DS_REQUIRE(p.C == 4, "sampler_step (panel schedules): latent channels must be 4");
+    DS_REQUIRE(p.ns > 0 && p.HW > 0 && p.eps && p.latents && p.model_in, "sampler_step (panel schedules): bad arguments");
+    DS_REQUIRE(p.coef && ctr, "sampler_step (panel schedules): the panel-schedule buffer and the step counter are needed");
+    DS_REQUIRE(((uintptr_t)p.coef & 15) == 0, "sampler_step (panel schedules): the panel-schedule buffer must be 16-byte aligned");
+    DS_REQUIRE(p.kind >= 0 && p.kind <= 3,
+               "sampler_step: kind must be 0 (Euler), 1 (DDIM), 2 (DPM-Solver++) or 3 (Euler Ancestral)");
+    DS_REQUIRE(!p.do_cfg || p.guidance, "sampler_step (panel schedules): guidance is the per-panel vector, it is missing");
+    DS_REQUIRE(p.kind != 2 || p.prev_x0, "sampler_step (panel schedules): kind 2 needs prev_x0");
+    DS_REQUIRE(p.kind != 3 || p.seeds, "sampler_step: kind 3 needs the per-panel seeds");
+    DS_REQUIRE(!p.redraw_on || p.redraw, "sampler_step: the redraw flag is set without the redraw buffer");
+    DS_REQUIRE(!p.redraw_on || ((uintptr_t)p.redraw & 15) == 0, "sampler_step: the redraw buffer must be 16-byte aligned");
+    const long total = (long)p.ns * p.HW;
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (p.redraw_on) hipLaunchKernelGGL((sampler_step_kernel<true, true, true>), grid, dim3(256), 0, stream, p, ctr);
+    else hipLaunchKernelGGL((sampler_step_kernel<true, false, true>), grid, dim3(256), 0, stream, p, ctr);
+    DS_LAUNCH_CHECK();
+    return 0;
+}
+
+int ds_launch_timestep_embed_panels(const void* panel, const int* ctr, half_t* out, int B, int dim, int flip,
+                                    float freq_shift, int ns, hipStream_t stream) {
+    DS_REQUIRE(dim > 0 && dim % 2 == 0, "timestep_embed (panel schedules): dim must be even");
+    DS_REQUIRE(panel && ctr && out, "timestep_embed (panel schedules): the panel-schedule buffer, the counter and out are needed");
+    DS_REQUIRE(((uintptr_t)panel & 15) == 0, "timestep_embed (panel schedules): the panel-schedule buffer must be 16-byte aligned");
+    DS_REQUIRE(ns > 0 && B > 0 && B % ns == 0, "timestep_embed (panel schedules): B = %d rows are not whole groups of ns = %d panels", B, ns);
+    hipLaunchKernelGGL(timestep_embed_panels_kernel, dim3((B * dim + 255) / 256), dim3(256), 0, stream, panel, ctr, out, B,
+                       dim, flip, freq_shift, ns);
+    DS_LAUNCH_CHECK();
+    return 0;
+}
+
+int ds_launch_panel_slot_start(const void* panel, const void* redraw, half_t* latents, half_t* model_in, int ns, int HW,
+                               int do_cfg, int slot0, int nslots, hipStream_t stream) {
+    DS_REQUIRE(panel && latents && model_in && ns > 0 && HW > 0, "panel_slot_start: bad arguments");
+    DS_REQUIRE(((uintptr_t)panel & 15) == 0, "panel_slot_start: the panel-schedule buffer must be 16-byte aligned");
+    DS_REQUIRE(((uintptr_t)redraw & 15) == 0, "panel_slot_start: the redraw buffer must be 16-byte aligned");
+    DS_REQUIRE(slot0 >= 0 && nslots > 0 && slot0 + nslots <= ns, "panel_slot_start: slots [%d, %d) outside the %d panels", slot0,
+               slot0 + nslots, ns);
+    const long total = (long)nslots * HW;
+    hipLaunchKernelGGL(panel_slot_start_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, panel, redraw,
+                       latents, model_in, ns, HW, do_cfg, slot0, nslots);
+    DS_LAUNCH_CHECK();
+    return 0;
+}
+
+int ds_launch_panel_slot_load(void* panel, int ns, int slot, int start, int steps, const float* coef, const float* solver,
+                              const float* renoise, int start_mode, float init_noise_sigma, hipStream_t stream) {
+    // the entry point (capi.hip) has checked the buffer, the slot, the mode and steps against DS_PANEL_MAX_ROWS
+    const int blocks = steps * 8 > 256 ? (steps * 8 + 255) / 256 : 1;
+    hipLaunchKernelGGL(panel_slot_load_kernel, dim3(blocks), dim3(256), 0, stream, panel, ns, slot, start, steps, coef, solver,
+                       renoise, (float)start_mode, init_noise_sigma);
     DS_LAUNCH_CHECK();
     return 0;
 }

@@ -488,6 +488,8 @@ class UNetEngine:
         self.noise_seeds = None                                 # Euler Ancestral: one Philox seed per panel
         self.redraw = None                                      # region redraw: x0k | noise | mask | renoise rows, one buffer
         self._redraw_ns = None
+        self.panel = None                                       # panel schedules: start | steps | mode | per-panel rows, one buffer
+        self._panel_ns = None
         # ---- request-level derived tensors
         self.enc_txt = E(B, LP, xdim)
         self.enc_ip = E(B, LP, xdim)
@@ -871,14 +873,19 @@ class UNetEngine:
         return ops
 
     # -- sampling: forward + CFG + scheduler step + counter advance as ONE replayable plan
-    def build_sampler(self, ns: int, kind: int, do_cfg: bool = True, redraw: bool = False):
+    def build_sampler(self, ns: int, kind: int, do_cfg: bool = True, redraw: bool = False, panel_schedules: bool = False):
         """reference src/pipelines/pipeline_diffsensei.py:310-337, one loop iteration per `step_plan.run()`.
         redraw: the region-redraw sampler - the prep plan first writes the start state out of the redraw buffer
         (`load_redraw`) and every step blends the kept region back in; part of the key, so a plain sampler built
-        afterwards has plans that never touch the buffer."""
+        afterwards has plans that never touch the buffer.
+        panel_schedules: continuous batching - every panel slot runs its own schedule out of the panel-schedule buffer
+        (include/diffsensei_hip.h, "Panel schedules"; `load_slots`, `set_slot_request`, `start_slots`): the step plan's
+        time embedding and sampler step are the panel-mode ops, the slots start empty, and the prep plan is a slot start
+        over all of them (a run starts its slots itself, as it admits requests).  Part of the key, like `redraw`; the
+        engine is in per-panel mode (`enable_per_panel`) from the start."""
         if self.B != (2 * ns if do_cfg else ns):
             raise ValueError(f"engine batch {self.B} does not match num_samples {ns} (cfg={do_cfg})")
-        key = (ns, kind, do_cfg, bool(redraw))
+        key = (ns, kind, do_cfg, bool(redraw), bool(panel_schedules))
         if self._sampler_key == key:
             return
         HW = self.H * self.W
@@ -889,8 +896,22 @@ class UNetEngine:
                 self.redraw = ops.redraw_buffer(ns, self.H, self.W, self.dev)
                 self.keep.append(self.redraw)
                 self._redraw_ns = ns
-            prep.append(make_op("REDRAW_START", i=(ns, HW), p=(self.redraw, self.latents)))
-        prep.append(make_op("PREP_INPUT", i=(ns, HW, int(do_cfg)), p=(self.latents, self.x_in, self.table, self.ctr)))
+            if not panel_schedules:
+                prep.append(make_op("REDRAW_START", i=(ns, HW), p=(self.redraw, self.latents)))
+        if panel_schedules:
+            if self.panel is None or self._panel_ns != ns:        # once per (ns, shape): the row capacity of the table
+                assert ops.PANEL_MAX_ROWS == self.table.shape[0]
+                self.panel = ops.panel_schedule_buffer(ns, self.dev)
+                self.keep.append(self.panel)
+                self._panel_ns = ns
+            self.panel.zero_()                                    # every slot empty
+            # an empty slot's rows still go through the UNet: whatever they compute stays in their rows, but it is finite
+            for t in (self.latents, self.x_in, self.enc, self.text_embeds, self.time_ids, self.bbox):
+                t.zero_()
+            prep.append(make_op("SLOT_START", i=(ns, HW, int(do_cfg), 0, ns),
+                                p=(self.panel, self.redraw if redraw else None, self.latents, self.x_in)))
+        else:
+            prep.append(make_op("PREP_INPUT", i=(ns, HW, int(do_cfg)), p=(self.latents, self.x_in, self.table, self.ctr)))
         self.prep_plan = Plan(prep, self.keep)
         # the buffers of this kind, allocated once per shape and kept when another kind is built in between
         if kind == KIND_DPM:
@@ -907,13 +928,37 @@ class UNetEngine:
             self.guidance = self._alloc((ns,), torch.float32)
             self.guidance.fill_(1.0)
         self._sampler_key, self.sampler_kind = key, kind
+        if panel_schedules:
+            if self.per_panel:
+                self._build_step_plan()
+            else:
+                self.enable_per_panel()      # makes the step plan as well
+            if redraw:                       # a plain panel of a redraw run repaints everything: mask 1 until a request says otherwise
+                ops.redraw_views(self.redraw, ns, self.H, self.W)[2].fill_(1.0)
+            self.ctr.zero_()
+            return
         self._build_step_plan()
 
     def _build_step_plan(self):
         """The step plan of the built sampler over the buffers `build_sampler` allocated (nothing is allocated here)."""
-        ns, kind, do_cfg, redraw = self._sampler_key
+        ns, kind, do_cfg, redraw, panels = self._sampler_key
         prev_x0, solver = (self.prev_x0, self.solver) if kind == KIND_DPM else (None, None)
         noise_seeds = self.noise_seeds if kind == KIND_EULER_ANCESTRAL else None
+        if panels:
+            # the forward with one timestep per row (row b = panel b % ns) and the step on the panels' own rows; the solver
+            # rows live in the panel-schedule buffer, which travels in the table's slot
+            assert self.forward_ops[0].code == OP["TIMESTEP_EMBED"]
+            cfg = self.cfg
+            temb = make_op("TIMESTEP_EMBED", i=(self.B, cfg.block_out_channels[0], int(cfg.flip_sin_to_cos), ns),
+                           f=(cfg.freq_shift,), p=(self.panel, self.ctr, self.t_sin))
+            step_ops = [temb] + list(self.forward_ops[1:]) + [
+                make_op("SAMPLER_STEP", i=(ns, self.H * self.W, kind, int(do_cfg), int(redraw), 1),
+                        p=(self.eps, self.latents, self.x_in, self.panel, self.ctr, prev_x0, None, noise_seeds,
+                           self.guidance, self.redraw if redraw else None)),
+                make_op("ADVANCE", p=(self.ctr,)),
+            ]
+            self.step_plan = Plan(step_ops, self.keep)
+            return
         step_ops = list(self.forward_ops) + [
             make_op("SAMPLER_STEP", i=(ns, self.H * self.W, kind, int(do_cfg), int(redraw)),
                     p=(self.eps, self.latents, self.x_in, self.table, self.ctr, prev_x0, solver, noise_seeds,
@@ -956,6 +1001,8 @@ class UNetEngine:
         switch the engine to per-panel plans (`enable_per_panel`).  The buffer is static like the seeds."""
         n = table_rows.shape[0]
         g = None
+        if self._sampler_key is not None and self._sampler_key[4]:
+            raise ValueError("load_schedule: the built sampler runs panel schedules, one per slot (load_slots)")
         if guidance is not None:
             if self._sampler_key is None:
                 raise ValueError("load_schedule: a guidance vector needs a built sampler (build_sampler)")
@@ -998,12 +1045,134 @@ class UNetEngine:
         the rows it gives `load_schedule`, whose counter still starts at 0 - into the static buffer.  A captured step
         graph replays with the new contents, like seeds and guidance.  full_strength: the prep plan starts from
         noise * init_noise_sigma, the latents of a plain run, instead of renoise row 0."""
-        if self._sampler_key is None or not self._sampler_key[3]:
+        if self._sampler_key is None or not self._sampler_key[3] or self._sampler_key[4]:
             raise ValueError("load_redraw: the built sampler is not a redraw sampler (build_sampler(..., redraw=True))")
         ns = self._sampler_key[0]
         if tuple(x0.shape) != (ns, 4, self.H, self.W):
             raise ValueError(f"load_redraw: x0 {tuple(x0.shape)}, ({ns}, 4, {self.H}, {self.W}) is needed")
         ops.redraw_load(self.redraw, x0, noise, mask, renoise_rows, full_strength, init_noise_sigma)
+
+    # -- panel schedules (continuous batching): everything below writes only the named slots' parts of the static buffers,
+    #    on the current stream between graph replays - never inside a capture - and never resets the device counter
+    def _panel_key(self):
+        if self._sampler_key is None or not self._sampler_key[4]:
+            raise ValueError("the built sampler has no panel schedules (build_sampler(..., panel_schedules=True))")
+        return self._sampler_key
+
+    def reset_slots(self):
+        """Every slot empty and the device counter at 0: the state a continuous run starts from."""
+        self._panel_key()
+        self.panel.zero_()
+        self.ctr.zero_()
+
+    def load_slots(self, slots, rows, solver_rows=None, renoise_rows=None, seeds=None, guidance=None, start: int = 0,
+                   latents: Optional[Tensor] = None, redraw: Optional[dict] = None, init_noise_sigma: float = 1.0):
+        """One request's panels into the slots `slots` (a list of slot numbers): its schedule - rows fp32 [steps, 8],
+        solver_rows [steps, 8] (DPM-Solver++ only), renoise_rows [steps + 1, 2] (a redraw request) - beginning when the
+        device counter reads `start` (the step boundary the caller is at; the counter is not touched), one Philox seed
+        (Euler Ancestral only) and one guidance scale per slot.  A plain request gives `latents` [k,4,H,W], its scaled
+        start latents; a redraw request gives `redraw` = {"x0", "noise", "mask", "full_strength"} ([k,4,H,W], [k,4,H,W],
+        [k,H,W]) and needs the redraw sampler, in which a plain request's slots get mask 1.  `start_slots` then writes
+        the start state."""
+        ns, kind, do_cfg, rd, _ = self._panel_key()
+        slots = [int(q) for q in slots]
+        k = len(slots)
+        if not slots or len(set(slots)) != k or min(slots) < 0 or max(slots) >= ns:
+            raise ValueError(f"load_slots: slots {slots} are not distinct slot numbers in [0, {ns})")
+        rows = torch.as_tensor(rows, dtype=torch.float32)
+        if rows.dim() != 2 or rows.shape[1] != 8 or not 1 <= rows.shape[0] <= ops.PANEL_MAX_ROWS:
+            raise ValueError(f"load_slots: rows {tuple(rows.shape)}, [steps, 8] with 1 <= steps <= {ops.PANEL_MAX_ROWS} is needed")
+        if (solver_rows is not None) != (kind == KIND_DPM):
+            raise ValueError(f"solver rows are given exactly for a DPM-Solver++ sampler (built kind: {kind})")
+        if (seeds is not None) != (kind == KIND_EULER_ANCESTRAL):
+            raise ValueError(f"noise seeds are given exactly for an Euler Ancestral sampler (built kind: {kind})")
+        if (latents is None) == (redraw is None):
+            raise ValueError("load_slots: `latents` (a plain request) or `redraw` (a redraw request), one of them")
+        if redraw is not None and not rd:
+            raise ValueError("load_slots: a redraw request needs the redraw sampler (build_sampler(..., redraw=True))")
+        if redraw is not None and renoise_rows is None:
+            raise ValueError("load_slots: a redraw request needs its renoise rows")
+        g = self._scale_values(guidance, k, "guidance") or [float(guidance)] * k
+        shape = (k, 4, self.H, self.W)
+        for name, t in (("latents", latents),) if redraw is None else (("x0", redraw["x0"]), ("noise", redraw["noise"])):
+            if tuple(t.shape) != shape:
+                raise ValueError(f"load_slots: {name} {tuple(t.shape)}, {shape} is needed")
+        if seeds is not None:
+            seeds = torch.as_tensor(seeds, dtype=torch.int64).reshape(-1)
+            if seeds.shape[0] != k:
+                raise ValueError(f"{seeds.shape[0]} noise seeds for {k} slots")
+        if redraw is not None:
+            mh = torch.as_tensor(redraw["mask"]).to(torch.float16)
+            if tuple(mh.shape) != (k, self.H, self.W) or not bool(((mh >= 0) & (mh <= 1)).all()):
+                raise ValueError(f"load_slots: mask {tuple(mh.shape)}: ({k}, {self.H}, {self.W}) values in [0, 1] are needed")
+        # everything is checked: only now is anything written
+        mode = ops.PANEL_START_KEEP if redraw is None else (
+            ops.PANEL_START_FULL if redraw.get("full_strength") else ops.PANEL_START_RENOISE)
+        idx = torch.tensor(slots, dtype=torch.int64).pin_memory().to(self.dev, non_blocking=True)
+        put = lambda dst, src: dst.index_copy_(0, idx, self._dev(src, dst.dtype))
+        put(self.guidance, torch.tensor(g, dtype=torch.float32))
+        if seeds is not None:
+            put(self.noise_seeds, seeds)
+        if rd:
+            vx, vn, vm = ops.redraw_views(self.redraw, ns, self.H, self.W)[:3]
+            if redraw is None:
+                put(vm, torch.ones(k, self.H, self.W, dtype=torch.float16))
+            else:
+                put(vx, redraw["x0"]), put(vn, redraw["noise"]), put(vm, mh)
+        if redraw is None:
+            put(self.latents, latents)
+        f32 = lambda t: None if t is None else self._dev(torch.as_tensor(t, dtype=torch.float32), torch.float32).contiguous()
+        rows, solver_rows, renoise_rows = f32(rows), f32(solver_rows), f32(renoise_rows)
+        for q in slots:
+            ops.panel_slot_load(self.panel, ns, q, int(start), rows, solver_rows, renoise_rows, mode, init_noise_sigma)
+
+    def _dev(self, t: Tensor, dtype) -> Tensor:
+        """`t` on the engine's device in `dtype`; host data goes through pinned memory, so no one waits for the stream."""
+        if not t.is_cuda:
+            t = t.to(dtype).pin_memory()
+        return t.to(self.dev, dtype, non_blocking=True)
+
+    def start_slots(self, slots):
+        """The start state and the first model input of the slots just loaded (the slot-start op, once per run of
+        consecutive slot numbers); no other slot is touched."""
+        ns, _, do_cfg, rd, _ = self._panel_key()
+        slots = sorted(int(q) for q in slots)
+        lib, st = _lib.load(), torch.cuda.current_stream().cuda_stream
+        a = 0
+        while a < len(slots):
+            b = a
+            while b + 1 < len(slots) and slots[b + 1] == slots[b] + 1:
+                b += 1
+            op = make_op("SLOT_START", i=(ns, self.H * self.W, int(do_cfg), slots[a], b - a + 1),
+                         p=(self.panel, self.redraw if rd else None, self.latents, self.x_in))
+            check(lib.ds_op_run(C.byref(op), st), "ds_op_run(SLOT_START)")
+            a = b + 1
+
+    def set_slot_request(self, slots, encoder_hidden_states: Tensor, text_embeds: Tensor, time_ids: Tensor, bbox: Tensor,
+                         dialog_boxes: Optional[Tensor], ip_scale):
+        """`set_request` for the batch rows of the slots `slots` alone.  The tensors hold those rows in batch order:
+        under classifier-free guidance the k negative rows, then the k conditional rows (rows q and ns + q of the batch
+        are slot q); `ip_scale`: a number or one value per slot.  The prepare plan then runs over the whole batch - it
+        is deterministic, so every other row gets the bits it already has."""
+        ns, _, do_cfg, _, _ = self._panel_key()
+        slots = [int(q) for q in slots]
+        k = len(slots)
+        rows = slots + [ns + q for q in slots] if do_cfg else slots
+        s = self._scale_values(ip_scale, k, "ip_scale") or [float(ip_scale)] * k
+        idx = torch.tensor(rows, dtype=torch.int64).pin_memory().to(self.dev, non_blocking=True)
+
+        def put(dst, src):
+            src = self._dev(src, dst.dtype).reshape((len(rows),) + tuple(dst.shape[1:]))
+            dst.index_copy_(0, idx, src)
+
+        put(self.enc, encoder_hidden_states), put(self.text_embeds, text_embeds), put(self.time_ids, time_ids)
+        put(self.bbox, bbox)
+        if dialog_boxes is None:
+            put(self.dialog_boxes, torch.zeros((len(rows),) + tuple(self.dialog_boxes.shape[1:]), dtype=torch.int32))
+        else:
+            put(self.dialog_boxes, dialog_boxes)
+        put(self.ip_scale, torch.tensor(s + s if do_cfg else s, dtype=torch.float32))
+        self.prepare_plan.run()
 
     # -- host-side setters (tiny H2D copies; never inside a captured graph)
     def set_request(self, encoder_hidden_states: Tensor, text_embeds: Tensor, time_ids: Tensor, bbox: Tensor,

@@ -564,6 +564,111 @@ def redraw_start(redraw: Tensor, latents: Tensor) -> None:
     check(_lib.load().ds_redraw_start_f16(_p(redraw), _p(latents), ns, H * W, _stream()), "ds_redraw_start_f16")
 
 
+# ---- panel schedules: the per-slot buffer of include/diffsensei_hip.h ("Panel schedules") and the launches that read it
+PANEL_MAX_ROWS = 1024
+PANEL_START_RENOISE, PANEL_START_FULL, PANEL_START_KEEP = 0, 1, 2
+
+
+def panel_schedule_buffer(ns: int, device) -> Tensor:
+    """The zeroed uint8 device buffer `start | steps | mode | coef | solver | renoise` for `ns` panel slots, all empty."""
+    return torch.zeros(int(_lib.load().ds_panel_schedule_bytes(int(ns))), dtype=torch.uint8, device=device)
+
+
+def _chk_panel(buf: Tensor, ns: int) -> None:
+    if buf.dtype != torch.uint8 or buf.dim() != 1 or not buf.is_contiguous() or buf.data_ptr() % 16:
+        raise _lib.DiffSenseiHipError("panel-schedule buffer: a contiguous, 16-byte aligned uint8 vector is needed")
+    if buf.numel() != int(_lib.load().ds_panel_schedule_bytes(ns)):
+        raise _lib.DiffSenseiHipError(f"panel-schedule buffer: {buf.numel()} bytes do not fit ns={ns}")
+
+
+def panel_schedule_views(buf: Tensor, ns: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """Views of a panel-schedule buffer: start int32 [ns], steps int32 [ns], mode fp32 [ns,4], coef fp32 [ns,R,8], solver
+    fp32 [ns,R,8], renoise fp32 [ns,R+1,2] with R = PANEL_MAX_ROWS."""
+    _chk_panel(buf, ns)
+    R = PANEL_MAX_ROWS
+    off = (8 * ns + 15) & ~15
+    i32 = buf[:8 * ns].view(torch.int32)
+    f32 = buf[off:].view(torch.float32)
+    a, b, c = 4 * ns, 4 * ns + 8 * R * ns, 4 * ns + 16 * R * ns
+    return (i32[:ns], i32[ns:], f32[:a].view(ns, 4), f32[a:b].view(ns, R, 8), f32[b:c].view(ns, R, 8),
+            f32[c:].view(ns, R + 1, 2))
+
+
+def panel_slot_load(buf: Tensor, ns: int, slot: int, start: int, rows: Optional[Tensor], solver_rows: Optional[Tensor] = None,
+                    renoise_rows: Optional[Tensor] = None, start_mode: int = PANEL_START_KEEP,
+                    init_noise_sigma: float = 1.0) -> None:
+    """Write slot `slot` of a panel-schedule buffer: its schedule begins when the step counter reads `start` and runs
+    `rows.shape[0]` rows.  rows: fp32 [steps, 8]; solver_rows: fp32 [steps, 8] (DPM-Solver++); renoise_rows: fp32
+    [steps + 1, 2] (region redraw).  Host tensors are copied to the device first; the launch is stream-ordered.
+    rows = None empties the slot."""
+    _chk(buf, dtype=torch.uint8)
+    _chk_panel(buf, ns)
+    dev = buf.device
+    f = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float32).to(dev, non_blocking=True).contiguous()
+    rows, solver_rows, renoise_rows = f(rows), f(solver_rows), f(renoise_rows)
+    steps = 0 if rows is None else int(rows.shape[0])
+    if rows is not None and (rows.dim() != 2 or rows.shape[1] != 8):
+        raise ValueError(f"panel_slot_load: rows {tuple(rows.shape)}, [steps, 8] is needed")
+    if solver_rows is not None and tuple(solver_rows.shape) != (steps, 8):
+        raise ValueError(f"panel_slot_load: solver rows {tuple(solver_rows.shape)} do not match the {steps} rows")
+    if renoise_rows is not None and tuple(renoise_rows.shape) != (steps + 1, 2):
+        raise ValueError(f"panel_slot_load: renoise rows {tuple(renoise_rows.shape)}, ({steps + 1}, 2) is needed")
+    check(_lib.load().ds_panel_slot_load(_p(buf), int(ns), int(slot), int(start), steps, _p(rows), _p(solver_rows),
+                                         _p(renoise_rows), int(start_mode), float(init_noise_sigma), _stream()),
+          "ds_panel_slot_load")
+
+
+def cfg_sampler_step_slots(eps: Tensor, latents: Tensor, model_in: Tensor, panel: Tensor, kind: int, ctr: Tensor,
+                           guidance: Optional[Tensor], do_cfg: bool = True, prev_x0: Optional[Tensor] = None,
+                           seeds: Optional[Tensor] = None, redraw: Optional[Tensor] = None) -> None:
+    """The sampler step on panel schedules: panel n runs row `ctr - start[n]` of its own rows in `panel`
+    (`panel_schedule_buffer` / `panel_slot_load`) and an inactive panel is left alone.  `redraw`: the region-redraw
+    buffer (its kept latents, noise and masks; the renoise rows come from `panel`), None for no blend."""
+    ns = latents.shape[0]
+    _chk(eps, latents, model_in, prev_x0)
+    _chk(guidance, dtype=torch.float32)
+    _chk(ctr, dtype=torch.int32)
+    _chk(panel, dtype=torch.uint8)
+    _chk_panel(panel, ns)
+    if guidance is not None and tuple(guidance.shape) != (ns,):
+        raise _lib.DiffSenseiHipError(f"guidance {tuple(guidance.shape)}: one fp32 per panel, ({ns},), is needed")
+    if prev_x0 is not None and prev_x0.shape != latents.shape:
+        raise ValueError(f"prev_x0 {tuple(prev_x0.shape)} must have the latents' shape {tuple(latents.shape)}")
+    _chk_seeds(seeds, ns)
+    if redraw is not None:
+        _chk(redraw, dtype=torch.uint8)
+        redraw_views(redraw, ns, latents.shape[2], latents.shape[3])
+    check(_lib.load().ds_cfg_sampler_step_slots_f16(_p(eps), _p(latents), _p(model_in), _p(panel), _p(guidance), _p(prev_x0),
+                                                    _p(seeds), _p(redraw), _p(ctr), ns, latents.shape[2] * latents.shape[3],
+                                                    int(kind), int(do_cfg), _stream()), "ds_cfg_sampler_step_slots_f16")
+
+
+def timestep_embed_slots(panel: Tensor, ns: int, B: int, dim: int, ctr: Tensor, flip: bool = True,
+                         freq_shift: float = 0.0) -> Tensor:
+    """[B, dim] sinusoidal embeddings, row b of the timestep panel b % ns is at (0 for an empty slot)."""
+    _chk(panel, dtype=torch.uint8)
+    _chk_panel(panel, ns)
+    _chk(ctr, dtype=torch.int32)
+    out = torch.empty((B, dim), dtype=torch.float16, device=panel.device)
+    check(_lib.load().ds_timestep_embed_slots_f16(_p(panel), _p(ctr), _p(out), B, dim, int(flip), freq_shift, int(ns),
+                                                  _stream()), "ds_timestep_embed_slots_f16")
+    return out
+
+
+def panel_slot_start(panel: Tensor, redraw: Optional[Tensor], latents: Tensor, model_in: Tensor, slot0: int, nslots: int,
+                     do_cfg: bool = True) -> None:
+    """Start state and first model input of slots [slot0, slot0 + nslots): see `ds_panel_slot_start_f16`."""
+    _chk(latents, model_in)
+    ns, _, H, W = latents.shape
+    _chk(panel, dtype=torch.uint8)
+    _chk_panel(panel, ns)
+    if redraw is not None:
+        _chk(redraw, dtype=torch.uint8)
+        redraw_views(redraw, ns, H, W)
+    check(_lib.load().ds_panel_slot_start_f16(_p(panel), _p(redraw), _p(latents), _p(model_in), ns, H * W, int(do_cfg),
+                                              int(slot0), int(nslots), _stream()), "ds_panel_slot_start_f16")
+
+
 def philox_u32(seeds: Tensor, step: int, HW: int, stream_id: int = 0) -> Tensor:
     """Raw Philox4x32-10 words, int32 [ns,HW,4] holding the uint32 bit patterns (include/diffsensei_hip.h)."""
     ns = seeds.shape[0]

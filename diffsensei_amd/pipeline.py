@@ -880,6 +880,19 @@ class DiffSenseiPipeline:
                     self.unet.set_adapters(list(before), list(before.values()))
         return hold()
 
+    # a request of `generate_batch` / `generate_continuous`: the keyword arguments of `__call__` (without `output_type`)
+    _REQUEST_FIELDS = ("prompt", "prompt_2", "height", "width", "num_inference_steps", "guidance_scale", "negative_prompt",
+                       "negative_prompt_2", "num_samples", "generator", "original_size", "crops_coords_top_left", "target_size",
+                       "ip_images", "ip_image_embeds", "ip_bbox", "ip_scale", "dialog_bbox", "latents", "prompt_embeds",
+                       "negative_prompt_embeds", "pooled_prompt_embeds", "negative_pooled_prompt_embeds", "noise_seeds",
+                       "redraw_latents", "redraw_bbox", "redraw_mask", "strength")
+    _REQUEST_DEFAULTS = dict(prompt_2=None, height=None, width=None, num_inference_steps=40, guidance_scale=5.0,
+                             negative_prompt=None, negative_prompt_2=None, num_samples=1, generator=None, original_size=None,
+                             crops_coords_top_left=(0, 0), target_size=None, ip_images=[], ip_image_embeds=None, ip_bbox=[],
+                             ip_scale=1.0, dialog_bbox=[], latents=None, prompt_embeds=None, negative_prompt_embeds=None,
+                             pooled_prompt_embeds=None, negative_pooled_prompt_embeds=None, noise_seeds=None,
+                             redraw_latents=None, redraw_bbox=None, redraw_mask=None, strength=1.0)
+
     @torch.no_grad()
     def _generate_batch(self, requests: List[dict], output_type: str = "pil") -> List[Any]:
         """Each request: the keyword arguments of `__call__` (without `output_type`).  All must share height, width and
@@ -919,17 +932,7 @@ class DiffSenseiPipeline:
             self.scheduler.set_timesteps(requests[0].get("num_inference_steps", 40), device=self._execution_device)
             self.scheduler.start_index(float(requests[0].get("strength", 1.0)))
         requests = self._encode_request_images(requests, images)
-        names = ("prompt", "prompt_2", "height", "width", "num_inference_steps", "guidance_scale", "negative_prompt",
-                 "negative_prompt_2", "num_samples", "generator", "original_size", "crops_coords_top_left", "target_size",
-                 "ip_images", "ip_image_embeds", "ip_bbox", "ip_scale", "dialog_bbox", "latents", "prompt_embeds",
-                 "negative_prompt_embeds", "pooled_prompt_embeds", "negative_pooled_prompt_embeds", "noise_seeds",
-                 "redraw_latents", "redraw_bbox", "redraw_mask", "strength")
-        defaults = dict(prompt_2=None, height=None, width=None, num_inference_steps=40, guidance_scale=5.0,
-                        negative_prompt=None, negative_prompt_2=None, num_samples=1, generator=None, original_size=None,
-                        crops_coords_top_left=(0, 0), target_size=None, ip_images=[], ip_image_embeds=None, ip_bbox=[],
-                        ip_scale=1.0, dialog_bbox=[], latents=None, prompt_embeds=None, negative_prompt_embeds=None,
-                        pooled_prompt_embeds=None, negative_pooled_prompt_embeds=None, noise_seeds=None,
-                        redraw_latents=None, redraw_bbox=None, redraw_mask=None, strength=1.0)
+        names, defaults = self._REQUEST_FIELDS, self._REQUEST_DEFAULTS
         conds = []
         for r in requests:
             unknown = set(r) - set(names)
@@ -942,4 +945,227 @@ class DiffSenseiPipeline:
         for c in conds:
             res.append(images[off:off + c["n"]])
             off += c["n"]
+        return res
+
+    # ---- continuous batching: per-panel schedules, slots refilled in flight (serving front-end)
+    def generate_continuous(self, requests: List[dict], slots: int, output_type: str = "pil") -> List[Any]:
+        """Run `requests` (the dicts `generate_batch` takes) through ONE UNet batch of `slots` panel slots in which every
+        slot carries its own schedule: when a panel finishes, its slot goes to the next request while the others keep
+        going.  All requests share height, width, the side of 1 their guidance is on and `lora` (one adapter state for the
+        run, handled like `generate_batch` handles it); everything else is per request - `num_inference_steps`,
+        `strength`, plain or region redraw, prompts, references, boxes, seeds, both sliders.  Requests are admitted
+        strictly in order, the head of the queue at the first step boundary at which `num_samples` slots are free
+        (`serving.plan_continuous`, which this method executes); a waiting request's conditioning runs at its admission.
+        If any request is a redraw the sampler is the redraw sampler and plain panels carry mask 1.  Finished latents are
+        cloned out of their slots at the boundary at which they finish and decoded after the run; results come back in
+        request order.  `num_samples > slots` is a ValueError before anything runs, as is every other input check of every
+        request (`_check_continuous`: sizes, guidance sides, redraw fields, step counts, prompts and references, slider and
+        seed lists, given latents - `latents` is [num_samples, 4, H/8, W/8] here).  `last_run_info["continuous"]` is the executed plan.  There is no `callback_on_step_end` here."""
+        absent = object()
+        states = [r.get("lora", absent) for r in requests]
+        norm = lambda st: st if st is absent else tuple(sorted((str(k), float(v)) for k, v in dict(st or {}).items()))
+        if len({norm(st) for st in states}) > 1:
+            raise ValueError("generate_continuous: the requests of one run must share their `lora` adapters and weights")
+        held = self._keep_adapters_until
+        if not requests or (states[0] is absent and held is None):
+            return self._generate_continuous(requests, slots, output_type)
+        want = list(held.items()) if states[0] is absent else list(norm(states[0]))
+        before = self.unet.adapter_weights()
+        requests = [{k: v for k, v in r.items() if k != "lora"} for r in requests]
+        if want == list(before.items()):
+            return self._generate_continuous(requests, slots, output_type)
+        checked = self._check_continuous(requests, slots)    # every refusal before the weights are touched
+        self.unet.set_adapters([k for k, _ in want], [v for _, v in want])
+        try:
+            return self._generate_continuous(requests, slots, output_type, checked)
+        finally:
+            if held is None:
+                self.unet.set_adapters(list(before), list(before.values()))
+
+    def _check_continuous(self, requests: List[dict], slots: int):
+        """Every input check of every request of a continuous run, before any encoder: returns (plan, schedules, images,
+        do_cfg) - `serving.plan_continuous` over the steps each request runs, each request's `panel_schedule`, and its
+        `redraw_image` as a host tensor (or None)."""
+        from . import ops
+        from .serving import plan_continuous
+        slots = int(slots)
+        if slots < 1:
+            raise ValueError("generate_continuous: slots must be >= 1")
+        names = self._REQUEST_FIELDS
+        for i, r in enumerate(requests):
+            unknown = set(r) - set(names) - {"redraw_image", "redraw_image_seeds"}
+            if unknown:
+                raise TypeError(f"generate_continuous: unknown request fields {sorted(unknown)}")
+            if int(r.get("num_samples", 1) or 1) > slots:
+                raise ValueError(f"generate_continuous: request {i} has num_samples {r.get('num_samples')} > slots {slots}")
+        size = lambda r: (r.get("height") or self.default_sample_size * self.vae_scale_factor,
+                          r.get("width") or self.default_sample_size * self.vae_scale_factor)
+        if any(size(r) != size(requests[0]) for r in requests):
+            raise ValueError("generate_continuous: requests must share height and width")
+        sides = [self._cfg_side(self._panel_values(r.get("guidance_scale", 5.0), r.get("num_samples", 1) or 1, "guidance_scale"))
+                 for r in requests]
+        if any(s != sides[0] for s in sides):
+            raise ValueError("generate_continuous: requests mix classifier-free guidance on (guidance_scale > 1) and off (<= 1)")
+        schedules, images = [], []
+        for i, r in enumerate(requests):
+            h, w = size(r)
+            ns = r.get("num_samples", 1) or 1
+            img = self._redraw_image_input(r.get("redraw_image"), r.get("redraw_latents"), ns, h, w)
+            if img is None and r.get("redraw_image_seeds") is not None:
+                raise ValueError("generate_continuous: `redraw_image_seeds` without `redraw_image`")
+            images.append(img)
+            x0 = r.get("redraw_latents") if img is None else torch.zeros(1, 4, h // self.vae_scale_factor, w // self.vae_scale_factor)
+            rd = self._redraw_inputs(x0, r.get("redraw_bbox"), r.get("redraw_mask"), r.get("strength", 1.0), ns, h, w)
+            self._check_request_fields(i, r, img, ns, h, w)
+            steps = r.get("num_inference_steps", 40)
+            if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
+                raise ValueError(f"generate_continuous: request {i}: num_inference_steps {steps!r} is not a positive integer")
+            sch = self.scheduler.panel_schedule(steps, 1.0 if rd is None else rd["strength"])   # "no step would run" raises here
+            if sch["steps"] > ops.PANEL_MAX_ROWS:
+                raise ValueError(f"generate_continuous: request {i} runs {sch['steps']} steps, a slot holds {ops.PANEL_MAX_ROWS}")
+            schedules.append(sch)
+        plan = plan_continuous([s["steps"] for s in schedules], [int(r.get("num_samples", 1) or 1) for r in requests], slots)
+        return plan, schedules, images, sides[0]
+
+    def _check_request_fields(self, i: int, r: dict, image: Optional[Tensor], ns: int, h: int, w: int) -> None:
+        """The checks `_conditioning` and `_encode_request_images` would make of request i at its admission - by then other
+        requests' steps have run -, made up front instead: prompts and references, the size, the slider and seed lists,
+        given latents, the picture's seeds, and a prompt without text encoders."""
+        what = f"generate_continuous: request {i}: "
+        get = lambda k: r[k] if k in r else self._REQUEST_DEFAULTS.get(k)
+        self.check_inputs(get("prompt"), get("prompt_2"), get("ip_images"), get("ip_image_embeds"), list(get("ip_bbox")))
+        if h % self.vae_scale_factor or w % self.vae_scale_factor:
+            raise ValueError(f"{what}`height` and `width` have to be divisible by {self.vae_scale_factor} but are {h} and {w}.")
+        self._panel_values(get("ip_scale"), ns, "ip_scale")
+        seeds = get("noise_seeds")
+        if seeds is not None:
+            if not self.scheduler.stochastic:
+                raise ValueError(f"{what}`noise_seeds` given, but {type(self.scheduler).__name__} draws no noise")
+            seeds = [int(v) for v in seeds]
+            if len(seeds) != ns or any(v < 0 or v >= 2 ** 63 for v in seeds):
+                raise ValueError(f"{what}`noise_seeds`: {ns} integers in [0, 2**63) are needed, got {seeds}")
+        gen = get("generator")
+        if isinstance(gen, (list, tuple)) and len(gen) != ns:
+            raise ValueError(f"{what}{len(gen)} generators for {ns} samples")
+        lat = get("latents")
+        shape = (ns, self.unet.config.in_channels, h // self.vae_scale_factor, w // self.vae_scale_factor)
+        if lat is not None and (not torch.is_tensor(lat) or tuple(lat.shape) != shape):
+            raise ValueError(f"{what}`latents` {tuple(lat.shape) if torch.is_tensor(lat) else type(lat)}, {shape} is needed")
+        rs = get("redraw_image_seeds") if "redraw_image_seeds" in r else None
+        if image is not None and rs is not None and len([int(v) for v in rs]) != image.shape[0]:
+            raise ValueError(f"{what}{image.shape[0]} `redraw_image_seeds` are needed, got {len(rs)}")
+        if get("prompt_embeds") is None:
+            if self.text_encoder is None or self.tokenizer is None:
+                raise ValueError(f"{what}no text encoders registered: pass prompt_embeds / negative_prompt_embeds / "
+                                 "pooled_prompt_embeds / negative_pooled_prompt_embeds")
+        elif get("pooled_prompt_embeds") is None:
+            raise ValueError(f"{what}`prompt_embeds` needs `pooled_prompt_embeds`")
+
+    @torch.no_grad()
+    def _generate_continuous(self, requests: List[dict], slots: int, output_type: str = "pil", checked=None) -> List[Any]:
+        if not requests:
+            return []
+        self._interrupt = False
+        slots = int(slots)
+        plan, schedules, images, do_cfg = checked if checked is not None else self._check_continuous(requests, slots)
+        device = self._execution_device
+        names, defaults = self._REQUEST_FIELDS, self._REQUEST_DEFAULTS
+        any_redraw = any(r.get("redraw_latents") is not None or r.get("redraw_image") is not None for r in requests)
+        r0 = requests[0]
+        H = (r0.get("height") or self.default_sample_size * self.vae_scale_factor) // self.vae_scale_factor
+        W = (r0.get("width") or self.default_sample_size * self.vae_scale_factor) // self.vae_scale_factor
+        B = 2 * slots if do_cfg else slots
+        eng = self.unet.engine(B, H, W, H / W)
+        eng.build_sampler(slots, self.scheduler.kind, do_cfg, redraw=any_redraw, panel_schedules=True)
+        if self._stream is None:
+            self._stream = torch.cuda.Stream(device=device)
+        st = self._stream
+        st.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(st):
+            eng.reset_slots()
+        admit, finish, where = {}, {}, {}
+        for s, r, sl in plan["admissions"]:
+            admit.setdefault(s, []).append((r, sl))
+            finish.setdefault(plan["finish"][r], []).append(r)
+            where[r] = sl
+        out: List[Optional[Tensor]] = [None] * len(requests)
+        graph = False
+        # The conditioning of a request is made on the caller's stream and read on the sampling stream, which runs far behind
+        # the host.  Every such tensor is told so (`record_stream`) and kept referenced until the caller's stream has waited
+        # for the sampling stream at the end of the run: its memory cannot go to a later request's conditioning before the
+        # copies that read it have executed.
+        alive: list = []
+
+        def hand_over(*tensors):
+            for t in tensors:
+                if torch.is_tensor(t):
+                    if t.is_cuda:
+                        t.record_stream(st)
+                    alive.append(t)
+
+        def admit_request(r, sl, s):
+            req = self._encode_request_images([requests[r]], [images[r]])[0]
+            cond = self._conditioning(*[req[n] if n in req else defaults[n] for n in names])
+            sch = schedules[r]
+            pos, neg = cond["pos"], cond["neg"]
+            if do_cfg:     # a slot's rows in batch order: the negative ones, then the conditional ones (`_denoise`)
+                enc = torch.cat([torch.cat([neg[0], neg[2]], dim=1), torch.cat([pos[0], pos[2]], dim=1)], dim=0)
+                text, tids = torch.cat([neg[1], pos[1]], dim=0), torch.cat([cond["time_ids"]] * 2, dim=0)
+                bbox, dialog = torch.cat([neg[3], pos[3]], dim=0), torch.cat([neg[4], pos[4]], dim=0)
+            else:          # without CFG the rows carry the all-zero negative boxes, like `_denoise`
+                enc, text, tids = torch.cat([pos[0], pos[2]], dim=1), pos[1], cond["time_ids"]
+                bbox, dialog = neg[3], pos[4]
+            rd = cond["redraw"]
+            boxes = dialog_pixel_boxes(dialog, H, W)
+            hand_over(enc, text, tids, bbox, dialog, boxes, cond["lat"], cond["time_ids"], *pos, *neg,
+                      *((rd["x0"], rd["mask"]) if rd is not None else ()))
+            st.wait_stream(torch.cuda.current_stream(device))      # the conditioning ran on the caller's stream
+            with torch.cuda.stream(st):
+                eng.set_slot_request(sl, enc, text, tids, bbox, boxes, cond["ip_scales"])
+                eng.load_slots(sl, torch.from_numpy(sch["rows"]),
+                               None if sch["solver_rows"] is None else torch.from_numpy(sch["solver_rows"]),
+                               torch.from_numpy(sch["renoise_rows"]) if rd is not None else None,
+                               cond["noise_seeds"], cond["guidance"], start=s,
+                               latents=cond["lat"] if rd is None else None,
+                               redraw=None if rd is None else {"x0": rd["x0"], "noise": cond["lat"], "mask": rd["mask"],
+                                                                "full_strength": rd["strength"] == 1.0},
+                               init_noise_sigma=sch["init_noise_sigma"])
+                eng.start_slots(sl)
+            return cond
+
+        conds = {}
+        for s in range(plan["forwards"] + 1):
+            if s in finish:                                        # this boundary: harvest, then hand the slots on
+                with torch.cuda.stream(st):
+                    for r in finish[s]:
+                        idx = torch.tensor(where[r], dtype=torch.int64).pin_memory().to(device, non_blocking=True)
+                        out[r] = eng.latents.index_select(0, idx)
+            for r, sl in admit.get(s, []):
+                conds[r] = admit_request(r, sl, s)
+            if s == plan["forwards"]:
+                break
+            with torch.cuda.stream(st):
+                if self.use_graph and not eng.step_plan.captured:
+                    eng.step_plan.run(st.cuda_stream)              # first step eager (also warms lazy kernel state)
+                    eng.step_plan.capture(st.cuda_stream)
+                elif self.use_graph:
+                    eng.step_plan.replay(st.cuda_stream)
+                    graph = True
+                else:
+                    eng.step_plan.run(st.cuda_stream)
+        torch.cuda.current_stream(device).wait_stream(st)
+        for t in out:                                              # allocated on the sampling stream, read on the caller's
+            t.record_stream(torch.cuda.current_stream(device))
+        alive.clear()                                              # the caller's stream is behind every copy that read them
+        self.last_run_info = {"graph": graph, "ops_per_step": eng.step_plan.n, "batch": B, "latent_hw": (H, W),
+                              "noise_seeds": [conds[r]["noise_seeds"] for r in range(len(requests))],
+                              "guidance_scales": [conds[r]["guidance"] for r in range(len(requests))],
+                              "ip_scales": [conds[r]["ip_scales"] for r in range(len(requests))],
+                              "continuous": dict(plan)}
+        images_out = self._postprocess(torch.cat(out, dim=0), output_type)
+        res, off = [], 0
+        for r in range(len(requests)):
+            n = out[r].shape[0]
+            res.append(images_out[off:off + n])
+            off += n
         return res

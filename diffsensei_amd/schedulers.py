@@ -154,6 +154,22 @@ class _Scheduler:
         rows[n] = (1.0, 0.0)
         return rows
 
+    # -- panel schedules (continuous batching): everything ONE panel needs, without touching this object's state
+    def panel_schedule(self, num_inference_steps: int, strength: float = 1.0, guidance_scale: float = 1.0) -> dict:
+        """The schedule of one panel that runs `num_inference_steps` steps at `strength` (1.0: all of them; < 1: a region
+        redraw that starts at `start_index(strength)`): {"t_start", "steps" (rows it runs), "rows" = coef_table[t_start:],
+        "solver_rows" = solver_table(start=t_start) (None unless DPM-Solver++), "renoise_rows" = renoise_table[t_start:]
+        (steps + 1 rows), "init_noise_sigma", "timesteps" (numpy, the run's own)}.  Computed on a copy: requests with
+        other step counts are in flight, so this scheduler's `set_timesteps` state stays what it was."""
+        import copy
+        s = copy.copy(self)             # `set_timesteps` only rebinds attributes, so a shallow copy shares nothing it writes
+        s.set_timesteps(int(num_inference_steps))
+        t0 = s.start_index(strength)
+        solver = s.solver_table(start=t0) if t0 else s.solver_table()
+        return {"t_start": t0, "steps": s.num_inference_steps - t0, "rows": s.coef_table(guidance_scale)[t0:],
+                "solver_rows": solver, "renoise_rows": s.renoise_table()[t0:],
+                "init_noise_sigma": float(s.init_noise_sigma), "timesteps": np.array(s.timesteps_np[t0:])}
+
     # -- stand-alone protocol (one kernel launch each; the pipeline's fused loop does not go through these)
     def _index_of(self, timestep, default: int) -> int:
         """diffusers `index_for_timestep`: the row of `timestep` - the second one when a timestep repeats (a Karras grid

@@ -22,6 +22,12 @@ on: classifier-free guidance doubles the UNet batch, so it is on or off for a wh
 five-value key above.  Multi-GPU: shard the request list with `distributed.shard_requests` (LPT by
 pixel count, no data-path collective) and run one batcher per rank.
 
+`continuous=True` (`BucketBatcher`; `plan_continuous`, `continuous_key`) takes step count, strength and plain / redraw out
+of the key as well: every panel slot of `DiffSenseiPipeline.generate_continuous` runs its own schedule, and a finished
+panel's slot is handed to the next request of the queue while the others keep going, so a queue of mixed step counts
+keeps one UNet batch full instead of falling apart into one small bucket per step count.  The default, False, plans
+the static batches described above.
+
 MLLM-conditioned requests: `BucketBatcher(pipe, agent=agent)` and `submit(..., ip_images=[...], mllm={"input_ids",
 "ids_cmp_mask", "mllm_scale", ...})`.  `run()` first turns every such request into an `ip_image_embeds` request through
 `mllm.mllm_prepass_batch`, in groups of at most `agent.llm.max_sequences` (one decode loop per group: a token step for 16
@@ -104,11 +110,67 @@ def plan_batches(requests: List[dict], max_panels: int, max_pixels: Optional[int
     return batches
 
 
+def plan_continuous(steps_run: List[int], panels: List[int], slots: int) -> dict:
+    """The timeline of a continuous-batching run over `slots` panel slots, from the step counts alone (pure host code: which
+    panel finishes at which step needs no look at the device).  Request r runs `steps_run[r]` consecutive steps on
+    `panels[r]` slots.  Requests are admitted strictly in order: the head of the queue is admitted at the first step
+    boundary at which `panels[head]` slots are free (the lowest-numbered free ones), and several may be admitted at one
+    boundary.  Returns {"forwards": UNet forwards of the run, "slot_steps": sum of steps x panels, "idle_slot_steps":
+    forwards x slots - slot_steps, "admissions": [(global_step, request, [slots])] in admission order, "finish":
+    [global step after which request r is done]}.  `DiffSenseiPipeline.generate_continuous` executes exactly this plan."""
+    if slots < 1:
+        raise ValueError("slots must be >= 1")
+    if len(steps_run) != len(panels):
+        raise ValueError(f"{len(steps_run)} step counts for {len(panels)} panel counts")
+    for r, (n, k) in enumerate(zip(steps_run, panels)):
+        if int(n) < 1 or int(k) < 1:
+            raise ValueError(f"request {r}: steps {n} and panels {k} must both be >= 1")
+        if int(k) > slots:
+            raise ValueError(f"request {r}: num_samples {k} exceeds the {slots} slots")
+    free = list(range(slots))
+    busy: Dict[int, int] = {}              # slot -> global step at which it is free again
+    admissions, finish = [], [0] * len(steps_run)
+    head, s = 0, 0
+    while True:
+        for slot in [q for q, end in busy.items() if end == s]:
+            del busy[slot]
+            free.append(slot)
+        free.sort()
+        while head < len(steps_run) and int(panels[head]) <= len(free):
+            take, free = free[:int(panels[head])], free[int(panels[head]):]
+            for slot in take:
+                busy[slot] = s + int(steps_run[head])
+            finish[head] = s + int(steps_run[head])
+            admissions.append((s, head, take))
+            head += 1
+        if not busy:
+            break
+        s += 1
+    slot_steps = sum(int(n) * int(k) for n, k in zip(steps_run, panels))
+    return {"forwards": s, "slot_steps": slot_steps, "idle_slot_steps": s * slots - slot_steps, "admissions": admissions,
+            "finish": finish}
+
+
+def continuous_key(request: dict) -> Tuple:
+    """What must agree for requests to share a continuous-batching run: (height, width, guidance > 1, lora state).  Step
+    counts, strengths, plain vs redraw and both sliders are per panel there."""
+    g = _scale_key(request.get("guidance_scale", 5.0))
+    on = {x > 1 for x in (g if isinstance(g, tuple) else (g,))}
+    if len(on) != 1:
+        raise ValueError(f"guidance_scale {list(g)} mixes classifier-free guidance on (> 1) and off (<= 1) in one request")
+    lora = None
+    if "lora" in request:
+        lora = tuple(sorted((str(k), float(v)) for k, v in dict(request["lora"] or {}).items()))
+    return (request.get("height"), request.get("width"), on.pop(), lora)
+
+
 class BucketBatcher:
-    """Collects requests, then runs them bucket by bucket through `pipe.generate_batch`."""
+    """Collects requests, then runs them bucket by bucket through `pipe.generate_batch` - or, with `continuous=True`, group
+    by group (`continuous_key`, largest resolution first) through `pipe.generate_continuous` on as many panel slots as
+    `plan_batches` would put panels into a batch: requests of any step count, strength and mode keep those slots full."""
 
     def __init__(self, pipe, max_panels: int = 32, max_pixels: Optional[int] = 32 * 1024 * 1024,
-                 mix_scales: bool = False, agent=None, prepass=None):
+                 mix_scales: bool = False, agent=None, prepass=None, continuous: bool = False):
         # defaults = the benchmark's operating point (bench.py: 32 panels of 1024 x 1024 per call = UNet batch 64, where every
         # projection of the level-2 transformers is a whole number of 256-tile rounds); the pixel cap scales the panel count
         # down for larger images and lets smaller ones use the full 32
@@ -121,6 +183,8 @@ class BucketBatcher:
         self._pending: List[dict] = []
         self.last_plan: List[List[int]] = []
         self.last_prepass: List[List[int]] = []   # tickets of each MLLM pre-pass batch of the last run()
+        self.continuous = continuous         # slots refilled in flight instead of one static batch per bucket
+        self.last_slots: List[int] = []      # continuous: the slot count of each group of the last run()
 
     def submit(self, **request) -> int:
         """Queue one request (keyword arguments of `DiffSenseiPipeline.__call__`, without `output_type`); returns its ticket."""
@@ -182,6 +246,8 @@ class BucketBatcher:
         """Run everything queued; returns the per-request outputs indexed by ticket and empties the queue."""
         reqs, self._pending = self._pending, []
         reqs = self._resolve_mllm(reqs)
+        if self.continuous:
+            return self._run_continuous(reqs, output_type)
         self.last_plan = plan_batches(reqs, self.max_panels, self.max_pixels, self.mix_scales)
         results: List[Any] = [None] * len(reqs)
         import contextlib
@@ -192,5 +258,32 @@ class BucketBatcher:
             for batch in self.last_plan:
                 outs = self.pipe.generate_batch([reqs[i] for i in batch], output_type=output_type)
                 for i, o in zip(batch, outs):
+                    results[i] = o
+        return results
+
+    def _run_continuous(self, reqs: List[dict], output_type: str) -> List[Any]:
+        groups: Dict[Tuple, List[int]] = {}
+        for i, r in enumerate(reqs):
+            groups.setdefault(continuous_key(r), []).append(i)
+        order = sorted(groups, key=lambda k: -((k[0] or 0) * (k[1] or 0)))
+        self.last_plan, self.last_slots = [], []
+        for k in order:
+            cap = self.max_panels
+            if self.max_pixels is not None and k[0] and k[1]:
+                cap = max(1, min(self.max_panels, self.max_pixels // (k[0] * k[1])))
+            ns = [int(reqs[i].get("num_samples", 1) or 1) for i in groups[k]]
+            for i, n in zip(groups[k], ns):
+                if n > self.max_panels:
+                    raise ValueError(f"request {i}: num_samples {n} exceeds max_panels {self.max_panels}")
+            # like `plan_batches`, the pixel cap shapes the packing only: a request larger than it is still served
+            self.last_plan.append(groups[k])
+            self.last_slots.append(max(cap, max(ns)))
+        results: List[Any] = [None] * len(reqs)
+        import contextlib
+        hold = self.pipe.hold_adapters() if any("lora" in r for r in reqs) else contextlib.nullcontext()
+        with hold:
+            for idx, slots in zip(self.last_plan, self.last_slots):
+                outs = self.pipe.generate_continuous([reqs[i] for i in idx], slots=slots, output_type=output_type)
+                for i, o in zip(idx, outs):
                     results[i] = o
         return results

@@ -418,6 +418,46 @@ int64_t ds_redraw_buffer_bytes(int ns, int HW);
 int ds_redraw_start_f16(const void* redraw, void* latents, int ns, int HW, void* stream);
 int ds_prepare_model_input_f16(const void* latents, void* model_in, const float* table, const int32_t* step_ctr,
                                int ns, int HW, int do_cfg, void* stream);
+/* Panel schedules (continuous batching): every panel slot of a sampling batch runs its own schedule, so requests with
+ * different step counts, strengths and plain / redraw modes share one UNet batch and a finished panel's slot is handed to
+ * the next request while the others keep going.  `panel`: ONE device buffer, 16-byte aligned,
+ * ds_panel_schedule_bytes(ns) bytes, offsets from ns alone; R = DS_PANEL_MAX_ROWS, the row capacity of a slot:
+ *   start    int32 [ns]          value of the global step counter at which the panel's schedule begins     at byte 0
+ *   steps    int32 [ns]          rows the panel runs; 0 = an empty slot                                    at byte 4*ns
+ *   (pad to the next multiple of 16 bytes: F = (8*ns + 15) & ~15)
+ *   mode     fp32 [ns][4]        {start mode, init_noise_sigma, 0, 0}; start mode 0 = renoise row 0,       at byte F
+ *                                1 = full strength (noise * init_noise_sigma), 2 = keep the latents (a plain panel)
+ *   coef     fp32 [ns][R][8]     the panel's rows of the per-step scalar table (column 7 is not read)      at byte F + 16*ns
+ *   solver   fp32 [ns][R][8]     its DPM-Solver++ rows (kind 2)                                            at byte F + 16*ns + 32*R*ns
+ *   renoise  fp32 [ns][R+1][2]   its renoise rows {ka, kb}, state r of ITS run (region redraw)             at byte F + 16*ns + 64*R*ns
+ * With s = *step_ctr panel n is at its row j = s - start[n]; it is active iff 0 <= j < steps[n] (steps above R count as R).
+ * ds_panel_slot_load writes one slot from DEVICE rows - coef_rows [steps][8], solver_rows [steps][8] (NULL: kept),
+ * renoise_rows [steps+1][2] (NULL: kept; start mode 0 needs them) - plus its clock and start mode, in one launch; no other
+ * slot's bytes change.  steps above DS_PANEL_MAX_ROWS, a slot outside [0, ns), a NULL or misaligned buffer fail. */
+#define DS_PANEL_MAX_ROWS 1024
+int64_t ds_panel_schedule_bytes(int ns);
+int ds_panel_slot_load(void* panel, int ns, int slot, int start, int steps, const float* coef_rows, const float* solver_rows,
+                       const float* renoise_rows, int start_mode, float init_noise_sigma, void* stream);
+/* ds_cfg_sampler_step_redraw_f16 on panel schedules: panel n takes row j of its own coefficient / solver / renoise rows
+ * where that call takes row *step_ctr of the shared tables; guidance is always the per-panel vector (needed when do_cfg);
+ * kind 3 draws its Philox noise for step j, so a panel's noise depends on neither its slot nor when it was admitted.
+ * An inactive panel (empty, not yet started, finished) has nothing stored: its latents, prev_x0 and both model_in rows keep
+ * their bits.  `redraw` NULL: no blend (every panel plain); given: the x0k | noise | mask parts of the redraw buffer above
+ * are read (its header and renoise rows are not), and a plain panel carries an all-ones mask.  step_ctr is required. */
+int ds_cfg_sampler_step_slots_f16(const void* eps, void* latents, void* model_in, const void* panel, const float* guidance,
+                                  void* prev_x0, const int64_t* seeds, const void* redraw, const int32_t* step_ctr, int ns,
+                                  int HW, int kind, int do_cfg, void* stream);
+/* ds_timestep_embed_f16 with one timestep per row: row b belongs to panel b % ns (B a multiple of ns) and embeds column 0
+ * of that panel's row clamp(j, 0, steps - 1); an empty slot embeds 0.  Always finite. */
+int ds_timestep_embed_slots_f16(const void* panel, const int32_t* step_ctr, void* out, int B, int dim, int flip_sin_to_cos,
+                                float freq_shift, int ns, void* stream);
+/* The state slots [slot0, slot0 + nslots) start from: ds_redraw_start_f16 + ds_prepare_model_input_f16 for those panels
+ * alone.  By start mode: 0 latents = fp16(ka0 * x0k + kb0 * noise), {ka0, kb0} = the panel's own renoise row 0; 1 latents =
+ * fp16(noise * init_noise_sigma); 2, or `redraw` NULL: the latents are the caller's.  Then model_in = fp16(latents /
+ * c_in_div) of the panel's coefficient row 0 into rows n and (do_cfg) ns + n.  Nothing of another slot is written, and
+ * nothing of an empty slot (steps = 0) in the range. */
+int ds_panel_slot_start_f16(const void* panel, const void* redraw, void* latents, void* model_in, int ns, int HW, int do_cfg,
+                            int slot0, int nslots, void* stream);
 int ds_nhwc_to_nchw_f16(const void* x, void* y, int B, int HW, int C, void* stream);
 int ds_nchw_to_nhwc_f16(const void* x, void* y, int B, int HW, int C, void* stream);
 int ds_pad_rows_f16(const void* x, void* y, int B, int rows_in, int rows_out, int row_off, int total_rows, int C,
@@ -561,13 +601,17 @@ enum ds_opcode {
     DS_OP_CONV_IN = 7,       /* p: x, w, bias, boxes, demb, y             i: B H W Cin Cout ndialog */
     DS_OP_CONV_OUT = 8,      /* p: x, w, bias, y                          i: B H W Cin Cout */
     DS_OP_SKINNY = 9,        /* p: x, w, bias, addend, y                  i: M N K silu_in silu_out */
-    DS_OP_TIMESTEP_EMBED = 10, /* p: table, ctr, out                      i: B dim flip               f: freq_shift */
+    DS_OP_TIMESTEP_EMBED = 10, /* p: table, ctr, out                      i: B dim flip               f: freq_shift
+                                  i[3] = ns > 0: panel schedules - p[0] is the panel-schedule buffer, row b reads panel b % ns
+                                  (ds_timestep_embed_slots_f16) */
     DS_OP_ADD_TIME_IDS = 11, /* p: text_embeds, time_ids, out             i: B pooled n_ids dim flip  f: freq_shift */
     DS_OP_SAMPLER_STEP = 12, /* p: eps, latents, model_in, table, ctr, prev_x0, solver (these two: kind 2 only),
                                    seeds (kind 3 only), guidance (p[8]: fp32 [ns], one per panel; NULL = column 7 of the table)
                                    p[9]: the region-redraw buffer (ds_cfg_sampler_step_redraw_f16), read when i[4] = 1
                                 i: ns HW kind (0 Euler, 1 DDIM, 2 DPM-Solver++, 3 Euler Ancestral) do_cfg redraw (i[4]: 0 | 1;
-                                   1 without p[9] fails the launch) */
+                                   1 without p[9] fails the launch)
+                                   i[5] = 1: panel schedules (ds_cfg_sampler_step_slots_f16) - p[3] is the panel-schedule buffer in
+                                   the table's place, p[6] is not read (the solver rows live in the buffer), p[8] is required */
     DS_OP_PREP_INPUT = 13,   /* p: latents, model_in, table, ctr          i: ns HW do_cfg */
     DS_OP_ADVANCE = 14,      /* p: ctr */
     DS_OP_NHWC2NCHW = 15,    /* p: x, y                                   i: B HW C */
@@ -591,7 +635,7 @@ enum ds_opcode {
     DS_OP_REDRAW_START = 33,      /* p: redraw buffer, latents                  i: ns HW   (ds_redraw_start_f16) */
     DS_OP_LLM_GEMV_W8 = 34,       /* DS_OP_LLM_GEMV with int8 weights in p[1] and p[5] = w_scale (ds_llm_gemv_w8) */
     DS_OP_LLM_GEMM16_W8 = 35,     /* DS_OP_LLM_GEMM16 with int8 weights in p[1] and p[5] = w_scale (ds_llm_gemm16_w8) */
-    DS_OP_LORA_MERGE = 36         /* p: W, out, A, B, seg, s, map, colscale, out2   l: ldw ldo lda ldb ldo2   i: N K R nseg
+    DS_OP_LORA_MERGE = 36,        /* p: W, out, A, B, seg, s, map, colscale, out2   l: ldw ldo lda ldb ldo2   i: N K R nseg
                                      out[n,k] = f16(f32(W[map(n),k]) + sum_i s[i] * sum_{r in [seg[i], seg[i+1])} B[map(n),r] A[r,k]):
                                      W [N,K] f16 is the base weight, read only - the launch fails when it is out or out2; A [R,K]
                                      and B [N,R] f16 hold the adapters concatenated along the rank (any rank, any boundary; nseg <= 16, empty segments legal);
@@ -600,6 +644,8 @@ enum ds_opcode {
                                      fp32, added in order, rounded once.  map (optional int32 [N]) permutes the rows of W and B alike;
                                      out2 (optional, with colscale f16 [K]) = f16(f32(out) * f32(colscale[k])), the fused-LayerNorm
                                      copy.  N, K multiples of 8; ldw, ldo, lda, ldo2 multiples of 8; no exported entry point */
+    DS_OP_SLOT_START = 37         /* p: panel-schedule buffer, redraw buffer (or NULL), latents, model_in
+                                     i: ns HW do_cfg slot0 nslots   (ds_panel_slot_start_f16) */
 };
 
 typedef struct ds_op {
