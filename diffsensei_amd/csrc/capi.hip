@@ -25,7 +25,7 @@ void ds_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* ds_last_error(void) { return g_err; }
-int ds_version(void) { return 105; }
+int ds_version(void) { return 106; }
 
 int ds_device_info(int* cu_count, int* lds_bytes, char* arch_name, int arch_name_len) {
     int dev = 0;
@@ -491,10 +491,13 @@ int ds_skinny_linear_f16(const void* x, const void* w, const void* bias, const v
 static int llm_gemv_impl(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, const void* residual,
                          int64_t ldr, int M, int N, int K, int rms, int swiglu, float eps, hipStream_t st,
                          const void* rms_gain = nullptr, bool gemm16 = false, const float* w_scale = nullptr,
-                         bool w8 = false) {
+                         bool w8 = false, const uint8_t* w_exp = nullptr, bool fp4 = false) {
     DS_REQUIRE(!w8 || w_scale, "%s: int8 weights need their scale vector", gemm16 ? "llm_gemm16_w8" : "llm_gemv_w8");
+    DS_REQUIRE(!fp4 || (w_scale && w_exp), "%s: MXFP4 weights need their row scales (w_scale) and block exponents (w_exp)",
+               gemm16 ? "llm_gemm16_fp4" : "llm_gemv_fp4");
     LlmGemvParams g;
     g.w_scale = w_scale;
+    g.w_exp = w_exp;
     g.x = H(x); g.w = w; g.y = HM(y); g.residual = H(residual); g.gain = rms ? H(rms_gain) : nullptr;
     g.ldx = ldx; g.ldy = ldy; g.ldr = ldr; g.M = M; g.N = N; g.K = K; g.rms = rms; g.swiglu = swiglu; g.eps = eps;
     return gemm16 ? ds_launch_llm_gemm16(g, st) : ds_launch_llm_gemv(g, st);
@@ -565,6 +568,25 @@ int ds_llm_gemm16_w8(const void* x, int64_t ldx, const void* w, void* y, int64_t
 
 int ds_llm_dequant_w8(const void* q, const float* w_scale, void* w16, int64_t N, int K, void* stream) {
     return ds_launch_llm_dequant_w8(reinterpret_cast<const int8_t*>(q), w_scale, HM(w16), (long)N, K, S(stream));
+}
+
+// ---- MXFP4 weight-only (W4A16) forms: w packed e2m1 [N,K/2] (K % 32 == 0), w_exp E8M0 [N,K/32], w_scale fp32 [N] (SwiGLU 2N rows)
+int ds_llm_gemv_fp4(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, const void* residual, int64_t ldr,
+                    int M, int N, int K, int rms, const void* rms_gain, int swiglu, float eps, const float* w_scale,
+                    const uint8_t* w_exp, void* stream) {
+    return llm_gemv_impl(x, ldx, w, y, ldy, residual, ldr, M, N, K, rms, swiglu, eps, S(stream), rms_gain, false, w_scale,
+                         false, w_exp, true);
+}
+
+int ds_llm_gemm16_fp4(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, const void* residual, int64_t ldr,
+                      int M, int N, int K, int rms, const void* rms_gain, int swiglu, float eps, const float* w_scale,
+                      const uint8_t* w_exp, void* stream) {
+    return llm_gemv_impl(x, ldx, w, y, ldy, residual, ldr, M, N, K, rms, swiglu, eps, S(stream), rms_gain, true, w_scale,
+                         false, w_exp, true);
+}
+
+int ds_llm_dequant_fp4(const void* q, const float* w_scale, void* w16, int64_t N, int K, const uint8_t* w_exp, void* stream) {
+    return ds_launch_llm_dequant_fp4(reinterpret_cast<const uint8_t*>(q), w_exp, w_scale, HM(w16), (long)N, K, S(stream));
 }
 
 // ---- batched decode: up to 16 sequences per weight pass
@@ -901,6 +923,12 @@ static int run_op(const ds_op& o, hipStream_t st) {
         case DS_OP_LLM_GEMM16_W8:
             return llm_gemv_impl(p[0], l[0], p[1], p[2], l[1], p[3], l[2], i[0], i[1], i[2], i[3], i[4], o.f[0], st, p[4],
                                  true, reinterpret_cast<const float*>(p[5]), true);
+        case DS_OP_LLM_GEMV_FP4:
+            return llm_gemv_impl(p[0], l[0], p[1], p[2], l[1], p[3], l[2], i[0], i[1], i[2], i[3], i[4], o.f[0], st, p[4],
+                                 false, reinterpret_cast<const float*>(p[5]), false, reinterpret_cast<const uint8_t*>(p[6]), true);
+        case DS_OP_LLM_GEMM16_FP4:
+            return llm_gemv_impl(p[0], l[0], p[1], p[2], l[1], p[3], l[2], i[0], i[1], i[2], i[3], i[4], o.f[0], st, p[4],
+                                 true, reinterpret_cast<const float*>(p[5]), false, reinterpret_cast<const uint8_t*>(p[6]), true);
         case DS_OP_LLM_ATTN_SLOTS:
             return llm_attn_impl(p[0], l[0], p[1], p[2], l[1], reinterpret_cast<const float*>(p[3]),
                                  reinterpret_cast<const float*>(p[4]), p[5], l[2], reinterpret_cast<const int32_t*>(p[6]),
@@ -984,6 +1012,12 @@ int ds_op_describe(const ds_op* op, char* name, int name_len, double* flops, dou
             nm = "llm_gemm16_kernel";
             fl = 2.0 * i[0] * (double)i[1] * i[2] * (i[4] ? 2 : 1);
             by = (double)i[1] * (i[4] ? 2 : 1) * (i[2] + 4.0) + 2.0 * ((double)i[0] * i[2] + (double)i[0] * i[1]);
+            break;
+        case DS_OP_LLM_GEMV_FP4:    // MXFP4 weights: half a byte per weight + one exponent byte per 32 + the fp32 row scales
+        case DS_OP_LLM_GEMM16_FP4:
+            nm = op->code == DS_OP_LLM_GEMV_FP4 ? "llm_gemv_kernel" : "llm_gemm16_kernel";
+            fl = 2.0 * i[0] * (double)i[1] * i[2] * (i[4] ? 2 : 1);
+            by = (double)i[1] * (i[4] ? 2 : 1) * (i[2] / 2.0 + i[2] / 32.0 + 4.0) + 2.0 * ((double)i[0] * i[2] + (double)i[0] * i[1]);
             break;
         case DS_OP_LLM_ATTN:
         case DS_OP_LLM_ATTN_SLOTS: nm = "llm_attn_kernel"; break;

@@ -301,7 +301,7 @@ int ds_launch_lora_merge_group(const LoraMergeParams* ps, int count, hipStream_t
 //                                      max_new_tokens, eos id, spare, spare}
 struct LlmGemvParams {
     const half_t* x = nullptr;         // [M,K] rows (ldx)
-    const void* w = nullptr;           // [N,K] row-major fp16 (int8 with w_scale); SwiGLU: [2N,K] = gate rows then up rows
+    const void* w = nullptr;           // [N,K] row-major fp16 (int8 with w_scale, MXFP4 with w_exp); SwiGLU: [2N,K] = gate rows then up rows
     half_t* y = nullptr;               // [M,N] rows (ldy)
     const half_t* residual = nullptr;  // [M,N] rows (ldr) added after the fp16 rounding; may alias y
     long ldx = 0, ldy = 0, ldr = 0;
@@ -314,6 +314,10 @@ struct LlmGemvParams {
     float eps = 1e-6f;
     const float* w_scale = nullptr;    // null: fp16 weights.  Given: w is int8 (K % 16 == 0) and w_scale fp32 [N] (SwiGLU [2N]),
                                        // one scale per weight row: y = (x' . q[n]) * w_scale[n], scaled in fp32 before the fp16 rounding
+    const uint8_t* w_exp = nullptr;    // given (with w_scale): w is MXFP4 - packed e2m1 [N,K/2], element 2i in the low nibble (K % 32
+                                       // == 0) - and w_exp [N,K/32] row-major (SwiGLU [2N,K/32]) holds one biased E8M0 exponent per
+                                       // 32-element block: weight = e2m1 * 2^(w_exp - 127) * w_scale[n].  The natural layout is the
+                                       // kernels' own: no permuted copy
 };
 int ds_launch_llm_gemv(const LlmGemvParams& p, hipStream_t stream);
 void ds_llm_gemv_set_variant(int v);   // 0 auto (pipelined), 1 one column per wavefront, 2 streaming without pipelining
@@ -353,6 +357,9 @@ int ds_launch_llm_swiglu(const half_t* gu, half_t* act, int M, int I, hipStream_
 int ds_launch_llm_gemm16(const LlmGemvParams& p, hipStream_t stream);
 // w16[n][k] = f16(f32(q[n][k]) * scale[n]): an int8 weight matrix back to fp16 for the prompt pass's MFMA GEMMs
 int ds_launch_llm_dequant_w8(const int8_t* q, const float* scale, half_t* w16, long N, int K, hipStream_t stream);
+// w16[n][k] = f16(f32(e2m1[n][k] * 2^(w_exp[n][k/32] - 127)) * scale[n]): the same for an MXFP4 matrix (q [N,K/2], K % 32 == 0)
+int ds_launch_llm_dequant_fp4(const uint8_t* q, const uint8_t* w_exp, const float* scale, half_t* w16, long N, int K,
+                              hipStream_t stream);
 
 // ---- character-reference pre-processing (preprocess.hip): Pillow's 8-bit separable resize + crop + normalise ----
 int ds_launch_resize_h(const uint8_t* src, int H, int W, const int* first, const int* count, const int* taps, int ksize,

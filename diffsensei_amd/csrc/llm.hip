@@ -17,6 +17,9 @@
 // int8 weight-only decoding (W8A16): the projection weights may instead be int8 [N,K] with one fp32 scale per row; the
 // GEMV / gemm16 kernels are templated on the weight element type (WLoad below) and share every line but the unpack and the
 // row scale in the epilogue.  Activations, KV cache, embedding, lm_head and gains stay fp16.
+// MXFP4 weight-only decoding (W4A16): the projection weights may also be packed e2m1 [N,K/2] (element 2i in the low nibble)
+// with one biased E8M0 exponent per 32-element block ([N,K/32], values 114..127) and one fp32 scale per row; a 16-byte load
+// is one block, unpacked by v_cvt_scalef32_pk_f16_fp4 with the block's scale - the third WLoad specialisation below.
 #include "ds_common.h"
 #include "ds_kernels.h"
 
@@ -44,22 +47,36 @@ __device__ __forceinline__ h8 rms_gain8(const h8& x, const h8& g, float r) {
 // fp32 scale per output row, fp16 activations).  `halves` turns a load into NH fragments of 8 halves; int8 -> f16 is exact
 // (|q| <= 127).  Per 32-bit word: q ^ 0x80 = q + 128 as an unsigned byte, v_perm_b32 puts it under the exponent byte 0x64
 // (f16 0x6400 + u = 1024 + u, ulp 1 there), a packed subtract of 1152 leaves q: 5 VALU instructions per 4 weights.
+// MXFP4: 32 e2m1 weights = one OCP MX block, so a load never mixes two block scales.  The block's biased E8M0 exponent e
+// (114..127) becomes the f32 2^(e-127) = bit_cast(e << 23), and one v_cvt_scalef32_pk_f16_fp4 per byte gives f16(e2m1 * scale)
+// for its two nibbles (low nibble = the even element; the byte of the word is the builtin's last argument): 16 conversions
+// + one shift per 32 weights.  Every product e2m1 * 2^(e-127) is a normal f16 (>= 2^-14), so the conversion is exact.
+// Common to the three: SH = log2(weights per WT storage unit) turns an element index into a WT index; ROW_SCALE = the sum is
+// multiplied by p.w_scale[n] in the epilogue; BLOCK_SCALE = a load comes with its p.w_exp byte; xpos = where x[k] (k % 8 == 0)
+// sits in the pipelined kernel's LDS copy of a row.
 typedef int i32x4 __attribute__((ext_vector_type(4)));
+struct fp4x2_t { uint8_t b; };   // two e2m1 weights
 template <typename WT>
 struct WLoad;
 template <>
 struct WLoad<half_t> {
     typedef h8 raw;
-    static constexpr int E = 8, NH = 1;
+    static constexpr int E = 8, NH = 1, SH = 0;
+    static constexpr bool ROW_SCALE = false, BLOCK_SCALE = false;
     static constexpr int PIPE_WAVES = 1;   // llm_gemv_pipe_kernel, M = 1: wavefronts per SIMD asked of the compiler (1 = no request)
-    static __device__ __forceinline__ void halves(const raw& r, h8 (&o)[1]) { o[0] = r; }
+    static constexpr int PIPE_BLOCKS = 5;  // llm_gemv_pipe_kernel: resident blocks per CU by registers (launch_gemv_stream)
+    static __device__ __forceinline__ int xpos(int k, int) { return k; }
+    static __device__ __forceinline__ void halves(const raw& r, unsigned, h8 (&o)[1]) { o[0] = r; }
 };
 template <>
 struct WLoad<int8_t> {
     typedef i32x4 raw;
-    static constexpr int E = 16, NH = 2;
+    static constexpr int E = 16, NH = 2, SH = 0;
+    static constexpr bool ROW_SCALE = true, BLOCK_SCALE = false;
     static constexpr int PIPE_WAVES = 5;   // the unpack temporaries must not cost the fifth resident block (launch_gemv_stream)
-    static __device__ __forceinline__ void halves(const raw& r, h8 (&o)[2]) {
+    static constexpr int PIPE_BLOCKS = 5;
+    static __device__ __forceinline__ int xpos(int k, int) { return k; }
+    static __device__ __forceinline__ void halves(const raw& r, unsigned, h8 (&o)[2]) {
         const h2 bias = {(half_t)1152.0f, (half_t)1152.0f};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -75,6 +92,33 @@ struct WLoad<int8_t> {
         }
     }
 };
+template <>
+struct WLoad<fp4x2_t> {
+    typedef i32x4 raw;
+    static constexpr int E = 32, NH = 4, SH = 1;
+    static constexpr bool ROW_SCALE = true, BLOCK_SCALE = true;
+    static constexpr int PIPE_WAVES = 1;
+    static constexpr int PIPE_BLOCKS = 4;  // two sets of 8 loads + 8 exponents and four h8 per load in flight: 125 VGPRs, four wavefronts per SIMD
+    // A lane's load covers x[32 l .. 32 l + 32) of a 2048-wide chunk (64 lanes): four 16-byte reads which in the natural
+    // layout sit at a 64-byte lane stride (a 4-way bank conflict).  The LDS copy of a row is therefore permuted inside every
+    // chunk of CL = min(2048, K - chunk start) halves: quarter j of every lane's 32 is stored together, x[chunk + 32 l + 8 j + e]
+    // at chunk + j * CL / 4 + 8 l + e.  Read j of lanes l .. l + 15 is then 256 consecutive bytes (tools/lds_bank_model.py:
+    // conflict-free), a ragged last chunk (K % 32 == 0: CL / 4 is a multiple of 8) stays inside the row's K halves.
+    static __device__ __forceinline__ int xpos(int k, int K) {
+        const int c0 = k & ~2047, r = k & 2047, cl = min(2048, K - c0);
+        return c0 + ((r >> 3) & 3) * (cl >> 2) + (r >> 5) * 8;
+    }
+    static __device__ __forceinline__ void halves(const raw& r, unsigned e, h8 (&o)[4]) {
+        const float sc = __builtin_bit_cast(float, e << 23);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const unsigned u = (unsigned)r[j];
+            const h2 a = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(u, sc, 0), b = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(u, sc, 1);
+            const h2 c = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(u, sc, 2), d = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(u, sc, 3);
+            o[j] = h8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+        }
+    }
+};
 
 // ---------------------------------------------------------------------------------------------------------------
 // y[m][n] = r_m * sum_k x[m][k] w[n][k]  (+ residual[m][n]),  r_m = rsqrt(mean_k x[m][k]^2 + eps) if rms else 1
@@ -84,11 +128,13 @@ struct WLoad<int8_t> {
 // ---------------------------------------------------------------------------------------------------------------
 // WT = int8_t: w is int8 [N,K] (K % 16 == 0) and the wave's sum is multiplied by p.w_scale[n] (SwiGLU: [n] for the gate
 // row, [n + N] for the up row) before the fp16 rounding; every other rounding point is the fp16 kernel's.
+// WT = fp4x2_t: w is packed e2m1 [N,K/2] (K % 32 == 0), a load's block exponent is p.w_exp[n * K/32 + k/32] (the clamped k of
+// the load, so weights and scale of a re-read come from the same block), and the row scale is applied as for int8.
 template <typename WT, int MC, int SWIGLU>
 __global__ __launch_bounds__(256) void llm_gemv_kernel(LlmGemvParams p) {
     typedef WLoad<WT> WL;
-    constexpr int E = WL::E, NH = WL::NH;
-    constexpr bool W8 = sizeof(WT) == 1;
+    constexpr int E = WL::E, NH = WL::NH, SH = WL::SH;
+    constexpr bool W8 = WL::ROW_SCALE;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n = blockIdx.x * 4 + wave;
     const int m0 = blockIdx.y * MC;
@@ -114,24 +160,30 @@ __global__ __launch_bounds__(256) void llm_gemv_kernel(LlmGemvParams p) {
     float acc[MC], acu[MC];
 #pragma unroll
     for (int m = 0; m < MC; ++m) acc[m] = acu[m] = 0.f;
-    const WT* wg = reinterpret_cast<const WT*>(p.w) + (long)n * K;
-    const WT* wu = reinterpret_cast<const WT*>(p.w) + ((long)n + p.N) * K;
+    const WT* wg = reinterpret_cast<const WT*>(p.w) + (((long)n * K) >> SH);
+    const WT* wu = reinterpret_cast<const WT*>(p.w) + ((((long)n + p.N) * K) >> SH);
     constexpr int U = (MC <= 4) ? 4 : 2;  // independent 16-byte loads in flight per lane
     for (int k0 = lane * E; k0 < K; k0 += 64 * E * U) {
         typename WL::raw wv[U], uv[U];
+        unsigned we[U], ue[U];   // block exponents of the loads (BLOCK_SCALE only)
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int k = min(k0 + 64 * E * u, K - E);  // clamped re-read past the end, masked below
-            wv[u] = *reinterpret_cast<const typename WL::raw*>(wg + k);
-            if (SWIGLU) uv[u] = *reinterpret_cast<const typename WL::raw*>(wu + k);
+            wv[u] = *reinterpret_cast<const typename WL::raw*>(wg + (k >> SH));
+            if (SWIGLU) uv[u] = *reinterpret_cast<const typename WL::raw*>(wu + (k >> SH));
+            we[u] = ue[u] = 0;
+            if constexpr (WL::BLOCK_SCALE) {
+                we[u] = p.w_exp[(long)n * (K / E) + k / E];
+                if (SWIGLU) ue[u] = p.w_exp[((long)n + p.N) * (K / E) + k / E];
+            }
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int k = k0 + 64 * E * u;
             if (k < K) {
                 h8 wh[NH], uh[NH];
-                WL::halves(wv[u], wh);
-                if (SWIGLU) WL::halves(uv[u], uh);
+                WL::halves(wv[u], we[u], wh);
+                if (SWIGLU) WL::halves(uv[u], ue[u], uh);
 #pragma unroll
                 for (int m = 0; m < MC; ++m) {
                     if (m0 + m < p.M) {
@@ -606,12 +658,14 @@ __global__ __launch_bounds__(256) void llm_gemv_stream_kernel(LlmGemvParams p) {
 // issued before the dot products of the current one, and the first block is requested before x is staged, so a
 // wavefront always has 8 KB of weights in flight - no load bubble at block start, between k-blocks or between columns.
 // WT = int8_t: 16 weights per load, so a lane's k-stride is 16 and a k-block is twice as long; x stays fp16 in LDS.
+// WT = fp4x2_t: 32 weights per load with the load's block exponent beside it; x stays fp16 in LDS, in the order WLoad::xpos
+// gives (the fp16 and int8 forms keep the natural order).
 template <typename WT, int MC, int SWIGLU>
 __global__ __launch_bounds__(256, MC == 1 ? WLoad<WT>::PIPE_WAVES : 1) void llm_gemv_pipe_kernel(LlmGemvParams p) {
     typedef WLoad<WT> WL;
     typedef typename WL::raw wraw;
-    constexpr int E = WL::E, NH = WL::NH;
-    constexpr bool W8 = sizeof(WT) == 1;
+    constexpr int E = WL::E, NH = WL::NH, SH = WL::SH;
+    constexpr bool W8 = WL::ROW_SCALE;
     extern __shared__ char smem_raw[];
     half_t* xs = reinterpret_cast<half_t*>(smem_raw);
     float* rs = reinterpret_cast<float*>(smem_raw + (size_t)MC * p.K * 2);
@@ -622,17 +676,23 @@ __global__ __launch_bounds__(256, MC == 1 ? WLoad<WT>::PIPE_WAVES : 1) void llm_
     const int stride = gridDim.x * 4;
     int n = blockIdx.x * 4 + wave;
     wraw wa[U], ua[U], wb[U], ub[U];
-    auto issue = [&](int col, int it, wraw(&wv)[U], wraw(&uv)[U]) {
-        const WT* wg = reinterpret_cast<const WT*>(p.w) + (long)col * K;
-        const WT* wu = reinterpret_cast<const WT*>(p.w) + ((long)col + N) * K;
+    unsigned ea[U], fa[U], eb[U], fb[U];   // block exponents of the loads (BLOCK_SCALE only): e* gate / plain, f* up
+    auto issue = [&](int col, int it, wraw(&wv)[U], wraw(&uv)[U], unsigned(&ev)[U], unsigned(&fv)[U]) {
+        const WT* wg = reinterpret_cast<const WT*>(p.w) + (((long)col * K) >> SH);
+        const WT* wu = reinterpret_cast<const WT*>(p.w) + ((((long)col + N) * K) >> SH);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int k = min(it * 64 * E * U + 64 * E * u + lane * E, K - E);
-            wv[u] = *reinterpret_cast<const wraw*>(wg + k);
-            if (SWIGLU) uv[u] = *reinterpret_cast<const wraw*>(wu + k);
+            wv[u] = *reinterpret_cast<const wraw*>(wg + (k >> SH));
+            if (SWIGLU) uv[u] = *reinterpret_cast<const wraw*>(wu + (k >> SH));
+            ev[u] = fv[u] = 0;
+            if constexpr (WL::BLOCK_SCALE) {   // the clamped k: weights and scale of a re-read are one block's
+                ev[u] = p.w_exp[(long)col * (K / E) + k / E];
+                if (SWIGLU) fv[u] = p.w_exp[((long)col + N) * (K / E) + k / E];
+            }
         }
     };
-    if (n < N) issue(n, 0, wa, ua);
+    if (n < N) issue(n, 0, wa, ua, ea, fa);
     {
         float ss[MC];
 #pragma unroll
@@ -641,7 +701,7 @@ __global__ __launch_bounds__(256, MC == 1 ? WLoad<WT>::PIPE_WAVES : 1) void llm_
             for (int k = tid * 8; k < K; k += 2048) {
                 h8 v = {0, 0, 0, 0, 0, 0, 0, 0};
                 if (m < p.M) v = *reinterpret_cast<const h8*>(p.x + (long)m * p.ldx + k);
-                *reinterpret_cast<h8*>(xs + (long)m * K + k) = v;
+                *reinterpret_cast<h8*>(xs + (long)m * K + WL::xpos(k, K)) = v;
                 ss[m] = dot8(v, v, ss[m]);
             }
             ss[m] = wave_sum(ss[m]);
@@ -658,7 +718,7 @@ __global__ __launch_bounds__(256, MC == 1 ? WLoad<WT>::PIPE_WAVES : 1) void llm_
             for (int m = 0; m < MC; ++m) {
                 const float r = rs[m];
                 for (int k = tid * 8; k < K; k += 2048) {
-                    h8* xp = reinterpret_cast<h8*>(xs + (long)m * K + k);
+                    h8* xp = reinterpret_cast<h8*>(xs + (long)m * K + WL::xpos(k, K));
                     *xp = rms_gain8(*xp, *reinterpret_cast<const h8*>(p.gain + k), r);
                 }
             }
@@ -674,19 +734,19 @@ __global__ __launch_bounds__(256, MC == 1 ? WLoad<WT>::PIPE_WAVES : 1) void llm_
         for (int it = 0; it < NIT; ++it) {
             const bool last = it + 1 == NIT;
             const int ncol = last ? n + stride : n;
-            if (ncol < N) issue(ncol, last ? 0 : it + 1, wb, ub);
+            if (ncol < N) issue(ncol, last ? 0 : it + 1, wb, ub, eb, fb);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int k = it * 64 * E * U + 64 * E * u + lane * E;
                 if (k < K) {
                     h8 wh[NH], uh[NH];
-                    WL::halves(wa[u], wh);
-                    if (SWIGLU) WL::halves(ua[u], uh);
+                    WL::halves(wa[u], ea[u], wh);
+                    if (SWIGLU) WL::halves(ua[u], fa[u], uh);
 #pragma unroll
                     for (int m = 0; m < MC; ++m) {
 #pragma unroll
                         for (int j = 0; j < NH; ++j) {
-                            const h8 xv = *reinterpret_cast<const h8*>(xs + (long)m * K + k + 8 * j);
+                            const h8 xv = *reinterpret_cast<const h8*>(xs + (long)m * K + WL::xpos(k + 8 * j, K));
                             acc[m] = dot8(xv, wh[j], acc[m]);
                             if (SWIGLU) acu[m] = dot8(xv, uh[j], acu[m]);
                         }
@@ -697,6 +757,10 @@ __global__ __launch_bounds__(256, MC == 1 ? WLoad<WT>::PIPE_WAVES : 1) void llm_
             for (int u = 0; u < U; ++u) {
                 wa[u] = wb[u];
                 if (SWIGLU) ua[u] = ub[u];
+                if constexpr (WL::BLOCK_SCALE) {
+                    ea[u] = eb[u];
+                    if (SWIGLU) fa[u] = fb[u];
+                }
             }
         }
 #pragma unroll
@@ -753,12 +817,16 @@ __global__ __launch_bounds__(256, MC == 1 ? WLoad<WT>::PIPE_WAVES : 1) void llm_
 // fragments of those two steps are read at the same k indices (any assignment of k to lanes is a valid MFMA as long as
 // A and B agree).  K % 16 == 0, so a load is inside K or wholly past it: past it the x fragments are zero, whatever number
 // of 16-weight groups the last block has.  The row scale w_scale[n] is applied in the epilogue by the writing thread.
+// WT = fp4x2_t: the same argument with four steps per load.  Lane l's load covers k + 32 (l >> 4) .. + 32 of a 128-wide
+// k-block (one MX block, converted with its exponent w_exp[n][k / 32]); step 4v + j takes its weights 8 j .. 8 j + 8 and the
+// lane's x fragment of that step is read at the same k.  K % 32 == 0, so a load is inside K or wholly past it (23 blocks: the
+// last 128-wide k-block has three loads inside K and one past it); U is 4 or 8, so a wavefront issues 1 or 2 loads per matrix.
 template <typename WT, int SWIGLU>
 __global__ __launch_bounds__(256) void llm_gemm16_kernel(LlmGemvParams p) {
     typedef WLoad<WT> WL;
     typedef typename WL::raw wraw;
-    constexpr int E = WL::E, NH = WL::NH;
-    constexpr bool W8 = sizeof(WT) == 1;
+    constexpr int E = WL::E, NH = WL::NH, SH = WL::SH;
+    constexpr bool W8 = WL::ROW_SCALE;
     constexpr int U = SWIGLU ? 4 : 8;   // MFMA steps per iteration
     constexpr int UL = U / NH;          // 16-byte weight loads per lane and matrix per iteration
     constexpr int KB = 32 * U;          // halves of K per wavefront iteration
@@ -773,20 +841,24 @@ __global__ __launch_bounds__(256) void llm_gemm16_kernel(LlmGemvParams p) {
     const int NT = (N + 15) / 16, NIT = (K + 4 * KB - 1) / (4 * KB);
     const h8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
     wraw wa[UL], ua[UL], wb[UL], ub[UL];
+    unsigned ea[UL], fa[UL], eb[UL], fb[UL];   // block exponents of the loads (BLOCK_SCALE only): e* gate / plain, f* up
     h8 xa[U], xb[U];
-    // first k of MFMA step u of this lane in iteration `it`
-    auto kof = [&](int it, int u) {
-        return (it * 4 + wave) * KB + (NH == 1 ? 32 * u + 8 * g : 64 * (u >> 1) + 16 * g + 8 * (u & 1));
-    };
-    auto issue_w = [&](int tile, int it, wraw(&wv)[UL], wraw(&uv)[UL]) {
+    // first k of MFMA step u of this lane in iteration `it`: a load spans NH steps, 32 NH k per group of 4 lanes-by-16
+    auto kof = [&](int it, int u) { return (it * 4 + wave) * KB + 32 * NH * (u / NH) + 8 * NH * g + 8 * (u % NH); };
+    auto issue_w = [&](int tile, int it, wraw(&wv)[UL], wraw(&uv)[UL], unsigned(&ev)[UL], unsigned(&fv)[UL]) {
         const long col = min(tile * 16 + c, N - 1);   // ragged last tile: re-read the last row, never stored
-        const WT* wg = reinterpret_cast<const WT*>(p.w) + col * K;
-        const WT* wu = reinterpret_cast<const WT*>(p.w) + (col + N) * K;
+        const WT* wg = reinterpret_cast<const WT*>(p.w) + ((col * K) >> SH);
+        const WT* wu = reinterpret_cast<const WT*>(p.w) + (((col + N) * K) >> SH);
 #pragma unroll
         for (int u = 0; u < UL; ++u) {
-            const int k = min(kof(it, u * NH), K - E);   // ragged K: clamped, x is zero there
-            wv[u] = *reinterpret_cast<const wraw*>(wg + k);
-            if (SWIGLU) uv[u] = *reinterpret_cast<const wraw*>(wu + k);
+            const int k = min(kof(it, u * NH), K - E);   // ragged K: clamped (the scale index with it), x is zero there
+            wv[u] = *reinterpret_cast<const wraw*>(wg + (k >> SH));
+            if (SWIGLU) uv[u] = *reinterpret_cast<const wraw*>(wu + (k >> SH));
+            ev[u] = fv[u] = 0;
+            if constexpr (WL::BLOCK_SCALE) {
+                ev[u] = p.w_exp[col * (K / E) + k / E];
+                if (SWIGLU) fv[u] = p.w_exp[(col + N) * (K / E) + k / E];
+            }
         }
     };
     const half_t* xr = p.x + (long)min(c, M - 1) * p.ldx;
@@ -799,7 +871,7 @@ __global__ __launch_bounds__(256) void llm_gemm16_kernel(LlmGemvParams p) {
         }
     };
     int tile = blockIdx.x;
-    if (tile < NT) issue_w(tile, 0, wa, ua);
+    if (tile < NT) issue_w(tile, 0, wa, ua, ea, fa);
     // ---- row scales (wavefront w: rows 4w .. 4w+3) and the gain vector
     if (p.rms) {
 #pragma unroll
@@ -833,13 +905,13 @@ __global__ __launch_bounds__(256) void llm_gemm16_kernel(LlmGemvParams p) {
             const int ntile = last ? tile + (int)gridDim.x : tile, nit = last ? 0 : it + 1;
             if (ntile < NT) {
                 issue_x(nit, xb);
-                issue_w(ntile, nit, wb, ub);
+                issue_w(ntile, nit, wb, ub, eb, fb);
             }
 #pragma unroll
             for (int v = 0; v < UL; ++v) {
                 h8 wh[NH], uh[NH];
-                WL::halves(wa[v], wh);
-                if (SWIGLU) WL::halves(ua[v], uh);
+                WL::halves(wa[v], ea[v], wh);
+                if (SWIGLU) WL::halves(ua[v], fa[v], uh);
 #pragma unroll
                 for (int j = 0; j < NH; ++j) {
                     const int u = v * NH + j;
@@ -858,6 +930,10 @@ __global__ __launch_bounds__(256) void llm_gemm16_kernel(LlmGemvParams p) {
             for (int u = 0; u < UL; ++u) {
                 wa[u] = wb[u];
                 if (SWIGLU) ua[u] = ub[u];
+                if constexpr (WL::BLOCK_SCALE) {
+                    ea[u] = eb[u];
+                    if (SWIGLU) fa[u] = fb[u];
+                }
             }
         }
         // ---- split-K reduction in wavefront order, then the epilogue: thread (wave = reg, lane) owns one element
@@ -917,6 +993,31 @@ __global__ __launch_bounds__(256) void llm_dequant_w8_kernel(const int8_t* __res
     *reinterpret_cast<h8*>(w16 + e0 + 8) = o[1];
 }
 
+// w16[n][k] = f16(f32(e2m1[n][k] * 2^(e[n][k/32] - 127)) * s[n]) for the prompt pass's MFMA GEMMs: one thread per MX block
+// (16 bytes), the block product through the same hardware conversion as the decode kernels (exact in f16), then one fp32
+// multiply by the row scale and one round-to-nearest-even per element.
+__global__ __launch_bounds__(256) void llm_dequant_fp4_kernel(const uint8_t* __restrict__ q, const uint8_t* __restrict__ ex,
+                                                              const float* __restrict__ s, half_t* __restrict__ w16,
+                                                              long blocks, int K) {
+    const long bi = (long)blockIdx.x * 256 + threadIdx.x;
+    if (bi >= blocks) return;
+    const float sc = s[bi / (K / 32)];
+    const i32x4 v = *reinterpret_cast<const i32x4*>(q + bi * 16);
+    h8 h[4];
+    WLoad<fp4x2_t>::halves(v, ex[bi], h);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        h8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float f = (float)h[j][e] * sc;
+            asm("" : "+v"(f));   // as in llm_dequant_w8_kernel: the fp32 product and the fp16 rounding stay two steps
+            o[e] = (half_t)f;
+        }
+        *reinterpret_cast<h8*>(w16 + bi * 32 + 8 * j) = o;
+    }
+}
+
 static thread_local int g_llm_gemv_variant = 0;  // 0 auto (pipelined), 1 one-column-per-wavefront kernel, 2 un-pipelined streaming kernel
 
 template <typename WT, int MC, int SWIGLU>
@@ -930,9 +1031,9 @@ int launch_gemv_stream(const LlmGemvParams& p, hipStream_t stream) {
         cus = prop.multiProcessorCount;
     }
     const size_t lds = (size_t)MC * p.K * 2 + (size_t)MC * 5 * sizeof(float);
-    // resident blocks per CU: 8 x 4 wavefronts at <= 64 VGPRs (streaming kernel), 5 at ~90 VGPRs (pipelined kernel);
-    // launching exactly the resident set makes every wavefront walk the same number of columns (no tail round)
-    const size_t by_regs = g_llm_gemv_variant == 2 ? 8 : 5;
+    // resident blocks per CU: 8 x 4 wavefronts at <= 64 VGPRs (streaming kernel), 5 at ~90 VGPRs (pipelined kernel; 4 for
+    // MXFP4 at ~125); launching exactly the resident set makes every wavefront walk the same number of columns (no tail round)
+    const size_t by_regs = g_llm_gemv_variant == 2 ? 8 : WLoad<WT>::PIPE_BLOCKS;
     const int per_cu = (int)min(by_regs, (size_t)(160 * 1024) / (lds + 512));
     // (N = 5120 = exactly one column per resident wavefront for the o / down projections.  Fewer, longer-lived wavefronts
     // with 2-4 columns each to pipeline were measured and are slower: 5.03 -> 5.13 / 5.22 / 5.56 ms per token,
@@ -1003,11 +1104,23 @@ static int check_llm_w8(const LlmGemvParams& p, const char* what) {
     return 0;
 }
 
+// MXFP4 weights (p.w_exp given): one 16-byte load is one 32-element block, so K % 32 == 0; the row scales are needed too
+static int check_llm_fp4(const LlmGemvParams& p, const char* what) {
+    DS_REQUIRE(p.w_scale, "%s: MXFP4 weights need their row scales (w_scale)", what);
+    DS_REQUIRE(p.K >= 32 && p.K % 32 == 0, "%s: MXFP4 weights need K %% 32 == 0 (K=%d)", what, p.K);
+    return 0;
+}
+
 int ds_launch_llm_gemv(const LlmGemvParams& p, hipStream_t stream) {
     DS_REQUIRE(p.M > 0 && p.N > 0 && p.K >= 8 && p.K % 8 == 0, "llm_gemv: bad shape M=%d N=%d K=%d", p.M, p.N, p.K);
     DS_REQUIRE(p.ldx % 8 == 0 && p.ldx >= p.K, "llm_gemv: ldx %ld must be a multiple of 8 and >= K", p.ldx);
     DS_REQUIRE(p.x && p.w && p.y, "llm_gemv: null operand");
     DS_REQUIRE(!(p.swiglu && p.residual), "llm_gemv: the SwiGLU epilogue takes no residual");
+    if (p.w_exp) {
+        if (const int rc = check_llm_fp4(p, "llm_gemv")) return rc;
+        DS_REQUIRE(g_llm_gemv_variant != 2, "llm_gemv: llm_gemv_variant 2 (un-pipelined streaming kernel) has no MXFP4-weight form");
+        return p.swiglu ? launch_gemv<fp4x2_t, 1>(p, stream) : launch_gemv<fp4x2_t, 0>(p, stream);
+    }
     if (p.w_scale) {
         if (const int rc = check_llm_w8(p, "llm_gemv")) return rc;
         DS_REQUIRE(g_llm_gemv_variant != 2, "llm_gemv: llm_gemv_variant 2 (un-pipelined streaming kernel) has no int8-weight form");
@@ -1023,6 +1136,10 @@ int ds_launch_llm_gemm16(const LlmGemvParams& p, hipStream_t stream) {
     DS_REQUIRE(p.x && p.w && p.y, "llm_gemm16: null operand");
     DS_REQUIRE(!(p.swiglu && p.residual), "llm_gemm16: the SwiGLU epilogue takes no residual");
     DS_REQUIRE(!(p.rms && p.gain) || p.K <= 20480, "llm_gemm16: K %d too long for the gain vector in LDS (20480)", p.K);
+    if (p.w_exp) {
+        if (const int rc = check_llm_fp4(p, "llm_gemm16")) return rc;
+        return launch_gemm16<fp4x2_t>(p, stream);
+    }
     if (p.w_scale) {
         if (const int rc = check_llm_w8(p, "llm_gemm16")) return rc;
         return launch_gemm16<int8_t>(p, stream);
@@ -1037,6 +1154,18 @@ int ds_launch_llm_dequant_w8(const int8_t* q, const float* scale, half_t* w16, l
     DS_REQUIRE((groups + 255) / 256 <= 0x7fffffffL, "llm_dequant_w8: matrix too large");
     hipLaunchKernelGGL(llm_dequant_w8_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, stream, q, scale, w16,
                        groups, K);
+    DS_LAUNCH_CHECK();
+    return 0;
+}
+
+int ds_launch_llm_dequant_fp4(const uint8_t* q, const uint8_t* w_exp, const float* scale, half_t* w16, long N, int K,
+                              hipStream_t stream) {
+    DS_REQUIRE(N > 0 && K >= 32 && K % 32 == 0, "llm_dequant_fp4: bad shape N=%ld K=%d (K %% 32 == 0)", N, K);
+    DS_REQUIRE(q && w_exp && scale && w16, "llm_dequant_fp4: null operand");
+    const long blocks = N * (long)(K / 32);
+    DS_REQUIRE((blocks + 255) / 256 <= 0x7fffffffL, "llm_dequant_fp4: matrix too large");
+    hipLaunchKernelGGL(llm_dequant_fp4_kernel, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, stream, q, w_exp, scale,
+                       w16, blocks, K);
     DS_LAUNCH_CHECK();
     return 0;
 }

@@ -37,6 +37,14 @@ runs the int8 forms of the same kernels (`DS_OP_LLM_GEMV_W8` / `DS_OP_LLM_GEMM16
 registers, fp32 accumulation, the row scale in the epilogue), so a step streams about half the bytes.  The embedding,
 `lm_head` and every RMSNorm gain stay fp16.  The prompt pass dequantises one matrix at a time into a reusable fp16
 scratch (`llm_dequant_w8_kernel`) and keeps the MFMA GEMMs.  Opt-in: the default stays fp16, bit for bit.
+
+MXFP4 weight-only decoding (`LlamaDecodeEngine(weight_dtype="mxfp4")`, W4A16): the same four groups in the OCP MX fp4
+format plus one fp32 scale per row (`quantize_rows_mxfp4`: packed e2m1 elements, one E8M0 exponent per 32-element block),
+a quarter of the fp16 bytes plus 1/32 for the block exponents.  The token step runs `DS_OP_LLM_GEMV_FP4` /
+`DS_OP_LLM_GEMM16_FP4` (gfx950's `v_cvt_scalef32_pk_f16_fp4` unpacks a byte into two f16 values times the block scale,
+exactly); the prompt pass dequantises through `llm_dequant_fp4_kernel`.  Everything else is as for int8, opt-in included.
+On Gaussian weights the format's relative rms error is 11 % (int8 per row: 0.9 %); no parity figure for a trained 13B
+checkpoint can be produced offline, so what the mode does to the agent's output quality is not measured.
 """
 from __future__ import annotations
 
@@ -131,6 +139,58 @@ def dequantize_rows_int8(q: Tensor, s: Tensor) -> Tensor:
     return q.to(torch.float32) * s.to(torch.float32)[:, None]
 
 
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)      # code 0..7 of an fp4 e2m1 magnitude (bit 3 of the nibble: sign)
+MX_BLOCK = 32                                                # elements along K that share one E8M0 exponent
+MX_MIN_EXP = -13                                             # stored exponents lie in [114, 127]
+
+
+def quantize_rows_mxfp4(w: Tensor):
+    """MXFP4 with one extra fp32 scale per row, of a weight matrix [N, K] (K % 32 == 0) ->
+    (q uint8 [N, K/2], e uint8 [N, K/32], s fp32 [N]) with w ~ e2m1(q) * 2^(e - 127) * s[:, None].
+    `w` is first rounded to fp16 (what the engine holds today), then: s[n] = max_k |w[n, k]| / 6 in fp32 (1 for an all-zero
+    row); the row / s[n] is cut into blocks of 32 along K; a block whose largest magnitude is a gets the exponent
+    floor(log2 a) - 2 (the OCP MX rule for an element format whose largest exponent is 2), clamped to [-13, 0] - never above
+    0 because a normalised row does not exceed 6 - and stored biased, e = exponent + 127 (an all-zero block stores 114); the
+    elements are x / 2^exponent, saturated to +-6 and rounded to the nearest of {0, 0.5, 1, 1.5, 2, 3, 4, 6}, ties to the
+    even mantissa (0.25 -> 0, 0.75 -> 1, 2.5 -> 2, 5 -> 4), as sign + 3 bits, two per byte with element 2i in the low nibble.
+    The clamp at -13: every e2m1 * 2^exponent is then a NORMAL f16 number (the smallest, 0.5 * 2^-13 = 2^-14, is f16's
+    smallest normal), so the kernels' in-register conversion to f16 is exact and no fdot2 / MFMA operand is subnormal.  What
+    the clamp flushes to zero lies below 0.25 * 2^-13 = 2^-15 of the normalised row, i.e. below 2^-15 * 6 of the row's
+    largest weight.  Works on host and device tensors; scales are per row and per block, so quantising stacked matrices
+    (q|k|v, gate|up) equals stacking the quantised ones."""
+    if w.dim() != 2:
+        raise ValueError(f"quantize_rows_mxfp4 takes a matrix [N, K], got {tuple(w.shape)}")
+    N, K = w.shape
+    if K % MX_BLOCK:
+        raise ValueError(f"quantize_rows_mxfp4: K = {K} is not a multiple of {MX_BLOCK}")
+    w = w.detach().to(torch.float16).to(torch.float32)
+    amax = w.abs().amax(dim=1)
+    s = torch.where(amax > 0, amax / 6.0, torch.ones_like(amax))
+    x = (w / s[:, None]).view(N, K // MX_BLOCK, MX_BLOCK)
+    a = x.abs().amax(dim=2)
+    ex = torch.frexp(a).exponent.to(torch.int32) - 1 - 2            # a = m 2^k, m in [0.5, 1): floor(log2 a) = k - 1
+    ex = torch.where(a > 0, ex, torch.full_like(ex, MX_MIN_EXP)).clamp_(MX_MIN_EXP, 0)
+    y = torch.ldexp(x, -ex[:, :, None]).view(N, K)                  # exact: a power of two
+    mag = y.abs().clamp_(max=6.0)
+    code = torch.zeros_like(mag, dtype=torch.uint8)
+    for i in range(7):                                              # midpoint i lies between codes i and i + 1; a tie goes to the
+        mid = 0.5 * (E2M1_VALUES[i] + E2M1_VALUES[i + 1])           # even code (mantissa bit 0): up when i is odd
+        code += ((mag >= mid) if i % 2 else (mag > mid)).to(torch.uint8)
+    code |= ((y < 0) & (code > 0)).to(torch.uint8) << 3
+    q = code[:, 0::2] | (code[:, 1::2] << 4)
+    return q.contiguous(), (ex + 127).to(torch.uint8).contiguous(), s.contiguous()
+
+
+def dequantize_rows_mxfp4(q: Tensor, e: Tensor, s: Tensor) -> Tensor:
+    """fp32 [N, K] = f32(e2m1) * 2^(e - 127) * s[:, None]: the block product is exact, the row scale is one fp32 multiply per
+    element (what the MXFP4 kernels compute with)."""
+    N, K = q.shape[0], 2 * q.shape[1]
+    lut = torch.tensor(E2M1_VALUES + tuple(-v for v in E2M1_VALUES), dtype=torch.float32, device=q.device)
+    v = torch.stack([lut[(q & 15).long()], lut[(q >> 4).long()]], dim=2).view(N, K // MX_BLOCK, MX_BLOCK)
+    v = torch.ldexp(v, (e.to(torch.int32) - 127)[:, :, None]).view(N, K)
+    return v * s.to(torch.float32)[:, None]
+
+
 class LlamaDecodeEngine:
     """Device-resident LLaMA decoder + KV cache + the captured one-token launch plan."""
 
@@ -142,12 +202,15 @@ class LlamaDecodeEngine:
         and [S] state / id / feature / logits rows.  `generate` is one sequence in slot 0, whatever S is.
         prompt_path applies to `generate` only: `generate_batch` always takes the MFMA prompt pass.
         weight_dtype "int8": the q|k|v, o, gate|up and down matrices are held as int8 with fp32 row scales (W8A16, see
-        `quantize_rows_int8`); the embedding, lm_head and the RMSNorm gains stay fp16."""
+        `quantize_rows_int8`); the embedding, lm_head and the RMSNorm gains stay fp16.
+        weight_dtype "mxfp4": the same matrices as MXFP4 (W4A16, see `quantize_rows_mxfp4`): packed e2m1 [N, K/2], block
+        exponents [N, K/32] and fp32 row scales.  Its effect on a trained checkpoint's output is not measured."""
         _lib.load()
-        if weight_dtype not in ("float16", "int8"):
-            raise ValueError(f"weight_dtype {weight_dtype!r}: 'float16' or 'int8'")
+        if weight_dtype not in ("float16", "int8", "mxfp4"):
+            raise ValueError(f"weight_dtype {weight_dtype!r}: 'float16', 'int8' or 'mxfp4'")
         self.weight_dtype = weight_dtype
-        w8 = weight_dtype == "int8"
+        kmul = {"float16": 8, "int8": 16, "mxfp4": MX_BLOCK}[weight_dtype]     # weights per 16-byte load: K is a multiple
+        quantised = weight_dtype != "float16"
         if not 1 <= int(max_sequences) <= CHUNK:
             raise ValueError(f"max_sequences {max_sequences} outside [1, {CHUNK}] (rows of one weight pass)")
         self.max_sequences = S = int(max_sequences)
@@ -162,9 +225,9 @@ class LlamaDecodeEngine:
             raise ValueError(f"head_dim {D}: the decode attention kernel is built for 64 and 128")
         if H % 8 or I % 8:
             raise ValueError("hidden and intermediate sizes must be multiples of 8")
-        if w8 and (H % 16 or I % 16 or (Hq * D) % 16):
-            raise ValueError("weight_dtype='int8': K of every quantised matrix (hidden, heads * head_dim, intermediate size) "
-                             "must be a multiple of 16")
+        if quantised and (H % kmul or I % kmul or (Hq * D) % kmul):
+            raise ValueError(f"weight_dtype={weight_dtype!r}: K of every quantised matrix (hidden, heads * head_dim, intermediate "
+                             f"size) must be a multiple of {kmul}")
         dev = self.dev
         f16 = lambda t: t.detach().to(device=dev, dtype=torch.float16).contiguous()
 
@@ -176,27 +239,33 @@ class LlamaDecodeEngine:
         # q|k|v and gate|up are stacked (one weight stream per projection group); the RMSNorm gains stay separate vectors
         # applied in the GEMV prologue with the reference's rounding points (normalise, round to fp16, times the fp16 gain)
         self.wqkv, self.wo, self.wgu, self.wdown, self.g_in, self.g_post = [], [], [], [], [], []
-        # int8: the fp32 row scales of the four groups (empty lists with fp16 weights)
+        # int8 / mxfp4: the fp32 row scales of the four groups; mxfp4: their block exponents (empty lists otherwise)
         self.sqkv, self.so, self.sgu, self.sdown = [], [], [], []
+        self.eqkv, self.eo, self.egu, self.edown = [], [], [], []
 
-        def put(ws: list, ss: list, w16: Tensor) -> None:
+        def put(ws: list, ss: list, es: list, w16: Tensor) -> None:
             """one matrix at a time: its fp16 copy is dropped as soon as it is quantised"""
-            if not w8:
+            if weight_dtype == "float16":
                 ws.append(w16)
-                return
-            q, s = quantize_rows_int8(w16)
-            ws.append(q)
-            ss.append(s)
+            elif weight_dtype == "int8":
+                q, s = quantize_rows_int8(w16)
+                ws.append(q)
+                ss.append(s)
+            else:
+                q, e, s = quantize_rows_mxfp4(w16)
+                ws.append(q)
+                ss.append(s)
+                es.append(e)
 
         for i in range(L):
             p = f"model.layers.{i}."
-            put(self.wqkv, self.sqkv, stack([sd[p + f"self_attn.{n}_proj.weight"] for n in "qkv"]))
+            put(self.wqkv, self.sqkv, self.eqkv, stack([sd[p + f"self_attn.{n}_proj.weight"] for n in "qkv"]))
             self.g_in.append(f16(sd[p + "input_layernorm.weight"]))
-            put(self.wo, self.so, f16(sd[p + "self_attn.o_proj.weight"]))
-            put(self.wgu, self.sgu, stack([sd[p + "mlp.gate_proj.weight"], sd[p + "mlp.up_proj.weight"]]))
+            put(self.wo, self.so, self.eo, f16(sd[p + "self_attn.o_proj.weight"]))
+            put(self.wgu, self.sgu, self.egu, stack([sd[p + "mlp.gate_proj.weight"], sd[p + "mlp.up_proj.weight"]]))
             self.g_post.append(f16(sd[p + "post_attention_layernorm.weight"]))
-            put(self.wdown, self.sdown, f16(sd[p + "mlp.down_proj.weight"]))
-        self._w16: Optional[Tensor] = None                  # int8: fp16 scratch of the prompt pass (largest group), on first use
+            put(self.wdown, self.sdown, self.edown, f16(sd[p + "mlp.down_proj.weight"]))
+        self._w16: Optional[Tensor] = None                  # int8 / mxfp4: fp16 scratch of the prompt pass (largest group), on first use
         E = lambda *s, dtype=torch.float16: torch.zeros(s, dtype=dtype, device=dev)
         self.qkv_dim = (Hq + 2 * Hkv) * D
         self.h, self.qkv, self.att = E(CHUNK, H), E(CHUNK, self.qkv_dim), E(CHUNK, Hq * D)
@@ -229,30 +298,33 @@ class LlamaDecodeEngine:
     def weight_bytes_per_token(self) -> int:
         """Algorithmic HBM bytes of one decode step: every layer matrix + lm_head once (+ one embedding row)."""
         n = sum(w.numel() for ws in (self.wqkv, self.wo, self.wgu, self.wdown) for w in ws)
-        if self.weight_dtype == "int8":                     # 1 byte per quantised weight + 4 per row scale; lm_head is fp16
-            ns = sum(s.numel() for ss in (self.sqkv, self.so, self.sgu, self.sdown) for s in ss)
-            return n + 4 * ns + 2 * (self.lm_head.numel() + self.cfg.hidden_size)
+        if self.weight_dtype != "float16":                  # the quantised bytes (int8: 1 per weight; mxfp4: 0.5 per weight + 1
+            ns = sum(s.numel() for ss in (self.sqkv, self.so, self.sgu, self.sdown) for s in ss)     # per block) + 4 per row
+            ne = sum(e.numel() for es in (self.eqkv, self.eo, self.egu, self.edown) for e in es)     # scale; lm_head is fp16
+            return n + ne + 4 * ns + 2 * (self.lm_head.numel() + self.cfg.hidden_size)
         return 2 * (n + self.lm_head.numel() + self.cfg.hidden_size)
 
     def tensors(self) -> List[Tensor]:
         """Frozen weights in kernel layout (the multi-GPU weight broadcast list)."""
         return ([self.embed, self.lm_head, self.norm_g] + self.wqkv + self.wo + self.wgu + self.wdown + self.g_in + self.g_post
-                + self.sqkv + self.so + self.sgu + self.sdown)
+                + self.sqkv + self.so + self.sgu + self.sdown + self.eqkv + self.eo + self.egu + self.edown)
 
     # ---- launch lists ------------------------------------------------------------------------------------
-    def _proj(self, code: str, w: Tensor, scale: Optional[Tensor], i, l, p) -> object:
-        """One projection launch: `code` (LLM_GEMV / LLM_GEMM16) as it is with fp16 weights, its _W8 form with p[5] = the
-        row scales for an int8 matrix.  p = (x, y, residual, gain)."""
+    def _proj(self, code: str, w: Tensor, scales: tuple, i, l, p) -> object:
+        """One projection launch: `code` (LLM_GEMV / LLM_GEMM16) as it is with fp16 weights (`scales` empty), its _W8 form
+        with p[5] = the row scales for an int8 matrix, its _FP4 form with p[5] = the row scales and p[6] = the block
+        exponents for an MXFP4 one.  p = (x, y, residual, gain)."""
         x, y, residual, gain = p
-        if scale is None:
+        if not scales:
             return make_op(code, i=i, f=(self.cfg.rms_norm_eps,), l=l, p=(x, w, y, residual) + ((gain,) if gain is not None else ()))
-        return make_op(code + "_W8", i=i, f=(self.cfg.rms_norm_eps,), l=l, p=(x, w, y, residual, gain, scale))
+        return make_op(code + ("_W8", "_FP4")[len(scales) - 1], i=i, f=(self.cfg.rms_norm_eps,), l=l,
+                       p=(x, w, y, residual, gain) + scales)
 
     def _scales(self, l: int):
-        """(qkv, o, gate|up, down) row scales of layer l; None each with fp16 weights"""
-        if self.weight_dtype != "int8":
-            return None, None, None, None
-        return self.sqkv[l], self.so[l], self.sgu[l], self.sdown[l]
+        """What the (qkv, o, gate|up, down) matrices of layer l come with: nothing (fp16), the row scales (int8), the row
+        scales and the block exponents (mxfp4)."""
+        groups = ((self.sqkv, self.eqkv), (self.so, self.eo), (self.sgu, self.egu), (self.sdown, self.edown))
+        return [tuple(t[l] for t in g if t) for g in groups]
 
     def _layer_ops(self, l: int, M: int, proj: str, slots: bool) -> list:
         """The five launches of layer l over M rows.  slots: every row is its own sequence (slot-form attention on the
@@ -428,15 +500,18 @@ class LlamaDecodeEngine:
                               "token_steps_launched": steps, "ops_per_token": tok.n}
         return out
 
-    def _w(self, ws: list, ss: list, l: int) -> Tensor:
-        """The fp16 matrix a prompt-pass GEMM reads: the weight itself, or - int8 - its dequantised copy in the one
+    def _w(self, ws: list, ss: list, l: int, es: Sequence[Tensor] = ()) -> Tensor:
+        """The fp16 matrix a prompt-pass GEMM reads: the weight itself, or - int8 / mxfp4 - its dequantised copy in the one
         reusable scratch (sized for the largest group, gate|up; stream order keeps the previous user ahead of the rewrite)."""
-        if self.weight_dtype != "int8":
+        if self.weight_dtype == "float16":
             return ws[l]
         if self._w16 is None:
-            n = max(w.numel() for group in (self.wqkv, self.wo, self.wgu, self.wdown) for w in group[:1])
+            per = 2 if self.weight_dtype == "mxfp4" else 1          # weights per stored byte
+            n = max(per * w.numel() for group in (self.wqkv, self.wo, self.wgu, self.wdown) for w in group[:1])
             self._w16 = torch.empty(n, dtype=torch.float16, device=self.dev)
-        return ops.llm_dequant_w8(ws[l], ss[l], out=self._w16)
+        if self.weight_dtype == "int8":
+            return ops.llm_dequant_w8(ws[l], ss[l], out=self._w16)
+        return ops.llm_dequant_fp4(ws[l], es[l], ss[l], out=self._w16)
 
     def _prompt_mfma(self, embs: List[Tensor], slots: List[int], width: int) -> None:
         """The prompts of n >= 1 sequences in one pass per layer over their concatenated rows: the projections are
@@ -455,7 +530,7 @@ class LlamaDecodeEngine:
         att = torch.empty((starts[-1], Hq * c.head_dim), dtype=torch.float16, device=self.dev)
         for l in range(c.num_hidden_layers):
             xn = ops.llm_rmsnorm(h, self.g_in[l], eps)                       # LlamaRMSNorm incl. its gain, then the plain GEMM
-            qkv = ops.gemm(xn, self._w(self.wqkv, self.sqkv, l))
+            qkv = ops.gemm(xn, self._w(self.wqkv, self.sqkv, l, self.eqkv))
             for i, s in enumerate(slots):
                 pf.zero_()                                                   # chunk cursor of this slot's cache
                 for r0 in range(starts[i], starts[i + 1], CHUNK):
@@ -463,10 +538,10 @@ class LlamaDecodeEngine:
                     ops.llm_attention(qkv[r0:r0 + m], self.kcs[l][s], self.vcs[l][s], self.rope_cos, self.rope_sin, pf,
                                       Hq, Hkv, scale, out=att[r0:r0 + m])
                     ops.llm_advance(pf, m)
-            h = ops.gemm(att, self._w(self.wo, self.so, l), residual=h)
+            h = ops.gemm(att, self._w(self.wo, self.so, l, self.eo), residual=h)
             xn = ops.llm_rmsnorm(h, self.g_post[l], eps)
-            act = ops.llm_swiglu(ops.gemm(xn, self._w(self.wgu, self.sgu, l)))
-            h = ops.gemm(act, self._w(self.wdown, self.sdown, l), residual=h)
+            act = ops.llm_swiglu(ops.gemm(xn, self._w(self.wgu, self.sgu, l, self.egu)))
+            h = ops.gemm(act, self._w(self.wdown, self.sdown, l, self.edown), residual=h)
         if width == 1:
             last_rows = h[-1:]
         else:                                                                # row s = the last prompt row of the sequence in slot s

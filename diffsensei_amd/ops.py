@@ -1086,6 +1086,80 @@ def llm_dequant_w8(w: Tensor, w_scale: Tensor, out: Optional[Tensor] = None) -> 
     return out.view(-1)[:N * K].view(N, K)
 
 
+# ---- MXFP4 weight-only decoding (W4A16): packed e2m1 weights + E8M0 block exponents + fp32 row scales ----------------------
+def _chk_fp4(x: Tensor, w: Tensor, w_exp: Tensor, w_scale: Tensor, swiglu: bool) -> None:
+    _chk(w, w_exp, dtype=torch.uint8)
+    _chk(w_scale, dtype=torch.float32)
+    K = x.shape[1]
+    if w.dim() != 2 or K % 32 or w.shape[1] * 2 != K:
+        raise ValueError(f"MXFP4 weights must be uint8 [N, K/2] with K = {K} a multiple of 32, got {tuple(w.shape)}")
+    if swiglu and w.shape[0] % 2:
+        raise ValueError("SwiGLU weights hold gate rows then up rows: an even number of rows")
+    if w_exp.dim() != 2 or tuple(w_exp.shape) != (w.shape[0], K // 32):
+        raise ValueError(f"w_exp must be uint8 [{w.shape[0]}, {K // 32}] (one exponent per 32-element block), got {tuple(w_exp.shape)}")
+    if w_scale.dim() != 1 or w_scale.shape[0] != w.shape[0]:
+        raise ValueError(f"w_scale must be fp32 [{w.shape[0]}] (one scale per weight row), got {tuple(w_scale.shape)}")
+
+
+def llm_gemv_fp4(x: Tensor, w: Tensor, w_exp: Tensor, w_scale: Tensor, out: Optional[Tensor] = None,
+                 residual: Optional[Tensor] = None, rms: bool = False, swiglu: bool = False, eps: float = 1e-6,
+                 gain: Optional[Tensor] = None) -> Tensor:
+    """`llm_gemv` with MXFP4 weights (`mllm.quantize_rows_mxfp4`): w uint8 [N,K/2] (swiglu: [2N,K/2]), w_exp uint8 [N,K/32],
+    w_scale fp32 [N]; y = (x' . (e2m1 * 2^(w_exp-127))[n]) * w_scale[n]."""
+    _chk(x, residual, gain)
+    _chk_fp4(x, w, w_exp, w_scale, swiglu)
+    M, K = x.shape
+    N = w.shape[0] // (2 if swiglu else 1)
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float16, device=x.device)
+    _chk(out)
+    check(_lib.load().ds_llm_gemv_fp4(_p(x), K, _p(w), _p(out), N, _p(residual), N, M, N, K, int(rms), _p(gain),
+                                      int(swiglu), eps, _p(w_scale), _p(w_exp), _stream()), "ds_llm_gemv_fp4")
+    return out
+
+
+def llm_gemm16_fp4(x: Tensor, w: Tensor, w_exp: Tensor, w_scale: Tensor, out: Optional[Tensor] = None,
+                   residual: Optional[Tensor] = None, rms: bool = False, swiglu: bool = False, eps: float = 1e-6,
+                   gain: Optional[Tensor] = None, M: Optional[int] = None, N: Optional[int] = None) -> Tensor:
+    """`llm_gemm16` with MXFP4 weights (`N` restricts the call to the first N rows of w / w_exp / w_scale)."""
+    _chk(x, residual, gain)
+    _chk_fp4(x, w, w_exp, w_scale, swiglu)
+    K = x.shape[1]
+    M = x.shape[0] if M is None else int(M)
+    rows = w.shape[0] // (2 if swiglu else 1)
+    N = rows if N is None else int(N)
+    assert 0 < M <= x.shape[0] and 0 < N <= rows and (not swiglu or N == rows)
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float16, device=x.device)
+    _chk(out)
+    assert out.dim() == 2 and out.stride(1) == 1 and out.shape[0] >= M and out.shape[1] >= N
+    ldr = 0
+    if residual is not None:
+        assert residual.dim() == 2 and residual.stride(1) == 1 and residual.shape[0] >= M and residual.shape[1] >= N
+        ldr = residual.stride(0)
+    check(_lib.load().ds_llm_gemm16_fp4(_p(x), x.stride(0), _p(w), _p(out), out.stride(0), _p(residual), ldr, M, N, K,
+                                        int(rms), _p(gain), int(swiglu), eps, _p(w_scale), _p(w_exp), _stream()),
+          "ds_llm_gemm16_fp4")
+    return out
+
+
+def llm_dequant_fp4(w: Tensor, w_exp: Tensor, w_scale: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """f16(f32(e2m1 * 2^(w_exp-127)) * w_scale[:, None]) for MXFP4 w [N,K/2] (K % 32 == 0); `out`: fp16, at least N*K
+    elements, contiguous."""
+    _chk(w, w_exp, dtype=torch.uint8)
+    _chk(w_scale, dtype=torch.float32)
+    N, K = w.shape[0], 2 * w.shape[1]
+    if w.dim() != 2 or K % 32 or tuple(w_exp.shape) != (N, K // 32) or tuple(w_scale.shape) != (N,):
+        raise ValueError(f"MXFP4 weights [N, K/2] (K % 32 == 0) with exponents [N, K/32] and fp32 scales [N] are needed, got "
+                         f"{tuple(w.shape)} / {tuple(w_exp.shape)} / {tuple(w_scale.shape)}")
+    if out is None:
+        out = torch.empty((N, K), dtype=torch.float16, device=w.device)
+    _chk(out)
+    assert out.numel() >= N * K
+    check(_lib.load().ds_llm_dequant_fp4(_p(w), _p(w_scale), _p(out), N, K, _p(w_exp), _stream()), "ds_llm_dequant_fp4")
+    return out.view(-1)[:N * K].view(N, K)
+
+
 def llm_attention_slots(qkv: Tensor, k_cache: Tensor, v_cache: Tensor, rope_cos: Tensor, rope_sin: Tensor, state: Tensor,
                         heads: int, kv_heads: int, scale: float, out: Optional[Tensor] = None) -> Tensor:
     """One new row per slot: qkv [S,(heads+2*kv_heads)*D]; caches [S, T_max, kv_heads*D]; state int32 [S, 8].  Slot s

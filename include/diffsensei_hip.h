@@ -537,6 +537,27 @@ int ds_llm_gemm16_w8(const void* x, int64_t ldx, const void* w, void* y, int64_t
 /* w16[n][k] = f16(f32(q[n][k]) * w_scale[n]) for q int8 [N,K], K % 16 == 0 (one fp32 multiply, one round to nearest even):
  * the prompt pass hands the result to ds_gemm_f16 */
 int ds_llm_dequant_w8(const void* q, const float* w_scale, void* w16, int64_t N, int K, void* stream);
+/* MXFP4 weight-only decoding (W4A16): the _w8 entry points with w in the OCP MX fp4 format plus one fp32 scale per row.
+ *   w        uint8 [N,K/2] row-major (SwiGLU [2N,K/2]): two e2m1 elements per byte (sign + 3 bits, values +-{0, 0.5, 1, 1.5, 2,
+ *            3, 4, 6}), element 2i in the low nibble, element 2i+1 in the high nibble
+ *   w_exp    uint8 [N,K/32] row-major (SwiGLU [2N,K/32]): one biased E8M0 exponent per block of 32 elements along K,
+ *            block scale = 2^(w_exp - 127); the quantiser stores 114..127 (exponents -13..0), so every e2m1 * block scale is a
+ *            normal f16 number and the in-register conversion (v_cvt_scalef32_pk_f16_fp4) is exact
+ *   w_scale  fp32 [N] (SwiGLU [2N]): one scale per weight row
+ *   weight[n][k] = e2m1(w[n][k]) * 2^(w_exp[n][k/32] - 127) * w_scale[n]
+ *   y[m][n] = f16( (sum_k x'[m][k] * f16(e2m1 * 2^(w_exp-127))) * r_m * w_scale[n] )  - fp32 sum, the row scale in fp32 before
+ * the one fp16 rounding; every other rounding point is that of the fp16 form.  K % 32 == 0 (a 16-byte load is one block).
+ * ds_llm_gemv_fp4 runs llm_gemv_pipe_kernel (M <= 4) or llm_gemv_kernel; with the option "llm_gemv_variant" = 2 it fails
+ * (that kernel has no MXFP4 form).  Both w_scale and w_exp are required.  No parity figure exists for a trained checkpoint. */
+int ds_llm_gemv_fp4(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, const void* residual, int64_t ldr,
+                    int M, int N, int K, int rms, const void* rms_gain, int swiglu, float eps, const float* w_scale,
+                    const uint8_t* w_exp, void* stream);
+int ds_llm_gemm16_fp4(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, const void* residual, int64_t ldr,
+                      int M, int N, int K, int rms, const void* rms_gain, int swiglu, float eps, const float* w_scale,
+                      const uint8_t* w_exp, void* stream);
+/* w16[n][k] = f16(f32(e2m1 * 2^(w_exp - 127)) * w_scale[n]) for an MXFP4 matrix (one fp32 multiply, one round to nearest even):
+ * the prompt pass hands the result to ds_gemm_f16 */
+int ds_llm_dequant_fp4(const void* q, const float* w_scale, void* w16, int64_t N, int K, const uint8_t* w_exp, void* stream);
 /* The slot forms of ds_llm_attn_f16 / _rmsnorm_ / _embed_ / _select_: the same four kernels with every row a sequence of
  * its own (state row s of an int32 [S][8] block) instead of the next position of one sequence.  The attention, the feature
  * tap and the pick leave a slot with state[s][2] set (finished, or never started) alone.
@@ -644,8 +665,10 @@ enum ds_opcode {
                                      fp32, added in order, rounded once.  map (optional int32 [N]) permutes the rows of W and B alike;
                                      out2 (optional, with colscale f16 [K]) = f16(f32(out) * f32(colscale[k])), the fused-LayerNorm
                                      copy.  N, K multiples of 8; ldw, ldo, lda, ldo2 multiples of 8; no exported entry point */
-    DS_OP_SLOT_START = 37         /* p: panel-schedule buffer, redraw buffer (or NULL), latents, model_in
+    DS_OP_SLOT_START = 37,        /* p: panel-schedule buffer, redraw buffer (or NULL), latents, model_in
                                      i: ns HW do_cfg slot0 nslots   (ds_panel_slot_start_f16) */
+    DS_OP_LLM_GEMV_FP4 = 38,      /* DS_OP_LLM_GEMV with MXFP4 weights in p[1], p[5] = w_scale, p[6] = w_exp (ds_llm_gemv_fp4) */
+    DS_OP_LLM_GEMM16_FP4 = 39     /* DS_OP_LLM_GEMM16 with MXFP4 weights in p[1], p[5] = w_scale, p[6] = w_exp (ds_llm_gemm16_fp4) */
 };
 
 typedef struct ds_op {

@@ -10,6 +10,10 @@ per k-tile instead of 96 - 40 % conflict cycles, exactly what SQ_LDS_BANK_CONFLI
 149.4M, profiles/r02_pmc_conv_attn_summary.txt).  Swizzling by the patch column, slot = chunk ^ ((qx>>1)&7), is conflict-free
 for all nine taps, both wave rows and all four k-steps, in both kernels.
 
+Also used for `llm_gemv_pipe_kernel` with MXFP4 weights (csrc/llm.hip, WLoad<fp4x2_t>::xpos): a lane's 16-byte weight load is 32
+weights, so it reads x four times; in the natural layout the four reads sit at a 64-byte lane stride (4-way conflict, 16 cycles),
+in the kernel's permuted layout read j of lanes l .. l + 15 is 256 consecutive bytes (4 cycles) - `fp4_x_read` below.
+
     python tools/lds_bank_model.py
 """
 HWD = 18
@@ -19,14 +23,39 @@ GROUPS = [_G, _H, [l + 32 for l in _G], [l + 32 for l in _H]]
 
 
 def read_cycles(addr_of_lane):
+    """LDS cycles of one wave64 ds_read_b128; a lane whose address is None is masked off (a group without active lanes is free)"""
     total = 0
     for g in GROUPS:
         slots = {}
         for lane in g:
             a = addr_of_lane(lane)
-            slots.setdefault((a // 16) % 16, set()).add(a // 16)
-        total += max(len(v) for v in slots.values())
+            if a is not None:
+                slots.setdefault((a // 16) % 16, set()).add(a // 16)
+        total += max((len(v) for v in slots.values()), default=0)
     return total
+
+
+def active_groups(addr_of_lane):
+    """16-lane groups with at least one active lane: the cycles of a conflict-free read"""
+    return sum(any(addr_of_lane(lane) is not None for lane in g) for g in GROUPS)
+
+
+def fp4_xpos(k, K):
+    """WLoad<fp4x2_t>::xpos of csrc/llm.hip: where x[k] (k % 8 == 0) of a row of K halves sits in the row's LDS copy"""
+    c0, r = k & ~2047, k & 2047
+    cl = min(2048, K - c0)
+    return c0 + ((r >> 3) & 3) * (cl >> 2) + (r >> 5) * 8
+
+
+def fp4_x_read(K, m, chunk, j, permuted=True):
+    """Byte address per lane of x read j (0..3) of the load that covers x[chunk + 32 lane .. + 32] of staged row m (rows are K
+    halves apart); lanes whose 32 weights lie past K do not read."""
+    def addr(lane):
+        k = chunk + 32 * lane + 8 * j
+        if k >= K:
+            return None
+        return 2 * (m * K + (fp4_xpos(k, K) if permuted else k))
+    return addr
 
 
 def halo_fragment(rows_per_wave_row, wm, mi, tap, kk, swizzle):
@@ -48,6 +77,11 @@ def average(rows_per_wave_row, n_mi, swizzle):
 SWIZZLES = {"row index   (q>>1)&7": lambda q: (q >> 1) & 7, "patch column (qx>>1)&7": lambda q: ((q % HWD) >> 1) & 7}
 
 if __name__ == "__main__":
+    for K in (5120, 13824):
+        c = {p: [read_cycles(fp4_x_read(K, m, chunk, j, p)) for m in range(4) for chunk in range(0, K, 2048) for j in range(4)
+                 if K - chunk >= 2048] for p in (False, True)}
+        print(f"llm_gemv_pipe_kernel MXFP4, K = {K}: LDS cycles per x read of a full 64-lane load: natural layout "
+              f"{sum(c[False]) / len(c[False]):.2f}, permuted {sum(c[True]) / len(c[True]):.2f} (4 = conflict-free)")
     for name, f in SWIZZLES.items():
         a8, a16 = average(4, 2, f), average(8, 4, f)
         # per k-tile of the 16 x 16 kernel: 16 A-fragment reads + 8 conflict-free W reads

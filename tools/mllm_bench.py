@@ -1,12 +1,16 @@
 #!/usr/bin/env python
 """MLLM pre-pass decode rate at LLaMA-2-13B dimensions (random weights): tokens/s of the captured one-token plan and
 the HBM roofline fraction (algorithmic bytes = every layer matrix + lm_head once per token).
-    python tools/mllm_bench.py [--layers 40] [--prompt 96] [--new 192] [--sequences S] [--weight-dtype {float16,int8}]
+    python tools/mllm_bench.py [--layers 40] [--prompt 96] [--new 192] [--sequences S] [--weight-dtype {float16,int8,mxfp4}]
 --sequences S > 1: the batched decode (`generate_batch`, S sequences per weight pass): ms per step, tokens/s over all
 sequences, the HBM fraction of a step, and the per-launch time of `llm_gemm16_kernel` at the projection shapes.
 --weight-dtype int8: the engine holds int8 projection weights with fp32 row scales (W8A16); the bytes of a step come from
 `weight_bytes_per_token()` (1 byte per quantised weight + the scales + the fp16 lm_head), the per-launch shapes run the int8
 form of the kernel.
+--weight-dtype mxfp4: MXFP4 projection weights (W4A16: 0.5 byte per weight, 1 per 32-element block, 4 per row), priced and
+launched the same way on the fp4 forms.
+Both modes print the per-launch time of the five projection shapes on the kernel the mode's token step runs (M = 1: the
+`llm_gemv` form, M = S: `llm_gemm16`), priced against the bytes of that launch's weights.
 """
 import argparse
 import json
@@ -25,8 +29,8 @@ ap.add_argument("--new", type=int, default=192)
 ap.add_argument("--graph", choices=["both", "on", "off"], default="both")
 ap.add_argument("--gemv-variant", type=int, default=0, help="0 pipelined, 1 one column per wavefront, 2 streaming")
 ap.add_argument("--sequences", type=int, default=1, help="sequences per weight pass (1: the one-sequence token loop)")
-ap.add_argument("--weight-dtype", choices=["float16", "int8"], default="float16",
-                help="int8: W8A16 projection weights (lm_head, embedding and norm gains stay fp16)")
+ap.add_argument("--weight-dtype", choices=["float16", "int8", "mxfp4"], default="float16",
+                help="int8 / mxfp4: W8A16 / W4A16 projection weights (lm_head, embedding and norm gains stay fp16)")
 a = ap.parse_args()
 dev = torch.device("cuda", 0)
 from diffsensei_amd import _lib
@@ -42,8 +46,41 @@ init_s = time.perf_counter() - t0
 emb = (torch.randn(a.prompt, cfg.hidden_size, device=dev) * 0.5).half()
 
 
-def batched(S):
+def launch_times(M):
+    """Per-launch times of the five projection shapes at M rows, back to back (event pair around 20 launches after 3 warm-up
+    launches), on the kernels of this engine's weight type: llm_gemv at M = 1, llm_gemm16 otherwise."""
     from diffsensei_amd import ops
+    H, I, V = cfg.hidden_size, cfg.intermediate_size, cfg.vocab_size
+    x5, x13 = (torch.randn(M, H, device=dev) * 0.5).half(), (torch.randn(M, I, device=dev) * 0.5).half()
+    form = "gemv" if M == 1 else "gemm16"
+    suffix = {"float16": "", "int8": "_w8", "mxfp4": "_fp4"}[a.weight_dtype]
+    # what comes with the weights of layer 0: nothing (fp16), the row scales (int8), the block exponents and row scales (mxfp4)
+    extra = lambda ss, es: () if not ss else ((ss[0],) if not es else (es[0], ss[0]))
+    shapes = {"qkv": (x5, eng.wqkv[0], extra(eng.sqkv, eng.eqkv), eng.qkv_dim, dict(rms=True, gain=eng.g_in[0])),
+              "o": (x5, eng.wo[0], extra(eng.so, eng.eo), H, {}),
+              "gate_up": (x5, eng.wgu[0], extra(eng.sgu, eng.egu), I, dict(rms=True, swiglu=True, gain=eng.g_post[0])),
+              "down": (x13, eng.wdown[0], extra(eng.sdown, eng.edown), H, {}), "lm_head": (x5, eng.lm_head, (), V, {})}
+    kern = {}
+    for name, (x, w, ex, N, kw) in shapes.items():
+        fn = getattr(ops, f"llm_{form}{suffix if ex else ''}")
+        y = torch.zeros(M, N, dtype=torch.float16, device=dev)
+        run = lambda: fn(x, w, *ex, out=y, **kw)
+        for _ in range(3):
+            run()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(20):
+            run()
+        e1.record()
+        torch.cuda.synchronize()
+        us = e0.elapsed_time(e1) * 1e3 / 20
+        nbytes = sum(float(t.element_size()) * t.numel() for t in (w,) + tuple(ex))
+        kern[name] = {"N": N, "K": int(x.shape[1]), "weights": str(w.dtype).replace("torch.", ""), "us": round(us, 2),
+                      "GBps": round(nbytes / us / 1e3, 1)}
+    return kern
+
+
+def batched(S):
     embs = [(torch.randn(a.prompt, cfg.hidden_size, device=dev) * 0.5).half() for _ in range(S)]
     rows = []
     for graph in {"both": (True, False), "on": (True,), "off": (False,)}[a.graph]:
@@ -66,31 +103,7 @@ def batched(S):
         r["ms_per_step"] = round((r["seconds"] * 1e3 - prompt_ms) / (a.new - 1), 4)
     best = min(r["ms_per_step"] for r in rows)
     gbs = eng.weight_bytes_per_token() / (best * 1e-3) / 1e9
-    # per-launch times of the new kernel, M = 16, back to back (event pair around 20 launches after 3 warm-up launches)
-    H, I, V = cfg.hidden_size, cfg.intermediate_size, cfg.vocab_size
-    x5, x13 = (torch.randn(16, H, device=dev) * 0.5).half(), (torch.randn(16, I, device=dev) * 0.5).half()
-    y = torch.zeros(16, max(eng.qkv_dim, I, V), dtype=torch.float16, device=dev)
-    w8 = a.weight_dtype == "int8"
-    sc = lambda ss: ss[0] if w8 else None                  # row scales of layer 0 (int8), None: the fp16 kernel
-    shapes = {"qkv": (x5, eng.wqkv[0], sc(eng.sqkv), eng.qkv_dim, dict(rms=True, gain=eng.g_in[0])),
-              "o": (x5, eng.wo[0], sc(eng.so), H, {}),
-              "gate_up": (x5, eng.wgu[0], sc(eng.sgu), I, dict(rms=True, swiglu=True, gain=eng.g_post[0])),
-              "down": (x13, eng.wdown[0], sc(eng.sdown), H, {}), "lm_head": (x5, eng.lm_head, None, V, {})}
-    kern = {}
-    for name, (x, w, s, N, kw) in shapes.items():
-        run = (lambda: ops.llm_gemm16(x, w, out=y, N=N, **kw)) if s is None else \
-              (lambda: ops.llm_gemm16_w8(x, w, s, out=y, N=N, **kw))
-        for _ in range(3):
-            run()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(20):
-            run()
-        e1.record()
-        torch.cuda.synchronize()
-        us = e0.elapsed_time(e1) * 1e3 / 20
-        kern[name] = {"N": N, "K": int(x.shape[1]), "weights": str(w.dtype).replace("torch.", ""), "us": round(us, 2),
-                      "GBps": round(float(w.element_size()) * w.numel() / us / 1e3, 1)}
+    kern = launch_times(S)
     print(json.dumps({"workload": f"LLaMA-2-13B dims x {a.layers} layers, {S} sequences greedy, prompt {a.prompt} + {a.new} new tokens",
                       "weight_dtype": a.weight_dtype,
                       "init_s": round(init_s, 1), "sequences": S, "runs": rows, "prompt_ms": prompt_ms,
@@ -99,7 +112,7 @@ def batched(S):
                       "roofline": {"bound": "hbm", "kernel": "llm_gemm16_kernel", "achieved": round(gbs, 1), "peak": 8000.0,
                                    "unit": "GB/s", "frac": round(gbs / 8000.0, 4),
                                    "note": "whole token step priced against the weight bytes, read once for all sequences"},
-                      "ops_per_step": eng.last_run_info["ops_per_token"], "gemm16_launches_m16": kern}))
+                      "ops_per_step": eng.last_run_info["ops_per_token"], f"gemm16_launches_m{S}": kern}))
 
 
 if a.sequences > 1:
@@ -139,4 +152,5 @@ print(json.dumps({"workload": f"LLaMA-2-13B dims x {a.layers} layers, batch 1 gr
                   "roofline": {"bound": "hbm", "kernel": "llm_gemv_pipe_kernel", "achieved": round(gbs, 1), "peak": 8000.0,
                                "unit": "GB/s", "frac": round(gbs / 8000.0, 4),
                                "note": "whole token step (204 launches) priced against the weight bytes"},
-                  "ops_per_token": eng.last_run_info["ops_per_token"], "gemv_variant": a.gemv_variant}))
+                  "ops_per_token": eng.last_run_info["ops_per_token"], "gemv_variant": a.gemv_variant,
+                  "gemv_launches_m1": launch_times(1)}))
