@@ -27,7 +27,7 @@ OP = dict(GEMM=1, CONV3X3=2, GROUPNORM=3, LAYERNORM=4, SELF_ATTN=5, IP_ATTN=6, C
           PAD_ROWS=17, SMALL_ATTN=18, LLM_GEMV=19, LLM_ATTN=20, LLM_RMSNORM=21, LLM_EMBED=22, LLM_SELECT=23,
           LLM_ADVANCE=24, LN_FINALIZE=27, LLM_GEMM16=28, LLM_ATTN_SLOTS=29, LLM_RMSNORM_SLOTS=30,
           LLM_EMBED_SLOTS=31, LLM_SELECT_SLOTS=32, REDRAW_START=33, LLM_GEMV_W8=34, LLM_GEMM16_W8=35, LORA_MERGE=36, SLOT_START=37,
-          LLM_GEMV_FP4=38, LLM_GEMM16_FP4=39)
+          LLM_GEMV_FP4=38, LLM_GEMM16_FP4=39, LLM_ATTN_KV8=40, LLM_ATTN_SLOTS_KV8=41)
 
 # name -> (restype, argtypes).  Every symbol declared in include/diffsensei_hip.h appears here;
 # tests/test_capi_symbols.py checks the two lists against each other.
@@ -123,6 +123,9 @@ SIGNATURES = {
     "ds_llm_gemm16_fp4": (i32, [vp, i64, vp, vp, i64, vp, i64, i32, i32, i32, i32, vp, i32, f32, vp, vp, vp]),
     "ds_llm_dequant_fp4": (i32, [vp, vp, vp, i64, i32, vp, vp]),
     "ds_llm_attn_slots_f16": (i32, [vp, i64, vp, vp, i64, i64, vp, vp, vp, i64, vp, i32, i32, i32, i32, i32, f32, vp]),
+    "ds_llm_attn_kv8": (i32, [vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, vp, i64, vp, i32, i32, i32, i32, i32, f32, vp]),
+    "ds_llm_attn_slots_kv8": (i32, [vp, i64, vp, vp, i64, i64, vp, vp, i64, i64, vp, vp, vp, i64, vp, i32, i32, i32, i32, i32,
+                                    f32, vp]),
     "ds_llm_rmsnorm_slots_f16": (i32, [vp, i64, vp, vp, i64, vp, vp, i32, i32, i32, f32, vp]),
     "ds_llm_embed_slots_f16": (i32, [vp, vp, vp, i64, i32, i32, i32, vp]),
     "ds_llm_select_slots_f16": (i32, [vp, i64, i32, vp, i32, i32, i32, vp, vp, i32, vp]),

@@ -25,7 +25,7 @@ void ds_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* ds_last_error(void) { return g_err; }
-int ds_version(void) { return 106; }
+int ds_version(void) { return 107; }
 
 int ds_device_info(int* cu_count, int* lds_bytes, char* arch_name, int arch_name_len) {
     int dev = 0;
@@ -510,8 +510,11 @@ constexpr int SEQ = 0, SLOTS = 8;
 static int llm_attn_impl(const void* qkv, int64_t ldqkv, void* kc, void* vc, int64_t ldc, const float* rope_cos,
                          const float* rope_sin, void* out, int64_t ldo, const int32_t* state, int M, int heads,
                          int kv_heads, int D, int T_max, float scale, hipStream_t st, int state_stride = SEQ,
-                         int64_t slot_stride = 0) {
+                         int64_t slot_stride = 0, bool kv8 = false, void* k_exp = nullptr, void* v_exp = nullptr,
+                         int64_t lde = 0, int64_t exp_slot_stride = 0) {
     LlmAttnParams a;
+    a.kv8 = kv8; a.k_exp = reinterpret_cast<uint8_t*>(k_exp); a.v_exp = reinterpret_cast<uint8_t*>(v_exp);
+    a.lde = (long)lde; a.exp_slot_stride = (long)exp_slot_stride;
     a.qkv = H(qkv); a.kc = HM(kc); a.vc = HM(vc); a.rope_cos = rope_cos; a.rope_sin = rope_sin; a.out = HM(out);
     a.state = state; a.ldqkv = ldqkv; a.ldc = ldc; a.ldo = ldo;
     a.M = M; a.heads = heads; a.kv_heads = kv_heads; a.D = D; a.T_max = T_max; a.scale = scale;
@@ -600,6 +603,22 @@ int ds_llm_attn_slots_f16(const void* qkv, int64_t ldqkv, void* k_cache, void* v
                           int slots, int heads, int kv_heads, int D, int T_max, float scale, void* stream) {
     return llm_attn_impl(qkv, ldqkv, k_cache, v_cache, ldc, rope_cos, rope_sin, out, ldo, state, slots, heads, kv_heads, D,
                          T_max, scale, S(stream), SLOTS, slot_stride);
+}
+
+// ---- fp8 KV cache: uint8 e4m3 caches (ldc, slot_stride in bytes) + uint8 exponent arrays [T_max, kv_heads] rows (lde)
+int ds_llm_attn_kv8(const void* qkv, int64_t ldqkv, void* k_cache, void* v_cache, int64_t ldc, void* k_exp, void* v_exp,
+                    int64_t lde, const float* rope_cos, const float* rope_sin, void* out, int64_t ldo, const int32_t* state,
+                    int M, int heads, int kv_heads, int D, int T_max, float scale, void* stream) {
+    return llm_attn_impl(qkv, ldqkv, k_cache, v_cache, ldc, rope_cos, rope_sin, out, ldo, state, M, heads, kv_heads, D,
+                         T_max, scale, S(stream), SEQ, 0, true, k_exp, v_exp, lde, 0);
+}
+
+int ds_llm_attn_slots_kv8(const void* qkv, int64_t ldqkv, void* k_cache, void* v_cache, int64_t ldc, int64_t slot_stride,
+                          void* k_exp, void* v_exp, int64_t lde, int64_t exp_slot_stride, const float* rope_cos,
+                          const float* rope_sin, void* out, int64_t ldo, const int32_t* state, int slots, int heads,
+                          int kv_heads, int D, int T_max, float scale, void* stream) {
+    return llm_attn_impl(qkv, ldqkv, k_cache, v_cache, ldc, rope_cos, rope_sin, out, ldo, state, slots, heads, kv_heads, D,
+                         T_max, scale, S(stream), SLOTS, slot_stride, true, k_exp, v_exp, lde, exp_slot_stride);
 }
 
 int ds_llm_rmsnorm_slots_f16(const void* x, int64_t ldx, const void* gamma, void* y, int64_t ldy, void* feat,
@@ -933,6 +952,14 @@ static int run_op(const ds_op& o, hipStream_t st) {
             return llm_attn_impl(p[0], l[0], p[1], p[2], l[1], reinterpret_cast<const float*>(p[3]),
                                  reinterpret_cast<const float*>(p[4]), p[5], l[2], reinterpret_cast<const int32_t*>(p[6]),
                                  i[0], i[1], i[2], i[3], i[4], o.f[0], st, SLOTS, l[3]);
+        case DS_OP_LLM_ATTN_KV8:
+            return llm_attn_impl(p[0], l[0], p[1], p[2], l[1], reinterpret_cast<const float*>(p[3]),
+                                 reinterpret_cast<const float*>(p[4]), p[5], l[2], reinterpret_cast<const int32_t*>(p[6]),
+                                 i[0], i[1], i[2], i[3], i[4], o.f[0], st, SEQ, 0, true, p[7], p[8], l[4], 0);
+        case DS_OP_LLM_ATTN_SLOTS_KV8:
+            return llm_attn_impl(p[0], l[0], p[1], p[2], l[1], reinterpret_cast<const float*>(p[3]),
+                                 reinterpret_cast<const float*>(p[4]), p[5], l[2], reinterpret_cast<const int32_t*>(p[6]),
+                                 i[0], i[1], i[2], i[3], i[4], o.f[0], st, SLOTS, l[3], true, p[7], p[8], l[4], l[5]);
         case DS_OP_LLM_RMSNORM_SLOTS:
             return ds_launch_llm_rmsnorm(H(p[0]), l[0], H(p[1]), HM(p[2]), l[1], HM(p[3]),
                                          reinterpret_cast<const int*>(p[4]), SLOTS, i[0], i[1], i[2], o.f[0], st);
@@ -1021,6 +1048,11 @@ int ds_op_describe(const ds_op* op, char* name, int name_len, double* flops, dou
             break;
         case DS_OP_LLM_ATTN:
         case DS_OP_LLM_ATTN_SLOTS: nm = "llm_attn_kernel"; break;
+        case DS_OP_LLM_ATTN_KV8:      // the fp8 cache read once at its full length (an upper bound: the length is device state):
+        case DS_OP_LLM_ATTN_SLOTS_KV8:   // D code bytes + 1 exponent byte per (row, kv head), for K and for V, per sequence
+            nm = "llm_attn_kernel";
+            by = 2.0 * (op->code == DS_OP_LLM_ATTN_SLOTS_KV8 ? i[0] : 1) * (double)i[4] * i[2] * (i[3] + 1.0);
+            break;
         case DS_OP_LLM_RMSNORM:
         case DS_OP_LLM_RMSNORM_SLOTS: nm = "llm_rmsnorm_kernel"; by = 4.0 * i[0] * (double)i[1]; break;
         case DS_OP_LLM_SELECT_SLOTS: nm = "llm_select_kernel"; by = 2.0 * i[0] * (double)i[4]; break;

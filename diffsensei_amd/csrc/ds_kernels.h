@@ -342,6 +342,15 @@ struct LlmAttnParams {
     float scale = 1.0f;
     long slot_stride = 0;              // elements between the caches of two rows (slot form; 0 in the one-sequence form)
     int state_stride = 0;              // 0 | 8, see above
+    int kv8 = 0;
+    // fp8 KV cache (kv8 = 1): kc / vc point at uint8 caches of OCP e4m3 codes with the same [T_max, kv_heads*D] rows (ldc
+    // and slot_stride then count bytes), k_exp / v_exp at uint8 [T_max, kv_heads] rows (lde) of one biased exponent per (row,
+    // kv head): value = f32(e4m3) * 2^(exp - 127), exp - 127 the smallest integer that brings the head's largest magnitude to
+    // <= 448 (0 for an all-zero head).  Every key and value, the chunk's own rows included, is seen through that quantiser.
+    uint8_t* k_exp = nullptr;
+    uint8_t* v_exp = nullptr;
+    long lde = 0;
+    long exp_slot_stride = 0;          // bytes between the exponent arrays of two rows (slot form)
 };
 int ds_launch_llm_attn(const LlmAttnParams& p, hipStream_t stream);
 int ds_launch_llm_rmsnorm(const half_t* x, long ldx, const half_t* gamma, half_t* y, long ldy, half_t* feat,

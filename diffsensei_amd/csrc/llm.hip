@@ -251,7 +251,50 @@ __device__ __forceinline__ void rope_chunk(const half_t* row, int c, const float
 
 constexpr int ATT_WAVES = 16;  // one key group per wavefront per iteration: the loop is a chain of dependent loads
 
+// ---- fp8 KV cache (LlmAttnParams::k_exp): OCP e4m3 codes and one biased power-of-two exponent per (row, kv head).
+// 2^(e - 127) of an exponent byte: the quantiser stores 94 .. 135, always the exponent field of a normal float
+__device__ __forceinline__ float kv8_scale(unsigned e) { return __uint_as_float(e << 23); }
+
+// 8 codes (two dwords, element 0 in the lowest byte) -> their e4m3 values in fp32, unscaled
+__device__ __forceinline__ void kv8_unpack(const uint2 c, float out[8]) {
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    const f2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)c.x, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)c.x, true);
+    const f2 d = __builtin_amdgcn_cvt_pk_f32_fp8((int)c.y, false), e = __builtin_amdgcn_cvt_pk_f32_fp8((int)c.y, true);
+    out[0] = a[0]; out[1] = a[1]; out[2] = b[0]; out[3] = b[1];
+    out[4] = d[0]; out[5] = d[1]; out[6] = e[0]; out[7] = e[1];
+}
+
+// The quantiser (diffsensei_amd/mllm.py: quantize_kv_fp8) on a head whose D values (fp16 numbers held in fp32) lie 8 per
+// lane over D/8 neighbouring lanes, all of them active: amax over the head with the score loop's shuffle pattern; the
+// exponent from the bits of amax = 1.f 2^(E-127): ex = E - 135 if 1.f <= 1.75 (amax / 2^ex <= 448) else E - 134, so the
+// stored byte ex + 127 is the exponent field of amax + 0x1FFFFF, minus 8 (127 for an all-zero head); x 2^-ex is exact and
+// at most 448, so the one rounding is v_cvt_pk_fp8_f32's (nearest even, subnormals kept) and nothing saturates.
 template <int D>
+__device__ __forceinline__ unsigned kv8_quantize(const float x[8], uint2& codes) {
+    constexpr int LPK = D / 8;
+    float a = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) a = fmaxf(a, fabsf(x[e]));
+#pragma unroll
+    for (int o = 1; o < LPK; o <<= 1) a = fmaxf(a, __shfl_xor(a, o, 64));
+    const unsigned bits = __float_as_uint(a);
+    const unsigned eb = bits ? ((bits + 0x1FFFFFu) >> 23) - 8u : 127u;
+    const float inv = __uint_as_float((254u - eb) << 23);     // 2^-ex
+    int lo = 0, hi = 0;
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(x[0] * inv, x[1] * inv, lo, false);
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(x[2] * inv, x[3] * inv, lo, true);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(x[4] * inv, x[5] * inv, hi, false);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(x[6] * inv, x[7] * inv, hi, true);
+    codes = make_uint2((unsigned)lo, (unsigned)hi);
+    return eb;
+}
+
+// KV8: the fp8-cache form (ds_kernels.h).  Same score / softmax / P V loop; a key or value is 8 code bytes per lane and
+// the exponent byte of its (row, kv head) - a load of its own, beside the codes' and not behind it - and the power of two
+// multiplies the finished dot product (keys) or the probability (values), so the conversion adds nothing to the loop's
+// chain of dependent loads.  The chunk's own rows go through kv8_quantize in registers and then through the same
+// arithmetic as a cached row: a row's result does not depend on how the prompt was cut into chunks.
+template <int D, bool KV8>
 __device__ __forceinline__ void llm_attn_body(const LlmAttnParams& p, const int h, const int r) {
     constexpr int LPK = D / 8, KPW = 64 / LPK, HALF = D / 2;
     // The state row first: the length every block starts from and, beside it, the flag only the slot form uses - one round
@@ -273,6 +316,8 @@ __device__ __forceinline__ void llm_attn_body(const LlmAttnParams& p, const int 
     if ((T > p.T_max) | ((p.state_stride != 0) & (finished != 0))) return;
     const long kcol = (long)(p.heads + hkv) * D, vcol = (long)(p.heads + p.kv_heads + hkv) * D;
     const half_t* qrow = p.qkv + (long)r * p.ldqkv;
+    uint8_t* const kc8 = reinterpret_cast<uint8_t*>(p.kc);     // KV8: the caches hold bytes
+    uint8_t* const vc8 = reinterpret_cast<uint8_t*>(p.vc);
 
     float qf[8];
     rope_chunk<D>(qrow + (long)h * D, c, p.rope_cos + (long)(pos0 + r) * HALF, p.rope_sin + (long)(pos0 + r) * HALF, qf);
@@ -281,24 +326,36 @@ __device__ __forceinline__ void llm_attn_body(const LlmAttnParams& p, const int 
     float mx = -3.0e38f;
     for (int g = wave; g * KPW < T; g += ATT_WAVES) {
         const int j = g * KPW + ks;
-        float s = 0.f;
+        float s = 0.f, ksc = 1.0f;
         if (j < T) {
             float kf[8];
             if (j < pos0) {
-                const h8 kv = *reinterpret_cast<const h8*>(p.kc + (long)j * p.ldc + (long)hkv * D + 8 * c);
+                if constexpr (KV8) {
+                    const uint2 kv = *reinterpret_cast<const uint2*>(kc8 + (long)j * p.ldc + (long)hkv * D + 8 * c);
+                    ksc = kv8_scale(p.k_exp[(long)j * p.lde + hkv]);
+                    kv8_unpack(kv, kf);
+                } else {
+                    const h8 kv = *reinterpret_cast<const h8*>(p.kc + (long)j * p.ldc + (long)hkv * D + 8 * c);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) kf[e] = (float)kv[e];
+                    for (int e = 0; e < 8; ++e) kf[e] = (float)kv[e];
+                }
             } else {
                 rope_chunk<D>(p.qkv + (long)(j - pos0) * p.ldqkv + kcol, c, p.rope_cos + (long)j * HALF,
                               p.rope_sin + (long)j * HALF, kf);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) kf[e] = (float)(half_t)kf[e];  // same rounding as the cached copy
+                if constexpr (KV8) {    // and the same codes: all LPK lanes of a key take this branch together
+                    uint2 kv;
+                    ksc = kv8_scale(kv8_quantize<D>(kf, kv));
+                    kv8_unpack(kv, kf);
+                }
             }
 #pragma unroll
             for (int e = 0; e < 8; ++e) s = fmaf(qf[e], kf[e], s);
         }
 #pragma unroll
         for (int o = 1; o < LPK; o <<= 1) s += __shfl_xor(s, o, 64);
+        if constexpr (KV8) s *= ksc;
         s *= p.scale;
         if (j < T) {
             if (c == 0) sc[j] = s;
@@ -331,12 +388,32 @@ __device__ __forceinline__ void llm_attn_body(const LlmAttnParams& p, const int 
     for (int g = wave; g * KPW < T; g += ATT_WAVES) {
         const int j = g * KPW + ks;
         if (j < T) {
-            const float pj = (float)(half_t)(sc[j] * inv);  // the reference casts the probabilities to fp16
-            const half_t* vp = (j < pos0) ? p.vc + (long)j * p.ldc + (long)hkv * D + 8 * c
-                                          : p.qkv + (long)(j - pos0) * p.ldqkv + vcol + 8 * c;
-            const h8 vv = *reinterpret_cast<const h8*>(vp);
+            float pj = (float)(half_t)(sc[j] * inv);  // the reference casts the probabilities to fp16
+            if constexpr (KV8) {
+                uint2 vv;
+                unsigned eb;
+                if (j < pos0) {
+                    vv = *reinterpret_cast<const uint2*>(vc8 + (long)j * p.ldc + (long)hkv * D + 8 * c);
+                    eb = p.v_exp[(long)j * p.lde + hkv];
+                } else {
+                    const h8 vh = *reinterpret_cast<const h8*>(p.qkv + (long)(j - pos0) * p.ldqkv + vcol + 8 * c);
+                    float vx[8];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) acc[e] = fmaf(pj, (float)vv[e], acc[e]);
+                    for (int e = 0; e < 8; ++e) vx[e] = (float)vh[e];
+                    eb = kv8_quantize<D>(vx, vv);
+                }
+                float vf[8];
+                kv8_unpack(vv, vf);
+                pj *= kv8_scale(eb);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[e] = fmaf(pj, vf[e], acc[e]);
+            } else {
+                const half_t* vp = (j < pos0) ? p.vc + (long)j * p.ldc + (long)hkv * D + 8 * c
+                                              : p.qkv + (long)(j - pos0) * p.ldqkv + vcol + 8 * c;
+                const h8 vv = *reinterpret_cast<const h8*>(vp);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[e] = fmaf(pj, (float)vv[e], acc[e]);
+            }
         }
     }
 #pragma unroll
@@ -363,8 +440,26 @@ __device__ __forceinline__ void llm_attn_body(const LlmAttnParams& p, const int 
 #pragma unroll
         for (int e = 0; e < 8; ++e) ko[e] = (half_t)kf[e];
         const long off = (long)(pos0 + r) * p.ldc + (long)hkv * D + 8 * c;
-        *reinterpret_cast<h8*>(p.kc + off) = ko;
-        *reinterpret_cast<h8*>(p.vc + off) = *reinterpret_cast<const h8*>(qrow + vcol + 8 * c);
+        if constexpr (KV8) {    // lanes 0 .. LPK-1 of wavefront 0 hold the head: codes with vector stores, one exponent byte each
+            const h8 vo = *reinterpret_cast<const h8*>(qrow + vcol + 8 * c);
+            float vf[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                kf[e] = (float)ko[e];
+                vf[e] = (float)vo[e];
+            }
+            uint2 k8, v8;
+            const unsigned ek = kv8_quantize<D>(kf, k8), ev = kv8_quantize<D>(vf, v8);
+            *reinterpret_cast<uint2*>(kc8 + off) = k8;
+            *reinterpret_cast<uint2*>(vc8 + off) = v8;
+            if (c == 0) {
+                p.k_exp[(long)(pos0 + r) * p.lde + hkv] = (uint8_t)ek;
+                p.v_exp[(long)(pos0 + r) * p.lde + hkv] = (uint8_t)ev;
+            }
+        } else {
+            *reinterpret_cast<h8*>(p.kc + off) = ko;
+            *reinterpret_cast<h8*>(p.vc + off) = *reinterpret_cast<const h8*>(qrow + vcol + 8 * c);
+        }
     }
 }
 
@@ -374,15 +469,22 @@ __device__ __forceinline__ void llm_attn_body(const LlmAttnParams& p, const int 
 // Only the slot form looks at the finished flag - a finished (or never started) slot returns before it touches anything;
 // the one-sequence form never did (the prompt cursor has the flag at zero), hence the `state_stride != 0 &` in the body's
 // early-out.
-template <int D>
+template <int D, bool KV8>
 __global__ __launch_bounds__(64 * ATT_WAVES) void llm_attn_kernel(LlmAttnParams p) {
     const int s = p.state_stride ? blockIdx.y : 0;   // rows in front of this block's row that are other sequences
     p.state += p.state_stride * s;
     p.qkv += (long)s * p.ldqkv;
     p.out += (long)s * p.ldo;
-    p.kc += (long)s * p.slot_stride;
-    p.vc += (long)s * p.slot_stride;
-    llm_attn_body<D>(p, blockIdx.x, blockIdx.y - s);
+    if constexpr (KV8) {                             // byte caches: the slot stride counts bytes
+        p.kc = reinterpret_cast<half_t*>(reinterpret_cast<uint8_t*>(p.kc) + (long)s * p.slot_stride);
+        p.vc = reinterpret_cast<half_t*>(reinterpret_cast<uint8_t*>(p.vc) + (long)s * p.slot_stride);
+        p.k_exp += (long)s * p.exp_slot_stride;
+        p.v_exp += (long)s * p.exp_slot_stride;
+    } else {
+        p.kc += (long)s * p.slot_stride;
+        p.vc += (long)s * p.slot_stride;
+    }
+    llm_attn_body<D, KV8>(p, blockIdx.x, blockIdx.y - s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1184,10 +1286,23 @@ int ds_launch_llm_attn(const LlmAttnParams& p, hipStream_t stream) {
         DS_REQUIRE(p.slot_stride % 8 == 0 && p.slot_stride >= (long)p.T_max * p.ldc, "llm_attn: slot stride %ld < T_max * ldc",
                    p.slot_stride);
     else DS_REQUIRE(p.slot_stride == 0, "llm_attn: the one-sequence form has one cache (slot stride %ld)", p.slot_stride);
+    if (p.kv8) {
+        DS_REQUIRE(p.k_exp && p.v_exp, "llm_attn: the fp8 cache needs both exponent arrays");
+        DS_REQUIRE(p.ldc >= (long)p.kv_heads * p.D && p.lde >= p.kv_heads, "llm_attn: fp8 cache rows ldc %ld / lde %ld < kv_heads",
+                   p.ldc, p.lde);
+        if (p.state_stride)
+            DS_REQUIRE(p.exp_slot_stride >= (long)p.T_max * p.lde, "llm_attn: exponent slot stride %ld < T_max * lde",
+                       p.exp_slot_stride);
+        else DS_REQUIRE(p.exp_slot_stride == 0, "llm_attn: the one-sequence form has one exponent array (slot stride %ld)",
+                        p.exp_slot_stride);
+    } else DS_REQUIRE(!p.k_exp && !p.v_exp, "llm_attn: exponent arrays belong to the fp8 cache form");
     const size_t lds = (size_t)(p.T_max + ATT_WAVES * p.D + 2 * ATT_WAVES) * sizeof(float);
     const dim3 grid(p.heads, p.M);
-    if (p.D == 128) hipLaunchKernelGGL(llm_attn_kernel<128>, grid, dim3(64 * ATT_WAVES), lds, stream, p);
-    else hipLaunchKernelGGL(llm_attn_kernel<64>, grid, dim3(64 * ATT_WAVES), lds, stream, p);
+    const dim3 block(64 * ATT_WAVES);
+    if (p.D == 128 && p.kv8) hipLaunchKernelGGL((llm_attn_kernel<128, true>), grid, block, lds, stream, p);
+    else if (p.D == 128) hipLaunchKernelGGL((llm_attn_kernel<128, false>), grid, block, lds, stream, p);
+    else if (p.kv8) hipLaunchKernelGGL((llm_attn_kernel<64, true>), grid, block, lds, stream, p);
+    else hipLaunchKernelGGL((llm_attn_kernel<64, false>), grid, block, lds, stream, p);
     DS_LAUNCH_CHECK();
     return 0;
 }

@@ -45,6 +45,19 @@ a quarter of the fp16 bytes plus 1/32 for the block exponents.  The token step r
 exactly); the prompt pass dequantises through `llm_dequant_fp4_kernel`.  Everything else is as for int8, opt-in included.
 On Gaussian weights the format's relative rms error is 11 % (int8 per row: 0.9 %); no parity figure for a trained 13B
 checkpoint can be produced offline, so what the mode does to the agent's output quality is not measured.
+
+FP8 KV cache (`LlamaDecodeEngine(kv_dtype="fp8")`, independent of `weight_dtype`): every cache row and kv head is stored as
+head_dim OCP e4m3 codes and one exponent byte (`quantize_kv_fp8`: value = f32(e4m3) * 2^(e - 127), the exponent the smallest
+that brings the head's largest magnitude to <= 448, so the scaling is exact and the one rounding is fp32 -> e4m3), K after
+the rotation and its rounding to fp16, V as projected.  A slot then costs 2 x layers x T_max x kv_heads x (head_dim + 1)
+bytes, (head_dim + 1) / (2 head_dim) = 0.504 of the fp16 cache at head_dim 128: 0.42 GB per slot and 6.8 GB for 16 slots at
+13B dimensions and T_max 1024 (`kv_cache_bytes()`).  The token step and the prompt pass run the fp8-cache forms of the
+attention op (`DS_OP_LLM_ATTN_KV8` / `DS_OP_LLM_ATTN_SLOTS_KV8`: `v_cvt_pk_f32_fp8` unpacks two codes per instruction, the
+power of two multiplies the finished score or the probability); every key and value, the launch's own rows included, is
+seen through the quantiser, so the result is attention over the dequantised cache whatever the chunking.  Opt-in: the
+default stays fp16, bit for bit.  A quantised mode with its own error (2.6 % relative rms on Gaussian heads; on the tiny test
+model the fed-back hidden states move by 2.2e-2 of max|ref| and the greedy ids stay the same); what it does to a trained 13B
+checkpoint's output cannot be measured offline and is not measured.  Decode rate: `profiles/mllm_kv8_decode.txt`.
 """
 from __future__ import annotations
 
@@ -191,12 +204,44 @@ def dequantize_rows_mxfp4(q: Tensor, e: Tensor, s: Tensor) -> Tensor:
     return v * s.to(torch.float32)[:, None]
 
 
+KV8_MAX = 448.0                                              # largest finite OCP e4m3fn value
+
+
+def quantize_kv_fp8(x: Tensor):
+    """The fp8 KV-cache format of heads [..., D] -> (codes uint8 [..., D], exponents uint8 [...]) with
+    x ~ f32(e4m3(codes)) * 2^(exponents - 127).  `x` is first rounded to fp16 (what the fp16 cache holds: the rotated key,
+    the value as projected), then per head: amax = its largest magnitude = m 2^k with m in [0.5, 1); ex = k - 9 if m <= 0.875
+    else k - 8 - the smallest integer with amax / 2^ex <= 448 - and 0 for an all-zero head (for fp16 input ex lies in
+    [-33, 8]: no clamp); the codes are x / 2^ex (exact: a power of two) rounded once, fp32 -> OCP e4m3fn, to nearest even with
+    subnormals kept.  Nothing saturates, since no scaled value exceeds 448 (`to(torch.float8_e4m3fn)` would return NaN above
+    464).  The exponent is stored biased, e = ex + 127.  Works on host and device tensors; everything is per head, so
+    quantising stacked heads equals stacking the quantised ones.  The kernels compute the same bits (csrc/llm.hip:
+    kv8_quantize).  On Gaussian heads the relative rms error is 2.6 %; what the format does to a trained 13B checkpoint's
+    output cannot be measured offline."""
+    if x.dim() < 1:
+        raise ValueError("quantize_kv_fp8 takes heads [..., D]")
+    x = x.detach().to(torch.float16).to(torch.float32)
+    amax = x.abs().amax(dim=-1)
+    m, k = torch.frexp(amax)
+    ex = k.to(torch.int32) - torch.where(m <= 0.875, 9, 8).to(torch.int32)
+    ex = torch.where(amax > 0, ex, torch.zeros_like(ex))
+    y = torch.ldexp(x, -ex[..., None])                              # exact: a power of two
+    codes = y.to(torch.float8_e4m3fn).view(torch.uint8)
+    return codes.contiguous(), (ex + 127).to(torch.uint8).contiguous()
+
+
+def dequantize_kv_fp8(codes: Tensor, exps: Tensor) -> Tensor:
+    """fp32 [..., D] = f32(e4m3(codes)) * 2^(exps - 127): exact (what the fp8-cache attention computes with)."""
+    v = codes.contiguous().view(torch.float8_e4m3fn).to(torch.float32)
+    return torch.ldexp(v, (exps.to(torch.int32) - 127)[..., None])
+
+
 class LlamaDecodeEngine:
     """Device-resident LLaMA decoder + KV cache + the captured one-token launch plan."""
 
     def __init__(self, cfg: LlamaConfig, sd: Dict[str, Tensor], device, max_positions: int = 1024,
                  max_new_tokens: int = 512, use_graph: bool = True, poll_every: int = 8, prompt_path: str = "mfma",
-                 max_sequences: int = 1, weight_dtype: str = "float16"):
+                 max_sequences: int = 1, weight_dtype: str = "float16", kv_dtype: str = "float16"):
         """max_sequences S > 1: `generate_batch` decodes up to S sequences per weight pass; the engine then holds S KV-cache
         slots (each 2 x layers x max_positions x kv_heads x head_dim fp16: 0.84 GB at 13B dimensions and 1024 positions)
         and [S] state / id / feature / logits rows.  `generate` is one sequence in slot 0, whatever S is.
@@ -204,8 +249,14 @@ class LlamaDecodeEngine:
         weight_dtype "int8": the q|k|v, o, gate|up and down matrices are held as int8 with fp32 row scales (W8A16, see
         `quantize_rows_int8`); the embedding, lm_head and the RMSNorm gains stay fp16.
         weight_dtype "mxfp4": the same matrices as MXFP4 (W4A16, see `quantize_rows_mxfp4`): packed e2m1 [N, K/2], block
-        exponents [N, K/32] and fp32 row scales.  Its effect on a trained checkpoint's output is not measured."""
+        exponents [N, K/32] and fp32 row scales.  Its effect on a trained checkpoint's output is not measured.
+        kv_dtype "fp8": the KV cache holds OCP e4m3 codes and one power-of-two exponent byte per (row, kv head) (see
+        `quantize_kv_fp8`): (head_dim + 1) / (2 head_dim) of the fp16 cache's bytes, and attention over the dequantised
+        cache.  Independent of weight_dtype.  Its effect on a trained checkpoint's output is not measured either."""
         _lib.load()
+        if kv_dtype not in ("float16", "fp8"):
+            raise ValueError(f"kv_dtype {kv_dtype!r}: 'float16' or 'fp8'")
+        self.kv_dtype = kv_dtype
         if weight_dtype not in ("float16", "int8", "mxfp4"):
             raise ValueError(f"weight_dtype {weight_dtype!r}: 'float16', 'int8' or 'mxfp4'")
         self.weight_dtype = weight_dtype
@@ -272,8 +323,12 @@ class LlamaDecodeEngine:
         self.act = E(CHUNK, I)
         # per slot: KV cache [S, T_max, kv_heads*D] per layer, state block, generated ids, fed-back hidden states, final-norm
         # row and logits.  `generate` uses slot 0.
-        self.kcs = [E(S, self.T_max, Hkv * D) for _ in range(L)]
-        self.vcs = [E(S, self.T_max, Hkv * D) for _ in range(L)]
+        # kv_dtype "fp8": the caches hold code bytes, and kes / ves [S, T_max, kv_heads] the exponent byte of every head
+        kv_t = torch.uint8 if kv_dtype == "fp8" else torch.float16
+        self.kcs = [E(S, self.T_max, Hkv * D, dtype=kv_t) for _ in range(L)]
+        self.vcs = [E(S, self.T_max, Hkv * D, dtype=kv_t) for _ in range(L)]
+        self.kes = [E(S, self.T_max, Hkv, dtype=torch.uint8) for _ in range(L)] if kv_dtype == "fp8" else []
+        self.ves = [E(S, self.T_max, Hkv, dtype=torch.uint8) for _ in range(L)] if kv_dtype == "fp8" else []
         self.state = E(S, 8, dtype=torch.int32)
         self.state[:, 2] = 1                                # no slot started: every per-slot kernel skips it
         self.out_ids, self.feats = E(S, self.cap, dtype=torch.int32), E(S, self.cap, H)
@@ -304,6 +359,11 @@ class LlamaDecodeEngine:
             return n + ne + 4 * ns + 2 * (self.lm_head.numel() + self.cfg.hidden_size)
         return 2 * (n + self.lm_head.numel() + self.cfg.hidden_size)
 
+    def kv_cache_bytes(self) -> int:
+        """Bytes of the KV cache over all slots and layers: 2 x layers x S x T_max x kv_heads x head_dim fp16 values, or -
+        kv_dtype "fp8" - (head_dim + 1) bytes per (row, kv head) for K and for V: the codes and the exponent byte."""
+        return sum(t.numel() * t.element_size() for ts in (self.kcs, self.vcs, self.kes, self.ves) for t in ts)
+
     def tensors(self) -> List[Tensor]:
         """Frozen weights in kernel layout (the multi-GPU weight broadcast list)."""
         return ([self.embed, self.lm_head, self.norm_g] + self.wqkv + self.wo + self.wgu + self.wdown + self.g_in + self.g_post
@@ -332,12 +392,19 @@ class LlamaDecodeEngine:
         c = self.cfg
         H, I, D, Hq, Hkv = c.hidden_size, c.intermediate_size, c.head_dim, c.num_attention_heads, c.kv_heads
         sq, so, sg, sd_ = self._scales(l)
+        kv8 = self.kv_dtype == "fp8"
+        al = (self.qkv_dim, Hkv * D, Hq * D)                                  # ldqkv, ldc, ldo; then the slot stride
+        if kv8:                                                               # fp8 cache: l[4] = lde, l[5] = the exponents' slot stride
+            al += (self.kcs[l].stride(0) if slots else 0, Hkv) + ((self.kes[l].stride(0),) if slots else ())
+        elif slots:
+            al += (self.kcs[l].stride(0),)
         return [
             self._proj(proj, self.wqkv[l], sq, (M, self.qkv_dim, H, 1, 0), (H, self.qkv_dim, 0),
                        (self.h, self.qkv, None, self.g_in[l])),
-            make_op("LLM_ATTN_SLOTS" if slots else "LLM_ATTN", i=(M, Hq, Hkv, D, self.T_max), f=(1.0 / math.sqrt(D),),
-                    l=(self.qkv_dim, Hkv * D, Hq * D) + ((self.kcs[l].stride(0),) if slots else ()),
-                    p=(self.qkv, self.kcs[l], self.vcs[l], self.rope_cos, self.rope_sin, self.att, self.state)),
+            make_op(("LLM_ATTN_SLOTS" if slots else "LLM_ATTN") + ("_KV8" if kv8 else ""), i=(M, Hq, Hkv, D, self.T_max),
+                    f=(1.0 / math.sqrt(D),), l=al,
+                    p=(self.qkv, self.kcs[l], self.vcs[l], self.rope_cos, self.rope_sin, self.att, self.state)
+                    + ((self.kes[l], self.ves[l]) if kv8 else ())),
             self._proj(proj, self.wo[l], so, (M, H, Hq * D, 0, 0), (Hq * D, H, H), (self.att, self.h, self.h, None)),
             self._proj(proj, self.wgu[l], sg, (M, I, H, 1, 1), (H, I, 0), (self.h, self.act, None, self.g_post[l])),
             self._proj(proj, self.wdown[l], sd_, (M, H, I, 0, 0), (I, H, H), (self.act, self.h, self.h, None)),
@@ -412,7 +479,8 @@ class LlamaDecodeEngine:
         out = self._decode([inputs_embeds], [int(last_prompt_id)], [int(eos_token_id)], [int(max_new_tokens)], [0], width=1)
         info = self.last_run_info
         self.last_run_info = {"graph": info["graph"], "prompt_tokens": info["prompt_tokens"][0], "new_tokens": info["new_tokens"][0],
-                              "token_steps_launched": info["token_steps_launched"], "ops_per_token": info["ops_per_token"]}
+                              "token_steps_launched": info["token_steps_launched"], "ops_per_token": info["ops_per_token"],
+                              "kv_dtype": info["kv_dtype"]}
         return out[0]
 
     @torch.no_grad()
@@ -497,7 +565,7 @@ class LlamaDecodeEngine:
                 out.append({"ids": self.out_ids[s, :k].to(torch.int64), "hidden": self.feats[s, :max(k - 1, 0)].clone()})
         torch.cuda.current_stream(dev).wait_stream(st)
         self.last_run_info = {"graph": graph, "sequences": len(embs), "prompt_tokens": T0s, "new_tokens": [len(o["ids"]) for o in out],
-                              "token_steps_launched": steps, "ops_per_token": tok.n}
+                              "token_steps_launched": steps, "ops_per_token": tok.n, "kv_dtype": self.kv_dtype}
         return out
 
     def _w(self, ws: list, ss: list, l: int, es: Sequence[Tensor] = ()) -> Tensor:
@@ -535,8 +603,12 @@ class LlamaDecodeEngine:
                 pf.zero_()                                                   # chunk cursor of this slot's cache
                 for r0 in range(starts[i], starts[i + 1], CHUNK):
                     m = min(CHUNK, starts[i + 1] - r0)
-                    ops.llm_attention(qkv[r0:r0 + m], self.kcs[l][s], self.vcs[l][s], self.rope_cos, self.rope_sin, pf,
-                                      Hq, Hkv, scale, out=att[r0:r0 + m])
+                    if self.kv_dtype == "fp8":
+                        ops.llm_attention_kv8(qkv[r0:r0 + m], self.kcs[l][s], self.vcs[l][s], self.kes[l][s], self.ves[l][s],
+                                              self.rope_cos, self.rope_sin, pf, Hq, Hkv, scale, out=att[r0:r0 + m])
+                    else:
+                        ops.llm_attention(qkv[r0:r0 + m], self.kcs[l][s], self.vcs[l][s], self.rope_cos, self.rope_sin, pf,
+                                          Hq, Hkv, scale, out=att[r0:r0 + m])
                     ops.llm_advance(pf, m)
             h = ops.gemm(att, self._w(self.wo, self.so, l, self.eo), residual=h)
             xn = ops.llm_rmsnorm(h, self.g_post[l], eps)

@@ -1180,6 +1180,58 @@ def llm_attention_slots(qkv: Tensor, k_cache: Tensor, v_cache: Tensor, rope_cos:
     return out
 
 
+def _chk_kv8(k_cache: Tensor, v_cache: Tensor, k_exp: Tensor, v_exp: Tensor, lead: tuple, kv_heads: int, D: int) -> None:
+    _chk(k_cache, v_cache, k_exp, v_exp, dtype=torch.uint8)
+    if tuple(k_cache.shape) != lead + (kv_heads * D,) or v_cache.shape != k_cache.shape:
+        raise ValueError(f"fp8 caches must be uint8 {lead + (kv_heads * D,)}, got {tuple(k_cache.shape)} / {tuple(v_cache.shape)}")
+    if tuple(k_exp.shape) != lead + (kv_heads,) or v_exp.shape != k_exp.shape:
+        raise ValueError(f"cache exponents must be uint8 {lead + (kv_heads,)} (one per row and kv head), got "
+                         f"{tuple(k_exp.shape)} / {tuple(v_exp.shape)}")
+
+
+def llm_attention_kv8(qkv: Tensor, k_cache: Tensor, v_cache: Tensor, k_exp: Tensor, v_exp: Tensor, rope_cos: Tensor,
+                      rope_sin: Tensor, state: Tensor, heads: int, kv_heads: int, scale: float,
+                      out: Optional[Tensor] = None) -> Tensor:
+    """`llm_attention` on the fp8 KV cache (mllm.quantize_kv_fp8): caches uint8 [T_max, kv_heads*D] of e4m3 codes, exponents
+    uint8 [T_max, kv_heads]; appends the codes and exponent bytes of the M rows at state[0].. and attends over the dequantised
+    cache, the rows of this launch included."""
+    _chk(qkv)
+    _chk(rope_cos, rope_sin, dtype=torch.float32)
+    _chk(state, dtype=torch.int32)
+    M = qkv.shape[0]
+    D = qkv.shape[1] // (heads + 2 * kv_heads)
+    T_max = k_cache.shape[0]
+    _chk_kv8(k_cache, v_cache, k_exp, v_exp, (T_max,), kv_heads, D)
+    assert rope_cos.shape == (T_max, D // 2)
+    if out is None:
+        out = torch.empty((M, heads * D), dtype=torch.float16, device=qkv.device)
+    check(_lib.load().ds_llm_attn_kv8(_p(qkv), qkv.shape[1], _p(k_cache), _p(v_cache), k_cache.shape[1], _p(k_exp), _p(v_exp),
+                                      kv_heads, _p(rope_cos), _p(rope_sin), _p(out), heads * D, _p(state), M, heads, kv_heads,
+                                      D, T_max, scale, _stream()), "ds_llm_attn_kv8")
+    return out
+
+
+def llm_attention_slots_kv8(qkv: Tensor, k_cache: Tensor, v_cache: Tensor, k_exp: Tensor, v_exp: Tensor, rope_cos: Tensor,
+                            rope_sin: Tensor, state: Tensor, heads: int, kv_heads: int, scale: float,
+                            out: Optional[Tensor] = None) -> Tensor:
+    """`llm_attention_slots` on the fp8 KV cache: caches uint8 [S, T_max, kv_heads*D], exponents uint8 [S, T_max, kv_heads]."""
+    _chk(qkv)
+    _chk(rope_cos, rope_sin, dtype=torch.float32)
+    _chk(state, dtype=torch.int32)
+    S = qkv.shape[0]
+    D = qkv.shape[1] // (heads + 2 * kv_heads)
+    T_max = k_cache.shape[1]
+    _chk_kv8(k_cache, v_cache, k_exp, v_exp, (S, T_max), kv_heads, D)
+    assert state.shape == (S, 8) and rope_cos.shape == (T_max, D // 2)
+    if out is None:
+        out = torch.empty((S, heads * D), dtype=torch.float16, device=qkv.device)
+    check(_lib.load().ds_llm_attn_slots_kv8(_p(qkv), qkv.shape[1], _p(k_cache), _p(v_cache), k_cache.shape[2], k_cache.stride(0),
+                                            _p(k_exp), _p(v_exp), kv_heads, k_exp.stride(0), _p(rope_cos), _p(rope_sin),
+                                            _p(out), heads * D, _p(state), S, heads, kv_heads, D, T_max, scale, _stream()),
+          "ds_llm_attn_slots_kv8")
+    return out
+
+
 def llm_rmsnorm_slots(x: Tensor, gamma: Tensor, eps: float, out: Optional[Tensor] = None, feat: Optional[Tensor] = None,
                       state: Optional[Tensor] = None) -> Tensor:
     """x [S,H]; feat [S, max_out, H] (optional) receives row s at state[s][1]-1 unless slot s is finished."""

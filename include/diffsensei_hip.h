@@ -566,6 +566,27 @@ int ds_llm_dequant_fp4(const void* q, const float* w_scale, void* w16, int64_t N
 int ds_llm_attn_slots_f16(const void* qkv, int64_t ldqkv, void* k_cache, void* v_cache, int64_t ldc, int64_t slot_stride,
                           const float* rope_cos, const float* rope_sin, void* out, int64_t ldo, const int32_t* state,
                           int slots, int heads, int kv_heads, int D, int T_max, float scale, void* stream);
+/* FP8 KV cache: ds_llm_attn_f16 / ds_llm_attn_slots_f16 on a cache of OCP e4m3 codes with one power-of-two exponent per
+ * (row, kv head).  For every cache row and kv head the D values are stored as
+ *   k_cache / v_cache  uint8 [T_max, kv_heads*D] rows (ldc BYTES; slot form: slot_stride BYTES between two slots): D e4m3fn
+ *                      codes (largest finite 448, subnormals down to 2^-9)
+ *   k_exp / v_exp      uint8 [T_max, kv_heads] rows (lde; slot form: exp_slot_stride between two slots): e = ex + 127 with ex
+ *                      the smallest integer such that amax / 2^ex <= 448, amax the head's largest fp16 magnitude (ex = 0 for an
+ *                      all-zero head; for fp16 input ex lies in [-33, 8])
+ *   value = f32(e4m3) * 2^(e - 127); x / 2^ex is exact, the one rounding is fp32 -> e4m3 to nearest even, nothing saturates.
+ * K is quantised after the rotation and its rounding to fp16, V as it is.  Scores, softmax and P.V as in the fp16 form (fp32
+ * accumulation, probabilities rounded to fp16): score_j = dot(q, f32(k8_j)) * 2^exk_j * scale, P.V term = (p_j * 2^exv_j) *
+ * f32(v8_j).  Every key and value - the chunk's own rows and the row's own key included - is seen through the quantiser, so the
+ * result is attention over the dequantised cache and does not depend on how the rows were cut into launches.  The guards of the
+ * fp16 form hold for codes and exponent bytes alike.  ldc % 8 == 0, 8-byte aligned caches.  A quantised mode with its own error
+ * (2.6 % relative rms on Gaussian heads); no parity figure exists for a trained checkpoint. */
+int ds_llm_attn_kv8(const void* qkv, int64_t ldqkv, void* k_cache, void* v_cache, int64_t ldc, void* k_exp, void* v_exp,
+                    int64_t lde, const float* rope_cos, const float* rope_sin, void* out, int64_t ldo, const int32_t* state,
+                    int M, int heads, int kv_heads, int D, int T_max, float scale, void* stream);
+int ds_llm_attn_slots_kv8(const void* qkv, int64_t ldqkv, void* k_cache, void* v_cache, int64_t ldc, int64_t slot_stride,
+                          void* k_exp, void* v_exp, int64_t lde, int64_t exp_slot_stride, const float* rope_cos,
+                          const float* rope_sin, void* out, int64_t ldo, const int32_t* state, int slots, int heads,
+                          int kv_heads, int D, int T_max, float scale, void* stream);
 /* row s normalised as ds_llm_rmsnorm_f16 does; `feat` (may be NULL): also stored as row state[s][1]-1 of feat[s] */
 int ds_llm_rmsnorm_slots_f16(const void* x, int64_t ldx, const void* gamma, void* y, int64_t ldy, void* feat,
                              const int32_t* state, int slots, int H, int max_out, float eps, void* stream);
@@ -668,7 +689,11 @@ enum ds_opcode {
     DS_OP_SLOT_START = 37,        /* p: panel-schedule buffer, redraw buffer (or NULL), latents, model_in
                                      i: ns HW do_cfg slot0 nslots   (ds_panel_slot_start_f16) */
     DS_OP_LLM_GEMV_FP4 = 38,      /* DS_OP_LLM_GEMV with MXFP4 weights in p[1], p[5] = w_scale, p[6] = w_exp (ds_llm_gemv_fp4) */
-    DS_OP_LLM_GEMM16_FP4 = 39     /* DS_OP_LLM_GEMM16 with MXFP4 weights in p[1], p[5] = w_scale, p[6] = w_exp (ds_llm_gemm16_fp4) */
+    DS_OP_LLM_GEMM16_FP4 = 39,    /* DS_OP_LLM_GEMM16 with MXFP4 weights in p[1], p[5] = w_scale, p[6] = w_exp (ds_llm_gemm16_fp4) */
+    DS_OP_LLM_ATTN_KV8 = 40,      /* DS_OP_LLM_ATTN on the fp8 cache: p[1], p[2] = uint8 e4m3 caches (l[1] = ldc in bytes), p[7] = k_exp,
+                                     p[8] = v_exp, l[4] = lde (ds_llm_attn_kv8) */
+    DS_OP_LLM_ATTN_SLOTS_KV8 = 41 /* DS_OP_LLM_ATTN_SLOTS likewise: l[3] = slot_stride in bytes, p[7] = k_exp, p[8] = v_exp, l[4] = lde,
+                                     l[5] = exp_slot_stride (ds_llm_attn_slots_kv8) */
 };
 
 typedef struct ds_op {
