@@ -27,7 +27,8 @@ OP = dict(GEMM=1, CONV3X3=2, GROUPNORM=3, LAYERNORM=4, SELF_ATTN=5, IP_ATTN=6, C
           PAD_ROWS=17, SMALL_ATTN=18, LLM_GEMV=19, LLM_ATTN=20, LLM_RMSNORM=21, LLM_EMBED=22, LLM_SELECT=23,
           LLM_ADVANCE=24, LN_FINALIZE=27, LLM_GEMM16=28, LLM_ATTN_SLOTS=29, LLM_RMSNORM_SLOTS=30,
           LLM_EMBED_SLOTS=31, LLM_SELECT_SLOTS=32, REDRAW_START=33, LLM_GEMV_W8=34, LLM_GEMM16_W8=35, LORA_MERGE=36, SLOT_START=37,
-          LLM_GEMV_FP4=38, LLM_GEMM16_FP4=39, LLM_ATTN_KV8=40, LLM_ATTN_SLOTS_KV8=41)
+          LLM_GEMV_FP4=38, LLM_GEMM16_FP4=39, LLM_ATTN_KV8=40, LLM_ATTN_SLOTS_KV8=41, LLM_ATTN_ROWS=42,
+          LLM_ATTN_ROWS_KV8=43)
 
 # name -> (restype, argtypes).  Every symbol declared in include/diffsensei_hip.h appears here;
 # tests/test_capi_symbols.py checks the two lists against each other.

@@ -511,7 +511,7 @@ static int llm_attn_impl(const void* qkv, int64_t ldqkv, void* kc, void* vc, int
                          const float* rope_sin, void* out, int64_t ldo, const int32_t* state, int M, int heads,
                          int kv_heads, int D, int T_max, float scale, hipStream_t st, int state_stride = SEQ,
                          int64_t slot_stride = 0, bool kv8 = false, void* k_exp = nullptr, void* v_exp = nullptr,
-                         int64_t lde = 0, int64_t exp_slot_stride = 0) {
+                         int64_t lde = 0, int64_t exp_slot_stride = 0, const int32_t* row_table = nullptr, int n_slots = 0) {
     LlmAttnParams a;
     a.kv8 = kv8; a.k_exp = reinterpret_cast<uint8_t*>(k_exp); a.v_exp = reinterpret_cast<uint8_t*>(v_exp);
     a.lde = (long)lde; a.exp_slot_stride = (long)exp_slot_stride;
@@ -519,6 +519,7 @@ static int llm_attn_impl(const void* qkv, int64_t ldqkv, void* kc, void* vc, int
     a.state = state; a.ldqkv = ldqkv; a.ldc = ldc; a.ldo = ldo;
     a.M = M; a.heads = heads; a.kv_heads = kv_heads; a.D = D; a.T_max = T_max; a.scale = scale;
     a.state_stride = state_stride; a.slot_stride = (long)slot_stride;
+    if (row_table) return ds_launch_llm_attn_rows(a, row_table, n_slots, st);   // the ragged form: M rows of the table
     return ds_launch_llm_attn(a, st);
 }
 
@@ -545,7 +546,7 @@ int ds_llm_embed_f16(const void* table, const int32_t* state, void* out, int Hd,
 
 int ds_llm_select_f16(const void* logits, int V, const int32_t* chain, int n_chain, int out_cap, int adv,
                       int32_t* state, int32_t* out_ids, void* stream) {
-    return ds_launch_llm_select(H(logits), V, V, chain, n_chain, out_cap, adv, state, SEQ, out_ids, 1, S(stream));
+    return ds_launch_llm_select(H(logits), V, V, chain, n_chain, out_cap, adv, state, SEQ, out_ids, 1, 0, S(stream));
 }
 
 int ds_llm_advance(int32_t* state, int rows, void* stream) { return ds_launch_llm_advance(state, rows, S(stream)); }
@@ -633,7 +634,7 @@ int ds_llm_embed_slots_f16(const void* table, const int32_t* state, void* out, i
 
 int ds_llm_select_slots_f16(const void* logits, int64_t ldl, int V, const int32_t* chain, int n_chain, int out_cap, int adv,
                             int32_t* state, int32_t* out_ids, int slots, void* stream) {
-    return ds_launch_llm_select(H(logits), ldl, V, chain, n_chain, out_cap, adv, state, SLOTS, out_ids, slots, S(stream));
+    return ds_launch_llm_select(H(logits), ldl, V, chain, n_chain, out_cap, adv, state, SLOTS, out_ids, slots, 0, S(stream));
 }
 
 int ds_resize_h_u8(const uint8_t* src, int H_, int W_, const int32_t* first, const int32_t* count, const int32_t* taps,
@@ -930,7 +931,7 @@ static int run_op(const ds_op& o, hipStream_t st) {
             return ds_launch_llm_embed(H(p[0]), reinterpret_cast<const int*>(p[1]), SEQ, HM(p[2]), i[0], 1, i[0], i[1], st);
         case DS_OP_LLM_SELECT:
             return ds_launch_llm_select(H(p[0]), i[0], i[0], reinterpret_cast<const int*>(p[1]), i[1], i[2], i[3],
-                                        reinterpret_cast<int*>(p[2]), SEQ, reinterpret_cast<int*>(p[3]), 1, st);
+                                        reinterpret_cast<int*>(p[2]), SEQ, reinterpret_cast<int*>(p[3]), 1, i[4], st);
         case DS_OP_LLM_ADVANCE:
             return ds_launch_llm_advance(reinterpret_cast<int*>(p[0]), i[0], st);
         case DS_OP_LLM_GEMM16:
@@ -960,6 +961,18 @@ static int run_op(const ds_op& o, hipStream_t st) {
             return llm_attn_impl(p[0], l[0], p[1], p[2], l[1], reinterpret_cast<const float*>(p[3]),
                                  reinterpret_cast<const float*>(p[4]), p[5], l[2], reinterpret_cast<const int32_t*>(p[6]),
                                  i[0], i[1], i[2], i[3], i[4], o.f[0], st, SLOTS, l[3], true, p[7], p[8], l[4], l[5]);
+        case DS_OP_LLM_ATTN_ROWS:       // without a table the launch fails (never the slot form by accident)
+            DS_REQUIRE(p[9], "DS_OP_LLM_ATTN_ROWS: p[9], the row table, is missing");
+            return llm_attn_impl(p[0], l[0], p[1], p[2], l[1], reinterpret_cast<const float*>(p[3]),
+                                 reinterpret_cast<const float*>(p[4]), p[5], l[2], reinterpret_cast<const int32_t*>(p[6]),
+                                 i[0], i[1], i[2], i[3], i[4], o.f[0], st, SLOTS, l[3], false, nullptr, nullptr, 0, 0,
+                                 reinterpret_cast<const int32_t*>(p[9]), i[5]);
+        case DS_OP_LLM_ATTN_ROWS_KV8:
+            DS_REQUIRE(p[9], "DS_OP_LLM_ATTN_ROWS_KV8: p[9], the row table, is missing");
+            return llm_attn_impl(p[0], l[0], p[1], p[2], l[1], reinterpret_cast<const float*>(p[3]),
+                                 reinterpret_cast<const float*>(p[4]), p[5], l[2], reinterpret_cast<const int32_t*>(p[6]),
+                                 i[0], i[1], i[2], i[3], i[4], o.f[0], st, SLOTS, l[3], true, p[7], p[8], l[4], l[5],
+                                 reinterpret_cast<const int32_t*>(p[9]), i[5]);
         case DS_OP_LLM_RMSNORM_SLOTS:
             return ds_launch_llm_rmsnorm(H(p[0]), l[0], H(p[1]), HM(p[2]), l[1], HM(p[3]),
                                          reinterpret_cast<const int*>(p[4]), SLOTS, i[0], i[1], i[2], o.f[0], st);
@@ -967,7 +980,7 @@ static int run_op(const ds_op& o, hipStream_t st) {
             return ds_launch_llm_embed(H(p[0]), reinterpret_cast<const int*>(p[1]), SLOTS, HM(p[2]), l[0], i[0], i[1], i[2], st);
         case DS_OP_LLM_SELECT_SLOTS:
             return ds_launch_llm_select(H(p[0]), l[0], i[0], reinterpret_cast<const int*>(p[1]), i[1], i[2], i[3],
-                                        reinterpret_cast<int*>(p[2]), SLOTS, reinterpret_cast<int*>(p[3]), i[4], st);
+                                        reinterpret_cast<int*>(p[2]), SLOTS, reinterpret_cast<int*>(p[3]), i[4], i[5], st);
         case DS_OP_LORA_MERGE:
             return ds_launch_lora_merge(lora_merge_params(o), st);
         default:
@@ -1048,6 +1061,11 @@ int ds_op_describe(const ds_op* op, char* name, int name_len, double* flops, dou
             break;
         case DS_OP_LLM_ATTN:
         case DS_OP_LLM_ATTN_SLOTS: nm = "llm_attn_kernel"; break;
+        case DS_OP_LLM_ATTN_ROWS: nm = "llm_attn_rows_kernel"; break;
+        case DS_OP_LLM_ATTN_ROWS_KV8:    // every slot's cache once at its full length, as for the slot form: an upper bound
+            nm = "llm_attn_rows_kernel";
+            by = 2.0 * i[5] * (double)i[4] * i[2] * (i[3] + 1.0);
+            break;
         case DS_OP_LLM_ATTN_KV8:      // the fp8 cache read once at its full length (an upper bound: the length is device state):
         case DS_OP_LLM_ATTN_SLOTS_KV8:   // D code bytes + 1 exponent byte per (row, kv head), for K and for V, per sequence
             nm = "llm_attn_kernel";

@@ -353,12 +353,17 @@ struct LlmAttnParams {
     long exp_slot_stride = 0;          // bytes between the exponent arrays of two rows (slot form)
 };
 int ds_launch_llm_attn(const LlmAttnParams& p, hipStream_t stream);
+// Ragged form (llm_attn_rows_kernel): p as in the slot form, p.M rows; table = device int32 [M][2] = (slot, row in the slot's
+// segment) - a segment's rows are consecutive in qkv / out and may be more than 16; slot in [0, n_slots).  The finished flag of
+// the state rows is not looked at.
+int ds_launch_llm_attn_rows(const LlmAttnParams& p, const int* table, int n_slots, hipStream_t stream);
 int ds_launch_llm_rmsnorm(const half_t* x, long ldx, const half_t* gamma, half_t* y, long ldy, half_t* feat,
                           const int* state, int state_stride, int M, int H, int max_out, float eps, hipStream_t stream);
 int ds_launch_llm_embed(const half_t* table, const int* state, int state_stride, half_t* out, long ldo, int M, int H,
                         int vocab, hipStream_t stream);
 int ds_launch_llm_select(const half_t* logits, long ldl, int V, const int* chain, int n_chain, int out_cap, int adv,
-                         int* state, int state_stride, int* out_ids, int M, hipStream_t stream);
+                         int* state, int state_stride, int* out_ids, int M, int pause, hipStream_t stream);
+// pause = 1 (chain fast-forward): a row that did not finish and whose new id lies in chain[:-1] gets state[2] = 2; 0: as ever
 int ds_launch_llm_advance(int* state, int rows, hipStream_t stream);
 int ds_launch_blend(const half_t* a, const half_t* b, half_t* out, long n, float s, hipStream_t stream);
 int ds_launch_llm_swiglu(const half_t* gu, half_t* act, int M, int I, hipStream_t stream);

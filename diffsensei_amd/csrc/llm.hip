@@ -487,6 +487,36 @@ __global__ __launch_bounds__(64 * ATT_WAVES) void llm_attn_kernel(LlmAttnParams 
     llm_attn_body<D, KV8>(p, blockIdx.x, blockIdx.y - s);
 }
 
+// Ragged form: the rows of several slots in one launch (the chain fast-forward pass, diffsensei_amd/mllm.py).  Row R of qkv /
+// out is row r of the segment of slot `slot`, table[R] = (slot, r); a segment's rows are consecutive, so its first row is
+// R - r.  Block (head h, row R) moves to that slot's cache, exponent planes and state row and to the segment's first row, and
+// runs the body on row r: keys below state[slot][0] come from the cache, the segment's own rows from qkv, rounded as a cached
+// copy, and the block appends its own K and V - nothing here reads what another block of the launch writes, so the result
+// does not depend on how the rows are cut into segments or launches.  Segments may be longer than 16 rows.  The finished
+// flag is not looked at (state_stride = 0 for the body): a paused slot carries 2 there.  A table entry outside the launch
+// (slot not in [0, n_slots), r not in [0, R]) is skipped; the body writes nothing at or past T_max.
+template <int D, bool KV8>
+__global__ __launch_bounds__(64 * ATT_WAVES) void llm_attn_rows_kernel(LlmAttnParams p, const int* __restrict__ table,
+                                                                       int n_slots) {
+    const int R = blockIdx.y;
+    const int s = table[2 * R], r = table[2 * R + 1];
+    if ((s < 0) | (s >= n_slots) | (r < 0) | (r > R)) return;
+    p.state += 8 * s;
+    p.qkv += (long)(R - r) * p.ldqkv;
+    p.out += (long)(R - r) * p.ldo;
+    if constexpr (KV8) {                             // byte caches: the slot stride counts bytes
+        p.kc = reinterpret_cast<half_t*>(reinterpret_cast<uint8_t*>(p.kc) + (long)s * p.slot_stride);
+        p.vc = reinterpret_cast<half_t*>(reinterpret_cast<uint8_t*>(p.vc) + (long)s * p.slot_stride);
+        p.k_exp += (long)s * p.exp_slot_stride;
+        p.v_exp += (long)s * p.exp_slot_stride;
+    } else {
+        p.kc += (long)s * p.slot_stride;
+        p.vc += (long)s * p.slot_stride;
+    }
+    p.state_stride = 0;
+    llm_attn_body<D, KV8>(p, blockIdx.x, r);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // y[m] = g * (x[m] / rms(x[m]))  (LlamaRMSNorm: normalise in fp32, cast to fp16, then multiply by the gain).
 // `feat` (token loop only, M = 1): the same row is also stored as row state[1]-1 of the per-token feature buffer —
@@ -551,7 +581,11 @@ __global__ __launch_bounds__(256) void llm_embed_kernel(const half_t* __restrict
 //   (the reference lifts its score to max + 10); otherwise the scores of chain[1:] are set to exactly 0.0 first.
 // argmax ties go to the lowest id (torch.argmax).  Then: append the id, make it the current token, advance the cache
 // length by `adv` rows, and raise `finished` on EOS (state[5]) or when state[4] ids are out.  One block.
+// PAUSE (chain fast-forward): a slot that did not finish and whose new token lies in chain[:-1] - every following id up to
+// </img> is then known without reading a weight - gets state[2] = 2: every per-slot kernel leaves it alone until the host
+// has run the forced rows in one pass and written the state row back.  Without PAUSE the code is what it was.
 // ---------------------------------------------------------------------------------------------------------------
+template <bool PAUSE>
 __device__ __forceinline__ void llm_select_body(const half_t* __restrict__ logits, int V,
                                                 const int* __restrict__ chain, int n_chain, int out_cap, int adv,
                                                 int* __restrict__ state, int* __restrict__ out_ids) {
@@ -613,18 +647,26 @@ __device__ __forceinline__ void llm_select_body(const half_t* __restrict__ logit
         state[3] = next;
         state[0] += adv;
         if (next == eos || n_out + 1 >= max_new) state[2] = 1;
+        else if constexpr (PAUSE) {
+            for (int q = 0; q < n_chain - 1; ++q)
+                if (chain[q] == next) {
+                    state[2] = 2;
+                    break;
+                }
+        }
     }
 }
 
 // One block per row m over logits[m] (row stride ldl), with the row's own state (its eos and max_new live there) and its
 // own out_ids[m] ([S][out_cap]).  The one-sequence form is one row.
+template <bool PAUSE>
 __global__ __launch_bounds__(1024) void llm_select_kernel(const half_t* __restrict__ logits, long ldl, int V,
                                                           const int* __restrict__ chain, int n_chain, int out_cap,
                                                           int adv, int* __restrict__ state, int state_stride,
                                                           int* __restrict__ out_ids) {
     const int m = blockIdx.x;
-    llm_select_body(logits + (long)m * ldl, V, chain, n_chain, out_cap, adv, state + state_stride * m,
-                    out_ids + (long)m * out_cap);
+    llm_select_body<PAUSE>(logits + (long)m * ldl, V, chain, n_chain, out_cap, adv, state + state_stride * m,
+                           out_ids + (long)m * out_cap);
 }
 
 // act[m][n] = silu(gu[m][n]) * gu[m][I+n]  (prompt pass: the gate|up projection comes out of the MFMA GEMM as [M,2I])
@@ -1274,9 +1316,9 @@ int ds_launch_llm_dequant_fp4(const uint8_t* q, const uint8_t* w_exp, const floa
 
 // ---- the four per-row kernels: one launcher and one argument check per kind, both row forms (ds_kernels.h; the callers in
 // capi.hip pass state_stride 0 or 8, and one row to the one-sequence embed and pick)
-int ds_launch_llm_attn(const LlmAttnParams& p, hipStream_t stream) {
+// what both attention launchers ask of their operands (the row count is each launcher's own)
+static int check_llm_attn(const LlmAttnParams& p) {
     DS_REQUIRE(p.D == 64 || p.D == 128, "llm_attn: head_dim %d unsupported (64 or 128)", p.D);
-    DS_REQUIRE(p.M > 0 && p.M <= 16, "llm_attn: %d rows per pass (1..16)", p.M);
     DS_REQUIRE(p.heads > 0 && p.kv_heads > 0 && p.heads % p.kv_heads == 0, "llm_attn: heads %d / kv_heads %d", p.heads,
                p.kv_heads);
     DS_REQUIRE(p.T_max > 0 && p.T_max <= 8192, "llm_attn: cache length %d (max 8192)", p.T_max);
@@ -1296,6 +1338,12 @@ int ds_launch_llm_attn(const LlmAttnParams& p, hipStream_t stream) {
         else DS_REQUIRE(p.exp_slot_stride == 0, "llm_attn: the one-sequence form has one exponent array (slot stride %ld)",
                         p.exp_slot_stride);
     } else DS_REQUIRE(!p.k_exp && !p.v_exp, "llm_attn: exponent arrays belong to the fp8 cache form");
+    return 0;
+}
+
+int ds_launch_llm_attn(const LlmAttnParams& p, hipStream_t stream) {
+    DS_REQUIRE(p.M > 0 && p.M <= 16, "llm_attn: %d rows per pass (1..16)", p.M);
+    if (const int rc = check_llm_attn(p)) return rc;
     const size_t lds = (size_t)(p.T_max + ATT_WAVES * p.D + 2 * ATT_WAVES) * sizeof(float);
     const dim3 grid(p.heads, p.M);
     const dim3 block(64 * ATT_WAVES);
@@ -1303,6 +1351,24 @@ int ds_launch_llm_attn(const LlmAttnParams& p, hipStream_t stream) {
     else if (p.D == 128) hipLaunchKernelGGL((llm_attn_kernel<128, false>), grid, block, lds, stream, p);
     else if (p.kv8) hipLaunchKernelGGL((llm_attn_kernel<64, true>), grid, block, lds, stream, p);
     else hipLaunchKernelGGL((llm_attn_kernel<64, false>), grid, block, lds, stream, p);
+    DS_LAUNCH_CHECK();
+    return 0;
+}
+
+// p in the slot form (state_stride 8, the slot strides), p.M = rows of qkv / out = entries of `table` (device int32 [M][2]).
+// Same block shape and LDS as llm_attn_kernel: 1024 threads, T_max + 16 D + 32 floats (at most 41 KB at T_max 8192).
+int ds_launch_llm_attn_rows(const LlmAttnParams& p, const int* table, int n_slots, hipStream_t stream) {
+    DS_REQUIRE(p.M > 0 && p.M <= 65535, "llm_attn_rows: %d rows (1..65535)", p.M);
+    DS_REQUIRE(table && n_slots > 0, "llm_attn_rows: the row table and the number of slots are needed");
+    DS_REQUIRE(p.state_stride == 8, "llm_attn_rows: the slot form's state block is needed (stride %d)", p.state_stride);
+    if (const int rc = check_llm_attn(p)) return rc;
+    const size_t lds = (size_t)(p.T_max + ATT_WAVES * p.D + 2 * ATT_WAVES) * sizeof(float);
+    const dim3 grid(p.heads, p.M);
+    const dim3 block(64 * ATT_WAVES);
+    if (p.D == 128 && p.kv8) hipLaunchKernelGGL((llm_attn_rows_kernel<128, true>), grid, block, lds, stream, p, table, n_slots);
+    else if (p.D == 128) hipLaunchKernelGGL((llm_attn_rows_kernel<128, false>), grid, block, lds, stream, p, table, n_slots);
+    else if (p.kv8) hipLaunchKernelGGL((llm_attn_rows_kernel<64, true>), grid, block, lds, stream, p, table, n_slots);
+    else hipLaunchKernelGGL((llm_attn_rows_kernel<64, false>), grid, block, lds, stream, p, table, n_slots);
     DS_LAUNCH_CHECK();
     return 0;
 }
@@ -1330,13 +1396,18 @@ int ds_launch_llm_embed(const half_t* table, const int* state, int state_stride,
 }
 
 int ds_launch_llm_select(const half_t* logits, long ldl, int V, const int* chain, int n_chain, int out_cap, int adv,
-                         int* state, int state_stride, int* out_ids, int M, hipStream_t stream) {
+                         int* state, int state_stride, int* out_ids, int M, int pause, hipStream_t stream) {
+    DS_REQUIRE(pause == 0 || pause == 1, "llm_select: pause flag %d (0 or 1)", pause);
     DS_REQUIRE(M > 0 && V > 0 && ldl >= V && n_chain >= 0 && n_chain <= 1024 && out_cap > 0 && adv >= 0,
                "llm_select: bad arguments");
     DS_REQUIRE(n_chain == 0 || chain, "llm_select: chain ids missing");
     DS_REQUIRE(logits && state && out_ids, "llm_select: null operand");
-    hipLaunchKernelGGL(llm_select_kernel, dim3(M), dim3(1024), 0, stream, logits, ldl, V, chain, n_chain, out_cap, adv,
-                       state, state_stride, out_ids);
+    if (pause)
+        hipLaunchKernelGGL(llm_select_kernel<true>, dim3(M), dim3(1024), 0, stream, logits, ldl, V, chain, n_chain, out_cap,
+                           adv, state, state_stride, out_ids);
+    else
+        hipLaunchKernelGGL(llm_select_kernel<false>, dim3(M), dim3(1024), 0, stream, logits, ldl, V, chain, n_chain, out_cap,
+                           adv, state, state_stride, out_ids);
     DS_LAUNCH_CHECK();
     return 0;
 }

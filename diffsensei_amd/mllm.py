@@ -58,6 +58,23 @@ seen through the quantiser, so the result is attention over the dequantised cach
 default stays fp16, bit for bit.  A quantised mode with its own error (2.6 % relative rms on Gaussian heads; on the tiny test
 model the fed-back hidden states move by 2.2e-2 of max|ref| and the greedy ids stay the same); what it does to a trained 13B
 checkpoint's output cannot be measured offline and is not measured.  Decode rate: `profiles/mllm_kv8_decode.txt`.
+
+Chain fast-forward (`LlamaDecodeEngine(chain_fast_forward=True)`, independent of `weight_dtype`, `kv_dtype`, `use_graph`,
+`prompt_path` and `max_sequences`): the image-token processor folded into the pick kernel forces the successor of any id in
+chain[:-1], so once a sequence's current token lies in the chain every following id up to and including </img> is known
+before a weight is read (`forced_run`, pure host arithmetic).  With the mode on the pick kernel marks such a slot
+(state[2] = 2, "paused": every per-slot kernel leaves it alone, as it does a finished one); the host, which reads the state
+block after the prompt pass and after every burst, then runs the forced rows of all paused slots in ONE pass - the embeddings
+of [cur] + f[:-1] at the slot's next positions through `_layers_mfma`, the layer loop of the prompt pass (MFMA GEMMs, int8 /
+mxfp4 from the dequantised scratch) with one launch of the ragged attention kernel per layer (`DS_OP_LLM_ATTN_ROWS[_KV8]`,
+`llm_attn_rows_kernel`: a row table (slot, row), every slot at its own cache length, segments of any length) - stores the
+final norm of every row as the fed-back hidden state of its id, writes the ids and rewrites the slot's state row; no lm_head,
+no pick.  The token loop then goes on with </img> as the current token.  Teacher forcing with the ids the pick kernel would
+have produced: the same ids; the hidden states differ from the default's by fp16 rounding (other GEMM kernels), which can flip
+a free near-tie after </img>.  What that does to a trained 13B checkpoint cannot be measured offline.  The first forced id
+after an <img>-ending prompt is still the prompt pass's own pick.  At 13B dimensions, 96-row prompt ending in <img>, 64 image
+tokens, 120 new ids: 628 -> 314 ms for one sequence, 1255 -> 702 ms for 16 (`profiles/mllm_chain_ff.txt`).
+A chain with a repeated id is refused in this mode.  Opt-in: the default stays as it is, bit for bit.
 """
 from __future__ import annotations
 
@@ -236,12 +253,31 @@ def dequantize_kv_fp8(codes: Tensor, exps: Tensor) -> Tensor:
     return torch.ldexp(v, (exps.to(torch.int32) - 127)[..., None])
 
 
+def forced_run(chain: Sequence[int], cur: int, n_out: int, max_new: int, eos: int) -> List[int]:
+    """The ids the pick kernel (`llm_select_body`, csrc/llm.hip) would append one by one without looking at a logit, starting
+    with current token `cur` and `n_out` ids already out: while `cur` lies in chain[:-1] and fewer than `max_new` ids are out,
+    the successor of `cur` in the chain is appended and becomes `cur`; the run ends after `eos` was appended (the kernel
+    finishes the sequence there) and when `max_new` ids are out.  Pure host arithmetic on a chain without repeated ids (with
+    repeats the kernel's rule and the reference's `.index()` rule differ: `set_image_token_chain` refuses them in this mode)."""
+    succ = {int(a): int(b) for a, b in zip(chain[:-1], chain[1:])}
+    out: List[int] = []
+    cur, n_out = int(cur), int(n_out)
+    while cur in succ and n_out < max_new:
+        cur = succ[cur]
+        out.append(cur)
+        n_out += 1
+        if cur == eos:
+            break
+    return out
+
+
 class LlamaDecodeEngine:
     """Device-resident LLaMA decoder + KV cache + the captured one-token launch plan."""
 
     def __init__(self, cfg: LlamaConfig, sd: Dict[str, Tensor], device, max_positions: int = 1024,
                  max_new_tokens: int = 512, use_graph: bool = True, poll_every: int = 8, prompt_path: str = "mfma",
-                 max_sequences: int = 1, weight_dtype: str = "float16", kv_dtype: str = "float16"):
+                 max_sequences: int = 1, weight_dtype: str = "float16", kv_dtype: str = "float16",
+                 chain_fast_forward: bool = False):
         """max_sequences S > 1: `generate_batch` decodes up to S sequences per weight pass; the engine then holds S KV-cache
         slots (each 2 x layers x max_positions x kv_heads x head_dim fp16: 0.84 GB at 13B dimensions and 1024 positions)
         and [S] state / id / feature / logits rows.  `generate` is one sequence in slot 0, whatever S is.
@@ -252,8 +288,14 @@ class LlamaDecodeEngine:
         exponents [N, K/32] and fp32 row scales.  Its effect on a trained checkpoint's output is not measured.
         kv_dtype "fp8": the KV cache holds OCP e4m3 codes and one power-of-two exponent byte per (row, kv head) (see
         `quantize_kv_fp8`): (head_dim + 1) / (2 head_dim) of the fp16 cache's bytes, and attention over the dequantised
-        cache.  Independent of weight_dtype.  Its effect on a trained checkpoint's output is not measured either."""
+        cache.  Independent of weight_dtype.  Its effect on a trained checkpoint's output is not measured either.
+        chain_fast_forward: once the current token of a sequence lies in the image-token chain, every following id up to
+        </img> is known; the decoder then runs those rows in one pass through the prompt pass's MFMA GEMMs and one ragged
+        attention launch per layer instead of one token step each (see the module docstring).  Teacher forcing with the ids
+        the pick kernel would have produced: the same ids, hidden states that differ by fp16 rounding (other GEMM kernels).
+        Independent of every other argument; needs a chain without repeated ids."""
         _lib.load()
+        self.chain_fast_forward = bool(chain_fast_forward)
         if kv_dtype not in ("float16", "fp8"):
             raise ValueError(f"kv_dtype {kv_dtype!r}: 'float16' or 'fp8'")
         self.kv_dtype = kv_dtype
@@ -423,7 +465,8 @@ class LlamaDecodeEngine:
         ops_.append(make_op("LLM_RMSNORM_SLOTS", i=(width, H, self.cap), f=(eps,), l=(H, H),
                             p=(self.h, self.norm_g, self.hn, self.feats, self.state)))
         ops_.append(make_op(proj, i=(width, V, H, 0, 0), f=(eps,), l=(H, V, 0), p=(self.hn, self.lm_head, self.logits, None)))
-        ops_.append(make_op("LLM_SELECT_SLOTS", i=(V, self.n_chain, self.cap, 1, width), l=(V,),
+        ops_.append(make_op("LLM_SELECT_SLOTS", i=(V, self.n_chain, self.cap, 1, width, int(self.chain_fast_forward)),
+                            l=(V,),
                             p=(self.logits, self.chain if self.n_chain else None, self.state, self.out_ids)))
         return ops_
 
@@ -443,7 +486,7 @@ class LlamaDecodeEngine:
                             p=(last_row, self.norm_g, self.hn, None, self.state)))
         ops_.append(make_op("LLM_GEMV", i=(1, V, H, 0, 0), f=(eps,), l=(H, V, 0),
                             p=(self.hn, self.lm_head, self.logits, None)))
-        ops_.append(make_op("LLM_SELECT", i=(V, self.n_chain, self.cap, M),
+        ops_.append(make_op("LLM_SELECT", i=(V, self.n_chain, self.cap, M, int(self.chain_fast_forward)),
                             p=(self.logits, self.chain if self.n_chain else None, self.state, self.out_ids)))
         return ops_
 
@@ -454,7 +497,7 @@ class LlamaDecodeEngine:
 
     def _plan(self, M: int, kind: str) -> Plan:
         """kind 'token': the token step at width M; 'chunk' / 'last': M prompt rows"""
-        key = (M, kind, self.n_chain, self.chain.data_ptr())
+        key = (M, kind, self.n_chain, self.chain.data_ptr(), self.chain_fast_forward)
         pl = self._plans.get(key)
         if pl is None:
             pl = Plan(self._token_ops(M) if kind == "token" else self._chunk_ops(M, kind), keep=[self])
@@ -463,7 +506,10 @@ class LlamaDecodeEngine:
 
     def set_image_token_chain(self, img_ids_list: Optional[Sequence[int]]) -> None:
         """[<img>, <img_00000> .. <img_{n-1}>, </img>] of the logits processor (None/empty = plain greedy)."""
-        ids = list(img_ids_list or [])
+        ids = [int(v) for v in (img_ids_list or [])]
+        if self.chain_fast_forward and len(set(ids)) != len(ids):
+            raise ValueError("chain_fast_forward: the image-token chain repeats an id; the successor of a repeated id is not "
+                             "defined the same way by the pick kernel and by the reference")
         if ids == getattr(self, "_chain_ids", None):
             return
         self._chain_ids = ids
@@ -480,7 +526,8 @@ class LlamaDecodeEngine:
         info = self.last_run_info
         self.last_run_info = {"graph": info["graph"], "prompt_tokens": info["prompt_tokens"][0], "new_tokens": info["new_tokens"][0],
                               "token_steps_launched": info["token_steps_launched"], "ops_per_token": info["ops_per_token"],
-                              "kv_dtype": info["kv_dtype"]}
+                              "kv_dtype": info["kv_dtype"], "fast_forward_rows": info["fast_forward_rows"][0],
+                              "fast_forward_passes": info["fast_forward_passes"]}
         return out[0]
 
     @torch.no_grad()
@@ -544,8 +591,19 @@ class LlamaDecodeEngine:
                 self._prompt_mfma(embs, slots, width)
             tok = self._plan(width, "token")
             done, most = False, max(max_new) - 1
-            while not done and steps < most:
-                burst = min(self.poll_every, most - steps)
+            ff = self.chain_fast_forward and self.n_chain > 1
+            ff_rows, ff_passes = {s: 0 for s in slots}, 0
+            state = self.state.cpu() if ff else None      # fast-forward: the prompt pass's pick may already have paused a slot
+            while True:
+                if ff:      # paused slots (flag 2) go through one pass; what is left follows from the rows the host now holds
+                    ff_passes += self._fast_forward(state, slots, ff_rows)
+                    done = bool(state[:, 2].all())
+                    left = max([int(state[s, 4] - state[s, 1]) for s in slots if not int(state[s, 2])], default=0)
+                else:
+                    left = most - steps
+                if done or left <= 0:
+                    break
+                burst = min(self.poll_every, left)
                 for _ in range(burst):
                     if self.use_graph and not tok.captured:
                         tok.run(st.cuda_stream)       # first step eager, then capture the launch list once
@@ -557,7 +615,8 @@ class LlamaDecodeEngine:
                         tok.run(st.cuda_stream)
                 steps += burst
                 # the only host<->device sync of the loop (every `poll_every` steps): every slot's flag in one copy
-                done = bool(self.state.cpu()[:, 2].all())
+                state = self.state.cpu()
+                done = bool(state[:, 2].all())
             state = self.state.cpu()
             out = []
             for s in slots:
@@ -565,8 +624,46 @@ class LlamaDecodeEngine:
                 out.append({"ids": self.out_ids[s, :k].to(torch.int64), "hidden": self.feats[s, :max(k - 1, 0)].clone()})
         torch.cuda.current_stream(dev).wait_stream(st)
         self.last_run_info = {"graph": graph, "sequences": len(embs), "prompt_tokens": T0s, "new_tokens": [len(o["ids"]) for o in out],
-                              "token_steps_launched": steps, "ops_per_token": tok.n, "kv_dtype": self.kv_dtype}
+                              "token_steps_launched": steps, "ops_per_token": tok.n, "kv_dtype": self.kv_dtype,
+                              "fast_forward_rows": [ff_rows[s] for s in slots], "fast_forward_passes": ff_passes}
         return out
+
+    def _fast_forward(self, state: Tensor, slots: List[int], ff_rows: Dict[int, int]) -> int:
+        """Chain fast-forward: every slot the pick kernel paused (flag 2 in `state`, the host copy of the state block) has a
+        current token inside the image-token chain, so its next ids are `forced_run`'s.  One pass over the concatenated rows
+        of all paused slots - slot s: the embeddings of [cur] + f[:-1] at positions len .. len + m - 1 - through
+        `_layers_mfma` with one ragged attention launch per layer; the final norm of row r is the fed-back hidden state of id
+        n_out - 1 + r; then f goes into out_ids and the slot's state row is rewritten (length + m, count + m, current token
+        f[-1], finished if f[-1] is the eos or the count reached max_new).  No lm_head, no pick.  The other slots' rows are
+        not touched; `state` is updated in place.  Returns the number of passes run (0 or 1)."""
+        segs = []                                               # (slot, ids fed, ids out)
+        for s in slots:
+            if int(state[s, 2]) != 2:
+                continue
+            ln, n_out, _, cur, mx, eos = (int(v) for v in state[s, :6])
+            f = forced_run(self._chain_ids, cur, n_out, mx, eos)
+            assert f and ln + len(f) <= self.T_max and n_out + len(f) <= self.cap, (s, ln, n_out, len(f))
+            segs.append((s, [cur] + f[:-1], f))
+        if not segs:
+            return 0
+        dev, eps = self.dev, self.cfg.rms_norm_eps
+        fed = torch.tensor([t for _, ids, _ in segs for t in ids], dtype=torch.long).to(dev)
+        table = torch.tensor([[s, r] for s, ids, _ in segs for r in range(len(ids))], dtype=torch.int32).to(dev)
+        starts = [0]
+        for _, ids, _ in segs:
+            starts.append(starts[-1] + len(ids))
+        h = self._layers_mfma(self.embed.index_select(0, fed), [s for s, _, _ in segs], starts, table)
+        for (s, _, f), a in zip(segs, starts):
+            m, n_out = len(f), int(state[s, 1])
+            ops.llm_rmsnorm(h[a:a + m], self.norm_g, eps, out=self.feats[s, n_out - 1:n_out - 1 + m])
+            self.out_ids[s, n_out:n_out + m].copy_(torch.tensor(f, dtype=torch.int32))
+            state[s, 0] += m
+            state[s, 1] += m
+            state[s, 3] = f[-1]
+            state[s, 2] = int(f[-1] == int(state[s, 5]) or n_out + m >= int(state[s, 4]))
+            self.state[s].copy_(state[s])
+            ff_rows[s] += m
+        return 1
 
     def _w(self, ws: list, ss: list, l: int, es: Sequence[Tensor] = ()) -> Tensor:
         """The fp16 matrix a prompt-pass GEMM reads: the weight itself, or - int8 / mxfp4 - its dequantised copy in the one
@@ -587,23 +684,49 @@ class LlamaDecodeEngine:
         chunk); only the attention walks each sequence's rows in chunks of 16 (causal inside a chunk, cache rows before
         it) into that sequence's slot.  Ends like the chunked path, per slot: final norm of each sequence's last row,
         lm_head (`llm_gemv` at width 1, `llm_gemm16_kernel` over all S rows otherwise) and the first pick."""
-        c = self.cfg
-        Hq, Hkv, eps = c.num_attention_heads, c.kv_heads, c.rms_norm_eps
-        scale = 1.0 / math.sqrt(c.head_dim)
-        pf = self.state_pf
+        eps = self.cfg.rms_norm_eps
         h = torch.cat([e.contiguous() for e in embs], 0) if width > 1 else embs[0].contiguous().clone()
         starts = [0]
         for e in embs:
             starts.append(starts[-1] + int(e.shape[0]))
+        h = self._layers_mfma(h, slots, starts)
+        if width == 1:
+            last_rows = h[-1:]
+        else:                                                                # row s = the last prompt row of the sequence in slot s
+            idx = torch.tensor([starts[i + 1] - 1 for i in range(len(embs))], dtype=torch.long, device=self.dev)
+            self.h.zero_()
+            self.h[torch.tensor(slots, dtype=torch.long, device=self.dev)] = h.index_select(0, idx)
+            last_rows = self.h[:width]
+        ops.llm_rmsnorm(last_rows, self.norm_g, eps, out=self.hn[:width])
+        (ops.llm_gemv if width == 1 else ops.llm_gemm16)(self.hn[:width], self.lm_head, out=self.logits[:width])
+        ops.llm_select_slots(self.logits[:width], self.chain if self.n_chain else None, 0, self.state[:width],
+                             self.out_ids[:width], pause=self.chain_fast_forward)
+
+    def _layers_mfma(self, h: Tensor, slots: List[int], starts: List[int], table: Optional[Tensor] = None) -> Tensor:
+        """Every decoder layer over known-token rows: h [rows, hidden], rows starts[i] .. starts[i + 1] - 1 are consecutive
+        positions of the sequence in slots[i].  RMSNorm, the MFMA GEMMs (int8 / mxfp4: from the dequantised scratch), attention,
+        o-proj, SwiGLU, down-proj; returns the last layer's residual stream.  Where a sequence's rows start decides the
+        attention: `table` None - the prompt pass, every sequence at position 0 - walks each sequence in chunks of 16 with the
+        one-sequence kernel and a cursor of its own; with `table` (int32 [rows][2] = (slot, row of the segment), the
+        fast-forward pass) sequence i starts at the length in its state row, state[slots[i]][0], and all rows of all
+        sequences are one launch of `llm_attn_rows_kernel`."""
+        c = self.cfg
+        Hq, Hkv, eps = c.num_attention_heads, c.kv_heads, c.rms_norm_eps
+        scale = 1.0 / math.sqrt(c.head_dim)
+        pf = self.state_pf
+        kv8 = self.kv_dtype == "fp8"
         att = torch.empty((starts[-1], Hq * c.head_dim), dtype=torch.float16, device=self.dev)
         for l in range(c.num_hidden_layers):
             xn = ops.llm_rmsnorm(h, self.g_in[l], eps)                       # LlamaRMSNorm incl. its gain, then the plain GEMM
             qkv = ops.gemm(xn, self._w(self.wqkv, self.sqkv, l, self.eqkv))
-            for i, s in enumerate(slots):
+            if table is not None:
+                ops.llm_attention_rows(qkv, self.kcs[l], self.vcs[l], self.rope_cos, self.rope_sin, self.state, table, Hq, Hkv,
+                                       scale, out=att, k_exp=self.kes[l] if kv8 else None, v_exp=self.ves[l] if kv8 else None)
+            for i, s in enumerate(slots if table is None else ()):
                 pf.zero_()                                                   # chunk cursor of this slot's cache
                 for r0 in range(starts[i], starts[i + 1], CHUNK):
                     m = min(CHUNK, starts[i + 1] - r0)
-                    if self.kv_dtype == "fp8":
+                    if kv8:
                         ops.llm_attention_kv8(qkv[r0:r0 + m], self.kcs[l][s], self.vcs[l][s], self.kes[l][s], self.ves[l][s],
                                               self.rope_cos, self.rope_sin, pf, Hq, Hkv, scale, out=att[r0:r0 + m])
                     else:
@@ -614,16 +737,7 @@ class LlamaDecodeEngine:
             xn = ops.llm_rmsnorm(h, self.g_post[l], eps)
             act = ops.llm_swiglu(ops.gemm(xn, self._w(self.wgu, self.sgu, l, self.egu)))
             h = ops.gemm(act, self._w(self.wdown, self.sdown, l, self.edown), residual=h)
-        if width == 1:
-            last_rows = h[-1:]
-        else:                                                                # row s = the last prompt row of the sequence in slot s
-            idx = torch.tensor([starts[i + 1] - 1 for i in range(len(embs))], dtype=torch.long, device=self.dev)
-            self.h.zero_()
-            self.h[torch.tensor(slots, dtype=torch.long, device=self.dev)] = h.index_select(0, idx)
-            last_rows = self.h[:width]
-        ops.llm_rmsnorm(last_rows, self.norm_g, eps, out=self.hn[:width])
-        (ops.llm_gemv if width == 1 else ops.llm_gemm16)(self.hn[:width], self.lm_head, out=self.logits[:width])
-        ops.llm_select_slots(self.logits[:width], self.chain if self.n_chain else None, 0, self.state[:width], self.out_ids[:width])
+        return h
 
     def embed_tokens(self, input_ids: Tensor) -> Tensor:
         """Row gather from the embedding table (data movement only)."""

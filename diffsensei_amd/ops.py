@@ -1258,15 +1258,72 @@ def llm_embed_slots(table: Tensor, state: Tensor, out: Tensor) -> Tensor:
     return out
 
 
-def llm_select_slots(logits: Tensor, chain: Optional[Tensor], adv: int, state: Tensor, out_ids: Tensor) -> None:
-    """`llm_select` per slot: logits [S,V], state int32 [S,8] (eos and max_new per slot), out_ids int32 [S,cap]."""
+def llm_select_slots(logits: Tensor, chain: Optional[Tensor], adv: int, state: Tensor, out_ids: Tensor,
+                     pause: bool = False) -> None:
+    """`llm_select` per slot: logits [S,V], state int32 [S,8] (eos and max_new per slot), out_ids int32 [S,cap].
+    pause (chain fast-forward): a slot that did not finish and whose new id lies in chain[:-1] gets state[s][2] = 2; that form
+    has no exported entry point and runs as DS_OP_LLM_SELECT_SLOTS with i[5] = 1."""
     _chk(logits)
     _chk(chain, state, out_ids, dtype=torch.int32)
     S, V = logits.shape
     assert state.shape == (S, 8) and out_ids.shape[0] == S
-    check(_lib.load().ds_llm_select_slots_f16(_p(logits), logits.stride(0), V, _p(chain),
-                                              0 if chain is None else chain.numel(), out_ids.shape[1], adv, _p(state),
-                                              _p(out_ids), S, _stream()), "ds_llm_select_slots_f16")
+    n_chain = 0 if chain is None else chain.numel()
+    if pause:
+        import ctypes
+        op = _lib.DsOp()
+        op.code = _lib.OP["LLM_SELECT_SLOTS"]
+        for k, v in enumerate((V, n_chain, out_ids.shape[1], adv, S, 1)):
+            op.i[k] = int(v)
+        op.l[0] = int(logits.stride(0))
+        for k, t in enumerate((logits, chain, state, out_ids)):
+            op.p[k] = _p(t)
+        check(_lib.load().ds_op_run(ctypes.byref(op), _stream()), "ds_op_run(LLM_SELECT_SLOTS)")
+        return
+    check(_lib.load().ds_llm_select_slots_f16(_p(logits), logits.stride(0), V, _p(chain), n_chain, out_ids.shape[1], adv,
+                                              _p(state), _p(out_ids), S, _stream()), "ds_llm_select_slots_f16")
+
+
+def llm_attention_rows(qkv: Tensor, k_cache: Tensor, v_cache: Tensor, rope_cos: Tensor, rope_sin: Tensor, state: Tensor,
+                       table: Tensor, heads: int, kv_heads: int, scale: float, out: Optional[Tensor] = None,
+                       k_exp: Optional[Tensor] = None, v_exp: Optional[Tensor] = None) -> Tensor:
+    """Ragged attention over the rows of several slots in one launch (llm_attn_rows_kernel through DS_OP_LLM_ATTN_ROWS[_KV8];
+    there is no exported entry point).  qkv [R,(heads+2*kv_heads)*D] un-rotated; caches [S, T_max, kv_heads*D] (fp16, or uint8
+    codes with `k_exp` / `v_exp` uint8 [S, T_max, kv_heads]: the fp8 cache); state int32 [S, 8]; table int32 [R, 2] on the
+    device, row R = (slot, r): row R of qkv / out is row r of that slot's segment, a run of consecutive rows (any length) that
+    starts at cache length state[slot][0].  Row r attends over the slot's cache and the segment's rows 0..r and appends its K
+    and V at state[slot][0] + r; state[slot][2] is not looked at and the state is not written.  Per row the bits are those of
+    `llm_attention` / `llm_attention_kv8` fed the same segment in chunks with the cursor at the start length."""
+    import ctypes
+    kv8 = k_exp is not None or v_exp is not None
+    _chk(qkv)
+    _chk(rope_cos, rope_sin, dtype=torch.float32)
+    _chk(state, table, dtype=torch.int32)
+    R = qkv.shape[0]
+    D = qkv.shape[1] // (heads + 2 * kv_heads)
+    S, T_max = k_cache.shape[0], k_cache.shape[1]
+    if kv8:
+        _chk_kv8(k_cache, v_cache, k_exp, v_exp, (S, T_max), kv_heads, D)
+    else:
+        _chk(k_cache, v_cache)
+        assert k_cache.shape == v_cache.shape == (S, T_max, kv_heads * D)
+    assert state.shape == (S, 8) and rope_cos.shape == (T_max, D // 2)
+    if tuple(table.shape) != (R, 2) or not table.is_contiguous():
+        raise ValueError(f"llm_attention_rows: the row table must be a contiguous int32 [{R}, 2], got {tuple(table.shape)}")
+    if out is None:
+        out = torch.empty((R, heads * D), dtype=torch.float16, device=qkv.device)
+    assert out.shape == (R, heads * D) and out.is_contiguous() and qkv.is_contiguous()
+    op = _lib.DsOp()
+    op.code = _lib.OP["LLM_ATTN_ROWS_KV8" if kv8 else "LLM_ATTN_ROWS"]
+    for k, v in enumerate((R, heads, kv_heads, D, T_max, S)):
+        op.i[k] = int(v)
+    op.f[0] = float(scale)
+    for k, v in enumerate((qkv.shape[1], k_cache.shape[2], heads * D, k_cache.stride(0))
+                          + ((kv_heads, k_exp.stride(0)) if kv8 else ())):
+        op.l[k] = int(v)
+    for k, t in enumerate((qkv, k_cache, v_cache, rope_cos, rope_sin, out, state, k_exp, v_exp, table)):
+        op.p[k] = _p(t)
+    check(_lib.load().ds_op_run(ctypes.byref(op), _stream()), "ds_op_run(LLM_ATTN_ROWS)")
+    return out
 
 
 def image_to_u8(image: Tensor) -> Tensor:

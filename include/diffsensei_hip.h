@@ -665,7 +665,10 @@ enum ds_opcode {
                                 i: M heads kv_heads D T_max                                           f: scale */
     DS_OP_LLM_RMSNORM = 21,  /* p: x, gamma, y, feat, state l: ldx ldy       i: M H max_out           f: eps */
     DS_OP_LLM_EMBED = 22,    /* p: table, state, out                         i: H vocab */
-    DS_OP_LLM_SELECT = 23,   /* p: logits, chain, state, out_ids             i: V n_chain out_cap adv */
+    DS_OP_LLM_SELECT = 23,   /* p: logits, chain, state, out_ids             i: V n_chain out_cap adv pause
+                                pause (i[4]; 0 | 1, chain fast-forward): 1 = a sequence that did not finish and whose new id lies in
+                                chain[:-1] gets state[2] = 2 - every per-slot kernel then leaves it alone until the host has decoded
+                                the forced ids in one pass and rewritten the state row; 0 = the pick as it always was */
     DS_OP_LLM_ADVANCE = 24,  /* p: state                                     i: rows */
     /* 25, 26: retired (fp8 attention, rounds 2-5) */
     DS_OP_LN_FINALIZE = 27,  /* p: partial, stats                            i: M strips C               f: eps */
@@ -673,7 +676,8 @@ enum ds_opcode {
     DS_OP_LLM_ATTN_SLOTS = 29,    /* as DS_OP_LLM_ATTN with i[0] = slots and l[3] = slot_stride (ds_llm_attn_slots_f16) */
     DS_OP_LLM_RMSNORM_SLOTS = 30, /* p: x, gamma, y, feat, state l: ldx ldy     i: slots H max_out       f: eps */
     DS_OP_LLM_EMBED_SLOTS = 31,   /* p: table, state, out        l: ldo         i: slots H vocab */
-    DS_OP_LLM_SELECT_SLOTS = 32,  /* p: logits, chain, state, out_ids  l: ldl   i: V n_chain out_cap adv slots */
+    DS_OP_LLM_SELECT_SLOTS = 32,  /* p: logits, chain, state, out_ids  l: ldl   i: V n_chain out_cap adv slots pause (i[5], as i[4]
+                                     of DS_OP_LLM_SELECT) */
     DS_OP_REDRAW_START = 33,      /* p: redraw buffer, latents                  i: ns HW   (ds_redraw_start_f16) */
     DS_OP_LLM_GEMV_W8 = 34,       /* DS_OP_LLM_GEMV with int8 weights in p[1] and p[5] = w_scale (ds_llm_gemv_w8) */
     DS_OP_LLM_GEMM16_W8 = 35,     /* DS_OP_LLM_GEMM16 with int8 weights in p[1] and p[5] = w_scale (ds_llm_gemm16_w8) */
@@ -692,8 +696,17 @@ enum ds_opcode {
     DS_OP_LLM_GEMM16_FP4 = 39,    /* DS_OP_LLM_GEMM16 with MXFP4 weights in p[1], p[5] = w_scale, p[6] = w_exp (ds_llm_gemm16_fp4) */
     DS_OP_LLM_ATTN_KV8 = 40,      /* DS_OP_LLM_ATTN on the fp8 cache: p[1], p[2] = uint8 e4m3 caches (l[1] = ldc in bytes), p[7] = k_exp,
                                      p[8] = v_exp, l[4] = lde (ds_llm_attn_kv8) */
-    DS_OP_LLM_ATTN_SLOTS_KV8 = 41 /* DS_OP_LLM_ATTN_SLOTS likewise: l[3] = slot_stride in bytes, p[7] = k_exp, p[8] = v_exp, l[4] = lde,
+    DS_OP_LLM_ATTN_SLOTS_KV8 = 41, /* DS_OP_LLM_ATTN_SLOTS likewise: l[3] = slot_stride in bytes, p[7] = k_exp, p[8] = v_exp, l[4] = lde,
                                      l[5] = exp_slot_stride (ds_llm_attn_slots_kv8) */
+    DS_OP_LLM_ATTN_ROWS = 42,     /* ragged attention over the rows of several slots in one launch (llm_attn_rows_kernel; the chain
+                                     fast-forward pass): p, l, f as DS_OP_LLM_ATTN_SLOTS plus p[9] = row table, device int32 [rows][2] =
+                                     (slot, row r inside the slot's segment); i: rows heads kv_heads D T_max slots.  A segment is a
+                                     run of consecutive rows of qkv / out with r = 0, 1, ..; it may be longer than 16 rows.  Row r sits
+                                     at position state[slot][0] + r, sees the slot's cache below state[slot][0] and the segment's rows
+                                     up to itself, and appends its K and V; state[slot][2] is not looked at, the state is not
+                                     written, nothing is written at or past T_max, a table entry with slot outside [0, slots) or r
+                                     outside [0, row] is skipped.  No exported entry point */
+    DS_OP_LLM_ATTN_ROWS_KV8 = 43  /* DS_OP_LLM_ATTN_ROWS on the fp8 cache: operands as DS_OP_LLM_ATTN_SLOTS_KV8 plus p[9] and i[5] */
 };
 
 typedef struct ds_op {
