@@ -488,16 +488,27 @@ int ds_skinny_linear_f16(const void* x, const void* w, const void* bias, const v
 }
 
 // ---- MLLM pre-pass (llm.hip): LLaMA greedy decoding
-static int llm_gemv_impl(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, const void* residual,
-                         int64_t ldr, int M, int N, int K, int rms, int swiglu, float eps, hipStream_t st,
-                         const void* rms_gain = nullptr, bool gemm16 = false, const float* w_scale = nullptr,
-                         bool w8 = false, const uint8_t* w_exp = nullptr, bool fp4 = false) {
-    DS_REQUIRE(!w8 || w_scale, "%s: int8 weights need their scale vector", gemm16 ? "llm_gemm16_w8" : "llm_gemv_w8");
-    DS_REQUIRE(!fp4 || (w_scale && w_exp), "%s: MXFP4 weights need their row scales (w_scale) and block exponents (w_exp)",
+// The six projection entry points and op codes are {gemv, gemm16} x the weight form: what the weights are made of and
+// therefore which of w_scale / w_exp the call carries (the others are not read).
+enum LlmWeights { LLM_W_F16, LLM_W_INT8, LLM_W_MXFP4 };
+static LlmWeights llm_weights_of(int code) {
+    return code == DS_OP_LLM_GEMV_FP4 || code == DS_OP_LLM_GEMM16_FP4 ? LLM_W_MXFP4
+           : code == DS_OP_LLM_GEMV_W8 || code == DS_OP_LLM_GEMM16_W8 ? LLM_W_INT8 : LLM_W_F16;
+}
+static bool llm_is_gemm16(int code) {
+    return code == DS_OP_LLM_GEMM16 || code == DS_OP_LLM_GEMM16_W8 || code == DS_OP_LLM_GEMM16_FP4;
+}
+
+static int llm_gemv_impl(bool gemm16, LlmWeights form, const void* x, int64_t ldx, const void* w, void* y, int64_t ldy,
+                         const void* residual, int64_t ldr, int M, int N, int K, int rms, const void* rms_gain, int swiglu,
+                         float eps, const void* w_scale, const void* w_exp, hipStream_t st) {
+    DS_REQUIRE(form != LLM_W_INT8 || w_scale, "%s: int8 weights need their scale vector", gemm16 ? "llm_gemm16_w8" : "llm_gemv_w8");
+    DS_REQUIRE(form != LLM_W_MXFP4 || (w_scale && w_exp),
+               "%s: MXFP4 weights need their row scales (w_scale) and block exponents (w_exp)",
                gemm16 ? "llm_gemm16_fp4" : "llm_gemv_fp4");
     LlmGemvParams g;
-    g.w_scale = w_scale;
-    g.w_exp = w_exp;
+    g.w_scale = form == LLM_W_F16 ? nullptr : reinterpret_cast<const float*>(w_scale);
+    g.w_exp = form == LLM_W_MXFP4 ? reinterpret_cast<const uint8_t*>(w_exp) : nullptr;
     g.x = H(x); g.w = w; g.y = HM(y); g.residual = H(residual); g.gain = rms ? H(rms_gain) : nullptr;
     g.ldx = ldx; g.ldy = ldy; g.ldr = ldr; g.M = M; g.N = N; g.K = K; g.rms = rms; g.swiglu = swiglu; g.eps = eps;
     return gemm16 ? ds_launch_llm_gemm16(g, st) : ds_launch_llm_gemv(g, st);
@@ -525,7 +536,8 @@ static int llm_attn_impl(const void* qkv, int64_t ldqkv, void* kc, void* vc, int
 
 int ds_llm_gemv_f16(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, const void* residual,
                     int64_t ldr, int M, int N, int K, int rms, const void* rms_gain, int swiglu, float eps, void* stream) {
-    return llm_gemv_impl(x, ldx, w, y, ldy, residual, ldr, M, N, K, rms, swiglu, eps, S(stream), rms_gain);
+    return llm_gemv_impl(false, LLM_W_F16, x, ldx, w, y, ldy, residual, ldr, M, N, K, rms, rms_gain, swiglu, eps, nullptr, nullptr,
+                         S(stream));
 }
 
 int ds_llm_attn_f16(const void* qkv, int64_t ldqkv, void* k_cache, void* v_cache, int64_t ldc, const float* rope_cos,
@@ -559,15 +571,15 @@ int ds_llm_swiglu_f16(const void* gate_up, void* act, int M, int I, void* stream
 int ds_llm_gemv_w8(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, const void* residual, int64_t ldr,
                    int M, int N, int K, int rms, const void* rms_gain, int swiglu, float eps, const float* w_scale,
                    void* stream) {
-    return llm_gemv_impl(x, ldx, w, y, ldy, residual, ldr, M, N, K, rms, swiglu, eps, S(stream), rms_gain, false, w_scale,
-                         true);
+    return llm_gemv_impl(false, LLM_W_INT8, x, ldx, w, y, ldy, residual, ldr, M, N, K, rms, rms_gain, swiglu, eps, w_scale, nullptr,
+                         S(stream));
 }
 
 int ds_llm_gemm16_w8(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, const void* residual, int64_t ldr,
                      int M, int N, int K, int rms, const void* rms_gain, int swiglu, float eps, const float* w_scale,
                      void* stream) {
-    return llm_gemv_impl(x, ldx, w, y, ldy, residual, ldr, M, N, K, rms, swiglu, eps, S(stream), rms_gain, true, w_scale,
-                         true);
+    return llm_gemv_impl(true, LLM_W_INT8, x, ldx, w, y, ldy, residual, ldr, M, N, K, rms, rms_gain, swiglu, eps, w_scale, nullptr,
+                         S(stream));
 }
 
 int ds_llm_dequant_w8(const void* q, const float* w_scale, void* w16, int64_t N, int K, void* stream) {
@@ -578,15 +590,15 @@ int ds_llm_dequant_w8(const void* q, const float* w_scale, void* w16, int64_t N,
 int ds_llm_gemv_fp4(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, const void* residual, int64_t ldr,
                     int M, int N, int K, int rms, const void* rms_gain, int swiglu, float eps, const float* w_scale,
                     const uint8_t* w_exp, void* stream) {
-    return llm_gemv_impl(x, ldx, w, y, ldy, residual, ldr, M, N, K, rms, swiglu, eps, S(stream), rms_gain, false, w_scale,
-                         false, w_exp, true);
+    return llm_gemv_impl(false, LLM_W_MXFP4, x, ldx, w, y, ldy, residual, ldr, M, N, K, rms, rms_gain, swiglu, eps, w_scale, w_exp,
+                         S(stream));
 }
 
 int ds_llm_gemm16_fp4(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, const void* residual, int64_t ldr,
                       int M, int N, int K, int rms, const void* rms_gain, int swiglu, float eps, const float* w_scale,
                       const uint8_t* w_exp, void* stream) {
-    return llm_gemv_impl(x, ldx, w, y, ldy, residual, ldr, M, N, K, rms, swiglu, eps, S(stream), rms_gain, true, w_scale,
-                         false, w_exp, true);
+    return llm_gemv_impl(true, LLM_W_MXFP4, x, ldx, w, y, ldy, residual, ldr, M, N, K, rms, rms_gain, swiglu, eps, w_scale, w_exp,
+                         S(stream));
 }
 
 int ds_llm_dequant_fp4(const void* q, const float* w_scale, void* w16, int64_t N, int K, const uint8_t* w_exp, void* stream) {
@@ -596,7 +608,8 @@ int ds_llm_dequant_fp4(const void* q, const float* w_scale, void* w16, int64_t N
 // ---- batched decode: up to 16 sequences per weight pass
 int ds_llm_gemm16(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, const void* residual, int64_t ldr,
                   int M, int N, int K, int rms, const void* rms_gain, int swiglu, float eps, void* stream) {
-    return llm_gemv_impl(x, ldx, w, y, ldy, residual, ldr, M, N, K, rms, swiglu, eps, S(stream), rms_gain, true);
+    return llm_gemv_impl(true, LLM_W_F16, x, ldx, w, y, ldy, residual, ldr, M, N, K, rms, rms_gain, swiglu, eps, nullptr, nullptr,
+                         S(stream));
 }
 
 int ds_llm_attn_slots_f16(const void* qkv, int64_t ldqkv, void* k_cache, void* v_cache, int64_t ldc, int64_t slot_stride,
@@ -919,11 +932,32 @@ static int run_op(const ds_op& o, hipStream_t st) {
             return ds_launch_small_attn(H(p[0]), H(p[1]), H(p[2]), HM(p[3]), l[0], l[1], l[2], l[3], l[4], l[5], l[6],
                                         l[7], i[0], i[1], i[2], i[3], i[4], o.f[0], st);
         case DS_OP_LLM_GEMV:
-            return llm_gemv_impl(p[0], l[0], p[1], p[2], l[1], p[3], l[2], i[0], i[1], i[2], i[3], i[4], o.f[0], st, p[4]);
+        case DS_OP_LLM_GEMM16:
+        case DS_OP_LLM_GEMV_W8:
+        case DS_OP_LLM_GEMM16_W8:
+        case DS_OP_LLM_GEMV_FP4:
+        case DS_OP_LLM_GEMM16_FP4: {   // one slot layout; p[5] (row scales) and p[6] (block exponents) by weight form
+            const LlmWeights form = llm_weights_of(o.code);
+            return llm_gemv_impl(llm_is_gemm16(o.code), form, p[0], l[0], p[1], p[2], l[1], p[3], l[2], i[0], i[1], i[2], i[3], p[4],
+                                 i[4], o.f[0], form != LLM_W_F16 ? p[5] : nullptr, form == LLM_W_MXFP4 ? p[6] : nullptr, st);
+        }
         case DS_OP_LLM_ATTN:
+        case DS_OP_LLM_ATTN_SLOTS:
+        case DS_OP_LLM_ATTN_KV8:
+        case DS_OP_LLM_ATTN_SLOTS_KV8:
+        case DS_OP_LLM_ATTN_ROWS:
+        case DS_OP_LLM_ATTN_ROWS_KV8: {   // one slot layout; the slot strides, exponent planes and row table by form
+            const bool rows = o.code == DS_OP_LLM_ATTN_ROWS || o.code == DS_OP_LLM_ATTN_ROWS_KV8;
+            const bool kv8 = o.code == DS_OP_LLM_ATTN_KV8 || o.code == DS_OP_LLM_ATTN_SLOTS_KV8 || o.code == DS_OP_LLM_ATTN_ROWS_KV8;
+            const bool slots = rows || o.code == DS_OP_LLM_ATTN_SLOTS || o.code == DS_OP_LLM_ATTN_SLOTS_KV8;
+            // without a table the launch fails (never the slot form by accident)
+            DS_REQUIRE(!rows || p[9], "%s: p[9], the row table, is missing", kv8 ? "DS_OP_LLM_ATTN_ROWS_KV8" : "DS_OP_LLM_ATTN_ROWS");
             return llm_attn_impl(p[0], l[0], p[1], p[2], l[1], reinterpret_cast<const float*>(p[3]),
                                  reinterpret_cast<const float*>(p[4]), p[5], l[2], reinterpret_cast<const int32_t*>(p[6]),
-                                 i[0], i[1], i[2], i[3], i[4], o.f[0], st);
+                                 i[0], i[1], i[2], i[3], i[4], o.f[0], st, slots ? SLOTS : SEQ, slots ? l[3] : 0, kv8,
+                                 kv8 ? p[7] : nullptr, kv8 ? p[8] : nullptr, kv8 ? l[4] : 0, kv8 && slots ? l[5] : 0,
+                                 rows ? reinterpret_cast<const int32_t*>(p[9]) : nullptr, rows ? i[5] : 0);
+        }
         case DS_OP_LLM_RMSNORM:
             return ds_launch_llm_rmsnorm(H(p[0]), l[0], H(p[1]), HM(p[2]), l[1], HM(p[3]),
                                          reinterpret_cast<const int*>(p[4]), SEQ, i[0], i[1], i[2], o.f[0], st);
@@ -934,45 +968,6 @@ static int run_op(const ds_op& o, hipStream_t st) {
                                         reinterpret_cast<int*>(p[2]), SEQ, reinterpret_cast<int*>(p[3]), 1, i[4], st);
         case DS_OP_LLM_ADVANCE:
             return ds_launch_llm_advance(reinterpret_cast<int*>(p[0]), i[0], st);
-        case DS_OP_LLM_GEMM16:
-            return llm_gemv_impl(p[0], l[0], p[1], p[2], l[1], p[3], l[2], i[0], i[1], i[2], i[3], i[4], o.f[0], st, p[4],
-                                 true);
-        case DS_OP_LLM_GEMV_W8:
-            return llm_gemv_impl(p[0], l[0], p[1], p[2], l[1], p[3], l[2], i[0], i[1], i[2], i[3], i[4], o.f[0], st, p[4],
-                                 false, reinterpret_cast<const float*>(p[5]), true);
-        case DS_OP_LLM_GEMM16_W8:
-            return llm_gemv_impl(p[0], l[0], p[1], p[2], l[1], p[3], l[2], i[0], i[1], i[2], i[3], i[4], o.f[0], st, p[4],
-                                 true, reinterpret_cast<const float*>(p[5]), true);
-        case DS_OP_LLM_GEMV_FP4:
-            return llm_gemv_impl(p[0], l[0], p[1], p[2], l[1], p[3], l[2], i[0], i[1], i[2], i[3], i[4], o.f[0], st, p[4],
-                                 false, reinterpret_cast<const float*>(p[5]), false, reinterpret_cast<const uint8_t*>(p[6]), true);
-        case DS_OP_LLM_GEMM16_FP4:
-            return llm_gemv_impl(p[0], l[0], p[1], p[2], l[1], p[3], l[2], i[0], i[1], i[2], i[3], i[4], o.f[0], st, p[4],
-                                 true, reinterpret_cast<const float*>(p[5]), false, reinterpret_cast<const uint8_t*>(p[6]), true);
-        case DS_OP_LLM_ATTN_SLOTS:
-            return llm_attn_impl(p[0], l[0], p[1], p[2], l[1], reinterpret_cast<const float*>(p[3]),
-                                 reinterpret_cast<const float*>(p[4]), p[5], l[2], reinterpret_cast<const int32_t*>(p[6]),
-                                 i[0], i[1], i[2], i[3], i[4], o.f[0], st, SLOTS, l[3]);
-        case DS_OP_LLM_ATTN_KV8:
-            return llm_attn_impl(p[0], l[0], p[1], p[2], l[1], reinterpret_cast<const float*>(p[3]),
-                                 reinterpret_cast<const float*>(p[4]), p[5], l[2], reinterpret_cast<const int32_t*>(p[6]),
-                                 i[0], i[1], i[2], i[3], i[4], o.f[0], st, SEQ, 0, true, p[7], p[8], l[4], 0);
-        case DS_OP_LLM_ATTN_SLOTS_KV8:
-            return llm_attn_impl(p[0], l[0], p[1], p[2], l[1], reinterpret_cast<const float*>(p[3]),
-                                 reinterpret_cast<const float*>(p[4]), p[5], l[2], reinterpret_cast<const int32_t*>(p[6]),
-                                 i[0], i[1], i[2], i[3], i[4], o.f[0], st, SLOTS, l[3], true, p[7], p[8], l[4], l[5]);
-        case DS_OP_LLM_ATTN_ROWS:       // without a table the launch fails (never the slot form by accident)
-            DS_REQUIRE(p[9], "DS_OP_LLM_ATTN_ROWS: p[9], the row table, is missing");
-            return llm_attn_impl(p[0], l[0], p[1], p[2], l[1], reinterpret_cast<const float*>(p[3]),
-                                 reinterpret_cast<const float*>(p[4]), p[5], l[2], reinterpret_cast<const int32_t*>(p[6]),
-                                 i[0], i[1], i[2], i[3], i[4], o.f[0], st, SLOTS, l[3], false, nullptr, nullptr, 0, 0,
-                                 reinterpret_cast<const int32_t*>(p[9]), i[5]);
-        case DS_OP_LLM_ATTN_ROWS_KV8:
-            DS_REQUIRE(p[9], "DS_OP_LLM_ATTN_ROWS_KV8: p[9], the row table, is missing");
-            return llm_attn_impl(p[0], l[0], p[1], p[2], l[1], reinterpret_cast<const float*>(p[3]),
-                                 reinterpret_cast<const float*>(p[4]), p[5], l[2], reinterpret_cast<const int32_t*>(p[6]),
-                                 i[0], i[1], i[2], i[3], i[4], o.f[0], st, SLOTS, l[3], true, p[7], p[8], l[4], l[5],
-                                 reinterpret_cast<const int32_t*>(p[9]), i[5]);
         case DS_OP_LLM_RMSNORM_SLOTS:
             return ds_launch_llm_rmsnorm(H(p[0]), l[0], H(p[1]), HM(p[2]), l[1], HM(p[3]),
                                          reinterpret_cast<const int*>(p[4]), SLOTS, i[0], i[1], i[2], o.f[0], st);
@@ -1034,31 +1029,21 @@ int ds_op_describe(const ds_op* op, char* name, int name_len, double* flops, dou
         case DS_OP_SLOT_START: nm = "panel_slot_start_kernel"; by = 2.0 * 3.0 * i[4] * 4.0 * i[1]; break;
         case DS_OP_REDRAW_START: nm = "redraw_start_kernel"; by = 2.0 * 3.0 * i[0] * 4.0 * i[1]; break;
         case DS_OP_LLM_GEMV:
-            nm = "llm_gemv_kernel";
-            fl = 2.0 * i[0] * (double)i[1] * i[2] * (i[4] ? 2 : 1);
-            by = 2.0 * ((double)i[1] * i[2] * (i[4] ? 2 : 1) + (double)i[0] * i[2] + (double)i[0] * i[1]);
-            break;
-        case DS_OP_LLM_GEMM16:   // W + x + y bytes: the weights are read once for all M rows
-            nm = "llm_gemm16_kernel";
-            fl = 2.0 * i[0] * (double)i[1] * i[2] * (i[4] ? 2 : 1);
-            by = 2.0 * ((double)i[1] * i[2] * (i[4] ? 2 : 1) + (double)i[0] * i[2] + (double)i[0] * i[1]);
-            break;
-        case DS_OP_LLM_GEMV_W8:     // int8 weights: 1 byte per weight + the fp32 row scales, x and y fp16
-            nm = "llm_gemv_kernel";
-            fl = 2.0 * i[0] * (double)i[1] * i[2] * (i[4] ? 2 : 1);
-            by = (double)i[1] * (i[4] ? 2 : 1) * (i[2] + 4.0) + 2.0 * ((double)i[0] * i[2] + (double)i[0] * i[1]);
-            break;
+        case DS_OP_LLM_GEMM16:
+        case DS_OP_LLM_GEMV_W8:
         case DS_OP_LLM_GEMM16_W8:
-            nm = "llm_gemm16_kernel";
+        case DS_OP_LLM_GEMV_FP4:
+        case DS_OP_LLM_GEMM16_FP4: {   // W + x + y bytes: the weights are read once for all M rows; x and y fp16
+            const LlmWeights form = llm_weights_of(op->code);
+            const double rows = (double)i[1] * (i[4] ? 2 : 1), K = i[2];
+            nm = llm_is_gemm16(op->code) ? "llm_gemm16_kernel" : "llm_gemv_kernel";
             fl = 2.0 * i[0] * (double)i[1] * i[2] * (i[4] ? 2 : 1);
-            by = (double)i[1] * (i[4] ? 2 : 1) * (i[2] + 4.0) + 2.0 * ((double)i[0] * i[2] + (double)i[0] * i[1]);
+            // per weight row: fp16 2 bytes per weight; int8 1 + the fp32 row scale; MXFP4 half a byte + one exponent byte per 32
+            // + the row scale
+            by = rows * (form == LLM_W_F16 ? 2.0 * K : form == LLM_W_INT8 ? K + 4.0 : K / 2.0 + K / 32.0 + 4.0) +
+                 2.0 * ((double)i[0] * i[2] + (double)i[0] * i[1]);
             break;
-        case DS_OP_LLM_GEMV_FP4:    // MXFP4 weights: half a byte per weight + one exponent byte per 32 + the fp32 row scales
-        case DS_OP_LLM_GEMM16_FP4:
-            nm = op->code == DS_OP_LLM_GEMV_FP4 ? "llm_gemv_kernel" : "llm_gemm16_kernel";
-            fl = 2.0 * i[0] * (double)i[1] * i[2] * (i[4] ? 2 : 1);
-            by = (double)i[1] * (i[4] ? 2 : 1) * (i[2] / 2.0 + i[2] / 32.0 + 4.0) + 2.0 * ((double)i[0] * i[2] + (double)i[0] * i[1]);
-            break;
+        }
         case DS_OP_LLM_ATTN:
         case DS_OP_LLM_ATTN_SLOTS: nm = "llm_attn_kernel"; break;
         case DS_OP_LLM_ATTN_ROWS: nm = "llm_attn_rows_kernel"; break;

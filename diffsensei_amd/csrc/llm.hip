@@ -20,6 +20,8 @@
 // MXFP4 weight-only decoding (W4A16): the projection weights may also be packed e2m1 [N,K/2] (element 2i in the low nibble)
 // with one biased E8M0 exponent per 32-element block ([N,K/32], values 114..127) and one fp32 scale per row; a 16-byte load
 // is one block, unpacked by v_cvt_scalef32_pk_f16_fp4 with the block's scale - the third WLoad specialisation below.
+#include <type_traits>
+
 #include "ds_common.h"
 #include "ds_kernels.h"
 
@@ -120,6 +122,103 @@ struct WLoad<fp4x2_t> {
     }
 };
 
+// The one weight load of the projection kernels: the 16 bytes of weight row `row` at element k and, under BLOCK_SCALE, the
+// exponent byte of that block (e = 0 otherwise).  Each kernel has its own rule for which k (and, in gemm16, which row) a load
+// past the end is clamped to; it clamps BEFORE the call, so the weights and the exponent of a clamped re-read are one block's.
+template <typename WT>
+__device__ __forceinline__ void wload(const LlmGemvParams& p, long row, int K, int k, typename WLoad<WT>::raw& v, unsigned& e) {
+    typedef WLoad<WT> WL;
+    const WT* wr = reinterpret_cast<const WT*>(p.w) + ((row * K) >> WL::SH);
+    v = *reinterpret_cast<const typename WL::raw*>(wr + (k >> WL::SH));
+    e = 0;
+    if constexpr (WL::BLOCK_SCALE) e = p.w_exp[row * (K / WL::E) + k / WL::E];
+}
+
+// ---- What the four projection kernels promise - the same bits whatever the kernel, the row count or the chunking, and the
+// reference's fp16 rounding points - rests on the three functions below; each is spelled here once.
+// 1/rms of one row of x read from global memory by one whole wavefront (`valid` false: a row past M, the sum is 0)
+__device__ __forceinline__ float llm_row_scale(const half_t* xr, bool valid, int K, float eps, int lane) {
+    float ss = 0.f;
+    if (valid) {
+        for (int k = lane * 8; k < K; k += 512) {
+            const h8 v = *reinterpret_cast<const h8*>(xr + k);
+            ss = dot8(v, v, ss);
+        }
+    }
+    return __builtin_amdgcn_rsqf(wave_sum(ss) / (float)K + eps);
+}
+
+// Row staging of the LDS kernels (256 threads, all of them call it): rows 0 .. MC-1 of x (zeros past M) go to xs[m][K] in the
+// order WL::xpos gives, rs[m] becomes the row's 1/rms (1 without p.rms) from per-wavefront partial sums added in wavefront
+// order (rs[MC ..] holds the [MC][4] partials); with a gain the staged rows become the RMSNorm OUTPUT (reference roundings,
+// rms_gain8) and no scale is left for the dots: rs[m] = 1.  Ends behind a barrier.
+template <typename WL, int MC>
+__device__ __forceinline__ void llm_stage_rows(const LlmGemvParams& p, half_t* xs, float* rs) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int K = p.K;
+    float ss[MC];
+#pragma unroll
+    for (int m = 0; m < MC; ++m) {
+        ss[m] = 0.f;
+        for (int k = tid * 8; k < K; k += 2048) {
+            h8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+            if (m < p.M) v = *reinterpret_cast<const h8*>(p.x + (long)m * p.ldx + k);
+            *reinterpret_cast<h8*>(xs + (long)m * K + WL::xpos(k, K)) = v;
+            ss[m] = dot8(v, v, ss[m]);
+        }
+        ss[m] = wave_sum(ss[m]);
+        if (lane == 0) rs[MC + m * 4 + wave] = ss[m];
+    }
+    __syncthreads();
+    if (tid < MC) {
+        const float s = rs[MC + tid * 4] + rs[MC + tid * 4 + 1] + rs[MC + tid * 4 + 2] + rs[MC + tid * 4 + 3];
+        rs[tid] = p.rms ? __builtin_amdgcn_rsqf(s / (float)K + p.eps) : 1.0f;
+    }
+    __syncthreads();
+    if (p.rms && p.gain) {
+#pragma unroll
+        for (int m = 0; m < MC; ++m) {
+            const float r = rs[m];
+            for (int k = tid * 8; k < K; k += 2048) {
+                h8* xp = reinterpret_cast<h8*>(xs + (long)m * K + WL::xpos(k, K));
+                *xp = rms_gain8(*xp, *reinterpret_cast<const h8*>(p.gain + k), r);
+            }
+        }
+        __syncthreads();
+        if (tid < MC) rs[tid] = 1.0f;
+        __syncthreads();
+    }
+}
+
+// The output element, from the wavefront's or tile's fp32 sum(s), in two steps because every lane of the GEMV kernels holds
+// the sum and one lane stores.  llm_proj_scale, in every lane: times the row's 1/rms `rr` (1 when a gain was applied: the scale
+// is already inside x'), then times the weight row's scale for ROW_SCALE formats (sg: row n, su: the up row n + N) - the
+// order of the two products is part of the bits.  (One fused function called by the storing lane alone gives the same bits
+// but other registers: it changed the occupancy of three instantiations.)
+template <typename WL, int SWIGLU>
+__device__ __forceinline__ void llm_proj_scale(float& g, float& u, float rr, float sg, float su) {
+    g *= rr;
+    if (SWIGLU) u *= rr;
+    if constexpr (WL::ROW_SCALE) {
+        g *= sg;
+        if (SWIGLU) u *= su;
+    }
+}
+// llm_proj_out, in the storing lane: the scaled sums meet their fp16 roundings HERE and nowhere else.  SwiGLU is the
+// reference's act_fn(gate_proj(x)) * up_proj(x) with an fp16 tensor after every step, f16(f16(silu(f16 g)) * f16 u); plain is
+// f16(f16(g) + residual) (`residual`: the element, null without one).
+template <int SWIGLU>
+__device__ __forceinline__ half_t llm_proj_out(float g, float u, const half_t* residual) {
+    float o;
+    if (SWIGLU) {
+        o = (float)(half_t)ds_silu((float)(half_t)g) * (float)(half_t)u;
+    } else {
+        o = (float)(half_t)g;
+        if (residual) o += (float)*residual;
+    }
+    return (half_t)o;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // y[m][n] = r_m * sum_k x[m][k] w[n][k]  (+ residual[m][n]),  r_m = rsqrt(mean_k x[m][k]^2 + eps) if rms else 1
 // (with p.gain: y[m][n] = sum_k f16(gain[k] * f16(x[m][k] r_m)) w[n][k], the reference's RMSNorm roundings)
@@ -133,8 +232,7 @@ struct WLoad<fp4x2_t> {
 template <typename WT, int MC, int SWIGLU>
 __global__ __launch_bounds__(256) void llm_gemv_kernel(LlmGemvParams p) {
     typedef WLoad<WT> WL;
-    constexpr int E = WL::E, NH = WL::NH, SH = WL::SH;
-    constexpr bool W8 = WL::ROW_SCALE;
+    constexpr int E = WL::E, NH = WL::NH;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n = blockIdx.x * 4 + wave;
     const int m0 = blockIdx.y * MC;
@@ -145,23 +243,11 @@ __global__ __launch_bounds__(256) void llm_gemv_kernel(LlmGemvParams p) {
     for (int m = 0; m < MC; ++m) r[m] = 1.0f;
     if (p.rms) {
 #pragma unroll
-        for (int m = 0; m < MC; ++m) {
-            float ss = 0.f;
-            if (m0 + m < p.M) {
-                const half_t* xr = p.x + (long)(m0 + m) * p.ldx;
-                for (int k = lane * 8; k < K; k += 512) {
-                    const h8 v = *reinterpret_cast<const h8*>(xr + k);
-                    ss = dot8(v, v, ss);
-                }
-            }
-            r[m] = __builtin_amdgcn_rsqf(wave_sum(ss) / (float)K + p.eps);
-        }
+        for (int m = 0; m < MC; ++m) r[m] = llm_row_scale(p.x + (long)(m0 + m) * p.ldx, m0 + m < p.M, K, p.eps, lane);
     }
     float acc[MC], acu[MC];
 #pragma unroll
     for (int m = 0; m < MC; ++m) acc[m] = acu[m] = 0.f;
-    const WT* wg = reinterpret_cast<const WT*>(p.w) + (((long)n * K) >> SH);
-    const WT* wu = reinterpret_cast<const WT*>(p.w) + ((((long)n + p.N) * K) >> SH);
     constexpr int U = (MC <= 4) ? 4 : 2;  // independent 16-byte loads in flight per lane
     for (int k0 = lane * E; k0 < K; k0 += 64 * E * U) {
         typename WL::raw wv[U], uv[U];
@@ -169,13 +255,9 @@ __global__ __launch_bounds__(256) void llm_gemv_kernel(LlmGemvParams p) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int k = min(k0 + 64 * E * u, K - E);  // clamped re-read past the end, masked below
-            wv[u] = *reinterpret_cast<const typename WL::raw*>(wg + (k >> SH));
-            if (SWIGLU) uv[u] = *reinterpret_cast<const typename WL::raw*>(wu + (k >> SH));
-            we[u] = ue[u] = 0;
-            if constexpr (WL::BLOCK_SCALE) {
-                we[u] = p.w_exp[(long)n * (K / E) + k / E];
-                if (SWIGLU) ue[u] = p.w_exp[((long)n + p.N) * (K / E) + k / E];
-            }
+            wload<WT>(p, n, K, k, wv[u], we[u]);
+            ue[u] = 0;
+            if (SWIGLU) wload<WT>(p, (long)n + p.N, K, k, uv[u], ue[u]);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -200,34 +282,22 @@ __global__ __launch_bounds__(256) void llm_gemv_kernel(LlmGemvParams p) {
         }
     }
     float sg = 1.0f, su = 1.0f;
-    if constexpr (W8) {
+    if constexpr (WL::ROW_SCALE) {
         sg = p.w_scale[n];
         if (SWIGLU) su = p.w_scale[n + p.N];
     }
 #pragma unroll
     for (int m = 0; m < MC; ++m) {
-        const float rr = p.gain ? 1.0f : r[m];  // with a gain the scale is already inside x'
-        acc[m] = wave_sum(acc[m]) * rr;
-        if (SWIGLU) acu[m] = wave_sum(acu[m]) * rr;
-        if constexpr (W8) {
-            acc[m] *= sg;
-            if (SWIGLU) acu[m] *= su;
-        }
+        acc[m] = wave_sum(acc[m]);
+        if (SWIGLU) acu[m] = wave_sum(acu[m]);
+        llm_proj_scale<WL, SWIGLU>(acc[m], acu[m], p.gain ? 1.0f : r[m], sg, su);
     }
     if (lane == 0) {
 #pragma unroll
         for (int m = 0; m < MC; ++m) {
-            if (m0 + m < p.M) {
-                float o;
-                if (SWIGLU) {  // fp16 roundings of the reference: act_fn(gate_proj(x)) * up_proj(x)
-                    const float g = (float)(half_t)acc[m], u = (float)(half_t)acu[m];
-                    o = (float)(half_t)ds_silu(g) * u;
-                } else {
-                    o = (float)(half_t)acc[m];
-                    if (p.residual) o += (float)p.residual[(long)(m0 + m) * p.ldr + n];
-                }
-                p.y[(long)(m0 + m) * p.ldy + n] = (half_t)o;
-            }
+            if (m0 + m < p.M)
+                p.y[(long)(m0 + m) * p.ldy + n] = llm_proj_out<SWIGLU>(
+                    acc[m], acu[m], p.residual ? p.residual + (long)(m0 + m) * p.ldr + n : nullptr);
         }
     }
 }
@@ -710,56 +780,22 @@ __global__ __launch_bounds__(256) void llm_gemv_stream_kernel(LlmGemvParams p) {
     extern __shared__ char smem_raw[];
     half_t* xs = reinterpret_cast<half_t*>(smem_raw);               // [MC][K]
     float* rs = reinterpret_cast<float*>(smem_raw + (size_t)MC * p.K * 2);  // [MC] row scales, then [MC][4] partials
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int K = p.K;
-    {
-        float ss[MC];
-#pragma unroll
-        for (int m = 0; m < MC; ++m) {
-            ss[m] = 0.f;
-            for (int k = tid * 8; k < K; k += 2048) {
-                h8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-                if (m < p.M) v = *reinterpret_cast<const h8*>(p.x + (long)m * p.ldx + k);
-                *reinterpret_cast<h8*>(xs + (long)m * K + k) = v;
-                ss[m] = dot8(v, v, ss[m]);
-            }
-            ss[m] = wave_sum(ss[m]);
-            if (lane == 0) rs[MC + m * 4 + wave] = ss[m];
-        }
-        __syncthreads();
-        if (tid < MC) {
-            const float s = rs[MC + tid * 4] + rs[MC + tid * 4 + 1] + rs[MC + tid * 4 + 2] + rs[MC + tid * 4 + 3];
-            rs[tid] = p.rms ? __builtin_amdgcn_rsqf(s / (float)K + p.eps) : 1.0f;
-        }
-        __syncthreads();
-        if (p.rms && p.gain) {  // the staged rows become the RMSNorm OUTPUT (reference roundings); no scale left for the dots
-#pragma unroll
-            for (int m = 0; m < MC; ++m) {
-                const float r = rs[m];
-                for (int k = tid * 8; k < K; k += 2048) {
-                    h8* xp = reinterpret_cast<h8*>(xs + (long)m * K + k);
-                    *xp = rms_gain8(*xp, *reinterpret_cast<const h8*>(p.gain + k), r);
-                }
-            }
-            __syncthreads();
-            if (tid < MC) rs[tid] = 1.0f;
-            __syncthreads();
-        }
-    }
+    llm_stage_rows<WLoad<half_t>, MC>(p, xs, rs);
     constexpr int U = SWIGLU ? 4 : 8;
     for (int n = blockIdx.x * 4 + wave; n < p.N; n += gridDim.x * 4) {
         float acc[MC], acu[MC];
 #pragma unroll
         for (int m = 0; m < MC; ++m) acc[m] = acu[m] = 0.f;
-        const half_t* wg = reinterpret_cast<const half_t*>(p.w) + (long)n * K;
-        const half_t* wu = reinterpret_cast<const half_t*>(p.w) + ((long)n + p.N) * K;
         for (int k0 = lane * 8; k0 < K; k0 += 512 * U) {
             h8 wv[U], uv[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int k = min(k0 + 512 * u, K - 8);
-                wv[u] = *reinterpret_cast<const h8*>(wg + k);
-                if (SWIGLU) uv[u] = *reinterpret_cast<const h8*>(wu + k);
+                unsigned none;
+                wload<half_t>(p, n, K, k, wv[u], none);
+                if (SWIGLU) wload<half_t>(p, (long)n + p.N, K, k, uv[u], none);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -776,23 +812,16 @@ __global__ __launch_bounds__(256) void llm_gemv_stream_kernel(LlmGemvParams p) {
         }
 #pragma unroll
         for (int m = 0; m < MC; ++m) {
-            acc[m] = wave_sum(acc[m]) * rs[m];
-            if (SWIGLU) acu[m] = wave_sum(acu[m]) * rs[m];
+            acc[m] = wave_sum(acc[m]);
+            if (SWIGLU) acu[m] = wave_sum(acu[m]);
+            llm_proj_scale<WLoad<half_t>, SWIGLU>(acc[m], acu[m], rs[m], 1.0f, 1.0f);
         }
         if (lane == 0) {
 #pragma unroll
             for (int m = 0; m < MC; ++m) {
-                if (m < p.M) {
-                    float o;
-                    if (SWIGLU) {
-                        const float g = (float)(half_t)acc[m], u = (float)(half_t)acu[m];
-                        o = (float)(half_t)ds_silu(g) * u;
-                    } else {
-                        o = (float)(half_t)acc[m];
-                        if (p.residual) o += (float)p.residual[(long)m * p.ldr + n];
-                    }
-                    p.y[(long)m * p.ldy + n] = (half_t)o;
-                }
+                if (m < p.M)
+                    p.y[(long)m * p.ldy + n] = llm_proj_out<SWIGLU>(
+                        acc[m], acu[m], p.residual ? p.residual + (long)m * p.ldr + n : nullptr);
             }
         }
     }
@@ -808,12 +837,11 @@ template <typename WT, int MC, int SWIGLU>
 __global__ __launch_bounds__(256, MC == 1 ? WLoad<WT>::PIPE_WAVES : 1) void llm_gemv_pipe_kernel(LlmGemvParams p) {
     typedef WLoad<WT> WL;
     typedef typename WL::raw wraw;
-    constexpr int E = WL::E, NH = WL::NH, SH = WL::SH;
-    constexpr bool W8 = WL::ROW_SCALE;
+    constexpr int E = WL::E, NH = WL::NH;
     extern __shared__ char smem_raw[];
     half_t* xs = reinterpret_cast<half_t*>(smem_raw);
     float* rs = reinterpret_cast<float*>(smem_raw + (size_t)MC * p.K * 2);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int K = p.K, N = p.N;
     constexpr int U = SWIGLU ? 4 : 8;
     const int NIT = (K + 64 * E * U - 1) / (64 * E * U);
@@ -822,55 +850,16 @@ __global__ __launch_bounds__(256, MC == 1 ? WLoad<WT>::PIPE_WAVES : 1) void llm_
     wraw wa[U], ua[U], wb[U], ub[U];
     unsigned ea[U], fa[U], eb[U], fb[U];   // block exponents of the loads (BLOCK_SCALE only): e* gate / plain, f* up
     auto issue = [&](int col, int it, wraw(&wv)[U], wraw(&uv)[U], unsigned(&ev)[U], unsigned(&fv)[U]) {
-        const WT* wg = reinterpret_cast<const WT*>(p.w) + (((long)col * K) >> SH);
-        const WT* wu = reinterpret_cast<const WT*>(p.w) + ((((long)col + N) * K) >> SH);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int k = min(it * 64 * E * U + 64 * E * u + lane * E, K - E);
-            wv[u] = *reinterpret_cast<const wraw*>(wg + (k >> SH));
-            if (SWIGLU) uv[u] = *reinterpret_cast<const wraw*>(wu + (k >> SH));
-            ev[u] = fv[u] = 0;
-            if constexpr (WL::BLOCK_SCALE) {   // the clamped k: weights and scale of a re-read are one block's
-                ev[u] = p.w_exp[(long)col * (K / E) + k / E];
-                if (SWIGLU) fv[u] = p.w_exp[((long)col + N) * (K / E) + k / E];
-            }
+            wload<WT>(p, col, K, k, wv[u], ev[u]);
+            fv[u] = 0;
+            if (SWIGLU) wload<WT>(p, (long)col + N, K, k, uv[u], fv[u]);
         }
     };
     if (n < N) issue(n, 0, wa, ua, ea, fa);
-    {
-        float ss[MC];
-#pragma unroll
-        for (int m = 0; m < MC; ++m) {
-            ss[m] = 0.f;
-            for (int k = tid * 8; k < K; k += 2048) {
-                h8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-                if (m < p.M) v = *reinterpret_cast<const h8*>(p.x + (long)m * p.ldx + k);
-                *reinterpret_cast<h8*>(xs + (long)m * K + WL::xpos(k, K)) = v;
-                ss[m] = dot8(v, v, ss[m]);
-            }
-            ss[m] = wave_sum(ss[m]);
-            if (lane == 0) rs[MC + m * 4 + wave] = ss[m];
-        }
-        __syncthreads();
-        if (tid < MC) {
-            const float s = rs[MC + tid * 4] + rs[MC + tid * 4 + 1] + rs[MC + tid * 4 + 2] + rs[MC + tid * 4 + 3];
-            rs[tid] = p.rms ? __builtin_amdgcn_rsqf(s / (float)K + p.eps) : 1.0f;
-        }
-        __syncthreads();
-        if (p.rms && p.gain) {  // the staged rows become the RMSNorm OUTPUT (reference roundings); no scale left for the dots
-#pragma unroll
-            for (int m = 0; m < MC; ++m) {
-                const float r = rs[m];
-                for (int k = tid * 8; k < K; k += 2048) {
-                    h8* xp = reinterpret_cast<h8*>(xs + (long)m * K + WL::xpos(k, K));
-                    *xp = rms_gain8(*xp, *reinterpret_cast<const h8*>(p.gain + k), r);
-                }
-            }
-            __syncthreads();
-            if (tid < MC) rs[tid] = 1.0f;
-            __syncthreads();
-        }
-    }
+    llm_stage_rows<WL, MC>(p, xs, rs);
     while (n < N) {
         float acc[MC], acu[MC];
 #pragma unroll
@@ -907,29 +896,23 @@ __global__ __launch_bounds__(256, MC == 1 ? WLoad<WT>::PIPE_WAVES : 1) void llm_
                 }
             }
         }
+        float sg = 1.0f, su = 1.0f;
+        if constexpr (WL::ROW_SCALE) {
+            sg = p.w_scale[n];
+            if (SWIGLU) su = p.w_scale[n + N];
+        }
 #pragma unroll
         for (int m = 0; m < MC; ++m) {
-            acc[m] = wave_sum(acc[m]) * rs[m];
-            if (SWIGLU) acu[m] = wave_sum(acu[m]) * rs[m];
-            if constexpr (W8) {   // the row scales, after the wave's sum and before the fp16 rounding
-                acc[m] *= p.w_scale[n];
-                if (SWIGLU) acu[m] *= p.w_scale[n + N];
-            }
+            acc[m] = wave_sum(acc[m]);
+            if (SWIGLU) acu[m] = wave_sum(acu[m]);
+            llm_proj_scale<WL, SWIGLU>(acc[m], acu[m], rs[m], sg, su);
         }
         if (lane == 0) {
 #pragma unroll
             for (int m = 0; m < MC; ++m) {
-                if (m < p.M) {
-                    float o;
-                    if (SWIGLU) {
-                        const float g = (float)(half_t)acc[m], u = (float)(half_t)acu[m];
-                        o = (float)(half_t)ds_silu(g) * u;
-                    } else {
-                        o = (float)(half_t)acc[m];
-                        if (p.residual) o += (float)p.residual[(long)m * p.ldr + n];
-                    }
-                    p.y[(long)m * p.ldy + n] = (half_t)o;
-                }
+                if (m < p.M)
+                    p.y[(long)m * p.ldy + n] = llm_proj_out<SWIGLU>(
+                        acc[m], acu[m], p.residual ? p.residual + (long)m * p.ldr + n : nullptr);
             }
         }
         n += stride;
@@ -969,8 +952,7 @@ template <typename WT, int SWIGLU>
 __global__ __launch_bounds__(256) void llm_gemm16_kernel(LlmGemvParams p) {
     typedef WLoad<WT> WL;
     typedef typename WL::raw wraw;
-    constexpr int E = WL::E, NH = WL::NH, SH = WL::SH;
-    constexpr bool W8 = WL::ROW_SCALE;
+    constexpr int E = WL::E, NH = WL::NH;
     constexpr int U = SWIGLU ? 4 : 8;   // MFMA steps per iteration
     constexpr int UL = U / NH;          // 16-byte weight loads per lane and matrix per iteration
     constexpr int KB = 32 * U;          // halves of K per wavefront iteration
@@ -991,18 +973,12 @@ __global__ __launch_bounds__(256) void llm_gemm16_kernel(LlmGemvParams p) {
     auto kof = [&](int it, int u) { return (it * 4 + wave) * KB + 32 * NH * (u / NH) + 8 * NH * g + 8 * (u % NH); };
     auto issue_w = [&](int tile, int it, wraw(&wv)[UL], wraw(&uv)[UL], unsigned(&ev)[UL], unsigned(&fv)[UL]) {
         const long col = min(tile * 16 + c, N - 1);   // ragged last tile: re-read the last row, never stored
-        const WT* wg = reinterpret_cast<const WT*>(p.w) + ((col * K) >> SH);
-        const WT* wu = reinterpret_cast<const WT*>(p.w) + (((col + N) * K) >> SH);
 #pragma unroll
         for (int u = 0; u < UL; ++u) {
             const int k = min(kof(it, u * NH), K - E);   // ragged K: clamped (the scale index with it), x is zero there
-            wv[u] = *reinterpret_cast<const wraw*>(wg + (k >> SH));
-            if (SWIGLU) uv[u] = *reinterpret_cast<const wraw*>(wu + (k >> SH));
-            ev[u] = fv[u] = 0;
-            if constexpr (WL::BLOCK_SCALE) {
-                ev[u] = p.w_exp[col * (K / E) + k / E];
-                if (SWIGLU) fv[u] = p.w_exp[(col + N) * (K / E) + k / E];
-            }
+            wload<WT>(p, col, K, k, wv[u], ev[u]);
+            fv[u] = 0;
+            if (SWIGLU) wload<WT>(p, col + N, K, k, uv[u], fv[u]);
         }
     };
     const half_t* xr = p.x + (long)min(c, M - 1) * p.ldx;
@@ -1021,16 +997,8 @@ __global__ __launch_bounds__(256) void llm_gemm16_kernel(LlmGemvParams p) {
 #pragma unroll
         for (int mm = 0; mm < 4; ++mm) {
             const int m = wave * 4 + mm;
-            float ss = 0.f;
-            if (m < M) {
-                const half_t* row = p.x + (long)m * p.ldx;
-                for (int k = lane * 8; k < K; k += 512) {
-                    const h8 v = *reinterpret_cast<const h8*>(row + k);
-                    ss = dot8(v, v, ss);
-                }
-            }
-            ss = wave_sum(ss);
-            if (lane == 0) rs[m] = m < M ? __builtin_amdgcn_rsqf(ss / (float)K + p.eps) : 1.0f;
+            const float r = llm_row_scale(p.x + (long)m * p.ldx, m < M, K, p.eps, lane);
+            if (lane == 0) rs[m] = m < M ? r : 1.0f;
         }
         if (p.gain)
             for (int k = tid * 8; k < K; k += 2048) *reinterpret_cast<h8*>(gl + k) = *reinterpret_cast<const h8*>(p.gain + k);
@@ -1091,22 +1059,16 @@ __global__ __launch_bounds__(256) void llm_gemm16_kernel(LlmGemvParams p) {
         {
             const int m = 4 * g + wave, n = tile * 16 + c;
             float a = ((rp[tid] + rp[256 + tid]) + rp[512 + tid]) + rp[768 + tid];
-            const float rr = gain ? 1.0f : rs[m];   // with a gain the scale is already inside x'
-            a *= rr;
+            const float rr = gain ? 1.0f : rs[m];
             if (m < M && n < N) {
-                if constexpr (W8) a *= p.w_scale[n];   // row scale: after the reduction, before the fp16 rounding
-                float o;
-                if (SWIGLU) {  // fp16 roundings of the reference: act_fn(gate_proj(x)) * up_proj(x)
-                    float b = ((rp[1024 + tid] + rp[1280 + tid]) + rp[1536 + tid]) + rp[1792 + tid];
-                    b *= rr;
-                    if constexpr (W8) b *= p.w_scale[n + N];
-                    const float gt = (float)(half_t)a, up = (float)(half_t)b;
-                    o = (float)(half_t)ds_silu(gt) * up;
-                } else {
-                    o = (float)(half_t)a;
-                    if (p.residual) o += (float)p.residual[(long)m * p.ldr + n];
+                float b = 0.f, sg = 1.0f, su = 1.0f;
+                if (SWIGLU) b = ((rp[1024 + tid] + rp[1280 + tid]) + rp[1536 + tid]) + rp[1792 + tid];
+                if constexpr (WL::ROW_SCALE) {
+                    sg = p.w_scale[n];
+                    if (SWIGLU) su = p.w_scale[n + N];
                 }
-                p.y[(long)m * p.ldy + n] = (half_t)o;
+                llm_proj_scale<WL, SWIGLU>(a, b, rr, sg, su);
+                p.y[(long)m * p.ldy + n] = llm_proj_out<SWIGLU>(a, b, p.residual ? p.residual + (long)m * p.ldr + n : nullptr);
             }
         }
         par ^= 1;
@@ -1164,16 +1126,24 @@ __global__ __launch_bounds__(256) void llm_dequant_fp4_kernel(const uint8_t* __r
 
 static thread_local int g_llm_gemv_variant = 0;  // 0 auto (pipelined), 1 one-column-per-wavefront kernel, 2 un-pipelined streaming kernel
 
-template <typename WT, int MC, int SWIGLU>
-int launch_gemv_stream(const LlmGemvParams& p, hipStream_t stream) {
-    static int cus = 0;
-    if (!cus) {
+// compute units of the device, asked once per process: the persistent kernels launch exactly their resident set
+int cu_count(int& cus) {
+    static int cached = 0;
+    if (!cached) {
         int dev = 0;
         hipDeviceProp_t prop;
         DS_HIP(hipGetDevice(&dev));
         DS_HIP(hipGetDeviceProperties(&prop, dev));
-        cus = prop.multiProcessorCount;
+        cached = prop.multiProcessorCount;
     }
+    cus = cached;
+    return 0;
+}
+
+template <typename WT, int MC, int SWIGLU>
+int launch_gemv_stream(const LlmGemvParams& p, hipStream_t stream) {
+    int cus;
+    if (const int rc = cu_count(cus)) return rc;
     const size_t lds = (size_t)MC * p.K * 2 + (size_t)MC * 5 * sizeof(float);
     // resident blocks per CU: 8 x 4 wavefronts at <= 64 VGPRs (streaming kernel), 5 at ~90 VGPRs (pipelined kernel; 4 for
     // MXFP4 at ~125); launching exactly the resident set makes every wavefront walk the same number of columns (no tail round)
@@ -1220,14 +1190,8 @@ constexpr int GEMM16_BLOCKS_PER_CU = 3;
 
 template <typename WT>
 int launch_gemm16(const LlmGemvParams& p, hipStream_t stream) {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        DS_HIP(hipGetDevice(&dev));
-        DS_HIP(hipGetDeviceProperties(&prop, dev));
-        cus = prop.multiProcessorCount;
-    }
+    int cus;
+    if (const int rc = cu_count(cus)) return rc;
     const size_t lds = (size_t)(2 * (p.swiglu ? 2 : 1) * 4 * 256 + 16) * sizeof(float) + (p.rms && p.gain ? (size_t)p.K * 2 : 0);
     // the resident set, as launch_gemv_stream sizes it: GEMM16_BLOCKS_PER_CU blocks of 4 wavefronts by registers
     const int per_cu = (int)min((size_t)GEMM16_BLOCKS_PER_CU, (size_t)(160 * 1024) / (lds + 512));
@@ -1255,22 +1219,32 @@ static int check_llm_fp4(const LlmGemvParams& p, const char* what) {
     return 0;
 }
 
+// From the operands to the weight type: p.w_exp says MXFP4, p.w_scale alone int8, neither fp16.  Checks what the format asks
+// of the shape, then calls f(a value of the WLoad element type, the format's name in messages - null for fp16).
+template <typename F>
+static int with_llm_weight_type(const LlmGemvParams& p, const char* what, F&& f) {
+    if (p.w_exp) {
+        if (const int rc = check_llm_fp4(p, what)) return rc;
+        return f(fp4x2_t{}, "MXFP4");
+    }
+    if (p.w_scale) {
+        if (const int rc = check_llm_w8(p, what)) return rc;
+        return f(int8_t{}, "int8");
+    }
+    return f(half_t{}, nullptr);
+}
+
 int ds_launch_llm_gemv(const LlmGemvParams& p, hipStream_t stream) {
     DS_REQUIRE(p.M > 0 && p.N > 0 && p.K >= 8 && p.K % 8 == 0, "llm_gemv: bad shape M=%d N=%d K=%d", p.M, p.N, p.K);
     DS_REQUIRE(p.ldx % 8 == 0 && p.ldx >= p.K, "llm_gemv: ldx %ld must be a multiple of 8 and >= K", p.ldx);
     DS_REQUIRE(p.x && p.w && p.y, "llm_gemv: null operand");
     DS_REQUIRE(!(p.swiglu && p.residual), "llm_gemv: the SwiGLU epilogue takes no residual");
-    if (p.w_exp) {
-        if (const int rc = check_llm_fp4(p, "llm_gemv")) return rc;
-        DS_REQUIRE(g_llm_gemv_variant != 2, "llm_gemv: llm_gemv_variant 2 (un-pipelined streaming kernel) has no MXFP4-weight form");
-        return p.swiglu ? launch_gemv<fp4x2_t, 1>(p, stream) : launch_gemv<fp4x2_t, 0>(p, stream);
-    }
-    if (p.w_scale) {
-        if (const int rc = check_llm_w8(p, "llm_gemv")) return rc;
-        DS_REQUIRE(g_llm_gemv_variant != 2, "llm_gemv: llm_gemv_variant 2 (un-pipelined streaming kernel) has no int8-weight form");
-        return p.swiglu ? launch_gemv<int8_t, 1>(p, stream) : launch_gemv<int8_t, 0>(p, stream);
-    }
-    return p.swiglu ? launch_gemv<half_t, 1>(p, stream) : launch_gemv<half_t, 0>(p, stream);
+    return with_llm_weight_type(p, "llm_gemv", [&](auto wt, const char* quantised) {
+        typedef decltype(wt) WT;
+        DS_REQUIRE(!quantised || g_llm_gemv_variant != 2,
+                   "llm_gemv: llm_gemv_variant 2 (un-pipelined streaming kernel) has no %s-weight form", quantised);
+        return p.swiglu ? launch_gemv<WT, 1>(p, stream) : launch_gemv<WT, 0>(p, stream);
+    });
 }
 
 int ds_launch_llm_gemm16(const LlmGemvParams& p, hipStream_t stream) {
@@ -1280,15 +1254,7 @@ int ds_launch_llm_gemm16(const LlmGemvParams& p, hipStream_t stream) {
     DS_REQUIRE(p.x && p.w && p.y, "llm_gemm16: null operand");
     DS_REQUIRE(!(p.swiglu && p.residual), "llm_gemm16: the SwiGLU epilogue takes no residual");
     DS_REQUIRE(!(p.rms && p.gain) || p.K <= 20480, "llm_gemm16: K %d too long for the gain vector in LDS (20480)", p.K);
-    if (p.w_exp) {
-        if (const int rc = check_llm_fp4(p, "llm_gemm16")) return rc;
-        return launch_gemm16<fp4x2_t>(p, stream);
-    }
-    if (p.w_scale) {
-        if (const int rc = check_llm_w8(p, "llm_gemm16")) return rc;
-        return launch_gemm16<int8_t>(p, stream);
-    }
-    return launch_gemm16<half_t>(p, stream);
+    return with_llm_weight_type(p, "llm_gemm16", [&](auto wt, const char*) { return launch_gemm16<decltype(wt)>(p, stream); });
 }
 
 int ds_launch_llm_dequant_w8(const int8_t* q, const float* scale, half_t* w16, long N, int K, hipStream_t stream) {
@@ -1341,36 +1307,41 @@ static int check_llm_attn(const LlmAttnParams& p) {
     return 0;
 }
 
-int ds_launch_llm_attn(const LlmAttnParams& p, hipStream_t stream) {
-    DS_REQUIRE(p.M > 0 && p.M <= 16, "llm_attn: %d rows per pass (1..16)", p.M);
+// Both attention kernel families have the same instantiations, block shape and LDS: one block of 1024 threads per (head, row),
+// T_max + 16 D + 32 floats (at most 41 KB at T_max 8192).  Picks <D, KV8> and calls launch(D, KV8 as integral constants,
+// grid, block, lds), which names the family and adds its own arguments.
+template <typename F>
+static int launch_llm_attn_form(const LlmAttnParams& p, F&& launch) {
     if (const int rc = check_llm_attn(p)) return rc;
     const size_t lds = (size_t)(p.T_max + ATT_WAVES * p.D + 2 * ATT_WAVES) * sizeof(float);
     const dim3 grid(p.heads, p.M);
     const dim3 block(64 * ATT_WAVES);
-    if (p.D == 128 && p.kv8) hipLaunchKernelGGL((llm_attn_kernel<128, true>), grid, block, lds, stream, p);
-    else if (p.D == 128) hipLaunchKernelGGL((llm_attn_kernel<128, false>), grid, block, lds, stream, p);
-    else if (p.kv8) hipLaunchKernelGGL((llm_attn_kernel<64, true>), grid, block, lds, stream, p);
-    else hipLaunchKernelGGL((llm_attn_kernel<64, false>), grid, block, lds, stream, p);
+    typedef std::integral_constant<int, 128> D128;
+    typedef std::integral_constant<int, 64> D64;
+    if (p.D == 128 && p.kv8) launch(D128{}, std::true_type{}, grid, block, lds);
+    else if (p.D == 128) launch(D128{}, std::false_type{}, grid, block, lds);
+    else if (p.kv8) launch(D64{}, std::true_type{}, grid, block, lds);
+    else launch(D64{}, std::false_type{}, grid, block, lds);
     DS_LAUNCH_CHECK();
     return 0;
 }
 
+int ds_launch_llm_attn(const LlmAttnParams& p, hipStream_t stream) {
+    DS_REQUIRE(p.M > 0 && p.M <= 16, "llm_attn: %d rows per pass (1..16)", p.M);
+    return launch_llm_attn_form(p, [&](auto d, auto kv8, dim3 grid, dim3 block, size_t lds) {
+        hipLaunchKernelGGL((llm_attn_kernel<decltype(d)::value, decltype(kv8)::value>), grid, block, lds, stream, p);
+    });
+}
+
 // p in the slot form (state_stride 8, the slot strides), p.M = rows of qkv / out = entries of `table` (device int32 [M][2]).
-// Same block shape and LDS as llm_attn_kernel: 1024 threads, T_max + 16 D + 32 floats (at most 41 KB at T_max 8192).
 int ds_launch_llm_attn_rows(const LlmAttnParams& p, const int* table, int n_slots, hipStream_t stream) {
     DS_REQUIRE(p.M > 0 && p.M <= 65535, "llm_attn_rows: %d rows (1..65535)", p.M);
     DS_REQUIRE(table && n_slots > 0, "llm_attn_rows: the row table and the number of slots are needed");
     DS_REQUIRE(p.state_stride == 8, "llm_attn_rows: the slot form's state block is needed (stride %d)", p.state_stride);
-    if (const int rc = check_llm_attn(p)) return rc;
-    const size_t lds = (size_t)(p.T_max + ATT_WAVES * p.D + 2 * ATT_WAVES) * sizeof(float);
-    const dim3 grid(p.heads, p.M);
-    const dim3 block(64 * ATT_WAVES);
-    if (p.D == 128 && p.kv8) hipLaunchKernelGGL((llm_attn_rows_kernel<128, true>), grid, block, lds, stream, p, table, n_slots);
-    else if (p.D == 128) hipLaunchKernelGGL((llm_attn_rows_kernel<128, false>), grid, block, lds, stream, p, table, n_slots);
-    else if (p.kv8) hipLaunchKernelGGL((llm_attn_rows_kernel<64, true>), grid, block, lds, stream, p, table, n_slots);
-    else hipLaunchKernelGGL((llm_attn_rows_kernel<64, false>), grid, block, lds, stream, p, table, n_slots);
-    DS_LAUNCH_CHECK();
-    return 0;
+    return launch_llm_attn_form(p, [&](auto d, auto kv8, dim3 grid, dim3 block, size_t lds) {
+        hipLaunchKernelGGL((llm_attn_rows_kernel<decltype(d)::value, decltype(kv8)::value>), grid, block, lds, stream, p, table,
+                           n_slots);
+    });
 }
 
 int ds_launch_llm_rmsnorm(const half_t* x, long ldx, const half_t* gamma, half_t* y, long ldy, half_t* feat,

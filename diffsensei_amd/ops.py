@@ -914,32 +914,69 @@ def llm_gemv(x: Tensor, w: Tensor, out: Optional[Tensor] = None, residual: Optio
     `gain` [K] the reference's roundings (f16(gain * f16(x / rms))), without it only the 1/rms scale (gain folded into w by
     the caller).  `residual` may be `out` itself (in-place h += ...)."""
     _chk(x, w, residual, gain)
-    M, K = x.shape
-    N = w.shape[0] // (2 if swiglu else 1)
-    assert w.shape[1] == K
+    assert w.shape[1] == x.shape[1]
+    return _llm_proj("ds_llm_gemv_f16", False, x, w, (), out, residual, rms, swiglu, eps, gain)
+
+
+def _llm_proj(entry: str, strided: bool, x: Tensor, w: Tensor, extra: tuple, out: Optional[Tensor], residual: Optional[Tensor],
+              rms: bool, swiglu: bool, eps: float, gain: Optional[Tensor], M: Optional[int] = None,
+              N: Optional[int] = None) -> Tensor:
+    """The body of the six projection wrappers, which check their operands' types first.  `entry`: the library's entry
+    point; `extra`: the weight format's operands behind eps (w_scale, w_exp).  The gemv family (`strided` false) takes whole
+    contiguous tensors and passes K / N as leading dimensions; the gemm16 family takes the `M` / `N` restrictions and passes
+    row strides."""
+    K = x.shape[1]
+    rows = w.shape[0] // (2 if swiglu else 1)
+    M = x.shape[0] if M is None else int(M)
+    N = rows if N is None else int(N)
+    if strided:
+        assert 0 < M <= x.shape[0] and 0 < N <= rows and (not swiglu or N == rows)
     if out is None:
         out = torch.empty((M, N), dtype=torch.float16, device=x.device)
     _chk(out)
-    check(_lib.load().ds_llm_gemv_f16(_p(x), K, _p(w), _p(out), N, _p(residual), N, M, N, K, int(rms), _p(gain),
-                                      int(swiglu), eps, _stream()), "ds_llm_gemv_f16")
+    ldx, ldy, ldr = K, N, N
+    if strided:
+        assert out.dim() == 2 and out.stride(1) == 1 and out.shape[0] >= M and out.shape[1] >= N
+        ldx, ldy, ldr = x.stride(0), out.stride(0), 0
+        if residual is not None:
+            assert residual.dim() == 2 and residual.stride(1) == 1 and residual.shape[0] >= M and residual.shape[1] >= N
+            ldr = residual.stride(0)
+    check(getattr(_lib.load(), entry)(_p(x), ldx, _p(w), _p(out), ldy, _p(residual), ldr, M, N, K, int(rms), _p(gain),
+                                      int(swiglu), eps, *(_p(t) for t in extra), _stream()), entry)
     return out
 
 
 def llm_attention(qkv: Tensor, k_cache: Tensor, v_cache: Tensor, rope_cos: Tensor, rope_sin: Tensor, state: Tensor,
                   heads: int, kv_heads: int, scale: float, out: Optional[Tensor] = None) -> Tensor:
     """qkv: [M,(heads+2*kv_heads)*D] un-rotated; caches [T_max, kv_heads*D]; appends the M rows at state[0].."""
-    _chk(qkv, k_cache, v_cache)
+    return _llm_attn(False, qkv, k_cache, v_cache, None, rope_cos, rope_sin, state, heads, kv_heads, scale, out)
+
+
+def _llm_attn(slots: bool, qkv: Tensor, k_cache: Tensor, v_cache: Tensor, exps: Optional[tuple], rope_cos: Tensor,
+              rope_sin: Tensor, state: Tensor, heads: int, kv_heads: int, scale: float, out: Optional[Tensor]) -> Tensor:
+    """The body of llm_attention, llm_attention_slots and their fp8-cache forms (`exps`: (k_exp, v_exp), or None for fp16
+    caches).  `slots`: one cache [T_max, ...] per row of qkv behind a leading slot dimension, and state int32 [S, 8]."""
+    _chk(qkv)
     _chk(rope_cos, rope_sin, dtype=torch.float32)
     _chk(state, dtype=torch.int32)
     M = qkv.shape[0]
     D = qkv.shape[1] // (heads + 2 * kv_heads)
-    T_max = k_cache.shape[0]
-    assert rope_cos.shape == (T_max, D // 2) and k_cache.shape[1] == kv_heads * D
+    T_max = k_cache.shape[-2]
+    lead = (M, T_max) if slots else (T_max,)
+    if exps is not None:
+        _chk_kv8(k_cache, v_cache, *exps, lead, kv_heads, D)
+    else:
+        _chk(k_cache, v_cache)
+        assert k_cache.shape == v_cache.shape == lead + (kv_heads * D,)
+    assert rope_cos.shape == (T_max, D // 2) and (not slots or state.shape == (M, 8))
     if out is None:
         out = torch.empty((M, heads * D), dtype=torch.float16, device=qkv.device)
-    check(_lib.load().ds_llm_attn_f16(_p(qkv), qkv.shape[1], _p(k_cache), _p(v_cache), k_cache.shape[1], _p(rope_cos),
-                                      _p(rope_sin), _p(out), heads * D, _p(state), M, heads, kv_heads, D, T_max, scale,
-                                      _stream()), "ds_llm_attn_f16")
+    entry = "ds_llm_attn" + ("_slots" if slots else "") + ("_f16" if exps is None else "_kv8")
+    cache = (_p(k_cache), _p(v_cache), k_cache.shape[-1]) + ((k_cache.stride(0),) if slots else ())
+    if exps is not None:   # the exponent planes: rows of kv_heads bytes, per slot behind the caches' slot stride
+        cache += (_p(exps[0]), _p(exps[1]), kv_heads) + ((exps[0].stride(0),) if slots else ())
+    check(getattr(_lib.load(), entry)(_p(qkv), qkv.shape[1], *cache, _p(rope_cos), _p(rope_sin), _p(out), heads * D, _p(state),
+                                      M, heads, kv_heads, D, T_max, scale, _stream()), entry)
     return out
 
 
@@ -1002,22 +1039,8 @@ def llm_gemm16(x: Tensor, w: Tensor, out: Optional[Tensor] = None, residual: Opt
     may be larger than [M, N] (their row stride is used; rows past M and columns past N stay untouched); `M` / `N`
     restrict the call to the first rows of `x` / weight rows of `w` (swiglu: `w` must then hold exactly 2N rows)."""
     _chk(x, w, residual, gain)
-    K = x.shape[1]
-    M = x.shape[0] if M is None else int(M)
-    rows = w.shape[0] // (2 if swiglu else 1)
-    N = rows if N is None else int(N)
-    assert w.shape[1] == K and 0 < M <= x.shape[0] and 0 < N <= rows and (not swiglu or N == rows)
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.float16, device=x.device)
-    _chk(out)
-    assert out.dim() == 2 and out.stride(1) == 1 and out.shape[0] >= M and out.shape[1] >= N
-    ldr = 0
-    if residual is not None:
-        assert residual.dim() == 2 and residual.stride(1) == 1 and residual.shape[0] >= M and residual.shape[1] >= N
-        ldr = residual.stride(0)
-    check(_lib.load().ds_llm_gemm16(_p(x), x.stride(0), _p(w), _p(out), out.stride(0), _p(residual), ldr, M, N, K,
-                                    int(rms), _p(gain), int(swiglu), eps, _stream()), "ds_llm_gemm16")
-    return out
+    assert w.shape[1] == x.shape[1]
+    return _llm_proj("ds_llm_gemm16", True, x, w, (), out, residual, rms, swiglu, eps, gain, M, N)
 
 
 # ---- int8 weight-only decoding (W8A16): the twins of llm_gemv / llm_gemm16 with int8 weights + fp32 row scales -----------
@@ -1037,14 +1060,7 @@ def llm_gemv_w8(x: Tensor, w: Tensor, w_scale: Tensor, out: Optional[Tensor] = N
     """`llm_gemv` with int8 weights: w int8 [N,K] (swiglu: [2N,K]), w_scale fp32 [N] ([2N]); y = (x' . q[n]) * w_scale[n]."""
     _chk(x, residual, gain)
     _chk_w8(x, w, w_scale, swiglu)
-    M, K = x.shape
-    N = w.shape[0] // (2 if swiglu else 1)
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.float16, device=x.device)
-    _chk(out)
-    check(_lib.load().ds_llm_gemv_w8(_p(x), K, _p(w), _p(out), N, _p(residual), N, M, N, K, int(rms), _p(gain),
-                                     int(swiglu), eps, _p(w_scale), _stream()), "ds_llm_gemv_w8")
-    return out
+    return _llm_proj("ds_llm_gemv_w8", False, x, w, (w_scale,), out, residual, rms, swiglu, eps, gain)
 
 
 def llm_gemm16_w8(x: Tensor, w: Tensor, w_scale: Tensor, out: Optional[Tensor] = None, residual: Optional[Tensor] = None,
@@ -1053,22 +1069,7 @@ def llm_gemm16_w8(x: Tensor, w: Tensor, w_scale: Tensor, out: Optional[Tensor] =
     """`llm_gemm16` with int8 weights and fp32 row scales (`N` restricts the call to the first N rows of w / w_scale)."""
     _chk(x, residual, gain)
     _chk_w8(x, w, w_scale, swiglu)
-    K = x.shape[1]
-    M = x.shape[0] if M is None else int(M)
-    rows = w.shape[0] // (2 if swiglu else 1)
-    N = rows if N is None else int(N)
-    assert 0 < M <= x.shape[0] and 0 < N <= rows and (not swiglu or N == rows)
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.float16, device=x.device)
-    _chk(out)
-    assert out.dim() == 2 and out.stride(1) == 1 and out.shape[0] >= M and out.shape[1] >= N
-    ldr = 0
-    if residual is not None:
-        assert residual.dim() == 2 and residual.stride(1) == 1 and residual.shape[0] >= M and residual.shape[1] >= N
-        ldr = residual.stride(0)
-    check(_lib.load().ds_llm_gemm16_w8(_p(x), x.stride(0), _p(w), _p(out), out.stride(0), _p(residual), ldr, M, N, K,
-                                       int(rms), _p(gain), int(swiglu), eps, _p(w_scale), _stream()), "ds_llm_gemm16_w8")
-    return out
+    return _llm_proj("ds_llm_gemm16_w8", True, x, w, (w_scale,), out, residual, rms, swiglu, eps, gain, M, N)
 
 
 def llm_dequant_w8(w: Tensor, w_scale: Tensor, out: Optional[Tensor] = None) -> Tensor:
@@ -1108,14 +1109,7 @@ def llm_gemv_fp4(x: Tensor, w: Tensor, w_exp: Tensor, w_scale: Tensor, out: Opti
     w_scale fp32 [N]; y = (x' . (e2m1 * 2^(w_exp-127))[n]) * w_scale[n]."""
     _chk(x, residual, gain)
     _chk_fp4(x, w, w_exp, w_scale, swiglu)
-    M, K = x.shape
-    N = w.shape[0] // (2 if swiglu else 1)
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.float16, device=x.device)
-    _chk(out)
-    check(_lib.load().ds_llm_gemv_fp4(_p(x), K, _p(w), _p(out), N, _p(residual), N, M, N, K, int(rms), _p(gain),
-                                      int(swiglu), eps, _p(w_scale), _p(w_exp), _stream()), "ds_llm_gemv_fp4")
-    return out
+    return _llm_proj("ds_llm_gemv_fp4", False, x, w, (w_scale, w_exp), out, residual, rms, swiglu, eps, gain)
 
 
 def llm_gemm16_fp4(x: Tensor, w: Tensor, w_exp: Tensor, w_scale: Tensor, out: Optional[Tensor] = None,
@@ -1124,23 +1118,7 @@ def llm_gemm16_fp4(x: Tensor, w: Tensor, w_exp: Tensor, w_scale: Tensor, out: Op
     """`llm_gemm16` with MXFP4 weights (`N` restricts the call to the first N rows of w / w_exp / w_scale)."""
     _chk(x, residual, gain)
     _chk_fp4(x, w, w_exp, w_scale, swiglu)
-    K = x.shape[1]
-    M = x.shape[0] if M is None else int(M)
-    rows = w.shape[0] // (2 if swiglu else 1)
-    N = rows if N is None else int(N)
-    assert 0 < M <= x.shape[0] and 0 < N <= rows and (not swiglu or N == rows)
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.float16, device=x.device)
-    _chk(out)
-    assert out.dim() == 2 and out.stride(1) == 1 and out.shape[0] >= M and out.shape[1] >= N
-    ldr = 0
-    if residual is not None:
-        assert residual.dim() == 2 and residual.stride(1) == 1 and residual.shape[0] >= M and residual.shape[1] >= N
-        ldr = residual.stride(0)
-    check(_lib.load().ds_llm_gemm16_fp4(_p(x), x.stride(0), _p(w), _p(out), out.stride(0), _p(residual), ldr, M, N, K,
-                                        int(rms), _p(gain), int(swiglu), eps, _p(w_scale), _p(w_exp), _stream()),
-          "ds_llm_gemm16_fp4")
-    return out
+    return _llm_proj("ds_llm_gemm16_fp4", True, x, w, (w_scale, w_exp), out, residual, rms, swiglu, eps, gain, M, N)
 
 
 def llm_dequant_fp4(w: Tensor, w_exp: Tensor, w_scale: Tensor, out: Optional[Tensor] = None) -> Tensor:
@@ -1164,20 +1142,7 @@ def llm_attention_slots(qkv: Tensor, k_cache: Tensor, v_cache: Tensor, rope_cos:
                         heads: int, kv_heads: int, scale: float, out: Optional[Tensor] = None) -> Tensor:
     """One new row per slot: qkv [S,(heads+2*kv_heads)*D]; caches [S, T_max, kv_heads*D]; state int32 [S, 8].  Slot s
     appends at state[s][0] in its own cache; a slot with state[s][2] set is left alone."""
-    _chk(qkv, k_cache, v_cache)
-    _chk(rope_cos, rope_sin, dtype=torch.float32)
-    _chk(state, dtype=torch.int32)
-    S = qkv.shape[0]
-    D = qkv.shape[1] // (heads + 2 * kv_heads)
-    T_max = k_cache.shape[1]
-    assert k_cache.shape == v_cache.shape == (S, T_max, kv_heads * D) and state.shape == (S, 8)
-    assert rope_cos.shape == (T_max, D // 2)
-    if out is None:
-        out = torch.empty((S, heads * D), dtype=torch.float16, device=qkv.device)
-    check(_lib.load().ds_llm_attn_slots_f16(_p(qkv), qkv.shape[1], _p(k_cache), _p(v_cache), k_cache.shape[2],
-                                            k_cache.stride(0), _p(rope_cos), _p(rope_sin), _p(out), heads * D, _p(state),
-                                            S, heads, kv_heads, D, T_max, scale, _stream()), "ds_llm_attn_slots_f16")
-    return out
+    return _llm_attn(True, qkv, k_cache, v_cache, None, rope_cos, rope_sin, state, heads, kv_heads, scale, out)
 
 
 def _chk_kv8(k_cache: Tensor, v_cache: Tensor, k_exp: Tensor, v_exp: Tensor, lead: tuple, kv_heads: int, D: int) -> None:
@@ -1195,41 +1160,14 @@ def llm_attention_kv8(qkv: Tensor, k_cache: Tensor, v_cache: Tensor, k_exp: Tens
     """`llm_attention` on the fp8 KV cache (mllm.quantize_kv_fp8): caches uint8 [T_max, kv_heads*D] of e4m3 codes, exponents
     uint8 [T_max, kv_heads]; appends the codes and exponent bytes of the M rows at state[0].. and attends over the dequantised
     cache, the rows of this launch included."""
-    _chk(qkv)
-    _chk(rope_cos, rope_sin, dtype=torch.float32)
-    _chk(state, dtype=torch.int32)
-    M = qkv.shape[0]
-    D = qkv.shape[1] // (heads + 2 * kv_heads)
-    T_max = k_cache.shape[0]
-    _chk_kv8(k_cache, v_cache, k_exp, v_exp, (T_max,), kv_heads, D)
-    assert rope_cos.shape == (T_max, D // 2)
-    if out is None:
-        out = torch.empty((M, heads * D), dtype=torch.float16, device=qkv.device)
-    check(_lib.load().ds_llm_attn_kv8(_p(qkv), qkv.shape[1], _p(k_cache), _p(v_cache), k_cache.shape[1], _p(k_exp), _p(v_exp),
-                                      kv_heads, _p(rope_cos), _p(rope_sin), _p(out), heads * D, _p(state), M, heads, kv_heads,
-                                      D, T_max, scale, _stream()), "ds_llm_attn_kv8")
-    return out
+    return _llm_attn(False, qkv, k_cache, v_cache, (k_exp, v_exp), rope_cos, rope_sin, state, heads, kv_heads, scale, out)
 
 
 def llm_attention_slots_kv8(qkv: Tensor, k_cache: Tensor, v_cache: Tensor, k_exp: Tensor, v_exp: Tensor, rope_cos: Tensor,
                             rope_sin: Tensor, state: Tensor, heads: int, kv_heads: int, scale: float,
                             out: Optional[Tensor] = None) -> Tensor:
     """`llm_attention_slots` on the fp8 KV cache: caches uint8 [S, T_max, kv_heads*D], exponents uint8 [S, T_max, kv_heads]."""
-    _chk(qkv)
-    _chk(rope_cos, rope_sin, dtype=torch.float32)
-    _chk(state, dtype=torch.int32)
-    S = qkv.shape[0]
-    D = qkv.shape[1] // (heads + 2 * kv_heads)
-    T_max = k_cache.shape[1]
-    _chk_kv8(k_cache, v_cache, k_exp, v_exp, (S, T_max), kv_heads, D)
-    assert state.shape == (S, 8) and rope_cos.shape == (T_max, D // 2)
-    if out is None:
-        out = torch.empty((S, heads * D), dtype=torch.float16, device=qkv.device)
-    check(_lib.load().ds_llm_attn_slots_kv8(_p(qkv), qkv.shape[1], _p(k_cache), _p(v_cache), k_cache.shape[2], k_cache.stride(0),
-                                            _p(k_exp), _p(v_exp), kv_heads, k_exp.stride(0), _p(rope_cos), _p(rope_sin),
-                                            _p(out), heads * D, _p(state), S, heads, kv_heads, D, T_max, scale, _stream()),
-          "ds_llm_attn_slots_kv8")
-    return out
+    return _llm_attn(True, qkv, k_cache, v_cache, (k_exp, v_exp), rope_cos, rope_sin, state, heads, kv_heads, scale, out)
 
 
 def llm_rmsnorm_slots(x: Tensor, gamma: Tensor, eps: float, out: Optional[Tensor] = None, feat: Optional[Tensor] = None,

@@ -132,3 +132,53 @@ def test_image_token_ids_follow_the_reference_tokenizer_convention():
         M.image_token_ids(None, n, ref_chain[:10])
     with pytest.raises(ValueError):
         M.image_token_ids(None, n)
+
+
+# (op, what its ints mean, kernel name, flops, bytes) as the library answered before the projection and attention cases of
+# ds_op_describe were folded into one group each: every LLM op code, the projections once per weight format and epilogue
+_DESCRIBE_INTS = {"proj": (3, 520, 736, 1, 0), "proj_swiglu": (3, 520, 738, 1, 1), "attn": (5, 8, 4, 128, 96, 3),
+                  "row": (4, 512, 7, 0, 3, 1)}
+_DESCRIBE = [
+    ("LLM_GEMV", "proj", "llm_gemv_kernel", 2296320.0, 772976.0),
+    ("LLM_GEMV", "proj_swiglu", "llm_gemv_kernel", 4605120.0, 1542588.0),
+    ("LLM_ATTN", "attn", "llm_attn_kernel", 0.0, 0.0),
+    ("LLM_RMSNORM", "row", "llm_rmsnorm_kernel", 0.0, 8192.0),
+    ("LLM_EMBED", "row", "other", 0.0, 0.0),
+    ("LLM_SELECT", "row", "llm_select_kernel", 0.0, 8.0),
+    ("LLM_ADVANCE", "row", "other", 0.0, 0.0),
+    ("LLM_GEMM16", "proj", "llm_gemm16_kernel", 2296320.0, 772976.0),
+    ("LLM_GEMM16", "proj_swiglu", "llm_gemm16_kernel", 4605120.0, 1542588.0),
+    ("LLM_ATTN_SLOTS", "attn", "llm_attn_kernel", 0.0, 0.0),
+    ("LLM_RMSNORM_SLOTS", "row", "llm_rmsnorm_kernel", 0.0, 8192.0),
+    ("LLM_EMBED_SLOTS", "row", "other", 0.0, 0.0),
+    ("LLM_SELECT_SLOTS", "row", "llm_select_kernel", 0.0, 24.0),
+    ("LLM_GEMV_W8", "proj", "llm_gemv_kernel", 2296320.0, 392336.0),
+    ("LLM_GEMV_W8", "proj_swiglu", "llm_gemv_kernel", 4605120.0, 779228.0),
+    ("LLM_GEMM16_W8", "proj", "llm_gemm16_kernel", 2296320.0, 392336.0),
+    ("LLM_GEMM16_W8", "proj_swiglu", "llm_gemm16_kernel", 4605120.0, 779228.0),
+    ("LLM_GEMV_FP4", "proj", "llm_gemv_kernel", 2296320.0, 212936.0),
+    ("LLM_GEMV_FP4", "proj_swiglu", "llm_gemv_kernel", 4605120.0, 419453.0),
+    ("LLM_GEMM16_FP4", "proj", "llm_gemm16_kernel", 2296320.0, 212936.0),
+    ("LLM_GEMM16_FP4", "proj_swiglu", "llm_gemm16_kernel", 4605120.0, 419453.0),
+    ("LLM_ATTN_KV8", "attn", "llm_attn_kernel", 0.0, 99072.0),
+    ("LLM_ATTN_SLOTS_KV8", "attn", "llm_attn_kernel", 0.0, 495360.0),
+    ("LLM_ATTN_ROWS", "attn", "llm_attn_rows_kernel", 0.0, 0.0),
+    ("LLM_ATTN_ROWS_KV8", "attn", "llm_attn_rows_kernel", 0.0, 297216.0),
+]
+
+
+def test_op_describe_of_every_llm_op_is_the_recorded_answer():
+    """host-only query: the same name and the same two doubles, bit for bit (K = 738: a block count that is no integer)"""
+    import ctypes as C
+
+    from diffsensei_amd import _lib
+    lib = _lib.load()
+    assert {r[0] for r in _DESCRIBE} == {n for n in _lib.OP if n.startswith("LLM_")}
+    for code, ints, name, flops, nbytes in _DESCRIBE:
+        op = _lib.DsOp()
+        op.code = _lib.OP[code]
+        for j, v in enumerate(_DESCRIBE_INTS[ints]):
+            op.i[j] = v
+        buf, fl, by = C.create_string_buffer(96), C.c_double(), C.c_double()
+        assert lib.ds_op_describe(C.byref(op), buf, 96, C.byref(fl), C.byref(by)) == 0
+        assert (buf.value.decode(), fl.value, by.value) == (name, flops, nbytes), (code, ints)
