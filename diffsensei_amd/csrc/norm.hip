@@ -112,6 +112,8 @@ __global__ __launch_bounds__(512) void gn_stats_kernel(GroupNormParams p) {
 // one block per (batch item, group): 256 lanes walk the group's nchunks x cpg partial pairs, four independent 8-byte loads
 // in flight per lane (one wave per group with one load in flight took 35 us per launch - 80 dependent round trips - whatever
 // the batch: 5 % of a batch-2 forward)
+// One-pass statistics (fp32 partial sums, var = E[x^2] - mean^2, clamped at 0): the 3e-3 of the GroupNorm tests holds through a
+// group mean of 64 standard deviations (bf16: 32); ~2e-3 at 128, ~1e-2 at 256 (tests/test_gpu_norm_conditioning.py).
 template <typename T>
 __global__ __launch_bounds__(256) void gn_finalize_kernel(GroupNormParams p, int nchunks) {
     __shared__ float red[8];
