@@ -7,7 +7,7 @@ Also the `cpu_baseline` workload of bench.py: BASELINE.json configs[0] — 512x5
 from __future__ import annotations
 
 import time
-from typing import Callable, Optional
+from typing import Callable, Optional, Sequence
 
 import torch
 
@@ -20,16 +20,20 @@ _h = lambda t: t.half().float()
 
 def sample_loop(unet: UNetOracle, scheduler, latents: torch.Tensor, enc: torch.Tensor, text_embeds: torch.Tensor,
                 time_ids: torch.Tensor, bbox: torch.Tensor, dialog_bbox: Optional[torch.Tensor], guidance_scale: float,
-                num_steps: int, ip_scale: float, q: Callable = _id, max_steps: Optional[int] = None) -> torch.Tensor:
+                num_steps: int, ip_scale: float, q: Callable = _id, max_steps: Optional[int] = None,
+                record: Optional[Sequence[int]] = None):
     """latents: [ns,4,H,W] already multiplied by init_noise_sigma; enc/text_embeds/time_ids/bbox/dialog_bbox are the
     CFG-concatenated ([neg..., pos...]) tensors of reference :294-303.  guidance_scale <= 1 (`do_classifier_free_guidance`
     False, reference :315, :333): the conditional rows only - the caller passes `num_samples` rows, and for `bbox` the
-    FIRST `num_samples` rows of cat([negative_ip_bbox, ip_bbox]) like the reference's mask builder ends up using."""
+    FIRST `num_samples` rows of cat([negative_ip_bbox, ip_bbox]) like the reference's mask builder ends up using.
+    record: step counts k; the return value is then (final latents, {k: the latents after k steps}) - snapshots of the one
+    pass, not one rerun per snapshot."""
     scheduler.set_timesteps(num_steps)
     unet.ip_scale = ip_scale
     x = q(latents.float())
     ar = latents.shape[-2] / latents.shape[-1]
     n = num_steps if max_steps is None else min(num_steps, max_steps)
+    snaps = {}
     for i in range(n):
         t = float(scheduler.timesteps[i])
         do_cfg = guidance_scale > 1
@@ -42,7 +46,9 @@ def sample_loop(unet: UNetOracle, scheduler, latents: torch.Tensor, enc: torch.T
         else:
             e = eps
         x = q(scheduler.step(e, i, x))                             # :337
-    return x
+        if record is not None and i + 1 in record:
+            snaps[i + 1] = x.clone()
+    return x if record is None else (x, snaps)
 
 
 def time_cpu_baseline(cfg, sd, height: int = 512, width: int = 512, steps: int = 20, budget_s: float = 25.0,

@@ -12,6 +12,12 @@ import numpy as np
 import torch
 
 
+def _up(x: torch.Tensor) -> torch.Tensor:
+    """The sample as the update sees it: fp32 like diffusers' upcast; a float64 sample stays float64 (the free-running
+    float64 loops of tests/_loop_cases.py), the 0-dim fp32 scalars below then enter exactly."""
+    return x if x.dtype == torch.float64 else x.float()
+
+
 def _alphas_cumprod(num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012) -> torch.Tensor:
     betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
     return torch.cumprod(1.0 - betas, dim=0)
@@ -44,8 +50,8 @@ class EulerDiscreteOracle:
     def step(self, eps: torch.Tensor, i: int, x: torch.Tensor) -> torch.Tensor:
         s = torch.tensor(self.sigmas[i], dtype=torch.float32)
         s_next = torch.tensor(self.sigmas[i + 1], dtype=torch.float32)
-        x32 = x.float()
-        pred_x0 = x32 - s * eps.float()
+        x32 = _up(x)
+        pred_x0 = x32 - s * _up(eps)
         derivative = (x32 - pred_x0) / s
         return x32 + derivative * (s_next - s)
 
@@ -74,7 +80,7 @@ class DDIMOracle:
         prev_t = t - self.T // self.n
         a_t = self.alphas_cumprod[t]
         a_prev = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
-        x32, e32 = x.float(), eps.float()
+        x32, e32 = _up(x), _up(eps)
         pred_x0 = (x32 - (1 - a_t) ** 0.5 * e32) / a_t ** 0.5
         return a_prev ** 0.5 * pred_x0 + (1 - a_prev) ** 0.5 * e32
 

@@ -23,7 +23,11 @@ def _alphas_cumprod(T=1000, beta_start=0.00085, beta_end=0.012) -> np.ndarray:
 class DPMSolverOracle:
     def __init__(self, solver_order=2, solver_type="midpoint", use_karras_sigmas=False, timestep_spacing="leading",
                  steps_offset=1, final_sigmas_type="zero", lower_order_final=True, euler_at_final=False,
-                 num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012):
+                 num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, q=_h, q_out=None):
+        """q: the rounding at diffusers' fp16 points (default: an fp16 round trip).  The identity gives the update the
+        rounded one approximates, in the sample's own dtype (the free-running float64 loops of tests/_loop_cases.py).
+        q_out: the rounding of the stored sample alone (default: q)."""
+        self.q, self.q_out = q, (q if q_out is None else q_out)
         self.solver_order, self.solver_type = solver_order, solver_type
         self.karras, self.spacing, self.offset = use_karras_sigmas, timestep_spacing, steps_offset
         self.final, self.lower_order_final, self.euler_at_final = final_sigmas_type, lower_order_final, euler_at_final
@@ -102,11 +106,13 @@ class DPMSolverOracle:
     def step(self, eps: torch.Tensor, i: int, x: torch.Tensor) -> torch.Tensor:
         order = self.orders[i]
         s_s, a_s, a, b, inv_r0, c = self.coefficients(i, order)
-        x16, e = _h(x.float()), _h(eps.float())
-        x0 = _h(_h(x16 - _h(s_s * e)) / a_s)
-        out = a * x16 - _h(b * x0)
+        q = self.q
+        up = lambda t: t if t.dtype == torch.float64 else t.float()
+        x16, e = q(up(x)), q(up(eps))
+        x0 = q(q(x16 - q(s_s * e)) / a_s)
+        out = a * x16 - q(b * x0)
         if order == 2:
-            d1 = _h(_h(x0 - self.prev_x0) * inv_r0)
-            out = out - _h(c * d1) if self.solver_type == "midpoint" else out + _h(c * d1)
+            d1 = q(q(x0 - self.prev_x0) * inv_r0)
+            out = out - q(c * d1) if self.solver_type == "midpoint" else out + q(c * d1)
         self.prev_x0 = x0
-        return _h(out)
+        return self.q_out(out)

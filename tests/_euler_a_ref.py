@@ -24,7 +24,10 @@ def _alphas_cumprod(T=1000, beta_start=0.00085, beta_end=0.012) -> np.ndarray:
 
 class EulerAncestralOracle:
     def __init__(self, seeds=None, timestep_spacing="leading", steps_offset=1, num_train_timesteps=1000,
-                 beta_start=0.00085, beta_end=0.012):
+                 beta_start=0.00085, beta_end=0.012, exact=False):
+        """exact: no fp16 rounding of the noise or of `noise * sigma_up`, and a float64 sample stays float64 - the update
+        the rounded one approximates (the free-running float64 loops of tests/_loop_cases.py)."""
+        self.exact = bool(exact)
         self.seeds = None if seeds is None else [int(s) for s in seeds]
         self.spacing, self.offset, self.T = timestep_spacing, steps_offset, num_train_timesteps
         self.ac = _alphas_cumprod(num_train_timesteps, beta_start, beta_end)
@@ -77,14 +80,15 @@ class EulerAncestralOracle:
         """fp16 noise of step i for panels [ns,4,H,W]: the float64 restatement rounded to the model output's dtype."""
         ns, c, h, w = shape
         assert c == 4 and self.seeds is not None and len(self.seeds) == ns, (shape, self.seeds)
-        z = philox_normal(self.seeds, i, 0, h * w).reshape(ns, 4, h, w)
-        return torch.from_numpy(z).to(torch.float16)
+        z = torch.from_numpy(philox_normal(self.seeds, i, 0, h * w).reshape(ns, 4, h, w))
+        return z if self.exact else z.to(torch.float16)
 
     def step(self, eps: torch.Tensor, i: int, x: torch.Tensor) -> torch.Tensor:
         s = torch.tensor(self.sigmas[i], dtype=torch.float32)
         up, down = self.up_down(i)
-        x32 = x.float()
-        pred_x0 = x32 - s * eps.float()
+        up64 = lambda t: t if t.dtype == torch.float64 else t.float()
+        x32 = up64(x)
+        pred_x0 = x32 - s * up64(eps)
         derivative = (x32 - pred_x0) / s
         out = x32 + derivative * (torch.tensor(down) - s)
-        return out + (self.noise(i, x.shape) * torch.tensor(up)).float()      # fp16 tensor * 0-dim fp32 -> fp16
+        return out + (self.noise(i, x.shape) * torch.tensor(up)).to(out.dtype)   # fp16 tensor * 0-dim fp32 -> fp16

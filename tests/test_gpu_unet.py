@@ -5,6 +5,7 @@ Tolerances: the HIP path stores activations in fp16 like the reference's fp16 in
 oracle run in fp16-storage emulation (`q = half-roundtrip`) at relative L2 error <= 5e-3 on a full UNet forward (measured
 1.3-1.6e-3 at every size from the tiny config to 2048 x 2048; the gate was 2e-2 until round 5) and with the pure-fp32
 oracle at <= 6e-3.  Every model-level gate goes through tests/_gates.gate, which logs the measured value beside its tolerance.
+The 50-step loops (all four samplers) are held to twice the distance between those two oracles' own loops, computed in the test.
 """
 import pytest
 import torch
@@ -132,6 +133,102 @@ def test_sampling_loop_vs_oracle(tiny, kind):
         results.append(eng.latents.clone())
     assert torch.equal(results[0], results[1]), "hipGraph replay differs from eager launches"
     gate(f"4 fused {kind} steps (CFG 7.5) vs oracle sample_loop", _rel(results[0], ref), 1.2e-2)
+
+
+# ---- the model in the loop for the benchmarked 50 steps, all four samplers
+LOOP_STEPS, LOOP_SNAPS, LOOP_SEEDS = 50, (5, 10, 25, 50), [20260101]
+_LOOP_KINDS = {"euler": 0, "ddim": 1, "dpm": 2, "euler_a": 3}
+_loop_oracles = {}          # kind -> (snapshots of the fp16-storage oracle loop, of the fp32 one): one CPU pass each per module
+
+
+def _loop_scheduler(kind):
+    from diffsensei_amd import schedulers as S
+    from tests._sampler_common import SDXL
+    cls = [S.EulerDiscreteScheduler, S.DDIMScheduler, S.DPMSolverMultistepScheduler, S.EulerAncestralDiscreteScheduler]
+    sch = cls[_LOOP_KINDS[kind]](**SDXL)
+    sch.set_timesteps(LOOP_STEPS)
+    return sch
+
+
+def _loop_oracle_scheduler(kind, exact):
+    """The scheduler restatement; exact: without fp16 points of its own (the fp32 loop)."""
+    from oracle.scheduler_ref import DDIMOracle, EulerDiscreteOracle
+    from tests._dpm_ref import DPMSolverOracle
+    from tests._euler_a_ref import EulerAncestralOracle
+    if kind == "euler":
+        return EulerDiscreteOracle()
+    if kind == "ddim":
+        return DDIMOracle()
+    if kind == "dpm":
+        return DPMSolverOracle(q=(lambda t: t)) if exact else DPMSolverOracle()
+    return EulerAncestralOracle(seeds=LOOP_SEEDS, exact=exact)
+
+
+def _loop_oracle_curves(tiny, kind, lat0, inputs):
+    from oracle.pipeline_ref import sample_loop
+    if kind not in _loop_oracles:
+        cfg, sd, model, o16, o32 = tiny
+        x, enc, te, tid, bbox, db = inputs
+        args = (enc.float(), te.float(), tid.float(), bbox, db, 7.5, LOOP_STEPS, 0.6)
+        with torch.no_grad():
+            r16 = sample_loop(o16, _loop_oracle_scheduler(kind, False), lat0.float(), *args, q=hq, record=LOOP_SNAPS)[1]
+            r32 = sample_loop(o32, _loop_oracle_scheduler(kind, True), lat0.float(), *args, record=LOOP_SNAPS)[1]
+        _loop_oracles[kind] = (r16, r32)
+    return _loop_oracles[kind]
+
+
+@pytest.mark.parametrize("kind", list(_LOOP_KINDS))
+def test_sampling_loop_50_steps_vs_oracle(tiny, kind):
+    """50 fused steps (UNet + CFG 7.5 + scheduler, ns 1, 16 x 16 latents) on the GPU, eager and 50 replays of the captured step
+    plan, against oracle/pipeline_ref.sample_loop with the fp16-storage UNet oracle and with the fp32 one.  The yardstick is
+    the references' own distance D16_32(k) = rel-L2(oracle16, oracle32) after k steps: the device differs from oracle16 by
+    summation order and fused rounding points only - a perturbation of the same kind and at most the same size - so at
+    k = 5, 10, 25, 50 it has to stay within 2 * D16_32(k) of both.  Condition on the references alone: D16_32(50) <= 1e-2
+    (the loop through this random-weight UNet is not chaotic)."""
+    from diffsensei_amd.unet import dialog_pixel_boxes
+    cfg, sd, model, o16, o32 = tiny
+    ns, H, W = 1, 16, 16
+    inputs = _inputs(cfg, 2 * ns, H, W, seed=3)
+    x, enc, te, tid, bbox, db = inputs
+    sch = _loop_scheduler(kind)
+    lat0 = (x[:ns].float() * sch.init_noise_sigma).half()
+    eng = model.engine(2 * ns, H, W, H / W)
+    eng.build_sampler(ns, sch.kind, True)
+    table = torch.from_numpy(sch.coef_table(7.5))
+    assert table.shape == (LOOP_STEPS, 8)
+    results = []
+    for mode in ("eager", "graph"):
+        eng.set_request(enc, te, tid, bbox, dialog_pixel_boxes(db, H, W), 0.6)
+        eng.load_schedule(table, solver_rows=torch.from_numpy(sch.solver_table()) if kind == "dpm" else None,
+                          noise_seeds=LOOP_SEEDS if kind == "euler_a" else None)
+        eng.latents.copy_(lat0)
+        snaps = {}
+        st = torch.cuda.Stream()
+        st.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(st):
+            eng.prep_plan.run(st.cuda_stream)
+            if mode == "graph" and not eng.step_plan.captured:
+                eng.step_plan.capture(st.cuda_stream)
+            for k in range(1, LOOP_STEPS + 1):
+                (eng.step_plan.replay if mode == "graph" else eng.step_plan.run)(st.cuda_stream)
+                if k in LOOP_SNAPS:
+                    snaps[k] = eng.latents.clone()
+        st.synchronize()
+        assert int(eng.ctr.item()) == LOOP_STEPS
+        results.append(snaps)
+    for k in LOOP_SNAPS:
+        assert torch.equal(results[0][k], results[1][k]), f"hipGraph replay differs from eager launches after {k} steps"
+    r16, r32 = _loop_oracle_curves(tiny, kind, lat0, inputs)
+    d16_32 = {k: _rel(r16[k], r32[k]) for k in LOOP_SNAPS}
+    d32 = {k: _rel(results[0][k], r32[k]) for k in LOOP_SNAPS}
+    d16 = {k: _rel(results[0][k], r16[k]) for k in LOOP_SNAPS}
+    for k in LOOP_SNAPS:                            # every figure first, then the assertions
+        assert torch.isfinite(results[0][k]).all()
+        print(f"{kind} after {k} steps: D16_32 {d16_32[k]:.3e}, device vs fp32 loop {d32[k]:.3e}, vs fp16-storage loop {d16[k]:.3e}")
+    gate(f"50-step {kind} loop: D16_32(50), the references alone", d16_32[LOOP_STEPS], 1e-2)
+    for k in LOOP_SNAPS:
+        gate(f"{k} of 50 fused {kind} steps (CFG 7.5) vs the fp32 oracle loop (2 x D16_32)", d32[k], 2 * d16_32[k])
+        gate(f"{k} of 50 fused {kind} steps (CFG 7.5) vs the fp16-storage oracle loop (2 x D16_32)", d16[k], 2 * d16_32[k])
 
 
 def test_unet_model_api_surface(hip_lib):
