@@ -26,6 +26,17 @@
 //
 // K order: channel slices outer, taps inner (k = tap*Cin + ci in the weight rows) - the sum is the same set of
 // products as the tap-major kernel's, in a different order, so results agree to fp32-accumulation rounding.
+//
+// Three kernels, three pipeline schedules (conv_halo_kernel: single W buffer, three blocks per CU; conv_halo_deep_kernel: W
+// ring + double-buffered patch for one block per CU; conv_halo256_kernel: 16 x 16 pixels, two W buffers), promised bit-equal
+// (tests/test_gpu_ops.py, tests/test_gpu_conv_halo_bits.py).  What that promise rests on stands in "Shared pieces" below, and
+// a kernel uses every piece that measured no slower in it than its own text (DESIGN 9.18 has the measurements):
+//   halo_tile (tile decode), halo_w_desc (weight descriptors): all three kernels;
+//   halo_swz (THE patch swizzle), halo_patch_desc, halo_frag_init, halo_epilogue_park / halo_epilogue_store: conv_halo_kernel
+//     and conv_halo_deep_kernel; conv_halo256_kernel keeps its own patch descriptors, swizzle spelling and epilogue;
+//   halo_a_base, halo_load, halo_mfmas, halo_w_k0, halo_next (the fragment walk of a k-tile): conv_halo_kernel; the two
+//     read-ahead kernels keep theirs as lambdas in their k-loops.
+// Every kernel keeps its LDS map, the issue of its DMA and its k-loop with every wait and barrier.
 #include "ds_epilogue.h"
 
 namespace {
@@ -36,6 +47,7 @@ constexpr int HROWS = (PH + 2) * HWD;     // 180 patch pixels
 constexpr int PROWS = 192;                // staged rows (24 LDS-DMA pieces of 8 rows)
 constexpr int BN = 128;
 constexpr int CS_STRIDE = 272;            // bytes per row of the epilogue staging tile (128 f16 + 8 pad)
+static_assert(128 * CS_STRIDE + 4096 <= PROWS * 128 + BN * 128, "conv_halo_kernel: staging tile + GroupNorm partials exceed its LDS");
 typedef __attribute__((address_space(3))) void lds_void;
 typedef const __attribute__((address_space(1))) void glb_void;
 
@@ -83,95 +95,6 @@ __device__ __forceinline__ void gn_emit(const GemmParams& p, float (&gs)[8], flo
     }
 }
 
-// Epilogue of the two 8 x 16-pixel kernels (conv_halo_kernel, conv_halo_deep_kernel): the caller has passed its last barrier.
-template <typename T, bool FOLD = false>
-__device__ __forceinline__ void conv_halo_epilogue8(const GemmParams& p, f32x16 (&acc)[2][2], char* smem, int tid, int wm, int wn,
-                                                    int l31, int lhi, int b, int oy0, int ox0, int n0, int tile_in_image, int phase = 0) {
-    const int TH = FOLD ? p.Hin : p.Hout, TW = FOLD ? p.Win : p.Wout;   // extent of the tile grid (phase mode: input resolution)
-    typedef typename Elt<T>::v8 V8;
-    typedef typename Elt<T>::v4 V4;
-    // ---- epilogue: bias (+ per-image bias), round to f16, park the 128 x 128 tile in LDS, then whole 16-byte pieces
-    // of output rows (+ residual).  D layout (operands swapped): lane holds row ..+(lane&31); register r is column
-    // (r&3) + 8*(r>>2) + 4*(lane>>5) of its 32-column fragment.
-    // (no branch / s_waitcnt per 4 values: biases fetched once with clamped addresses, residual pieces requested in
-    // batches of four before they are needed - see conv_halo256_kernel)
-    char* const sC = smem;
-    V4 b0[2][4], b1[2][4];
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) b0[ni][g] = b1[ni][g] = V4{0, 0, 0, 0};
-    if (p.bias) {
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-                b0[ni][g] = *reinterpret_cast<const V4*>(p.bias + min(n0 + wn * 64 + ni * 32 + 8 * g + 4 * lhi, p.N - 4));
-    }
-    if (p.rowbias) {
-        const half_t* rb = p.rowbias + (long)b * p.rowbias_ld;
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-                b1[ni][g] = *reinterpret_cast<const V4*>(rb + min(n0 + wn * 64 + ni * 32 + 8 * g + 4 * lhi, p.N - 4));
-    }
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi) {
-        const int ms = wm * 64 + mi * 32 + l31;
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int nl = wn * 64 + ni * 32 + 8 * g + 4 * lhi;
-                V4 o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float v = acc[mi][ni][4 * g + e];
-                    v += (float)b0[ni][g][e];
-                    v += (float)b1[ni][g][e];
-                    o[e] = (T)v;
-                }
-                *reinterpret_cast<V4*>(sC + ms * CS_STRIDE + nl * 2) = o;
-            }
-    }
-    __syncthreads();
-    const T* const Rp = reinterpret_cast<const T*>(p.residual);
-    float gs[8], gq[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) gs[e] = gq[e] = 0.f;
-#pragma unroll 1
-    for (int j0 = 0; j0 < 8; j0 += 4) {
-        long mrow[4];
-        int ncol[4];
-        bool ok[4];
-        V8 rv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int id = tid + 256 * (j0 + u);
-            const int row = id >> 4, c = id & 15;
-            const int ty_ = oy0 + (row >> 4), tx_ = ox0 + (row & 15);
-            ok[u] = (n0 + c * 8 < p.N) & (ty_ < TH) & (tx_ < TW);
-            // phase mode: tile pixel (Y, X) of phase (py, px) is output pixel (2Y + py, 2X + px)
-            const int oy = FOLD ? 2 * min(ty_, TH - 1) + (phase >> 1) : min(ty_, TH - 1);
-            const int ox = FOLD ? 2 * min(tx_, TW - 1) + (phase & 1) : min(tx_, TW - 1);
-            mrow[u] = ((long)b * p.Hout + oy) * p.Wout + ox;
-            ncol[u] = min(n0 + c * 8, p.N - 8);
-            if (Rp) rv[u] = *reinterpret_cast<const V8*>(Rp + mrow[u] * p.ldr + ncol[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int id = tid + 256 * (j0 + u);
-            const int row = id >> 4, c = id & 15;
-            V8 v = *reinterpret_cast<const V8*>(sC + row * CS_STRIDE + c * 16);
-            if (Rp) v = add_residual8<T>(v, rv[u]);
-            if (ok[u]) *reinterpret_cast<V8*>(reinterpret_cast<T*>(p.C) + mrow[u] * p.ldc + ncol[u]) = v;
-            if (p.gn_partial && ok[u]) gn_accumulate(v, gs, gq);
-        }
-    }
-    if (p.gn_partial) gn_emit(p, gs, gq, smem + 128 * CS_STRIDE, tid, b, tile_in_image, n0);
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // Phase mode (TPS = 4, GemmParams::up_fold): nearest x2 + 3 x 3 as four 2 x 2 convolutions of the INPUT-resolution image.
 // In the upsampled image every 2 x 2 block is one input pixel, so of the three rows a tap window covers two are the same
@@ -195,11 +118,218 @@ __device__ __forceinline__ void halo_tap(int tap, int phase, int& ky, int& kx) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Shared pieces.  A block = 4 waves (wm = wave >> 1, wn = wave & 1), lane = 32 lhi + l31.  ROWS: GEMM rows of the block's tile
+// (128: 8 x 16 pixels, 256: 16 x 16); MI: 32-row fragments per wave; rbase / cbase: first tile row / column of the wave.
+// A next kernel variant brings its LDS map, DMA issue and k-loop, calls these in this order, and is timed against its own text.
+// ---------------------------------------------------------------------------------------------------------------
+// The block's tile, decoded once from (p, blockIdx); PHT: pixel rows of a tile (PH / PH2).
+struct HaloTile {
+    int phase;              // phase mode: py * 2 + px, the low two bits of the pixel-tile index (else 0)
+    int TH, TW;             // extent of the tile grid (phase mode: input resolution)
+    int tiles_x;            // pixel tiles per image row; ragged edges: masked stores
+    int b, oy0, ox0, n0;    // image, first pixel and first output channel of the tile
+    int in_image;           // index of the pixel tile in its image (GroupNorm partials)
+};
+template <int PHT, bool FOLD>
+__device__ __forceinline__ HaloTile halo_tile(const GemmParams& p) {
+    const int tile = xcd_remap(blockIdx.x, gridDim.x);
+    int tm, tn;
+    tile_coords(tile, p.tiles_m, p.tiles_n, tm, tn);
+    HaloTile t;
+    t.phase = FOLD ? (tm & 3) : 0;
+    if (FOLD) tm >>= 2;
+    t.TH = FOLD ? p.Hin : p.Hout, t.TW = FOLD ? p.Win : p.Wout;
+    t.tiles_x = (t.TW + PW - 1) / PW;
+    const int tiles_y = (t.TH + PHT - 1) / PHT;
+    const int tx = tm % t.tiles_x, ty = (tm / t.tiles_x) % tiles_y;
+    t.b = tm / (t.tiles_x * tiles_y);
+    t.oy0 = ty * PHT, t.ox0 = tx * PW, t.n0 = tn * BN;
+    t.in_image = ty * t.tiles_x + tx;
+    return t;
+}
+
+// THE patch swizzle of the file header, writer and reader: the chunk XOR of patch pixel q in patch column qx.
+// rowswz (gemm_debug bit 10, A/B only): the row-index swizzle (2-way bank conflicts on every A read).
+__device__ __forceinline__ int halo_swz(int q, int qx, bool rowswz) { return ((rowswz ? q : qx) >> 1) & 7; }
+
+// Patch descriptors: this wave stages patch rows (PIECES wave + j) * 8 + (lane >> 3), j < PIECES, of a patch of HR pixels.
+// poff[j]: element offset of the lane's 16-byte chunk at channel 0, or -1: zero page (halo / pad rows).
+template <int PIECES, int HR, bool FOLD>
+__device__ __forceinline__ void halo_patch_desc(int (&poff)[PIECES], const GemmParams& p, const HaloTile& t, int wave, int lane, bool rowswz) {
+    const int lrow = lane >> 3, slot = lane & 7;
+#pragma unroll
+    for (int j = 0; j < PIECES; ++j) {
+        const int q = (wave * PIECES + j) * 8 + lrow;
+        const int qy = q / HWD, qx = q - qy * HWD;
+        const int uy = t.oy0 - 1 + qy, ux = t.ox0 - 1 + qx;  // output-resolution pixel
+        const bool ok = (q < HR) & (uy >= 0) & (uy < t.TH) & (ux >= 0) & (ux < t.TW);
+        const int iy = !FOLD && p.upsample ? nearest_src(uy, p.up_sy, p.Hin) : uy, ix = !FOLD && p.upsample ? nearest_src(ux, p.up_sx, p.Win) : ux;
+        const int chunk = slot ^ halo_swz(q, qx, rowswz);
+        poff[j] = ok ? ((t.b * p.Hin + iy) * p.Win + ix) * p.Cin + chunk * 8 : -1;
+    }
+}
+// Weight descriptors: woff[j], element offset of the lane's chunk in the weight matrix at k = 0 (Cout * 9 * Cin < 2^31); rows past
+// N re-read row N - 1 (never stored).
+template <bool FOLD>
+__device__ __forceinline__ void halo_w_desc(int (&woff)[4], const GemmParams& p, const HaloTile& t, int wave, int lane) {
+    const int lrow = lane >> 3, slot = lane & 7;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int row = (wave * 4 + j) * 8 + lrow;
+        const int chunk = slot ^ ((row >> 1) & 7);
+        const int n = min(t.n0 + row, p.N - 1);
+        woff[j] = (FOLD ? t.phase * p.N + n : n) * (int)p.ldw + chunk * 8;   // phase mode: weight slab `phase` of [4][N][4 Cin]
+    }
+}
+
+// A fragment rows: GEMM row r = rbase + 32 mi + l31  <->  patch pixel (r >> 4, r & 15), tap (0, 0) at q0; accumulators to zero
+template <int MI>
+__device__ __forceinline__ void halo_frag_init(int (&q0)[MI], f32x16 (&acc)[MI][2], int rbase, int l31) {
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) {
+        q0[mi] = ((rbase >> 4) + mi * 2 + (l31 >> 4)) * HWD + (l31 & 15);
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+    }
+}
+// byte offset of the lane's A fragments of k-tile `tap` in the patch (k-step kk at ab ^ (kk << 5))
+template <int TPS, int MI>
+__device__ __forceinline__ void halo_a_base(int (&ab)[MI], const int (&q0)[MI], int tap, int phase, int l31, int lhi, bool rowswz) {
+    int ky, kx;
+    halo_tap<TPS>(tap, phase, ky, kx);
+    const int shift = ky * HWD + kx;
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) {
+        const int q = q0[mi] + shift;
+        ab[mi] = q * 128 + ((lhi ^ halo_swz(q, (l31 & 15) + kx, rowswz)) << 4);
+    }
+}
+// the fragments of k-step kk: A from patch `cp`, B = rows cbase + 32 ni + l31 of W tile `cw`
+template <int MI, typename V8>
+__device__ __forceinline__ void halo_load(V8 (&af)[MI], V8 (&bf)[2], const int (&ab)[MI], const char* cp, const char* cw, int cbase, int l31,
+                                          int lhi, int kk) {
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) af[mi] = *reinterpret_cast<const V8*>(cp + (ab[mi] ^ (kk << 5)));
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) {
+        const int r = cbase + ni * 32 + l31;
+        bf[ni] = *reinterpret_cast<const V8*>(cw + r * 128 + swz(r, kk * 2 + lhi));
+    }
+}
+template <typename T, int MI, typename V8>
+__device__ __forceinline__ void halo_mfmas(f32x16 (&acc)[MI][2], const V8 (&af)[MI], const V8 (&bf)[2]) {
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = Elt<T>::mfma(bf[ni], af[mi], acc[mi][ni]);
+}
+// k-tile (slice, tap): column offset of its W tile (k = tap * Cin + ci), and the k-tile behind it (taps inner)
+__device__ __forceinline__ int halo_w_k0(const GemmParams& p, int tap, int slice) { return tap * p.Cin + slice * 64; }
+template <int TPS>
+__device__ __forceinline__ void halo_next(int tap, int s, int& ntap, int& ns) {
+    ntap = tap == TPS - 1 ? 0 : tap + 1;
+    ns = tap == TPS - 1 ? s + 1 : s;
+}
+
+// ---- epilogue; the caller has passed its last barrier.  Stage 1 (per wave, from MI / rbase / cbase): bias (+ per-image bias), round
+// to f16, park the tile in LDS at CS_STRIDE.  D layout (operands swapped): lane holds row ..+(lane&31); register r is column
+// (r&3) + 8*(r>>2) + 4*(lane>>5) of its 32-column fragment.  No branch (and no s_waitcnt vmcnt(0), which the compiler puts behind
+// each conditional load) per 4 values: the bias + per-image bias of the lane's 8 column groups are fetched once (clamped addresses:
+// masked columns are never stored).  fp32 add order as the generic kernels: acc, bias, per-image bias, round.
+template <typename T, int MI>
+__device__ __forceinline__ void halo_epilogue_park(const GemmParams& p, const f32x16 (&acc)[MI][2], char* sC, const HaloTile& t, int rbase,
+                                                   int cbase, int l31, int lhi) {
+    typedef typename Elt<T>::v4 V4;
+    V4 b0[2][4], b1[2][4];
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) b0[ni][g] = b1[ni][g] = V4{0, 0, 0, 0};
+    if (p.bias) {
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                b0[ni][g] = *reinterpret_cast<const V4*>(p.bias + min(t.n0 + cbase + ni * 32 + 8 * g + 4 * lhi, p.N - 4));
+    }
+    if (p.rowbias) {
+        const half_t* rb = p.rowbias + (long)t.b * p.rowbias_ld;
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                b1[ni][g] = *reinterpret_cast<const V4*>(rb + min(t.n0 + cbase + ni * 32 + 8 * g + 4 * lhi, p.N - 4));
+    }
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) {
+        const int ms = rbase + mi * 32 + l31;
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int nl = cbase + ni * 32 + 8 * g + 4 * lhi;
+                V4 o;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float v = acc[mi][ni][4 * g + e];
+                    v += (float)b0[ni][g][e];
+                    v += (float)b1[ni][g][e];
+                    o[e] = (T)v;
+                }
+                *reinterpret_cast<V4*>(sC + ms * CS_STRIDE + nl * 2) = o;
+            }
+    }
+}
+// Stage 2 (the block, ROWS x 128 tile at smem): whole 16-byte pieces of output rows, + residual in the element type, masked stores;
+// the residual pieces are requested in batches of four before they are needed.  GroupNorm partials go behind the staging tile.
+template <typename T, bool FOLD, int ROWS>
+__device__ __forceinline__ void halo_epilogue_store(const GemmParams& p, char* smem, const HaloTile& t, int tid) {
+    typedef typename Elt<T>::v8 V8;
+    typedef __attribute__((address_space(1))) V8 GV8;   // the residual: a global load in every kernel, never a flat one
+    __syncthreads();
+    const T* const Rp = reinterpret_cast<const T*>(p.residual);
+    float gs[8], gq[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) gs[e] = gq[e] = 0.f;
+#pragma unroll 1
+    for (int j0 = 0; j0 < ROWS / 16; j0 += 4) {
+        long mrow[4];
+        int ncol[4];
+        bool ok[4];
+        V8 rv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int id = tid + 256 * (j0 + u);
+            const int row = id >> 4, c = id & 15;
+            const int ty_ = t.oy0 + (row >> 4), tx_ = t.ox0 + (row & 15);
+            ok[u] = (t.n0 + c * 8 < p.N) & (ty_ < t.TH) & (tx_ < t.TW);
+            // phase mode: tile pixel (Y, X) of phase (py, px) is output pixel (2Y + py, 2X + px)
+            const int oy = FOLD ? 2 * min(ty_, t.TH - 1) + (t.phase >> 1) : min(ty_, t.TH - 1);
+            const int ox = FOLD ? 2 * min(tx_, t.TW - 1) + (t.phase & 1) : min(tx_, t.TW - 1);
+            mrow[u] = ((long)t.b * p.Hout + oy) * p.Wout + ox;
+            ncol[u] = min(t.n0 + c * 8, p.N - 8);
+            if (Rp) rv[u] = *(const GV8*)(Rp + mrow[u] * p.ldr + ncol[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int id = tid + 256 * (j0 + u);
+            const int row = id >> 4, c = id & 15;
+            V8 v = *reinterpret_cast<const V8*>(smem + row * CS_STRIDE + c * 16);
+            if (Rp) v = add_residual8<T>(v, rv[u]);
+            if (ok[u]) *reinterpret_cast<V8*>(reinterpret_cast<T*>(p.C) + mrow[u] * p.ldc + ncol[u]) = v;
+            if (p.gn_partial && ok[u]) gn_accumulate(v, gs, gq);
+        }
+    }
+    if (p.gn_partial) gn_emit(p, gs, gq, smem + ROWS * CS_STRIDE, tid, t.b, t.in_image, t.n0);
+}
+
 template <typename T, int TPS = 9>  // half_t (UNet) or bf16_t (VAE decoder); TPS: k-tiles (taps) per channel slice, 4 = phase mode
 __global__ __launch_bounds__(256, 3) void conv_halo_kernel(const GemmParams p) {
     constexpr bool FOLD = TPS == 4;
     typedef typename Elt<T>::v8 V8;
-    typedef typename Elt<T>::v4 V4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const sP = smem;
     char* const sW = smem + PROWS * 128;
@@ -207,39 +337,12 @@ __global__ __launch_bounds__(256, 3) void conv_halo_kernel(const GemmParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
     const int l31 = lane & 31, lhi = lane >> 5;
-    const int lrow = lane >> 3, slot = lane & 7;
-    const bool rowswz = (p.debug & 1024) != 0;  // A/B only: the row-index patch swizzle (2-way bank conflicts on every A read)
+    const bool rowswz = (p.debug & 1024) != 0;
 
-    const int tile = xcd_remap(blockIdx.x, gridDim.x);
-    int tm, tn;
-    tile_coords(tile, p.tiles_m, p.tiles_n, tm, tn);
-    const int phase = FOLD ? (tm & 3) : 0;
-    if (FOLD) tm >>= 2;
-    const int TH = FOLD ? p.Hin : p.Hout, TW = FOLD ? p.Win : p.Wout;
-    const int tiles_x = (TW + PW - 1) / PW, tiles_y = (TH + PH - 1) / PH;  // ragged edges: masked stores
-    const int tx = tm % tiles_x, ty = (tm / tiles_x) % tiles_y, b = tm / (tiles_x * tiles_y);
-    const int oy0 = ty * PH, ox0 = tx * PW, n0 = tn * BN;
-
-    // ---- patch descriptors: this wave stages patch rows (6w + j) * 8 + lrow, j < 6
-    int poff[6];  // element offset of the lane's 16-byte chunk at channel 0, or -1: zero page (halo / pad rows)
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        const int q = (wave * 6 + j) * 8 + lrow;
-        const int qy = q / HWD, qx = q - qy * HWD;
-        const int uy = oy0 - 1 + qy, ux = ox0 - 1 + qx;  // output-resolution pixel
-        const bool ok = (q < HROWS) & (uy >= 0) & (uy < TH) & (ux >= 0) & (ux < TW);
-        const int iy = !FOLD && p.upsample ? nearest_src(uy, p.up_sy, p.Hin) : uy, ix = !FOLD && p.upsample ? nearest_src(ux, p.up_sx, p.Win) : ux;
-        const int chunk = slot ^ (((rowswz ? q : qx) >> 1) & 7);  // swizzle by patch COLUMN (see the header)
-        poff[j] = ok ? ((b * p.Hin + iy) * p.Win + ix) * p.Cin + chunk * 8 : -1;
-    }
-    int woff[4];  // element offset of the lane's chunk in the weight matrix at k = 0 (Cout * 9 * Cin < 2^31)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int row = (wave * 4 + j) * 8 + lrow;
-        const int chunk = slot ^ ((row >> 1) & 7);
-        const int n = min(n0 + row, p.N - 1);
-        woff[j] = (FOLD ? phase * p.N + n : n) * (int)p.ldw + chunk * 8;   // phase mode: weight slab `phase` of [4][N][4 Cin]
-    }
+    const HaloTile t = halo_tile<PH, FOLD>(p);
+    int poff[6], woff[4];
+    halo_patch_desc<6, HROWS, FOLD>(poff, p, t, wave, lane, rowswz);
+    halo_w_desc<FOLD>(woff, p, t, wave, lane);
     auto issue_patch = [&](int ci0) {
         char* d = sP + wave * 6 * 1024;
 #pragma unroll
@@ -255,18 +358,9 @@ __global__ __launch_bounds__(256, 3) void conv_halo_kernel(const GemmParams p) {
             __builtin_amdgcn_global_load_lds((glb_void*)(p.W + k0 + woff[j]), (lds_void*)(d + j * 1024), 16, 0, 0);
     };
 
-    // ---- A fragment rows: GEMM row r = 64 wm + 32 mi + l31  <->  patch pixel (r >> 4, r & 15), tap (0,0) at q0
     int q0[2];
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi) q0[mi] = (wm * 4 + mi * 2 + (l31 >> 4)) * HWD + (l31 & 15);
-
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    halo_frag_init(q0, acc, wm * 64, l31);
 
     const int slices = p.Cin / 64;
     issue_patch(0);
@@ -277,60 +371,29 @@ __global__ __launch_bounds__(256, 3) void conv_halo_kernel(const GemmParams p) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
-            int ky, kx;
-            halo_tap<TPS>(tap, phase, ky, kx);
-            const int shift = ky * HWD + kx;
+            int abase[2];
+            halo_a_base<TPS>(abase, q0, tap, t.phase, l31, lhi, rowswz);
             V8 af[4][2], bf[4][2];
 #pragma unroll
-            for (int mi = 0; mi < 2; ++mi) {
-                const int q = q0[mi] + shift;
-                const int base = q * 128 + ((lhi ^ (((rowswz ? q : (l31 & 15) + kx) >> 1) & 7)) << 4);
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) af[kk][mi] = *reinterpret_cast<const V8*>(sP + (base ^ (kk << 5)));
-            }
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni) {
-                    const int r = wn * 64 + ni * 32 + l31;
-                    bf[kk][ni] = *reinterpret_cast<const V8*>(sW + r * 128 + swz(r, kk * 2 + lhi));
-                }
+            for (int kk = 0; kk < 4; ++kk) halo_load(af[kk], bf[kk], abase, sP, sW, wn * 64, l31, lhi, kk);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             const bool last = (s + 1 == slices) & (tap == TPS - 1);
             if (!last) {  // the W buffer (and after the last tap the patch) is drained once everyone holds its fragments
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
-                if (tap == TPS - 1) {
-                    issue_patch((s + 1) * 64);
-                    issue_w((s + 1) * 64);
-                } else {
-                    issue_w((tap + 1) * p.Cin + s * 64);
-                }
+                int ntap, ns;
+                halo_next<TPS>(tap, s, ntap, ns);
+                if (ntap == 0) issue_patch(ns * 64);
+                issue_w(halo_w_k0(p, ntap, ns));
             }
 #pragma unroll
-            for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-                for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                    for (int ni = 0; ni < 2; ++ni)
-                        acc[mi][ni] = Elt<T>::mfma(bf[kk][ni], af[kk][mi], acc[mi][ni]);
+            for (int kk = 0; kk < 4; ++kk) halo_mfmas<T>(acc, af[kk], bf[kk]);
         }
     }
     __syncthreads();
-
-    conv_halo_epilogue8<T, FOLD>(p, acc, smem, tid, wm, wn, l31, lhi, b, oy0, ox0, n0, ty * tiles_x + tx, phase);
+    halo_epilogue_park<T>(p, acc, smem, t, wm * 64, wn * 64, l31, lhi);
+    halo_epilogue_store<T, FOLD, 128>(p, smem, t, tid);
 }
-
-// ---------------------------------------------------------------------------------------------------------------
-// Large-batch variant: 16 x 16 output pixels (M tile = 256) x 128 channels per block.  The 8 x 16 kernel above still
-// moves 36 B/clk/CU through L2 -> LDS (its W tile serves only 128 pixels), i.e. it sits on the same fill limit as the
-// 128 x 128 GEMMs; doubling the pixels per W tile takes that to 20 B/clk/CU (204 flop/B).  Waves 2 x 2, each
-// 128 pixels x 64 channels (acc 128 VGPRs, 0.75 KiB of fragment reads per MFMA instead of 1).  LDS: 18 x 18 halo patch
-// 44 KiB + TWO W buffers (the next k-tile's W is in flight under the current tile's MFMAs, one barrier per k-tile) =
-// 76 KiB -> two blocks per CU.  The patch is single-buffered: at a slice boundary the block waits for the new patch
-// while the co-resident block computes.
-// ---------------------------------------------------------------------------------------------------------------
-static_assert(128 * CS_STRIDE + 4096 <= PROWS * 128 + BN * 128, "conv_halo_kernel: staging tile + GroupNorm partials exceed its LDS");
 
 // ---------------------------------------------------------------------------------------------------------------
 // Small-grid variant of the 8 x 16 kernel (round 6): the same tile (8 x 16 output pixels x 128 channels, 4 waves), but the W
@@ -375,43 +438,18 @@ __global__ __launch_bounds__(256, 1) void conv_halo_deep_kernel(const GemmParams
     constexpr bool FOLD = TPS == 4;
     static_assert(TPS >= DEEP_NW, "the next slice's patch must be older than the W tile its first k-tile waits for");
     typedef typename Elt<T>::v8 V8;
-    typedef typename Elt<T>::v4 V4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
     const int l31 = lane & 31, lhi = lane >> 5;
-    const int lrow = lane >> 3, slot = lane & 7;
+    // this kernel has never read gemm_debug bit 10 (the row-index patch swizzle of the other two): always the column swizzle
+    constexpr bool rowswz = false;
 
-    const int tile = xcd_remap(blockIdx.x, gridDim.x);
-    int tm, tn;
-    tile_coords(tile, p.tiles_m, p.tiles_n, tm, tn);
-    const int phase = FOLD ? (tm & 3) : 0;
-    if (FOLD) tm >>= 2;
-    const int TH = FOLD ? p.Hin : p.Hout, TW = FOLD ? p.Win : p.Wout;
-    const int tiles_x = (TW + PW - 1) / PW, tiles_y = (TH + PH - 1) / PH;
-    const int tx = tm % tiles_x, ty = (tm / tiles_x) % tiles_y, b = tm / (tiles_x * tiles_y);
-    const int oy0 = ty * PH, ox0 = tx * PW, n0 = tn * BN;
-
-    int poff[6];  // element offset of the lane's 16-byte chunk at channel 0, or -1: zero page (halo / pad rows)
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        const int q = (wave * 6 + j) * 8 + lrow;
-        const int qy = q / HWD, qx = q - qy * HWD;
-        const int uy = oy0 - 1 + qy, ux = ox0 - 1 + qx;
-        const bool ok = (q < HROWS) & (uy >= 0) & (uy < TH) & (ux >= 0) & (ux < TW);
-        const int iy = !FOLD && p.upsample ? nearest_src(uy, p.up_sy, p.Hin) : uy, ix = !FOLD && p.upsample ? nearest_src(ux, p.up_sx, p.Win) : ux;
-        const int chunk = slot ^ ((qx >> 1) & 7);  // swizzle by patch COLUMN (see the file header)
-        poff[j] = ok ? ((b * p.Hin + iy) * p.Win + ix) * p.Cin + chunk * 8 : -1;
-    }
-    int woff[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int row = (wave * 4 + j) * 8 + lrow;
-        const int chunk = slot ^ ((row >> 1) & 7);
-        const int n = min(n0 + row, p.N - 1);
-        woff[j] = (FOLD ? phase * p.N + n : n) * (int)p.ldw + chunk * 8;   // phase mode: weight slab `phase` of [4][N][4 Cin]
-    }
+    const HaloTile t = halo_tile<PH, FOLD>(p);
+    int poff[6], woff[4];
+    halo_patch_desc<6, HROWS, FOLD>(poff, p, t, wave, lane, rowswz);
+    halo_w_desc<FOLD>(woff, p, t, wave, lane);
     const unsigned lds0 = (unsigned)(size_t)(lds_void*)smem;
     auto issue_patch = [&](int ci0, int pbuf) {
         const unsigned d = lds0 + pbuf * (PROWS * 128) + wave * 6 * 1024;
@@ -428,31 +466,25 @@ __global__ __launch_bounds__(256, 1) void conv_halo_deep_kernel(const GemmParams
     };
 
     int q0[2];
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi) q0[mi] = (wm * 4 + mi * 2 + (l31 >> 4)) * HWD + (l31 & 15);
-
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    halo_frag_init(q0, acc, wm * 64, l31);
 
     const int slices = p.Cin / 64;
     const int nkt = slices * TPS;
+    // The fragment walk as this kernel's own lambdas: on halo_a_base / halo_load / halo_mfmas / halo_w_k0 / halo_next its k-tile
+    // measured 2.2 % longer
     auto w_k0 = [&](int kt) {   // k-tile kt = (slice, tap): column offset of its W tile (k = tap * Cin + ci)
         const int sl = kt / TPS, tp = kt - sl * TPS;
         return tp * p.Cin + sl * 64;
     };
     auto set_abase = [&](int (&ab)[2], int tp) {
         int ky, kx;
-        halo_tap<TPS>(tp, phase, ky, kx);
+        halo_tap<TPS>(tp, t.phase, ky, kx);
         const int shift = ky * HWD + kx;
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi) {
             const int q = q0[mi] + shift;
-            ab[mi] = q * 128 + ((lhi ^ ((((l31 & 15) + kx) >> 1) & 7)) << 4);
+            ab[mi] = q * 128 + ((lhi ^ halo_swz(q, (l31 & 15) + kx, rowswz)) << 4);
         }
     };
     auto load = [&](V8 (&af)[2], V8 (&bf)[2], const int (&ab)[2], const char* cp, const char* cw, int kk) {
@@ -539,16 +571,27 @@ __global__ __launch_bounds__(256, 1) void conv_halo_deep_kernel(const GemmParams
         }
     }
     __syncthreads();
-    conv_halo_epilogue8<T, FOLD>(p, acc, smem, tid, wm, wn, l31, lhi, b, oy0, ox0, n0, ty * tiles_x + tx, phase);
+    halo_epilogue_park<T>(p, acc, smem, t, wm * 64, wn * 64, l31, lhi);
+    halo_epilogue_store<T, FOLD, 128>(p, smem, t, tid);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Large-batch variant: 16 x 16 output pixels (M tile = 256) x 128 channels per block.  The 8 x 16 kernel above still
+// moves 36 B/clk/CU through L2 -> LDS (its W tile serves only 128 pixels), i.e. it sits on the same fill limit as the
+// 128 x 128 GEMMs; doubling the pixels per W tile takes that to 20 B/clk/CU (204 flop/B).  Waves 2 x 2, each
+// 128 pixels x 64 channels (acc 128 VGPRs, 0.75 KiB of fragment reads per MFMA instead of 1).  LDS: 18 x 18 halo patch
+// 44 KiB + TWO W buffers (the next k-tile's W is in flight under the current tile's MFMAs, one barrier per k-tile) =
+// 76 KiB -> two blocks per CU.  The patch is single-buffered: at a slice boundary the block waits for the new patch
+// while the co-resident block computes.
+// ---------------------------------------------------------------------------------------------------------------
 constexpr int PH2 = 16;
 constexpr int HROWS2 = (PH2 + 2) * HWD;   // 324 patch pixels
 constexpr int NPIECE2 = (HROWS2 + 7) / 8;  // 41 LDS-DMA pieces of 8 rows
 constexpr int PPW2 = (NPIECE2 + 3) / 4;    // 11 per wave
 constexpr int PBYTES2 = PPW2 * 4 * 1024;   // 44 KiB
+constexpr int LDS2 = PBYTES2 + 2 * BN * 128;   // 76 KiB
 
-static_assert(256 * CS_STRIDE + 4096 <= PBYTES2 + 2 * BN * 128, "conv_halo256_kernel: staging tile + GroupNorm partials exceed its LDS");
+static_assert(256 * CS_STRIDE + 4096 <= LDS2, "conv_halo256_kernel: staging tile + GroupNorm partials exceed its LDS");
 
 template <typename T, int TPS = 9>
 __global__ __launch_bounds__(256, 2) void conv_halo256_kernel(const GemmParams p) {
@@ -563,18 +606,13 @@ __global__ __launch_bounds__(256, 2) void conv_halo256_kernel(const GemmParams p
     const int wm = wave >> 1, wn = wave & 1;
     const int l31 = lane & 31, lhi = lane >> 5;
     const int lrow = lane >> 3, slot = lane & 7;
-    const bool rowswz = (p.debug & 1024) != 0;  // A/B only: the row-index patch swizzle (2-way bank conflicts on every A read)
+    const bool rowswz = (p.debug & 1024) != 0;
 
-    const int tile = xcd_remap(blockIdx.x, gridDim.x);
-    int tm, tn;
-    tile_coords(tile, p.tiles_m, p.tiles_n, tm, tn);
-    const int phase = FOLD ? (tm & 3) : 0;
-    if (FOLD) tm >>= 2;
-    const int TH = FOLD ? p.Hin : p.Hout, TW = FOLD ? p.Win : p.Wout;
-    const int tiles_x = (TW + PW - 1) / PW, tiles_y = (TH + PH2 - 1) / PH2;
-    const int tx = tm % tiles_x, ty = (tm / tiles_x) % tiles_y, b = tm / (tiles_x * tiles_y);
-    const int oy0 = ty * PH2, ox0 = tx * PW, n0 = tn * BN;
+    const HaloTile t = halo_tile<PH2, FOLD>(p);
+    const int phase = t.phase, TH = t.TH, TW = t.TW, b = t.b, oy0 = t.oy0, ox0 = t.ox0, n0 = t.n0;
 
+    // This kernel's own patch descriptors, fragment lambdas and epilogue: on halo_patch_desc it measured 0.7 %, on the shared
+    // epilogue 1.4 % longer.  They compute what the shared pieces compute; tests/test_gpu_conv_halo_bits.py holds both.
     int poff[PPW2];  // element offset of the lane's chunk at channel 0; -1: zero page (halo / pad rows)
 #pragma unroll
     for (int j = 0; j < PPW2; ++j) {
@@ -583,17 +621,11 @@ __global__ __launch_bounds__(256, 2) void conv_halo256_kernel(const GemmParams p
         const int uy = oy0 - 1 + qy, ux = ox0 - 1 + qx;
         const bool ok = (q < HROWS2) & (uy >= 0) & (uy < TH) & (ux >= 0) & (ux < TW);
         const int iy = !FOLD && p.upsample ? nearest_src(uy, p.up_sy, p.Hin) : uy, ix = !FOLD && p.upsample ? nearest_src(ux, p.up_sx, p.Win) : ux;
-        const int chunk = slot ^ (((rowswz ? q : qx) >> 1) & 7);  // swizzle by patch COLUMN (see the header)
+        const int chunk = slot ^ (((rowswz ? q : qx) >> 1) & 7);  // = halo_swz, this kernel's own spelling
         poff[j] = ok ? ((b * p.Hin + iy) * p.Win + ix) * p.Cin + chunk * 8 : -1;
     }
     int woff[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int row = (wave * 4 + j) * 8 + lrow;
-        const int chunk = slot ^ ((row >> 1) & 7);
-        const int n = min(n0 + row, p.N - 1);
-        woff[j] = (FOLD ? phase * p.N + n : n) * (int)p.ldw + chunk * 8;   // phase mode: weight slab `phase` of [4][N][4 Cin]
-    }
+    halo_w_desc<FOLD>(woff, p, t, wave, lane);
     // LDS-DMA from inline asm (`lds_dma16_v`, ds_common.h): behind the builtin the compiler turns every LDS wait of the kernel
     // into lgkmcnt(0), and the fragment read-ahead of the k-loop below would wait for the reads it has just issued
     const unsigned lds0 = (unsigned)(size_t)(lds_void*)smem;
@@ -647,7 +679,7 @@ __global__ __launch_bounds__(256, 2) void conv_halo256_kernel(const GemmParams p
     #pragma unroll
             for (int mi = 0; mi < MI; ++mi) {
                 const int q = q0[mi] + shift;
-                ab[mi] = q * 128 + ((lhi ^ (((rowswz ? q : (l31 & 15) + kx) >> 1) & 7)) << 4);
+                ab[mi] = q * 128 + ((lhi ^ (((rowswz ? q : (l31 & 15) + kx) >> 1) & 7)) << 4);   // = halo_swz, this kernel's own spelling
             }
         };
         auto load = [&](V8 (&af)[MI], V8 (&bf)[2], const int (&ab)[MI], const char* cw, int kk) {
@@ -801,7 +833,7 @@ __global__ __launch_bounds__(256, 2) void conv_halo256_kernel(const GemmParams p
             if (p.gn_partial && ok[u]) gn_accumulate(v, gs, gq);
         }
     }
-    if (p.gn_partial) gn_emit(p, gs, gq, smem + 256 * CS_STRIDE, tid, b, ty * tiles_x + tx, n0);
+    if (p.gn_partial) gn_emit(p, gs, gq, smem + 256 * CS_STRIDE, tid, b, t.in_image, n0);
 }
 
 // Weights of the phase mode: packed 3 x 3 weight [Cout][(ky*3+kx) Cin + ci] -> [phase py*2+px][Cout][(a*2+b) Cin + ci], each entry the
@@ -909,12 +941,26 @@ const char* ds_conv_halo_kernel_name(const GemmParams& p) {
     }
 }
 
+// One kernel's instantiations, pixel rows per tile and dynamic LDS, indexed by HaloKernel: the one list behind the launch
+// (halo_instance maps (dtype, up_fold) to the instantiation) and the one-time LDS attribute (every entry); nullptr: none
+// (halo_pick keeps bf16 off the ring kernel).
+typedef void (*HaloFn)(const GemmParams);
+struct HaloFamily {
+    HaloFn f16, f16_fold, bf16;
+    int ph, lds;   // 8 x 16: 40 KiB, 16 x 16: 76 KiB, ring: 96 KiB; each holds its epilogue tile + 4 KiB of GroupNorm partials
+};
+static const HaloFamily g_halo_family[3] = {
+    {conv_halo_kernel<half_t>, conv_halo_kernel<half_t, 4>, conv_halo_kernel<bf16_t>, PH, PROWS * 128 + BN * 128},
+    {conv_halo256_kernel<half_t>, conv_halo256_kernel<half_t, 4>, conv_halo256_kernel<bf16_t>, PH2, LDS2},
+    {conv_halo_deep_kernel<half_t>, conv_halo_deep_kernel<half_t, 4>, nullptr, PH, DEEP_LDS}};
+
+static HaloFn halo_instance(const HaloFamily& k, int dtype, bool up_fold) {
+    return up_fold ? k.f16_fold : dtype == DS_DTYPE_BF16 ? k.bf16 : k.f16;
+}
+
 int ds_launch_conv_halo(const GemmParams& p0, hipStream_t stream) {
     GemmParams p = p0;
     DS_REQUIRE(ds_conv_halo_applicable(p), "conv_halo: shape not supported");
-    const int batch = p.M / (p.Hout * p.Wout);
-    p.tiles_n = (p.N + BN - 1) / BN;
-    const HaloKernel kern = halo_pick(p);
     if (p.up_fold) {
         DS_REQUIRE(p.upsample && p.Hout == 2 * p.Hin && p.Wout == 2 * p.Win, "conv_halo: the phase mode is the exact x2 upsample (%d x %d -> %d x %d)",
                    p.Hin, p.Win, p.Hout, p.Wout);
@@ -931,44 +977,18 @@ int ds_launch_conv_halo(const GemmParams& p0, hipStream_t stream) {
         DS_REQUIRE(planned == 0 || planned == p.gn_chunks,"conv_halo: GroupNorm statistics planned as %d chunks per image, the launch would write %d",
                    planned, p.gn_chunks);
     }
-    if (kern == HALO_16X16) {
-        p.tiles_m = batch * (int)halo_tiles(p, PH2);
-        const size_t lds2 = PBYTES2 + 2 * BN * 128;  // 76 KiB; the 256 x 272 B epilogue tile (68 KiB) + 4 KiB of GroupNorm partials fit inside
-        static unsigned long long attr_devs = 0;
-        if (ds_first_on_device(attr_devs)) {
-            DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_halo256_kernel<half_t>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-            DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_halo256_kernel<bf16_t>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-            DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_halo256_kernel<half_t, 4>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-        }
-        dim3 grid2(p.tiles_m * p.tiles_n);
-        if (p.up_fold) hipLaunchKernelGGL((conv_halo256_kernel<half_t, 4>), grid2, dim3(256), lds2, stream, p);
-        else if (p.dtype == DS_DTYPE_BF16) hipLaunchKernelGGL(conv_halo256_kernel<bf16_t>, grid2, dim3(256), lds2, stream, p);
-        else hipLaunchKernelGGL(conv_halo256_kernel<half_t>, grid2, dim3(256), lds2, stream, p);
-        DS_LAUNCH_CHECK();
-        return 0;
+    const HaloKernel kern = halo_pick(p);
+    const HaloFamily& k = g_halo_family[kern];
+    const HaloFn fn = halo_instance(k, p.dtype, p.up_fold != 0);
+    DS_REQUIRE(fn != nullptr, "conv_halo: no instantiation of %s for this element type", ds_conv_halo_kernel_name(p));
+    static unsigned long long attr_devs[3] = {0, 0, 0};
+    if (k.lds > 64 * 1024 && ds_first_on_device(attr_devs[kern])) {   // (the 8 x 16 kernel's 40 KiB need no opt-in)
+        for (const HaloFn f : {k.f16, k.f16_fold, k.bf16})
+            if (f) DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, k.lds));
     }
-    p.tiles_m = batch * (int)halo_tiles(p, PH);
-    if (kern == HALO_DEEP) {
-        static unsigned long long attr_devs_deep = 0;
-        if (ds_first_on_device(attr_devs_deep)) {
-            DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_halo_deep_kernel<half_t>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEEP_LDS));
-            DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_halo_deep_kernel<half_t, 4>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEEP_LDS));
-        }
-        if (p.up_fold) hipLaunchKernelGGL((conv_halo_deep_kernel<half_t, 4>), dim3(p.tiles_m * p.tiles_n), dim3(256), (size_t)DEEP_LDS, stream, p);
-        else hipLaunchKernelGGL(conv_halo_deep_kernel<half_t>, dim3(p.tiles_m * p.tiles_n), dim3(256), (size_t)DEEP_LDS, stream, p);
-        DS_LAUNCH_CHECK();
-        return 0;
-    }
-    const size_t lds = PROWS * 128 + BN * 128;  // 40 KiB; the 128 x 272 B epilogue tile (34 KiB) + 4 KiB of GroupNorm partials fit inside
-    dim3 grid(p.tiles_m * p.tiles_n);
-    if (p.up_fold) hipLaunchKernelGGL((conv_halo_kernel<half_t, 4>), grid, dim3(256), lds, stream, p);
-    else if (p.dtype == DS_DTYPE_BF16) hipLaunchKernelGGL(conv_halo_kernel<bf16_t>, grid, dim3(256), lds, stream, p);
-    else hipLaunchKernelGGL(conv_halo_kernel<half_t>, grid, dim3(256), lds, stream, p);
+    p.tiles_n = (p.N + BN - 1) / BN;
+    p.tiles_m = p.M / (p.Hout * p.Wout) * (int)halo_tiles(p, k.ph);
+    hipLaunchKernelGGL(fn, dim3(p.tiles_m * p.tiles_n), dim3(256), (size_t)k.lds, stream, p);
     DS_LAUNCH_CHECK();
     return 0;
 }
