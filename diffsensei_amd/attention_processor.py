@@ -70,12 +70,21 @@ class AttentionWeights:
 
 
 def _vt(x: Tensor, w: Tensor) -> Tensor:
-    """V^T panels [B, C, N] = W @ x[b]^T (values stored key-contiguous for the attention kernels)."""
-    return ops.gemm_batched_nt(w, x.contiguous())
+    """V^T panels [B, C, ceil8(N)] = W @ x[b]^T (values stored key-contiguous for the attention kernels).
+
+    The attention kernels read V^T rows 8 keys at a time and the GEMM writes whole 8-column pieces, so a token count that is no
+    multiple of 8 (a 25 x 37 grid) is zero-padded to the next one: the pad columns are then exact zeros, and the kernels mask
+    keys >= N anyway.  The engine's launch plan does the same with slack rows behind its buffers."""
+    x = x.contiguous()
+    n = x.shape[1]
+    if n % 8:
+        x = ops.pad_rows(x, 0, n, (n + 7) // 8 * 8)
+    return ops.gemm_batched_nt(w, x)
 
 
 class AttnProcessor2_0:
-    """Self-attention processor (reference src/models/attention_processor.py:7-96)."""
+    """Self-attention processor (reference src/models/attention_processor.py:7-96).  Any token count: V^T is padded to a
+    multiple of 8 keys (`_vt`), as the engine's launch plan does for odd latent grids."""
 
     def __call__(self, attn, hidden_states: Tensor, encoder_hidden_states=None, attention_mask=None, temb=None,
                  bbox=None, dialog_bbox=None, aspect_ratio=None, *args, **kwargs) -> Tensor:

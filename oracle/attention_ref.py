@@ -35,13 +35,17 @@ def sdpa(qh: Tensor, kh: Tensor, vh: Tensor, mask: Optional[Tensor] = None, q: C
 
 
 def self_attention(x: Tensor, wq: Tensor, wk: Tensor, wv: Tensor, wo: Tensor, bo: Tensor, heads: int,
-                   q: Callable = _id) -> Tensor:
+                   q: Callable = _id, rows: Optional[Tensor] = None) -> Tensor:
     """AttnProcessor2_0 for a BasicTransformerBlock.attn1 (no mask, no group/spatial norm, no residual inside).
 
     reference: src/models/attention_processor.py:56-84 (to_q/to_k/to_v without bias, SDPA, to_out[0] with bias).
+    `rows` (index tensor): only those output rows [b, len(rows), c] - every row is one query against all keys, so this is the
+    full result's `[:, rows]` without the N x N score matrix.
     """
-    b, n, c = x.shape
-    query = q(x @ wq.t())
+    b, _, c = x.shape
+    xq = x if rows is None else x[:, rows]
+    n = xq.shape[1]
+    query = q(xq @ wq.t())
     key = q(x @ wk.t())
     value = q(x @ wv.t())
     o = sdpa(_heads(query, heads), _heads(key, heads), _heads(value, heads))
@@ -90,21 +94,27 @@ def ip_region_mask(bbox: Tensor, sequence_length: int, heads: int, aspect_ratio:
 def masked_ip_cross_attention(x: Tensor, enc: Tensor, bbox: Tensor, aspect_ratio: float,
                               wq: Tensor, wk: Tensor, wv: Tensor, wk_ip: Tensor, wv_ip: Tensor,
                               wo: Tensor, bo: Tensor, heads: int, scale: float,
-                              num_ip_tokens: int, num_dummy_tokens: int, q: Callable = _id) -> Tensor:
+                              num_ip_tokens: int, num_dummy_tokens: int, q: Callable = _id,
+                              rows: Optional[Tensor] = None) -> Tensor:
     """MaskedIPAttnProcessor2_0 for BasicTransformerBlock.attn2.
 
     reference :207-261: q = to_q(x); split enc into text / ip at L-(num_ip+num_dummy); text SDPA;
     ip SDPA with the region mask; `text + scale*ip`; to_out[0].
+    `rows` (index tensor): only those output rows (the region mask is still that of the whole N-token grid).
     """
-    b, n, c = x.shape
+    b, n_all, c = x.shape
+    xq = x if rows is None else x[:, rows]
+    n = xq.shape[1]
     end_pos = enc.shape[1] - (num_ip_tokens + num_dummy_tokens)
     txt, ip = enc[:, :end_pos], enc[:, end_pos:]
-    query = q(x @ wq.t())
+    query = q(xq @ wq.t())
     key, value = q(txt @ wk.t()), q(txt @ wv.t())
     qh = _heads(query, heads)
     t_out = sdpa(qh, _heads(key, heads), _heads(value, heads))
     t_out = q(t_out.transpose(1, 2).reshape(b, n, c))
-    mask = ip_region_mask(bbox, n, heads, aspect_ratio, num_ip_tokens, num_dummy_tokens, dtype=x.dtype)
+    mask = ip_region_mask(bbox, n_all, heads, aspect_ratio, num_ip_tokens, num_dummy_tokens, dtype=x.dtype)
+    if rows is not None:
+        mask = mask[:, :, rows]
     ip_key, ip_value = q(ip @ wk_ip.t()), q(ip @ wv_ip.t())
     i_out = sdpa(qh, _heads(ip_key, heads), _heads(ip_value, heads), mask)
     i_out = q(i_out.transpose(1, 2).reshape(b, n, c))

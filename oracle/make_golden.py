@@ -4,6 +4,7 @@ Run in the build container only (needs /root/reference, which does not exist on 
 
     python -m oracle.make_golden            # every fixture
     python -m oracle.make_golden layouts    # only ip_region_masks_layouts.npz
+    python -m oracle.make_golden realdims   # only realdim_<case>.npz (real-width processors and Resampler)
 
 Imports reference src/models/attention_processor.py and src/models/resampler.py unmodified (they depend
 only on torch), drives them with seeded inputs through a duck-typed `attn` stub that has exactly the
@@ -76,6 +77,79 @@ def write_layout_masks(processor_cls):
     np.savez_compressed(os.path.join(OUT, "ip_region_masks_layouts.npz"), **out)
 
 
+def _save_npz(path, arrays):
+    """np.savez_compressed with a fixed member date, so that two runs write the same bytes."""
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as zf:
+        for k, v in arrays.items():
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            with zf.open(info, "w", force_zip64=True) as fh:
+                np.lib.format.write_array(fh, np.asanyarray(v), allow_pickle=False)
+
+
+def write_realdims(masked_cls, self_cls, resampler_cls):
+    """tests/golden/realdim_<case>.npz: the reference's processors and Resampler at the model's real widths, on the inputs and
+    weights of oracle/realdim_cases.py.  Stored: case name, seed, digest of the inputs, reference outputs in fp32 - for the
+    processors the rows `fixture_rows(case)` of each batch item, all columns - and nothing else (the inputs are regenerated)."""
+    from oracle import realdim_cases as RC
+    total = 0
+    for name in RC.PROCESSOR_CASES:
+        c = RC.processor_case(name)
+        rows = RC.fixture_rows(name)
+        H, W = c["hw"]
+        need = {0, 1, 127, 128, W - 1, W, c["N"] - W, c["N"] - 2, c["N"] - 1}
+        assert need <= set(rows) and len(rows) >= 24 and len(set(rows)) == len(rows), name
+        attn = _AttnStub(c["C"], c["cross_dim"], c["heads"])
+        proc = masked_cls(hidden_size=c["C"], cross_attention_dim=c["cross_dim"], scale=c["scale"],
+                          num_ip_tokens=c["num_ip_tokens"], num_dummy_tokens=c["num_dummy_tokens"])
+        w = c["cross"]
+        with torch.no_grad():
+            attn.to_q.weight.copy_(w["wq"]); attn.to_k.weight.copy_(w["wk"]); attn.to_v.weight.copy_(w["wv"])
+            attn.to_out[0].weight.copy_(w["wo"]); attn.to_out[0].bias.copy_(w["bo"])
+            proc.to_k_ip.weight.copy_(w["wk_ip"]); proc.to_v_ip.weight.copy_(w["wv_ip"])
+            y = proc(attn, c["x"], encoder_hidden_states=c["enc"], bbox=c["bbox"], aspect_ratio=c["aspect_ratio"])
+            attn1 = _AttnStub(c["C"], c["C"], c["heads"])
+            w = c["self"]
+            attn1.to_q.weight.copy_(w["wq"]); attn1.to_k.weight.copy_(w["wk"]); attn1.to_v.weight.copy_(w["wv"])
+            attn1.to_out[0].weight.copy_(w["wo"]); attn1.to_out[0].bias.copy_(w["bo"])
+            y1 = self_cls()(attn1, c["x"])
+        assert y.shape == y1.shape == c["x"].shape and y.dtype == y1.dtype == torch.float32
+        path = os.path.join(OUT, f"realdim_{name}.npz")
+        _save_npz(path, {"case": np.array(name), "seed": np.int64(c["seed"]), "digest": np.array(c["digest"]),
+                         "rows": np.array(rows, dtype=np.int32), "y_masked_ip": y[:, rows].numpy(),
+                         "y_self": y1[:, rows].numpy()})
+        total += os.path.getsize(path)
+        assert os.path.getsize(path) < (1 << 20), (path, os.path.getsize(path))
+
+    c = RC.resampler_case()
+    cfg = c["config"]
+    rs = resampler_cls(**cfg).eval()
+    rs.load_state_dict(c["sd"], strict=True)
+    with torch.no_grad():
+        out = rs(c["x"], c["magi"])
+        out_absent = rs(c["x_absent"], c["magi_absent"])
+    nd, nq = cfg["num_dummy_tokens"], cfg["num_queries"]
+    assert out.shape == (1, nd + RC.RESAMPLER_CHARS * nq, cfg["output_dim"])
+    # characters are processed independently: zeroing some leaves the others' rows (and the dummy rows) as they were, and
+    # every zeroed character gives the same 16 rows - one of them is all the second input adds
+    sl = lambda ch: slice(nd + ch * nq, nd + (ch + 1) * nq)
+    present = [ch for ch in range(RC.RESAMPLER_CHARS) if ch not in RC.RESAMPLER_ABSENT]
+    assert torch.equal(out_absent[:, :nd], out[:, :nd])
+    for ch in present:
+        assert torch.allclose(out_absent[:, sl(ch)], out[:, sl(ch)], atol=1e-6, rtol=0), ch
+    a0 = RC.RESAMPLER_ABSENT[0]
+    for ch in RC.RESAMPLER_ABSENT[1:]:
+        assert torch.allclose(out_absent[:, sl(ch)], out_absent[:, sl(a0)], atol=1e-6, rtol=0), ch
+    path = os.path.join(OUT, f"realdim_{RC.RESAMPLER_CASE}.npz")
+    _save_npz(path, {"case": np.array(RC.RESAMPLER_CASE), "seed": np.int64(c["seed"]), "digest": np.array(c["digest"]),
+                     "out": out.numpy(), "absent_character": np.int32(a0), "out_absent_rows": out_absent[0, sl(a0)].numpy()})
+    total += os.path.getsize(path)
+    assert os.path.getsize(path) < (1 << 20), (path, os.path.getsize(path))
+    assert total < 3 * (1 << 20), total
+    print(f"wrote realdim_*.npz: {total} bytes together")
+
+
 def main():
     sys.path.insert(0, REF)
     from src.models.attention_processor import AttnProcessor2_0, MaskedIPAttnProcessor2_0
@@ -83,6 +157,9 @@ def main():
     os.makedirs(OUT, exist_ok=True)
     if sys.argv[1:] == ["layouts"]:   # only the layout masks (no random numbers involved; the other fixtures stay as they are)
         write_layout_masks(MaskedIPAttnProcessor2_0)
+        return
+    if sys.argv[1:] == ["realdims"]:  # only tests/golden/realdim_*.npz (seeded by oracle/realdim_cases.py, not by torch)
+        write_realdims(MaskedIPAttnProcessor2_0, AttnProcessor2_0, Resampler)
         return
     torch.manual_seed(0)
 
@@ -143,6 +220,9 @@ def main():
 
     # ---- 5. region masks at other token layouts
     write_layout_masks(MaskedIPAttnProcessor2_0)
+
+    # ---- 6. processors and Resampler at the model's real widths (last: building the modules draws from torch's generator)
+    write_realdims(MaskedIPAttnProcessor2_0, AttnProcessor2_0, Resampler)
     print("wrote", sorted(os.listdir(OUT)))
 
 

@@ -14,6 +14,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests._gates import gate
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "mllm_tiny.npz")
@@ -211,7 +213,11 @@ def test_qwen_resampler_at_the_agent_dimensions(hip_lib, E, KV):
     sd = random_qwen_resampler_state_dict(8, E, KV, DEV, seed=E)
     x = _h((1, 64, KV), torch.Generator().manual_seed(KV))
     ref = R.qwen_resampler({k: v.float().cpu() for k, v in sd.items()}, x.float(), 32)
-    _close(QwenResampler(sd, 32, DEV)(x.to(DEV)), ref, tol=1e-2, what=f"resampler {KV}->{E}")
+    got = QwenResampler(sd, 32, DEV)(x.to(DEV)).float().cpu()
+    assert got.shape == ref.shape and torch.isfinite(got).all()
+    # measured on MI355X: 9.6e-4 (2048 -> 5120), 1.06e-3 (5120 -> 2048); gate = 3 x
+    gate(f"Qwen resampler {KV}->{E} vs oracle: max|err|/max|ref|", ((got - ref).abs().max() / ref.abs().max()).item(),
+         2.9e-3 if E == 5120 else 3.2e-3)
 
 
 def _check_ids(got, want, margins, what):
