@@ -25,7 +25,7 @@ void ds_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* ds_last_error(void) { return g_err; }
-int ds_version(void) { return 107; }
+int ds_version(void) { return 108; }
 
 int ds_device_info(int* cu_count, int* lds_bytes, char* arch_name, int arch_name_len) {
     int dev = 0;
@@ -815,7 +815,7 @@ static LoraMergeParams lora_merge_params(const ds_op& o) {
     m.W = H(p[0]); m.out = HM(p[1]); m.A = H(p[2]); m.B = H(p[3]);
     m.seg = reinterpret_cast<const int*>(p[4]); m.s = reinterpret_cast<const float*>(p[5]);
     m.map = reinterpret_cast<const int*>(p[6]); m.colscale = H(p[7]); m.out2 = HM(p[8]);
-    m.N = i[0]; m.K = i[1]; m.R = i[2]; m.nseg = i[3];
+    m.N = i[0]; m.K = i[1]; m.R = i[2]; m.nseg = i[3]; m.cin = i[4];
     m.ldw = l[0]; m.ldo = l[1]; m.lda = l[2]; m.ldb = l[3]; m.ldo2 = l[4];
     return m;
 }
@@ -1060,7 +1060,7 @@ int ds_op_describe(const ds_op* op, char* name, int name_len, double* flops, dou
         case DS_OP_LLM_RMSNORM_SLOTS: nm = "llm_rmsnorm_kernel"; by = 4.0 * i[0] * (double)i[1]; break;
         case DS_OP_LLM_SELECT_SLOTS: nm = "llm_select_kernel"; by = 2.0 * i[0] * (double)i[4]; break;
         case DS_OP_LLM_SELECT: nm = "llm_select_kernel"; by = 2.0 * i[0]; break;
-        case DS_OP_LORA_MERGE:   // W in, out (and out2) out, A and B once; the adapters' products
+        case DS_OP_LORA_MERGE:   // W in, out (and out2) out, A and B once; the adapters' products (convolution mode: K = 9 Cin)
             nm = "lora_merge_kernel";
             fl = 2.0 * i[0] * (double)i[1] * i[2];
             by = 2.0 * ((op->p[8] ? 3.0 : 2.0) * i[0] * (double)i[1] + (double)i[2] * ((double)i[0] + i[1]));

@@ -290,9 +290,10 @@ struct LoraMergeParams {
     half_t* out2 = nullptr;            // optional [N,K] rows (ldo2): f16(f32(out) * f32(colscale[k]))
     long ldw = 0, ldo = 0, lda = 0, ldb = 0, ldo2 = 0;
     int N = 0, K = 0, R = 0, nseg = 0;
+    int cin = 0;                       // > 0: convolution mode - W is [N][cin][3][3] (checkpoint order), out / A are tap-major, K = 9 cin
 };
 int ds_launch_lora_merge(const LoraMergeParams& p, hipStream_t stream);
-#define DS_LORA_GROUP 24   // matrices per launch: 24 x 128 bytes of parameters fit the 4 KiB of kernel arguments
+#define DS_LORA_GROUP 24   // matrices per launch: 24 x 136 bytes of parameters fit the 4 KiB of kernel arguments
 // `count` (1..DS_LORA_GROUP) independent merges in ONE launch; the plan executor groups consecutive DS_OP_LORA_MERGE ops
 int ds_launch_lora_merge_group(const LoraMergeParams* ps, int count, hipStream_t stream);
 

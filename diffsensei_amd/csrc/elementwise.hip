@@ -253,6 +253,10 @@ __global__ __launch_bounds__(256) void philox_normal_kernel(const long long* __r
 // Euler Ancestral (kind 3) is diffusers' EulerAncestralDiscreteScheduler [3P]: the Euler update towards sigma_down in
 // fp32, then sigma_up * noise with the noise drawn in the model output's dtype (fp16) and the product an fp16 tensor.
 // The noise is this thread's own Philox draw for (seed[n], pixel, *ctr): nothing is read for it but the seed.
+// LCM (kind 4) is diffusers' LCMScheduler [3P]: x0 from the epsilon prediction, the consistency boundary condition
+// c_out * x0 + c_skip * x in fp32, then sqrt(a_prev) * denoised + sqrt(1 - a_prev) * noise with the noise of kind 3 (same
+// stream, same counter, an fp16 tensor times a scalar).  Six scalars per row: four in the table, the pair of the NEXT
+// timestep in the solver row, which is {1, 0} on the last row - the denoised value itself.
 // GV: the guidance scale of panel n is p.guidance[n] instead of column 7 of the table row - the same product at the same
 // rounding points.  An instantiation of its own, so that the one-scalar launch stays the kernel it was (34 SGPRs; the
 // vector's pointer costs 4 more: profiles/per_panel_scales_resource_usage_*.txt).
@@ -298,7 +302,7 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p, 
         x0k = rv.x0k; nz = rv.noise;
         m = (float)rv.mask[(long)n * p.HW + pix];
     }
-    const float* sv = p.kind == 2 ? (PS ? psv : coef_row(p.solver, ctr)) : nullptr;
+    const float* sv = (p.kind == 2 || p.kind == 4) ? (PS ? psv : coef_row(p.solver, ctr)) : nullptr;
     const h4 eu = *reinterpret_cast<const h4*>(p.eps + ((long)n * p.HW + pix) * 4);
     h4 e = eu;
     if (p.do_cfg) {
@@ -312,7 +316,7 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p, 
         }
     }
     float z[4] = {0.f, 0.f, 0.f, 0.f};
-    if (p.kind == 3) panel_normals(p.seeds[n], pix, PS ? j : (ctr ? *ctr : 0), 0, z);   // stream 0 = sampler-step noise
+    if (p.kind == 3 || p.kind == 4) panel_normals(p.seeds[n], pix, PS ? j : (ctr ? *ctr : 0), 0, z);   // stream 0 = sampler-step noise
     h4 xin;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -334,6 +338,10 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p, 
             const float deriv = (x - pred_x0) / s;
             xn = x + deriv * (cf[3] - s);
             xn = xn + (float)(half_t)(cf[4] * (float)(half_t)z[c]);
+        } else if (p.kind == 4) {  // LCM: k0 = sqrt(a_t), k1 = sqrt(1-a_t), k2 = c_out, k3 = c_skip; sv = {sqrt(a_prev), sqrt(1-a_prev)}
+            const float pred_x0 = (x - cf[3] * ef) / cf[2];
+            const float den = cf[4] * pred_x0 + cf[5] * x;
+            xn = sv[0] * den + (float)(half_t)(sv[1] * (float)(half_t)z[c]);   // the last row is {1, 0}: the denoised value, no noise
         } else {                   // DPM-Solver++: sv = {order, sigma_s, alpha_s, a, b, 1/r0, c, -}
             half_t* pp = p.prev_x0 + ((long)n * 4 + c) * p.HW + pix;
             const half_t x0 = (half_t)((float)(half_t)(x - (float)(half_t)(sv[1] * ef)) / sv[2]);
@@ -619,10 +627,12 @@ int ds_launch_add_time_ids(const half_t* text_embeds, const half_t* time_ids, ha
 int ds_launch_sampler_step(const SamplerStepParams& p, const int* ctr, hipStream_t stream) {
     DS_REQUIRE(p.C == 4, "sampler_step: latent channels must be 4");
     DS_REQUIRE(p.ns > 0 && p.HW > 0 && p.coef, "sampler_step: bad arguments");
-    DS_REQUIRE(p.kind >= 0 && p.kind <= 3,
-               "sampler_step: kind must be 0 (Euler), 1 (DDIM), 2 (DPM-Solver++) or 3 (Euler Ancestral)");
+    DS_REQUIRE(p.kind >= 0 && p.kind <= 4,
+               "sampler_step: kind must be 0 (Euler), 1 (DDIM), 2 (DPM-Solver++), 3 (Euler Ancestral) or 4 (LCM)");
     DS_REQUIRE(p.kind != 2 || (p.prev_x0 && p.solver), "sampler_step: kind 2 needs prev_x0 and the solver rows");
+    DS_REQUIRE(p.kind != 4 || p.solver, "sampler_step: kind 4 needs the solver rows");
     DS_REQUIRE(p.kind != 3 || p.seeds, "sampler_step: kind 3 needs the per-panel seeds");
+    DS_REQUIRE(p.kind != 4 || p.seeds, "sampler_step: kind 4 needs the per-panel seeds");
     DS_REQUIRE(!p.redraw_on || p.redraw, "sampler_step: the redraw flag is set without the redraw buffer");
     DS_REQUIRE(!p.redraw_on || ((uintptr_t)p.redraw & 15) == 0, "sampler_step: the redraw buffer must be 16-byte aligned");
     const long total = (long)p.ns * p.HW;
@@ -644,11 +654,12 @@ int ds_launch_sampler_step_panels(const SamplerStepParams& p, const int* ctr, hi
     DS_REQUIRE(p.ns > 0 && p.HW > 0 && p.eps && p.latents && p.model_in, "sampler_step (panel schedules): bad arguments");
     DS_REQUIRE(p.coef && ctr, "sampler_step (panel schedules): the panel-schedule buffer and the step counter are needed");
     DS_REQUIRE(((uintptr_t)p.coef & 15) == 0, "sampler_step (panel schedules): the panel-schedule buffer must be 16-byte aligned");
-    DS_REQUIRE(p.kind >= 0 && p.kind <= 3,
-               "sampler_step: kind must be 0 (Euler), 1 (DDIM), 2 (DPM-Solver++) or 3 (Euler Ancestral)");
+    DS_REQUIRE(p.kind >= 0 && p.kind <= 4,
+               "sampler_step: kind must be 0 (Euler), 1 (DDIM), 2 (DPM-Solver++), 3 (Euler Ancestral) or 4 (LCM)");
     DS_REQUIRE(!p.do_cfg || p.guidance, "sampler_step (panel schedules): guidance is the per-panel vector, it is missing");
     DS_REQUIRE(p.kind != 2 || p.prev_x0, "sampler_step (panel schedules): kind 2 needs prev_x0");
     DS_REQUIRE(p.kind != 3 || p.seeds, "sampler_step: kind 3 needs the per-panel seeds");
+    DS_REQUIRE(p.kind != 4 || p.seeds, "sampler_step: kind 4 needs the per-panel seeds");
     DS_REQUIRE(!p.redraw_on || p.redraw, "sampler_step: the redraw flag is set without the redraw buffer");
     DS_REQUIRE(!p.redraw_on || ((uintptr_t)p.redraw & 15) == 0, "sampler_step: the redraw buffer must be 16-byte aligned");
     const long total = (long)p.ns * p.HW;

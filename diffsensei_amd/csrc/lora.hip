@@ -27,6 +27,14 @@
 // W, out, out2 and A move in 16-byte accesses throughout; the transposed staging of A writes single halves to LDS (4-way bank
 // conflicts at this pitch), which the global traffic hides.
 // No atomics: every output element is written by one lane.
+//
+// Convolution mode (cin > 0): W is a 3x3 weight as the checkpoint has it, [N][Cin][3][3], and out / A / K are in the packed
+// tap-major order of engine.pack_conv3x3, k = (ky * 3 + kx) * Cin + ci, K = 9 Cin:
+//   out[n, tap * Cin + ci] = f16( f32(W[n][ci][tap]) + sum_i s_i * (B_i A_i)[n, tap * Cin + ci] )
+// Only the read of W differs: Cin is a multiple of 8, so an 8-column piece never straddles a tap (a 64-column tile may, when
+// Cin < 64: tap and channel are found per piece), and the piece is 8 halves 18 bytes apart.  The nine tap tiles of one
+// (row block, channel range) read the same lines of W, eight of the nine times out of L2; the stores stay whole 16-byte
+// pieces.  No adapter gives the bits of pack_conv3x3(W): the base of the state dict is the only base there is.
 #include "ds_common.h"
 #include "ds_kernels.h"
 
@@ -64,7 +72,16 @@ __global__ __launch_bounds__(256) void lora_merge_kernel(LoraMergeGroup grp) {
     for (int hh = 0; hh < 2; ++hh) {
         const int kk = k0 + 32 * hh + 8 * g;
         h8 w = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (n_ok && kk < p.K) w = *reinterpret_cast<const h8*>(p.W + src * p.ldw + kk);
+        if (n_ok && kk < p.K) {
+            if (p.cin > 0) {   // checkpoint order [ci][tap]: 8 channels of one tap, 18 bytes apart; the other taps' blocks hit the same lines in L2
+                const int tap = kk / p.cin, ci = kk - tap * p.cin;
+                const half_t* wr = p.W + src * p.ldw + (long)ci * 9 + tap;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) w[j] = wr[9 * j];
+            } else {
+                w = *reinterpret_cast<const h8*>(p.W + src * p.ldw + kk);
+            }
+        }
 #pragma unroll
         for (int j = 0; j < 8; ++j) tot[hh][j] = (float)w[j];
     }
@@ -147,7 +164,9 @@ static int lora_merge_check(const LoraMergeParams& p) {
     DS_REQUIRE(p.nseg >= 0 && p.nseg <= DS_LORA_MAX_SEGMENTS, "lora_merge: %d segments (at most %d)", p.nseg, DS_LORA_MAX_SEGMENTS);
     DS_REQUIRE(p.R >= 0, "lora_merge: negative rank total");
     DS_REQUIRE(p.nseg == 0 || (p.A && p.B && p.seg && p.s && p.R > 0), "lora_merge: adapters need A, B, seg, s and R > 0");
-    DS_REQUIRE((const void*)p.W != (const void*)p.out && (const void*)p.W != (const void*)p.out2,
+    DS_REQUIRE(p.cin == 0 || (p.cin > 0 && p.cin % 8 == 0 && p.K == 9 * p.cin && p.ldw == (long)p.K),
+               "lora_merge: convolution mode needs Cin (%d) a positive multiple of 8, K (%d) = 9 Cin and a contiguous base", p.cin, p.K);
+    DS_REQUIRE((const void*)p.W != (const void*)p.out &&(const void*)p.W != (const void*)p.out2,
                "lora_merge: the base weight W is read only and must not be an output (merge from the base, not in place)");
     DS_REQUIRE((p.out2 != nullptr) == (p.colscale != nullptr), "lora_merge: out2 and colscale come together");
     DS_REQUIRE(p.out2 != p.out, "lora_merge: out2 must not be out");

@@ -14,14 +14,14 @@ transformer); conv weights [Cout, 3*3*Cin]; V operands of attention stored key-c
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
 from . import _lib, ops
 from ._lib import OP, DsOp, check
 from .attention_processor import mask_grid_size
-from .schedulers import KIND_DPM, KIND_EULER_ANCESTRAL
+from .schedulers import KIND_DPM, NOISE_KINDS, SOLVER_KINDS
 from .unet_config import AttnSpec, ResnetSpec, UNetMangaConfig, build_topology
 
 Tensor = torch.Tensor
@@ -293,13 +293,18 @@ class PackedUNet:
             out[f"{t}.ff.net.0.proj.weight_ln"], out[f"{t}.ff.net.0.proj.c_ln"], out[f"{t}.ff.net.0.proj.bias_ln"] = gwp, c2p, b2p
         return out
 
-    def refresh_derived(self, blocks: Dict[str, set]) -> None:
+    def refresh_derived(self, blocks: Dict[str, set], upsamplers: Sequence[str] = ()) -> None:
         """After weights of the transformer blocks `blocks` ({block: parts of LN_PARTS}) were rewritten in place (LoRA merge):
         re-derive, INTO the existing storage, what packing derives from them - the c / b' vectors of the fused LayerNorms,
         from the gamma (.) W copies the merge wrote as its second output, with the functions packing uses (`ln_fused_cb`,
-        `ln_fused_vb`), all blocks of one width in one call - and the lazily made 320-row GEGLU copies.  Pointers do not
-        change, so plans and graphs stay valid."""
+        `ln_fused_vb`), all blocks of one width in one call - and the lazily made 320-row GEGLU copies.  `upsamplers`: whose
+        packed 3x3 weight was rewritten; where the four folded phase weights exist (`upsample_fold`) the native fold kernel
+        recomputes them in place.  Pointers do not change, so plans and graphs stay valid."""
         w = self.w
+        for name in upsamplers:
+            if name + ".weight.up2fold" in w:
+                from . import ops
+                ops.fold_upsample2x(w[name + ".weight"], out=w[name + ".weight.up2fold"])
         groups: Dict[Tuple, List[str]] = {}
         for t, parts in blocks.items():
             if f"{t}.attn1.qk.weight_ln" not in w:
@@ -917,10 +922,11 @@ class UNetEngine:
         if kind == KIND_DPM:
             if self.prev_x0 is None or self.prev_x0.shape != self.latents.shape:
                 self.prev_x0 = self._alloc(tuple(self.latents.shape), torch.float16)
+        if kind in SOLVER_KINDS:
             if self.solver is None:
                 self.solver = self._alloc((self.table.shape[0], 8), torch.float32)
                 self.solver.zero_()
-        if kind == KIND_EULER_ANCESTRAL:
+        if kind in NOISE_KINDS:
             if self.noise_seeds is None or self.noise_seeds.shape[0] != ns:
                 self.noise_seeds = self._alloc((ns,), torch.int64)
                 self.noise_seeds.zero_()
@@ -942,8 +948,9 @@ class UNetEngine:
     def _build_step_plan(self):
         """The step plan of the built sampler over the buffers `build_sampler` allocated (nothing is allocated here)."""
         ns, kind, do_cfg, redraw, panels = self._sampler_key
-        prev_x0, solver = (self.prev_x0, self.solver) if kind == KIND_DPM else (None, None)
-        noise_seeds = self.noise_seeds if kind == KIND_EULER_ANCESTRAL else None
+        prev_x0 = self.prev_x0 if kind == KIND_DPM else None
+        solver = self.solver if kind in SOLVER_KINDS else None
+        noise_seeds = self.noise_seeds if kind in NOISE_KINDS else None
         if panels:
             # the forward with one timestep per row (row b = panel b % ns) and the step on the panels' own rows; the solver
             # rows live in the panel-schedule buffer, which travels in the table's slot
@@ -993,8 +1000,8 @@ class UNetEngine:
         return vals
 
     def load_schedule(self, table_rows: Tensor, solver_rows: Optional[Tensor] = None, noise_seeds=None, guidance=None):
-        """table_rows: fp32 [n_steps, 8]; solver_rows: fp32 [n_steps, 8], the DPM-Solver++ rows (kind 2 only);
-        noise_seeds: one non-negative int64 per panel, the Euler Ancestral Philox keys (kind 3 only)
+        """table_rows: fp32 [n_steps, 8]; solver_rows: fp32 [n_steps, 8], the DPM-Solver++ or LCM rows (kinds 2 and 4);
+        noise_seeds: one non-negative int64 per panel, the Philox keys of Euler Ancestral and LCM (kinds 3 and 4)
         (see include/diffsensei_hip.h); resets the device step counter.  The seed buffer is static: a captured step
         graph replays with the new seeds and, through the device step counter, new noise every step.
         guidance: one guidance scale per panel (`ns` values) in place of column 7 of the table; values that differ
@@ -1011,10 +1018,10 @@ class UNetEngine:
         if n > self.table.shape[0]:
             raise ValueError("too many steps for the scalar table")
         kind = self.sampler_kind
-        if (solver_rows is not None) != (kind == KIND_DPM):
-            raise ValueError(f"solver rows are given exactly for a DPM-Solver++ sampler (built kind: {kind})")
-        if (noise_seeds is not None) != (kind == KIND_EULER_ANCESTRAL):
-            raise ValueError(f"noise seeds are given exactly for an Euler Ancestral sampler (built kind: {kind})")
+        if (solver_rows is not None) != (kind in SOLVER_KINDS):
+            raise ValueError(f"solver rows are given exactly for a DPM-Solver++ or LCM sampler (built kind: {kind})")
+        if (noise_seeds is not None) != (kind in NOISE_KINDS):
+            raise ValueError(f"noise seeds are given exactly for an Euler Ancestral or LCM sampler (built kind: {kind})")
         seeds = None
         if noise_seeds is not None:
             seeds = torch.as_tensor(noise_seeds, dtype=torch.int64).reshape(-1)
@@ -1082,10 +1089,10 @@ class UNetEngine:
         rows = torch.as_tensor(rows, dtype=torch.float32)
         if rows.dim() != 2 or rows.shape[1] != 8 or not 1 <= rows.shape[0] <= ops.PANEL_MAX_ROWS:
             raise ValueError(f"load_slots: rows {tuple(rows.shape)}, [steps, 8] with 1 <= steps <= {ops.PANEL_MAX_ROWS} is needed")
-        if (solver_rows is not None) != (kind == KIND_DPM):
-            raise ValueError(f"solver rows are given exactly for a DPM-Solver++ sampler (built kind: {kind})")
-        if (seeds is not None) != (kind == KIND_EULER_ANCESTRAL):
-            raise ValueError(f"noise seeds are given exactly for an Euler Ancestral sampler (built kind: {kind})")
+        if (solver_rows is not None) != (kind in SOLVER_KINDS):
+            raise ValueError(f"solver rows are given exactly for a DPM-Solver++ or LCM sampler (built kind: {kind})")
+        if (seeds is not None) != (kind in NOISE_KINDS):
+            raise ValueError(f"noise seeds are given exactly for an Euler Ancestral or LCM sampler (built kind: {kind})")
         if (latents is None) == (redraw is None):
             raise ValueError("load_slots: `latents` (a plain request) or `redraw` (a redraw request), one of them")
         if redraw is not None and not rd:

@@ -9,7 +9,7 @@ directory layout [3P] is read directly:
 
     model_index.json                      component table {name: [library, class]} + pipeline flags
     scheduler/scheduler_config.json       `_class_name` EulerDiscreteScheduler | DDIMScheduler | DPMSolverMultistepScheduler
-                                          | EulerAncestralDiscreteScheduler + its constructor arguments
+                                          | EulerAncestralDiscreteScheduler | LCMScheduler + its constructor arguments
     vae/config.json + weights             AutoencoderKL (only the decoder + post_quant_conv are used on this path)
     text_encoder/, text_encoder_2/        transformers CLIPTextModel / CLIPTextModelWithProjection (config.json + weights)
     tokenizer/, tokenizer_2/              transformers CLIPTokenizer files (loaded with transformers, host only)

@@ -15,8 +15,16 @@ Host side only - nothing here computes on the data path:
   c / b' vectors of the fused LayerNorms, the 320-row GEGLU copies) is re-derived into its existing storage by the packing
   functions themselves (`PackedUNet.refresh_derived`).
 
+Targets (`all_target_modules`) are the transformer-block linears (`target_modules`, what the reference trains) and, for the
+distillation and style adapters that reach further, conv1 / conv2 / conv_shortcut / time_emb_proj of every resnet and the
+down / upsampler convolutions.  A 3x3 weight lives in the packed tap-major order while its base and the adapter come in
+checkpoint order: the kernel's convolution mode reads the base as it lies and the adapter's down matrix is permuted once
+at load time (`pack_conv_down`), so the state dict's tensor stays the only base.  conv_shortcut is a plain matrix,
+time_emb_proj a row range of `temb_all.weight`, and an upsampler's folded phase weights are recomputed in place.
+
 The peft key names (`<module>.lora_A[.<adapter>].weight` / `.lora_B...`) are restated from peft's saved format; peft itself
-is not a dependency.
+is not a dependency.  The underscore names (`lora_unet_<module with '.' written '_'>.lora_down.weight`) are resolved through
+a table built from this UNet's own targets (`underscore_table`).
 """
 from __future__ import annotations
 
@@ -36,7 +44,14 @@ MAX_RANK = 256
 BLOCK_LEAVES = ("attn1.to_q", "attn1.to_k", "attn1.to_v", "attn1.to_out.0", "attn2.to_q", "attn2.to_k", "attn2.to_v",
                 "attn2.to_out.0", "ff.net.0.proj", "ff.net.2")
 _PREFIXES = ("unet.", "base_model.model.")
-_KEY = re.compile(r"^(?P<m>.+?)\.(?:(?P<peft>lora_[AB])(?:\.(?P<ad>[^.]+))?\.weight|lora\.(?P<dif>down|up)\.weight|(?P<alpha>alpha))$")
+_KEY = re.compile(r"^(?P<m>.+?)\.(?:(?P<peft>lora_[AB])(?:\.(?P<ad>[^.]+))?\.weight|lora\.(?P<dif>down|up)\.weight"
+                  r"|lora_(?P<und>down|up)\.weight|(?P<alpha>alpha))$")
+UNDERSCORE_PREFIX = "lora_unet_"
+_SGM = ("input_blocks_", "middle_block_", "output_blocks_", "time_embed_", "label_emb_", "out_")
+# adapter families that are not a plain B A product: refused by key, never half-merged
+_OTHER_FAMILIES = (("lora_mid", "a Tucker-decomposed convolution adapter (LoCon lora_mid)"), ("hada_", "a LoHa (Hadamard) adapter"),
+                   ("lokr_", "a LoKr (Kronecker) adapter"), ("dora_scale", "a DoRA magnitude"),
+                   ("lora_magnitude_vector", "a DoRA magnitude"))
 
 
 def target_modules(cfg: UNetMangaConfig) -> "OrderedDict[str, Tuple[int, int]]":
@@ -55,6 +70,37 @@ def target_modules(cfg: UNetMangaConfig) -> "OrderedDict[str, Tuple[int, int]]":
             if len(shp) == 2:
                 out[m] = shp
     return out
+
+
+def all_target_modules(cfg: UNetMangaConfig) -> "OrderedDict[str, Tuple[int, ...]]":
+    """module path -> shape of the base weight of everything an adapter may target: the transformer-block linears of
+    `target_modules` as (N, K), then per resnet conv1 / conv2 (Cout, Cin, 3, 3), conv_shortcut (Cout, Cin, 1, 1) and
+    time_emb_proj (Cout, time_embed_dim), and the down / upsampler convolutions (C, C, 3, 3).  conv_in, conv_out, the time and
+    add embeddings, every norm, to_k_ip / to_v_ip and the dialog embedding are not targets."""
+    shapes = param_shapes(cfg)
+    topo = build_topology(cfg)
+    out: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict(target_modules(cfg))
+    for blk in list(topo.down) + [topo.mid] + list(topo.up):
+        for r in blk["resnets"]:
+            for leaf in ("conv1", "conv2", "conv_shortcut", "time_emb_proj"):
+                if f"{r.prefix}.{leaf}.weight" in shapes:
+                    out[f"{r.prefix}.{leaf}"] = tuple(shapes[f"{r.prefix}.{leaf}.weight"])
+        for smp in (blk.get("downsample"), blk.get("upsample")):
+            if smp:
+                out[smp] = tuple(shapes[smp + ".weight"])
+    return out
+
+
+def underscore_table(cfg: UNetMangaConfig) -> Dict[str, str]:
+    """{module path with '.' replaced by '_': module path} over `all_target_modules(cfg)`: how a `lora_unet_<name>` key finds
+    its module ('_' also occurs inside names - to_q, proj_in - so the name is looked up, never split).  The underscore form
+    must be unique."""
+    table: Dict[str, str] = {}
+    for m in all_target_modules(cfg):
+        u = m.replace(".", "_")
+        assert u not in table, f"underscore names collide: {table[u]} and {m} both give {u}"
+        table[u] = m
+    return table
 
 
 def _strip(key: str) -> str:
@@ -80,54 +126,83 @@ def drop_text_encoder_keys(sd: Dict[str, Tensor]) -> Tuple[Dict[str, Tensor], in
 
 def parse_lora_state_dict(sd: Dict[str, Tensor], alpha: Optional[float] = None, cfg: Optional[UNetMangaConfig] = None,
                           device=None) -> Dict[str, Tuple[Tensor, Tensor, float]]:
-    """{module: (A [r,K], B [N,r], alpha)} in f16 (on `device` if given) from
+    """{module: (A, B [N,r], alpha)} in f16 (on `device` if given) from
 
         peft        <module>.lora_A.weight / .lora_B.weight, also with an adapter name (<module>.lora_A.default.weight)
         diffusers   <module>.lora.down.weight / .lora.up.weight
         both        optional prefixes `unet.` / `base_model.model.`, optional scalar <module>.alpha
+        underscore  lora_unet_<module with '.' written '_'>.lora_down.weight / .lora_up.weight / .alpha
 
     `module` is a diffusers UNet path (down_blocks.1.attentions.0.transformer_blocks.0.attn1.to_q).  The merged factor is
     alpha / r: the `alpha` argument, else the dict's `<module>.alpha`, else r (the reference's lora_alpha = lora_rank).
-    Every nn.Linear of the transformer blocks of `cfg` (default: SDXL) is a target; any other key is a ValueError that names
-    it - convolutions, time embeddings, to_k_ip / to_v_ip, processor-era `to_q_lora` names, kohya `lora_unet_*` names and
-    `text_encoder*` adapters included: nothing is ignored silently."""
+    Every module of `all_target_modules(cfg)` (default: SDXL) is a target.  For a linear A is [r, K]; for a convolution A is
+    [r, Cin, kh, kw] with the layer's own kernel size and B is [Cout, r, 1, 1] or [Cout, r] (returned 2-D):
+    dW[o,i,ky,kx] = sum_r B[o,r] A[r,i,ky,kx].  Any other key is a ValueError that names it - conv_in / conv_out, the time and
+    add embeddings, norms, to_k_ip / to_v_ip, processor-era `to_q_lora` names, SGM block names (`lora_unet_input_blocks_...`),
+    Tucker / LoHa / LoKr / DoRA tensors and `text_encoder*` adapters included: nothing is ignored silently."""
     cfg = cfg or sdxl_config()
-    targets = target_modules(cfg)
+    targets = all_target_modules(cfg)
+    under = underscore_table(cfg)
     if not sd:
         raise ValueError("LoRA state dict is empty")
     down: Dict[str, Tensor] = {}
     up: Dict[str, Tensor] = {}
     alphas: Dict[str, float] = {}
     names: Dict[str, str] = {}
+    keys: Dict[str, List[str]] = {}
     bad: List[str] = []
     for key, v in sd.items():
-        mt = _KEY.match(_strip(key))
+        for mark, what in _OTHER_FAMILIES:
+            if mark in key:
+                raise ValueError(f"LoRA key {key} belongs to {what}; only plain down / up (B A) adapters are merged")
+        k = _strip(key)
+        if k.startswith(UNDERSCORE_PREFIX):
+            rest = k[len(UNDERSCORE_PREFIX):]
+            if rest.startswith(_SGM):
+                raise ValueError(f"LoRA key {key} uses the SGM (original Stable Diffusion) block naming - input_blocks / "
+                                 f"middle_block / output_blocks; convert the adapter to diffusers module names first")
+            u, dot, tail = rest.partition(".")
+            k = f"{under[u]}.{tail}" if dot and u in under else None
+        mt = _KEY.match(k) if k is not None else None
         if mt is None or mt.group("m") not in targets:
             bad.append(key)
             continue
         m = mt.group("m")
+        keys.setdefault(m, []).append(key)
         if mt.group("alpha"):
             alphas[m] = float(v)
             continue
-        is_down = mt.group("peft") == "lora_A" or mt.group("dif") == "down"
+        is_down = mt.group("peft") == "lora_A" or "down" in (mt.group("dif"), mt.group("und"))
         slot = down if is_down else up
         ad = mt.group("ad") or ""
         if m in slot or names.setdefault(m, ad) != ad:
             raise ValueError(f"LoRA state dict holds more than one adapter for {m} (key {key}): load them one at a time")
         slot[m] = v
     if bad:
-        raise ValueError(f"LoRA keys that are not adapters of a transformer-block linear of this UNet (to_q/to_k/to_v/to_out.0 of "
-                         f"attn1/attn2, ff.net.0.proj, ff.net.2, proj_in, proj_out) and are not merged: {_first(bad)}")
+        raise ValueError(f"LoRA keys that are not adapters of a target of this UNet (the transformer-block linears, proj_in, "
+                         f"proj_out, and per resnet conv1, conv2, conv_shortcut, time_emb_proj, the down / upsampler "
+                         f"convolutions) and are not merged: {_first(bad)}")
     lone = sorted(set(down) ^ set(up)) + sorted(m for m in alphas if m not in down)
     if lone:
-        raise ValueError(f"LoRA modules without both a down (lora_A) and an up (lora_B) matrix: {_first(lone)}")
+        raise ValueError(f"LoRA modules without both a down (lora_A) and an up (lora_B) matrix: {_first(lone)} "
+                         f"(keys {_first([k for m in lone for k in keys[m]])})")
     out: Dict[str, Tuple[Tensor, Tensor, float]] = {}
     for m in down:
         A, B = down[m], up[m]
-        N, K = targets[m]
-        if A.dim() != 2 or B.dim() != 2 or A.shape[1] != K or B.shape[0] != N or A.shape[0] != B.shape[1]:
-            raise ValueError(f"LoRA {m}: A {tuple(A.shape)} / B {tuple(B.shape)} do not fit the [{N}, {K}] weight "
-                             f"(A is [r, {K}], B is [{N}, r])")
+        shp = targets[m]
+        N, K = shp[0], shp[1]
+        if len(shp) == 4:
+            kh, kw = shp[2], shp[3]
+            if B.dim() == 4 and tuple(B.shape[2:]) == (1, 1):
+                B = B.reshape(B.shape[0], B.shape[1])
+            fits = A.dim() == 4 and B.dim() == 2 and tuple(A.shape[1:]) == (K, kh, kw) and B.shape[0] == N and A.shape[0] == B.shape[1]
+            want = f"A is [r, {K}, {kh}, {kw}] with the layer's own kernel size, B is [{N}, r, 1, 1] or [{N}, r]"
+        else:
+            fits = A.dim() == 2 and B.dim() == 2 and A.shape[1] == K and B.shape[0] == N and A.shape[0] == B.shape[1]
+            want = f"A is [r, {K}], B is [{N}, r]"
+        if not fits:
+            raise ValueError(f"LoRA {m}: A {tuple(A.shape)} / B {tuple(up[m].shape)} do not fit the {list(shp)} weight "
+                             f"({want}; keys {_first(keys[m])})")
         r = A.shape[0]
         if not 1 <= r <= MAX_RANK:
             raise ValueError(f"LoRA {m}: rank {r} is outside 1..{MAX_RANK}")
@@ -141,6 +216,12 @@ def parse_lora_state_dict(sd: Dict[str, Tensor], alpha: Optional[float] = None, 
             A16, B16 = A16.to(device), B16.to(device)
         out[m] = (A16.contiguous(), B16.contiguous(), a)
     return out
+
+
+def pack_conv_down(A: Tensor) -> Tensor:
+    """A convolution adapter's down matrix [r, Cin, kh, kw] in the packed weights' tap-major order [r, kh*kw*Cin]
+    (k = (ky*kw+kx)*Cin + ci, `engine.pack_conv3x3`); a linear's [r, K] as it is."""
+    return A if A.dim() == 2 else A.permute(0, 2, 3, 1).reshape(A.shape[0], -1).contiguous()
 
 
 def split_reference_ckpt(unet_trained: Dict[str, Tensor]) -> Tuple[Dict[str, Tensor], Dict[str, Tensor]]:
@@ -178,8 +259,9 @@ def _names(names) -> List[str]:
 class _MergePlan:
     """One launch plan of LORA_MERGE ops for an ordered adapter set, with its device tables."""
 
-    def __init__(self, plan, modules, seg, table, scale, blocks, ops):
+    def __init__(self, plan, modules, seg, table, scale, blocks, ops, folds=()):
         self.plan, self.modules, self.seg, self.table = plan, modules, seg, table
+        self.folds = list(folds)    # upsamplers whose packed 3x3 weight the plan rewrites (PackedUNet.refresh_derived)
         self.ops = ops              # the DsOp list (roofline accounting: ds_op_describe)
         self.scale = scale          # host fp32 [modules, adapters]: alpha / r where the adapter targets the module, else 0
         self.blocks = blocks        # {transformer block: parts of PackedUNet.ln_fused to re-derive}
@@ -197,7 +279,8 @@ class LoraState:
         self.plans: Dict[Tuple, _MergePlan] = {}
         self._perm: Dict[int, Tensor] = {}
         self.last_plan: Optional[_MergePlan] = None
-        self.order: List[str] = list(target_modules(cfg))
+        self.targets = all_target_modules(cfg)
+        self.order: List[str] = list(self.targets)
         self._stream = None          # side stream the merge plans are captured and replayed on
 
     # ---- bookkeeping
@@ -205,7 +288,8 @@ class LoraState:
         if name in self.adapters:
             raise ValueError(f"adapter {name!r} is already loaded; delete_adapters it first")
         sd = sd_or_path if isinstance(sd_or_path, dict) else read_lora_file(sd_or_path)
-        self.adapters[name] = parse_lora_state_dict(sd, alpha, self.cfg, device)
+        # held kernel-ready: a convolution's down matrix is permuted to the packed order once, here
+        self.adapters[name] = {m: (pack_conv_down(A), B, a) for m, (A, B, a) in parse_lora_state_dict(sd, alpha, self.cfg, device).items()}
 
     def invalidate(self) -> None:
         """The packed buffers (or the base tensors the plans read) are gone: the next `packed()` re-applies `active`."""
@@ -248,8 +332,17 @@ class LoraState:
         """out (a view of the packed buffer the module's rows live in), and where there is one the fused-LayerNorm copy out2
         with its gamma, the GEGLU row map, and (block, part) of what `refresh_derived` re-derives."""
         w = pk.w
+        shp = self.targets[m]
+        if len(shp) == 4 and shp[2] == 3:           # packed tap-major; an upsampler also has its folded phase weights
+            d = dict(out=w[m + ".weight"], conv_cin=shp[1])
+            if ".upsamplers." in m:
+                d["fold"] = m
+            return d
+        if m.endswith(".time_emb_proj"):
+            off = pk.temb_off[m[:-len(".time_emb_proj")]]
+            return dict(out=w["temb_all.weight"][off:off + shp[0]])
         leaf = next((lf for lf in BLOCK_LEAVES if m.endswith("." + lf)), None)
-        if leaf is None:
+        if leaf is None:                            # proj_in / proj_out, conv_shortcut (packed as a plain [Cout, Cin] matrix)
             return dict(out=w[m + ".weight"])
         t = m[:-len(leaf) - 1]
         has_ln = f"{t}.attn1.qk.weight_ln" in w
@@ -286,7 +379,7 @@ class LoraState:
         seg = torch.zeros(len(modules), n + 1, dtype=torch.int32, device=dev)
         table = torch.zeros(len(modules), max(n, 1), dtype=torch.float32, device=dev)
         keep: list = [seg, table]
-        op_list, blocks = [], {}
+        op_list, blocks, folds = [], {}, []
         for j, m in enumerate(modules):
             As, Bs, off = [], [], 0
             for i, name in enumerate(names):
@@ -298,17 +391,22 @@ class LoraState:
                 seg_host[j, i + 1] = off
             d = self._dest(pk, m)
             base = sd[m + ".weight"]
+            if base.dim() == 4:                     # checkpoint order; the kernel's convolution mode reads it as it lies
+                base = base.reshape(base.shape[0], -1)
             A = B = None
             if As:
                 A = As[0] if len(As) == 1 else torch.cat(As, 0).contiguous()
                 B = Bs[0] if len(Bs) == 1 else torch.cat(Bs, 1).contiguous()
             op_list.append(ops.lora_merge_op(base, d["out"], A, B, seg[j] if As else None, table[j] if As else None,
-                                             d.get("map"), d.get("colscale"), d.get("out2"), nseg=n if As else 0))
+                                             d.get("map"), d.get("colscale"), d.get("out2"), nseg=n if As else 0,
+                                             conv_cin=d.get("conv_cin", 0)))
             keep += [base, A, B, d["out"], d.get("out2"), d.get("colscale"), d.get("map")]
             if "block" in d:
                 blocks.setdefault(d["block"], set()).add(d["part"])
+            if "fold" in d:
+                folds.append(d["fold"])
         seg.copy_(seg_host)
-        return _MergePlan(Plan(op_list, [k for k in keep if k is not None]), modules, seg, table, scale, blocks, op_list)
+        return _MergePlan(Plan(op_list, [k for k in keep if k is not None]), modules, seg, table, scale, blocks, op_list, folds)
 
     def touched(self, names: Sequence[str]) -> set:
         return {m for n in names for m in self.adapters[n]}
@@ -356,7 +454,7 @@ class LoraState:
                 mp.plan.capture(self._stream.cuda_stream)
             mp.plan.replay(self._stream.cuda_stream)
         cur.wait_stream(self._stream)
-        pk.refresh_derived(mp.blocks)
+        pk.refresh_derived(mp.blocks, mp.folds)
         self.applied = self.touched(names)
         self.active = list(active)
         self.last_plan = mp

@@ -204,12 +204,16 @@ def conv3x3(x: Tensor, w: Tensor, bias: Optional[Tensor], stride: int = 1, upsam
     return y
 
 
-def fold_upsample2x(w: Tensor) -> Tensor:
+def fold_upsample2x(w: Tensor, out: Optional[Tensor] = None) -> Tensor:
     """w: [Cout,3,3,Cin] (= packed [Cout, 9*Cin]) -> [4, Cout, 4*Cin]: the four 2x2 phase weights of nearest x2 + conv3x3
-    (ds_fold_upsample2x_f16; torch model: `engine.fold_upsample2x_reference`)."""
-    _chk(w)
+    (ds_fold_upsample2x_f16; torch model: `engine.fold_upsample2x_reference`).  `out`: existing storage to fold into (after a
+    LoRA merge rewrote `w` in place)."""
+    _chk(w, out)
     Cout, Cin = w.shape[0], w.numel() // (9 * w.shape[0])
-    out = torch.empty((4, Cout, 4 * Cin), dtype=torch.float16, device=w.device)
+    if out is None:
+        out = torch.empty((4, Cout, 4 * Cin), dtype=torch.float16, device=w.device)
+    elif tuple(out.shape) != (4, Cout, 4 * Cin):
+        raise ValueError(f"fold_upsample2x: out must be [4, {Cout}, {4 * Cin}]")
     check(_lib.load().ds_fold_upsample2x_f16(_p(w), _p(out), Cout, Cin, _stream()), "ds_fold_upsample2x_f16")
     return out
 
@@ -485,6 +489,16 @@ def cfg_sampler_step_noise(eps: Tensor, latents: Tensor, model_in: Tensor, table
     check(_lib.load().ds_cfg_sampler_step_noise_f16(_p(eps), _p(latents), _p(model_in), _p(table), _p(seeds), _p(ctr),
                                                     ns, HW, kind, int(do_cfg), _stream()),
           "ds_cfg_sampler_step_noise_f16")
+
+
+def cfg_lcm_step(eps: Tensor, latents: Tensor, model_in: Tensor, table: Tensor, solver: Optional[Tensor],
+                 seeds: Optional[Tensor], do_cfg: bool = True, ctr: Optional[Tensor] = None,
+                 guidance: Optional[Tensor] = None) -> None:
+    """LCM step (kind 4): `cfg_sampler_step_noise` plus the solver rows fp32 [n,8] = {sqrt(a_prev), sqrt(1-a_prev), 0...} that
+    carry the row's fifth and sixth scalar (include/diffsensei_hip.h).  It goes through the per-panel entry point, the one
+    that takes table, solver rows and seeds together; `guidance` None keeps column 7 of the table."""
+    ns, HW = _sampler_step_dims(eps, latents, model_in, table, solver=solver, seeds=seeds, guidance=guidance)
+    _step_panels(eps, latents, model_in, table, guidance, solver, None, seeds, ctr, ns, HW, 4, do_cfg)
 
 
 # ---- region redraw: the packed buffer of include/diffsensei_hip.h ("Region redraw") and the two launches that read it
@@ -1290,8 +1304,13 @@ def _chk_rows(t: Optional[Tensor], what: str) -> None:
 
 def lora_merge_op(W: Tensor, out: Tensor, A: Optional[Tensor] = None, B: Optional[Tensor] = None,
                   seg: Optional[Tensor] = None, s: Optional[Tensor] = None, map: Optional[Tensor] = None,
-                  colscale: Optional[Tensor] = None, out2: Optional[Tensor] = None, nseg: Optional[int] = None) -> _lib.DsOp:
+                  colscale: Optional[Tensor] = None, out2: Optional[Tensor] = None, nseg: Optional[int] = None,
+                  conv_cin: int = 0) -> _lib.DsOp:
     """The DS_OP_LORA_MERGE plan op of `lora_merge` (same operands; `seg` / `s` / `map` are device tensors here)."""
+    if W.dim() == 4:
+        if conv_cin != W.shape[1] or tuple(W.shape[2:]) != (3, 3) or not W.is_contiguous():
+            raise ValueError("lora_merge: a 4-D base is a contiguous [Cout, Cin, 3, 3] weight merged with conv_cin = Cin")
+        W = W.reshape(W.shape[0], -1)
     _chk_rows(W, "W"), _chk_rows(out, "out"), _chk_rows(A, "A"), _chk_rows(B, "B"), _chk_rows(out2, "out2")
     _chk(seg, map, dtype=torch.int32)
     _chk(s, dtype=torch.float32)
@@ -1310,9 +1329,11 @@ def lora_merge_op(W: Tensor, out: Tensor, A: Optional[Tensor] = None, B: Optiona
         raise ValueError(f"lora_merge: map must be int32 [{N}]")
     if (colscale is None) != (out2 is None) or (colscale is not None and colscale.numel() != K):
         raise ValueError(f"lora_merge: out2 comes with colscale fp16 [{K}]")
+    if conv_cin and (conv_cin <= 0 or K != 9 * conv_cin or W.stride(0) != K):
+        raise ValueError(f"lora_merge: convolution mode reads a contiguous [N, Cin, 3, 3] base as [N, 9 * Cin]; got K {K}, Cin {conv_cin}")
     op = _lib.DsOp()
     op.code = _lib.OP["LORA_MERGE"]
-    for k, v in enumerate((N, K, R, n)):
+    for k, v in enumerate((N, K, R, n, conv_cin)):
         op.i[k] = int(v)
     ld = lambda t: 0 if t is None else int(t.stride(0))
     for k, v in enumerate((ld(W), ld(out), ld(A), ld(B), ld(out2))):
@@ -1324,12 +1345,16 @@ def lora_merge_op(W: Tensor, out: Tensor, A: Optional[Tensor] = None, B: Optiona
 
 def lora_merge(W: Tensor, A: Optional[Tensor] = None, B: Optional[Tensor] = None, seg=None, s=None,
                out: Optional[Tensor] = None, map: Optional[Tensor] = None, colscale: Optional[Tensor] = None,
-               out2: Optional[Tensor] = None) -> Tensor:
+               out2: Optional[Tensor] = None, conv_cin: int = 0) -> Tensor:
     """out[n] = f16(f32(W[map[n]]) + sum_i s[i] * B[map[n], seg[i]:seg[i+1]] @ A[seg[i]:seg[i+1]]) (lora_merge_kernel through
     DS_OP_LORA_MERGE; there is no exported entry point).  W [N,K] is the base weight and is never written: `out` must be
-    another buffer.  A [R,K] / B [N,R]: up to 8 adapters concatenated along the rank; `seg` (n + 1 offsets) and `s` (n
+    another buffer.  conv_cin = Cin > 0 is the convolution mode: W is a 3x3 weight in checkpoint order ([N, Cin, 3, 3], or its
+    [N, 9 * Cin] view), A [R, 9 * Cin] and `out` are in the packed tap-major order k = (ky * 3 + kx) * Cin + ci
+    (`engine.pack_conv3x3`), so no adapter gives `out` the bits of pack_conv3x3(W).  A [R,K] / B [N,R]: up to 8 adapters concatenated along the rank; `seg` (n + 1 offsets) and `s` (n
     strengths) may be sequences or device tensors; none: `out` gets the bits of W.  `out` / `out2` may be row or column slices of
     larger buffers.  out2 = f16(f32(out) * f32(colscale)), the fused-LayerNorm copy (`engine.pack_ln_fused`'s gw)."""
+    if W.dim() == 4 and W.is_contiguous():
+        W = W.reshape(W.shape[0], -1)
     _chk_rows(W, "W")
     dev = W.device
     if seg is not None and not torch.is_tensor(seg):
@@ -1340,7 +1365,7 @@ def lora_merge(W: Tensor, A: Optional[Tensor] = None, B: Optional[Tensor] = None
         seg = s = None
     if out is None:
         out = torch.empty((W.shape[0], W.shape[1]), dtype=torch.float16, device=dev)
-    op = lora_merge_op(W, out, A, B, seg, s, map, colscale, out2)
+    op = lora_merge_op(W, out, A, B, seg, s, map, colscale, out2, conv_cin=conv_cin)
     import ctypes
     check(_lib.load().ds_op_run(ctypes.byref(op), _stream()), "ds_op_run(LORA_MERGE)")
     return out

@@ -469,7 +469,7 @@ class DiffSenseiPipeline:
         plan can hand out per step, so other `callback_on_step_end_tensor_inputs` are refused like diffusers refuses unknown
         names.
 
-        `noise_seeds` (stochastic samplers only, i.e. `EulerAncestralDiscreteScheduler`): `num_samples` non-negative
+        `noise_seeds` (stochastic samplers only: `EulerAncestralDiscreteScheduler`, `LCMScheduler`): `num_samples` non-negative
         int64 seeds, one per panel, that the step kernel draws its noise from; by default they are drawn from `generator`
         after the initial latents (`schedulers.draw_noise_seeds`).  The seeds used are in `last_run_info["noise_seeds"]`.
 

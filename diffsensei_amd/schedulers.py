@@ -14,8 +14,9 @@ the training sigmas and their interpolation, the timestep -> row lookup and the 
 (DPM-Solver++ adds `solver_table`); tests/golden/scheduler_tables.npz pins every table and every refusal
 (tools/dump_scheduler_tables.py).
 
-`EulerAncestralDiscreteScheduler` is the one stochastic sampler: its per-step noise is drawn inside the step kernel
-from one int64 seed per panel, `draw_noise_seeds`.
+`EulerAncestralDiscreteScheduler` and `LCMScheduler` are the stochastic samplers: their per-step noise is drawn inside the
+step kernel from one int64 seed per panel, `draw_noise_seeds`.  `LCMScheduler` is the few-step consistency sampler; its
+tables are pinned by tests/golden/lcm_tables.npz (tools/dump_lcm_tables.py), not by the matrix above.
 """
 from __future__ import annotations
 
@@ -27,7 +28,9 @@ import torch
 
 from . import ops
 
-KIND_EULER, KIND_DDIM, KIND_DPM, KIND_EULER_ANCESTRAL = 0, 1, 2, 3
+KIND_EULER, KIND_DDIM, KIND_DPM, KIND_EULER_ANCESTRAL, KIND_LCM = 0, 1, 2, 3, 4
+SOLVER_KINDS = (KIND_DPM, KIND_LCM)                 # read a second per-step table, the solver rows
+NOISE_KINDS = (KIND_EULER_ANCESTRAL, KIND_LCM)      # draw Philox noise inside the step kernel: one seed per panel
 
 
 class _Config(dict):
@@ -193,8 +196,8 @@ class _Scheduler:
         return ops.nhwc_to_nchw(tmp).reshape(ns, c, h, w)
 
     def _step_extras(self, i: int, lat: torch.Tensor, generator) -> dict:
-        """What row i of this sampler reads besides the table: `solver` + `prev_x0` (DPM-Solver++) or `seeds`
-        (Euler Ancestral), on `lat`'s device.  Both tables are indexed with the step counter, here i."""
+        """What row i of this sampler reads besides the table: `solver` + `prev_x0` (DPM-Solver++), `seeds`
+        (Euler Ancestral) or `solver` + `seeds` (LCM), on `lat`'s device.  Both tables are indexed with the step counter, here i."""
         return {}
 
     def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, *, generator=None,
@@ -223,7 +226,9 @@ def _is_real(v) -> bool:
 
 def _launch_step(eps, lat, scratch, table, kind, ctr, solver=None, prev_x0=None, seeds=None):
     """One `sampler_step_kernel` launch through the C entry point that carries the given extras."""
-    if solver is not None:
+    if solver is not None and seeds is not None:
+        ops.cfg_lcm_step(eps, lat, scratch, table, solver, seeds, do_cfg=False, ctr=ctr)
+    elif solver is not None:
         ops.cfg_dpm_step(eps, lat, scratch, table, solver, prev_x0, do_cfg=False, ctr=ctr)
     elif seeds is not None:
         ops.cfg_sampler_step_noise(eps, lat, scratch, table, seeds, kind, do_cfg=False, ctr=ctr)
@@ -517,9 +522,118 @@ class EulerAncestralDiscreteScheduler(_Scheduler):
         return None if self._seeds is None else list(self._seeds)
 
 
+class LCMScheduler(_Scheduler):
+    """diffusers LCMScheduler [3P], epsilon prediction: the consistency sampler a latent-consistency distillation (an LCM
+    adapter merged into the UNet, or a distilled UNet) is run with, in 1 - 8 steps.  Per step: x0 from the prediction, the
+    boundary condition denoised = c_out * x0 + c_skip * x, then the denoised value re-noised to the NEXT timestep,
+    sqrt(a_prev) * denoised + sqrt(1 - a_prev) * z; the last step returns the denoised value itself.
+
+    The timesteps are a subset of the `original_inference_steps` grid the distillation was trained on (`set_timesteps`),
+    not of this project's other grids; `timestep_spacing`, `steps_offset` and `set_alpha_to_one` are kept in the config and
+    never reach the arithmetic, as in diffusers.  Per step the engine reads the table row {t, 1, sqrt(a_t), sqrt(1 - a_t),
+    c_out, c_skip, 1, guidance} (init_noise_sigma = 1, the model input is unscaled) plus one solver row {sqrt(a_prev),
+    sqrt(1 - a_prev), 0, ...}, which is {1, 0} on the last row (include/diffsensei_hip.h).  The noise z is Euler Ancestral's
+    source unchanged: Philox stream 0, one int64 seed per panel, indexed by the device step counter.  Scalars are 0-dim
+    fp32 torch values computed in diffusers' order.
+
+    Region redraw and strength runs truncate the n-step grid with this project's own `start_index` rule (skip the first
+    n - int(n * strength) rows).  That is NOT diffusers' LCM img2img rule, which re-derives the grid from
+    original_inference_steps * strength."""
+    kind = KIND_LCM
+    stochastic = True
+    init_noise_sigma = 1.0
+    SIGMA_DATA = 0.5
+    _DEFAULTS = dict(num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
+                     trained_betas=None, original_inference_steps=50, clip_sample=False, clip_sample_range=1.0,
+                     set_alpha_to_one=True, steps_offset=0, prediction_type="epsilon", thresholding=False,
+                     dynamic_thresholding_ratio=0.995, sample_max_value=1.0, timestep_spacing="leading", timestep_scaling=10.0,
+                     rescale_betas_zero_snr=False)
+    _SUPPORTED = {"beta_schedule": ("scaled_linear",), "prediction_type": ("epsilon",), "clip_sample": (False,),
+                  "thresholding": (False,), "rescale_betas_zero_snr": (False,), "trained_betas": (None,)}
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        orig = self.config.original_inference_steps
+        if not _is_real(orig) or int(orig) != orig or not 1 <= int(orig) <= self.T:
+            raise ValueError(f"original_inference_steps={orig!r} must be an integer in 1..{self.T}")
+        if not _is_real(self.config.timestep_scaling):
+            raise ValueError(f"timestep_scaling={self.config.timestep_scaling!r} must be a number")
+        self._seeds = None
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        """diffusers `set_timesteps` (no `timesteps=` / `strength=`): the training grid of the distillation is
+        origin = (1 .. original_inference_steps) * k - 1 with k = T // original_inference_steps, descending, and the run
+        takes the n entries at floor(linspace(0, len(origin), n, endpoint=False))."""
+        n, orig = int(num_inference_steps), int(self.config.original_inference_steps)
+        if n < 1:
+            raise ValueError(f"num_inference_steps={num_inference_steps!r} must be at least 1")
+        if n > self.T:
+            raise ValueError(f"num_inference_steps={n} cannot exceed num_train_timesteps={self.T}")
+        if n > orig:
+            raise ValueError(f"num_inference_steps={n} cannot exceed original_inference_steps={orig}: the distillation "
+                             f"knows no finer grid")
+        k = self.T // orig
+        origin = (np.arange(1, orig + 1) * k - 1)[::-1].copy()
+        idx = np.floor(np.linspace(0, len(origin), num=n, endpoint=False)).astype(np.int64)
+        self._set_grid(origin[idx].astype(np.int64), device)
+        self._seeds = None      # the stand-alone `step` draws new seeds for a new run
+
+    def _alpha_pairs(self):
+        """(sqrt(a_t), sqrt(1 - a_t)) of every row, 0-dim fp32 tensors."""
+        return [(self.alphas_cumprod[int(t)].sqrt(), (1 - self.alphas_cumprod[int(t)]).sqrt()) for t in self.timesteps_np]
+
+    def boundary_scalings(self, t: int):
+        """(c_skip, c_out) of diffusers' `get_scalings_for_boundary_condition_discrete`, 0-dim fp32 tensors."""
+        s = torch.tensor(int(t)) * float(self.config.timestep_scaling)
+        c_skip = self.SIGMA_DATA ** 2 / (s ** 2 + self.SIGMA_DATA ** 2)
+        c_out = s / (s ** 2 + self.SIGMA_DATA ** 2) ** 0.5
+        return c_skip, c_out
+
+    def coef_table(self, guidance_scale: float) -> np.ndarray:
+        tab = self._coef_frame(guidance_scale)
+        for i, (sa, sb) in enumerate(self._alpha_pairs()):
+            c_skip, c_out = self.boundary_scalings(self.timesteps_np[i])
+            tab[i, 2:6] = [float(sa), float(sb), float(c_out), float(c_skip)]
+        return tab
+
+    def solver_table(self, start: int = 0) -> np.ndarray:
+        """fp32 [n_steps - start, 8] rows {sqrt(a_prev), sqrt(1 - a_prev), 0 x 6}: the noise level of the NEXT row's
+        timestep, which the step re-noises its denoised value to; the last row is {1, 0} - the denoised value, no noise."""
+        if self.num_inference_steps is None:
+            raise RuntimeError("call set_timesteps first")
+        n = self.num_inference_steps
+        if not 0 <= int(start) < n:
+            raise ValueError(f"solver_table: start {start} outside the {n} steps")
+        rows = np.zeros((n, 8), dtype=np.float32)
+        pairs = self._alpha_pairs()
+        for i in range(n - 1):
+            rows[i, 0], rows[i, 1] = float(pairs[i + 1][0]), float(pairs[i + 1][1])
+        rows[n - 1, 0] = 1.0
+        return rows[int(start):]
+
+    def renoise_table(self) -> np.ndarray:
+        pairs = self._alpha_pairs()                                             # diffusers `add_noise` [3P]
+        return self._renoise_rows([float(a) for a, _ in pairs], [float(b) for _, b in pairs])
+
+    # -- stand-alone protocol
+    def scale_model_input(self, sample: torch.Tensor, timestep=None) -> torch.Tensor:
+        return sample
+
+    def _step_extras(self, i: int, lat: torch.Tensor, generator) -> dict:
+        if self._seeds is None or len(self._seeds) != lat.shape[0]:
+            self._seeds = draw_noise_seeds(lat.shape[0], generator)
+        return dict(solver=torch.from_numpy(self.solver_table()).to(lat.device),
+                    seeds=torch.tensor(self._seeds, dtype=torch.int64, device=lat.device))
+
+    @property
+    def noise_seeds(self):
+        """The seeds of the current stand-alone run (None before its first `step`)."""
+        return None if self._seeds is None else list(self._seeds)
+
+
 # scheduler_config.json `_class_name` -> class
 SCHEDULERS = {c.__name__: c for c in (EulerDiscreteScheduler, DDIMScheduler, DPMSolverMultistepScheduler,
-                                      EulerAncestralDiscreteScheduler)}
+                                      EulerAncestralDiscreteScheduler, LCMScheduler)}
 
 
 def _sigma_to_t(sigmas: np.ndarray, log_sigmas: np.ndarray) -> np.ndarray:

@@ -377,10 +377,20 @@ int ds_cfg_sampler_step_noise_f16(const void* eps, void* latents, void* model_in
                                   const int64_t* seeds, const int32_t* step_ctr, int ns, int HW, int kind, int do_cfg,
                                   void* stream);
 /* The sampler step with one guidance scale per panel, for every kind (0 Euler, 1 DDIM, 2 DPM-Solver++, 3 Euler
- * Ancestral): the superset of the three calls above.  guidance: device fp32 [ns]; panel n - eps rows n (negative) and
+ * Ancestral, 4 LCM): the superset of the three calls above.  guidance: device fp32 [ns]; panel n - eps rows n (negative) and
  * ns + n (conditional), latents / prev_x0 / seeds element n - uses guidance[n] where the calls above use column 7 of the
  * table row:  gd = fp16(guidance[n] * fp16(ec - eu)),  e = fp16(eu + gd).  NULL = column 7, i.e. exactly the calls above.
- * Not read when do_cfg = 0.  solver / prev_x0: kind 2 only, seeds: kind 3 only (NULL otherwise). */
+ * Not read when do_cfg = 0.  solver: kinds 2 and 4, prev_x0: kind 2, seeds: kinds 3 and 4 (NULL otherwise).
+ * kind 4 = LCM (diffusers LCMScheduler, epsilon prediction), the few-step consistency sampler.  Six scalars per step: four
+ * in the table row, two in the solver row of the same step_ctr -
+ *   table  {t, 1, sqrt(a_t), sqrt(1 - a_t), c_out, c_skip, 1, guidance}     solver  {sqrt(a_prev), sqrt(1 - a_prev), 0 x 6}
+ *   with s = t * timestep_scaling, c_skip = 0.25 / (s^2 + 0.25), c_out = s / sqrt(s^2 + 0.25), a = alphas_cumprod, prev = the
+ *   NEXT row's timestep; the last row's solver pair is {1, 0}
+ *   x0 = (x - sqrt(1 - a_t) * eps) / sqrt(a_t);  d = c_out * x0 + c_skip * x                                (fp32, x upcast)
+ *   x' = fp16( sqrt(a_prev) * d + fp16(sqrt(1 - a_prev) * fp16(z)) ),  z = the normals of kind 3: same stream, same counter
+ * so the last row stores the denoised value d itself, without noise.  The model input is the latent (c_in_div = 1).  kind 4
+ * needs `solver` AND `seeds`: this call, the redraw call and the slots call carry both; ds_cfg_sampler_step_f16,
+ * ds_cfg_dpm_step_f16 and ds_cfg_sampler_step_noise_f16 cannot and refuse it. */
 int ds_cfg_sampler_step_panels_f16(const void* eps, void* latents, void* model_in, const float* table,
                                    const float* guidance, const float* solver, void* prev_x0, const int64_t* seeds,
                                    const int32_t* step_ctr, int ns, int HW, int kind, int do_cfg, void* stream);
@@ -396,7 +406,7 @@ int ds_cfg_sampler_step_panels_f16(const void* eps, void* latents, void* model_i
  *   rows   fp32 [1025][2]        the renoise table, row r = {ka, kb} of STATE r                  at byte F + 16
  * Renoise table: state r is what enters step r of the run (r = 0: the start) and state n_run is the result; a kept
  * latent at the noise level of state r is ka * x0k + kb * noise:
- *   Euler, Euler Ancestral  {1, sigma_r}                     DDIM  {sqrt(a_r), sqrt(1 - a_r)}
+ *   Euler, Euler Ancestral  {1, sigma_r}                     DDIM, LCM  {sqrt(a_r), sqrt(1 - a_r)}
  *   DPM-Solver++            {alpha_r, sigma_r * alpha_r}, alpha = 1 / sqrt(sigma^2 + 1)      final state, every kind  {1, 0}
  * The table does not depend on `kind` inside the kernel.  A run that starts mid-schedule (strength < 1) loads the rows
  * of its own states: row 0 is its start state, and step_ctr counts from 0 (kind 3 therefore draws its Philox noise for
@@ -428,7 +438,7 @@ int ds_prepare_model_input_f16(const void* latents, void* model_in, const float*
  *   mode     fp32 [ns][4]        {start mode, init_noise_sigma, 0, 0}; start mode 0 = renoise row 0,       at byte F
  *                                1 = full strength (noise * init_noise_sigma), 2 = keep the latents (a plain panel)
  *   coef     fp32 [ns][R][8]     the panel's rows of the per-step scalar table (column 7 is not read)      at byte F + 16*ns
- *   solver   fp32 [ns][R][8]     its DPM-Solver++ rows (kind 2)                                            at byte F + 16*ns + 32*R*ns
+ *   solver   fp32 [ns][R][8]     its DPM-Solver++ or LCM rows (kinds 2, 4)                                 at byte F + 16*ns + 32*R*ns
  *   renoise  fp32 [ns][R+1][2]   its renoise rows {ka, kb}, state r of ITS run (region redraw)             at byte F + 16*ns + 64*R*ns
  * With s = *step_ctr panel n is at its row j = s - start[n]; it is active iff 0 <= j < steps[n] (steps above R count as R).
  * ds_panel_slot_load writes one slot from DEVICE rows - coef_rows [steps][8], solver_rows [steps][8] (NULL: kept),
@@ -440,7 +450,7 @@ int ds_panel_slot_load(void* panel, int ns, int slot, int start, int steps, cons
                        const float* renoise_rows, int start_mode, float init_noise_sigma, void* stream);
 /* ds_cfg_sampler_step_redraw_f16 on panel schedules: panel n takes row j of its own coefficient / solver / renoise rows
  * where that call takes row *step_ctr of the shared tables; guidance is always the per-panel vector (needed when do_cfg);
- * kind 3 draws its Philox noise for step j, so a panel's noise depends on neither its slot nor when it was admitted.
+ * kinds 3 and 4 draw their Philox noise for step j, so a panel's noise depends on neither its slot nor when it was admitted.
  * An inactive panel (empty, not yet started, finished) has nothing stored: its latents, prev_x0 and both model_in rows keep
  * their bits.  `redraw` NULL: no blend (every panel plain); given: the x0k | noise | mask parts of the redraw buffer above
  * are read (its header and renoise rows are not), and a plain panel carries an all-ones mask.  step_ctr is required. */
@@ -647,10 +657,10 @@ enum ds_opcode {
                                   i[3] = ns > 0: panel schedules - p[0] is the panel-schedule buffer, row b reads panel b % ns
                                   (ds_timestep_embed_slots_f16) */
     DS_OP_ADD_TIME_IDS = 11, /* p: text_embeds, time_ids, out             i: B pooled n_ids dim flip  f: freq_shift */
-    DS_OP_SAMPLER_STEP = 12, /* p: eps, latents, model_in, table, ctr, prev_x0, solver (these two: kind 2 only),
-                                   seeds (kind 3 only), guidance (p[8]: fp32 [ns], one per panel; NULL = column 7 of the table)
+    DS_OP_SAMPLER_STEP = 12, /* p: eps, latents, model_in, table, ctr, prev_x0 (kind 2), solver (kinds 2 and 4),
+                                   seeds (kinds 3 and 4), guidance (p[8]: fp32 [ns], one per panel; NULL = column 7 of the table)
                                    p[9]: the region-redraw buffer (ds_cfg_sampler_step_redraw_f16), read when i[4] = 1
-                                i: ns HW kind (0 Euler, 1 DDIM, 2 DPM-Solver++, 3 Euler Ancestral) do_cfg redraw (i[4]: 0 | 1;
+                                i: ns HW kind (0 Euler, 1 DDIM, 2 DPM-Solver++, 3 Euler Ancestral, 4 LCM) do_cfg redraw (i[4]: 0 | 1;
                                    1 without p[9] fails the launch)
                                    i[5] = 1: panel schedules (ds_cfg_sampler_step_slots_f16) - p[3] is the panel-schedule buffer in
                                    the table's place, p[6] is not read (the solver rows live in the buffer), p[8] is required */
@@ -681,7 +691,10 @@ enum ds_opcode {
     DS_OP_REDRAW_START = 33,      /* p: redraw buffer, latents                  i: ns HW   (ds_redraw_start_f16) */
     DS_OP_LLM_GEMV_W8 = 34,       /* DS_OP_LLM_GEMV with int8 weights in p[1] and p[5] = w_scale (ds_llm_gemv_w8) */
     DS_OP_LLM_GEMM16_W8 = 35,     /* DS_OP_LLM_GEMM16 with int8 weights in p[1] and p[5] = w_scale (ds_llm_gemm16_w8) */
-    DS_OP_LORA_MERGE = 36,        /* p: W, out, A, B, seg, s, map, colscale, out2   l: ldw ldo lda ldb ldo2   i: N K R nseg
+    DS_OP_LORA_MERGE = 36,        /* p: W, out, A, B, seg, s, map, colscale, out2   l: ldw ldo lda ldb ldo2   i: N K R nseg cin
+                                     i[4] = cin > 0: convolution mode - W is a 3x3 weight in checkpoint order [N][cin][3][3] (contiguous,
+                                     ldw = K = 9 cin) while out and A are in the packed tap-major order k = (ky*3 + kx)*cin + ci, so
+                                     nseg = 0 gives the packed base; cin a multiple of 8.  cin = 0, a plain matrix:
                                      out[n,k] = f16(f32(W[map(n),k]) + sum_i s[i] * sum_{r in [seg[i], seg[i+1])} B[map(n),r] A[r,k]):
                                      W [N,K] f16 is the base weight, read only - the launch fails when it is out or out2; A [R,K]
                                      and B [N,R] f16 hold the adapters concatenated along the rank (any rank, any boundary; nseg <= 16, empty segments legal);
