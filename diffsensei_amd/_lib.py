@@ -79,6 +79,10 @@ SIGNATURES = {
                                     i32, f32, f32, vp, i64, i64, i64, vp]),
     "ds_masked_ip_attn_rows_f16": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32,
                                          i32, f32, vp, i64, i64, i64, vp]),
+    "ds_masked_ip_attn_long_f16": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32,
+                                         i32, i32, f32, f32, vp, i64, i64, i64, i64, i64, i64, vp]),
+    "ds_masked_ip_attn_long_rows_f16": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32,
+                                              i32, i32, f32, vp, i64, i64, i64, i64, i64, i64, vp]),
     "ds_ip_region_flags": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "ds_small_attn_f16": (i32, [vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, i32, f32,
                                 vp]),

@@ -130,7 +130,8 @@ class MaskedIPAttnProcessor2_0:
         n_ctx = self.num_ip_tokens + self.num_dummy_tokens
         end_pos = encoder_hidden_states.shape[1] - n_ctx
         enc = encoder_hidden_states.contiguous()
-        txt = ops.pad_rows(enc, 0, end_pos, LP)
+        # up to 96 text keys: one panel (ip_attn_kernel); a longer, chunked prompt: ceil(end_pos / 96) panels (ip_attn_long_kernel)
+        txt = ops.pad_rows(enc, 0, end_pos, LP * max(1, (end_pos + LP - 1) // LP))
         ip = ops.pad_rows(enc, end_pos, n_ctx, LP)
         q = attn.to_q(x)
         kt, ki = attn.to_k(txt), self.to_k_ip(ip)

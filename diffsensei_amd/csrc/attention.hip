@@ -7,6 +7,8 @@
 //                     (16 dummy + 4x16 character keys) + `text + scale*ip`.  The additive mask the reference
 //                     materialises as [B,heads,N,80] every layer of every step (:115-169, a Python double loop
 //                     with a host sync per box) is evaluated analytically per query row from the 4 boxes.
+//  ip_attn_long_kernel  the same core for prompts of more than one 77-token chunk: up to four 96-key text panels, online
+//                     softmax across them (1..384 text keys); the IP side is ip_attn_kernel's.
 //
 // CDNA4 mapping (both kernels): a wave owns 32 query rows.  Scores are computed TRANSPOSED,
 // S^T = K * Q^T with v_mfma_f32_32x32x16_f16, so lane (l&31) holds one query row's scores in registers:
@@ -745,6 +747,328 @@ __global__ __launch_bounds__(NW * 64, 2) void ip_attn_kernel(const IPAttnParams 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Long-prompt form of the fused cross-attention: the text side is T = ceil(Lt / 96) panels of 96 keys (T <= 4, Lt <= 384:
+// chunked prompts of 77 tokens each), the IP side is ip_attn_kernel's - one 96-key panel, the same region test, -10000 bias,
+// open_ip / act_ip and per-batch or per-row ip_scale, the same arithmetic in the same order.
+// All T + 1 panels of a (batch, head) stay RESIDENT in LDS, (T + 1) x 25088 bytes (50176 .. 125440): one block per CU.  The block
+// is eight waves (256 query rows per tile), so a SIMD holds two waves as it does under ip_attn_kernel's two four-wave blocks,
+// and the staging of the larger panels is shared by twice the query rows.  (The alternative - text panels streamed through a
+// double buffer, two blocks per CU - needs a block-wide barrier per panel and query tile; not built, not measured.)
+// Text softmax: online over the panels.  Per panel the scores of up to 96 keys sit in registers as in ip_attn_kernel; the
+// running maximum m and the lane's partial sum l carry over, and O^T (fp32) is rescaled by exp(m_old - m_new) before a panel's
+// P V MFMAs.  Rounding points: fp32 scores, exp(s - m_run) packed to fp16 for the MFMA, fp32 accumulation, ONE division by
+// the fp32 row sum after the last panel (ip_attn_kernel normalises before packing; the flash kernel above after, as here).
+// Keys >= Lt: their score is replaced by NEG_BIG, exp2 of it is exactly 0, so whatever finite values their panel rows
+// hold never reaches the output; a 16-key half block wholly past Lt issues no P V MFMA (block-uniform; its scores are computed).
+// ------------------------------------------------------------------------------------------------
+constexpr int IPL_KPANEL = LP * 128;     // bytes of one K panel in LDS
+constexpr int IPL_VPANEL = 64 * VSTR;    // bytes of one V^T panel in LDS
+template <int NW>
+__global__ __launch_bounds__(NW * 64, 2) void ip_attn_long_kernel(const IPAttnLongParams pl, int qt) {
+    extern __shared__ __attribute__((aligned(16))) char ipl_smem[];   // ONE LDS object: K panels 0..T (T = the IP panel) | V^T panels 0..T
+    const IPAttnParams& p = pl.a;
+    const int T = pl.T;
+    char* const sK = ipl_smem;
+    char* const sV = ipl_smem + (T + 1) * IPL_KPANEL;
+    constexpr int ROWS = NW * 32;   // query rows per block and tile
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l31 = lane & 31, lhi = lane >> 5;
+    const int b = blockIdx.y / p.heads, h = blockIdx.y % p.heads;
+
+    h8 qn[4];
+    auto load_q = [&](int it) {
+        const int qrow = min((int)(blockIdx.x * qt + it) * ROWS + wave * 32 + l31, p.N - 1);
+        const half_t* qp = p.q + ((long)b * p.N + qrow) * p.ldq + h * 64 + lhi * 8;
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) qn[kk] = *reinterpret_cast<const h8*>(qp + kk * 16);
+    };
+    load_q(0);
+    float bv[4] = {2.f, 2.f, -1.f, -1.f};
+    {
+        const float* bbox_b = p.bbox + (long)b * p.max_ips * 4;
+        if (lane < p.max_ips) {
+#pragma unroll
+            for (int c4 = 0; c4 < 4; ++c4) bv[c4] = bbox_b[4 * lane + c4];
+        }
+    }
+    // ---- stage the T + 1 panels once: 768 sixteen-byte pieces of K and of V^T per panel, whole panels (rows >= Lt included:
+    // the caller's panels are [B, 96 T, C] / [B, C, 96 T], so every piece lies inside them)
+    for (int j = 0; j <= T; ++j) {
+        const bool ipp = j == T;
+        const half_t* kp = ipp ? p.ki + (long)b * p.sk + h * 64 : p.kt + (long)b * pl.skt + (long)(j * LP) * pl.ldkt + h * 64;
+        const long ldk = ipp ? p.ldk : pl.ldkt;
+        const long ldv = ipp ? LP : (long)LP * T;
+        const half_t* vp = ipp ? p.vti + (long)b * p.sv + (long)(h * 64) * ldv : p.vtt + (long)b * pl.svt + (long)(h * 64) * ldv + j * LP;
+        char* const dK = sK + j * IPL_KPANEL;
+        char* const dV = sV + j * IPL_VPANEL;
+        constexpr int ITER = (LP * 8 + NW * 64 - 1) / (NW * 64);
+        h8 rk[ITER], rv[ITER];
+#pragma unroll
+        for (int i = 0; i < ITER; ++i) {
+            const int id = min(tid + i * NW * 64, LP * 8 - 1);
+            const int row = id >> 3, c = id & 7;
+            rk[i] = *reinterpret_cast<const h8*>(kp + (long)row * ldk + c * 8);
+            const int vrow = id / 12, vc = id - vrow * 12;
+            rv[i] = *reinterpret_cast<const h8*>(vp + (long)vrow * ldv + vc * 8);
+        }
+#pragma unroll
+        for (int i = 0; i < ITER; ++i) {
+            const int id = tid + i * NW * 64;
+            if (id >= LP * 8) continue;
+            const int row = id >> 3, c = id & 7;
+            *reinterpret_cast<h8*>(&dK[row * 128 + swz(row, c)]) = rk[i];
+            const int vrow = id / 12, vc = id - vrow * 12;
+            const h8 a = rv[i];
+            h4 lo, hi;
+            lo[0] = a[0]; lo[1] = a[1]; lo[2] = a[2]; lo[3] = a[3];
+            hi[0] = a[4]; hi[1] = a[5]; hi[2] = a[6]; hi[3] = a[7];
+            *reinterpret_cast<h4*>(&dV[vrow * VSTR + vc * 16]) = lo;
+            *reinterpret_cast<h4*>(&dV[vrow * VSTR + vc * 16 + 8]) = hi;
+        }
+    }
+    __syncthreads();   // the only barrier: behind it every wave walks its own query rows
+
+    float box[8][4];
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+#pragma unroll
+        for (int c4 = 0; c4 < 4; ++c4) box[k][c4] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bv[c4]), k));
+    const float ip_scale = p.ip_scale_ptr ? p.ip_scale_ptr[b * p.ip_scale_rows] : p.ip_scale;
+
+    // Fragment addresses relative to a panel: K row 32 kb + l31 keeps the swizzle of row l31 ((row >> 1) & 7 has period 16), so a
+    // key block is an immediate offset; V^T row 32 db + l31, keys from 4 lhi on, the half block an immediate as well
+    int koff[4];
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) koff[kk] = l31 * 128 + swz(l31, kk * 2 + lhi);
+    const int voff = l31 * VSTR + 8 * lhi;
+    // S^T block kb of the panel at sKp: four MFMAs from zero, kk ascending (ip_attn_kernel's order)
+    h8 qf[4];
+    auto score_block = [&](const char* sKp, int kb) {
+        f32x16 s;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[r] = 0.f;
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            const h8 kf = *reinterpret_cast<const h8*>(sKp + kb * (32 * 128) + koff[kk]);
+            s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[kk], s, 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);   // one block's fragments at a time: hoisted together they spill
+        return s;
+    };
+    // O^T += V^T P^T for 16 keys: half block hb of key block kb of the panel at sVp
+    f32x16 ot[2];
+    auto pv_half = [&](const char* sVp, const f32x16& st, int kb, int hb) {
+        const h8 pf = pack8(st, hb * 8);
+#pragma unroll
+        for (int db = 0; db < 2; ++db) {
+            const int off = db * (32 * VSTR) + (kb * 32 + hb * 16) * 2;  // immediate: V^T row block + the half block's first key
+            const h4 v0 = *reinterpret_cast<const h4*>(sVp + voff + off);
+            const h4 v1 = *reinterpret_cast<const h4*>(sVp + voff + off + 16);
+            h8 v;
+            v[0] = v0[0]; v[1] = v0[1]; v[2] = v0[2]; v[3] = v0[3];
+            v[4] = v1[0]; v[5] = v1[1]; v[6] = v1[2]; v[7] = v1[3];
+            ot[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(v, pf, ot[db], 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+
+    for (int it = 0; it < qt; ++it) {
+        const int q0 = (blockIdx.x * qt + it) * ROWS + wave * 32;
+        if (q0 >= p.N) break;     // wave-uniform; no barrier below
+        const int qidx = min(q0 + l31, p.N - 1);
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) qf[kk] = qn[kk];
+        if (it + 1 < qt) load_q(it + 1);   // (row index clamped to N - 1)
+#pragma unroll
+        for (int d = 0; d < 2; ++d)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) ot[d][r] = 0.f;
+
+        // ---- text: online softmax over the T panels
+        float m_run = NEG_BIG, l_part = 0.f;
+#pragma unroll 1
+        for (int t = 0; t < T; ++t) {
+            const char* sKp = sK + t * IPL_KPANEL;
+            const char* sVp = sV + t * IPL_VPANEL;
+            const int Lrem = p.Lt - t * LP;   // >= 1: T = ceil(Lt / 96)
+            f32x16 st[3];
+#pragma unroll
+            for (int kb = 0; kb < 3; ++kb) st[kb] = score_block(sKp, kb);   // (unconditional: a block defined under a branch costs registers)
+            float mloc = NEG_BIG;
+            if (Lrem < LP) {   // block-uniform: only the last panel holds keys >= Lt
+                const int lim = Lrem - 4 * lhi;   // register r of block kb is key 32 kb + (r & 3) + 8 (r >> 2) + 4 lhi
+#pragma unroll
+                for (int kb = 0; kb < 3; ++kb)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float sv = kb * 32 + (r & 3) + 8 * (r >> 2) >= lim ? NEG_BIG : st[kb][r] * p.qk_scale;
+                        st[kb][r] = sv;
+                        mloc = fmaxf(mloc, sv);
+                    }
+            } else {
+#pragma unroll
+                for (int kb = 0; kb < 3; ++kb)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float sv = st[kb][r] * p.qk_scale;
+                        st[kb][r] = sv;
+                        mloc = fmaxf(mloc, sv);
+                    }
+            }
+            mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
+            const float m_new = fmaxf(m_run, mloc);    // finite from the first panel on: every panel has a key < Lt
+            const float alpha = fast_exp2((m_run - m_new) * LOG2E);   // first panel: exp2(-huge) = 0 on O = 0, l = 0
+            m_run = m_new;
+            f32x2 psum2 = {0.f, 0.f};
+            const f32x2 l2 = {LOG2E, LOG2E}, m2 = {-m_new * LOG2E, -m_new * LOG2E};
+#pragma unroll
+            for (int kb = 0; kb < 3; ++kb) {
+#pragma unroll
+                for (int r = 0; r < 16; r += 2) {
+                    f32x2 v = {st[kb][r], st[kb][r + 1]};
+                    v = __builtin_elementwise_fma(v, l2, m2);
+                    const f32x2 e = {fast_exp2(v[0]), fast_exp2(v[1])};
+                    st[kb][r] = e[0];
+                    st[kb][r + 1] = e[1];
+                    psum2 += e;
+                }
+            }
+            l_part = fmaf(l_part, alpha, psum2[0] + psum2[1]);
+            if (t > 0) {
+#pragma unroll
+                for (int d = 0; d < 2; ++d)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) ot[d][r] *= alpha;
+            }
+#pragma unroll
+            for (int kb = 0; kb < 3; ++kb)
+#pragma unroll
+                for (int hb = 0; hb < 2; ++hb)
+                    if (kb * 32 + hb * 16 < Lrem) pv_half(sVp, st[kb], kb, hb);
+        }
+        {
+            const float l = l_part + __shfl_xor(l_part, 32, 64);
+            const float inv = 1.0f / l;
+#pragma unroll
+            for (int d = 0; d < 2; ++d)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) ot[d][r] *= inv;
+        }
+
+        // ---- IP: ip_attn_kernel's part 1 (region test, 96-bit open set, active blocks, biased softmax weighted by ip_scale)
+        unsigned inside = 0;
+        {
+            const int yi = qidx / p.mask_w, xi = qidx - yi * p.mask_w;
+            const float x = linspace01(xi, p.mask_w, p.step_x), y = linspace01(yi, p.mask_h, p.step_y);
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                inside |= (unsigned)((x >= box[k][0]) & (x <= box[k][2]) & (y >= box[k][1]) & (y <= box[k][3])) << k;
+        }
+        unsigned open_ip[3] = {0u, 0u, 0u};
+        {
+            auto set_range = [&](int lo, int hi) {
+#pragma unroll
+                for (int w = 0; w < 3; ++w) {
+                    const int a = max(lo - 32 * w, 0), e = min(hi - 32 * w, 32);
+                    if (e > a) open_ip[w] |= (e - a == 32 ? 0xffffffffu : ((1u << (e - a)) - 1u)) << a;
+                }
+            };
+            if (inside == 0) set_range(0, p.n_dummy);
+            for (int k = 0; k < p.max_ips; ++k)
+                if ((inside >> k) & 1u) set_range(p.n_dummy + k * p.tok_per_ip, p.n_dummy + (k + 1) * p.tok_per_ip);
+        }
+        bool act_ip[3];
+#pragma unroll
+        for (int kb = 0; kb < 3; ++kb)
+            act_ip[kb] = p.n_dummy == 0 || __builtin_amdgcn_ballot_w64(open_ip[kb] != 0u) != 0;
+        {
+            const char* sKp = sK + T * IPL_KPANEL;
+            const char* sVp = sV + T * IPL_VPANEL;
+            f32x16 st[3];
+#pragma unroll
+            for (int kb = 0; kb < 3; ++kb)
+                if (act_ip[kb]) st[kb] = score_block(sKp, kb);
+            float mloc = NEG_BIG;
+            // (the lane's key offset is made opaque per tile: as loop invariants the 48 "key >= Li" tests and the 48 bit masks are
+            // hoisted out of the tile loop into registers the kernel does not have)
+            int lane_key = 4 * lhi;
+            asm volatile("" : "+v"(lane_key));
+            const int lim = p.Li - lane_key;
+#pragma unroll
+            for (int kb = 0; kb < 3; ++kb) {
+                if (!act_ip[kb]) continue;
+                const unsigned open_lane = open_ip[kb] >> lane_key;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int kc = (r & 3) + 8 * (r >> 2);   // key 32 kb + kc + 4 lhi
+                    float sv = fmaf(st[kb][r], p.qk_scale, ((open_lane >> kc) & 1u) ? 0.0f : -10000.0f);
+                    if (kb * 32 + kc >= lim) sv = NEG_BIG;
+                    st[kb][r] = sv;
+                    mloc = fmaxf(mloc, sv);
+                }
+            }
+            mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
+            f32x2 psum2 = {0.f, 0.f};
+            const f32x2 l2 = {LOG2E, LOG2E}, m2 = {-mloc * LOG2E, -mloc * LOG2E};
+#pragma unroll
+            for (int kb = 0; kb < 3; ++kb) {
+                if (!act_ip[kb]) continue;
+#pragma unroll
+                for (int r = 0; r < 16; r += 2) {
+                    f32x2 v = {st[kb][r], st[kb][r + 1]};
+                    v = __builtin_elementwise_fma(v, l2, m2);
+                    const f32x2 e = {fast_exp2(v[0]), fast_exp2(v[1])};
+                    st[kb][r] = e[0];
+                    st[kb][r + 1] = e[1];
+                    psum2 += e;
+                }
+            }
+            float psum = psum2[0] + psum2[1];
+            psum += __shfl_xor(psum, 32, 64);
+            const float w = ip_scale / psum;
+            const f32x2 w2 = {w, w};
+#pragma unroll
+            for (int kb = 0; kb < 3; ++kb) {
+                if (!act_ip[kb]) continue;
+#pragma unroll
+                for (int r = 0; r < 16; r += 2) {
+                    f32x2 v = {st[kb][r], st[kb][r + 1]};
+                    v *= w2;
+                    st[kb][r] = v[0];
+                    st[kb][r + 1] = v[1];
+                }
+#pragma unroll
+                for (int hb = 0; hb < 2; ++hb) pv_half(sVp, st[kb], kb, hb);
+            }
+        }
+
+        // ---- store: ip_attn_kernel's 16-byte rows (one v_permlane32_swap per dword and group pair; only the stores are masked)
+        half_t* op = p.o + ((long)b * p.N + min(q0 + l31, p.N - 1)) * p.ldo + h * 64 + lhi * 8;
+        const bool row_ok = q0 + l31 < p.N;
+#pragma unroll
+        for (int db = 0; db < 2; ++db) {
+            unsigned og[4][2];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                h4 o;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = (half_t)ot[db][4 * g + e];
+                const u32x2_t t2 = __builtin_bit_cast(u32x2_t, o);
+                og[g][0] = t2[0], og[g][1] = t2[1];
+            }
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(og[2 * j][0]), "+v"(og[2 * j + 1][0]));
+                asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(og[2 * j][1]), "+v"(og[2 * j + 1][1]));
+                const u32x4_t v = {og[2 * j][0], og[2 * j][1], og[2 * j + 1][0], og[2 * j + 1][1]};
+                if (row_ok) *reinterpret_cast<u32x4_t*>(op + db * 32 + j * 16) = v;
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Generic small attention (any head_dim <= 256, any token counts) for the once-per-panel encoders:
 // CLIP ViT-H (257 tokens, head_dim 80), ViT-MAE, the perceiver Resampler and the MLLM's QwenResamplers (head_dim 160)
 // (reference src/models/resampler.py:67-72: (q*s)(k*s)^T, fp32 softmax).  One wavefront per query row.
@@ -887,6 +1211,45 @@ int ds_launch_ip_attn(const IPAttnParams& p0, hipStream_t stream) {
     const bool t16 = g_ip_variant != 3 && p.Lt > 64 && p.Lt <= 80 && p.Li > 64 && p.Li <= 80;
     if (t16) hipLaunchKernelGGL((ip_attn_kernel<4, false, true>), grid, dim3(256), (size_t)IP_PANEL_BYTES, stream, p, qt);
     else hipLaunchKernelGGL((ip_attn_kernel<4, false, false>), grid, dim3(256), (size_t)IP_PANEL_BYTES, stream, p, qt);
+    DS_LAUNCH_CHECK();
+    return 0;
+}
+
+int ds_launch_ip_attn_long(const IPAttnLongParams& pl0, hipStream_t stream) {
+    IPAttnLongParams pl = pl0;
+    IPAttnParams& p = pl.a;
+    DS_REQUIRE(p.Lt > 0 && p.Lt <= 4 * LP, "ip_attn_long: Lt=%d: 1 .. %d text keys (four panels of %d) are supported", p.Lt, 4 * LP, LP);
+    DS_REQUIRE(pl.T >= 1 && pl.T <= 4 && p.Lt <= pl.T * LP, "ip_attn_long: %d text panels of %d rows do not hold Lt=%d (at most 4 panels)", pl.T, LP, p.Lt);
+    DS_REQUIRE(p.Lt > (pl.T - 1) * LP, "ip_attn_long: Lt=%d leaves the last of %d text panels empty", p.Lt, pl.T);
+    if (p.ldk == 0) p.ldk = p.C;
+    if (p.sk == 0) p.sk = (long)LP * p.C;
+    if (p.sv == 0) p.sv = (long)LP * p.C;
+    if (pl.ldkt == 0) pl.ldkt = p.C;
+    if (pl.skt == 0) pl.skt = (long)LP * pl.T * p.C;
+    if (pl.svt == 0) pl.svt = (long)LP * pl.T * p.C;
+    p.step_x = linspace_step(p.mask_w), p.step_y = linspace_step(p.mask_h);
+    DS_REQUIRE(p.ldk % 8 == 0 && p.sk % 8 == 0 && p.sv % 8 == 0 && pl.ldkt % 8 == 0 && pl.skt % 8 == 0 && pl.svt % 8 == 0,
+               "ip_attn_long: key/value panel strides must be multiples of 8 (ldk=%ld sk=%ld sv=%ld, text: ldk=%ld sk=%ld sv=%ld)",
+               p.ldk, p.sk, p.sv, pl.ldkt, pl.skt, pl.svt);
+    DS_REQUIRE(p.B > 0 && p.heads > 0 && p.N > 0, "ip_attn_long: empty problem");
+    DS_REQUIRE(p.Li > 0 && p.Li <= LP, "ip_attn_long: Li=%d exceeds %d", p.Li, LP);
+    DS_REQUIRE(p.C == p.heads * 64, "ip_attn_long: head_dim must be 64 (C=%d heads=%d)", p.C, p.heads);
+    DS_REQUIRE(p.max_ips >= 1 && p.max_ips <= 8 && p.tok_per_ip > 0, "ip_attn_long: bad ip token layout");
+    DS_REQUIRE(p.n_dummy + p.max_ips * p.tok_per_ip == p.Li, "ip_attn_long: Li (%d) != n_dummy + max_ips*tok_per_ip", p.Li);
+    DS_REQUIRE(p.mask_h * p.mask_w == p.N, "ip_attn_long: mask grid %dx%d != N %d", p.mask_h, p.mask_w, p.N);
+    DS_REQUIRE(p.ip_scale_rows == 0 || (p.ip_scale_rows == 1 && p.ip_scale_ptr),
+               "ip_attn_long: ip_scale_rows must be 0, or 1 with a device vector of B scales");
+    DS_REQUIRE(p.ldq % 8 == 0 && p.ldo % 8 == 0, "ip_attn_long: ldq (%ld) and ldo (%ld) must be multiples of 8 (16-byte row pieces)", (long)p.ldq, (long)p.ldo);
+    // 256 query rows per block and tile; several tiles per block once there are plenty of blocks (ip_attn's rule and knob)
+    const int tiles = (p.N + 255) / 256;
+    int qt = 1;
+    while (qt < 8 && (long)((tiles + 2 * qt - 1) / (2 * qt)) * p.B * p.heads >= g_ip_min_blocks) qt *= 2;
+    const size_t lds = (size_t)(pl.T + 1) * (IPL_KPANEL + IPL_VPANEL);
+    auto kern = ip_attn_long_kernel<8>;
+    static unsigned long long attr_devs = 0;
+    if (ds_first_on_device(attr_devs))
+        DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 5 * (IPL_KPANEL + IPL_VPANEL)));
+    hipLaunchKernelGGL(kern, dim3((tiles + qt - 1) / qt, p.B * p.heads), dim3(512), lds, stream, pl, qt);
     DS_LAUNCH_CHECK();
     return 0;
 }

@@ -446,6 +446,43 @@ int ds_masked_ip_attn_rows_f16(const void* q, int64_t ldq, const void* kt, const
     return ds_launch_ip_attn(p, S(stream));
 }
 
+static IPAttnLongParams ip_attn_long_params(const void* q, int64_t ldq, const void* kt, const void* vtt, const void* ki, const void* vti,
+                                            const float* bbox, void* o, int64_t ldo, int B, int heads, int N, int Lt, int text_panels,
+                                            int Li, int n_dummy, int tok_per_ip, int max_ips, int mask_h, int mask_w, float qk_scale,
+                                            int64_t ldkt, int64_t skt, int64_t svt, int64_t ldk, int64_t sk, int64_t sv) {
+    IPAttnLongParams pl;
+    IPAttnParams& p = pl.a;
+    pl.ldkt = ldkt; pl.skt = skt; pl.svt = svt; pl.T = text_panels;
+    p.ldk = ldk; p.sk = sk; p.sv = sv;
+    p.q = H(q); p.kt = H(kt); p.vtt = H(vtt); p.ki = H(ki); p.vti = H(vti); p.bbox = bbox; p.o = HM(o);
+    p.ldq = ldq; p.ldo = ldo; p.B = B; p.heads = heads; p.N = N; p.C = heads * 64;
+    p.Lt = Lt; p.Li = Li; p.LP = 96; p.n_dummy = n_dummy; p.tok_per_ip = tok_per_ip; p.max_ips = max_ips;
+    p.mask_h = mask_h; p.mask_w = mask_w; p.qk_scale = qk_scale;
+    return pl;
+}
+
+int ds_masked_ip_attn_long_f16(const void* q, int64_t ldq, const void* kt, const void* vtt, const void* ki, const void* vti,
+                               const float* bbox, void* o, int64_t ldo, int B, int heads, int N, int Lt, int text_panels, int Li,
+                               int n_dummy, int tok_per_ip, int max_ips, int mask_h, int mask_w, float qk_scale, float ip_scale,
+                               const float* ip_scale_dev, int64_t ldkt, int64_t skt, int64_t svt, int64_t ldk, int64_t sk,
+                               int64_t sv, void* stream) {
+    IPAttnLongParams pl = ip_attn_long_params(q, ldq, kt, vtt, ki, vti, bbox, o, ldo, B, heads, N, Lt, text_panels, Li, n_dummy,
+                                              tok_per_ip, max_ips, mask_h, mask_w, qk_scale, ldkt, skt, svt, ldk, sk, sv);
+    pl.a.ip_scale = ip_scale; pl.a.ip_scale_ptr = ip_scale_dev;
+    return ds_launch_ip_attn_long(pl, S(stream));
+}
+
+int ds_masked_ip_attn_long_rows_f16(const void* q, int64_t ldq, const void* kt, const void* vtt, const void* ki, const void* vti,
+                                    const float* bbox, void* o, int64_t ldo, int B, int heads, int N, int Lt, int text_panels,
+                                    int Li, int n_dummy, int tok_per_ip, int max_ips, int mask_h, int mask_w, float qk_scale,
+                                    const float* ip_scale_rows_dev, int64_t ldkt, int64_t skt, int64_t svt, int64_t ldk,
+                                    int64_t sk, int64_t sv, void* stream) {
+    IPAttnLongParams pl = ip_attn_long_params(q, ldq, kt, vtt, ki, vti, bbox, o, ldo, B, heads, N, Lt, text_panels, Li, n_dummy,
+                                              tok_per_ip, max_ips, mask_h, mask_w, qk_scale, ldkt, skt, svt, ldk, sk, sv);
+    pl.a.ip_scale_ptr = ip_scale_rows_dev; pl.a.ip_scale_rows = 1;
+    return ds_launch_ip_attn_long(pl, S(stream));
+}
+
 int ds_ip_region_flags(const float* bbox, uint8_t* flags, int B, int N, int max_ips, int mask_h, int mask_w,
                        void* stream) {
     return ds_launch_ip_region_flags(bbox, flags, B, N, max_ips, mask_h, mask_w, S(stream));
@@ -882,6 +919,11 @@ static int run_op(const ds_op& o, hipStream_t st) {
             a.B = i[0]; a.heads = i[1]; a.N = i[2]; a.C = i[1] * 64; a.Lt = i[3]; a.Li = i[4]; a.LP = 96;
             a.n_dummy = i[5]; a.tok_per_ip = i[6]; a.max_ips = i[7]; a.mask_h = i[8]; a.mask_w = i[9];
             a.qk_scale = o.f[0]; a.ip_scale = o.f[1]; a.ip_scale_rows = i[10];
+            if (i[11] > 1) {   // long prompt: i[11] text panels with the strides l[5..7] of their own
+                IPAttnLongParams pl;
+                pl.a = a; pl.T = i[11]; pl.ldkt = l[5]; pl.skt = l[6]; pl.svt = l[7];
+                return ds_launch_ip_attn_long(pl, st);
+            }
             return ds_launch_ip_attn(a, st);
         }
         case DS_OP_CONV_IN:
@@ -1016,7 +1058,7 @@ int ds_op_describe(const ds_op* op, char* name, int name_len, double* flops, dou
             by = 2.0 * i[0] * (double)i[1] * 64 * (2.0 * i[2] + 2.0 * i[3]);
             break;
         case DS_OP_IP_ATTN:
-            nm = "ip_attn_kernel";
+            nm = i[11] > 1 ? "ip_attn_long_kernel" : "ip_attn_kernel";
             fl = 4.0 * i[0] * (double)i[1] * i[2] * (double)(i[3] + i[4]) * 64;
             by = 2.0 * i[0] * (double)i[1] * 64 * (2.0 * i[2] + 2.0 * (i[3] + i[4]));
             break;

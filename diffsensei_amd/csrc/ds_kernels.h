@@ -172,6 +172,15 @@ struct IPAttnParams {
                                    // both belong to panel n: the caller writes that panel's scale into both)
 };
 int ds_launch_ip_attn(const IPAttnParams& p, hipStream_t stream);
+// Long prompts (ip_attn_long_kernel): the text side is T panels of 96 rows, kt [B,96 T,C] / vtt [B,C,96 T] (value rows dense),
+// with strides of their own; a.ldk / a.sk / a.sv describe the IP panels alone.  1 <= a.Lt <= 384, (T - 1) 96 < a.Lt <= 96 T.
+struct IPAttnLongParams {
+    IPAttnParams a;
+    long ldkt = 0, skt = 0;        // text key panel: row stride / batch stride (elements); 0 -> dense [B,96 T,C]
+    long svt = 0;                  // text value panel: batch stride (elements); 0 -> dense [B,C,96 T]
+    int T = 0;                     // text panels
+};
+int ds_launch_ip_attn_long(const IPAttnLongParams& p, hipStream_t stream);
 int ds_launch_small_attn(const half_t* q, const half_t* k, const half_t* v, half_t* o, long ldq, long ldk, long ldv,
                          long ldo, long sq, long sk, long sv, long so, int B, int heads, int Nq, int Nk, int D,
                          float scale, hipStream_t stream, int causal = 0);

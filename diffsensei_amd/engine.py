@@ -26,6 +26,7 @@ from .unet_config import AttnSpec, ResnetSpec, UNetMangaConfig, build_topology
 
 Tensor = torch.Tensor
 LP = 96  # padded key-panel length of the fused cross-attention kernel
+MAX_TEXT_TOKENS = 4 * LP  # text keys of the long-prompt kernel: four panels
 
 
 # ------------------------------------------------------------------------------------------ weight packing
@@ -446,13 +447,21 @@ class UNetEngine:
     """Static-shape execution state for one (batch, latent H, latent W) bucket."""
 
     def __init__(self, packed: PackedUNet, batch: int, height: int, width: int, aspect_ratio: Optional[float] = None,
-                 attention: str = "fp16"):
+                 attention: str = "fp16", text_tokens: Optional[int] = None):
         """attention: "fp16" - the reference's arithmetic, the only one since round 6 (the OCP e4m3 variant of rounds 2-5 was
-        retired: 5.4e-2 per op for +3.7 % at 2048 x 2048)."""
+        retired: 5.4e-2 per op for +3.7 % at 2048 x 2048).
+        text_tokens: the text length of `encoder_hidden_states`, 1..384 (None: cfg.num_text_tokens).  One engine has one text
+        length: the text K / V^T panels are T = ceil(text_tokens / 96) panels of 96 rows, and with T > 1 every attn2 op is the
+        long-prompt form (ip_attn_long_kernel).  Up to 96 tokens the plans are op for op those of an engine built without it."""
         if attention != "fp16":
             raise ValueError(f"attention must be 'fp16', got {attention!r} (the fp8 variant was removed in round 6)")
         self.attention = attention
         cfg = packed.cfg
+        self.text_tokens = int(cfg.num_text_tokens if text_tokens is None else text_tokens)
+        if not 1 <= self.text_tokens <= MAX_TEXT_TOKENS:
+            raise ValueError(f"text_tokens must lie in 1..{MAX_TEXT_TOKENS} (four key panels of {LP}), got {text_tokens!r}")
+        self.text_panels = (self.text_tokens + LP - 1) // LP
+        LPT = LP * self.text_panels
         self.pk, self.cfg = packed, cfg
         self.B, self.H, self.W = batch, height, width
         self.dev = packed.device
@@ -463,7 +472,7 @@ class UNetEngine:
         E = lambda *shape, dtype=torch.float16: self._alloc(shape, dtype)
         c0 = cfg.block_out_channels[0]
         temb = cfg.time_embed_dim
-        n_txt, n_ip = cfg.num_text_tokens, cfg.num_ip_tokens
+        n_txt, n_ip = self.text_tokens, cfg.num_ip_tokens
         xdim = cfg.cross_attention_dim
         # ---- request-level inputs (written by the host before `prepare`)
         self.enc = E(B, n_txt + n_ip, xdim)                     # encoder_hidden_states = [text | dummy+ip]
@@ -496,12 +505,12 @@ class UNetEngine:
         self.panel = None                                       # panel schedules: start | steps | mode | per-panel rows, one buffer
         self._panel_ns = None
         # ---- request-level derived tensors
-        self.enc_txt = E(B, LP, xdim)
+        self.enc_txt = E(B, LPT, xdim)
         self.enc_ip = E(B, LP, xdim)
         kvt = packed.kv_total
-        self.k_txt = E(B * LP, kvt)
+        self.k_txt = E(B * LPT, kvt)
         self.k_ip = E(B * LP, kvt)
-        self.v_txt = E(B, kvt, LP)
+        self.v_txt = E(B, kvt, LPT)
         self.v_ip = E(B, kvt, LP)
         self.add_in = E(B, cfg.projection_class_embeddings_input_dim)
         self.add_h = E(B, temb)
@@ -571,20 +580,21 @@ class UNetEngine:
     def _build_prepare(self) -> Plan:
         cfg, pk, B = self.cfg, self.pk, self.B
         w = pk.w
-        n_txt, n_ip, xdim = cfg.num_text_tokens, cfg.num_ip_tokens, cfg.cross_attention_dim
+        n_txt, n_ip, xdim = self.text_tokens, cfg.num_ip_tokens, cfg.cross_attention_dim
         kvt = pk.kv_total
+        LPT = LP * self.text_panels
         ops = [
-            make_op("PAD_ROWS", i=(B, n_txt, LP, 0, n_txt + n_ip, xdim), p=(self.enc, self.enc_txt)),
+            make_op("PAD_ROWS", i=(B, n_txt, LPT, 0, n_txt + n_ip, xdim), p=(self.enc, self.enc_txt)),
             make_op("PAD_ROWS", i=(B, n_ip, LP, n_txt, n_txt + n_ip, xdim), p=(self.enc, self.enc_ip)),
         ]
-        for enc, wk, wv, kout, vout in ((self.enc_txt, w["xattn.k_text"], w["xattn.v_text"], self.k_txt, self.v_txt),
-                                        (self.enc_ip, w["xattn.k_ip"], w["xattn.v_ip"], self.k_ip, self.v_ip)):
-            # K panels of every layer: [B*96, sumC] = enc_pad @ Wk_all^T
-            ops.append(make_op("GEMM", i=(B * LP, kvt, xdim, xdim, 0, 1, 0, 1), l=(xdim, 0, xdim, kvt, 0),
+        for enc, wk, wv, kout, vout, rows in ((self.enc_txt, w["xattn.k_text"], w["xattn.v_text"], self.k_txt, self.v_txt, LPT),
+                                              (self.enc_ip, w["xattn.k_ip"], w["xattn.v_ip"], self.k_ip, self.v_ip, LP)):
+            # K panels of every layer: [B*rows, sumC] = enc_pad @ Wk_all^T   (rows: 96 per panel)
+            ops.append(make_op("GEMM", i=(B * rows, kvt, xdim, xdim, 0, 1, 0, 1), l=(xdim, 0, xdim, kvt, 0),
                                p=(enc, None, wk, kout)))
-            # V^T panels: per image [sumC, 96] = Wv_all @ enc_pad[b]^T
-            ops.append(make_op("GEMM", i=(kvt, LP, xdim, xdim, 0, B, 0, 1),
-                               l=(xdim, 0, xdim, LP, 0, 0, 0, LP * xdim, kvt * LP, 0), p=(wv, None, enc, vout)))
+            # V^T panels: per image [sumC, rows] = Wv_all @ enc_pad[b]^T
+            ops.append(make_op("GEMM", i=(kvt, rows, xdim, xdim, 0, B, 0, 1),
+                               l=(xdim, 0, xdim, rows, 0, 0, 0, rows * xdim, kvt * rows, 0), p=(wv, None, enc, vout)))
         pooled = self.text_embeds.shape[1]
         ops += [
             make_op("ADD_TIME_IDS", i=(B, pooled, 6, cfg.addition_time_embed_dim, int(cfg.flip_sin_to_cos)),
@@ -761,12 +771,15 @@ class UNetEngine:
                 ops.append(make_op("LAYERNORM", i=(M, Cc), f=(1e-5,), p=(h, tn, w[t + ".norm2.weight"], w[t + ".norm2.bias"])))
                 self._gemm(ops, tn, w[t + ".attn2.to_q.weight"], q2, M, Cc, Cc)
             off = self.pk.kv_off[t]
+            TP = self.text_panels
+            LPT = LP * TP
+            # TP > 1 (long prompt): i[11] text panels whose strides are l[5..7]; one panel: today's op, slot for slot
             ops.append(make_op(
                 "IP_ATTN",
-                i=(B, a.heads, N, cfg.num_text_tokens, cfg.num_ip_tokens, cfg.num_vision_tokens, cfg.num_vision_tokens,
-                   cfg.max_num_ips, mh, mw),
-                f=(scale, 1.0), l=(Cc, Cc, kvt, LP * kvt, kvt * LP),
-                p=(q2, self.k_txt.data_ptr() + 2 * off, self.v_txt.data_ptr() + 2 * off * LP,
+                i=(B, a.heads, N, self.text_tokens, cfg.num_ip_tokens, cfg.num_vision_tokens, cfg.num_vision_tokens,
+                   cfg.max_num_ips, mh, mw) + ((0, TP) if TP > 1 else ()),
+                f=(scale, 1.0), l=(Cc, Cc, kvt, LP * kvt, kvt * LP) + ((kvt, LPT * kvt, kvt * LPT) if TP > 1 else ()),
+                p=(q2, self.k_txt.data_ptr() + 2 * off, self.v_txt.data_ptr() + 2 * off * LPT,
                    self.k_ip.data_ptr() + 2 * off, self.v_ip.data_ptr() + 2 * off * LP, self.bbox, ao, self.ip_scale)))
             self._gemm(ops, ao, w[t + ".attn2.to_out.0.weight"], h, M, Cc, Cc, bias=w[t + ".attn2.to_out.0.bias"],
                        residual=h, stats_out=part if fuse else None, stats_strip=sw)
@@ -1166,6 +1179,7 @@ class UNetEngine:
         k = len(slots)
         rows = slots + [ns + q for q in slots] if do_cfg else slots
         s = self._scale_values(ip_scale, k, "ip_scale") or [float(ip_scale)] * k
+        self._check_text_length(encoder_hidden_states)
         idx = torch.tensor(rows, dtype=torch.int64).pin_memory().to(self.dev, non_blocking=True)
 
         def put(dst, src):
@@ -1181,11 +1195,21 @@ class UNetEngine:
         put(self.ip_scale, torch.tensor(s + s if do_cfg else s, dtype=torch.float32))
         self.prepare_plan.run()
 
+    def _check_text_length(self, encoder_hidden_states: Tensor):
+        """One engine has one text length: a tensor of another length is refused, never reshaped into the buffer."""
+        n = self.enc.shape[1]
+        if encoder_hidden_states.dim() == 3 and encoder_hidden_states.shape[1] != n:
+            n_ip = self.cfg.num_ip_tokens
+            raise ValueError(f"encoder_hidden_states has {encoder_hidden_states.shape[1]} tokens "
+                             f"({encoder_hidden_states.shape[1] - n_ip} text + {n_ip} image); this engine was built for "
+                             f"{self.text_tokens} text tokens ({n} in all) - ask for an engine with that text_tokens")
+
     # -- host-side setters (tiny H2D copies; never inside a captured graph)
     def set_request(self, encoder_hidden_states: Tensor, text_embeds: Tensor, time_ids: Tensor, bbox: Tensor,
                     dialog_boxes: Optional[Tensor], ip_scale):
         """ip_scale: a number, or one value per batch row (`B` values; under CFG rows n and ns + n belong to panel n and
         carry the same value).  Values that differ switch the engine to per-panel plans (`enable_per_panel`)."""
+        self._check_text_length(encoder_hidden_states)
         self.enc.copy_(encoder_hidden_states.to(self.dev, torch.float16).reshape(self.enc.shape))
         self.text_embeds.copy_(text_embeds.to(self.dev, torch.float16).reshape(self.text_embeds.shape))
         self.time_ids.copy_(time_ids.to(self.dev, torch.float16).reshape(self.time_ids.shape))

@@ -279,7 +279,10 @@ def masked_ip_attention(q: Tensor, kt: Tensor, vtt: Tensor, ki: Tensor, vti: Ten
     they are: q / out `buf[:, :, c0:c0+C]` (row stride ldq / ldo, batch stride N rows), key panels `stacked[:, :, c0:c0+C]`
     (ldk, sk), value panels `stacked_t[:, c0:c0+C, :]` (sv).  `ldq, ldo, ldk, sk, sv` override what the tensors say;
     `ip_scale_dev` (fp32 on the device) replaces `ip_scale`: shape [1] is one scale for the batch, shape [B] one per batch
-    row (under CFG rows n and ns + n belong to panel n and carry the same value).  With B = 1 the two mean the same."""
+    row (under CFG rows n and ns + n belong to panel n and carry the same value).  With B = 1 the two mean the same.
+
+    Long prompts: kt [B,96 T,C] / vtt [B,C,96 T] with T = ceil(Lt / 96) in 2..4 (Lt up to 384) take the long-prompt kernel
+    (ds_masked_ip_attn_long_f16 / ..._rows_f16); the text panels then have strides of their own, taken from the tensors."""
     for t in (q, kt, vtt, ki, vti, out):
         if t is None:
             continue
@@ -302,6 +305,27 @@ def masked_ip_attention(q: Tensor, kt: Tensor, vtt: Tensor, ki: Tensor, vti: Ten
     ldo = out.stride(1) if ldo is None else ldo
     if B > 1 and (q.stride(0) != N * ldq or out.stride(0) != N * ldo):
         raise _lib.DiffSenseiHipError("masked_ip_attention: q / out batch stride must be N rows")
+    if kt.shape[1] != 96:
+        # long prompt: T text panels of 96 rows with strides of their own (ds_masked_ip_attn_long_f16); one panel stays below
+        T = kt.shape[1] // 96
+        if kt.shape[1] % 96 or vtt.shape[2] != kt.shape[1] or vtt.stride(1) != vtt.shape[2] or vti.stride(1) != vti.shape[2]:
+            raise _lib.DiffSenseiHipError(f"masked_ip_attention: text panels [B,96 T,C] / [B,C,96 T] with dense value rows are needed "
+                                          f"(kt {tuple(kt.shape)}, vtt {tuple(vtt.shape)})")
+        if ldk is not None or sk is not None or sv is not None:
+            raise _lib.DiffSenseiHipError("masked_ip_attention: ldk / sk / sv overrides are for the one-panel form")
+        strides = (kt.stride(1), kt.stride(0), vtt.stride(0), ki.stride(1), ki.stride(0), vti.stride(0))
+        if ip_scale_dev is not None and ip_scale_dev.shape[0] > 1:
+            check(_lib.load().ds_masked_ip_attn_long_rows_f16(_p(q), ldq, _p(kt), _p(vtt), _p(ki), _p(vti), _p(bbox), _p(out), ldo,
+                                                              B, heads, N, Lt, T, Li, n_dummy, tok_per_ip, bbox.shape[1],
+                                                              mask_hw[0], mask_hw[1], qk_scale, _p(ip_scale_dev), *strides,
+                                                              _stream()),
+                  "ds_masked_ip_attn_long_rows_f16")
+            return out
+        check(_lib.load().ds_masked_ip_attn_long_f16(_p(q), ldq, _p(kt), _p(vtt), _p(ki), _p(vti), _p(bbox), _p(out), ldo, B, heads,
+                                                     N, Lt, T, Li, n_dummy, tok_per_ip, bbox.shape[1], mask_hw[0], mask_hw[1],
+                                                     qk_scale, ip_scale, _p(ip_scale_dev), *strides, _stream()),
+              "ds_masked_ip_attn_long_f16")
+        return out
     if kt.stride() != ki.stride() or vtt.stride() != vti.stride() or vtt.stride(1) != vtt.shape[2]:
         raise _lib.DiffSenseiHipError("masked_ip_attention: text and IP panels must share strides; value rows are dense")
     ldk = kt.stride(1) if ldk is None else ldk

@@ -37,6 +37,38 @@ class StableDiffusionXLPipelineOutput:
     images: Any
 
 
+CHUNK_IDS = 75            # prompt ids per chunk: a CLIP window of 77 less BOS and EOS
+MAX_PROMPT_CHUNKS = 4     # 4 x 77 = 308 text keys, inside the 384 of the long-prompt cross-attention kernel
+MAX_TEXT_TOKENS = 384
+
+
+def chunk_count(n_ids: int, max_chunks: int) -> Tuple[int, int]:
+    """(chunks, dropped ids) of a prompt of `n_ids` ids (without special tokens): k = max(1, ceil(n / 75)) clipped to
+    `max_chunks`; what does not fit into the kept chunks is dropped from the tail."""
+    k = min(max(1, -(-int(n_ids) // CHUNK_IDS)), int(max_chunks))
+    return k, max(0, int(n_ids) - CHUNK_IDS * k)
+
+
+def chunk_token_ids(ids, bos: int, eos: int, pad: int, max_chunks: int) -> Tensor:
+    """Prompt ids WITHOUT special tokens -> int64 [k, 77]: every chunk is [bos] + up to 75 ids + [eos], then `pad` up to 77
+    (the tokenizer's own pad id: CLIP-L pads with its EOS, OpenCLIP-bigG with id 0).  k and the dropped tail: `chunk_count`.
+    For at most 75 ids the one chunk is what `tok(text, padding="max_length", max_length=77, truncation=True)` gives."""
+    ids = [int(v) for v in (ids.reshape(-1).tolist() if torch.is_tensor(ids) else ids)]
+    k, _ = chunk_count(len(ids), max_chunks)
+    rows = []
+    for c in range(k):
+        part = ids[c * CHUNK_IDS:(c + 1) * CHUNK_IDS]
+        row = [int(bos)] + part + [int(eos)]
+        rows.append(row + [int(pad)] * (CHUNK_IDS + 2 - len(row)))
+    return torch.tensor(rows, dtype=torch.int64)
+
+
+def check_max_prompt_chunks(value) -> int:
+    if isinstance(value, bool) or not isinstance(value, int) or not 1 <= value <= MAX_PROMPT_CHUNKS:
+        raise ValueError(f"`max_prompt_chunks` must be an integer in 1..{MAX_PROMPT_CHUNKS}, got {value!r}")
+    return value
+
+
 def _black_image():
     from PIL import Image
     return Image.new("RGB", (224, 224), (0, 0, 0))
@@ -85,6 +117,7 @@ class DiffSenseiPipeline:
         self._stream = None
         self.use_graph = os.environ.get("DIFFSENSEI_GRAPH", "1") != "0"
         self.last_run_info = {}
+        self.last_prompt_info = {}
         self._keep_adapters_until = None     # set inside `hold_adapters()`: the adapter state to restore at its end
 
     @classmethod
@@ -279,10 +312,63 @@ class DiffSenseiPipeline:
                 attn_processor.scale = scale
 
     # ---- text encoding (transformers modules, not on this path; diffusers SDXL `encode_prompt` semantics [3P])
-    def encode_prompt(self, prompt, prompt_2, device, num_images_per_prompt, do_cfg, negative_prompt, negative_prompt_2):
+    @staticmethod
+    def _raw_ids(tok, text) -> List[int]:
+        """The ids of `text` without special tokens and without truncation (host only)."""
+        ids = tok(text, add_special_tokens=False, truncation=False).input_ids
+        ids = ids.reshape(-1).tolist() if torch.is_tensor(ids) else ids
+        if ids and isinstance(ids[0], (list, tuple)):
+            ids = ids[0]
+        return [int(v) for v in ids]
+
+    def _prompt_texts(self, prompt, prompt_2, do_cfg, negative_prompt, negative_prompt_2):
+        """[(tokenizer, text), ...] of everything `encode_prompt` encodes: both prompts and, under CFG unless the empty
+        negative is forced to zeros, both negative prompts."""
+        toks = [self.tokenizer, self.tokenizer_2]
+        texts = list(zip(toks, [prompt, prompt_2 or prompt]))
+        if not (do_cfg and negative_prompt is None and self.force_zeros_for_empty_prompt):
+            texts += list(zip(toks, [negative_prompt or "", negative_prompt_2 or negative_prompt or ""]))
+        return texts
+
+    def prompt_chunk_count(self, request: dict) -> int:
+        """How many 77-token chunks the text context of this request (the keyword arguments of `__call__`) will have: from
+        the length of `prompt_embeds` if given, else from tokenizing its prompts under `max_prompt_chunks` (host only, no
+        encoder runs).  `serving.bucket_key` keys on it: one engine, and one UNet batch, has one text length."""
+        pe = request.get("prompt_embeds")
+        if pe is not None:
+            return -(-int(pe.shape[-2]) // 77)
+        mc = check_max_prompt_chunks(request.get("max_prompt_chunks", 1))
+        if mc == 1 or self.tokenizer is None:
+            return 1
+        g = request.get("guidance_scale", 5.0)
+        g = g if _is_number(g) else (g.reshape(-1).tolist() if torch.is_tensor(g) else list(g))[0]
+        texts = self._prompt_texts(request.get("prompt"), request.get("prompt_2"), float(g) > 1,
+                                   request.get("negative_prompt"), request.get("negative_prompt_2"))
+        return max(chunk_count(len(self._raw_ids(tok, text)), mc)[0] for tok, text in texts)
+
+    def encode_prompt(self, prompt, prompt_2, device, num_images_per_prompt, do_cfg, negative_prompt, negative_prompt_2,
+                      max_prompt_chunks: int = 1):
+        """max_prompt_chunks = 1: the reference's path - one 77-token window per encoder, the tail of a longer prompt
+        truncated.  2..4: chunked encoding.  The ids of every text (both prompts and, under CFG, both negatives) are cut
+        into chunks of 75 (`chunk_token_ids`); k is the largest chunk count among them, shorter ones are padded with empty
+        chunks; each encoder encodes its [k, 77] ids in one call; the penultimate hidden states are concatenated on the
+        token axis to [1, 77 k, 2048].  The pooled embedding is that of the FIRST chunk of `text_encoder_2`: this project's
+        rule (diffusers was not at hand to compare with).  A prompt of at most 75 ids gives the tensors of the one-window
+        path.  `self.last_prompt_info` = {"prompt_chunks": k, "prompt_tokens_dropped": n} (n: ids cut from the tails, summed
+        over the texts; None when max_prompt_chunks = 1 and the tokenizer cannot tokenize without special tokens)."""
         if self.text_encoder is None or self.tokenizer is None:
             raise ValueError("no text encoders registered: pass prompt_embeds / negative_prompt_embeds / "
                              "pooled_prompt_embeds / negative_pooled_prompt_embeds")
+        max_prompt_chunks = check_max_prompt_chunks(max_prompt_chunks)
+        if max_prompt_chunks > 1:
+            return self._encode_prompt_chunked(prompt, prompt_2, device, num_images_per_prompt, do_cfg, negative_prompt,
+                                               negative_prompt_2, max_prompt_chunks)
+        try:
+            dropped = sum(chunk_count(len(self._raw_ids(tok, text)), 1)[1]
+                          for tok, text in self._prompt_texts(prompt, prompt_2, do_cfg, negative_prompt, negative_prompt_2))
+        except TypeError:         # a tokenizer without `add_special_tokens`: the count is unknown, the encoding is unaffected
+            dropped = None
+        self.last_prompt_info = {"prompt_chunks": 1, "prompt_tokens_dropped": dropped}
         prompts = [prompt, prompt_2 or prompt]
         negs = [negative_prompt or "", negative_prompt_2 or negative_prompt or ""]
         toks, encs = [self.tokenizer, self.tokenizer_2], [self.text_encoder, self.text_encoder_2]
@@ -302,6 +388,37 @@ class DiffSenseiPipeline:
                 ne, npool = torch.zeros_like(pe), torch.zeros_like(pp)
             else:
                 ne, npool = enc(negs)
+        rep = lambda t: t.repeat_interleave(num_images_per_prompt, dim=0).to(device, torch.float16)
+        return rep(pe), rep(ne), rep(pp), rep(npool)
+
+    def _encode_prompt_chunked(self, prompt, prompt_2, device, num_images_per_prompt, do_cfg, negative_prompt,
+                               negative_prompt_2, max_chunks):
+        texts = self._prompt_texts(prompt, prompt_2, do_cfg, negative_prompt, negative_prompt_2)
+        raw = [self._raw_ids(tok, text) for tok, text in texts]
+        counts = [chunk_count(len(ids), max_chunks) for ids in raw]
+        k = max(c for c, _ in counts)
+        self.last_prompt_info = {"prompt_chunks": k, "prompt_tokens_dropped": sum(d for _, d in counts)}
+        encs = [self.text_encoder, self.text_encoder_2]
+
+        def enc(pair):            # pair: the entries of `texts` / `raw` of one side, tokenizer 1 then tokenizer 2
+            embs, pooled = [], None
+            for j, te in zip(pair, encs):
+                tok = texts[j][0]
+                special = (tok.bos_token_id, tok.eos_token_id, tok.pad_token_id)
+                ids = chunk_token_ids(raw[j], *special, max_chunks)
+                if ids.shape[0] < k:                      # a shorter text: empty chunks behind it
+                    ids = torch.cat([ids, chunk_token_ids([], *special, 1).repeat(k - ids.shape[0], 1)], dim=0)
+                hidden, pooled = te.encode(ids)           # [k, 77, D], [k, P]: one call per encoder
+                embs.append(hidden.reshape(1, k * hidden.shape[1], hidden.shape[2]))
+                pooled = pooled[:1]                       # the first chunk's (the last encoder's is the one returned)
+            return torch.cat(embs, dim=-1), pooled
+
+        with torch.no_grad():
+            pe, pp = enc((0, 1))
+            if len(texts) == 2:                           # CFG with the empty negative forced to zeros
+                ne, npool = torch.zeros_like(pe), torch.zeros_like(pp)
+            else:
+                ne, npool = enc((2, 3))
         rep = lambda t: t.repeat_interleave(num_images_per_prompt, dim=0).to(device, torch.float16)
         return rep(pe), rep(ne), rep(pp), rep(npool)
 
@@ -461,7 +578,8 @@ class DiffSenseiPipeline:
                  callback_on_step_end=None, callback_on_step_end_tensor_inputs: Sequence[str] = ("latents",),
                  noise_seeds: Optional[Sequence[int]] = None, redraw_latents: Optional[Tensor] = None,
                  redraw_bbox: Optional[List[List[float]]] = None, redraw_mask: Optional[Tensor] = None,
-                 strength: float = 1.0, redraw_image=None, redraw_image_seeds: Optional[Sequence[int]] = None):
+                 strength: float = 1.0, redraw_image=None, redraw_image_seeds: Optional[Sequence[int]] = None,
+                 max_prompt_chunks: int = 1):
         """`callback_on_step_end(pipe, step_index, timestep, {"latents": device tensor}) -> dict | None` is diffusers'
         SDXL-pipeline hook [3P]; together with `pipe._interrupt = True` it is the reference's early exit: the loop
         `continue`s over the remaining steps (reference :314-315) and the call still decodes and post-processes.  Latents
@@ -488,7 +606,14 @@ class DiffSenseiPipeline:
         `last_run_info["redraw"]` = {"t_start", "steps_run", "repaint_fraction"}.  `redraw_image` (a PIL image or a list, a
         uint8 array / tensor [H,W,3] or [B,H,W,3], a float tensor [B,3,H,W] in [0, 1]; exactly `height` x `width`, no resize)
         takes the place of `redraw_latents`: it goes through the VAE encoder (`encode_image`: the posterior's mode, or a
-        sample when `redraw_image_seeds` gives one int64 per image) and then follows the same path."""
+        sample when `redraw_image_seeds` gives one int64 per image) and then follows the same path.
+
+        Long prompts: `max_prompt_chunks` (1..4; anything else is a ValueError before any encoder runs).  1, the default, is
+        the reference's behaviour: the prompt is truncated to one 77-token CLIP window.  With 2..4 a prompt of more than 75
+        ids is encoded in chunks of 75 (`encode_prompt`) and the UNet attends all 77 k text tokens
+        (`last_run_info["prompt_chunks"]` = k, `["prompt_tokens_dropped"]` = ids cut behind the last chunk, 0 if none).
+        `prompt_embeds` / `negative_prompt_embeds` may have any equal length in 1..384; a shorter negative is an error."""
+        check_max_prompt_chunks(max_prompt_chunks)
         bad = [k for k in callback_on_step_end_tensor_inputs if k != "latents"]
         if bad:
             raise ValueError(f"`callback_on_step_end_tensor_inputs` has to be in ['latents'], but found {bad}")
@@ -498,7 +623,7 @@ class DiffSenseiPipeline:
                                   target_size, ip_images, ip_image_embeds, ip_bbox, ip_scale, dialog_bbox, latents,
                                   prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds,
                                   negative_pooled_prompt_embeds, noise_seeds, redraw_latents, redraw_bbox, redraw_mask,
-                                  strength, redraw_image, redraw_image_seeds)
+                                  strength, redraw_image, redraw_image_seeds, max_prompt_chunks)
         out_latents = self._denoise([cond], num_inference_steps, callback_on_step_end)
         return StableDiffusionXLPipelineOutput(images=self._postprocess(out_latents, output_type))
 
@@ -508,7 +633,9 @@ class DiffSenseiPipeline:
                       ip_images, ip_image_embeds, ip_bbox, ip_scale, dialog_bbox, latents, prompt_embeds,
                       negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, noise_seeds=None,
                       redraw_latents=None, redraw_bbox=None, redraw_mask=None, strength=1.0, redraw_image=None,
-                      redraw_image_seeds=None):
+                      redraw_image_seeds=None, max_prompt_chunks=1):
+        check_max_prompt_chunks(max_prompt_chunks)
+        self._check_prompt_embeds(prompt_embeds, negative_prompt_embeds)
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         original_size = original_size or (height, width)
@@ -541,8 +668,11 @@ class DiffSenseiPipeline:
 
         if prompt_embeds is None:
             prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = \
-                self.encode_prompt(prompt, prompt_2, device, num_samples, do_cfg, negative_prompt, negative_prompt_2)
+                self.encode_prompt(prompt, prompt_2, device, num_samples, do_cfg, negative_prompt, negative_prompt_2,
+                                   max_prompt_chunks)
+            prompt_info = dict(self.last_prompt_info)
         else:
+            prompt_info = {"prompt_chunks": -(-int(prompt_embeds.shape[-2]) // 77), "prompt_tokens_dropped": 0}
             f = lambda t: None if t is None else t.to(device, torch.float16)
             prompt_embeds, pooled_prompt_embeds = f(prompt_embeds), f(pooled_prompt_embeds)
             negative_prompt_embeds = f(negative_prompt_embeds) if negative_prompt_embeds is not None \
@@ -574,10 +704,22 @@ class DiffSenseiPipeline:
         neg_dialog, dialog = self.prepare_dialog_bbox(list(dialog_bbox), num_samples)
         to = lambda t: t.to(device)
         return {"n": num_samples, "lat": lat, "time_ids": add_time_ids, "noise_seeds": seeds,
-                "guidance": guidance, "ip_scales": ip_scales, "redraw": redraw,
+                "guidance": guidance, "ip_scales": ip_scales, "redraw": redraw, "prompt_info": prompt_info,
                 "pos": (to(prompt_embeds), to(pooled_prompt_embeds), to(img), to(bbox), to(dialog)),
                 "neg": (to(negative_prompt_embeds), to(negative_pooled_prompt_embeds), to(neg_img), to(neg_bbox),
                         to(neg_dialog))}
+
+    @staticmethod
+    def _check_prompt_embeds(prompt_embeds, negative_prompt_embeds, what: str = "") -> None:
+        """Direct embeddings: [*, L, D] with 1 <= L <= 384, the negative ones of the same length (never padded)."""
+        if prompt_embeds is None:
+            return
+        n = int(prompt_embeds.shape[-2]) if torch.is_tensor(prompt_embeds) and prompt_embeds.dim() >= 2 else 0
+        if not 1 <= n <= MAX_TEXT_TOKENS:
+            raise ValueError(f"{what}`prompt_embeds` must hold 1..{MAX_TEXT_TOKENS} text tokens, got {n}")
+        if negative_prompt_embeds is not None and int(negative_prompt_embeds.shape[-2]) != n:
+            raise ValueError(f"{what}`negative_prompt_embeds` has {int(negative_prompt_embeds.shape[-2])} text tokens, "
+                             f"`prompt_embeds` {n}: both must have the same length (pad the shorter text yourself)")
 
     # ---- the denoising loop over one UNet batch assembled from >= 1 requests of the same shape (reference :310-337)
     @staticmethod
@@ -599,6 +741,14 @@ class DiffSenseiPipeline:
                              f"UNet batch; run them in separate calls (serving: separate buckets)")
         return all(on)
 
+    @staticmethod
+    def _prompt_run_info(infos) -> dict:
+        """`last_run_info` entries of a UNet batch: its chunk count and the prompt ids dropped, summed over its requests."""
+        infos = [i for i in infos if i]
+        dropped = [i["prompt_tokens_dropped"] for i in infos]
+        return {"prompt_chunks": max([i["prompt_chunks"] for i in infos], default=1),
+                "prompt_tokens_dropped": None if any(d is None for d in dropped) else sum(dropped)}
+
     def _denoise(self, conds, num_inference_steps, callback_on_step_end=None) -> Tensor:
         device = self._execution_device
         guidance = [g for c in conds for g in c["guidance"]]          # per panel, in batch order
@@ -611,6 +761,11 @@ class DiffSenseiPipeline:
         num_samples = lat.shape[0]
         H, W = lat.shape[-2], lat.shape[-1]
         aspect_ratio = H / W
+        lengths = sorted({int(c[side][0].shape[1]) for c in conds for side in ("pos", "neg")})
+        if len(lengths) > 1:              # one engine, and one UNet batch, has one text length
+            raise ValueError(f"the requests of one UNet batch have text contexts of {lengths[0]} and {lengths[-1]} tokens "
+                             f"({-(-lengths[0] // 77)} and {-(-lengths[-1] // 77)} prompt chunks): run them in separate "
+                             f"batches (serving: `bucket_key` keeps them apart)")
         cat = lambda side, i: torch.cat([c[side][i] for c in conds], dim=0)
         prompt_embeds, add_text_embeds, img, bbox, dialog = (cat("pos", i) for i in range(5))
         add_time_ids = torch.cat([c["time_ids"] for c in conds], dim=0)
@@ -631,7 +786,7 @@ class DiffSenseiPipeline:
 
         # one plan replay per step
         B = enc.shape[0]
-        eng = self.unet.engine(B, H, W, aspect_ratio)
+        eng = self.unet.engine(B, H, W, aspect_ratio, text_tokens=prompt_embeds.shape[1])
         redraw = [c.get("redraw") for c in conds]
         if any(r is None for r in redraw) and any(r is not None for r in redraw):
             raise ValueError("a UNet batch is all region redraw or all plain sampling, not a mix")
@@ -701,6 +856,7 @@ class DiffSenseiPipeline:
         torch.cuda.current_stream(device).wait_stream(st)
         self.last_run_info = {"graph": graph, "ops_per_step": eng.step_plan.n, "batch": B, "latent_hw": (H, W),
                               "noise_seeds": seeds, "guidance_scales": guidance, "ip_scales": ip_scales}
+        self.last_run_info.update(self._prompt_run_info([c.get("prompt_info") for c in conds]))
         if redraw is not None:
             self.last_run_info["redraw"] = {"t_start": t_start, "steps_run": steps_run,
                                             "repaint_fraction": float(mask.mean())}
@@ -886,12 +1042,13 @@ class DiffSenseiPipeline:
                        "ip_images", "ip_image_embeds", "ip_bbox", "ip_scale", "dialog_bbox", "latents", "prompt_embeds",
                        "negative_prompt_embeds", "pooled_prompt_embeds", "negative_pooled_prompt_embeds", "noise_seeds",
                        "redraw_latents", "redraw_bbox", "redraw_mask", "strength")
+    _REQUEST_KEYWORDS = ("max_prompt_chunks",)     # request fields `_conditioning` takes by keyword (behind `redraw_image`)
     _REQUEST_DEFAULTS = dict(prompt_2=None, height=None, width=None, num_inference_steps=40, guidance_scale=5.0,
                              negative_prompt=None, negative_prompt_2=None, num_samples=1, generator=None, original_size=None,
                              crops_coords_top_left=(0, 0), target_size=None, ip_images=[], ip_image_embeds=None, ip_bbox=[],
                              ip_scale=1.0, dialog_bbox=[], latents=None, prompt_embeds=None, negative_prompt_embeds=None,
                              pooled_prompt_embeds=None, negative_pooled_prompt_embeds=None, noise_seeds=None,
-                             redraw_latents=None, redraw_bbox=None, redraw_mask=None, strength=1.0)
+                             redraw_latents=None, redraw_bbox=None, redraw_mask=None, strength=1.0, max_prompt_chunks=1)
 
     @torch.no_grad()
     def _generate_batch(self, requests: List[dict], output_type: str = "pil") -> List[Any]:
@@ -916,6 +1073,7 @@ class DiffSenseiPipeline:
         if any(rd) != all(rd):
             raise ValueError("generate_batch: a batch is all region redraw (`redraw_latents` / `redraw_image`) or all plain, not a mix")
         images = []
+        self._check_prompt_chunks(requests, "generate_batch")
         for r in requests:                          # every request's redraw fields, before any encoder runs
             h = r.get("height") or self.default_sample_size * self.vae_scale_factor
             w = r.get("width") or self.default_sample_size * self.vae_scale_factor
@@ -935,10 +1093,11 @@ class DiffSenseiPipeline:
         names, defaults = self._REQUEST_FIELDS, self._REQUEST_DEFAULTS
         conds = []
         for r in requests:
-            unknown = set(r) - set(names)
+            unknown = set(r) - set(names) - set(self._REQUEST_KEYWORDS)
             if unknown:
                 raise TypeError(f"generate_batch: unknown request fields {sorted(unknown)}")
-            conds.append(self._conditioning(*[r[n] if n in r else defaults[n] for n in names]))
+            conds.append(self._conditioning(*[r[n] if n in r else defaults[n] for n in names],
+                                            **{n: r[n] for n in self._REQUEST_KEYWORDS if n in r}))
         out = self._denoise(conds, requests[0].get("num_inference_steps", 40))
         images = self._postprocess(out, output_type)
         res, off = [], 0
@@ -993,7 +1152,7 @@ class DiffSenseiPipeline:
             raise ValueError("generate_continuous: slots must be >= 1")
         names = self._REQUEST_FIELDS
         for i, r in enumerate(requests):
-            unknown = set(r) - set(names) - {"redraw_image", "redraw_image_seeds"}
+            unknown = set(r) - set(names) - {"redraw_image", "redraw_image_seeds"} - set(self._REQUEST_KEYWORDS)
             if unknown:
                 raise TypeError(f"generate_continuous: unknown request fields {sorted(unknown)}")
             if int(r.get("num_samples", 1) or 1) > slots:
@@ -1006,6 +1165,7 @@ class DiffSenseiPipeline:
                  for r in requests]
         if any(s != sides[0] for s in sides):
             raise ValueError("generate_continuous: requests mix classifier-free guidance on (guidance_scale > 1) and off (<= 1)")
+        self._check_prompt_chunks(requests, "generate_continuous")
         schedules, images = [], []
         for i, r in enumerate(requests):
             h, w = size(r)
@@ -1026,6 +1186,29 @@ class DiffSenseiPipeline:
             schedules.append(sch)
         plan = plan_continuous([s["steps"] for s in schedules], [int(r.get("num_samples", 1) or 1) for r in requests], slots)
         return plan, schedules, images, sides[0]
+
+    def _text_tokens(self, request: dict) -> int:
+        """The text length of a request's context: that of its `prompt_embeds`, else 77 per prompt chunk."""
+        pe = request.get("prompt_embeds")
+        return int(pe.shape[-2]) if pe is not None else 77 * self.prompt_chunk_count(request)
+
+    def _check_prompt_chunks(self, requests: List[dict], who: str) -> None:
+        """Before any encoder runs: every request's `max_prompt_chunks` and direct embeddings, and that all requests of
+        the UNet batch have one text length (the engine is sized by it)."""
+        lengths = []
+        for i, r in enumerate(requests):
+            what = f"{who}: request {i}: "
+            try:
+                check_max_prompt_chunks(r.get("max_prompt_chunks", 1))
+            except ValueError as e:
+                raise ValueError(what + str(e)) from None
+            self._check_prompt_embeds(r.get("prompt_embeds"), r.get("negative_prompt_embeds"), what)
+            lengths.append(self._text_tokens(r))
+        for i, n in enumerate(lengths):
+            if n != lengths[0]:
+                raise ValueError(f"{who}: request {i} has {-(-n // 77)} prompt chunks ({n} text tokens), request 0 has "
+                                 f"{-(-lengths[0] // 77)} ({lengths[0]}): requests with different chunk counts never share a "
+                                 f"UNet batch (`serving.bucket_key` / `continuous_key` keep them apart)")
 
     def _check_request_fields(self, i: int, r: dict, image: Optional[Tensor], ns: int, h: int, w: int) -> None:
         """The checks `_conditioning` and `_encode_request_images` would make of request i at its admission - by then other
@@ -1075,7 +1258,7 @@ class DiffSenseiPipeline:
         H = (r0.get("height") or self.default_sample_size * self.vae_scale_factor) // self.vae_scale_factor
         W = (r0.get("width") or self.default_sample_size * self.vae_scale_factor) // self.vae_scale_factor
         B = 2 * slots if do_cfg else slots
-        eng = self.unet.engine(B, H, W, H / W)
+        eng = self.unet.engine(B, H, W, H / W, text_tokens=self._text_tokens(requests[0]))
         eng.build_sampler(slots, self.scheduler.kind, do_cfg, redraw=any_redraw, panel_schedules=True)
         if self._stream is None:
             self._stream = torch.cuda.Stream(device=device)
@@ -1105,7 +1288,11 @@ class DiffSenseiPipeline:
 
         def admit_request(r, sl, s):
             req = self._encode_request_images([requests[r]], [images[r]])[0]
-            cond = self._conditioning(*[req[n] if n in req else defaults[n] for n in names])
+            cond = self._conditioning(*[req[n] if n in req else defaults[n] for n in names],
+                                      **{n: req[n] for n in self._REQUEST_KEYWORDS if n in req})
+            if cond["pos"][0].shape[1] + cond["pos"][2].shape[1] != eng.enc.shape[1]:
+                raise ValueError(f"generate_continuous: request {r} has a text context of {cond['pos'][0].shape[1]} tokens, "
+                                 f"the run's engine {eng.text_tokens}")
             sch = schedules[r]
             pos, neg = cond["pos"], cond["neg"]
             if do_cfg:     # a slot's rows in batch order: the negative ones, then the conditional ones (`_denoise`)
@@ -1161,7 +1348,8 @@ class DiffSenseiPipeline:
                               "noise_seeds": [conds[r]["noise_seeds"] for r in range(len(requests))],
                               "guidance_scales": [conds[r]["guidance"] for r in range(len(requests))],
                               "ip_scales": [conds[r]["ip_scales"] for r in range(len(requests))],
-                              "continuous": dict(plan)}
+                              "continuous": dict(plan),
+                              **self._prompt_run_info([conds[r].get("prompt_info") for r in range(len(requests))])}
         images_out = self._postprocess(torch.cat(out, dim=0), output_type)
         res, off = [], 0
         for r in range(len(requests)):

@@ -28,6 +28,10 @@ panel's slot is handed to the next request of the queue while the others keep go
 keeps one UNet batch full instead of falling apart into one small bucket per step count.  The default, False, plans
 the static batches described above.
 
+Long prompts: a request with `max_prompt_chunks` (or direct `prompt_embeds` of another length than 77) carries the chunk
+count it results in as one more key element (`_chunks_key`): the UNet engine is sized by its text length, so requests with
+different chunk counts never share a UNet batch.  Requests without the field are keyed as before.
+
 MLLM-conditioned requests: `BucketBatcher(pipe, agent=agent)` and `submit(..., ip_images=[...], mllm={"input_ids",
 "ids_cmp_mask", "mllm_scale", ...})`.  `run()` first turns every such request into an `ip_image_embeds` request through
 `mllm.mllm_prepass_batch`, in groups of at most `agent.llm.max_sequences` (one decode loop per group: a token step for 16
@@ -47,11 +51,33 @@ def _scale_key(v):
         return tuple(float(x) for x in v)
 
 
-def bucket_key(request: dict, mix_scales: bool = False) -> Tuple:
+def _chunks_key(request: dict, chunks=None) -> Tuple:
+    """(("chunks", k),) for a request that carries `max_prompt_chunks` or direct `prompt_embeds` of another length than 77,
+    () for every other request: its key is what it was.  k is the chunk count the request RESULTS in - the UNet engine is
+    sized by it -: `chunks(request)` (`DiffSenseiPipeline.prompt_chunk_count`, which tokenizes the prompts) or, for direct
+    embeddings, ceil(length / 77).  A text prompt with `max_prompt_chunks` > 1 cannot be counted without the tokenizers."""
+    pe = request.get("prompt_embeds")
+    if "max_prompt_chunks" not in request and (pe is None or int(pe.shape[-2]) == 77):
+        return ()
+    if pe is not None:
+        return (("chunks", -(-int(pe.shape[-2]) // 77)),)
+    mc = request["max_prompt_chunks"]
+    if isinstance(mc, bool) or not isinstance(mc, int) or not 1 <= mc <= 4:
+        raise ValueError(f"`max_prompt_chunks` must be an integer in 1..4, got {mc!r}")
+    if mc == 1:
+        return (("chunks", 1),)
+    if chunks is None:
+        raise ValueError("the chunk count of a text prompt with max_prompt_chunks > 1 needs the tokenizers: pass "
+                         "chunks=pipe.prompt_chunk_count")
+    return (("chunks", int(chunks(request))),)
+
+
+def bucket_key(request: dict, mix_scales: bool = False, chunks=None) -> Tuple:
     """What must agree for two requests to share a UNet batch.  mix_scales: (height, width, steps, guidance > 1) - the
     sliders travel per panel, only classifier-free guidance on / off is a property of the batch.  A request whose own
     guidance values lie on both sides of 1 fits no batch and is a ValueError here, so that it cannot take the requests
-    bucketed with it down (`BucketBatcher.submit` checks every request this way)."""
+    bucketed with it down (`BucketBatcher.submit` checks every request this way).  `chunks`: see `_chunks_key` - requests
+    whose prompts result in different chunk counts never share a batch."""
     g = _scale_key(request.get("guidance_scale", 5.0))
     # a region-redraw request (`redraw_latents` or `redraw_image`) runs a shortened schedule with another step kernel: it shares a batch
     # only with redraws of the same strength.  A plain request's key is what it was.
@@ -61,6 +87,7 @@ def bucket_key(request: dict, mix_scales: bool = False) -> Tuple:
     # element, so every other key is what it was; {} (no adapter) is a state of its own, distinct from "whatever is set"
     if "lora" in request:
         redraw = redraw + (("lora", tuple(sorted((str(k), float(v)) for k, v in dict(request["lora"] or {}).items()))),)
+    redraw = redraw + _chunks_key(request, chunks)
     if mix_scales:
         on = {x > 1 for x in (g if isinstance(g, tuple) else (g,))}
         if len(on) != 1:
@@ -71,7 +98,7 @@ def bucket_key(request: dict, mix_scales: bool = False) -> Tuple:
 
 
 def plan_batches(requests: List[dict], max_panels: int, max_pixels: Optional[int] = None,
-                 mix_scales: bool = False) -> List[List[int]]:
+                 mix_scales: bool = False, chunks=None) -> List[List[int]]:
     """Indices of `requests` grouped into batches: same bucket, at most `max_panels` panels (sum of num_samples) per
     batch - and at most `max_pixels` output pixels if given, so small resolutions get proportionally larger batches (a
     single request above the pixel cap but within `max_panels` runs alone; only `num_samples > max_panels` is an error) -
@@ -80,7 +107,7 @@ def plan_batches(requests: List[dict], max_panels: int, max_pixels: Optional[int
         raise ValueError("max_panels must be >= 1")
     buckets: Dict[Tuple, List[int]] = {}
     for i, r in enumerate(requests):
-        buckets.setdefault(bucket_key(r, mix_scales), []).append(i)
+        buckets.setdefault(bucket_key(r, mix_scales, chunks), []).append(i)
     order = sorted(buckets, key=lambda k: -((k[0] or 0) * (k[1] or 0)))
     batches: List[List[int]] = []
     for k in order:
@@ -151,9 +178,10 @@ def plan_continuous(steps_run: List[int], panels: List[int], slots: int) -> dict
             "finish": finish}
 
 
-def continuous_key(request: dict) -> Tuple:
-    """What must agree for requests to share a continuous-batching run: (height, width, guidance > 1, lora state).  Step
-    counts, strengths, plain vs redraw and both sliders are per panel there."""
+def continuous_key(request: dict, chunks=None) -> Tuple:
+    """What must agree for requests to share a continuous-batching run: (height, width, guidance > 1, lora state) and, for
+    a request with `max_prompt_chunks` or long `prompt_embeds`, its chunk count (`_chunks_key`).  Step counts, strengths,
+    plain vs redraw and both sliders are per panel there."""
     g = _scale_key(request.get("guidance_scale", 5.0))
     on = {x > 1 for x in (g if isinstance(g, tuple) else (g,))}
     if len(on) != 1:
@@ -161,7 +189,7 @@ def continuous_key(request: dict) -> Tuple:
     lora = None
     if "lora" in request:
         lora = tuple(sorted((str(k), float(v)) for k, v in dict(request["lora"] or {}).items()))
-    return (request.get("height"), request.get("width"), on.pop(), lora)
+    return (request.get("height"), request.get("width"), on.pop(), lora) + _chunks_key(request, chunks)
 
 
 class BucketBatcher:
@@ -185,12 +213,13 @@ class BucketBatcher:
         self.last_prepass: List[List[int]] = []   # tickets of each MLLM pre-pass batch of the last run()
         self.continuous = continuous         # slots refilled in flight instead of one static batch per bucket
         self.last_slots: List[int] = []      # continuous: the slot count of each group of the last run()
+        self._chunks = getattr(pipe, "prompt_chunk_count", None)   # resolves `max_prompt_chunks` to a chunk count (tokenizers)
 
     def submit(self, **request) -> int:
         """Queue one request (keyword arguments of `DiffSenseiPipeline.__call__`, without `output_type`); returns its ticket."""
         if "output_type" in request:
             raise TypeError("output_type is chosen per run(), not per request")
-        bucket_key(request, True)            # a request no batch can hold is refused here, not when its batch runs
+        bucket_key(request, True, self._chunks)   # a request no batch can hold is refused here, not when its batch runs
         m = request.get("mllm")
         if m is not None:
             if self.agent is None:
@@ -248,7 +277,7 @@ class BucketBatcher:
         reqs = self._resolve_mllm(reqs)
         if self.continuous:
             return self._run_continuous(reqs, output_type)
-        self.last_plan = plan_batches(reqs, self.max_panels, self.max_pixels, self.mix_scales)
+        self.last_plan = plan_batches(reqs, self.max_panels, self.max_pixels, self.mix_scales, self._chunks)
         results: List[Any] = [None] * len(reqs)
         import contextlib
         # requests with `lora`: a batch leaves its adapters set, so consecutive batches of one state switch once, and the state
@@ -264,7 +293,7 @@ class BucketBatcher:
     def _run_continuous(self, reqs: List[dict], output_type: str) -> List[Any]:
         groups: Dict[Tuple, List[int]] = {}
         for i, r in enumerate(reqs):
-            groups.setdefault(continuous_key(r), []).append(i)
+            groups.setdefault(continuous_key(r, self._chunks), []).append(i)
         order = sorted(groups, key=lambda k: -((k[0] or 0) * (k[1] or 0)))
         self.last_plan, self.last_slots = [], []
         for k in order:

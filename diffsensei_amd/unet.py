@@ -266,11 +266,15 @@ class UNetMangaModel:
     # is never evicted.
     engine_cache_bytes = int(float(os.environ.get("DIFFSENSEI_ENGINE_CACHE_GB", "64")) * (1 << 30))
 
-    def engine(self, batch: int, height: int, width: int, aspect_ratio: Optional[float] = None) -> UNetEngine:
-        key = (batch, height, width, None if aspect_ratio is None else round(float(aspect_ratio), 6), self.attention_dtype)
+    def engine(self, batch: int, height: int, width: int, aspect_ratio: Optional[float] = None,
+               text_tokens: Optional[int] = None) -> UNetEngine:
+        """text_tokens: the text length of encoder_hidden_states (None: cfg.num_text_tokens, 77) - part of the cache key: one
+        engine has one text length (1..384; above 96 its attn2 ops are the long-prompt kernel's)."""
+        n_txt = int(self.config.num_text_tokens if text_tokens is None else text_tokens)
+        key = (batch, height, width, None if aspect_ratio is None else round(float(aspect_ratio), 6), self.attention_dtype, n_txt)
         eng = self._engines.pop(key, None)
         if eng is None:
-            eng = UNetEngine(self.packed(), batch, height, width, aspect_ratio, attention=self.attention_dtype)
+            eng = UNetEngine(self.packed(), batch, height, width, aspect_ratio, attention=self.attention_dtype, text_tokens=n_txt)
         self._engines[key] = eng                      # dict order = recency (most recent last)
         total = sum(e.nbytes() for e in self._engines.values())
         for k in list(self._engines):
@@ -302,7 +306,7 @@ class UNetMangaModel:
             raise ValueError("added_cond_kwargs={'text_embeds':..., 'time_ids':...} is required")
         B, Cin, H, W = sample.shape
         ar = cross_attention_kwargs.get("aspect_ratio", H / W)
-        eng = self.engine(B, H, W, ar)
+        eng = self.engine(B, H, W, ar, text_tokens=encoder_hidden_states.shape[1] - self.config.num_ip_tokens)
         boxes = None if dialog_bbox is None else dialog_pixel_boxes(dialog_bbox, H, W)
         eng.set_request(encoder_hidden_states, added_cond_kwargs["text_embeds"], added_cond_kwargs["time_ids"],
                         cross_attention_kwargs["bbox"], boxes, self.ip_scale())

@@ -296,6 +296,24 @@ int ds_masked_ip_attn_rows_f16(const void* q, int64_t ldq, const void* kt, const
                                const void* vti, const float* bbox, void* o, int64_t ldo, int B, int heads, int N, int Lt,
                                int Li, int n_dummy, int tok_per_ip, int max_ips, int mask_h, int mask_w, float qk_scale,
                                const float* ip_scale_rows_dev, int64_t ldk, int64_t sk, int64_t sv, void* stream);
+/* Long prompts: the same core with 1 <= Lt <= 384 text keys in text_panels = ceil(Lt / 96) panels of 96 rows (at most 4) -
+ * kt [B, 96 text_panels, C] with row / batch strides ldkt / skt, vtt [B, C, 96 text_panels] (rows dense) with batch stride svt
+ * (elements; 0 = dense).  ki / vti stay one 96-row panel with ldk / sk / sv.  The text softmax runs over all Lt keys (online
+ * over the panels: fp32 scores, exp(s - running max) packed to fp16 for the P V product, fp32 accumulation, one division by
+ * the row sum at the end); keys >= Lt get probability exactly 0 whatever finite values their rows hold.  The IP side, the
+ * output and ip_scale_dev are ds_masked_ip_attn_f16's.  Lt > 384, Lt <= 0, a panel count that does not match Lt and strides
+ * that are no multiples of 8 are refused before any launch. */
+int ds_masked_ip_attn_long_f16(const void* q, int64_t ldq, const void* kt, const void* vtt, const void* ki, const void* vti,
+                               const float* bbox, void* o, int64_t ldo, int B, int heads, int N, int Lt, int text_panels, int Li,
+                               int n_dummy, int tok_per_ip, int max_ips, int mask_h, int mask_w, float qk_scale, float ip_scale,
+                               const float* ip_scale_dev, int64_t ldkt, int64_t skt, int64_t svt, int64_t ldk, int64_t sk,
+                               int64_t sv, void* stream);
+/* ds_masked_ip_attn_long_f16 with one IP scale per batch row (see ds_masked_ip_attn_rows_f16) */
+int ds_masked_ip_attn_long_rows_f16(const void* q, int64_t ldq, const void* kt, const void* vtt, const void* ki, const void* vti,
+                                    const float* bbox, void* o, int64_t ldo, int B, int heads, int N, int Lt, int text_panels,
+                                    int Li, int n_dummy, int tok_per_ip, int max_ips, int mask_h, int mask_w, float qk_scale,
+                                    const float* ip_scale_rows_dev, int64_t ldkt, int64_t skt, int64_t svt, int64_t ldk,
+                                    int64_t sk, int64_t sv, void* stream);
 /* debug/test hook: bit k of flags[b*N+i] = token i inside box k (the reference's inside_bbox_mask) */
 int ds_ip_region_flags(const float* bbox, uint8_t* flags, int B, int N, int max_ips, int mask_h, int mask_w,
                        void* stream);
@@ -649,6 +667,8 @@ enum ds_opcode {
     DS_OP_IP_ATTN = 6,       /* p: q, kt, vtt, ki, vti, bbox, o, ip_scale_dev   l: ldq ldo ldk sk sv
                                 i: B heads N Lt Li n_dummy tok_per_ip max_ips mask_h mask_w; i[10] = 1: ip_scale_dev is a
                                    [B] vector, one scale per batch row (ds_masked_ip_attn_rows_f16); 0: one device scalar
+                                   i[11] = T > 1: long prompt (ds_masked_ip_attn_long_f16) - kt / vtt are T panels of 96 rows
+                                   with the strides l[5] ldkt, l[6] skt, l[7] svt; 0 or 1: one text panel sharing ldk sk sv
                                 f: qk_scale ip_scale */
     DS_OP_CONV_IN = 7,       /* p: x, w, bias, boxes, demb, y             i: B H W Cin Cout ndialog */
     DS_OP_CONV_OUT = 8,      /* p: x, w, bias, y                          i: B H W Cin Cout */
