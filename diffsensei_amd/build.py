@@ -19,7 +19,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libdiffsensei_hip.so")
 SOURCES = ["gemm.hip", "gemm_pp.hip", "gemm_t160.hip", "gemm_g320.hip", "conv_halo.hip", "vae.hip", "norm.hip", "attention.hip", "attention_sp.hip", "elementwise.hip", "llm.hip", "preprocess.hip",
            "lora.hip", "capi.hip"]
-HEADERS = ["ds_common.h", "ds_kernels.h", "ds_epilogue.h", "ds_philox.h", os.path.join("..", "..", "include", "diffsensei_hip.h")]
+HEADERS = ["ds_common.h", "ds_kernels.h", "ds_epilogue.h", "ds_attention.h", "ds_philox.h", os.path.join("..", "..", "include", "diffsensei_hip.h")]
 # -ffast-math spelled out WITHOUT -fassociative-math and -ffinite-math-only (round 3): with reassociation
 # allowed, two kernel variants that share a source expression could be rounded differently at the optimizer's whim, and the
 # suite's "bit-identical between variants" guarantees (ping-pong vs register-staged GEMM, 8x16 vs 16x16 conv blocks, flash

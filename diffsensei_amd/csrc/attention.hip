@@ -17,7 +17,7 @@
 // key-contiguous ("V transposed", produced that way by the projection GEMM) so its A fragments are
 // plain 8-byte LDS reads.  O^T keeps the query row on the lane as well, so the online-softmax rescale is
 // one multiply per accumulator register.
-#include "ds_common.h"
+#include "ds_attention.h"
 #include "ds_kernels.h"
 
 static thread_local int g_attn_variant = 0;  // 0 auto, 1 force 32 query rows per wave (QB = 1), 2 force 64 rows per wave (QB = 2)
@@ -28,23 +28,6 @@ static thread_local int g_ip_variant = 0;  // ip_attn: 0 auto, 1 force the 4-wav
 void ds_ip_attn_set_variant(int v) { g_ip_variant = v; }
 
 namespace {
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float NEG_BIG = -1.0e30f;
-
-// 2^x as ONE v_exp_f32.  exp2f() adds a denormal-range rescue (compare, select, ldexp: five more VALU slots per score);
-// softmax arguments are <= 0 and anything below 2^-126 may flush to zero.  The softmax of the flash kernels is VALU
-// bound (32 scores per lane per 16 MFMAs), so every slot per score shows up in the kernel time.
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-__device__ __forceinline__ h8 pack8(const f32x16& s, int base) {
-    h8 o;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = (half_t)s[base + e];
-    return o;
-}
 
 // ------------------------------------------------------------------------------------------------
 // Flash self-attention.  grid = (ceil(Nq/(128*QB)), B*heads), 256 threads, KV tile 64 keys, LDS 32 KiB.
@@ -170,10 +153,11 @@ __global__ __launch_bounds__(256, 2) void self_attn_kernel(const SelfAttnParams 
             const bool moved = __builtin_amdgcn_ballot_w64(m_new != m_run[qb]) != 0;  // wave-uniform
             m_run[qb] = m_new;
             const float mc = m_new * c;
-            // two scores per VALU slot where the ISA allows it: v_pk_fma_f32 for the scale-and-shift, v_pk_add_f32
-            // for the row sum (the exponential itself has no packed form)
             f32x2 psum2 = {0.f, 0.f};
             const f32x2 c2 = {c, c}, mc2 = {-mc, -mc};
+            // = exp2_sum_block<16>(st[qb][kb], c2, mc2, psum2) (ds_attention.h), in this kernel's own text: through the shared
+            // function the <2> instantiation's row-sum adds come out with their operands exchanged, and the kernel is held to
+            // the parent's assembly, not to a timing (profiles/attention_refactor_bisect.txt)
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -220,10 +204,11 @@ __global__ __launch_bounds__(256, 2) void self_attn_kernel(const SelfAttnParams 
         const float l = l_part[qb] + __shfl_xor(l_part[qb], 32, 64);
         const float inv = 1.0f / l;
         const int qrow = q0 + qb * 32 + l31;
-        // 16-byte stores (round 6; the store shape was measured on ip_attn_kernel below): a lane holds columns 8g + 4 lhi + {0..3}
-        // of its query row, lane ^ 32 the other four of every group of eight; one v_permlane32_swap per dword and group pair
-        // leaves the lower lane with columns 16j .. 16j+7, the upper one with 16j+8 .. 16j+15.  The swaps run on every lane
-        // (clamped row address past Nq); only the stores are masked.
+        // 16-byte rows, O / l on the way; the row address is clamped, only the stores are masked.
+        // = store_rows16<true>(op, row_ok, ot[qb], inv) (ds_attention.h), in this kernel's own text: through the shared function
+        // the multiplies' operands come out exchanged, and with both shared pieces in, three of the kernel's six timings lay
+        // 0.1 - 0.4 % above the parent's margin (profiles/attention_refactor_bisect.txt); with this text and the exp2 pass above
+        // the kernel's assembly is the parent's.
         half_t* op = p.o + (long)b * p.so + (long)min(qrow, p.Nq - 1) * p.ldo + h * 64 + lhi * 8;
         const bool row_ok = qrow < p.Nq;
 #pragma unroll
@@ -234,15 +219,15 @@ __global__ __launch_bounds__(256, 2) void self_attn_kernel(const SelfAttnParams 
                 h4 o;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) o[e] = (half_t)(ot[qb][db][4 * g + e] * inv);
-                const u32x2_t t2 = __builtin_bit_cast(u32x2_t, o);
+                const u32x2 t2 = __builtin_bit_cast(u32x2, o);
                 og[g][0] = t2[0], og[g][1] = t2[1];
             }
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(og[2 * j][0]), "+v"(og[2 * j + 1][0]));
-                asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(og[2 * j][1]), "+v"(og[2 * j + 1][1]));
-                const u32x4_t v = {og[2 * j][0], og[2 * j][1], og[2 * j + 1][0], og[2 * j + 1][1]};
-                if (row_ok) *reinterpret_cast<u32x4_t*>(op + db * 32 + j * 16) = v;
+                swap32(og[2 * j][0], og[2 * j + 1][0]);
+                swap32(og[2 * j][1], og[2 * j + 1][1]);
+                const u32x4 v = {og[2 * j][0], og[2 * j][1], og[2 * j + 1][0], og[2 * j + 1][1]};
+                if (row_ok) *reinterpret_cast<u32x4*>(op + db * 32 + j * 16) = v;
             }
         }
     }
@@ -268,15 +253,23 @@ static float linspace_step(int n) {
     volatile double m = (double)(n - 1);   // volatile: the quotient is a real division whatever the math flags allow
     return (float)(1.0 / m);
 }
-// bit k set <=> token inside box k
+// the grid point of query token idx: for the flags kernel and the fused kernels (`ip_open_set`)
+__device__ __forceinline__ void token_xy(int idx, int mh, int mw, float step_x, float step_y, float& x, float& y) {
+    const int yi = idx / mw, xi = idx - yi * mw;
+    x = linspace01(xi, mw, step_x), y = linspace01(yi, mh, step_y);
+}
+// bit k set <=> token inside box k, edges included.  The box test is written TWICE: here with the boxes in memory, short-circuited
+// (a rolled loop, 10 VGPRs), and in `ip_open_set` with the boxes in registers and no short circuit.  One body with the
+// unconditional form unrolls this loop and costs this kernel 14 VGPRs (profiles/attention_refactor_resource_usage.txt): a
+// change to the predicate goes to both; tests/test_gpu_attention_bits.py holds either to the recorded bits.
 __device__ __forceinline__ unsigned region_flags(const float* __restrict__ bbox_b, int max_ips, int idx, int mh,
                                                  int mw, float step_x, float step_y) {
-    const int yi = idx / mw, xi = idx - yi * mw;
-    const float x = linspace01(xi, mw, step_x), y = linspace01(yi, mh, step_y);
+    float x, y;
+    token_xy(idx, mh, mw, step_x, step_y, x, y);
     unsigned f = 0;
     for (int k = 0; k < max_ips; ++k) {
         const float x1 = bbox_b[4 * k + 0], y1 = bbox_b[4 * k + 1], x2 = bbox_b[4 * k + 2], y2 = bbox_b[4 * k + 3];
-        if (x >= x1 && x <= x2 && y >= y1 && y <= y2) f |= 1u << k;
+        if (x >= x1 && x <= x2 && y >= y1 && y <= y2) f |= 1u << k;   // = ip_open_set's test
     }
     return f;
 }
@@ -313,13 +306,111 @@ constexpr int VSTR = 200;  // bytes per V^T row in LDS (96 keys * 2 B + 8 pad): 
 // rows as well (16 bytes per lane, 4 instructions instead of 8).  Same arithmetic in the same order: bit-identical to RING = false.
 constexpr int IP_PANEL_BYTES = 2 * LP * 128 + 2 * 64 * VSTR;   // sKt | sKi | sVt | sVi
 constexpr int IP_SLOT = 4096;                                  // one wave's 32 x 64 f16 tile
-#ifndef IP_DIRECT_STORE
-#define IP_DIRECT_STORE 1
-#endif
-template <int V>
-struct IPC {
-    static constexpr int value = V;
+
+// ---- what ip_attn_kernel and ip_attn_long_kernel share: the Q load, the panel staging, the boxes and the IP side's key set ----
+
+// Q fragments (B operand of S^T) of query tile `tile` (ROWS rows per block and tile): lane holds Q[q][kk*16 + lhi*8 .. +7],
+// row index clamped to N - 1
+template <int ROWS>
+__device__ __forceinline__ void ip_load_q(const IPAttnParams& p, int b, int h, int tile, int wave, int l31, int lhi, h8 (&qn)[4]) {
+    const int qrow = min(tile * ROWS + wave * 32 + l31, p.N - 1);
+    const half_t* qp = p.q + ((long)b * p.N + qrow) * p.ldq + h * 64 + lhi * 8;
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) qn[kk] = *reinterpret_cast<const h8*>(qp + kk * 16);
+}
+
+// One K / V^T panel pair of a (batch, head), global -> registers -> LDS, by NW waves: LP * 8 == 64 * 12 == 768 sixteen-byte
+// pieces of each; a thread's piece j is number tid + j * NW * 64 (ITER pieces per thread, the last ones past the panel: their
+// request re-reads the last piece, their write is skipped).  K [LP, 64] rows at stride ldk -> 128-byte LDS rows, chunk-swizzled;
+// V^T [64, LP] rows at stride ldv -> LDS rows of VSTR bytes.  One piece at a time, request and write apart: the ORDER belongs to
+// the kernel - ip_attn_kernel requests every piece of its four panels before its first write, ip_attn_long_kernel stages panel
+// after panel.
+template <int NW>
+struct IPStage {
+    static constexpr int ITER = (LP * 8 + NW * 64 - 1) / (NW * 64);
+    static __device__ __forceinline__ h8 request_k(const half_t* kp, long ldk, int tid, int j) {
+        const int id = min(tid + j * NW * 64, LP * 8 - 1);
+        const int row = id >> 3, c = id & 7;
+        return *reinterpret_cast<const h8*>(kp + (long)row * ldk + c * 8);
+    }
+    static __device__ __forceinline__ h8 request_v(const half_t* vp, long ldv, int tid, int j) {
+        const int id = min(tid + j * NW * 64, LP * 8 - 1);
+        const int vrow = id / 12, vc = id - vrow * 12;
+        return *reinterpret_cast<const h8*>(vp + (long)vrow * ldv + vc * 8);
+    }
+    static __device__ __forceinline__ bool in_panel(int tid, int j) { return tid + j * NW * 64 < LP * 8; }
+    static __device__ __forceinline__ void write_k(char* dK, int tid, int j, const h8 r) {
+        const int id = tid + j * NW * 64;
+        const int row = id >> 3, c = id & 7;
+        *reinterpret_cast<h8*>(&dK[row * 128 + swz(row, c)]) = r;
+    }
+    static __device__ __forceinline__ void write_v(char* dV, int tid, int j, const h8 a) {
+        const int id = tid + j * NW * 64;
+        const int vrow = id / 12, vc = id - vrow * 12;
+        h4 lo, hi;
+        lo[0] = a[0]; lo[1] = a[1]; lo[2] = a[2]; lo[3] = a[3];
+        hi[0] = a[4]; hi[1] = a[5]; hi[2] = a[6]; hi[3] = a[7];
+        *reinterpret_cast<h4*>(&dV[vrow * VSTR + vc * 16]) = lo;
+        *reinterpret_cast<h4*>(&dV[vrow * VSTR + vc * 16 + 8]) = hi;
+    }
 };
+
+// The character boxes of this image, fetched ONCE per block: lane k reads box k (requested ahead of the panel loads) and the
+// eight (x1, y1, x2, y2) are broadcast into scalar registers behind the staging barrier.  (Read inside the tile loop, the
+// short-circuited test became a chain of two dependent global loads per box, each behind an s_waitcnt vmcnt(0) that also
+// waited for the next tile's Q rows requested just before it - every query tile stalled for whole memory round trips.)
+// Boxes >= max_ips: x1 = 2, which no grid point (x in [0, 1]) satisfies.
+__device__ __forceinline__ void ip_request_box(const IPAttnParams& p, int b, int lane, float (&bv)[4]) {
+    bv[0] = 2.f, bv[1] = 2.f, bv[2] = -1.f, bv[3] = -1.f;
+    const float* bbox_b = p.bbox + (long)b * p.max_ips * 4;
+    if (lane < p.max_ips) {
+#pragma unroll
+        for (int c4 = 0; c4 < 4; ++c4) bv[c4] = bbox_b[4 * lane + c4];
+    }
+}
+__device__ __forceinline__ void ip_broadcast_boxes(const float (&bv)[4], float (&box)[8][4]) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+#pragma unroll
+        for (int c4 = 0; c4 < 4; ++c4) box[k][c4] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bv[c4]), k));
+}
+// The IP scale, ONCE per block as well: the batch's device scalar (ip_scale_rows = 0) or element b of a [B] vector
+// (ip_scale_rows = 1), a scalar load at a block-uniform index.  Called behind the box broadcast: hoisted up to the box request,
+// or loaded unconditionally from a dummy address with a select behind it, it cost one more VGPR for its spilled SGPR on both
+// four-wave instantiations.
+__device__ __forceinline__ float ip_read_scale(const IPAttnParams& p, int b) {
+    return p.ip_scale_ptr ? p.ip_scale_ptr[b * p.ip_scale_rows] : p.ip_scale;
+}
+
+// Query token qidx against the eight boxes (`region_flags()` with the boxes in registers) -> the 96-bit "attendable IP key" set
+// of its row: dummy keys [0, n_dummy) iff the token lies in NO box, character k's keys [n_dummy + k*tpi, +tpi) iff it lies in box
+// k (reference :155-163) -> which 32-key blocks of the IP panel this WAVE needs.  A masked key's probability is exactly 0
+// (exp(-10000 + ...) underflows in fp32 as it does in the reference's fp16), so a block in which NO query row of the wave has an
+// attendable key contributes nothing and is skipped whole (wave-uniform): the unconditional half of the CFG batch only ever
+// attends the dummy tokens, a panel with two characters never touches the fourth character's block.  Every row keeps at least
+// one attendable key in an active block as long as dummy tokens exist (no box -> dummies).
+__device__ __forceinline__ void ip_open_set(const IPAttnParams& p, const float (&box)[8][4], int qidx, unsigned (&open_ip)[3],
+                                            bool (&act_ip)[3]) {
+    unsigned inside = 0;  // bit k set <=> the token lies in box k
+    float x, y;
+    token_xy(qidx, p.mask_h, p.mask_w, p.step_x, p.step_y, x, y);
+#pragma unroll
+    for (int k = 0; k < 8; ++k)   // = region_flags()'s test
+        inside |= (unsigned)((x >= box[k][0]) & (x <= box[k][2]) & (y >= box[k][1]) & (y <= box[k][3])) << k;
+    open_ip[0] = open_ip[1] = open_ip[2] = 0u;
+    auto set_range = [&](int lo, int hi) {  // bits [lo, hi) of the 96-bit set
+#pragma unroll
+        for (int w = 0; w < 3; ++w) {
+            const int a = max(lo - 32 * w, 0), e = min(hi - 32 * w, 32);
+            if (e > a) open_ip[w] |= (e - a == 32 ? 0xffffffffu : ((1u << (e - a)) - 1u)) << a;
+        }
+    };
+    if (inside == 0) set_range(0, p.n_dummy);
+    for (int k = 0; k < p.max_ips; ++k)
+        if ((inside >> k) & 1u) set_range(p.n_dummy + k * p.tok_per_ip, p.n_dummy + (k + 1) * p.tok_per_ip);
+#pragma unroll
+    for (int kb = 0; kb < 3; ++kb) act_ip[kb] = p.n_dummy == 0 || __builtin_amdgcn_ballot_w64(open_ip[kb] != 0u) != 0;
+}
 
 // T16 (round 6): both key counts lie in (64, 80] (the model's 77 text / 80 image keys), so keys 80..95 of the third 32-key block -
 // registers 8..15 of its score block on every lane - are padding for every row: their scale / maximum / exponential /
@@ -343,12 +434,7 @@ __global__ __launch_bounds__(NW * 64, 2) void ip_attn_kernel(const IPAttnParams 
     // Q fragments (B operand of S^T) are fetched one query tile ahead: the kernel runs two waves per SIMD, too few to
     // hide a global-load round trip inside the tile loop, and the first tile's rows are requested before the panels.
     h8 qn[4];
-    auto load_q = [&](int it) {
-        const int qrow = min((int)(blockIdx.x * qt + it) * ROWS + wave * 32 + l31, p.N - 1);
-        const half_t* qp = p.q + ((long)b * p.N + qrow) * p.ldq + h * 64 + lhi * 8;
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) qn[kk] = *reinterpret_cast<const h8*>(qp + kk * 16);
-    };
+    auto load_q = [&](int it) { ip_load_q<ROWS>(p, b, h, (int)(blockIdx.x * qt + it), wave, l31, lhi, qn); };
     // RING: tile `it` of this wave -> slot it % 3, four 1-KiB LDS-DMA pieces of 8 whole rows each; LDS row r keeps its 16-byte
     // chunk c at position c ^ ((r >> 1) & 7) (the swizzle is applied to the lane's SOURCE chunk, the DMA destination is linear)
     auto dma_q = [&](int it) {
@@ -373,75 +459,41 @@ __global__ __launch_bounds__(NW * 64, 2) void ip_attn_kernel(const IPAttnParams 
     }
     // (the boxes are requested here, ahead of the panel loads, and broadcast behind the barrier below: one more round trip that
     // used to sit on its own between the staging and the first tile)
-    float bv[4] = {2.f, 2.f, -1.f, -1.f};
-    {
-        const float* bbox_b = p.bbox + (long)b * p.max_ips * 4;
-        if (lane < p.max_ips) {
-#pragma unroll
-            for (int c4 = 0; c4 < 4; ++c4) bv[c4] = bbox_b[4 * lane + c4];
-        }
-    }
+    float bv[4];
+    ip_request_box(p, b, lane, bv);
     // ---- stage the four panels once.  All 4 x ITER global loads are REQUESTED first, then the LDS writes (round 6): as two
     // rolled loops of {load, load, wait, write, write} the staging cost a block 6 memory round trips back to back - fitted from the
     // grid-rule sweep of profiles/r06_ipattn_microbench.txt (time = rounds x (S + tiles T)): S = 7-9 us per block against
     // T = 4 us per query tile, i.e. a fifth of the kernel at UNet batch 64 and most of it at batch 2 (one tile per block).
     {
-        constexpr int ITER = (LP * 8 + NW * 64 - 1) / (NW * 64);   // LP * 8 == 64 * 12 == 768 sixteen-byte pieces per panel
+        using Stage = IPStage<NW>;
         const half_t* ktp = p.kt + (long)b * p.sk + h * 64;
         const half_t* kip = p.ki + (long)b * p.sk + h * 64;
         const half_t* vtp = p.vtt + (long)b * p.sv + (long)(h * 64) * LP;
         const half_t* vip = p.vti + (long)b * p.sv + (long)(h * 64) * LP;
-        h8 rk[ITER][2], rv[ITER][2];
+        h8 rk[Stage::ITER][2], rv[Stage::ITER][2];
 #pragma unroll
-        for (int j = 0; j < ITER; ++j) {
-            const int id = min(tid + j * NW * 64, LP * 8 - 1);
-            const int row = id >> 3, c = id & 7;
-            rk[j][0] = *reinterpret_cast<const h8*>(ktp + (long)row * p.ldk + c * 8);
-            rk[j][1] = *reinterpret_cast<const h8*>(kip + (long)row * p.ldk + c * 8);
-            const int vrow = id / 12, vc = id - vrow * 12;
-            rv[j][0] = *reinterpret_cast<const h8*>(vtp + (long)vrow * LP + vc * 8);
-            rv[j][1] = *reinterpret_cast<const h8*>(vip + (long)vrow * LP + vc * 8);
+        for (int j = 0; j < Stage::ITER; ++j) {
+            rk[j][0] = Stage::request_k(ktp, p.ldk, tid, j);
+            rk[j][1] = Stage::request_k(kip, p.ldk, tid, j);
+            rv[j][0] = Stage::request_v(vtp, LP, tid, j);
+            rv[j][1] = Stage::request_v(vip, LP, tid, j);
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int j = 0; j < ITER; ++j) {
-            const int id = tid + j * NW * 64;
-            if (id >= LP * 8) continue;
-            const int row = id >> 3, c = id & 7;
-            *reinterpret_cast<h8*>(&sKt[row * 128 + swz(row, c)]) = rk[j][0];
-            *reinterpret_cast<h8*>(&sKi[row * 128 + swz(row, c)]) = rk[j][1];
-            const int vrow = id / 12, vc = id - vrow * 12;
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                const h8 a = rv[j][t];
-                char* const sV = t ? sVi : sVt;
-                h4 lo, hi;
-                lo[0] = a[0]; lo[1] = a[1]; lo[2] = a[2]; lo[3] = a[3];
-                hi[0] = a[4]; hi[1] = a[5]; hi[2] = a[6]; hi[3] = a[7];
-                *reinterpret_cast<h4*>(&sV[vrow * VSTR + vc * 16]) = lo;
-                *reinterpret_cast<h4*>(&sV[vrow * VSTR + vc * 16 + 8]) = hi;
-            }
+        for (int j = 0; j < Stage::ITER; ++j) {
+            if (!Stage::in_panel(tid, j)) continue;
+            Stage::write_k(sKt, tid, j, rk[j][0]);
+            Stage::write_k(sKi, tid, j, rk[j][1]);
+            Stage::write_v(sVt, tid, j, rv[j][0]);
+            Stage::write_v(sVi, tid, j, rv[j][1]);
         }
     }
     __syncthreads();
 
-    // The character boxes of this image, fetched ONCE per block: lane k reads box k and the eight (x1, y1, x2, y2) are
-    // broadcast into scalar registers.  (Read inside the tile loop, the short-circuited test became a chain of two
-    // dependent global loads per box, each behind an s_waitcnt vmcnt(0) that also waited for the next tile's Q rows
-    // requested just before it - every query tile stalled for whole memory round trips.)  Boxes >= max_ips: x1 = 2,
-    // which no grid point (x in [0, 1]) satisfies.
     float box[8][4];
-    {
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-#pragma unroll
-            for (int c4 = 0; c4 < 4; ++c4) box[k][c4] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bv[c4]), k));
-    }
-    // The IP scale, ONCE per block as well: the batch's device scalar (ip_scale_rows = 0) or element b of a [B] vector
-    // (ip_scale_rows = 1), a scalar load at a block-uniform index.  (Hoisted up to the box request above, or loaded
-    // unconditionally from a dummy address with a select behind it, it cost one more VGPR for its spilled SGPR on both
-    // four-wave instantiations; here every instantiation keeps the register counts it had with the single scalar.)
-    const float ip_scale = p.ip_scale_ptr ? p.ip_scale_ptr[b * p.ip_scale_rows] : p.ip_scale;
+    ip_broadcast_boxes(bv, box);
+    const float ip_scale = ip_read_scale(p, b);
     for (int it = 0; it < qt; ++it) {
         const int q0 = (blockIdx.x * qt + it) * ROWS + wave * 32;
         if constexpr (RING) {
@@ -473,29 +525,9 @@ __global__ __launch_bounds__(NW * 64, 2) void ip_attn_kernel(const IPAttnParams 
             for (int kk = 0; kk < 4; ++kk) qf[kk] = qn[kk];
             if (it + 1 < qt) load_q(it + 1);  // next tile's Q rows land under this tile's MFMAs / softmax
         }
-        unsigned inside = 0;  // bit k set <=> the token lies in box k (region_flags() with the boxes in registers)
-        {
-            const int yi = qidx / p.mask_w, xi = qidx - yi * p.mask_w;
-            const float x = linspace01(xi, p.mask_w, p.step_x), y = linspace01(yi, p.mask_h, p.step_y);
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                inside |= (unsigned)((x >= box[k][0]) & (x <= box[k][2]) & (y >= box[k][1]) & (y <= box[k][3])) << k;
-        }
-        // 96-bit "attendable IP key" set of this query row: dummy keys [0, n_dummy) iff the token lies in NO box,
-        // character k's keys [n_dummy + k*tpi, +tpi) iff it lies in box k  (reference :155-163)
-        unsigned open_ip[3] = {0u, 0u, 0u};
-        {
-            auto set_range = [&](int lo, int hi) {  // bits [lo, hi) of the 96-bit set
-#pragma unroll
-                for (int w = 0; w < 3; ++w) {
-                    const int a = max(lo - 32 * w, 0), b = min(hi - 32 * w, 32);
-                    if (b > a) open_ip[w] |= (b - a == 32 ? 0xffffffffu : ((1u << (b - a)) - 1u)) << a;
-                }
-            };
-            if (inside == 0) set_range(0, p.n_dummy);
-            for (int k = 0; k < p.max_ips; ++k)
-                if ((inside >> k) & 1u) set_range(p.n_dummy + k * p.tok_per_ip, p.n_dummy + (k + 1) * p.tok_per_ip);
-        }
+        unsigned open_ip[3];   // the row's attendable IP keys
+        bool act_ip[3];        // the wave's active 32-key blocks of the IP panel
+        ip_open_set(p, box, qidx, open_ip, act_ip);
 
         f32x16 ot[2];
 #pragma unroll
@@ -503,15 +535,6 @@ __global__ __launch_bounds__(NW * 64, 2) void ip_attn_kernel(const IPAttnParams 
 #pragma unroll
             for (int r = 0; r < 16; ++r) ot[d][r] = 0.f;
 
-        // A masked key's probability is exactly 0 (exp(-10000 + ...) underflows in fp32 as it does in the reference's
-        // fp16), so a 32-key block of the IP panel in which NO query row of this wave has an attendable key contributes
-        // nothing and is skipped whole (wave-uniform): the unconditional half of the CFG batch only ever attends the
-        // dummy tokens, a panel with two characters never touches the fourth character's block.  Every row keeps at
-        // least one attendable key in an active block as long as dummy tokens exist (no box -> dummies).
-        bool act_ip[3];
-#pragma unroll
-        for (int kb = 0; kb < 3; ++kb)
-            act_ip[kb] = p.n_dummy == 0 || __builtin_amdgcn_ballot_w64(open_ip[kb] != 0u) != 0;
         // Round 6: every LDS fragment of a phase is REQUESTED before the phase's first MFMA.  Left to the compiler the tile loop was
         // a chain of {ds_read, s_waitcnt lgkmcnt(0), v_mfma} triples - the registers of one fragment reused for the next - i.e. ~60
         // exposed LDS round trips per query tile with two waves per SIMD to hide them (ISA of the round-5 kernel; PMC: 47 % of the
@@ -540,7 +563,7 @@ __global__ __launch_bounds__(NW * 64, 2) void ip_attn_kernel(const IPAttnParams 
             constexpr int part = decltype(partc)::value;
 #pragma unroll
             for (int kb = 0; kb < 3; ++kb) {
-                if (kb == 0) load_k(partc, IPC<2>{}, IPC<3>{});   // the last block's fragments land under the first two blocks' MFMAs
+                if (kb == 0) load_k(partc, IC<2>{}, IC<3>{});   // the last block's fragments land under the first two blocks' MFMAs
                 if (part && !act_ip[kb]) continue;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) st[kb][r] = 0.f;
@@ -623,38 +646,22 @@ __global__ __launch_bounds__(NW * 64, 2) void ip_attn_kernel(const IPAttnParams 
             }
             mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
             f32x2 psum2 = {0.f, 0.f};
-            {
-                const f32x2 l2 = {LOG2E, LOG2E}, m2 = {-mloc * LOG2E, -mloc * LOG2E};
+            const f32x2 l2 = {LOG2E, LOG2E}, m2 = {-mloc * LOG2E, -mloc * LOG2E};
 #pragma unroll
-                for (int kb = 0; kb < 3; ++kb) {
-                    if (part && !act_ip[kb]) continue;
-#pragma unroll
-                    for (int r = 0; r < ((T16 && kb == 2) ? 8 : 16); r += 2) {
-                        f32x2 v = {st[kb][r], st[kb][r + 1]};
-                        v = __builtin_elementwise_fma(v, l2, m2);
-                        const f32x2 e = {fast_exp2(v[0]), fast_exp2(v[1])};
-                        st[kb][r] = e[0];
-                        st[kb][r + 1] = e[1];
-                        psum2 += e;
-                    }
-                }
+            for (int kb = 0; kb < 3; ++kb) {
+                if (part && !act_ip[kb]) continue;
+                if (T16 && kb == 2) exp2_sum_block<8>(st[kb], l2, m2, psum2);
+                else exp2_sum_block<16>(st[kb], l2, m2, psum2);
             }
             float psum = psum2[0] + psum2[1];
             psum += __shfl_xor(psum, 32, 64);
             const float w = (part ? ip_scale : 1.0f) / psum;
-            {
-                const f32x2 w2 = {w, w};
+            const f32x2 w2 = {w, w};
 #pragma unroll
-                for (int kb = 0; kb < 3; ++kb) {
-                    if (part && !act_ip[kb]) continue;
-#pragma unroll
-                    for (int r = 0; r < ((T16 && kb == 2) ? 8 : 16); r += 2) {
-                        f32x2 v = {st[kb][r], st[kb][r + 1]};
-                        v *= w2;
-                        st[kb][r] = v[0];
-                        st[kb][r + 1] = v[1];
-                    }
-                }
+            for (int kb = 0; kb < 3; ++kb) {
+                if (part && !act_ip[kb]) continue;
+                if (T16 && kb == 2) scale_block<8>(st[kb], w2);
+                else scale_block<16>(st[kb], w2);
             }
         };
         // O^T += V^T P^T
@@ -663,7 +670,7 @@ __global__ __launch_bounds__(NW * 64, 2) void ip_attn_kernel(const IPAttnParams 
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int kb = 0; kb < 3; ++kb) {
-                if (kb == 0) load_v(partc, IPC<(RING ? 0 : 1)>{}, IPC<3>{});   // land under the first block's four MFMAs
+                if (kb == 0) load_v(partc, IC<(RING ? 0 : 1)>{}, IC<3>{});   // land under the first block's four MFMAs
                 if (part && !act_ip[kb]) continue;
 #pragma unroll
                 for (int hb = 0; hb < ((T16 && kb == 2) ? 1 : 2); ++hb) {
@@ -673,14 +680,14 @@ __global__ __launch_bounds__(NW * 64, 2) void ip_attn_kernel(const IPAttnParams 
                 }
             }
         };
-        load_k(partc, IPC<0>{}, IPC<2>{});
+        load_k(partc, IC<0>{}, IC<2>{});
         qk(partc);
-        load_v(partc, IPC<0>{}, IPC<(RING ? 0 : 1)>{});   // (more of them ahead of the softmax spills: 244 registers as it is; the ring variant has none to spare)
+        load_v(partc, IC<0>{}, IC<(RING ? 0 : 1)>{});   // (round 6: more of them ahead of the softmax spilled; not re-tried at today's 193 - 212 registers)
         softmax(partc);
         pv(partc);
         };
-        run_part(IPC<0>{});
-        run_part(IPC<1>{});
+        run_part(IC<0>{});
+        run_part(IC<1>{});
         if constexpr (RING) {
             // O^T -> the tile's own (consumed) Q slot, rows of 128 bytes with the same chunk swizzle, -> whole rows out
             char* ep = ring + (it % 3) * IP_SLOT;
@@ -702,46 +709,11 @@ __global__ __launch_bounds__(NW * 64, 2) void ip_attn_kernel(const IPAttnParams 
                 // store instructions per tile and wave, and a store whose lanes are all masked off is branched around
                 *reinterpret_cast<h8*>(p.o + ((long)b * p.N + q0 + row) * p.ldo + h * 64 + ch * 8) = v;
             }
-        } else if constexpr (IP_DIRECT_STORE == 0) {   // build-time A/B: eight 8-byte stores per row (rounds 1-5)
-            if (q0 + l31 < p.N) {
-                half_t* op = p.o + ((long)b * p.N + q0 + l31) * p.ldo + h * 64;
-#pragma unroll
-                for (int db = 0; db < 2; ++db)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        h4 o;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) o[e] = (half_t)ot[db][4 * g + e];
-                        *reinterpret_cast<h4*>(op + db * 32 + 8 * g + 4 * lhi) = o;
-                    }
-            }
         } else {
-            // A lane holds columns 8g + 4 lhi + {0..3} of its query row; its partner lane ^ 32 the other four of every group of
-            // eight.  One v_permlane32_swap per dword and group pair leaves the lower lane with columns 16j .. 16j+7 and the upper one
-            // with 16j+8 .. 16j+15: 16-byte stores, four per wave and 32-dim block instead of eight 8-byte ones (the hand-over of
-            // gemm_pp_kernel's GEGLU epilogue, cdna_hip_programming.md T21).  The swaps run on every lane (rows past N included);
-            // only the stores are masked.
+            // 16-byte rows (ds_attention.h; eight 8-byte stores per row until round 5: profiles/r06_ipattn_forward_ab_b*.txt); the
+            // row address is clamped, only the stores are masked
             half_t* op = p.o + ((long)b * p.N + min(q0 + l31, p.N - 1)) * p.ldo + h * 64 + lhi * 8;
-            const bool row_ok = q0 + l31 < p.N;
-#pragma unroll
-            for (int db = 0; db < 2; ++db) {
-                unsigned og[4][2];
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    h4 o;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = (half_t)ot[db][4 * g + e];
-                    const u32x2_t t = __builtin_bit_cast(u32x2_t, o);
-                    og[g][0] = t[0], og[g][1] = t[1];
-                }
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(og[2 * j][0]), "+v"(og[2 * j + 1][0]));
-                    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(og[2 * j][1]), "+v"(og[2 * j + 1][1]));
-                    const u32x4_t v = {og[2 * j][0], og[2 * j][1], og[2 * j + 1][0], og[2 * j + 1][1]};
-                    if (row_ok) *reinterpret_cast<u32x4_t*>(op + db * 32 + j * 16) = v;
-                }
-            }
+            store_rows16<false>(op, q0 + l31 < p.N, ot);
         }
     }
 }
@@ -777,21 +749,10 @@ __global__ __launch_bounds__(NW * 64, 2) void ip_attn_long_kernel(const IPAttnLo
     const int b = blockIdx.y / p.heads, h = blockIdx.y % p.heads;
 
     h8 qn[4];
-    auto load_q = [&](int it) {
-        const int qrow = min((int)(blockIdx.x * qt + it) * ROWS + wave * 32 + l31, p.N - 1);
-        const half_t* qp = p.q + ((long)b * p.N + qrow) * p.ldq + h * 64 + lhi * 8;
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) qn[kk] = *reinterpret_cast<const h8*>(qp + kk * 16);
-    };
+    auto load_q = [&](int it) { ip_load_q<ROWS>(p, b, h, (int)(blockIdx.x * qt + it), wave, l31, lhi, qn); };
     load_q(0);
-    float bv[4] = {2.f, 2.f, -1.f, -1.f};
-    {
-        const float* bbox_b = p.bbox + (long)b * p.max_ips * 4;
-        if (lane < p.max_ips) {
-#pragma unroll
-            for (int c4 = 0; c4 < 4; ++c4) bv[c4] = bbox_b[4 * lane + c4];
-        }
-    }
+    float bv[4];
+    ip_request_box(p, b, lane, bv);
     // ---- stage the T + 1 panels once: 768 sixteen-byte pieces of K and of V^T per panel, whole panels (rows >= Lt included:
     // the caller's panels are [B, 96 T, C] / [B, C, 96 T], so every piece lies inside them)
     for (int j = 0; j <= T; ++j) {
@@ -800,41 +761,25 @@ __global__ __launch_bounds__(NW * 64, 2) void ip_attn_long_kernel(const IPAttnLo
         const long ldk = ipp ? p.ldk : pl.ldkt;
         const long ldv = ipp ? LP : (long)LP * T;
         const half_t* vp = ipp ? p.vti + (long)b * p.sv + (long)(h * 64) * ldv : p.vtt + (long)b * pl.svt + (long)(h * 64) * ldv + j * LP;
-        char* const dK = sK + j * IPL_KPANEL;
-        char* const dV = sV + j * IPL_VPANEL;
-        constexpr int ITER = (LP * 8 + NW * 64 - 1) / (NW * 64);
-        h8 rk[ITER], rv[ITER];
+        using Stage = IPStage<NW>;
+        h8 rk[Stage::ITER], rv[Stage::ITER];
 #pragma unroll
-        for (int i = 0; i < ITER; ++i) {
-            const int id = min(tid + i * NW * 64, LP * 8 - 1);
-            const int row = id >> 3, c = id & 7;
-            rk[i] = *reinterpret_cast<const h8*>(kp + (long)row * ldk + c * 8);
-            const int vrow = id / 12, vc = id - vrow * 12;
-            rv[i] = *reinterpret_cast<const h8*>(vp + (long)vrow * ldv + vc * 8);
+        for (int i = 0; i < Stage::ITER; ++i) {
+            rk[i] = Stage::request_k(kp, ldk, tid, i);
+            rv[i] = Stage::request_v(vp, ldv, tid, i);
         }
 #pragma unroll
-        for (int i = 0; i < ITER; ++i) {
-            const int id = tid + i * NW * 64;
-            if (id >= LP * 8) continue;
-            const int row = id >> 3, c = id & 7;
-            *reinterpret_cast<h8*>(&dK[row * 128 + swz(row, c)]) = rk[i];
-            const int vrow = id / 12, vc = id - vrow * 12;
-            const h8 a = rv[i];
-            h4 lo, hi;
-            lo[0] = a[0]; lo[1] = a[1]; lo[2] = a[2]; lo[3] = a[3];
-            hi[0] = a[4]; hi[1] = a[5]; hi[2] = a[6]; hi[3] = a[7];
-            *reinterpret_cast<h4*>(&dV[vrow * VSTR + vc * 16]) = lo;
-            *reinterpret_cast<h4*>(&dV[vrow * VSTR + vc * 16 + 8]) = hi;
+        for (int i = 0; i < Stage::ITER; ++i) {
+            if (!Stage::in_panel(tid, i)) continue;
+            Stage::write_k(sK + j * IPL_KPANEL, tid, i, rk[i]);
+            Stage::write_v(sV + j * IPL_VPANEL, tid, i, rv[i]);
         }
     }
     __syncthreads();   // the only barrier: behind it every wave walks its own query rows
 
     float box[8][4];
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-#pragma unroll
-        for (int c4 = 0; c4 < 4; ++c4) box[k][c4] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bv[c4]), k));
-    const float ip_scale = p.ip_scale_ptr ? p.ip_scale_ptr[b * p.ip_scale_rows] : p.ip_scale;
+    ip_broadcast_boxes(bv, box);
+    const float ip_scale = ip_read_scale(p, b);
 
     // Fragment addresses relative to a panel: K row 32 kb + l31 keeps the swizzle of row l31 ((row >> 1) & 7 has period 16), so a
     // key block is an immediate offset; V^T row 32 db + l31, keys from 4 lhi on, the half block an immediate as well
@@ -923,17 +868,7 @@ __global__ __launch_bounds__(NW * 64, 2) void ip_attn_long_kernel(const IPAttnLo
             f32x2 psum2 = {0.f, 0.f};
             const f32x2 l2 = {LOG2E, LOG2E}, m2 = {-m_new * LOG2E, -m_new * LOG2E};
 #pragma unroll
-            for (int kb = 0; kb < 3; ++kb) {
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    f32x2 v = {st[kb][r], st[kb][r + 1]};
-                    v = __builtin_elementwise_fma(v, l2, m2);
-                    const f32x2 e = {fast_exp2(v[0]), fast_exp2(v[1])};
-                    st[kb][r] = e[0];
-                    st[kb][r + 1] = e[1];
-                    psum2 += e;
-                }
-            }
+            for (int kb = 0; kb < 3; ++kb) exp2_sum_block<16>(st[kb], l2, m2, psum2);
             l_part = fmaf(l_part, alpha, psum2[0] + psum2[1]);
             if (t > 0) {
 #pragma unroll
@@ -956,32 +891,10 @@ __global__ __launch_bounds__(NW * 64, 2) void ip_attn_long_kernel(const IPAttnLo
                 for (int r = 0; r < 16; ++r) ot[d][r] *= inv;
         }
 
-        // ---- IP: ip_attn_kernel's part 1 (region test, 96-bit open set, active blocks, biased softmax weighted by ip_scale)
-        unsigned inside = 0;
-        {
-            const int yi = qidx / p.mask_w, xi = qidx - yi * p.mask_w;
-            const float x = linspace01(xi, p.mask_w, p.step_x), y = linspace01(yi, p.mask_h, p.step_y);
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                inside |= (unsigned)((x >= box[k][0]) & (x <= box[k][2]) & (y >= box[k][1]) & (y <= box[k][3])) << k;
-        }
-        unsigned open_ip[3] = {0u, 0u, 0u};
-        {
-            auto set_range = [&](int lo, int hi) {
-#pragma unroll
-                for (int w = 0; w < 3; ++w) {
-                    const int a = max(lo - 32 * w, 0), e = min(hi - 32 * w, 32);
-                    if (e > a) open_ip[w] |= (e - a == 32 ? 0xffffffffu : ((1u << (e - a)) - 1u)) << a;
-                }
-            };
-            if (inside == 0) set_range(0, p.n_dummy);
-            for (int k = 0; k < p.max_ips; ++k)
-                if ((inside >> k) & 1u) set_range(p.n_dummy + k * p.tok_per_ip, p.n_dummy + (k + 1) * p.tok_per_ip);
-        }
+        // ---- IP: the row's open key set and the wave's active blocks, then the per-key biased softmax weighted by ip_scale
+        unsigned open_ip[3];
         bool act_ip[3];
-#pragma unroll
-        for (int kb = 0; kb < 3; ++kb)
-            act_ip[kb] = p.n_dummy == 0 || __builtin_amdgcn_ballot_w64(open_ip[kb] != 0u) != 0;
+        ip_open_set(p, box, qidx, open_ip, act_ip);
         {
             const char* sKp = sK + T * IPL_KPANEL;
             const char* sVp = sV + T * IPL_VPANEL;
@@ -1012,18 +925,8 @@ __global__ __launch_bounds__(NW * 64, 2) void ip_attn_long_kernel(const IPAttnLo
             f32x2 psum2 = {0.f, 0.f};
             const f32x2 l2 = {LOG2E, LOG2E}, m2 = {-mloc * LOG2E, -mloc * LOG2E};
 #pragma unroll
-            for (int kb = 0; kb < 3; ++kb) {
-                if (!act_ip[kb]) continue;
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    f32x2 v = {st[kb][r], st[kb][r + 1]};
-                    v = __builtin_elementwise_fma(v, l2, m2);
-                    const f32x2 e = {fast_exp2(v[0]), fast_exp2(v[1])};
-                    st[kb][r] = e[0];
-                    st[kb][r + 1] = e[1];
-                    psum2 += e;
-                }
-            }
+            for (int kb = 0; kb < 3; ++kb)
+                if (act_ip[kb]) exp2_sum_block<16>(st[kb], l2, m2, psum2);
             float psum = psum2[0] + psum2[1];
             psum += __shfl_xor(psum, 32, 64);
             const float w = ip_scale / psum;
@@ -1031,40 +934,15 @@ __global__ __launch_bounds__(NW * 64, 2) void ip_attn_long_kernel(const IPAttnLo
 #pragma unroll
             for (int kb = 0; kb < 3; ++kb) {
                 if (!act_ip[kb]) continue;
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    f32x2 v = {st[kb][r], st[kb][r + 1]};
-                    v *= w2;
-                    st[kb][r] = v[0];
-                    st[kb][r + 1] = v[1];
-                }
+                scale_block<16>(st[kb], w2);
 #pragma unroll
                 for (int hb = 0; hb < 2; ++hb) pv_half(sVp, st[kb], kb, hb);
             }
         }
 
-        // ---- store: ip_attn_kernel's 16-byte rows (one v_permlane32_swap per dword and group pair; only the stores are masked)
+        // ---- store: 16-byte rows (ds_attention.h); the row address is clamped, only the stores are masked
         half_t* op = p.o + ((long)b * p.N + min(q0 + l31, p.N - 1)) * p.ldo + h * 64 + lhi * 8;
-        const bool row_ok = q0 + l31 < p.N;
-#pragma unroll
-        for (int db = 0; db < 2; ++db) {
-            unsigned og[4][2];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                h4 o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = (half_t)ot[db][4 * g + e];
-                const u32x2_t t2 = __builtin_bit_cast(u32x2_t, o);
-                og[g][0] = t2[0], og[g][1] = t2[1];
-            }
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(og[2 * j][0]), "+v"(og[2 * j + 1][0]));
-                asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(og[2 * j][1]), "+v"(og[2 * j + 1][1]));
-                const u32x4_t v = {og[2 * j][0], og[2 * j][1], og[2 * j + 1][0], og[2 * j + 1][1]};
-                if (row_ok) *reinterpret_cast<u32x4_t*>(op + db * 32 + j * 16) = v;
-            }
-        }
+        store_rows16<false>(op, q0 + l31 < p.N, ot);
     }
 }
 
@@ -1161,37 +1039,49 @@ int ds_launch_self_attn(const SelfAttnParams& p, hipStream_t stream) {
     return 0;
 }
 
-int ds_launch_ip_attn(const IPAttnParams& p0, hipStream_t stream) {
-    IPAttnParams p = p0;
+// What both fused cross-attention launchers fill in and require of the IP side and the problem: the dense-panel stride defaults,
+// the two linspace steps of the region test, and the checks whose text differs only in the launcher's name.  (Each launcher
+// keeps the checks of its own text side and of its panel strides, whose wording differs.)
+static int ip_attn_check(const char* who, IPAttnParams& p) {
     if (p.ldk == 0) p.ldk = p.C;
     if (p.sk == 0) p.sk = (long)LP * p.C;
     if (p.sv == 0) p.sv = (long)LP * p.C;
     p.step_x = linspace_step(p.mask_w), p.step_y = linspace_step(p.mask_h);
-    DS_REQUIRE(p.ldk % 8 == 0 && p.sk % 8 == 0 && p.sv % 8 == 0, "ip_attn: key/value panel strides must be multiples of 8");
-    DS_REQUIRE(p.B > 0 && p.heads > 0 && p.N > 0, "ip_attn: empty problem");
+    DS_REQUIRE(p.B > 0 && p.heads > 0 && p.N > 0, "%s: empty problem", who);
+    DS_REQUIRE(p.C == p.heads * 64, "%s: head_dim must be 64 (C=%d heads=%d)", who, p.C, p.heads);
+    DS_REQUIRE(p.max_ips >= 1 && p.max_ips <= 8 && p.tok_per_ip > 0, "%s: bad ip token layout", who);
+    DS_REQUIRE(p.n_dummy + p.max_ips * p.tok_per_ip == p.Li, "%s: Li (%d) != n_dummy + max_ips*tok_per_ip", who, p.Li);
+    DS_REQUIRE(p.mask_h * p.mask_w == p.N, "%s: mask grid %dx%d != N %d", who, p.mask_h, p.mask_w, p.N);
+    DS_REQUIRE(p.ip_scale_rows == 0 || (p.ip_scale_rows == 1 && p.ip_scale_ptr),
+               "%s: ip_scale_rows must be 0, or 1 with a device vector of B scales", who);
+    DS_REQUIRE(p.ldq % 8 == 0 && p.ldo % 8 == 0, "%s: ldq (%ld) and ldo (%ld) must be multiples of 8 (16-byte row pieces)", who, (long)p.ldq, (long)p.ldo);
+    return 0;
+}
+
+// Query tiles per block: doubled (up to 8) while the grid keeps g_ip_min_blocks blocks - several tiles per block amortise the
+// K / V panel staging once there are plenty of blocks.  cap_by_tiles (the ring): never more tiles per block than there are.
+static int ip_tiles_per_block(int tiles, long bh, bool cap_by_tiles) {
+    int qt = 1;
+    while (qt < 8 && (!cap_by_tiles || qt * 2 <= tiles) && (long)((tiles + 2 * qt - 1) / (2 * qt)) * bh >= g_ip_min_blocks) qt *= 2;
+    return qt;
+}
+
+int ds_launch_ip_attn(const IPAttnParams& p0, hipStream_t stream) {
+    IPAttnParams p = p0;
     DS_REQUIRE(p.LP == LP, "ip_attn: key panels must be padded to %d rows (got %d)", LP, p.LP);
     DS_REQUIRE(p.Lt > 0 && p.Lt <= LP && p.Li > 0 && p.Li <= LP, "ip_attn: Lt=%d Li=%d exceed %d", p.Lt, p.Li, LP);
-    DS_REQUIRE(p.C == p.heads * 64, "ip_attn: head_dim must be 64 (C=%d heads=%d)", p.C, p.heads);
-    DS_REQUIRE(p.max_ips >= 1 && p.max_ips <= 8 && p.tok_per_ip > 0, "ip_attn: bad ip token layout");
-    DS_REQUIRE(p.n_dummy + p.max_ips * p.tok_per_ip == p.Li, "ip_attn: Li (%d) != n_dummy + max_ips*tok_per_ip", p.Li);
-    DS_REQUIRE(p.mask_h * p.mask_w == p.N, "ip_attn: mask grid %dx%d != N %d", p.mask_h, p.mask_w, p.N);
-    DS_REQUIRE(p.ip_scale_rows == 0 || (p.ip_scale_rows == 1 && p.ip_scale_ptr),
-               "ip_attn: ip_scale_rows must be 0, or 1 with a device vector of B scales");
-    DS_REQUIRE(p.ldq % 8 == 0 && p.ldo % 8 == 0, "ip_attn: ldq (%ld) and ldo (%ld) must be multiples of 8 (16-byte row pieces)", (long)p.ldq, (long)p.ldo);
-    // walk several query tiles per block once there are plenty of blocks (amortises the K/V panel staging)
+    if (int rc = ip_attn_check("ip_attn", p)) return rc;
+    DS_REQUIRE(p.ldk % 8 == 0 && p.sk % 8 == 0 && p.sv % 8 == 0, "ip_attn: key/value panel strides must be multiples of 8");
     // The 8-wave LDS-DMA ring variant, 256 query rows per block and tile: g_ip_variant 2 only (see below).
     {
         const int tiles8 = (p.N + 255) / 256;
-        int qt8 = 1;
-        while (qt8 < 8 && qt8 * 2 <= tiles8 && (long)((tiles8 + 2 * qt8 - 1) / (2 * qt8)) * p.B * p.heads >= g_ip_min_blocks) qt8 *= 2;
-        const long blocks8 = (long)((tiles8 + qt8 - 1) / qt8) * p.B * p.heads;
+        const int qt8 = ip_tiles_per_block(tiles8, (long)p.B * p.heads, true);
         // Measured (profiles/r04_ipattn_ring_ab.txt): back to back on its own, B = 64 N = 1024 163 -> 154 us, N = 4096 269 -> 246 us (four
         // and eight tiles per block; with two tiles per block the ring has nothing to run ahead of and the larger block loses
         // 15-20 %) - but INSIDE the UNet forward, where Q has just been written by the to_q GEMM, the same launches take 0.35 ms
         // per forward LONGER than the register-staged kernel (in-situ A/B, three interleaved rounds; the rocprofv3 trace of a
         // whole call agrees: 214 vs 188 us per launch).  The kernel is VALU-bound, not bound by its loads and stores: the
         // variant is kept for A/B (ip_attn_variant 2, bit-identical) and never chosen automatically.
-        (void)blocks8;
         if (p.N % 256 == 0 && p.ldo % 8 == 0 && p.ldq % 8 == 0 && g_ip_variant == 2) {
             const size_t lds = IP_PANEL_BYTES + 8 * 3 * IP_SLOT;
             auto kern = ip_attn_kernel<8, true>;
@@ -1204,8 +1094,7 @@ int ds_launch_ip_attn(const IPAttnParams& p0, hipStream_t stream) {
         }
     }
     const int tiles = (p.N + 127) / 128;
-    int qt = 1;
-    while (qt < 8 && (long)((tiles + 2 * qt - 1) / (2 * qt)) * p.B * p.heads >= g_ip_min_blocks) qt *= 2;
+    const int qt = ip_tiles_per_block(tiles, (long)p.B * p.heads, false);
     dim3 grid((tiles + qt - 1) / qt, p.B * p.heads);
     // keys 80..95 are padding for every row of both panels (the model's 77 / 80 keys): the T16 instantiation (ip_attn_variant 3: off, A/B)
     const bool t16 = g_ip_variant != 3 && p.Lt > 64 && p.Lt <= 80 && p.Li > 64 && p.Li <= 80;
@@ -1221,29 +1110,17 @@ int ds_launch_ip_attn_long(const IPAttnLongParams& pl0, hipStream_t stream) {
     DS_REQUIRE(p.Lt > 0 && p.Lt <= 4 * LP, "ip_attn_long: Lt=%d: 1 .. %d text keys (four panels of %d) are supported", p.Lt, 4 * LP, LP);
     DS_REQUIRE(pl.T >= 1 && pl.T <= 4 && p.Lt <= pl.T * LP, "ip_attn_long: %d text panels of %d rows do not hold Lt=%d (at most 4 panels)", pl.T, LP, p.Lt);
     DS_REQUIRE(p.Lt > (pl.T - 1) * LP, "ip_attn_long: Lt=%d leaves the last of %d text panels empty", p.Lt, pl.T);
-    if (p.ldk == 0) p.ldk = p.C;
-    if (p.sk == 0) p.sk = (long)LP * p.C;
-    if (p.sv == 0) p.sv = (long)LP * p.C;
+    DS_REQUIRE(p.Li > 0 && p.Li <= LP, "ip_attn_long: Li=%d exceeds %d", p.Li, LP);
+    if (int rc = ip_attn_check("ip_attn_long", p)) return rc;
     if (pl.ldkt == 0) pl.ldkt = p.C;
     if (pl.skt == 0) pl.skt = (long)LP * pl.T * p.C;
     if (pl.svt == 0) pl.svt = (long)LP * pl.T * p.C;
-    p.step_x = linspace_step(p.mask_w), p.step_y = linspace_step(p.mask_h);
     DS_REQUIRE(p.ldk % 8 == 0 && p.sk % 8 == 0 && p.sv % 8 == 0 && pl.ldkt % 8 == 0 && pl.skt % 8 == 0 && pl.svt % 8 == 0,
                "ip_attn_long: key/value panel strides must be multiples of 8 (ldk=%ld sk=%ld sv=%ld, text: ldk=%ld sk=%ld sv=%ld)",
                p.ldk, p.sk, p.sv, pl.ldkt, pl.skt, pl.svt);
-    DS_REQUIRE(p.B > 0 && p.heads > 0 && p.N > 0, "ip_attn_long: empty problem");
-    DS_REQUIRE(p.Li > 0 && p.Li <= LP, "ip_attn_long: Li=%d exceeds %d", p.Li, LP);
-    DS_REQUIRE(p.C == p.heads * 64, "ip_attn_long: head_dim must be 64 (C=%d heads=%d)", p.C, p.heads);
-    DS_REQUIRE(p.max_ips >= 1 && p.max_ips <= 8 && p.tok_per_ip > 0, "ip_attn_long: bad ip token layout");
-    DS_REQUIRE(p.n_dummy + p.max_ips * p.tok_per_ip == p.Li, "ip_attn_long: Li (%d) != n_dummy + max_ips*tok_per_ip", p.Li);
-    DS_REQUIRE(p.mask_h * p.mask_w == p.N, "ip_attn_long: mask grid %dx%d != N %d", p.mask_h, p.mask_w, p.N);
-    DS_REQUIRE(p.ip_scale_rows == 0 || (p.ip_scale_rows == 1 && p.ip_scale_ptr),
-               "ip_attn_long: ip_scale_rows must be 0, or 1 with a device vector of B scales");
-    DS_REQUIRE(p.ldq % 8 == 0 && p.ldo % 8 == 0, "ip_attn_long: ldq (%ld) and ldo (%ld) must be multiples of 8 (16-byte row pieces)", (long)p.ldq, (long)p.ldo);
-    // 256 query rows per block and tile; several tiles per block once there are plenty of blocks (ip_attn's rule and knob)
+    // 256 query rows per block and tile
     const int tiles = (p.N + 255) / 256;
-    int qt = 1;
-    while (qt < 8 && (long)((tiles + 2 * qt - 1) / (2 * qt)) * p.B * p.heads >= g_ip_min_blocks) qt *= 2;
+    const int qt = ip_tiles_per_block(tiles, (long)p.B * p.heads, false);
     const size_t lds = (size_t)(pl.T + 1) * (IPL_KPANEL + IPL_VPANEL);
     auto kern = ip_attn_long_kernel<8>;
     static unsigned long long attr_devs = 0;

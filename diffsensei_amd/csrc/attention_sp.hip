@@ -25,21 +25,17 @@
 //     store-time shuffle.
 // Not bit-identical to self_attn_kernel (deferred rescale, pre-scaled Q): compared with the fp32 reference and the golden
 // fixture at the same tolerance (tests/test_gpu_ops.py).
-#include "ds_common.h"
+#include "ds_attention.h"
 #include "ds_kernels.h"
 
 namespace {
 
-constexpr float LOG2E = 1.4426950408889634f;
 constexpr int TILE_B = 8192;      // one 64 x 64 f16 tile
 constexpr int V_BASE = 3 * TILE_B;
 constexpr float LIM = 16384.0f;   // a lane's 32-key partial row sum above this re-centres the row (p < 2^14 always)
-constexpr float NEG_BIG = -1.0e30f;
 typedef __attribute__((address_space(3))) void lds_void;
 typedef const __attribute__((address_space(1))) void glb_void;
 typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2_sp __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4_sp __attribute__((ext_vector_type(4)));
 
 // Debug counter (ds_debug_counter("attn_sp_recentre")): how often the rare re-centring branch behind a step ran, per wave and
 // pair, since the last reset.  One atomic from one lane inside the rare branch - nothing in the steady state.  It exists so that
@@ -59,8 +55,6 @@ __device__ unsigned long long g_sp_recentre_count = 0;
 __device__ __forceinline__ int pi32(int i) {  // swap bits 2 and 3 of a 5-bit index
     return (i & 19) | ((i & 4) << 1) | ((i & 8) >> 1);
 }
-
-__device__ __forceinline__ float fexp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
 // max over both half-waves of a per-lane value (lanes l and l^32 hold the two halves of one query row's scores)
 __device__ __forceinline__ float cross_max(float x) {
@@ -219,7 +213,7 @@ __global__ __launch_bounds__(256, 2) void self_attn_sp_kernel(const SelfAttnPara
             for (int hb = 0; hb < 2; ++hb) {
 #pragma unroll
                 for (int e = 0; e < 8; e += 2) {
-                    const h2v pr = {(half_t)fexp2(S[kb][hb * 8 + e]), (half_t)fexp2(S[kb][hb * 8 + e + 1])};
+                    const h2v pr = {(half_t)fast_exp2(S[kb][hb * 8 + e]), (half_t)fast_exp2(S[kb][hb * 8 + e + 1])};
                     P[kb][hb][e] = pr[0];
                     P[kb][hb][e + 1] = pr[1];
                     sum[hb] = __builtin_amdgcn_fdot2(pr, h2v{(half_t)1.f, (half_t)1.f}, sum[hb], false);
@@ -259,7 +253,7 @@ __global__ __launch_bounds__(256, 2) void self_attn_sp_kernel(const SelfAttnPara
         qk(S, qb, kc_base);
         if (ragged && t == nt - 1) mask_ragged(S, t);
         const float delta = fmaxf(cross_max(tile_max(S)), 0.f);
-        const float alpha = fexp2(-delta);
+        const float alpha = fast_exp2(-delta);
         mref[qb] += delta;
         lsum[qb] *= alpha;
 #pragma unroll
@@ -317,7 +311,7 @@ __global__ __launch_bounds__(256, 2) void self_attn_sp_kernel(const SelfAttnPara
             if (g + 4 < 16) fr[g & 3] = frag(g + 4);
             {   // probabilities of score pair g of the current pair (S is consumed: its registers free up as the step proceeds)
                 const int kb = g >> 3, hb = (g >> 2) & 1, e = (g & 3) * 2;
-                const h2v pr = {(half_t)fexp2(Sc[kb][hb * 8 + e]), (half_t)fexp2(Sc[kb][hb * 8 + e + 1])};
+                const h2v pr = {(half_t)fast_exp2(Sc[kb][hb * 8 + e]), (half_t)fast_exp2(Sc[kb][hb * 8 + e + 1])};
                 Pc[kb][hb][e] = pr[0];
                 Pc[kb][hb][e + 1] = pr[1];
                 sum[g & 1] = __builtin_amdgcn_fdot2(pr, h2v{(half_t)1.f, (half_t)1.f}, sum[g & 1], false);
@@ -361,31 +355,9 @@ __global__ __launch_bounds__(256, 2) void self_attn_sp_kernel(const SelfAttnPara
         const float l = lsum[qb] + __shfl_xor(lsum[qb], 32, 64);
         const float inv = 1.0f / l;
         const int qrow = q0 + qb * 32 + l31;
-        // 16-byte stores (round 6, as in ip_attn_kernel where the store shape was measured: attention.hip): a lane holds columns
-        // 8g + 4 lhi + {0..3} of its query row, its partner lane ^ 32 the other four of every group of eight; one
-        // v_permlane32_swap per dword and group pair leaves the lower lane with columns 16j .. 16j+7, the upper one with 16j+8 ..
-        // 16j+15.  The swaps run on every lane (rows past Nq included); only the stores are masked.
+        // 16-byte rows, O / l on the way (ds_attention.h); the row address is clamped, only the stores are masked
         half_t* op = p.o + (long)b * p.so + (long)min(qrow, p.Nq - 1) * p.ldo + h * 64 + lhi * 8;
-        const bool row_ok = qrow < p.Nq;
-#pragma unroll
-        for (int db = 0; db < 2; ++db) {
-            unsigned og[4][2];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                h4 o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = (half_t)(O[qb][db][4 * g + e] * inv);
-                const u32x2_sp t2 = __builtin_bit_cast(u32x2_sp, o);
-                og[g][0] = t2[0], og[g][1] = t2[1];
-            }
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(og[2 * j][0]), "+v"(og[2 * j + 1][0]));
-                asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(og[2 * j][1]), "+v"(og[2 * j + 1][1]));
-                const u32x4_sp v = {og[2 * j][0], og[2 * j][1], og[2 * j + 1][0], og[2 * j + 1][1]};
-                if (row_ok) *reinterpret_cast<u32x4_sp*>(op + db * 32 + j * 16) = v;
-            }
-        }
+        store_rows16<true>(op, qrow < p.Nq, O[qb], inv);
     }
 }
 

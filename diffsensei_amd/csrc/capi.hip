@@ -419,46 +419,42 @@ int ds_self_attn_f16(const void* q, int64_t ldq, int64_t sq, const void* k, int6
     return ds_launch_self_attn(p, S(stream));
 }
 
-int ds_masked_ip_attn_f16(const void* q, int64_t ldq, const void* kt, const void* vtt, const void* ki,
-                          const void* vti, const float* bbox, void* o, int64_t ldo, int B, int heads, int N, int Lt,
-                          int Li, int n_dummy, int tok_per_ip, int max_ips, int mask_h, int mask_w, float qk_scale,
-                          float ip_scale, const float* ip_scale_dev, int64_t ldk, int64_t sk, int64_t sv,
-                          void* stream) {
+// THE filling of an IPAttnParams: the four entry points below and the DS_OP_IP_ATTN case.  ip_scale_rows 1: ip_scale_dev is [B].
+static IPAttnParams ip_attn_params(const void* q, int64_t ldq, const void* kt, const void* vtt, const void* ki, const void* vti,
+                                   const float* bbox, void* o, int64_t ldo, int B, int heads, int N, int Lt, int Li, int n_dummy,
+                                   int tok_per_ip, int max_ips, int mask_h, int mask_w, float qk_scale, float ip_scale,
+                                   const float* ip_scale_dev, int ip_scale_rows, int64_t ldk, int64_t sk, int64_t sv) {
     IPAttnParams p;
     p.ldk = ldk; p.sk = sk; p.sv = sv;
     p.q = H(q); p.kt = H(kt); p.vtt = H(vtt); p.ki = H(ki); p.vti = H(vti); p.bbox = bbox; p.o = HM(o);
     p.ldq = ldq; p.ldo = ldo; p.B = B; p.heads = heads; p.N = N; p.C = heads * 64;
     p.Lt = Lt; p.Li = Li; p.LP = 96; p.n_dummy = n_dummy; p.tok_per_ip = tok_per_ip; p.max_ips = max_ips;
-    p.mask_h = mask_h; p.mask_w = mask_w; p.qk_scale = qk_scale; p.ip_scale = ip_scale; p.ip_scale_ptr = ip_scale_dev;
-    return ds_launch_ip_attn(p, S(stream));
+    p.mask_h = mask_h; p.mask_w = mask_w; p.qk_scale = qk_scale;
+    p.ip_scale = ip_scale; p.ip_scale_ptr = ip_scale_dev; p.ip_scale_rows = ip_scale_rows;
+    return p;
+}
+// the long-prompt form: the same, and the text panels' count and strides
+static IPAttnLongParams ip_attn_long_params(const IPAttnParams& a, int text_panels, int64_t ldkt, int64_t skt, int64_t svt) {
+    IPAttnLongParams pl;
+    pl.a = a; pl.T = text_panels; pl.ldkt = ldkt; pl.skt = skt; pl.svt = svt;
+    return pl;
+}
+
+int ds_masked_ip_attn_f16(const void* q, int64_t ldq, const void* kt, const void* vtt, const void* ki,
+                          const void* vti, const float* bbox, void* o, int64_t ldo, int B, int heads, int N, int Lt,
+                          int Li, int n_dummy, int tok_per_ip, int max_ips, int mask_h, int mask_w, float qk_scale,
+                          float ip_scale, const float* ip_scale_dev, int64_t ldk, int64_t sk, int64_t sv,
+                          void* stream) {
+    return ds_launch_ip_attn(ip_attn_params(q, ldq, kt, vtt, ki, vti, bbox, o, ldo, B, heads, N, Lt, Li, n_dummy, tok_per_ip, max_ips,
+                                            mask_h, mask_w, qk_scale, ip_scale, ip_scale_dev, 0, ldk, sk, sv), S(stream));
 }
 
 int ds_masked_ip_attn_rows_f16(const void* q, int64_t ldq, const void* kt, const void* vtt, const void* ki,
                                const void* vti, const float* bbox, void* o, int64_t ldo, int B, int heads, int N, int Lt,
                                int Li, int n_dummy, int tok_per_ip, int max_ips, int mask_h, int mask_w, float qk_scale,
                                const float* ip_scale_rows_dev, int64_t ldk, int64_t sk, int64_t sv, void* stream) {
-    IPAttnParams p;
-    p.ldk = ldk; p.sk = sk; p.sv = sv;
-    p.q = H(q); p.kt = H(kt); p.vtt = H(vtt); p.ki = H(ki); p.vti = H(vti); p.bbox = bbox; p.o = HM(o);
-    p.ldq = ldq; p.ldo = ldo; p.B = B; p.heads = heads; p.N = N; p.C = heads * 64;
-    p.Lt = Lt; p.Li = Li; p.LP = 96; p.n_dummy = n_dummy; p.tok_per_ip = tok_per_ip; p.max_ips = max_ips;
-    p.mask_h = mask_h; p.mask_w = mask_w; p.qk_scale = qk_scale; p.ip_scale_ptr = ip_scale_rows_dev; p.ip_scale_rows = 1;
-    return ds_launch_ip_attn(p, S(stream));
-}
-
-static IPAttnLongParams ip_attn_long_params(const void* q, int64_t ldq, const void* kt, const void* vtt, const void* ki, const void* vti,
-                                            const float* bbox, void* o, int64_t ldo, int B, int heads, int N, int Lt, int text_panels,
-                                            int Li, int n_dummy, int tok_per_ip, int max_ips, int mask_h, int mask_w, float qk_scale,
-                                            int64_t ldkt, int64_t skt, int64_t svt, int64_t ldk, int64_t sk, int64_t sv) {
-    IPAttnLongParams pl;
-    IPAttnParams& p = pl.a;
-    pl.ldkt = ldkt; pl.skt = skt; pl.svt = svt; pl.T = text_panels;
-    p.ldk = ldk; p.sk = sk; p.sv = sv;
-    p.q = H(q); p.kt = H(kt); p.vtt = H(vtt); p.ki = H(ki); p.vti = H(vti); p.bbox = bbox; p.o = HM(o);
-    p.ldq = ldq; p.ldo = ldo; p.B = B; p.heads = heads; p.N = N; p.C = heads * 64;
-    p.Lt = Lt; p.Li = Li; p.LP = 96; p.n_dummy = n_dummy; p.tok_per_ip = tok_per_ip; p.max_ips = max_ips;
-    p.mask_h = mask_h; p.mask_w = mask_w; p.qk_scale = qk_scale;
-    return pl;
+    return ds_launch_ip_attn(ip_attn_params(q, ldq, kt, vtt, ki, vti, bbox, o, ldo, B, heads, N, Lt, Li, n_dummy, tok_per_ip, max_ips,
+                                            mask_h, mask_w, qk_scale, 1.0f, ip_scale_rows_dev, 1, ldk, sk, sv), S(stream));
 }
 
 int ds_masked_ip_attn_long_f16(const void* q, int64_t ldq, const void* kt, const void* vtt, const void* ki, const void* vti,
@@ -466,10 +462,9 @@ int ds_masked_ip_attn_long_f16(const void* q, int64_t ldq, const void* kt, const
                                int n_dummy, int tok_per_ip, int max_ips, int mask_h, int mask_w, float qk_scale, float ip_scale,
                                const float* ip_scale_dev, int64_t ldkt, int64_t skt, int64_t svt, int64_t ldk, int64_t sk,
                                int64_t sv, void* stream) {
-    IPAttnLongParams pl = ip_attn_long_params(q, ldq, kt, vtt, ki, vti, bbox, o, ldo, B, heads, N, Lt, text_panels, Li, n_dummy,
-                                              tok_per_ip, max_ips, mask_h, mask_w, qk_scale, ldkt, skt, svt, ldk, sk, sv);
-    pl.a.ip_scale = ip_scale; pl.a.ip_scale_ptr = ip_scale_dev;
-    return ds_launch_ip_attn_long(pl, S(stream));
+    const IPAttnParams a = ip_attn_params(q, ldq, kt, vtt, ki, vti, bbox, o, ldo, B, heads, N, Lt, Li, n_dummy, tok_per_ip, max_ips,
+                                          mask_h, mask_w, qk_scale, ip_scale, ip_scale_dev, 0, ldk, sk, sv);
+    return ds_launch_ip_attn_long(ip_attn_long_params(a, text_panels, ldkt, skt, svt), S(stream));
 }
 
 int ds_masked_ip_attn_long_rows_f16(const void* q, int64_t ldq, const void* kt, const void* vtt, const void* ki, const void* vti,
@@ -477,10 +472,9 @@ int ds_masked_ip_attn_long_rows_f16(const void* q, int64_t ldq, const void* kt, 
                                     int Li, int n_dummy, int tok_per_ip, int max_ips, int mask_h, int mask_w, float qk_scale,
                                     const float* ip_scale_rows_dev, int64_t ldkt, int64_t skt, int64_t svt, int64_t ldk,
                                     int64_t sk, int64_t sv, void* stream) {
-    IPAttnLongParams pl = ip_attn_long_params(q, ldq, kt, vtt, ki, vti, bbox, o, ldo, B, heads, N, Lt, text_panels, Li, n_dummy,
-                                              tok_per_ip, max_ips, mask_h, mask_w, qk_scale, ldkt, skt, svt, ldk, sk, sv);
-    pl.a.ip_scale_ptr = ip_scale_rows_dev; pl.a.ip_scale_rows = 1;
-    return ds_launch_ip_attn_long(pl, S(stream));
+    const IPAttnParams a = ip_attn_params(q, ldq, kt, vtt, ki, vti, bbox, o, ldo, B, heads, N, Lt, Li, n_dummy, tok_per_ip, max_ips,
+                                          mask_h, mask_w, qk_scale, 1.0f, ip_scale_rows_dev, 1, ldk, sk, sv);
+    return ds_launch_ip_attn_long(ip_attn_long_params(a, text_panels, ldkt, skt, svt), S(stream));
 }
 
 int ds_ip_region_flags(const float* bbox, uint8_t* flags, int B, int N, int max_ips, int mask_h, int mask_w,
@@ -911,19 +905,11 @@ static int run_op(const ds_op& o, hipStream_t st) {
             return ds_launch_self_attn(a, st);
         }
         case DS_OP_IP_ATTN: {
-            IPAttnParams a;
-            a.q = H(p[0]); a.kt = H(p[1]); a.vtt = H(p[2]); a.ki = H(p[3]); a.vti = H(p[4]);
-            a.bbox = reinterpret_cast<const float*>(p[5]); a.o = HM(p[6]);
-            a.ip_scale_ptr = reinterpret_cast<const float*>(p[7]);
-            a.ldq = l[0]; a.ldo = l[1]; a.ldk = l[2]; a.sk = l[3]; a.sv = l[4];
-            a.B = i[0]; a.heads = i[1]; a.N = i[2]; a.C = i[1] * 64; a.Lt = i[3]; a.Li = i[4]; a.LP = 96;
-            a.n_dummy = i[5]; a.tok_per_ip = i[6]; a.max_ips = i[7]; a.mask_h = i[8]; a.mask_w = i[9];
-            a.qk_scale = o.f[0]; a.ip_scale = o.f[1]; a.ip_scale_rows = i[10];
-            if (i[11] > 1) {   // long prompt: i[11] text panels with the strides l[5..7] of their own
-                IPAttnLongParams pl;
-                pl.a = a; pl.T = i[11]; pl.ldkt = l[5]; pl.skt = l[6]; pl.svt = l[7];
-                return ds_launch_ip_attn_long(pl, st);
-            }
+            const IPAttnParams a = ip_attn_params(p[0], l[0], p[1], p[2], p[3], p[4], reinterpret_cast<const float*>(p[5]), p[6], l[1],
+                                                  i[0], i[1], i[2], i[3], i[4], i[5], i[6], i[7], i[8], i[9], o.f[0], o.f[1],
+                                                  reinterpret_cast<const float*>(p[7]), i[10], l[2], l[3], l[4]);
+            if (i[11] > 1)   // long prompt: i[11] text panels with the strides l[5..7] of their own
+                return ds_launch_ip_attn_long(ip_attn_long_params(a, i[11], l[5], l[6], l[7]), st);
             return ds_launch_ip_attn(a, st);
         }
         case DS_OP_CONV_IN:

@@ -175,6 +175,15 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// v_permlane32_swap_b32 vdst, src: lanes 32..63 of vdst <-> lanes 0..31 of src.  Inline asm: through the builtin hipcc has folded
+// uses of the second result away (attention_sp.hip, cross_max); the s_nop covers the VALU-write -> permlane-read hazard.
+// (gemm_pp_kernel's GEGLU epilogue and the attention kernels' row store, ds_attention.h `store_rows16`.)
+__device__ __forceinline__ void swap32(unsigned& vdst, unsigned& src) {
+    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(vdst), "+v"(src));
+}
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
 // XCD-aware bijective remap of a 1-D block id: the dispatcher places block b on XCD b % 8, so hand
 // each XCD one contiguous chunk of the logical tile order (neighbouring tiles share operand panels in
 // that XCD's L2).  Speed only — correctness never depends on it.

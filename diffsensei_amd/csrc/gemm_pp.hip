@@ -85,14 +85,6 @@ static_assert(EX_MAX >= 0 && EX_MAX <= 16, "PP_EX: no epilogue path leaves more 
 typedef __attribute__((address_space(3))) void lds_void;
 typedef const __attribute__((address_space(1))) void glb_void;
 
-// v_permlane32_swap_b32 vdst, src: lanes 32..63 of vdst <-> lanes 0..31 of src.  Inline asm: through the builtin hipcc has folded
-// uses of the second result away (attention_sp.hip, cross_max); the s_nop covers the VALU-write -> permlane-read hazard.
-__device__ __forceinline__ void swap32(unsigned& vdst, unsigned& src) {
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(vdst), "+v"(src));
-}
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 // PP_DIRECT_EPI (round 5): the branch-free GEGLU epilogue hands its 32 x 32 output pieces to memory WITHOUT the transposition
 // through LDS.  A lane holds tile row l31; its two half-wave partners (l, l + 32) hold columns 8g + {0..3} and 8g + {4..7} of every
 // group g, so one v_permlane32_swap per dword and group pair leaves the lower lane with columns 16j .. 16j+7 and the upper one
